@@ -10,6 +10,7 @@ all-gather of the sampled structures at the end of the timed region.
     python bench.py --gpus 1 --steps 100 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     ... bench.py --train [--gpus N]        BASELINE config 4 (training step, 128 patches per GPU, gradient all-reduce) instead
+    ... bench.py --dump-outputs DIR        + what the last timed step computed, as DIR/<name>.npy (same arguments: same inputs)
 
 Prints ONE JSON line on rank 0 (contract: task prompt section 4).
 """
@@ -25,7 +26,7 @@ sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
 
 import torch  # noqa: E402
 
-HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E: 8.0 TB/s spec
 
 
 def algorithmic_bytes_per_attention_launch(B, K, D, C):
@@ -150,7 +151,7 @@ def cpu_baseline(dims, sd, K, seed, budget_s=30.0):
 
 def gpu_clocks():
     """sclk / mclk / power / power cap of GPU 0 as rocm-smi reports them (a child process; None where the tool or a field is missing).
-    Read before and after the timed blocks so that a slow box can be told from a regression."""
+    Read before the warm-up and after the timed blocks so that a slow box can be told from a regression."""
     import shutil
     import subprocess
 
@@ -171,6 +172,37 @@ def gpu_clocks():
         if any(t in kl for t in ("sclk", "mclk", "fclk", "power", "performance level")):
             keep[k] = v
     return keep
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor as <out_dir>/<name>.npy (float64 stays float64, every other dtype becomes float32), so that two builds
+    can be compared output for output.  DUMP_LIMIT_BYTES in all at most: the arrays that fit are written whole, each of the others keeps an
+    equal share of the rest as a fixed, seeded sample of the indices of its leading dimension (sorted; of its flattened elements when one
+    leading row alone is over the share)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy()
+        arrs[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    share, left = None, DUMP_LIMIT_BYTES - 256 * len(arrs)  # (256 bytes per file for the .npy header)
+    sizes = sorted(a.nbytes for a in arrs.values())
+    for i, nb in enumerate(sizes):
+        if nb * (len(sizes) - i) > left:  # this array and every larger one get an equal share of what is left
+            share = left // (len(sizes) - i)
+            break
+        left -= nb
+    for k, a in arrs.items():
+        if share is not None and a.nbytes > share:
+            if a.nbytes // a.shape[0] > share:
+                a = a.reshape(-1)
+            keep = a.shape[0] * share // a.nbytes
+            a = a[np.sort(np.random.default_rng(0).permutation(a.shape[0])[:keep])]
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def train_bytes_per_patch(K, dims, dpair):
@@ -422,6 +454,11 @@ def train_bench(args, model, dims, rank, world, dist):
 
     elapsed = timed(True)
     had_dpair = batch["pair_context_emb"].grad is not None
+    if args.dump_outputs and rank == 0:  # the last step of the reported leg: its loss, the reduced parameter gradients (parameter order)
+        # and d pair_ctx - written now, before the contexts-constant leg below reuses the gradient buffers
+        grads = torch.cat([p.grad.reshape(-1) for p in model.parameters() if p.grad is not None])
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1), "param_grads": grads,
+                                         "pair_context_grad": batch["pair_context_emb"].grad})
     elapsed_const = timed(False)
     in_place = all(p.grad is None or any(f is not None and p.grad.untyped_storage().data_ptr() == f.untyped_storage().data_ptr()
                                          for f in model.gradient_buckets()) for p in model.denoiser.parameters())
@@ -464,9 +501,14 @@ def main():
     ap.add_argument("--train", action="store_true",
                     help="BASELINE config 4 instead of the sampling headline: training steps (noise + taped forward + 3 losses + HIP "
                          "backward + gradient all-reduce over RCCL + Adam), 128 patches per GPU unless --batch is given")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed block of --steps steps is run this many times back to back (each bracketed by barrier + synchronize, "
-                         "max over ranks); ms_per_step / value are the MEDIAN block, every block is listed in ms_per_step_runs")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the --steps timed steps are split into this many blocks run back to back (at most one per step; each bracketed "
+                         "by barrier + synchronize, max over ranks); ms_per_step / value are the MEDIAN block, every block is listed in "
+                         "ms_per_step_runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step of the reported measurement returned (sampling: seq_idx, "
+                         "translations, orientations of every patch; --train, the reported leg with d pair_ctx: loss, param_grads, "
+                         "pair_context_grad) as DIR/<name>.npy, float32 / float64, 64 MB at most (larger arrays: a fixed, seeded sample)")
     ap.add_argument("--multi-launch", action="store_true",
                     help="DIFFAB_FLAG_MULTI_LAUNCH: one launch per kernel of an IPA layer instead of the patch-resident module launch the "
                          "sampler chooses at this batch size (bitwise the same samples; for profiles of the separate kernels)")
@@ -558,18 +600,24 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # read before the warm-up: the GPU idles while rocm-smi runs, and the steps right after that gap are slower.  Measured with
+    # --repeats 5 --steps 100: read here, the first 20-step block carries 0.3-0.5 ms more than the others; read right before the timed
+    # region, 2.3 ms more (2.59 against 2.48 ms per step), which a single timed block would put straight into ms_per_step
+    clocks_before = gpu_clocks() if rank == 0 else None
     t_next = run_steps(args.warmup, model.T)
     if dist is not None:  # untimed: RCCL sets up its channels / buffers on the first collective of each kind
         gather_samples({"seq_idx": seq, "translations": x, "orientations": O}, dist)
-    clocks_before = gpu_clocks() if rank == 0 else None
     lib.diffab_kernel_timer_enable(1)
-    # The timed block (EXACTLY --steps steps + the all-gather, barrier + synchronize on both sides, max over ranks) is run --repeats
-    # times back to back in this process: one number per round cannot tell a 3 % change from the box-to-box spread.
+    # EXACTLY --steps timed steps, in --repeats blocks run back to back in this process (each: its steps + the all-gather, barrier +
+    # synchronize on both sides, max over ranks).  runs = seconds per step of each block.  One block by default: every block pays the
+    # once-per-call setup of diffab_sample_loop (~0.5 ms), so smaller blocks would raise ms_per_step at small --steps.
+    n_blocks = max(1, min(args.repeats, args.steps))
+    blocks = [args.steps // n_blocks + (1 if i < args.steps % n_blocks else 0) for i in range(n_blocks)]
     runs = []
-    for _rep in range(max(1, args.repeats)):
+    for n_ in blocks:
         barrier()
         t0 = time.perf_counter()
-        t_next = run_steps(args.steps, t_next)
+        t_next = run_steps(n_, t_next)
         samples = gather_samples({"seq_idx": seq, "translations": x, "orientations": O}, dist)  # RCCL all-gather when N > 1
         barrier()
         el = time.perf_counter() - t0
@@ -577,8 +625,10 @@ def main():
             tmax = torch.tensor([el], device="cuda", dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             el = float(tmax.item())
-        runs.append(el)
-    elapsed = sorted(runs)[len(runs) // 2]  # median block
+        runs.append(el / n_)
+    step_s = sorted(runs)[len(runs) // 2]  # median block
+    if args.dump_outputs and rank == 0:  # what the last timed step returned (the steps below continue on the same buffers)
+        samples = {k: v.clone() for k, v in samples.items()}
     launches, total_ms = C.c_int64(0), C.c_double(0.0)
     _hip.check(lib.diffab_kernel_timer_read(C.byref(launches), C.byref(total_ms)), "kernel_timer_read")
     lib.diffab_kernel_timer_enable(0)
@@ -588,8 +638,7 @@ def main():
     # Which kernel the timer bracketed: the sampler runs the IPA module as ONE patch-resident launch per step when the batch fills the
     # chip (csrc/ipa_persistent.hip; bitwise the per-layer launches), else one attention launch per layer.  In the first case the
     # attention tile body is also timed as its own launch (DIFFAB_FLAG_MULTI_LAUNCH, 20 untimed-for-`value` steps) for comparison.
-    total_steps = args.steps * len(runs)
-    module_form = launches.value == total_steps
+    module_form = launches.value == args.steps
     attn_alone = None
     if module_form and rank == 0 and not args.generic:
         fl2 = flags | _hip.FLAG_MULTI_LAUNCH
@@ -611,7 +660,7 @@ def main():
         attn_alone = (l2.value, ms2.value / max(l2.value, 1), ms_step_multi)
 
     if rank == 0:
-        value = world * B * K * args.steps / elapsed
+        value = world * B * K / step_s
         avg_ms = total_ms.value / max(launches.value, 1)
         alg = algorithmic_bytes_per_attention_launch(B, K, dims["D"], dims["C"]) * (dims["NL"] if module_form else 1)
         achieved = alg / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
@@ -631,11 +680,11 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            # every timed block of this process (each: --steps steps + gather, bracketed); ms_per_step / value = the median block
-            "ms_per_step_runs": [r / args.steps * 1e3 for r in runs],
-            "ms_per_step_min": min(runs) / args.steps * 1e3,
-            "ms_per_step_median": elapsed / args.steps * 1e3,
+            "ms_per_step": step_s * 1e3,
+            # every timed block of this process (together --steps steps, each + gather, bracketed); ms_per_step / value = the median block
+            "ms_per_step_runs": [r * 1e3 for r in runs],
+            "ms_per_step_min": min(runs) * 1e3,
+            "ms_per_step_median": step_s * 1e3,
             "gpu_clocks": {"before": clocks_before, "after": clocks_after},
             "higher_is_better": True,
             "scaling": "weak",
@@ -693,6 +742,8 @@ def main():
             torch.manual_seed(0)
             sd = {k: v.detach().cpu() for k, v in model.denoiser.state_dict().items()}
             out["cpu_baseline"] = cpu_baseline(dims, sd, K, seed=seed, budget_s=args.cpu_budget)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, samples)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -386,3 +386,71 @@ def test_two_sampler_pipelines_on_two_streams_are_bitwise_the_sequential_runs(hi
         torch.cuda.synchronize()
     assert hip.diffab_set_stream_guard(0) == 0
     assert int(bad.sum()) == 0, dict(zip(ref, bad.tolist()))
+
+
+
+def _bench_dump(tmp_path, name, *args):
+    """One bench.py run with --dump-outputs into tmp_path/name: (its JSON line, {array name: array})."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    from conftest import REPO
+
+    out_dir = tmp_path / name
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--no-cpu-baseline", "--dump-outputs", str(out_dir), *args]
+    res = subprocess.run(cmd, cwd=str(tmp_path), capture_output=True, text=True, timeout=400)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, res.stdout[-2000:]
+    assert sum(f.stat().st_size for f in out_dir.iterdir()) <= 64 << 20
+    return json.loads(lines[0]), {f.stem: np.load(f) for f in out_dir.iterdir()}
+
+
+def test_bench_times_exactly_steps_and_dumps_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs on the sampling headline at B = 256, where the sampler takes the patch-resident module launch and bench.py
+    runs 20 more steps on the same buffers after the timed region: the timed region holds exactly --steps steps (the kernel timer's
+    launches: one module launch per step, or NL attention launches with --multi-launch), two runs with the same arguments write the same
+    arrays bit for bit, and the per-layer form, which runs no extra steps, writes them too (the two forms are bitwise equal)."""
+    B, K, steps, NL = 256, 128, 7, syn.BENCH_DIMS["NL"]
+    common = ("--steps", str(steps), "--warmup", "2", "--batch", str(B), "--no-other-configs")
+    runs = [_bench_dump(tmp_path, "a", *common), _bench_dump(tmp_path, "b", *common),
+            _bench_dump(tmp_path, "multi", *common, "--multi-launch")]
+    for (out, _), launches in zip(runs, (steps, steps, steps * NL)):
+        assert out["steps"] == steps and len(out["ms_per_step_runs"]) == 1 and out["outputs_finite"]
+        assert out["roofline"]["launches"] == launches, (out["roofline"]["launches"], launches)
+        assert abs(out["value"] - B * K / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert "roofline_attention_launch" in runs[0][0]  # the extra steps after the timed region did run
+    a = runs[0][1]
+    assert sorted(a) == ["orientations", "seq_idx", "translations"]
+    assert a["seq_idx"].shape == (B, K) and a["translations"].shape == (B, K, 3) and a["orientations"].shape == (B, K, 3, 3)
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        for _, other in runs[1:]:
+            assert np.array_equal(a[n], other[n]), n
+
+
+TRAIN_DUMP_TOL = 1e-5  # max|a-b| / max|b| between two --train runs of the same first step (measured: <= 5e-7)
+
+
+def test_bench_train_dumps_the_reported_leg_with_d_pair_ctx(tmp_path):
+    """bench.py --train --dump-outputs: the last step of the reported leg (contexts requiring grad): loss, the parameter gradients and
+    d pair_ctx, which at 128 patches (537 MB) is written as a fixed, seeded sample of patches.  Two runs with the same arguments agree,
+    not bit for bit: the backward kernels accumulate with float atomics.  The dumped step is the first one (no warm-up), taken from the
+    same seeded parameters in both runs: after Adam steps, a summation-order difference in a gradient element near zero can flip the sign
+    of its update and move the parameters apart by up to the learning rate."""
+    from conftest import maxrel
+
+    B, K = 128, 128
+    runs = [_bench_dump(tmp_path, r, "--train", "--steps", "1", "--warmup", "0") for r in ("a", "b")]
+    (out, a), (_, b) = runs
+    assert out["d_pair_ctx_computed"] and out["loss_finite"] and out["steps"] == 1
+    assert sorted(a) == ["loss", "pair_context_grad", "param_grads"]
+    g = a["pair_context_grad"]
+    assert g.dtype == np.float32 and g.ndim == 4 and g.shape[1:] == (K, K, syn.BENCH_DIMS["C"]) and 0 < g.shape[0] < B
+    assert a["param_grads"].ndim == 1 and a["param_grads"].size > 1_000_000
+    for n in a:
+        assert a[n].shape == b[n].shape and np.isfinite(a[n]).all(), n
+        assert np.abs(a[n]).max() > 0, n
+        assert maxrel(a[n], b[n]) < TRAIN_DUMP_TOL, (n, maxrel(a[n], b[n]))
