@@ -111,7 +111,8 @@ struct StepBuffers {
 };
 static size_t mlp_planes_bytes() { return (rowgemm128_b6_scratch_bytes(128) + 255) & ~static_cast<size_t>(255); }
 
-static StepBuffers carve_step(const diffab_dims* d, void* ws) {
+// n_pair: patches of the pair embedding whose fp16 planes the buffers hold (0: d->B; shared contexts: n_ctx)
+static StepBuffers carve_step(const diffab_dims* d, void* ws, int n_pair = 0) {
   Carver c(ws);
   const size_t rows = static_cast<size_t>(d->B) * d->K;
   StepBuffers b;
@@ -130,7 +131,7 @@ static StepBuffers carve_step(const diffab_dims* d, void* ws) {
   if (fast_path_supported(d)) ipa_floats = ipa_floats > ipa_fast_workspace_floats(d) ? ipa_floats : ipa_fast_workspace_floats(d);
   b.ipa = c.take<float>(ipa_floats);
   b.planes = fast_path_supported(d) ? c.take<char>(d->NL * ipa_layer_planes_bytes() + 11 * mlp_planes_bytes()) : nullptr;
-  b.pair = pair_planes_supported(d) ? c.take<float>(pair_planes_floats(d)) : nullptr;
+  b.pair = pair_planes_supported(d) ? c.take<float>(pair_planes_floats(d, n_pair)) : nullptr;  // (last: n_pair moves no other buffer)
   b.bytes = c.bytes();
   return b;
 }
@@ -139,14 +140,14 @@ static int ipa_layer_dispatch(const diffab_dims* d, const diffab_ipa_layer_weigh
                               const float* t, float* y, float* ws, uint32_t flags, hipStream_t st, float* sp_keep = nullptr,
                               float* d2_keep = nullptr, const void* planes = nullptr, const float* pair_planes = nullptr,
                               bool taped = false,  // taped: ws is a slot of the training tape (the backward reads proj and feat)
-                              const unsigned char* tile_needed = nullptr) {
+                              const unsigned char* tile_needed = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0) {
   DIFFAB_REQUIRE(w && w->gamma && w->wq_s && w->wk_s && w->wv_s && (w->w_bias || d->C == 0) && w->wq_p && w->wk_p && w->wv_p && w->w_out &&
                      w->b_out,
                  DIFFAB_ERR_ARG, "ipa layer: null weight pointer");
   if (!(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d))
     return ipa_layer_fast(d, w, x, e, R, t, y, ws, st, sp_keep, d2_keep, planes, pair_planes, (flags & DIFFAB_FLAG_FP32_GEMM) != 0,
-                          taped, tile_needed);
-  return ipa_layer_generic(d, w, x, e, R, t, y, ws, st);
+                          taped, tile_needed, ctx_of_row, n_ctx);
+  return ipa_layer_generic(d, w, x, e, R, t, y, ws, st, ctx_of_row);
 }
 
 static int mlp3(const diffab_dims* d, const diffab_mlp3_weights* w, const float* cat3, float* t1, float* t2, float* out, int n_out,
@@ -195,8 +196,10 @@ static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, 
                         bool pair_prepared = false, const float* sched_beta = nullptr, int t_step = 0, const int* t_dev = nullptr,
                         const unsigned char* last_layer_tiles = nullptr,  // row tiles of the LAST layer whose outputs are read
                         bool skip_heads_finish = false,  // the caller finishes the heads itself from b.vbuf / b.logits (reverse sampler)
-                        const float* beta_traj = nullptr, int traj_rows = 0) {  // [3 heads][traj_rows steps][D]: the heads' folded beta
-                                                                               // columns of EVERY step (row t_step is this step's)
+                        const float* beta_traj = nullptr, int traj_rows = 0,  // [3 heads][traj_rows steps][D]: the heads' folded beta
+                                                                              // columns of EVERY step (row t_step is this step's)
+                        const int* ctx_of_row = nullptr, int n_ctx = 0) {  // shared contexts (reverse sampler): pair_ctx / its planes hold
+                                                                           // n_ctx patches, state row b reads context ctx_of_row[b]
   // sched_beta (reverse sampler): every patch is at step t_step (or *t_dev): the folded head tables take beta from the schedule and
   // `beta` is only read by the unfolded path
   const StepBuffers b = carve_step(d, ws);
@@ -276,14 +279,14 @@ static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, 
   }
   if (persistent) {
     if (int rc = launch_ipa_module_persistent(d, b.hA, b.hB, O_t, x_t, b.ipa, b.planes, pair_planes, st, fused_mlps ? res_ctx : nullptr,
-                                              &emb_set, &head_set))
+                                              &emb_set, &head_set, ctx_of_row, n_ctx))
       return rc;
     cur = (d->NL & 1) ? b.hB : b.hA;
   }
   for (int l = 0; l < d->NL && !persistent; ++l) {
     const void* planes = (fold && use_b6_gemm(flags)) ? b.planes + l * ipa_layer_planes_bytes() : nullptr;
     if (int rc = ipa_layer_dispatch(d, &w->layers[l], cur, pair_ctx, O_t, x_t, nxt, b.ipa, flags, st, nullptr, nullptr, planes, pair_planes,
-                                    false, l == d->NL - 1 ? last_layer_tiles : nullptr))
+                                    false, l == d->NL - 1 ? last_layer_tiles : nullptr, ctx_of_row, n_ctx))
       return rc;
     float* tmp = cur; cur = nxt; nxt = tmp;
   }
@@ -358,11 +361,14 @@ struct SampleBuffers {
   int* t_dev;  // the current timestep in device memory (graph replay)
   unsigned char* tiles;  // [B][K / 16]: row tiles with a generated residue (DIFFAB_FLAG_SKIP_UNUSED_ROWS)
   float* beta_traj;      // [3 heads][kTrajRows][D]: the heads' folded beta columns of every step of a schedule with T < kTrajRows
+  int* ctx_of_row;       // shared contexts: [B] the context of every state row (device copy of the caller's map)
+  float* res_ctx;        // shared contexts: [B][K][D] the residue context of every state row (gathered once per call)
   void* step;
   size_t bytes;
 };
 
-static SampleBuffers carve_sample(const diffab_dims* d, void* ws) {
+// n_pair: patches of the pair embedding (0: d->B); mapped: diffab_sample_loop_shared with a context map (its two buffers)
+static SampleBuffers carve_sample(const diffab_dims* d, void* ws, int n_pair = 0, bool mapped = false) {
   Carver c(ws);
   const size_t rows = static_cast<size_t>(d->B) * d->K;
   SampleBuffers s;
@@ -373,7 +379,9 @@ static SampleBuffers carve_sample(const diffab_dims* d, void* ws) {
   s.t_dev = c.take<int>(64);
   s.tiles = c.take<unsigned char>(static_cast<size_t>(d->B) * ((d->K + 15) / 16));
   s.beta_traj = c.take<float>(static_cast<size_t>(3) * kTrajRows * d->D);
-  const size_t step_bytes = carve_step(d, nullptr).bytes;
+  s.ctx_of_row = mapped ? c.take<int>(d->B) : nullptr;
+  s.res_ctx = mapped ? c.take<float>(rows * d->D) : nullptr;  // 256-byte aligned: the folded embedding MLP takes it as it takes the caller's
+  const size_t step_bytes = carve_step(d, nullptr, n_pair).bytes;
   s.step = c.take<char>(step_bytes);
   s.bytes = c.bytes();
   return s;
@@ -494,6 +502,15 @@ size_t diffab_denoise_workspace_bytes(const diffab_dims* d) {
 size_t diffab_sample_workspace_bytes(const diffab_dims* d) {
   if (check_dims(d, "sample_workspace_bytes")) return 0;
   return carve_sample(d, nullptr).bytes;
+}
+
+size_t diffab_sample_shared_workspace_bytes(const diffab_dims* d, int32_t n_ctx) {
+  if (check_dims(d, "sample_shared_workspace_bytes")) return 0;
+  if (n_ctx < 1 || static_cast<int64_t>(n_ctx) * d->K >= (1ll << 31)) {
+    set_error("sample_shared_workspace_bytes: need 1 <= n_ctx and n_ctx*K < 2^31 (n_ctx=%d)", n_ctx);
+    return 0;
+  }
+  return carve_sample(d, nullptr, n_ctx, true).bytes;
 }
 
 int diffab_ipa_layer_fwd(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R,
@@ -671,6 +688,16 @@ int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, c
                        int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, const uint8_t* gen_mask, uint64_t seed,
                        int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags,
                        void* stream) {
+  // one context per state row: the shared-context loop with the identity map (which launches exactly what it always did)
+  if (int rc = check_dims(d, "sample_loop")) return rc;
+  return diffab_sample_loop_shared(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, d->B, nullptr, gen_mask, seed, first_patch, t_start, t_stop,
+                                   workspace, workspace_bytes, flags, stream);
+}
+
+int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                              int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
@@ -679,20 +706,41 @@ int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, c
                  "sample_loop: reverse IGSO3 table must have T+1 rows");
   DIFFAB_REQUIRE(seq && x && O && res_ctx && pair_ctx && gen_mask && workspace, DIFFAB_ERR_ARG, "sample_loop: null pointer");
   DIFFAB_REQUIRE(t_start <= s->T && t_stop >= 0 && t_stop <= t_start, DIFFAB_ERR_ARG, "sample_loop: need T >= t_start >= t_stop >= 0");
-  const SampleBuffers sb = carve_sample(d, workspace);
+  // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
+  // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
+  const bool mapped = ctx_of_row != nullptr;
+  DIFFAB_REQUIRE(mapped || n_ctx == d->B, DIFFAB_ERR_ARG, "sample_loop: without ctx_of_row n_ctx must equal B (%d != %d)", n_ctx, d->B);
+  DIFFAB_REQUIRE(n_ctx >= 1 && static_cast<int64_t>(n_ctx) * d->K < (1ll << 31), DIFFAB_ERR_ARG, "sample_loop: need 1 <= n_ctx, n_ctx*K < 2^31");
+  bool identity = n_ctx == d->B;
+  for (int b = 0; mapped && b < d->B; ++b) {
+    DIFFAB_REQUIRE(ctx_of_row[b] >= 0 && ctx_of_row[b] < n_ctx, DIFFAB_ERR_ARG, "sample_loop: ctx_of_row[%d] = %d outside [0, %d)", b,
+                   ctx_of_row[b], n_ctx);
+    identity = identity && ctx_of_row[b] == b;
+  }
+  const SampleBuffers sb = carve_sample(d, workspace, n_ctx, mapped);
   DIFFAB_REQUIRE(workspace_bytes >= sb.bytes, DIFFAB_ERR_WORKSPACE, "sample_loop: workspace %zu < %zu bytes", workspace_bytes, sb.bytes);
   hipStream_t st = as_stream(stream);
+  const int* ctx_dev = nullptr;  // device map of the kernels (nullptr: the identity)
+  if (!identity) {
+    // once per call: the map, and the residue context of every state row (64 KiB per row at K = 128 - the per-row MLPs read it as
+    // before; only the pair stream is read through the map)
+    DIFFAB_HIP_CHECK(hipMemcpyAsync(sb.ctx_of_row, ctx_of_row, sizeof(int32_t) * d->B, hipMemcpyHostToDevice, st));
+    if (int rc = launch_gather_rows(res_ctx, sb.ctx_of_row, d->B, static_cast<int64_t>(d->K) * d->D, sb.res_ctx, st)) return rc;
+    ctx_dev = sb.ctx_of_row;
+    res_ctx = sb.res_ctx;
+  }
   // the folded sequence-embedding table depends on the weights only: once per call, not once per step (same condition as denoise_step)
-  const StepBuffers b0 = carve_step(d, sb.step);
+  const StepBuffers b0 = carve_step(d, sb.step, n_ctx);
   const bool fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) &&
                     rowgemm128_ok(res_ctx, d->D, b0.h1, d->D, d->B * d->K, d->D);
   if (fold)
     if (int rc = prepare_weights(d, w, b0, flags, st)) return rc;
-  // the pair embedding is the same tensor in all T x NL attention launches of a trajectory: its fp16 planes are built once here
+  // the pair embedding is the same tensor in all T x NL attention launches of a trajectory: its fp16 planes are built once here, for the
+  // n_ctx contexts
   if (!(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
   const bool pair_ready = use_pair_planes(d, flags, pair_ctx, b0);
   if (pair_ready)
-    if (int rc = launch_pair_split(d, pair_ctx, b0.pair, st)) return rc;
+    if (int rc = launch_pair_split(d, pair_ctx, b0.pair, st, n_ctx)) return rc;
   // The IPA module as ONE patch-resident launch per step (ipa_persistent.hip; bitwise the 3 NL launches it replaces, so the choice never
   // shows in the samples) when the batch fills the chip with one work-group per patch: B = 256 is 2.60 ms per step against 2.70.  Fewer
   // patches than CUs leave CUs idle for the whole module (B = 8: 2.07 ms against 0.47), a ragged last round of patches costs a module
@@ -728,7 +776,8 @@ int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, c
     if (!fold)  // (the folded head tables read the schedule themselves: one launch less per step)
       if (int rc = launch_fill_beta(s, t, d->B, sb.beta, st, t_dev)) return rc;
     if (int rc = denoise_step(d, w, seq, x, O, res_ctx, pair_ctx, sb.beta, sb.eps, sb.O0, sb.post, nullptr, nullptr, sb.step, flags, st, fold,
-                              pair_ready, fold ? s->beta : nullptr, t, t_dev, tiles, true, t_dev ? nullptr : beta_traj, s->T + 1))
+                              pair_ready, fold ? s->beta : nullptr, t, t_dev, tiles, true, t_dev ? nullptr : beta_traj, s->T + 1, ctx_dev,
+                              n_ctx))
       return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,

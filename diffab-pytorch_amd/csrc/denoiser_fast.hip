@@ -352,7 +352,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void ipa_attn_fast_kernel
                                                             unsigned long long* __restrict__ stamps, const float* __restrict__ esc = nullptr,
                                                             float* __restrict__ tape_p = nullptr, float* __restrict__ tape_d2 = nullptr,
                                                             const unsigned char* __restrict__ tile_needed = nullptr,
-                                                            const f32x4* __restrict__ vpl = nullptr, const float* __restrict__ vsc = nullptr) {
+                                                            const f32x4* __restrict__ vpl = nullptr, const float* __restrict__ vsc = nullptr,
+                                                            const int* __restrict__ ctx_of_row = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int ntile = (MULTI ? NC_arg : 1) * NT;  // K / TI
   // XCD-aware map: blocks b and b+8 share an XCD (round-robin dispatch), so give all row tiles of one patch to one XCD.
@@ -369,7 +370,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void ipa_attn_fast_kernel
   // tile_needed (reverse sampler, last layer, DIFFAB_FLAG_SKIP_UNUSED_ROWS): the outputs of this layer are read for generated residues
   // only - a row tile without one leaves at once (uniform; its feature rows keep the previous layer's values, which nothing reads)
   if (tile_needed != nullptr && !tile_needed[b * ntile + tile]) return;
-  ipa_attn_tile<NT, MULTI, PLANES, TAPE, NW, VPL>(S, b, tile, bid, proj, e, R, t, Wb, gamma, feat, NC_arg, stamps, esc, tape_p, tape_d2, vpl, vsc);
+  ipa_attn_tile<NT, MULTI, PLANES, TAPE, NW, VPL>(S, b, tile, bid, proj, e, R, t, Wb, gamma, feat, NC_arg, stamps, esc, tape_p, tape_d2, vpl, vsc,
+                                                  ctx_of_row);
 }
 
 static unsigned long long* g_attn_stamps = nullptr;  // diagnostics only (diffab_debug_set_attn_stamps)
@@ -517,19 +519,25 @@ __global__ void pair_split_kernel(const float* __restrict__ e, const float* __re
   *reinterpret_cast<f16x8*>(base + 1024) = h2;   // plane 1: blocks (1, ks)
 }
 bool pair_planes_supported(const diffab_dims* d) { return fast_path_supported(d); }  // any K the fused kernel takes (K % 64 == 0)
-size_t pair_planes_floats(const diffab_dims* d) {  // 64 (alignment) | planes | row scales {s, 1 / s} per pair row
-  return pair_planes_supported(d) ? static_cast<size_t>(d->B) * d->K * d->K * AC + 64 + 2 * static_cast<size_t>(d->B) * d->K + 64 : 0;
+// n_pair: the patches of the pair embedding (0: d->B; shared contexts: n_ctx)
+static size_t pair_patches(const diffab_dims* d, int n_pair) { return static_cast<size_t>(n_pair > 0 ? n_pair : d->B); }
+size_t pair_planes_floats(const diffab_dims* d, int n_pair) {  // 64 (alignment) | planes | row scales {s, 1 / s} per pair row
+  const size_t np = pair_patches(d, n_pair);
+  return pair_planes_supported(d) ? np * d->K * d->K * AC + 64 + 2 * np * d->K + 64 : 0;
 }
 // the row scales inside a launch_pair_split() buffer (the planes themselves start at planes + 64)
-const float* pair_row_scales(const diffab_dims* d, const float* planes) { return planes + 64 + static_cast<size_t>(d->B) * d->K * d->K * AC; }
-// planes: pair_planes_floats(d) floats, 256-byte aligned
-int launch_pair_split(const diffab_dims* d, const float* e, float* planes, hipStream_t st) {
+const float* pair_row_scales(const diffab_dims* d, const float* planes, int n_pair) {
+  return planes + 64 + pair_patches(d, n_pair) * d->K * d->K * AC;
+}
+// planes: pair_planes_floats(d, n_pair) floats, 256-byte aligned; e: (n_pair, K, K, C)
+int launch_pair_split(const diffab_dims* d, const float* e, float* planes, hipStream_t st, int n_pair) {
   DIFFAB_REQUIRE(pair_planes_supported(d) && e && planes && (reinterpret_cast<uintptr_t>(planes) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(e) & 15) == 0,
                  DIFFAB_ERR_ARG, "pair_split: unsupported operands");
-  const int64_t n = static_cast<int64_t>(d->B) * d->K * d->K * AC;
-  float* rs = const_cast<float*>(pair_row_scales(d, planes));
-  hipLaunchKernelGGL(pair_rowscale_kernel, dim3(d->B * d->K), dim3(256), 0, st, e, d->K * AC / 4, rs);
+  const int64_t np = static_cast<int64_t>(pair_patches(d, n_pair));
+  const int64_t n = np * d->K * d->K * AC;
+  float* rs = const_cast<float*>(pair_row_scales(d, planes, n_pair));
+  hipLaunchKernelGGL(pair_rowscale_kernel, dim3(static_cast<unsigned>(np * d->K)), dim3(256), 0, st, e, d->K * AC / 4, rs);
   hipLaunchKernelGGL(pair_split_kernel, dim3(static_cast<unsigned>((n / 8 + 255) / 256)), dim3(256), 0, st, e, rs, d->K, n / 8,
                      reinterpret_cast<_Float16*>(planes + 64));
   DIFFAB_LAUNCH_CHECK();
@@ -616,8 +624,9 @@ int launch_attn_value_planes(const diffab_dims* d, const float* proj, const floa
 
 int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R, const float* t,
                    float* y, float* ws, hipStream_t st, float* sp_keep, float* d2_keep, const void* planes, const float* pair_planes,
-                   bool fp32_gemm, bool taped, const unsigned char* tile_needed) {
+                   bool fp32_gemm, bool taped, const unsigned char* tile_needed, const int* ctx_of_row, int n_ctx) {
   const int rows = d->B * d->K, D = d->D;
+  DIFFAB_REQUIRE(ctx_of_row == nullptr || sp_keep == nullptr, DIFFAB_ERR_ARG, "ipa_layer_fast: shared contexts are an inference form");
   float* proj = ws;
   float* feat = ws + static_cast<size_t>(rows) * ANP;
   // Dense projections on the bf16 matrix cores (gemm_bf16x6.hip) from split weight planes: the caller's (reverse sampler: split once
@@ -684,7 +693,7 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
   // pair_planes (launch_pair_split): the pair-tile products on the f16 matrix cores, the pair stream read as two fp16 planes
   const bool use_planes = pair_planes != nullptr && pair_planes_supported(d);
   const float* e_arg = use_planes ? pair_planes + 64 : e;
-  const float* esc = use_planes ? pair_row_scales(d, pair_planes) : nullptr;
+  const float* esc = use_planes ? pair_row_scales(d, pair_planes, n_ctx) : nullptr;
 #define ATTN_LAUNCH(NT_, MULTI_, PLANES_, VPL_)                                                                                       \
   do {                                                                                                                                \
     DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_fast_kernel<NT_, MULTI_, PLANES_, false, 8, VPL_>),   \
@@ -692,7 +701,7 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
     timer_begin(st);                                                                                                                  \
     hipLaunchKernelGGL((ipa_attn_fast_kernel<NT_, MULTI_, PLANES_, false, 8, VPL_>), grid, dim3(512), lds, st, proj, e_arg, R, t,     \
                        w->w_bias, w->gamma, feat, d->B, nc, g_attn_stamps, esc, nullptr, nullptr, tile_needed,                        \
-                       reinterpret_cast<const f32x4*>(vpl), vsc);                                                                     \
+                       reinterpret_cast<const f32x4*>(vpl), vsc, ctx_of_row);                                                         \
     timer_end(st);                                                                                                                    \
   } while (0)
   if (tape) {
@@ -708,7 +717,7 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds4)));
     timer_begin(st);
     hipLaunchKernelGGL((ipa_attn_fast_kernel<4, true, true, false, 4>), grid, dim3(256), lds4, st, proj, e_arg, R, t, w->w_bias, w->gamma, feat,
-                       d->B, nc4, g_attn_stamps, esc, nullptr, nullptr, tile_needed);
+                       d->B, nc4, g_attn_stamps, esc, nullptr, nullptr, tile_needed, nullptr, nullptr, ctx_of_row);
     timer_end(st);
   } else if (vpl_on) {
     if (nt == 8 && nc == 1) ATTN_LAUNCH(8, false, true, true);

@@ -118,10 +118,12 @@ __global__ void points_to_global_kernel(float* __restrict__ buf, int ld, int col
 // ------------------------------------------------------------------ attention, one work-group per (patch, query residue)
 // proj row layout (ld = NP): [q_s H*DS | k_s H*DS | v_s H*DS | gq H*PQ*3 | gk H*PQ*3 | gv H*PV*3], points already global.
 // feat row layout (F): [o_s H*DS | o_e H*C | o_l H*PV*3 | o_n H*PV]   (diffab_pytorch.py:460)
+// ctx_of_row (shared contexts): e holds the pair rows of the contexts, state row b reads those of context ctx_of_row[b]; nullptr: identity
 __global__ __launch_bounds__(256) void ipa_attn_generic_kernel(const float* __restrict__ proj, const float* __restrict__ e,
                                                                const float* __restrict__ R, const float* __restrict__ t,
                                                                const float* __restrict__ Wb, const float* __restrict__ gamma,
-                                                               float* __restrict__ feat, int K, int C, int H, int DS, int PQ, int PV) {
+                                                               float* __restrict__ feat, int K, int C, int H, int DS, int PQ, int PV,
+                                                               const int* __restrict__ ctx_of_row) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int b = blockIdx.x / K, i = blockIdx.x % K;
   const int NP = 3 * H * DS + 2 * H * PQ * 3 + H * PV * 3;
@@ -135,7 +137,8 @@ __global__ __launch_bounds__(256) void ipa_attn_generic_kernel(const float* __re
   for (int d = threadIdx.x; d < H * DS; d += blockDim.x) qrow[d] = prow[d];
   for (int d = threadIdx.x; d < H * PQ * 3; d += blockDim.x) qrow[H * DS + d] = prow[off_gq + d];
   __syncthreads();
-  const float* erow = e + row_i * K * C;  // e[b, i, :, :]
+  const int64_t erow_i = static_cast<int64_t>(ctx_of_row != nullptr ? ctx_of_row[b] : b) * K + i;
+  const float* erow = e + erow_i * K * C;  // e[ctx(b), i, :, :]
   const float scale_s = 1.0f / sqrtf(static_cast<float>(DS));
   const float scale_p = -0.5f / sqrtf(4.5f * PQ);
   const float scale_t = 1.0f / sqrtf(C > 0 ? 3.0f : 2.0f);  // num_independent_logits^-1/2: 3 with the pair bias, 2 without (C == 0, :385-387)
@@ -211,7 +214,7 @@ size_t ipa_generic_workspace_floats(const diffab_dims* d) {
 }
 
 int ipa_layer_generic(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R, const float* t,
-                      float* y, float* ws, hipStream_t st) {
+                      float* y, float* ws, hipStream_t st, const int* ctx_of_row) {
   const int rows = d->B * d->K;
   const int H = d->H, DS = d->DS, PQ = d->PQ, PV = d->PV, D = d->D, C = d->C;
   const int NP = 3 * H * DS + 2 * H * PQ * 3 + H * PV * 3;
@@ -238,7 +241,8 @@ int ipa_layer_generic(const diffab_dims* d, const diffab_ipa_layer_weights* w, c
     DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_generic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          static_cast<int>(lds)));
   timer_begin(st);
-  hipLaunchKernelGGL(ipa_attn_generic_kernel, dim3(rows), dim3(256), lds, st, proj, e, R, t, w->w_bias, w->gamma, feat, d->K, C, H, DS, PQ, PV);
+  hipLaunchKernelGGL(ipa_attn_generic_kernel, dim3(rows), dim3(256), lds, st, proj, e, R, t, w->w_bias, w->gamma, feat, d->K, C, H, DS, PQ, PV,
+                     ctx_of_row);
   timer_end(st);
   DIFFAB_LAUNCH_CHECK();
   return launch_linear_generic(feat, F, w->w_out, w->b_out, y, D, rows, D, F, false, st);

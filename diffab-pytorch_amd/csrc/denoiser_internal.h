@@ -8,8 +8,10 @@ namespace diffab {
 int launch_linear_generic(const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int Kd, bool relu,
                           hipStream_t st);
 size_t ipa_generic_workspace_floats(const diffab_dims* d);
+// ctx_of_row (here and in ipa_layer_fast / launch_ipa_module_persistent): shared contexts - device [B] map, the pair rows of state row b
+// are those of context ctx_of_row[b] of the n_ctx patches in e / pair_planes; nullptr: the identity (n_ctx = B)
 int ipa_layer_generic(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R, const float* t,
-                      float* y, float* ws, hipStream_t st);
+                      float* y, float* ws, hipStream_t st, const int* ctx_of_row = nullptr);
 int launch_embed_concat(const float* res_ctx, const float* emb, const int64_t* seq, int D, int64_t rows, float* out, hipStream_t st);
 int launch_beta_concat(const float* h, const float* beta, int D, int K, int64_t rows, float* out, hipStream_t st);
 int launch_heads_finish(const float* v, const float* O_t, const float* logits, int V, int64_t rows, float* O0, float* post, hipStream_t st);
@@ -34,12 +36,14 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
                    const float* pair_planes = nullptr,  // launch_pair_split() output: attention's pair-tile products on f16 MFMA
                    bool fp32_gemm = false,
                    bool taped = false,   // ws is a slot of the training tape: proj and feat are read by the backward (no scratch use)
-                   const unsigned char* tile_needed = nullptr);  // [B][K / 16]: row tiles whose outputs are read (nullptr: all)  // DIFFAB_FLAG_FP32_GEMM: dense products on the f32-input MFMA kernels
-// fp16 planes of the pair embedding for the fused attention kernel (K = 64 / 128): pair_planes_floats(d) floats, 256-byte aligned
+                   const unsigned char* tile_needed = nullptr,  // [B][K / 16]: row tiles whose outputs are read (nullptr: all)  // DIFFAB_FLAG_FP32_GEMM: dense products on the f32-input MFMA kernels
+                   const int* ctx_of_row = nullptr, int n_ctx = 0);  // shared contexts (inference only; n_ctx 0: d->B)
+// fp16 planes of the pair embedding for the fused attention kernel (K = 64 / 128): pair_planes_floats(d) floats, 256-byte aligned.
+// n_pair: patches of the pair embedding, 0 = d->B (shared contexts: n_ctx - the planes are built once per context, not per state row)
 bool pair_planes_supported(const diffab_dims* d);
-size_t pair_planes_floats(const diffab_dims* d);
-int launch_pair_split(const diffab_dims* d, const float* e, float* planes, hipStream_t st);
-const float* pair_row_scales(const diffab_dims* d, const float* planes);  // {s_i, 1 / s_i} per pair row (b, i) of a launch_pair_split() buffer
+size_t pair_planes_floats(const diffab_dims* d, int n_pair = 0);
+int launch_pair_split(const diffab_dims* d, const float* e, float* planes, hipStream_t st, int n_pair = 0);
+const float* pair_row_scales(const diffab_dims* d, const float* planes, int n_pair = 0);  // {s_i, 1 / s_i} per pair row (b, i) of a launch_pair_split() buffer
 // Y = act(X W^T + b) on MFMA; requires Kd % 4 == 0 (falls back to the generic kernel otherwise)
 int launch_linear(const float* X, int ldx, const float* W, const float* bias, float* Y, int ldy, int M, int N, int Kd, bool relu,
                   hipStream_t st);
@@ -120,7 +124,7 @@ int ipa_layer_split_weights(const diffab_ipa_layer_weights* w, void* planes, hip
 bool ipa_module_persistent_supported(const diffab_dims* d);
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X = nullptr, const MlpChainSet* emb = nullptr,
-                                 const MlpChainSet* heads = nullptr);
+                                 const MlpChainSet* heads = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0);
 void set_module_stagger(int ticks, int classes);  // diagnostics: start-up stagger of the persistent module kernel (10 ns ticks)
 void set_module_stamps(void* device_buffer);      // diagnostics: phase stamps of the persistent module kernel
 // bias tables of the folded concatenations: emb_tab[25][D] and beta_tab[3 heads][B][D] (see denoiser_fast.hip)
@@ -239,6 +243,8 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const float* head_v = nullptr, const float* head_logits = nullptr);  // heads' epilogue done in the kernel  // t_dev: read the timestep from device memory (graph replay)
 int launch_fill_beta(const diffab_sched* s, int t, int B, float* out, hipStream_t st, const int* t_dev = nullptr);
 int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hipStream_t st);  // [B][K / 16]: any generated residue in the tile
+// shared contexts: out[b] = src[ctx_of_row[b]] for the B rows of `row_floats` floats each (16-byte aligned rows)
+int launch_gather_rows(const float* src, const int* ctx_of_row, int B, int64_t row_floats, float* out, hipStream_t st);
 int launch_set_int(int* p, int v, hipStream_t st);
 int launch_dec_int(int* p, hipStream_t st);
 

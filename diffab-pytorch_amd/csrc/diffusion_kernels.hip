@@ -822,6 +822,20 @@ int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hip
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
+// shared contexts (diffab_sample_loop_shared): the residue context rows of every state row, once per call
+__global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ ctx_of_row, int64_t row_floats, int64_t n,
+                                   float* __restrict__ out) {
+  const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+  if (i >= n) return;
+  const int64_t b = i / row_floats;
+  out[i] = src[static_cast<int64_t>(ctx_of_row[b]) * row_floats + (i - b * row_floats)];
+}
+int launch_gather_rows(const float* src, const int* ctx_of_row, int B, int64_t row_floats, float* out, hipStream_t st) {
+  const int64_t n = static_cast<int64_t>(B) * row_floats;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, src, ctx_of_row, row_floats, n, out);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
 int launch_set_int(int* p, int v, hipStream_t st) {
   hipLaunchKernelGGL(set_int_kernel, dim3(1), dim3(1), 0, st, p, v);
   DIFFAB_LAUNCH_CHECK();

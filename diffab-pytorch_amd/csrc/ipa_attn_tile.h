@@ -94,6 +94,21 @@ __device__ __forceinline__ void attn_p1_request(AttnP1Pre<SD>& pre, const int pi
   pre.gqr[1] = *reinterpret_cast<const f32x4*>(ug + lo.p1);
 }
 
+// Shared contexts: the pair rows of patch b's context start (ctx_of_row[b] - b) K rows away from row b's.  One wave-uniform scalar load
+// moves the two base pointers (pair stream, PLANES: row scales), so every pair address of the tile stays the identity form's - the same
+// code and registers on the default path (ctx_of_row == nullptr: nothing happens).
+template <bool PLANES, typename FP>  // FP: const float* (with or without __restrict__)
+__device__ __forceinline__ void attn_shift_pair_rows(FP& e, FP& esc, const int* __restrict__ ctx_of_row, const int b, const int K) {
+  if (ctx_of_row == nullptr) return;
+  // (spelled as a scalar load: where the kernel also stores to global memory - the module kernel - hipcc would otherwise fetch the
+  // uniform entry with a vector load and a readfirstlane)
+  int c;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(c) : "s"(ctx_of_row + b) : "memory");
+  const int64_t shift = static_cast<int64_t>(c - b) * K;
+  e += shift * K * AC;  // (a pair row is K x 64 floats in either form: fp32, or the two fp16 planes)
+  if constexpr (PLANES) esc += 2 * shift;
+}
+
 // One (patch b, 16-row tile) item of the fused attention: the body of ipa_attn_fast_kernel (denoiser_fast.hip: one item per work-group)
 // and of the patch-resident module kernel (ipa_persistent.hip: a work-group walks the eight row tiles of ITS patch, layer after layer).
 // 512 threads; S: the dynamic LDS (ipa_attn_lds_bytes(NT)); stamp_id: the slot of this item in the diagnostic stamp buffer.
@@ -105,6 +120,8 @@ __device__ __forceinline__ void attn_p1_request(AttnP1Pre<SD>& pre, const int pi
 // coordinates relative to the patch's first translation); the probabilities are split into two fp16 planes
 // on the fly (2^15 P = p1 + p2): three exact partial products per tile and 32 keys - 12 MFMAs of 16 cycles per (head, 32 keys) against 32
 // f32 MFMAs of 32 cycles (which also block the vector ALU), 8 linear 1 KiB loads per 32 keys straight into B fragments, no LDS staging.
+// ctx_of_row (shared contexts, diffab_sample_loop_shared): the pair rows (and their row scales) of state row b are those of context
+// ctx_of_row[b] - `e` / `esc` then hold n_ctx patches; the projections, features and value planes stay on row b.  nullptr: the identity.
 template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false, int NW = 8, bool VPL = false>
 __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b, const int tile, const unsigned stamp_id,
                                               const float* __restrict__ proj, const float* __restrict__ e,
@@ -113,7 +130,8 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
                                               float* __restrict__ feat, int NC_arg,
                                               unsigned long long* __restrict__ stamps, const float* __restrict__ esc = nullptr,
                                               float* __restrict__ tape_p = nullptr, float* __restrict__ tape_d2 = nullptr,
-                                              const f32x4* __restrict__ vpl = nullptr, const float* __restrict__ vsc = nullptr) {
+                                              const f32x4* __restrict__ vpl = nullptr, const float* __restrict__ vsc = nullptr,
+                                              const int* __restrict__ ctx_of_row = nullptr) {
   static_assert(NW == 8 || (NW == 4 && PLANES && !TAPE), "the four-wave form exists for the plane kernels");
   static_assert(!VPL || (PLANES && NW == 8 && NT % 2 == 0), "value planes: the eight-wave plane kernels");
   constexpr int HPW = AH / NW;  // heads per wave (phases 1 and 3)
@@ -149,6 +167,7 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
   // + 56 B of scratch to none)
   constexpr int HS = KC + 8, IS = AH * (KC + 8) + 8;  // == 8 (mod 64): both ds_read_b128 patterns on the image are conflict-free
   const int64_t prow0 = static_cast<int64_t>(b) * K;  // first projection row of this patch
+  attn_shift_pair_rows<PLANES>(e, esc, ctx_of_row, b, K);
   const float scale_t = 0.57735026918962576f;         // 3^-1/2   (diffab_pytorch.py:387, :439)
 
   // Per-wave LDS scratch behind the logits image.  Every global load below is issued in full 128-byte lines (consecutive

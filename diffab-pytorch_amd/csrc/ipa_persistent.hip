@@ -34,6 +34,7 @@ struct ModuleArgs {
   float* feat;               // [B K][1024] workspace
   const float* pair;         // fp16 planes of the pair embedding (launch_pair_split)
   const float* esc;          // {s, 1 / s} per pair row
+  const int* ctx_of_row;     // shared contexts: [B] context of each patch's pair rows (null: the identity)
   float* vpl;                // value planes of the P x V product (proj_frames_h3_tile.h), null: phase 3 from the fp32 value columns
   float* vsc;                // their scales
   const float* R;            // [B K][9]
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
       for (int tile = 0; tile < NTILE; ++tile) {
         ipa_attn_tile<8, (KRES > 128), true, false, 8, VPL>(lds, b, tile, static_cast<unsigned>((b * a.NL + l) * NTILE + tile), a.proj, a.pair, a.R,
                                                             a.t, small, small + 512, a.feat, K / 128, a.stamps, a.esc, nullptr, nullptr,
-                                                            reinterpret_cast<const f32x4*>(a.vpl), a.vsc);
+                                                            reinterpret_cast<const f32x4*>(a.vpl), a.vsc, a.ctx_of_row);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // the next tile's phase 1 overwrites the image; the last tile's feature rows are complete
       }
@@ -175,12 +176,13 @@ bool ipa_module_persistent_supported(const diffab_dims* d) {
   return fast_path_supported(d) && (d->K == 128 || d->K == 256) && d->NL >= 1 && dense_h3_enabled();  // (the kernel holds the fp16 tiles only)
 }
 
-// planes: d->NL x ipa_layer_planes_bytes() (ipa_layer_split_weights); pair_planes: launch_pair_split(); xa in, result in (NL odd ? xb : xa)
+// planes: d->NL x ipa_layer_planes_bytes() (ipa_layer_split_weights); pair_planes: launch_pair_split() of n_ctx patches (0: d->B), state
+// patch b reading those of ctx_of_row[b] (null: b); xa in, result in (NL odd ? xb : xa)
 // emb_X (optional, with emb and heads): the embedding MLP's input rows - the launch then also runs the embedding MLP (-> xa) and the three
 // heads (module output -> heads->Y[]) of every patch
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X, const MlpChainSet* emb,
-                                 const MlpChainSet* heads) {
+                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx) {
   DIFFAB_REQUIRE(ipa_module_persistent_supported(d) && xa && xb && R && t && ws && planes && pair_planes, DIFFAB_ERR_ARG,
                  "ipa_module_persistent: unsupported operands");
   const size_t rows = static_cast<size_t>(d->B) * d->K;
@@ -190,7 +192,8 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
   a.proj = ws;
   a.feat = ws + rows * ANP;
   a.pair = pair_planes + 64;
-  a.esc = pair_row_scales(d, pair_planes);
+  a.esc = pair_row_scales(d, pair_planes, n_ctx);
+  a.ctx_of_row = ctx_of_row;
   const bool vpl_on = value_planes_enabled();
   if (vpl_on) ipa_ws_value_planes(d, ws, &a.vpl, &a.vsc);
   a.R = R;

@@ -117,6 +117,7 @@ SYMBOLS = {
     "diffab_philox_fill": (C.c_int, [_u64, _i64, _i32, _i32, _i32, _i32, C.c_int, _fp, _fp]),
     "diffab_denoise_workspace_bytes": (_sz, [_PD]),
     "diffab_sample_workspace_bytes": (_sz, [_PD]),
+    "diffab_sample_shared_workspace_bytes": (_sz, [_PD, _i32]),
     "diffab_ipa_layer_fwd": (C.c_int, [_PD, C.POINTER(IpaLayerWeights), _fp, _fp, _fp, _fp, _fp, _fp, _sz, _u32, _fp]),
     "diffab_denoise_step_fwd": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                           _fp, _sz, _u32, _fp]),
@@ -163,6 +164,10 @@ SYMBOLS = {
     "diffab_reverse_update": (C.c_int, [_PS, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "diffab_sample_loop": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _fp, _u64, _i64, _i32,
                                      _i32, _fp, _sz, _u32, _fp]),
+    # (d, w, sched, tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row (host int32[B]), gen_mask, seed, first_patch, t_start, t_stop,
+    #  ws, ws_bytes, flags, stream)
+    "diffab_sample_loop_shared": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                            _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp]),
     "diffab_sample_init": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _fp]),
 }
 

@@ -850,7 +850,8 @@ class DiffAb(_ModuleBase):
                distmat=None, atom_mask=None, chain_idx=None, residue_idx=None, generate_structure: bool = True,
                generate_sequence: bool = True, seed: Optional[int] = None, first_patch: int = 0, t_start: Optional[int] = None,
                t_stop: int = 0, init: bool = True, flags: int = 0, graph: Optional[bool] = None,
-               skip_unused_rows: bool = False) -> Dict[str, torch.Tensor]:
+               skip_unused_rows: bool = False, num_samples: int = 1,
+               context_index: Optional[torch.LongTensor] = None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -867,9 +868,56 @@ class DiffAb(_ModuleBase):
         chain of ~45 dependent kernels on 8-work-group grids (1.45 ms), not 45 launch overheads.
         ``skip_unused_rows=True``: a step's outputs are used for generated residues only, so the LAST layer's attention runs only for the
         16-row tiles that contain one (`DIFFAB_FLAG_SKIP_UNUSED_ROWS`): bitwise the same samples, less work when few residues are
-        generated (one CDR: 5-7 of the 8 row tiles of the last layer are skipped)."""
+        generated (one CDR: 5-7 of the 8 row tiles of the last layer are skipped).
+
+        Many designs per patch from one shared context:
+        ``num_samples=N``: every per-patch input (seq_idx, xyz, orientations, generation_mask; B rows) is replicated N times on the
+        device and the result has B*N rows, row b*N + r being design r of patch b.  The contexts stay B rows - given, or computed by ONE
+        encode_context call over the B patches - and the sampler reads them through a row -> context map
+        (`diffab_sample_loop_shared`): no (B*N, K, K, C) copy of the pair context and no per-replica fp16 planes.  Bitwise the result
+        of num_samples=1 on the repeat_interleave(N, dim=0) of every per-patch input with the same seed and first_patch (the replicas
+        differ by their noise keys, patch id first_patch + b*N + r).
+        ``context_index`` (R,) is the general form: res_context_emb / pair_context_emb hold n_ctx contexts (required), the state
+        inputs have R rows and row i is denoised against context context_index[i].  A rank that owns output rows [lo, hi) of a
+        num_samples run passes the state rows lo..hi-1, context_index = arange(lo, hi) // N and first_patch = lo.
+        Both together, num_samples < 1, lengths that do not match and indices outside [0, n_ctx) raise ValueError before any
+        device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
+        if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+            raise ValueError(f"sample(): num_samples must be an int >= 1, got {num_samples!r}")
+        if num_samples > 1 and context_index is not None:
+            raise ValueError("sample(): give num_samples or context_index, not both (context_index is the general form)")
+        n_rows, K_ = seq_idx.shape
+        ctx_map = None  # host int32 (rows,): the context of every state row (None: one context per row)
+        if num_samples > 1 or context_index is not None:
+            for name, v in (("xyz", xyz), ("orientations", orientations), ("generation_mask", generation_mask)):
+                if v.shape[0] != n_rows or v.shape[1] != K_:
+                    raise ValueError(f"sample(): {name} is {tuple(v.shape)}, seq_idx is {(n_rows, K_)}")
+            dd = self.denoiser.dims
+            for name, v, tail in (("res_context_emb", res_context_emb, (K_, dd["D"])), ("pair_context_emb", pair_context_emb, (K_, K_, dd["C"]))):
+                if v is not None and tuple(v.shape[1:]) != tail:
+                    raise ValueError(f"sample(): {name} is {tuple(v.shape)}, expected (contexts, {', '.join(map(str, tail))})")
+        if context_index is not None:
+            if res_context_emb is None or pair_context_emb is None:
+                raise ValueError("sample(): context_index needs res_context_emb and pair_context_emb (the n_ctx shared contexts)")
+            ci = torch.as_tensor(context_index)
+            n_ctx = res_context_emb.shape[0]
+            if pair_context_emb.shape[0] != n_ctx:
+                raise ValueError(f"sample(): res_context_emb has {n_ctx} contexts, pair_context_emb {pair_context_emb.shape[0]}")
+            if ci.dim() != 1 or ci.numel() != n_rows or ci.is_floating_point() or ci.is_complex():
+                raise ValueError(f"sample(): context_index must be an integer vector of length {n_rows} (the state rows), "
+                                 f"got shape {tuple(ci.shape)} {ci.dtype}")
+            ci = ci.detach().to("cpu", torch.int64)
+            if n_rows and (int(ci.min()) < 0 or int(ci.max()) >= n_ctx):
+                raise ValueError(f"sample(): context_index entries must lie in [0, {n_ctx})")
+            ctx_map = ci.to(torch.int32)
+        elif num_samples > 1:
+            for name, v in (("res_context_emb", res_context_emb), ("pair_context_emb", pair_context_emb)):
+                if v is not None and v.shape[0] != n_rows:
+                    raise ValueError(f"sample(): with num_samples the contexts are per patch: {name} has {v.shape[0]} rows, "
+                                     f"seq_idx has {n_rows}")
+            ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
         if res_context_emb is None or pair_context_emb is None:
             need = {"atom_mask": atom_mask, "chain_idx": chain_idx}
             missing = [k for k, v in need.items() if v is None]
@@ -892,10 +940,14 @@ class DiffAb(_ModuleBase):
                                                                     generation_mask, residue_mask, generate_structure, generate_sequence)
         lib = _hip.lib()
         out_dev = seq_idx.device
-        seq = _hip.dev_i64(seq_idx).clone()
-        x = _hip.dev_f32(xyz[:, :, CA_IDX] if xyz.dim() == 4 else xyz).clone()
-        O = _hip.dev_f32(orientations).clone()
+        seq = _hip.dev_i64(seq_idx)
+        x = _hip.dev_f32(xyz[:, :, CA_IDX] if xyz.dim() == 4 else xyz)
+        O = _hip.dev_f32(orientations)
         rc, pc, gm = _hip.dev_f32(res_context_emb), _hip.dev_f32(pair_context_emb), _hip.dev_mask(generation_mask)
+        if num_samples > 1:  # the state of every design: the patch's rows, replicated on the device (the contexts are not)
+            seq, x, O, gm = (v.repeat_interleave(num_samples, dim=0) for v in (seq, x, O, gm))
+        else:
+            seq, x, O = seq.clone(), x.clone(), O.clone()
         B, K = seq.shape
         seed = _so3._draw_seed() if seed is None else int(seed)
         t_start = self.T if t_start is None else int(t_start)
@@ -903,7 +955,12 @@ class DiffAb(_ModuleBase):
         w = self.denoiser.hip_weights()
         sd = self._sched_on_device()
         tab = self._reverse_so3().struct()
-        ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(dims)))
+        if ctx_map is None:
+            ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(dims)))
+        else:
+            n_ctx = rc.shape[0]
+            ws = _hip.workspace(lib.diffab_sample_shared_workspace_bytes(C.byref(dims), n_ctx))
+            ctx_host = (C.c_int32 * B)(*ctx_map.tolist())
         if graph:
             flags |= _hip.FLAG_GRAPH_SAMPLER
         if skip_unused_rows:
@@ -911,7 +968,13 @@ class DiffAb(_ModuleBase):
         if init:
             _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T,
                                               _hip.stream_ptr()), "diffab_sample_init")
-        _hip.check(lib.diffab_sample_loop(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
-                                          _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), _hip.ptr(gm), seed, first_patch, t_start, t_stop,
-                                          _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()), "diffab_sample_loop")
+        if ctx_map is None:
+            _hip.check(lib.diffab_sample_loop(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                              _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), _hip.ptr(gm), seed, first_patch, t_start, t_stop,
+                                              _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()), "diffab_sample_loop")
+        else:
+            _hip.check(lib.diffab_sample_loop_shared(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
+                                                     _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), n_ctx, ctx_host, _hip.ptr(gm), seed,
+                                                     first_patch, t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()),
+                       "diffab_sample_loop_shared")
         return {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}

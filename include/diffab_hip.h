@@ -291,6 +291,9 @@ int diffab_philox_fill(uint64_t seed, int64_t first_patch, int32_t B, int32_t K,
 /* ---- IPA / denoiser --------------------------------------------------------- */
 size_t diffab_denoise_workspace_bytes(const diffab_dims* d);
 size_t diffab_sample_workspace_bytes(const diffab_dims* d); /* for diffab_sample_loop */
+/* for diffab_sample_loop_shared with a context map: the fp16 pair planes and their row scales are sized by n_ctx, not d->B, plus the
+ * device copy of the map and a (B,K,D) residue-context buffer.  0 (and diffab_last_error) for bad dims or n_ctx < 1. */
+size_t diffab_sample_shared_workspace_bytes(const diffab_dims* d, int32_t n_ctx);
 /* diffab_pytorch.py:389-465  one InvariantPointAttentionLayer.forward */
 int diffab_ipa_layer_fwd(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x /* (B,K,D) */,
                          const float* e /* (B,K,K,C) */, const float* R /* (B,K,3,3) */, const float* t /* (B,K,3) */,
@@ -484,6 +487,20 @@ int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, c
                        const diffab_igso3* rev_tab, int64_t* seq, float* x, float* O, const float* res_ctx,
                        const float* pair_ctx, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
                        int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
+/* diffab_sample_loop with contexts shared between state rows (many designs of one patch from one context): res_ctx (n_ctx,K,D) and
+ * pair_ctx (n_ctx,K,K,C) hold n_ctx contexts, and state row b (seq/x/O/gen_mask are (d->B,K,...)) is denoised against context
+ * ctx_of_row[b].  ctx_of_row is a HOST array of d->B entries, each in [0, n_ctx) (else DIFFAB_ERR_ARG, nothing enqueued); it is copied
+ * to the workspace once per call (the call returns with the host array no longer needed).  The pair context is read through the map by
+ * every attention form (planes, DIFFAB_FLAG_PAIR_F32, DIFFAB_FLAG_FORCE_GENERIC, the patch-resident module, graph replay, skipped row
+ * tiles) and never expanded to B rows; its fp16 planes are built once per context.  Noise stays keyed by (seed, first_patch + b,
+ * residue, t): the result is bitwise that of diffab_sample_loop on the contexts replicated row by row.  workspace:
+ * diffab_sample_shared_workspace_bytes(d, n_ctx).  ctx_of_row NULL: the identity (n_ctx must be d->B; diffab_sample_workspace_bytes(d)
+ * suffices) - diffab_sample_loop is exactly that call. */
+int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s,
+                              const diffab_igso3* rev_tab, int64_t* seq, float* x, float* O, const float* res_ctx,
+                              const float* pair_ctx, int32_t n_ctx, const int32_t* ctx_of_row, const uint8_t* gen_mask,
+                              uint64_t seed, int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace,
+                              size_t workspace_bytes, uint32_t flags, void* stream);
 /* Initial state at t = T on generated residues: x ~ N(0,I), O ~ uniform SO(3), s ~ U{0..19} (Philox, step = T+1). */
 int diffab_sample_init(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch,
                        int32_t B, int32_t K, int32_t T, void* stream);
