@@ -706,6 +706,12 @@ int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weight
                  "sample_loop: reverse IGSO3 table must have T+1 rows");
   DIFFAB_REQUIRE(seq && x && O && res_ctx && pair_ctx && gen_mask && workspace, DIFFAB_ERR_ARG, "sample_loop: null pointer");
   DIFFAB_REQUIRE(t_start <= s->T && t_stop >= 0 && t_stop <= t_start, DIFFAB_ERR_ARG, "sample_loop: need T >= t_start >= t_stop >= 0");
+  // design modes: the modality a KEEP bit names is never written by the update kernel (the only writer of the state in the loop); the
+  // bits mean nothing to the denoiser, which sees the state as it is
+  const uint32_t keep = flags & (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE);
+  DIFFAB_REQUIRE(keep != (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE), DIFFAB_ERR_ARG,
+                 "sample_loop: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to sample");
+  flags &= ~keep;
   // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
   // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
   const bool mapped = ctx_of_row != nullptr;
@@ -781,7 +787,7 @@ int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weight
       return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits);
+                                        t_dev, b0.vbuf, b0.logits, keep);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is

@@ -673,9 +673,10 @@ __global__ void angular_encoding_kernel(const float* __restrict__ x, int64_t n, 
 }
 
 // ------------------------------------------------------------------ reverse update
-__device__ inline void reverse_update_one(int64_t i, int t, float beta, float alpha, float omabs, int64_t* seq, float* x, float* O,
-                                          const float* eps_hat, const float* O0_hat, const float* post, int V, float zx, float zy,
-                                          float zz, float rx, float ry, float rz, float u_seq) {
+// (the design modes, DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE, run one of the two halves)
+__device__ inline void reverse_update_structure(int64_t i, int t, float beta, float alpha, float omabs, float* x, float* O,
+                                                const float* eps_hat, const float* O0_hat, float zx, float zy, float zz, float rx, float ry,
+                                                float rz) {
   const float c = beta / omabs;
   const float sa = sqrtf(alpha), sb = sqrtf(beta);
   const float zn[3] = {zx, zy, zz};
@@ -697,6 +698,12 @@ __device__ inline void reverse_update_one(int64_t i, int t, float beta, float al
   }
 #pragma unroll
   for (int k = 0; k < 9; ++k) O[i * 9 + k] = o[k];
+}
+
+__device__ inline void reverse_update_one(int64_t i, int t, float beta, float alpha, float omabs, int64_t* seq, float* x, float* O,
+                                          const float* eps_hat, const float* O0_hat, const float* post, int V, float zx, float zy,
+                                          float zz, float rx, float ry, float rz, float u_seq) {
+  reverse_update_structure(i, t, beta, alpha, omabs, x, O, eps_hat, O0_hat, zx, zy, zz, rx, ry, rz);
   seq[i] = categorical_draw(post + i * V, V, u_seq);
 }
 
@@ -715,16 +722,19 @@ __global__ void reverse_update_kernel(const float* __restrict__ beta, const floa
 // head_v / head_logits != nullptr (the folded sampler path): the heads' epilogue of the row - O0 = O_t exp(hat(v)) (diffab_pytorch.py:594-596)
 // and posterior = softmax(logits) (:555), what heads_finish_kernel computes for every row - is done here, for the generated rows only,
 // into O0_hat / post (read back by the same thread below; no __restrict__ on the two for that reason): one launch less per step.
+// keep (DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE, uniform per launch): the kept modality is never written and its share of the epilogue
+// and the draws is skipped; the other half runs exactly as with keep = 0.
 __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs,
                                              int t, const float* __restrict__ rev_sigmas, const float* __restrict__ rev_cdf, int n_bins,
                                              float thr, int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
                                              const float* __restrict__ eps_hat, float* O0_hat, float* post, const uint8_t* __restrict__ gm,
                                              uint64_t seed, int64_t first_patch, int B, int K, int V, const int* __restrict__ t_dev,
-                                             const float* __restrict__ head_v, const float* __restrict__ head_logits) {
+                                             const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   if (t_dev != nullptr) t = *t_dev;  // graph replay: the timestep lives in device memory (one captured step serves every t)
-  if (head_v != nullptr) {
+  const bool upd_struct = !(keep & DIFFAB_FLAG_KEEP_STRUCTURE), upd_seq = !(keep & DIFFAB_FLAG_KEEP_SEQUENCE);
+  if (head_v != nullptr && upd_struct) {
     float ex[9], o[9], res[9];
     so3_rotvec_to_matrix(head_v[i * 3], head_v[i * 3 + 1], head_v[i * 3 + 2], ex);
 #pragma unroll
@@ -732,6 +742,8 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
     mat3_mul(o, ex, res);
 #pragma unroll
     for (int k = 0; k < 9; ++k) O0_hat[i * 9 + k] = res[k];
+  }
+  if (head_v != nullptr && upd_seq) {
     float m = -INFINITY;
     for (int c = 0; c < V; ++c) m = fmaxf(m, head_logits[i * V + c]);
     float s = 0.f;
@@ -740,22 +752,32 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
     for (int c = 0; c < V; ++c) post[i * V + c] = expf(head_logits[i * V + c] - m) * inv;
   }
   const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K), st = static_cast<uint32_t>(t);
-  const f32x4 zt = philox_normal4(seed, patch, res, st, STREAM_TRANS);
-  f32x4 ax = philox_normal4(seed, patch, res, st, STREAM_AXIS);
-  const f32x4 ua = philox_uniform4(seed, patch, res, st, STREAM_ANGLE);
-  const f32x4 na = normals_from_uniforms(ua);  // .z is the Box-Muller normal of (u2,u3)
-  const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_SEQ);
-  const float theta = igso3_theta(rev_cdf, n_bins, rev_sigmas[t], thr, t, ua.x, ua.y, na.z);
-  normalize3(ax.x, ax.y, ax.z);
-  reverse_update_one(i, t, beta[t], alpha[t], omabs[t], seq, x, O, eps_hat, O0_hat, post, V, zt.x, zt.y, zt.z, ax.x * theta,
-                     ax.y * theta, ax.z * theta, us.x);
+  if (upd_struct) {
+    const f32x4 zt = philox_normal4(seed, patch, res, st, STREAM_TRANS);
+    f32x4 ax = philox_normal4(seed, patch, res, st, STREAM_AXIS);
+    const f32x4 ua = philox_uniform4(seed, patch, res, st, STREAM_ANGLE);
+    const f32x4 na = normals_from_uniforms(ua);  // .z is the Box-Muller normal of (u2,u3)
+    const float theta = igso3_theta(rev_cdf, n_bins, rev_sigmas[t], thr, t, ua.x, ua.y, na.z);
+    normalize3(ax.x, ax.y, ax.z);
+    reverse_update_structure(i, t, beta[t], alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z, ax.x * theta, ax.y * theta,
+                             ax.z * theta);
+  }
+  if (upd_seq) {
+    const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_SEQ);
+    seq[i] = categorical_draw(post + i * V, V, us.x);
+  }
 }
 
 __global__ void sample_init_kernel(int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O, const uint8_t* __restrict__ gm,
-                                   uint64_t seed, int64_t first_patch, int B, int K, int T) {
+                                   uint64_t seed, int64_t first_patch, int B, int K, int T, uint32_t keep) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K), st = static_cast<uint32_t>(T + 1);
+  if (!(keep & DIFFAB_FLAG_KEEP_SEQUENCE)) {
+    const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_INIT_S);
+    seq[i] = min(static_cast<int>(us.x * 20.0f), 19);
+  }
+  if (keep & DIFFAB_FLAG_KEEP_STRUCTURE) return;
   const f32x4 nx = philox_normal4(seed, patch, res, st, STREAM_INIT_X);
   x[i * 3 + 0] = nx.x; x[i * 3 + 1] = nx.y; x[i * 3 + 2] = nx.z;
   f32x4 q = philox_normal4(seed, patch, res, st, STREAM_INIT_O);
@@ -765,8 +787,45 @@ __global__ void sample_init_kernel(int64_t* __restrict__ seq, float* __restrict_
   o[0] = 1 - 2 * (b * b + c * c); o[1] = 2 * (a * b - c * w);     o[2] = 2 * (a * c + b * w);
   o[3] = 2 * (a * b + c * w);     o[4] = 1 - 2 * (a * a + c * c); o[5] = 2 * (b * c - a * w);
   o[6] = 2 * (a * c - b * w);     o[7] = 2 * (b * c + a * w);     o[8] = 1 - 2 * (a * a + b * b);
-  const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_INIT_S);
-  seq[i] = min(static_cast<int>(us.x * 20.0f), 19);
+}
+
+// Antibody optimisation: the native state of the generated residues forward-noised to step t, in place (diffusion.py:105-135 for the
+// sequence - seq_forward_prob_kernel mode 1 + categorical_draw -, coord_forward_kernel's x_t, orient_forward_kernel's O_t with the rotation
+// vector drawn as the reverse loop draws it, from row t of the forward table).  Philox streams STREAM_OPT_*, counter step = t.
+__global__ void sample_init_noised_kernel(const float* __restrict__ alpha_bar, const float* __restrict__ abs_, const float* __restrict__ omabs,
+                                          const float* __restrict__ fwd_sigmas, const float* __restrict__ fwd_cdf, int n_bins, float thr, int t,
+                                          int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
+                                          const uint8_t* __restrict__ gm, uint64_t seed, int64_t first_patch, int B, int K, uint32_t keep) {
+  const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+  if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
+  const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K), st = static_cast<uint32_t>(t);
+  if (!(keep & DIFFAB_FLAG_KEEP_SEQUENCE)) {
+    const float wk = alpha_bar[t], wn = 1.0f - wk;
+    const int64_t s0 = seq[i];
+    float p[kV];
+    for (int v = 0; v < kV; ++v) p[v] = seq_prob(v, s0, wk, wn, true);
+    const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_OPT_SEQ);
+    seq[i] = categorical_draw(p, kV, us.x);
+  }
+  if (keep & DIFFAB_FLAG_KEEP_STRUCTURE) return;
+  const float a = abs_[t], b = omabs[t];
+  const f32x4 eps = philox_normal4(seed, patch, res, st, STREAM_OPT_TRANS);
+  const float e[3] = {eps.x, eps.y, eps.z};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) x[i * 3 + c] = a * x[i * 3 + c] + b * e[c];
+  f32x4 ax = philox_normal4(seed, patch, res, st, STREAM_OPT_AXIS);
+  const f32x4 ua = philox_uniform4(seed, patch, res, st, STREAM_OPT_ANGLE);
+  const f32x4 na = normals_from_uniforms(ua);
+  const float theta = igso3_theta(fwd_cdf, n_bins, fwd_sigmas[t], thr, t, ua.x, ua.y, na.z);
+  normalize3(ax.x, ax.y, ax.z);
+  float r[9], mean[9], noise[9], o[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) r[k] = O[i * 9 + k];
+  so3_scale(r, a, mean);
+  so3_rotvec_to_matrix(ax.x * theta, ax.y * theta, ax.z * theta, noise);
+  mat3_mul(mean, noise, o);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) O[i * 9 + k] = o[k];
 }
 
 __global__ void fill_beta_kernel(const float* __restrict__ beta, int t, int B, float* __restrict__ out, const int* __restrict__ t_dev) {
@@ -781,11 +840,11 @@ __global__ void dec_int_kernel(int* __restrict__ p) { *p -= 1; }
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
-                                 const float* head_logits) {
+                                 const float* head_logits, uint32_t keep) {
   const int64_t n = static_cast<int64_t>(B) * K;
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
@@ -1160,12 +1219,40 @@ int diffab_reverse_update(const diffab_sched* s, int32_t t, int64_t* seq, float*
 
 int diffab_sample_init(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K,
                        int32_t T, void* stream) {
+  return diffab_sample_init_ex(seq, x, O, gen_mask, seed, first_patch, B, K, T, 0u, stream);
+}
+
+int diffab_sample_init_ex(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
+                          int32_t K, int32_t T, uint32_t flags, void* stream) {
   StreamOrder order_(stream);
   DIFFAB_REQUIRE(seq && x && O && gen_mask && B >= 0 && K > 0 && T > 0, DIFFAB_ERR_ARG, "sample_init: bad argument");
+  const uint32_t keep = flags & (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE);
+  DIFFAB_REQUIRE(keep != (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE), DIFFAB_ERR_ARG,
+                 "sample_init: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to sample");
   const int64_t n = static_cast<int64_t>(B) * K;
   if (n == 0) return DIFFAB_OK;
   hipLaunchKernelGGL(sample_init_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), seq, x, O, gen_mask, seed, first_patch, B,
-                     K, T);
+                     K, T, keep);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+
+int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O, const uint8_t* gen_mask,
+                              uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t, uint32_t flags, void* stream) {
+  StreamOrder order_(stream);
+  if (int rc = check_sched(s)) return rc;
+  DIFFAB_REQUIRE(seq && x && O && gen_mask && B >= 0 && K > 0, DIFFAB_ERR_ARG, "sample_init_noised: bad argument");
+  DIFFAB_REQUIRE(t >= 1 && t <= s->T, DIFFAB_ERR_ARG, "sample_init_noised: t = %d outside [1, T = %d]", t, s->T);
+  DIFFAB_REQUIRE(fwd_tab && fwd_tab->sigmas && fwd_tab->cdf && fwd_tab->n_bins > 0 && fwd_tab->n_sigmas >= s->T + 1, DIFFAB_ERR_ARG,
+                 "sample_init_noised: forward IGSO3 table must have T+1 rows");
+  const uint32_t keep = flags & (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE);
+  DIFFAB_REQUIRE(keep != (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE), DIFFAB_ERR_ARG,
+                 "sample_init_noised: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to noise");
+  const int64_t n = static_cast<int64_t>(B) * K;
+  if (n == 0) return DIFFAB_OK;
+  hipLaunchKernelGGL(sample_init_noised_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), s->alpha_bar, s->alpha_bar_sqrt,
+                     s->one_minus_alpha_bar_sqrt, fwd_tab->sigmas, fwd_tab->cdf, fwd_tab->n_bins, fwd_tab->sigma_threshold, t, seq, x, O,
+                     gen_mask, seed, first_patch, B, K, keep);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

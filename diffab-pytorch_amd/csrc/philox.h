@@ -16,6 +16,11 @@ enum PhiloxStream : uint32_t {
   STREAM_INIT_X = 4,
   STREAM_INIT_O = 5,
   STREAM_INIT_S = 6,
+  // forward noise of the native state to step t_opt (diffab_sample_init_noised, antibody optimisation); counter step = t_opt
+  STREAM_OPT_SEQ = 7,    // categorical draw of s_t ~ q(s_t | s_0)
+  STREAM_OPT_TRANS = 8,  // translation noise eps
+  STREAM_OPT_AXIS = 9,   // rotation axis
+  STREAM_OPT_ANGLE = 10, // rotation angle (u_bin, u_in, z via Box-Muller of lanes 2,3), as STREAM_ANGLE
 };
 
 struct u32x4 {

@@ -25,6 +25,8 @@ FLAG_GRAPH_SAMPLER = 16  # sample_loop: one captured step replayed as a hipGraph
 FLAG_PERSISTENT_MODULE = 512  # MFMA path, K = 128 / 256, pair planes: the IPA module as one patch-resident launch (bitwise the multi-launch result)
 FLAG_MULTI_LAUNCH = 1024  # sample_loop: never choose the patch-resident module launch (bitwise the same samples either way)
 FLAG_SKIP_UNUSED_ROWS = 256  # sample_loop: the last layer's attention only for row tiles with a generated residue (same trajectory)
+FLAG_KEEP_STRUCTURE = 2048  # design mode: the sampler never writes x and O (fixed-backbone sequence design)
+FLAG_KEEP_SEQUENCE = 4096  # design mode: the sampler never writes seq (structure prediction)
 
 
 class HipUnavailable(RuntimeError):
@@ -169,6 +171,10 @@ SYMBOLS = {
     "diffab_sample_loop_shared": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
                                             _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp]),
     "diffab_sample_init": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _fp]),
+    # (seq, x, O, gen_mask, seed, first_patch, B, K, T, flags, stream)
+    "diffab_sample_init_ex": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
+    # (sched, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, stream)
+    "diffab_sample_init_noised": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
 }
 
 _lib: Optional[C.CDLL] = None

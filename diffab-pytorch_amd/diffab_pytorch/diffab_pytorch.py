@@ -41,6 +41,12 @@ except ImportError:  # pragma: no cover - this image has no pytorch_lightning
 
 
 CA_IDX = 1  # protstruc.general.ATOM.CA (reference diffab_pytorch.py:9, :820)
+# DiffAb.sample(mode=...): (generate_structure, generate_sequence) of encode_context, and the modality the sampler keeps as given
+SAMPLE_MODES = {
+    "codesign": (True, True, 0),
+    "fixed_backbone": (False, True, _hip.FLAG_KEEP_STRUCTURE),
+    "structure": (True, False, _hip.FLAG_KEEP_SEQUENCE),
+}
 
 
 def _named(module: nn.Module) -> Dict[str, torch.Tensor]:
@@ -851,7 +857,8 @@ class DiffAb(_ModuleBase):
                generate_sequence: bool = True, seed: Optional[int] = None, first_patch: int = 0, t_start: Optional[int] = None,
                t_stop: int = 0, init: bool = True, flags: int = 0, graph: Optional[bool] = None,
                skip_unused_rows: bool = False, num_samples: int = 1,
-               context_index: Optional[torch.LongTensor] = None) -> Dict[str, torch.Tensor]:
+               context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
+               optimize_from: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -881,9 +888,39 @@ class DiffAb(_ModuleBase):
         inputs have R rows and row i is denoised against context context_index[i].  A rank that owns output rows [lo, hi) of a
         num_samples run passes the state rows lo..hi-1, context_index = arange(lo, hi) // N and first_patch = lo.
         Both together, num_samples < 1, lengths that do not match and indices outside [0, n_ctx) raise ValueError before any
-        device work."""
+        device work.
+
+        Design modes (Luo et al.'s three tasks; every mode combines with num_samples, context_index, graph and the launch flags):
+        ``mode=None`` is the behaviour above (generate_structure / generate_sequence as given, all three modalities diffused);
+        ``"codesign"`` is the same with both flags true (bitwise mode=None); ``"fixed_backbone"`` encodes the context with the generated
+        residues' structure visible (encode_context(generate_structure=False)) and diffuses only the sequence - x and O of the generated
+        residues are returned exactly as given (`DIFFAB_FLAG_KEEP_STRUCTURE`); ``"structure"`` encodes it with their sequence visible
+        and diffuses only x and O - seq is returned as given (`DIFFAB_FLAG_KEEP_SEQUENCE`).  The diffused modality sees the same Philox
+        draws as in co-design.  A mode sets generate_structure / generate_sequence itself: giving either as False with a mode raises.
+        ``optimize_from=t`` (antibody optimisation): the given state of the generated residues is the native; it is forward-noised to
+        step t on the device (`diffab_sample_init_noised`, Philox keyed like the loop, so sharding and num_samples behave as above)
+        instead of re-initialised, and the loop runs t .. t_stop+1 (a few steps instead of T).  The kept modality of a mode is not
+        noised.  An unknown mode, a mode with generate_structure / generate_sequence False, optimize_from outside [1, T], optimize_from
+        with init=False and a t_start other than optimize_from raise ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
+        keep = 0  # DIFFAB_FLAG_KEEP_* of the mode
+        if mode is not None:
+            if not isinstance(mode, str) or mode not in SAMPLE_MODES:
+                raise ValueError(f"sample(): unknown mode {mode!r}; expected None or one of {sorted(SAMPLE_MODES)}")
+            if not generate_structure or not generate_sequence:
+                raise ValueError(f"sample(): mode={mode!r} sets generate_structure / generate_sequence itself; leave them at their "
+                                 "defaults")
+            generate_structure, generate_sequence, keep = SAMPLE_MODES[mode]
+        if optimize_from is not None:
+            if isinstance(optimize_from, bool) or not isinstance(optimize_from, int) or not 1 <= optimize_from <= self.T:
+                raise ValueError(f"sample(): optimize_from must be an int in [1, T = {self.T}], got {optimize_from!r}")
+            if not init:
+                raise ValueError("sample(): optimize_from noises the given native state itself; it cannot be combined with init=False")
+            if t_start is not None and int(t_start) != optimize_from:
+                raise ValueError(f"sample(): t_start = {t_start} disagrees with optimize_from = {optimize_from} (the loop starts at "
+                                 "optimize_from; leave t_start out)")
+            t_start = optimize_from
         if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
             raise ValueError(f"sample(): num_samples must be an int >= 1, got {num_samples!r}")
         if num_samples > 1 and context_index is not None:
@@ -965,7 +1002,16 @@ class DiffAb(_ModuleBase):
             flags |= _hip.FLAG_GRAPH_SAMPLER
         if skip_unused_rows:
             flags |= _hip.FLAG_SKIP_UNUSED_ROWS
-        if init:
+        flags |= keep
+        if init and optimize_from is not None:
+            fwd_tab = self.orientation_diffuser.so3.struct()
+            _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd_tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm),
+                                                     seed, first_patch, B, K, optimize_from, keep, _hip.stream_ptr()),
+                       "diffab_sample_init_noised")
+        elif init and keep:
+            _hip.check(lib.diffab_sample_init_ex(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T, keep,
+                                                 _hip.stream_ptr()), "diffab_sample_init_ex")
+        elif init:
             _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T,
                                               _hip.stream_ptr()), "diffab_sample_init")
         if ctx_map is None:

@@ -102,6 +102,12 @@ extern "C" {
                                          next).  Bitwise the same trajectory; the work skipped depends on the mask - with one CDR-like
                                          segment per patch 5-7 of the 8 row tiles of the last layer - so it is opt-in and bench.py's
                                          headline keeps it off (reported separately). */
+/* Design modes of the reverse loop (diffab_sample_loop / _shared, diffab_sample_init_ex, diffab_sample_init_noised).  With one of these
+   bits set the sampler never writes that modality of the state; the other is updated exactly as without the bit, from the same Philox
+   draws.  The branch is uniform per launch, on every launch form of the loop.  Both bits together: DIFFAB_ERR_ARG, nothing enqueued. */
+#define DIFFAB_FLAG_KEEP_STRUCTURE 2048u /* fixed-backbone sequence design: x and O of the generated residues stay as given (the
+                                            heads' O0 epilogue is skipped); only seq is diffused */
+#define DIFFAB_FLAG_KEEP_SEQUENCE 4096u /* structure prediction: seq of the generated residues stays as given; only x and O are diffused */
 
 /* Model and batch geometry.  Reference ctor: diffab_pytorch.py:629-647. */
 typedef struct {
@@ -482,7 +488,9 @@ int diffab_reverse_update(const diffab_sched* s, int32_t t, int64_t* seq, float*
 /* The whole reverse trajectory t = t_start .. t_stop+1 (normally T .. 1) for B patches, all launches
  * enqueued on `stream` with no host synchronisation: denoise step + Philox noise + IGSO3 draw (table
  * over sqrt(beta)) + update.  State (seq, x, O) is updated in place.  Noise is keyed by
- * (seed, first_patch + b, residue, t), so any sharding of a batch over ranks gives identical samples. */
+ * (seed, first_patch + b, residue, t), so any sharding of a batch over ranks gives identical samples.  The design-mode bits
+ * DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE restrict the update to the other modality (fixed-backbone sequence design, structure
+ * prediction); antibody optimisation starts the loop at t_start = t from diffab_sample_init_noised. */
 int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s,
                        const diffab_igso3* rev_tab, int64_t* seq, float* x, float* O, const float* res_ctx,
                        const float* pair_ctx, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
@@ -504,6 +512,23 @@ int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weight
 /* Initial state at t = T on generated residues: x ~ N(0,I), O ~ uniform SO(3), s ~ U{0..19} (Philox, step = T+1). */
 int diffab_sample_init(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch,
                        int32_t B, int32_t K, int32_t T, void* stream);
+/* diffab_sample_init with the design-mode bits of `flags`: DIFFAB_FLAG_KEEP_STRUCTURE leaves x and O, DIFFAB_FLAG_KEEP_SEQUENCE leaves
+ * seq as given (other bits are ignored).  flags without either bit: bitwise diffab_sample_init. */
+int diffab_sample_init_ex(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch,
+                          int32_t B, int32_t K, int32_t T, uint32_t flags, void* stream);
+/* Starting state of antibody optimisation: the given (native) state of the generated residues is forward-noised to step t, in place
+ * (reference forward process, diffusion.py:105-135, 199-236, 262-294), with Philox noise keyed by (seed, first_patch + b, residue, t) on
+ * its own streams (philox.h STREAM_OPT_*), so sharding and replicated rows behave as in the reverse loop:
+ *   x_t = sqrt(abar_t) x_0 + sqrt(1 - abar_t) eps,
+ *   O_t = scale(O_0, sqrt(abar_t)) exp(w), w drawn from row t of fwd_tab (the IGSO3 table over sigma_t = sqrt(1 - abar_t),
+ *         T+1 rows) by the reverse loop's rule: inverse CDF of the histogram below the table's threshold, the Gaussian angle above,
+ *   s_t ~ q(s_t | s_0) = abar_t onehot(s_0) + (1 - abar_t) / 21, by inverse CDF.
+ * Build-defined: every residue's angle is an independent inverse-CDF draw (the reference's forward noise draws a patch's histogram
+ * bins without replacement, so3.py:78), as in the reverse loop.  Context residues are never written; DIFFAB_FLAG_KEEP_STRUCTURE /
+ * _SEQUENCE leave that modality un-noised.  DIFFAB_ERR_ARG for t outside [1, T], a fwd_tab with fewer than T+1 rows, or both bits. */
+int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
+                              const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t,
+                              uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,104 @@
+"""CPU: the host side of the sampler's design modes (DiffAb.sample(mode=..., optimize_from=...)) - the C-ABI flags and entries, and the
+argument checks that happen before any library call."""
+import ctypes
+import os
+import re
+import types
+
+import pytest
+import torch
+
+from conftest import REPO
+from diffab_pytorch import DiffAb, _hip, synthetic as syn
+from diffab_pytorch.diffab_pytorch import SAMPLE_MODES, Denoiser
+
+
+def header_defines():
+    src = open(os.path.join(REPO, "include", "diffab_hip.h")).read()
+    return {k: int(v) for k, v in re.findall(r"#define\s+(DIFFAB_FLAG_\w+)\s+(\d+)u", src)}
+
+
+def test_flags_match_the_header():
+    h = header_defines()
+    assert h["DIFFAB_FLAG_KEEP_STRUCTURE"] == _hip.FLAG_KEEP_STRUCTURE == 2048
+    assert h["DIFFAB_FLAG_KEEP_SEQUENCE"] == _hip.FLAG_KEEP_SEQUENCE == 4096
+    # bits 2, 4 and 8 are retired; every flag is its own bit
+    values = list(h.values())
+    assert len(set(values)) == len(values) and all(v & (v - 1) == 0 for v in values)
+    assert not {2, 4, 8} & set(values)
+
+
+def test_library_exports_the_new_entries():
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    for name in ("diffab_sample_init_ex", "diffab_sample_init_noised"):
+        assert hasattr(lib, name), name
+        assert name in _hip.SYMBOLS, name
+    assert len(_hip.SYMBOLS["diffab_sample_init_ex"][1]) == 11
+    assert len(_hip.SYMBOLS["diffab_sample_init_noised"][1]) == 13
+
+
+def test_mode_table():
+    assert SAMPLE_MODES["codesign"] == (True, True, 0)
+    assert SAMPLE_MODES["fixed_backbone"] == (False, True, _hip.FLAG_KEEP_STRUCTURE)
+    assert SAMPLE_MODES["structure"] == (True, False, _hip.FLAG_KEEP_SEQUENCE)
+
+
+@pytest.fixture(scope="module")
+def model():
+    """DiffAb.sample bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device): every check
+    below must fire before sample() touches anything else - the library above all."""
+    d = dict(syn.BENCH_DIMS, NL=1)
+    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], 21)
+    stub = types.SimpleNamespace(denoiser=den, T=10)
+    stub.sample = types.MethodType(DiffAb.sample, stub)
+    return stub
+
+
+def inputs(B=2, K=16, D=128, Cp=64):
+    gm = torch.zeros(B, K, dtype=torch.bool)
+    gm[:, 3:8] = True
+    return dict(seq_idx=torch.zeros(B, K, dtype=torch.long), xyz=torch.zeros(B, K, 3), orientations=torch.eye(3).expand(B, K, 3, 3).clone(),
+                generation_mask=gm, res_context_emb=torch.zeros(B, K, D), pair_context_emb=torch.zeros(B, K, K, Cp))
+
+
+def call(model, **kw):
+    inp = inputs()
+    return model.sample(inp.pop("seq_idx"), inp.pop("xyz"), inp.pop("orientations"), seed=1, **inp, **kw)
+
+
+@pytest.mark.parametrize("mode", ["co-design", "Structure", "", 3])
+def test_unknown_mode_is_rejected(model, mode):
+    with pytest.raises(ValueError, match="unknown mode"):
+        call(model, mode=mode)
+
+
+@pytest.mark.parametrize("mode", sorted(SAMPLE_MODES))
+@pytest.mark.parametrize("kw", [dict(generate_structure=False), dict(generate_sequence=False),
+                                dict(generate_structure=False, generate_sequence=False)])
+def test_mode_with_generate_flags_is_rejected(model, mode, kw):
+    with pytest.raises(ValueError, match="sets generate_structure"):
+        call(model, mode=mode, **kw)
+
+
+@pytest.mark.parametrize("t", [0, -1, 11, 100, True, 2.0])
+def test_optimize_from_outside_the_schedule_is_rejected(model, t):
+    with pytest.raises(ValueError, match=r"optimize_from must be an int in \[1, T = 10\]"):
+        call(model, optimize_from=t)
+
+
+@pytest.mark.parametrize("mode", [None, "fixed_backbone"])
+def test_optimize_from_with_init_false_is_rejected(model, mode):
+    with pytest.raises(ValueError, match="init=False"):
+        call(model, optimize_from=4, init=False, mode=mode)
+
+
+@pytest.mark.parametrize("t_start", [10, 3, 0])
+def test_t_start_that_disagrees_with_optimize_from_is_rejected(model, t_start):
+    with pytest.raises(ValueError, match="disagrees with optimize_from"):
+        call(model, optimize_from=4, t_start=t_start)
+
+
+def test_mode_checks_come_before_the_shared_context_checks(model):
+    # the design-mode checks fire first, whatever else is wrong with the call
+    with pytest.raises(ValueError, match="unknown mode"):
+        call(model, mode="bogus", num_samples=0)
