@@ -463,10 +463,7 @@ int diffab_debug_set_module_stamps(void* device_buffer) {
   return DIFFAB_OK;
 }
 
-int diffab_debug_set_attn_variant(int32_t v) {
-  set_attn_variant(v);
-  return DIFFAB_OK;
-}
+int diffab_debug_set_attn_variant(int32_t v) { return set_attn_variant(v); }
 
 int diffab_debug_set_attn_stamps(void* device_buffer) {
   set_attn_stamps(device_buffer);

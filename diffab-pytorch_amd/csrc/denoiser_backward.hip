@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void gemm_tn_mfma_kernel(const float* __restri
   }
 }
 
-// db / db_done: the bias gradient db[N1] += column sums of A rides along when the bf16x6 kernel takes the product (*db_done = true)
+// db / db_done: the bias gradient db[N1] += column sums of A rides along when the fp16 x 3 kernel takes the product (*db_done = true)
 static int gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N1, int N2, hipStream_t st,
                    const GemmSegs* segs = nullptr, float* db = nullptr, bool* db_done = nullptr) {
   GemmSegs sg{};
@@ -353,8 +353,7 @@ static int gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, i
     for (int i = 0; i < sg.nseg; ++i) seg_ok = seg_ok && sg.n_end[i] % 64 == 0;
     if (seg_ok) {
       if (db_done) *db_done = db != nullptr;
-      if (tn_h3_enabled()) return launch_gemm_tn_h3(A, lda, B, ldb, C, ldc, M, N1, N2, db_done ? db : nullptr, sg.p, sg.n_end, sg.nseg, st);
-      return launch_gemm_tn_b6(A, lda, B, ldb, C, ldc, M, N1, N2, db_done ? db : nullptr, sg.p, sg.n_end, sg.nseg, st);
+      return launch_gemm_tn_h3(A, lda, B, ldb, C, ldc, M, N1, N2, db_done ? db : nullptr, sg.p, sg.n_end, sg.nseg, st);
     }
   }
   const bool aligned = N1 % 64 == 0 && N2 % 64 == 0 && lda % 4 == 0 && ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
@@ -1711,9 +1710,8 @@ static size_t bwd_planes_floats(const diffab_dims* d) {
   const size_t NP = 3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3;
   const size_t F = d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV;
   const size_t kmax = ((NP > F ? NP : F) + 31) / 32 * 32;
-  const size_t a = rowgemm128_b6_scratch_bytes(static_cast<int>(kmax)), b = xstat_b6_scratch_bytes(static_cast<int>(F)),
-               c = xstat_h3_scratch_bytes(static_cast<int>(F));
-  return (a > b ? (a > c ? a : c) : (b > c ? b : c)) / sizeof(float) + 128;
+  const size_t a = rowgemm128_b6_scratch_bytes(static_cast<int>(kmax)), c = xstat_h3_scratch_bytes(static_cast<int>(F));
+  return (a > c ? a : c) / sizeof(float) + 128;
 }
 size_t train_bwd_workspace_floats(const diffab_dims* d) {
   const size_t rows = static_cast<size_t>(d->B) * d->K, D = d->D;
@@ -1834,14 +1832,10 @@ static int run_backward(int mode, const diffab_dims* d, const diffab_denoiser_we
     float* dproj = dprojs[l & 1];
     side.before_write(dproj);  // the projection weight gradient of layer l + 2 (beside the chain) read this buffer
     // to_out
-    if (planes && (reinterpret_cast<uintptr_t>(dcur) & 15) == 0) {  // d feat = d y W_out on the x-stationary kernel (fp16 x 3; bf16 x 6 under the A/B switch)
+    if (planes && (reinterpret_cast<uintptr_t>(dcur) & 15) == 0) {  // d feat = d y W_out on the x-stationary kernel (fp16 x 3)
       if (int rc = linear_bwd(dcur, D, feat, F, lw->w_out, const_cast<float*>(lg->w_out), const_cast<float*>(lg->b_out), nullptr, F, rows, D,
                               F, false, st, &side)) return rc;
-      if (dense_h3_enabled()) {
-        if (int rc = launch_xstat_h3(dcur, lw->w_out, 1, F, dfeat, F, rows, F, planes, st)) return rc;
-      } else if (int rc = launch_xstat_b6(dcur, lw->w_out, 1, F, dfeat, F, rows, F, planes, st)) {
-        return rc;
-      }
+      if (int rc = launch_xstat_h3(dcur, lw->w_out, 1, F, dfeat, F, rows, F, planes, st)) return rc;
     } else if (int rc = linear_bwd(dcur, D, feat, F, lw->w_out, const_cast<float*>(lg->w_out), const_cast<float*>(lg->b_out), dfeat, F, rows,
                                    D, F, false, st, &side)) {
       return rc;

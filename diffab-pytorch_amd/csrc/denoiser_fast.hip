@@ -23,7 +23,6 @@
 #include "denoiser_internal.h"
 #include "rowgemm_b6_tile.h"
 #include "ipa_attn_tile.h"
-#include "attn_planes_tile.h"
 
 namespace diffab {
 
@@ -344,15 +343,14 @@ int launch_linear(const float* X, int ldx, const float* W, const float* bias, fl
 // ================================================================== fused IPA attention (benchmark geometry)
 // The body is ipa_attn_tile.h (a device function, shared with the patch-resident module kernel of ipa_persistent.hip); here one
 // work-group per (patch, 16 query residues), grid = B K / 16.
-template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false, int NW = 8, bool VPL = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void ipa_attn_fast_kernel(const float* __restrict__ proj, const float* __restrict__ e,
+template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false>
+__global__ __launch_bounds__(512) void ipa_attn_fast_kernel(const float* __restrict__ proj, const float* __restrict__ e,
                                                             const float* __restrict__ R, const float* __restrict__ t,
                                                             const float* __restrict__ Wb, const float* __restrict__ gamma,
                                                             float* __restrict__ feat, int B, int NC_arg,
                                                             unsigned long long* __restrict__ stamps, const float* __restrict__ esc = nullptr,
                                                             float* __restrict__ tape_p = nullptr, float* __restrict__ tape_d2 = nullptr,
                                                             const unsigned char* __restrict__ tile_needed = nullptr,
-                                                            const f32x4* __restrict__ vpl = nullptr, const float* __restrict__ vsc = nullptr,
                                                             const int* __restrict__ ctx_of_row = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float S[];
   const int ntile = (MULTI ? NC_arg : 1) * NT;  // K / TI
@@ -370,28 +368,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void ipa_attn_fast_kernel
   // tile_needed (reverse sampler, last layer, DIFFAB_FLAG_SKIP_UNUSED_ROWS): the outputs of this layer are read for generated residues
   // only - a row tile without one leaves at once (uniform; its feature rows keep the previous layer's values, which nothing reads)
   if (tile_needed != nullptr && !tile_needed[b * ntile + tile]) return;
-  ipa_attn_tile<NT, MULTI, PLANES, TAPE, NW, VPL>(S, b, tile, bid, proj, e, R, t, Wb, gamma, feat, NC_arg, stamps, esc, tape_p, tape_d2, vpl, vsc,
-                                                  ctx_of_row);
+  ipa_attn_tile<NT, MULTI, PLANES, TAPE>(S, b, tile, bid, proj, e, R, t, Wb, gamma, feat, NC_arg, stamps, esc, tape_p, tape_d2, ctx_of_row);
 }
 
 static unsigned long long* g_attn_stamps = nullptr;  // diagnostics only (diffab_debug_set_attn_stamps)
 static bool g_pair_chain_off = false;                // diffab_debug_set_attn_variant bit 6 (64)
-static bool g_tn_b6 = false;                         // diffab_debug_set_attn_variant bit 5 (32)
-static int g_attn_variant = 0;                       // diagnostics only (diffab_debug_set_attn_variant): 1 = four-wave work-groups
-static bool g_value_planes = false;                  // diffab_debug_set_attn_variant bit 4 (16): the value side of P x V as fp16 planes (measured, not the default:
-                                                     // profiles/r06_attention.md)
-bool value_planes_enabled() { return g_value_planes; }
 void set_pair_embed_fused(bool on);  // pair_embed_fused.hip
-void set_attn_variant(int v) {       // A/B switches for tests and tools (include/diffab_hip.h)
-  g_attn_variant = v & 9;  // 1: four-wave attention work-groups; 8: the two big dense products of a layer as six-term bf16 products
+int set_attn_variant(int v) {        // reference paths for tests and tools (include/diffab_hip.h)
+  DIFFAB_REQUIRE((v & ~(4 | 64)) == 0, DIFFAB_ERR_ARG, "debug_set_attn_variant: %d has bits other than 4 and 64", v);
+  set_pair_embed_fused(!(v & 4));    // 4: the PairEmbedding forward / backward as their unfused launches
   g_pair_chain_off = (v & 64) != 0;  // 64: the PairEmbedding backward's 64-wide tail as its separate launches (A/B of pair_chain_bwd_kernel)
-  g_tn_b6 = (v & 32) != 0;  // 32: the weight-gradient products of the training backward in the six-term bf16 form (A/B of gemm_tn_h3_kernel)
-  set_pair_embed_fused(!(v & 4));
-  g_value_planes = (v & 16) != 0;  // 16: value planes - phase 3 of the attention tile on the f16 matrix cores (proj_frames_h3_tile.h "Value planes")
+  return DIFFAB_OK;
 }
-bool dense_h3_enabled() { return g_attn_variant != 8; }
 bool pair_chain_bwd_enabled() { return !g_pair_chain_off; }
-bool tn_h3_enabled() { return g_attn_variant != 8 && !g_tn_b6; }
 void set_attn_stamps(void* p) {
   g_attn_stamps = static_cast<unsigned long long*>(p);
 }
@@ -549,18 +538,15 @@ int launch_pair_split(const diffab_dims* d, const float* e, float* planes, hipSt
 // (gemm_bf16x6.hip; same results to fp32 rounding) - the plain-fp32 reference path
 bool use_b6_gemm(uint32_t flags) { return !(flags & DIFFAB_FLAG_FP32_GEMM); }
 static size_t round256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-// one layer's prepared weights: [projection planes | to_out planes | small: w_bias 8 x 64, gamma 8 (padded to 64), b_out 128 (fp32)]
-// - the small vectors ride along so that the patch-resident module kernel (ipa_persistent.hip) finds everything of layer l at
-// base + l * ipa_layer_planes_bytes()
+// one layer's prepared weights: [small: w_bias 8 x 64, gamma 8 (padded to 64), b_out 128 (fp32) | projection planes | to_out planes |
+// 1 / scale per output column] - the projections and to_out as two-piece fp16 planes (gemm_f16x3.hip); the small vectors ride along
+// so that the patch-resident module kernel (ipa_persistent.hip) finds everything of layer l at base + l * ipa_layer_planes_bytes()
 constexpr size_t kLayerSmallFloats = AH * AC + 64 + 128;
-size_t ipa_layer_out_planes_offset() { return round256(proj_frames_b6_scratch_bytes()); }
-size_t ipa_layer_small_offset() { return ipa_layer_out_planes_offset() + round256(rowgemm128_b6_scratch_bytes(AF)); }
-// behind the small vectors: the same two weight sets as two-piece fp16 planes + 1 / scale per output column (gemm_f16x3.hip) - what the
-// forward paths use; the bf16 planes in front stay for the A/B switch and for the callers that still hand them to the bf16x6 tiles
+size_t ipa_layer_small_offset() { return 0; }
 size_t ipa_layer_h3_pj_offset() { return ipa_layer_small_offset() + round256(kLayerSmallFloats * sizeof(float)); }
 size_t ipa_layer_h3_out_offset() { return ipa_layer_h3_pj_offset() + round256(proj_frames_h3_planes_bytes()); }
 size_t ipa_layer_h3_wis_offset() { return ipa_layer_h3_out_offset() + round256(rowgemm128_h3_planes_bytes(AF)); }  // [1344 projections | 128 to_out]
-size_t ipa_layer_planes_bytes() { return ipa_layer_h3_wis_offset() + round256((ANP + 128 + 64) * sizeof(float)); }  // + 28 group maxima (value planes)
+size_t ipa_layer_planes_bytes() { return ipa_layer_h3_wis_offset() + round256((ANP + 128) * sizeof(float)); }
 __global__ void layer_small_copy_kernel(const float* __restrict__ w_bias, const float* __restrict__ gamma, const float* __restrict__ b_out,
                                         float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -571,7 +557,6 @@ __global__ void layer_small_copy_kernel(const float* __restrict__ w_bias, const 
 int ipa_layer_split_weights(const diffab_ipa_layer_weights* w, void* planes, hipStream_t st) {
   DIFFAB_REQUIRE(w && w->wq_s && w->wk_s && w->wv_s && w->wq_p && w->wk_p && w->wv_p && w->w_out, DIFFAB_ERR_ARG, "ipa layer: null weight pointer");
   const float* W6[6] = {w->wq_s, w->wk_s, w->wv_s, w->wq_p, w->wk_p, w->wv_p};
-  if (int rc = launch_pjsplit(W6, planes, st)) return rc;
   if (w->w_bias && w->gamma && w->b_out) {
     hipLaunchKernelGGL(layer_small_copy_kernel, dim3((kLayerSmallFloats + 255) / 256), dim3(256), 0, st, w->w_bias, w->gamma, w->b_out,
                        reinterpret_cast<float*>(static_cast<char*>(planes) + ipa_layer_small_offset()));
@@ -580,47 +565,18 @@ int ipa_layer_split_weights(const diffab_ipa_layer_weights* w, void* planes, hip
   char* pl = static_cast<char*>(planes);
   float* wis = reinterpret_cast<float*>(pl + ipa_layer_h3_wis_offset());
   if (int rc = launch_pjsplit_h3(W6, pl + ipa_layer_h3_pj_offset(), wis, st)) return rc;
-  if (int rc = launch_wsplit128_h3(w->w_out, AF, AF, pl + ipa_layer_h3_out_offset(), wis + ANP, st)) return rc;
-  return launch_wsplit128(w->w_out, AF, AF, pl + ipa_layer_out_planes_offset(), st);
+  return launch_wsplit128_h3(w->w_out, AF, AF, pl + ipa_layer_h3_out_offset(), wis + ANP, st);
 }
 static size_t b6_scratch_floats() { return (ipa_layer_planes_bytes() + 256) / sizeof(float); }
 
 // workspace of one layer: proj | feat | 128 | three-launch attention's logits (K = 64 / 128) | per-call weight planes | k parts of
-// to_out (small batches: launch_rowgemm128_h3p) | operand planes of the logits product (proj_planes.hip) | patch centroids
+// to_out (small batches: launch_rowgemm128_h3p)
 static size_t ipa_ws_parts_offset(const diffab_dims* d) {
   const size_t rows = static_cast<size_t>(d->B) * d->K;
   const size_t o = rows * (ANP + AF) + 128 + (attention_split_supported(d) ? attention_split_workspace_floats(d) : 0) + b6_scratch_floats();
   return (o + 63) & ~static_cast<size_t>(63);
 }
-static size_t ipa_ws_operands_offset(const diffab_dims* d) {
-  const size_t o = ipa_ws_parts_offset(d) + rowgemm128_h3_parts_floats(d->B * d->K, AF);
-  return (o + 63) & ~static_cast<size_t>(63);
-}
-// ... | value planes + their scales (the P x V operands of the plane attention kernels, written by the h3 projection tile)
-static size_t ipa_ws_vpl_offset(const diffab_dims* d) { return ipa_ws_operands_offset(d) + 64; }
-size_t ipa_fast_workspace_floats(const diffab_dims* d) {
-  const int64_t rows = static_cast<int64_t>(d->B) * d->K;
-  return ipa_ws_vpl_offset(d) + proj_value_planes_floats(rows) + proj_value_scales_floats(rows) + 64;
-}
-// the value planes of a layer workspace: 256-byte aligned planes, the scales behind them
-void ipa_ws_value_planes(const diffab_dims* d, float* ws, float** vpl, float** vsc) {
-  float* base = ws + ipa_ws_vpl_offset(d);
-  *vpl = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(base) + 255) & ~static_cast<uintptr_t>(255));
-  *vsc = *vpl + proj_value_planes_floats(static_cast<int64_t>(d->B) * d->K);
-}
-
-// the value side of every patch as fp16 planes (attn_planes_tile.h): one work-group per patch
-__global__ __launch_bounds__(512) void attn_value_planes_kernel(const float* __restrict__ proj, const float* __restrict__ t, int K,
-                                                                _Float16* __restrict__ vpl, float* __restrict__ osc) {
-  extern __shared__ __attribute__((aligned(16))) float ap_lds[];
-  aplanes::attn_value_planes_tile(ap_lds, threadIdx.x, blockIdx.x, proj, t, K, vpl, osc);
-}
-int launch_attn_value_planes(const diffab_dims* d, const float* proj, const float* t, float* vpl, float* vsc, hipStream_t st) {
-  DIFFAB_REQUIRE(proj && t && vpl && vsc && d->K % 32 == 0 && fast_path_supported(d), DIFFAB_ERR_ARG, "attn_value_planes: unsupported operands");
-  hipLaunchKernelGGL(attn_value_planes_kernel, dim3(d->B), dim3(512), aplanes::LDS_BYTES, st, proj, t, d->K, reinterpret_cast<_Float16*>(vpl), vsc);
-  DIFFAB_LAUNCH_CHECK();
-  return DIFFAB_OK;
-}
+size_t ipa_fast_workspace_floats(const diffab_dims* d) { return ipa_ws_parts_offset(d) + rowgemm128_h3_parts_floats(d->B * d->K, AF) + 64; }
 
 int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R, const float* t,
                    float* y, float* ws, hipStream_t st, float* sp_keep, float* d2_keep, const void* planes, const float* pair_planes,
@@ -629,30 +585,23 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
   DIFFAB_REQUIRE(ctx_of_row == nullptr || sp_keep == nullptr, DIFFAB_ERR_ARG, "ipa_layer_fast: shared contexts are an inference form");
   float* proj = ws;
   float* feat = ws + static_cast<size_t>(rows) * ANP;
-  // Dense projections on the bf16 matrix cores (gemm_bf16x6.hip) from split weight planes: the caller's (reverse sampler: split once
+  // Dense projections on the f16 matrix cores (gemm_f16x3.hip) from split weight planes: the caller's (reverse sampler: split once
   // per trajectory) or, per call, the tail of the workspace.  sp_keep != nullptr (training tape): that workspace slot has no tail,
   // fp32 kernels there.
-  const bool b6 = use_b6_gemm(fp32_gemm ? DIFFAB_FLAG_FP32_GEMM : 0u) && (planes != nullptr || sp_keep == nullptr);
-  if (b6 && planes == nullptr) {
+  const bool h3 = use_b6_gemm(fp32_gemm ? DIFFAB_FLAG_FP32_GEMM : 0u) && (planes != nullptr || sp_keep == nullptr);
+  if (h3 && planes == nullptr) {
     float* tail = ws + static_cast<size_t>(rows) * (ANP + AF) + 128 + (attention_split_supported(d) ? attention_split_workspace_floats(d) : 0);
     void* own = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(tail) + 255) & ~static_cast<uintptr_t>(255));
     if (int rc = ipa_layer_split_weights(w, own, st)) return rc;
     planes = own;
   }
-  const void* out_planes = b6 ? static_cast<const char*>(planes) + ipa_layer_out_planes_offset() : nullptr;
-  // the three-term fp16 form of the two products (gemm_f16x3.hip) unless the A/B switch asks for the six-term bf16 form
-  const bool h3 = b6 && dense_h3_enabled();
   const char* plc = static_cast<const char*>(planes);
-  const float* wis = b6 ? reinterpret_cast<const float*>(plc + ipa_layer_h3_wis_offset()) : nullptr;
+  const float* wis = h3 ? reinterpret_cast<const float*>(plc + ipa_layer_h3_wis_offset()) : nullptr;
   // to_out (diffab_pytorch.py:459-464): feat (rows x 1024) Wo^T + b
   auto to_out = [&]() -> int {
     if (h3 && rowgemm128_b6_ok(feat, AF, y, D, rows, AF))
       return launch_rowgemm128_h3p(feat, AF, plc + ipa_layer_h3_out_offset(), wis + ANP, w->b_out, nullptr, 0, y, D, rows, AF, false, st,
                                    taped ? nullptr : ws + ipa_ws_parts_offset(d));
-    if (b6 && rowgemm128_b6_ok(feat, AF, y, D, rows, AF))
-      // (inference: the projections are dead once the attention has run, their rows take the k parts of a small batch; on the
-      // training tape they are kept for the backward)
-      return launch_rowgemm128_b6p(feat, AF, out_planes, w->b_out, nullptr, 0, y, D, rows, AF, false, st, taped ? nullptr : proj);
     return launch_linear(feat, AF, w->w_out, w->b_out, y, D, rows, D, AF, false, st);
   };
   // one GEMM for the six projections: Y[:, 0:1344] = x [Wq_s; Wk_s; Wv_s; Wq_p; Wk_p; Wv_p]^T
@@ -663,19 +612,8 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
   bool vec = aligned16(x);
   for (int s = 0; s < 6; ++s) vec = vec && aligned16(segs.W[s]);
   DIFFAB_REQUIRE(vec, DIFFAB_ERR_ARG, "ipa_layer_fast: x and the projection weights must be 16-byte aligned");
-  // Value planes (round 6, diffab_debug_set_attn_variant(16)): with the pair planes (inference) a small kernel cuts the value side of the
-  // fresh projection rows into fp16 planes (attn_planes_tile.h) and the attention tile's P x V product runs on the f16 matrix cores.
-  const bool vpl_on = h3 && !taped && sp_keep == nullptr && pair_planes != nullptr && pair_planes_supported(d) && g_attn_variant != 1 &&
-                      d->K % 32 == 0 && g_value_planes;
-  float* vpl = nullptr;
-  float* vsc = nullptr;
-  if (vpl_on) ipa_ws_value_planes(d, ws, &vpl, &vsc);
   if (h3) {
     if (int rc = launch_proj_frames_h3p(x, plc + ipa_layer_h3_pj_offset(), wis, R, t, proj, rows, st)) return rc;
-    if (vpl_on)
-      if (int rc = launch_attn_value_planes(d, proj, t, vpl, vsc, st)) return rc;
-  } else if (b6) {
-    if (int rc = launch_proj_frames_b6p(x, planes, R, t, proj, rows, st)) return rc;
   } else {
     if (int rc = launch_proj_frames_f32(x, segs.W, R, t, proj, rows, st)) return rc;  // noslp_kernels.hip
   }
@@ -694,14 +632,13 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
   const bool use_planes = pair_planes != nullptr && pair_planes_supported(d);
   const float* e_arg = use_planes ? pair_planes + 64 : e;
   const float* esc = use_planes ? pair_row_scales(d, pair_planes, n_ctx) : nullptr;
-#define ATTN_LAUNCH(NT_, MULTI_, PLANES_, VPL_)                                                                                       \
+#define ATTN_LAUNCH(NT_, MULTI_, PLANES_)                                                                                             \
   do {                                                                                                                                \
-    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_fast_kernel<NT_, MULTI_, PLANES_, false, 8, VPL_>),   \
+    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_fast_kernel<NT_, MULTI_, PLANES_>),                   \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));                         \
     timer_begin(st);                                                                                                                  \
-    hipLaunchKernelGGL((ipa_attn_fast_kernel<NT_, MULTI_, PLANES_, false, 8, VPL_>), grid, dim3(512), lds, st, proj, e_arg, R, t,     \
-                       w->w_bias, w->gamma, feat, d->B, nc, g_attn_stamps, esc, nullptr, nullptr, tile_needed,                        \
-                       reinterpret_cast<const f32x4*>(vpl), vsc, ctx_of_row);                                                         \
+    hipLaunchKernelGGL((ipa_attn_fast_kernel<NT_, MULTI_, PLANES_>), grid, dim3(512), lds, st, proj, e_arg, R, t, w->w_bias, w->gamma, \
+                       feat, d->B, nc, g_attn_stamps, esc, nullptr, nullptr, tile_needed, ctx_of_row);                                \
     timer_end(st);                                                                                                                    \
   } while (0)
   if (tape) {
@@ -709,30 +646,15 @@ int ipa_layer_fast(const diffab_dims* d, const diffab_ipa_layer_weights* w, cons
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     hipLaunchKernelGGL((ipa_attn_fast_kernel<8, false, false, true>), grid, dim3(512), lds, st, proj, e, R, t, w->w_bias, w->gamma, feat,
                        d->B, nc, nullptr, nullptr, sp_keep, d2_keep);
-  } else if (use_planes && g_attn_variant == 1) {
-    // four-wave work-groups, two per CU, 64-key chunks (ipa_attn_tile.h, NW = 4)
-    const int nc4 = d->K / 64;
-    const size_t lds4 = ipa_attn_lds_bytes(4, 4, true);
-    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_fast_kernel<4, true, true, false, 4>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds4)));
-    timer_begin(st);
-    hipLaunchKernelGGL((ipa_attn_fast_kernel<4, true, true, false, 4>), grid, dim3(256), lds4, st, proj, e_arg, R, t, w->w_bias, w->gamma, feat,
-                       d->B, nc4, g_attn_stamps, esc, nullptr, nullptr, tile_needed, nullptr, nullptr, ctx_of_row);
-    timer_end(st);
-  } else if (vpl_on) {
-    if (nt == 8 && nc == 1) ATTN_LAUNCH(8, false, true, true);
-    else if (nt == 8) ATTN_LAUNCH(8, true, true, true);
-    else if (nc == 1) ATTN_LAUNCH(4, false, true, true);
-    else ATTN_LAUNCH(4, true, true, true);
   } else if (use_planes) {
-    if (nt == 8 && nc == 1) ATTN_LAUNCH(8, false, true, false);
-    else if (nt == 8) ATTN_LAUNCH(8, true, true, false);
-    else if (nc == 1) ATTN_LAUNCH(4, false, true, false);
-    else ATTN_LAUNCH(4, true, true, false);
-  } else if (nt == 8 && nc == 1) ATTN_LAUNCH(8, false, false, false);
-  else if (nt == 8) ATTN_LAUNCH(8, true, false, false);
-  else if (nc == 1) ATTN_LAUNCH(4, false, false, false);
-  else ATTN_LAUNCH(4, true, false, false);
+    if (nt == 8 && nc == 1) ATTN_LAUNCH(8, false, true);
+    else if (nt == 8) ATTN_LAUNCH(8, true, true);
+    else if (nc == 1) ATTN_LAUNCH(4, false, true);
+    else ATTN_LAUNCH(4, true, true);
+  } else if (nt == 8 && nc == 1) ATTN_LAUNCH(8, false, false);
+  else if (nt == 8) ATTN_LAUNCH(8, true, false);
+  else if (nc == 1) ATTN_LAUNCH(4, false, false);
+  else ATTN_LAUNCH(4, true, false);
 #undef ATTN_LAUNCH
   DIFFAB_LAUNCH_CHECK();
   return to_out();

@@ -54,8 +54,8 @@ bool rowgemm128_ok(const float* X, int ldx, const float* Y, int ldy, int M, int 
 int launch_rowgemm128(const float* X, int ldx, const float* W, int ldw, const float* bias, const int64_t* bias_idx, int bias_div, float* Y,
                       int ldy, int M, int Kd, bool relu, hipStream_t st);
 // gemm_bf16x6.hip: the same products on the bf16 matrix cores, fp32-accurate (three-way bf16 split of both operands, six partial
-// products, fp32 accumulation).  The weights are split once into bf16 planes (launch_wsplit128 / launch_pjsplit: per call, or
-// once per trajectory by the reverse sampler) and the ...p launchers take the planes.
+// products, fp32 accumulation).  The weights are split once into bf16 planes (launch_wsplit128: per call, or once per trajectory by
+// the reverse sampler) and the ...p launchers take the planes.
 size_t rowgemm128_b6_scratch_bytes(int Kd);
 bool rowgemm128_b6_ok(const float* X, int ldx, const float* Y, int ldy, int M, int Kd);
 int launch_wsplit128(const float* W, int ldw, int Kd, void* planes, hipStream_t st, int nrows = 128);  // rows >= nrows: zero planes
@@ -75,18 +75,11 @@ int launch_rowgemm128_b6p(const float* X, int ldx, const void* planes, const flo
                           int ldy, int M, int Kd, bool relu, hipStream_t st, float* parts = nullptr);
 size_t rowgemm128_b6_parts_floats(int M, int Kd);  // scratch of the k-parts form (few row tiles)
 size_t rowgemm128_h3_parts_floats(int M, int Kd);
-bool value_planes_enabled();  // true: diffab_debug_set_attn_variant(16)
-void ipa_ws_value_planes(const diffab_dims* d, float* ws, float** vpl, float** vsc);  // the value planes / scales inside a layer workspace
-bool tn_h3_enabled();     // false: diffab_debug_set_attn_variant(8 | 32): weight-gradient products in the six-term bf16 form
-bool dense_h3_enabled();  // false: diffab_debug_set_attn_variant(8), the six-term bf16 form of the projections and to_out
 int launch_rowgemm128_b6(const float* X, int ldx, const float* W, int ldw, const float* bias, const int64_t* bias_idx, int bias_div, float* Y,
                          int ldy, int M, int Kd, bool relu, void* scratch, hipStream_t st);
 bool use_b6_gemm(uint32_t flags = 0);  // false with DIFFAB_FLAG_FP32_GEMM (experimental builds: or DIFFAB_FP32_GEMM=1 in the environment)
-// the six IPA projections + frames; W6 = {wq_s, wk_s, wv_s, wq_p, wk_p, wv_p}
-size_t proj_frames_b6_scratch_bytes();
-int launch_pjsplit(const float* const* W6, void* planes, hipStream_t st);
-int launch_proj_frames_b6p(const float* x, const void* planes, const float* R, const float* t, float* proj, int rows, hipStream_t st);
-// the same x-stationary kernel as a plain product Y[rows x N] = X[rows x 128] W'^T, (n, k) of W' = W[n sn + k sk] (to_out input gradient)
+// the x-stationary product Y[rows x N] = X[rows x 128] W'^T, (n, k) of W' = W[n sn + k sk] (to_out input gradient; a test reference of
+// launch_xstat_h3)
 size_t xstat_b6_scratch_bytes(int N);
 // gemm_f16x3.hip: C[N1 x N2] += A^T B as three fp16 terms (launch_gemm_tn_b6's contract)
 int launch_gemm_tn_h3(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N1, int N2, float* db,
@@ -95,14 +88,13 @@ size_t xstat_h3_scratch_bytes(int N);  // gemm_f16x3.hip: the same product as th
 int launch_xstat_h3(const float* X, const float* W, int64_t sn, int64_t sk, float* Y, int ldy, int rows, int N, void* scratch, hipStream_t st);
 int launch_xstat_b6(const float* X, const float* W, int64_t sn, int64_t sk, float* Y, int ldy, int rows, int N, void* scratch, hipStream_t st);
 // weight-gradient product C[N1 x N2] += A[M x N1]^T B[M x N2] (transposing LDS reads), any widths / row strides; rows of C optionally
-// spread over nseg matrices
+// spread over nseg matrices (a test reference of launch_gemm_tn_h3; gemm_tn_b6_ok is the contract of both)
 bool gemm_tn_b6_ok(const float* A, int lda, const float* B, int ldb, int M, int N1, int N2);
 int launch_gemm_tn_b6(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N1, int N2, float* db,
                       float* const* seg_ptrs, const int* seg_ends, int nseg, hipStream_t st);  // db (nullable): += column sums of A
 // split planes of one IPA layer's projection and to_out weights: ipa_layer_planes_bytes() bytes, 256-byte aligned
 size_t ipa_layer_planes_bytes();
-size_t ipa_layer_out_planes_offset();  // the to_out planes inside a layer's block
-size_t ipa_layer_small_offset();       // fp32 copies of w_bias [8][64], gamma [8] (padded to 64), b_out [128] behind the planes
+size_t ipa_layer_small_offset();       // fp32 copies of w_bias [8][64], gamma [8] (padded to 64), b_out [128] in front of the planes
 size_t ipa_layer_h3_pj_offset();       // gemm_f16x3.hip: the projections' two-piece fp16 planes,
 size_t ipa_layer_h3_out_offset();      //   to_out's,
 size_t ipa_layer_h3_wis_offset();      //   and 1 / scale per output column: [1344 | 128] floats
@@ -115,8 +107,6 @@ int launch_rowgemm128_h3p(const float* X, int ldx, const void* planes, const flo
                           float* Y, int ldy, int M, int Kd, bool relu, hipStream_t st, float* parts = nullptr);
 int launch_proj_frames_h3p(const float* x, const void* planes, const float* wis, const float* R, const float* t, float* proj, int rows,
                            hipStream_t st);
-size_t proj_value_planes_floats(int64_t rows);   // (attn_planes_tile.h; consumer: ipa_attn_tile.h phase 3, VPL)
-size_t proj_value_scales_floats(int64_t rows);
 int ipa_layer_split_weights(const diffab_ipa_layer_weights* w, void* planes, hipStream_t st);
 // ipa_persistent.hip: all NL layers of the IPA module for K = 128 patches as ONE patch-resident launch (one work-group owns a patch
 // through projections -> 8 attention row tiles -> to_out, layer after layer; no inter-CU synchronisation).  xa: input, the result is in
@@ -162,7 +152,7 @@ int launch_attention_split(const diffab_dims* d, const float* proj, const float*
                            const float* gamma, float* feat, float* SP, hipStream_t st, float* D2 = nullptr);
 
 void set_stream_order(bool on);  // api.hip: the cross-stream ordering guard (common.h StreamOrder)
-void set_attn_variant(int v);  // diagnostics: 1 = the four-wave / two-groups-per-CU form of the plane attention kernel
+int set_attn_variant(int v);  // reference paths for tests: 4 = unfused PairEmbedding launches, 64 = separate PairEmbedding backward launches
 void set_attn_stamps(void* device_buffer);  // diagnostics: per-wave s_memtime stamps of the attention kernel's phases
 
 // api.hip: opt-in hipEvent bracket around the dominant (attention) kernel

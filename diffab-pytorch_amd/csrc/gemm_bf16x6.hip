@@ -278,61 +278,22 @@ int launch_rowgemm128_b6(const float* X, int ldx, const float* W, int ldw, const
   return launch_rowgemm128_b6p(X, ldx, scratch, bias, bias_idx, bias_div, Y, ldy, M, Kd, relu, st);
 }
 
-// ================================================================== six IPA projections + local->global frames (bf16x6)
-// proj[:, 0:1344] = x [Wq_s; Wk_s; Wv_s; Wq_p; Wk_p; Wv_p]^T, the three point blocks mapped to the global frame (x R + t,
-// diffab_pytorch.py:324) before they are stored - the bf16x6 form of proj_frames_kernel (denoiser_fast.hip), same decomposition:
-// x-stationary (a wave keeps its 32 x 128 slab of x as SPLIT A fragments: 96 VGPRs), 14 blocks of 96 output columns, MFMA n index
-// permuted so that a lane ends up with three consecutive output columns (one point) per row.  The weights arrive pre-split
-// (pjsplit_kernel) in stage order - stage = (block, k half): 3 planes x 96 LDS rows x 64 k, 36 KiB contiguous - and are staged
-// through a ring of two LDS buffers with rows padded to 160 bytes (conflict-free ds_read_b128 for the 16-row B fragment).
+// ================================================================== x-stationary product (bf16x6)
+// Y[rows x N] = X[rows x 128] W'^T, element (n, k) of W' = W[n sn + k sk]: the input-gradient product of to_out, kept as the fp32-accurate
+// reference of its three-term fp16 form (xstat_h3_kernel, gemm_f16x3.hip).  A wave keeps its 32 x 128 slab of x as SPLIT A fragments (96
+// VGPRs), blocks of 96 output columns, MFMA n index permuted so that a lane ends up with three consecutive output columns per row.  The
+// weights arrive pre-split (xsplit_kernel) in stage order - stage = (block, k half): 3 planes x 96 LDS rows x 64 k, 36 KiB contiguous - and
+// are staged through a ring of two LDS buffers with rows padded to 160 bytes (conflict-free ds_read_b128 for the 16-row B fragment).
 // (the tile body and its constants: proj_frames_b6_tile.h)
 using namespace pjtile;
 
-// stage-ordered split weights: out[((blk * 2 + kh) * 3 + plane) * 96 + l][kk], l = 48 cw + 16 tt + j <-> output column
-// 96 blk + 48 cw + 3 j + tt, k = 64 kh + kk
-__global__ void pjsplit_kernel(const float* __restrict__ W0, const float* __restrict__ W1, const float* __restrict__ W2,
-                               const float* __restrict__ W3, const float* __restrict__ W4, const float* __restrict__ W5,
-                               __bf16* __restrict__ out) {
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x;  // (output column gc, k)
-  if (gid >= PJ_NP * 128) return;
-  const int gc = gid >> 7, k = gid & 127;
-  const float* Wp;
-  int row;
-  if (gc < PJ_GQ) {
-    Wp = gc < 256 ? W0 : (gc < 512 ? W1 : W2);
-    row = gc & 255;
-  } else {
-    Wp = gc < PJ_GK ? W3 : (gc < PJ_GV ? W4 : W5);
-    row = gc - (gc < PJ_GK ? PJ_GQ : (gc < PJ_GV ? PJ_GK : PJ_GV));
-  }
-  __bf16 h, m, l;
-  split3(Wp[row * 128 + k], h, m, l);
-  const int blk = gc / PJ_B, rem = gc % PJ_B, cwl = rem / 48, r48 = rem % 48, j = r48 / 3, tt = r48 % 3;
-  const int lrow = 48 * cwl + 16 * tt + j, kh = k >> 6, kk = k & 63;
-  const size_t base = (static_cast<size_t>(blk * 2 + kh) * 3 * PJ_B + lrow) * 64 + kk;
-  out[base] = h;
-  out[base + PJ_B * 64] = m;
-  out[base + 2 * PJ_B * 64] = l;
-}
-
-template <bool FULL, bool PROJ, bool SPLIT = false>
+template <bool FULL, bool SPLIT = false>
 __global__ __launch_bounds__(512) void proj_frames_b6_kernel(const float* __restrict__ X, const __bf16* __restrict__ Wc,
                                                              const float* __restrict__ R, const float* __restrict__ t,
                                                              float* __restrict__ Y, int M, int N_, int NB_, int ldy_, int frames_from_) {
   extern __shared__ __attribute__((aligned(16))) __bf16 pj_lds[];
-  pjtile::proj_frames_b6_tile<FULL, PROJ, SPLIT>(pj_lds, threadIdx.x, blockIdx.x, blockIdx.y, gridDim.y, X, Wc, R, t, Y, M, N_, NB_, ldy_,
-                                                 frames_from_);
-}
-
-size_t proj_frames_b6_scratch_bytes() { return static_cast<size_t>(2 * PJ_NB) * PJ_STAGE_ELEMS * sizeof(__bf16); }
-
-// W6 = {wq_s, wk_s, wv_s, wq_p, wk_p, wv_p} -> stage-ordered split planes (proj_frames_b6_scratch_bytes() bytes, 16-byte aligned)
-int launch_pjsplit(const float* const* W6, void* planes, hipStream_t st) {
-  DIFFAB_REQUIRE(planes && (reinterpret_cast<uintptr_t>(planes) & 15) == 0, DIFFAB_ERR_ARG, "pjsplit: bad operands");
-  hipLaunchKernelGGL(pjsplit_kernel, dim3((PJ_NP * 128 + 255) / 256), dim3(256), 0, st, W6[0], W6[1], W6[2], W6[3], W6[4], W6[5],
-                     static_cast<__bf16*>(planes));
-  DIFFAB_LAUNCH_CHECK();
-  return DIFFAB_OK;
+  pjtile::proj_frames_b6_tile<FULL, SPLIT>(pj_lds, threadIdx.x, blockIdx.x, blockIdx.y, gridDim.y, X, Wc, R, t, Y, M, N_, NB_, ldy_,
+                                           frames_from_);
 }
 
 static int launch_xstat(const float* x, const void* planes, const float* R, const float* t, float* Y, int rows, int N, int NB, int ldy,
@@ -341,27 +302,23 @@ static int launch_xstat(const float* x, const void* planes, const float* R, cons
                      (reinterpret_cast<uintptr_t>(Y) & 3) == 0 && rows >= 1 && NB % 2 == 0 && NB * PJ_B >= N,
                  DIFFAB_ERR_ARG, "proj_frames_b6: unsupported operands");
   const __bf16* Wc = static_cast<const __bf16*>(planes);
-  const dim3 grid((rows + PJ_ROWS - 1) / PJ_ROWS);
-  const bool proj_geom = N == PJ_NP && NB == PJ_NB && ldy == PJ_NP && frames_from == PJ_GQ / PJ_B;
   const int ntiles = (rows + PJ_ROWS - 1) / PJ_ROWS;
   // half the chip or less: several groups per row tile, each with its share of the column blocks (B = 1: one block per group)
   int nsplit = 256 / ntiles;
   nsplit = nsplit < 1 ? 1 : (nsplit > NB ? NB : nsplit);
   const bool split = nsplit > 1;
   const dim3 grid2(ntiles, nsplit);
-#define XSTAT_LAUNCH(FULL_, PROJ_, SPLIT_)                                                                                               \
+#define XSTAT_LAUNCH(FULL_, SPLIT_)                                                                                                      \
   do {                                                                                                                                   \
-    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(proj_frames_b6_kernel<FULL_, PROJ_, SPLIT_>),                      \
+    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(proj_frames_b6_kernel<FULL_, SPLIT_>),                             \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, PJ_LDS_BYTES));                                      \
-    hipLaunchKernelGGL((proj_frames_b6_kernel<FULL_, PROJ_, SPLIT_>), grid2, dim3(512), PJ_LDS_BYTES, st, x, Wc, R, t, Y, rows, N, NB,    \
-                       ldy, frames_from);                                                                                                \
+    hipLaunchKernelGGL((proj_frames_b6_kernel<FULL_, SPLIT_>), grid2, dim3(512), PJ_LDS_BYTES, st, x, Wc, R, t, Y, rows, N, NB, ldy,      \
+                       frames_from);                                                                                                     \
   } while (0)
-#define XSTAT_PICK(FULL_)                                     \
-  do {                                                        \
-    if (proj_geom && split) XSTAT_LAUNCH(FULL_, true, true);  \
-    else if (proj_geom) XSTAT_LAUNCH(FULL_, true, false);     \
-    else if (split) XSTAT_LAUNCH(FULL_, false, true);         \
-    else XSTAT_LAUNCH(FULL_, false, false);                   \
+#define XSTAT_PICK(FULL_)                 \
+  do {                                    \
+    if (split) XSTAT_LAUNCH(FULL_, true); \
+    else XSTAT_LAUNCH(FULL_, false);      \
   } while (0)
   if (rows % PJ_ROWS == 0) XSTAT_PICK(true);
   else XSTAT_PICK(false);
@@ -371,12 +328,6 @@ static int launch_xstat(const float* x, const void* planes, const float* R, cons
   return DIFFAB_OK;
 }
 
-// the six projections of one IPA layer (D = 128) into proj[rows x 1344], weights given as split planes (launch_pjsplit)
-int launch_proj_frames_b6p(const float* x, const void* planes, const float* R, const float* t, float* proj, int rows, hipStream_t st) {
-  return launch_xstat(x, planes, R, t, proj, rows, PJ_NP, PJ_NB, PJ_NP, PJ_GQ / PJ_B, st);
-}
-
-// ---- the x-stationary kernel as a plain product: Y[rows x N] = X[rows x 128] W'^T, element (n, k) of W' = W[n sn + k sk]
 static int xstat_blocks(int N) { return ((N + PJ_B - 1) / PJ_B + 1) / 2 * 2; }
 size_t xstat_b6_scratch_bytes(int N) { return static_cast<size_t>(2 * xstat_blocks(N)) * PJ_STAGE_ELEMS * sizeof(__bf16); }
 __global__ void xsplit_kernel(const float* __restrict__ W, int64_t sn, int64_t sk, int N, int ncols, __bf16* __restrict__ out) {

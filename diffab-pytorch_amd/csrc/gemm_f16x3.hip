@@ -217,9 +217,6 @@ __global__ __launch_bounds__(512) void proj_frames_h3_kernel(const float* __rest
   pjh3::proj_frames_h3_tile<FULL, SPLIT>(pj_lds, threadIdx.x, blockIdx.x, blockIdx.y, gridDim.y, X, Wc, wis, R, t, Y, M);
 }
 
-// operand planes of the attention tile (attn_planes_tile.h): floats of workspace for `rows` projection rows
-size_t proj_value_planes_floats(int64_t rows) { return static_cast<size_t>(rows) * 512; }  // V: 8 heads x 4 tiles x 16 columns x 2 planes x 2 bytes per row
-size_t proj_value_scales_floats(int64_t rows) { return (static_cast<size_t>(rows / 32 + 1) * 64 + 63) & ~static_cast<size_t>(63); }
 size_t proj_frames_h3_planes_bytes() { return static_cast<size_t>(2 * pjh3::PJ_NB) * pjh3::PJ_STAGE_ELEMS * sizeof(_Float16); }
 // W6 = {wq_s, wk_s, wv_s, wq_p, wk_p, wv_p} -> stage-ordered planes (proj_frames_h3_planes_bytes(), 16-byte aligned) + wis[1344]
 int launch_pjsplit_h3(const float* const* W6, void* planes, float* wis, hipStream_t st) {

@@ -112,17 +112,10 @@ __device__ __forceinline__ void attn_shift_pair_rows(FP& e, FP& esc, const int* 
 // One (patch b, 16-row tile) item of the fused attention: the body of ipa_attn_fast_kernel (denoiser_fast.hip: one item per work-group)
 // and of the patch-resident module kernel (ipa_persistent.hip: a work-group walks the eight row tiles of ITS patch, layer after layer).
 // 512 threads; S: the dynamic LDS (ipa_attn_lds_bytes(NT)); stamp_id: the slot of this item in the diagnostic stamp buffer.
-// NW: waves of the work-group (8: wave = head in phases 1 and 3, two rows in phase 2; 4: two heads / four rows per wave - the form that
-// fits two work-groups on a CU: with the 64-key chunk image its LDS is 79.5 KiB, and the two groups' phases interleave on the CU's pipes).
-// VPL (with PLANES, NW = 8; round 6): phase 3 (P x V) runs on the f16 matrix cores as well.  The value side arrives as two fp16 planes in
-// fragment order, cut once per (patch, layer) by attn_planes_tile.h (per (patch, head, 32-key step) the four 16-column tiles [v_s 0..15 |
-// v_s 16..31 | x, y of the 8 points | z of the 8 points + a ones column], one power-of-two scale per (head, step) and kind in vsc, point
-// coordinates relative to the patch's first translation); the probabilities are split into two fp16 planes
-// on the fly (2^15 P = p1 + p2): three exact partial products per tile and 32 keys - 12 MFMAs of 16 cycles per (head, 32 keys) against 32
-// f32 MFMAs of 32 cycles (which also block the vector ALU), 8 linear 1 KiB loads per 32 keys straight into B fragments, no LDS staging.
+// Eight waves: wave = head in phases 1 and 3, two query rows in phase 2.
 // ctx_of_row (shared contexts, diffab_sample_loop_shared): the pair rows (and their row scales) of state row b are those of context
-// ctx_of_row[b] - `e` / `esc` then hold n_ctx patches; the projections, features and value planes stay on row b.  nullptr: the identity.
-template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false, int NW = 8, bool VPL = false>
+// ctx_of_row[b] - `e` / `esc` then hold n_ctx patches; the projections and features stay on row b.  nullptr: the identity.
+template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false>
 __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b, const int tile, const unsigned stamp_id,
                                               const float* __restrict__ proj, const float* __restrict__ e,
                                               const float* __restrict__ R, const float* __restrict__ t,
@@ -130,12 +123,7 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
                                               float* __restrict__ feat, int NC_arg,
                                               unsigned long long* __restrict__ stamps, const float* __restrict__ esc = nullptr,
                                               float* __restrict__ tape_p = nullptr, float* __restrict__ tape_d2 = nullptr,
-                                              const f32x4* __restrict__ vpl = nullptr, const float* __restrict__ vsc = nullptr,
                                               const int* __restrict__ ctx_of_row = nullptr) {
-  static_assert(NW == 8 || (NW == 4 && PLANES && !TAPE), "the four-wave form exists for the plane kernels");
-  static_assert(!VPL || (PLANES && NW == 8 && NT % 2 == 0), "value planes: the eight-wave plane kernels");
-  constexpr int HPW = AH / NW;  // heads per wave (phases 1 and 3)
-  constexpr int RPW = TI / NW;  // query rows per wave (phase 2)
   static_assert(!PLANES || NT % 2 == 0, "the o_e product takes key tiles in pairs");
   static_assert(!TAPE || (!MULTI && !PLANES), "the tape form is the single-chunk fp32-pair kernel");
   const int NC = MULTI ? NC_arg : 1;
@@ -182,7 +170,7 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
   constexpr int E_LAG = MULTI ? 2 : 0;    // the next row's tile loads trail the retiring tiles by this many (VGPRs)
   constexpr int E_EARLY = MULTI ? 1 : 2;  // pair tiles of phase 2's first row started under the tail of phase 1 (swept in rounds 2-3)
   float* scr = S + TI * IS + wv * SCR_FLOATS;
-  float* st_fac = S + TI * IS + NW * SCR_FLOATS;  // [TI][AH] exp(M_old - M_new) of the current chunk
+  float* st_fac = S + TI * IS + 8 * SCR_FLOATS;  // [TI][AH] exp(M_old - M_new) of the current chunk
   float* st_inv = st_fac + TI * AH;              // [TI][AH] 1 / L after the last chunk (1 before)
   float* wb_lds = st_inv + TI * AH;              // [4 sg][64 lanes][4]: B fragments of the bias product (same for every wave)
   float* gq_lds = wb_lds + (PLANES ? 0 : 4 * 64 * 4) + wv * (TI * 24);  // per wave: the item's query points of its head, [16 rows][24] as loaded
@@ -201,23 +189,23 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
   // must not evict the K/V-side operands, re-read by the other row tiles of the patch, from L2), in the orientation of
   // the o_e product: lane (l15, q) holds e[i][j = 16 jt + 4 q + r][c = 4 l15 .. 4 l15 + 3] - 1 KiB contiguous per load.
   // A chunk of a row (16 NT VGPRs) stays in registers from the bias product to the o_e product.
-  const float* erow[RPW];
-  float Mrun[RPW], Lrun[RPW];  // online-softmax state of (row RPW wv + ii, head l15 & 7)
+  const float* erow[2];
+  float Mrun[2], Lrun[2];  // online-softmax state of (row 2 wv + ii, head l15 & 7)
 #pragma unroll
-  for (int ii = 0; ii < RPW; ++ii) {
-    erow[ii] = e + ((prow0 + i0 + RPW * wv + ii) * K) * AC;
+  for (int ii = 0; ii < 2; ++ii) {
+    erow[ii] = e + ((prow0 + i0 + 2 * wv + ii) * K) * AC;
     Mrun[ii] = -INFINITY;
     Lrun[ii] = 0.f;
   }
   // PLANES: 1 / s_i of the wave's two pair rows, fetched here through the scalar cache (wave-uniform address).  As a vector load at
   // the top of each row its s_waitcnt - vmcnt retires in order - drained every pair tile in flight, twice per wave and phase 2.
-  float inv_s2[RPW];
+  float inv_s2[2];
 #pragma unroll
-  for (int ii = 0; ii < RPW; ++ii) inv_s2[ii] = 1.0f;
+  for (int ii = 0; ii < 2; ++ii) inv_s2[ii] = 1.0f;
   if constexpr (PLANES) {
-    const float* ep = esc + 2 * (prow0 + i0 + RPW * __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    const float* ep = esc + 2 * (prow0 + i0 + 2 * __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
 #pragma unroll
-    for (int ii = 0; ii < RPW; ++ii) inv_s2[ii] = ep[2 * ii + 1];
+    for (int ii = 0; ii < 2; ++ii) inv_s2[ii] = ep[2 * ii + 1];
   }
 
 #pragma unroll 1
@@ -229,7 +217,7 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
     int lane = lane0;
     asm volatile("" : "+v"(lane));
     const int l15 = lane & 15, q = lane >> 4;
-    f32x4 ev[RPW][NT][4];
+    f32x4 ev[2][NT][4];
     f32x4 wv4[2][2];  // PLANES: the bias weights of lane (head, channel group), requested in phase 1's tail AHEAD of the first pair tiles:
                       // vmcnt retires in order, so loaded behind them they would cost every wave a pair-tile latency in front of the barrier
     auto load_e_tile = [&](int ii, int cc_, int jt) {
@@ -243,10 +231,9 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
         for (int r = 0; r < 4; ++r) ev[ii][jt][r] = __builtin_nontemporal_load(ep + r * (AC / 4));
       }
     };
-    // ---------------------------------------------------------------- phase 1: wave = head (NW = 4: two heads, one after the other)
-#pragma unroll
-    for (int hw = 0; hw < HPW; ++hw) {
-      const int h = HPW * wv + hw;
+    // ---------------------------------------------------------------- phase 1: wave = head
+    {
+      const int h = wv;
       const float scale_s = 0.17677669529663687f;                    // 32^-1/2  (:353)
       const float coef_p = -0.5f * 0.16666666666666666f * gamma[h];  // -1/2 (4.5*8)^-1/2 gamma_h  (:372, :431-436)
       // line-shaped loads of one key tile (16 keys): k_s 16 x 128 B (8 lanes per key), gk 16 x 96 B (6 lanes per key)
@@ -307,7 +294,7 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
         if (jt + 1 < NT) nxt = read_frags(jt + 1);
         if (jt + SD < NT) {
           load_keys(jt % SD, jt + SD);  // slot of tile jt (staged two iterations ago)
-        } else if (jt + E_EARLY >= NT && hw == HPW - 1) {
+        } else if (jt + E_EARLY >= NT) {
           if constexpr (PLANES) {
             if (jt + E_EARLY == NT) {
               const int hh = lane & 7, qq = lane >> 4;
@@ -352,8 +339,8 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
           S[(4 * q + r) * IS + h * HS + jt * 16 + l15] = scale_t * (acc[r] * scale_s + coef_p * d2);
           if constexpr (TAPE) tape_d2[((static_cast<int64_t>(b) * AH + h) * K + i0 + 4 * q + r) * K + jt * 16 + l15] = d2;
         }
-        if (c == 0 && jt == 0 && hw == 0) stamp(6);
-        if (c == 0 && jt == 3 && hw == 0) stamp(7);
+        if (c == 0 && jt == 0) stamp(6);
+        if (c == 0 && jt == 3) stamp(7);
       }
     }
     if (c == 0) stamp(1);
@@ -437,8 +424,8 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
         const int rrow = 4 * q + (l15 >> 2);
         const int rd_off = rrow * 128 + 8 * ((l15 & 3) ^ (4 * ((rrow >> 1) & 3)) ^ (2 * (rrow & 1)));  // ^ 32 ct: unit 4 ct + (l15 & 3) of row rrow
 #pragma unroll
-        for (int ii = 0; ii < RPW; ++ii) {
-          const int il = RPW * wv + ii;  // local row
+        for (int ii = 0; ii < 2; ++ii) {
+          const int il = 2 * wv + ii;  // local row
           float* Srow = S + il * IS + h * HS;
           const float inv_s = inv_s2[ii];  // 1 / s_i: the power-of-two scale of this pair row's planes
           const float bscale_r = bscale * inv_s, oscale_r = oscale * inv_s;
@@ -512,7 +499,7 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
               constexpr int dummy_ = 0;
               (void)dummy_;
               const int nx = ii * NT + 2 * T + RT;  // compile-time after unrolling
-              if (nx < RPW * NT) {
+              if (nx < 2 * NT) {
                 load_e_tile(nx / NT, c, nx % NT);
                 load_e_tile((nx + 1) / NT, c, (nx + 1) % NT);
                 MEM_FENCE();
@@ -689,116 +676,9 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
     }
     if (c == 0) stamp(3);
 
-    // ---------------------------------------------------------------- phase 3: wave = head (NW = 4: two heads, one after the other)
-    if constexpr (VPL) {
+    // ---------------------------------------------------------------- phase 3: wave = head
+    {
       const int h = wv;
-      constexpr int TPC = NT / 2;  // 32-key steps per chunk
-      const int Tsteps = K >> 5;   // per patch
-      // all value fragments of this chunk (TPC x 8 KiB per head), requested before the barrier: [step][tile 0..3][plane h1, h2]
-      int lane3 = lane0;
-      asm volatile("" : "+v"(lane3));
-      const f32x4* vsrc = vpl + ((static_cast<int64_t>(b) * AH + h) * Tsteps + c * TPC) * 512 + lane3;
-      f32x4 vf[TPC][8];
-#pragma unroll
-      for (int T = 0; T < TPC; ++T)
-#pragma unroll
-        for (int u = 0; u < 8; ++u) vf[T][u] = vsrc[(T * 8 + u) * 64];
-      // 1 / s of the head's v_s and point planes, per step (wave-uniform: scalar loads); x 2^-15 for the scaled P
-      const float* scp = vsc + ((static_cast<int64_t>(b) * AH + h) * Tsteps + c * TPC) * 2;
-      float isc[TPC][3];
-#pragma unroll
-      for (int T = 0; T < TPC; ++T) {
-        isc[T][0] = isc[T][1] = scp[2 * T] * (1.0f / 32768.0f);
-        isc[T][2] = scp[2 * T + 1] * (1.0f / 32768.0f);
-      }
-      MEM_FENCE();
-      __syncthreads();  // exp(logit - M) of all rows and the rescale factors are in LDS (the value fragments arrive during the wait)
-      if (c == 0) stamp(4);
-      // tot: o_s dims 0..15 | o_s dims 16..31 | x, y of the points | z of the points.  Column 8 of the z tile is the planes' ones column:
-      // mass = sum_j (p1 + p2)_j, the probability mass AS THE SPLIT PLANES SEE IT - the local points are (sum_j P~_j (gv_j - c) -
-      // (t_i - c) mass) / L = sum_j P~_j (gv_j - t_i) / L, so the 2^-22 the planes cut off P multiplies the distance of key j from the
-      // QUERY (small where the mass is), not from the patch's reference point c.
-      f32x4 tot[4], mass = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int u = 0; u < 4; ++u) tot[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* Prow = S + l15 * IS + h * HS + 4 * q;  // A operand: P[i = l15][j = 32 T + 16 tl + 4 q + r] <-> k slot (q, e = 4 tl + r)
-#pragma unroll
-      for (int T = 0; T < TPC; ++T) {
-        const f32x4 pa0 = *reinterpret_cast<const f32x4*>(Prow + (2 * T) * 16), pa1 = *reinterpret_cast<const f32x4*>(Prow + (2 * T + 1) * 16);
-        f16x8 p1, p2;  // 2^15 P = p1 + p2 (P <= 1: as high in the fp16 range as overflow allows, so small P keep their second plane)
-#pragma unroll
-        for (int e8 = 0; e8 < 8; ++e8) {
-          const float x = 32768.0f * (e8 < 4 ? pa0[e8 & 3] : pa1[e8 & 3]);
-          const _Float16 hh = static_cast<_Float16>(x);
-          p1[e8] = hh;
-          p2[e8] = static_cast<_Float16>(x - static_cast<float>(hh));
-        }
-        f32x4 acc[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(p2, __builtin_bit_cast(f16x8, vf[T][2 * u]), acc[u], 0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(p1, __builtin_bit_cast(f16x8, vf[T][2 * u + 1]), acc[u], 0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(p1, __builtin_bit_cast(f16x8, vf[T][2 * u]), acc[u], 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          tot[0][r] = __builtin_fmaf(isc[T][0], acc[0][r], tot[0][r]);
-          tot[1][r] = __builtin_fmaf(isc[T][1], acc[1][r], tot[1][r]);
-          tot[2][r] = __builtin_fmaf(isc[T][2], acc[2][r], tot[2][r]);
-          tot[3][r] = __builtin_fmaf(isc[T][2], acc[3][r], tot[3][r]);
-          mass[r] += acc[3][r];  // (lanes l15 == 8: the ones column, unscaled)
-        }
-      }
-      // D rows i = 4 q + r, column n = l15; earlier chunks' sums are rescaled through the feature row
-      const float* tc = t + prow0 * 3;  // the reference point of the value planes' coordinates: the patch's first translation
-      const float c0 = tc[0], c1 = tc[1], c2 = tc[2];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int il = 4 * q + r;
-        const int64_t row = prow0 + i0 + il;
-        const float fac = st_fac[il * AH + h], inv = st_inv[il * AH + h];
-        float* fr = feat + row * AF;
-        float o0 = tot[0][r], o1 = tot[1][r];
-        float* po = fr + FOFF_OS + h * ADS + l15;
-        if (MULTI && c > 0) {
-          o0 += po[0] * fac;
-          o1 += po[16] * fac;
-        }
-        po[0] = o0 * inv;
-        po[16] = o1 * inv;
-        const float gy_lane = __shfl_xor(tot[2][r], 8);  // lanes 0..7 hold x of point l15, lanes 8..15 y of point l15 - 8
-        float m_ = __shfl(mass[r], (lane & 48) | 8) * (1.0f / 32768.0f);  // the mass of row 4 q + r, from the ones column's lane
-        if (l15 < 8) {
-          float* fo = fr + FOFF_OL + h * 24 + 3 * l15;
-          float* fm = fr + FOFF_ON + h * AP + l15;  // the norm's slot parks the running mass between chunks
-          float g0_ = tot[2][r], g1_ = gy_lane, g2_ = tot[3][r];
-          if (MULTI && c > 0) {  // running (unnormalised, centred) sums are parked in the o_l slot between chunks
-            g0_ += fo[0] * fac;
-            g1_ += fo[1] * fac;
-            g2_ += fo[2] * fac;
-            m_ += fm[0] * fac;
-          }
-          if (last) {
-            const float* Rr = R + row * 9;
-            const float* tr = t + row * 3;
-            const float dx = (g0_ - m_ * (tr[0] - c0)) * inv, dy = (g1_ - m_ * (tr[1] - c1)) * inv, dz = (g2_ - m_ * (tr[2] - c2)) * inv;
-            const float lx = dx * Rr[0] + dy * Rr[1] + dz * Rr[2];  // (p - t) R^T   (diffab_pytorch.py:336)
-            const float ly = dx * Rr[3] + dy * Rr[4] + dz * Rr[5];
-            const float lz = dx * Rr[6] + dy * Rr[7] + dz * Rr[8];
-            fo[0] = lx; fo[1] = ly; fo[2] = lz;
-            fm[0] = sqrtf(lx * lx + ly * ly + lz * lz);
-          } else {
-            fo[0] = g0_; fo[1] = g1_; fo[2] = g2_;
-            fm[0] = m_;
-          }
-        }
-      }
-    } else {
-#pragma unroll
-    for (int hw = 0; hw < HPW; ++hw) {
-      const int h = HPW * wv + hw;
       const int pp = l15 & 7;
       // Point sums: columns 0..7 of ONE MFMA tile hold x of the 8 points, columns 8..15 y (z in a second tile, its upper half
       // duplicates): 4 f32 MFMAs per key step instead of 5 - this phase is bound by exactly those (32 cycles each).
@@ -839,10 +719,8 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
 #pragma unroll
       for (int jt = 0; jt < SD3; ++jt) load_vals(jt, jt);
       MEM_FENCE();
-      if (hw == 0) {
-        __syncthreads();  // exp(logit - M) of all rows and the rescale factors are in LDS (the first value tiles arrive during the wait)
-        if (c == 0) stamp(4);
-      }
+      __syncthreads();  // exp(logit - M) of all rows and the rescale factors are in LDS (the first value tiles arrive during the wait)
+      if (c == 0) stamp(4);
       stage_vals(0, 0);
       ValFrag vcur = read_vfrags(0);
       if (NT > 1) stage_vals(1 % SD3, 1);
@@ -916,15 +794,14 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
         }
       }
     }
-    }  // !VPL
     if (!last) __syncthreads();  // the next chunk's phase 1 overwrites the image
   }
   stamp(5);
 }
 
 // dynamic LDS of one item: logits image + per-wave scratch + softmax state + bias fragments + per-wave query-point tiles
-constexpr size_t ipa_attn_lds_bytes(int nt, int nw = 8, bool planes = false) {
-  return (static_cast<size_t>(TI) * (AH * (16 * nt + 8) + 8) + nw * 2 * 16 * 72 + 2 * TI * AH + (planes ? 0 : 4 * 64 * 4) + nw * TI * 24) * sizeof(float);
+constexpr size_t ipa_attn_lds_bytes(int nt) {
+  return (static_cast<size_t>(TI) * (AH * (16 * nt + 8) + 8) + 8 * 2 * 16 * 72 + 2 * TI * AH + 4 * 64 * 4 + 8 * TI * 24) * sizeof(float);
 }
 
 }  // namespace diffab

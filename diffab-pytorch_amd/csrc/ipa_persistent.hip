@@ -15,7 +15,6 @@
 #include "denoiser_internal.h"
 #define AT_STAMP_REALTIME 1  // the diagnostic stamps of this file's kernels use the chip-wide 100 MHz counter (comparable between CUs)
 #include "ipa_attn_tile.h"
-#include "attn_planes_tile.h"
 #include "proj_frames_h3_tile.h"
 #include "rowgemm_h3_tile.h"
 #include "mlp_chain_tile.h"
@@ -35,11 +34,9 @@ struct ModuleArgs {
   const float* pair;         // fp16 planes of the pair embedding (launch_pair_split)
   const float* esc;          // {s, 1 / s} per pair row
   const int* ctx_of_row;     // shared contexts: [B] context of each patch's pair rows (null: the identity)
-  float* vpl;                // value planes of the P x V product (proj_frames_h3_tile.h), null: phase 3 from the fp32 value columns
-  float* vsc;                // their scales
   const float* R;            // [B K][9]
   const float* t;            // [B K][3]
-  const char* planes;        // per layer: ipa_layer_planes_bytes() (projection planes | to_out planes | w_bias, gamma, b_out)
+  const char* planes;        // per layer: ipa_layer_planes_bytes() (w_bias, gamma, b_out | projection planes | to_out planes | 1 / scales)
   size_t layer_stride, pj_off, out_off, wis_off, small_off;  // offsets of the fp16 planes, 1 / scale vectors and small vectors in a layer's block
   unsigned long long* stamps;  // diagnostics (null in production): [item][wave][8] of the attention tiles + [B][NL][4] phase stamps behind them
   // the denoiser's MLPs as phases of the same launch (null emb_X: not fused): the embedding MLP of the patch's rows in front of layer 0
@@ -53,7 +50,7 @@ struct ModuleArgs {
 
 // KRES: residues per patch - 128 (one 128-row dense tile per patch, single-chunk attention items) or 256 (BASELINE config 5: two dense
 // tiles, sixteen attention items of two 128-key chunks with the online softmax across them - ipa_attn_tile<8, true, ...>)
-template <bool VPL, int KRES>
+template <int KRES>
 __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const ModuleArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int K = KRES, NTILE = K / TI, DT = K / 128;  // DT: dense 128-row tiles per patch
@@ -104,23 +101,12 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      if constexpr (VPL) {  // ---- the value side of the patch as fp16 planes for phase 3 of its attention items (attn_planes_tile.h)
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        aplanes::attn_value_planes_tile(lds, tid, b, a.proj, a.t, K, reinterpret_cast<_Float16*>(a.vpl), a.vsc);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // the scales were written (vector stores) over the previous layer's at the same addresses and are read through the SCALAR cache
-        // by phase 3: drop its lines (the vector L1 needs nothing: same CU, written through)
-        __builtin_amdgcn_s_dcache_inv();
-      }
       pstamp(b, l, 1);
       // ---- attention: the eight row tiles of the patch
 #pragma unroll 1
       for (int tile = 0; tile < NTILE; ++tile) {
-        ipa_attn_tile<8, (KRES > 128), true, false, 8, VPL>(lds, b, tile, static_cast<unsigned>((b * a.NL + l) * NTILE + tile), a.proj, a.pair, a.R,
-                                                            a.t, small, small + 512, a.feat, K / 128, a.stamps, a.esc, nullptr, nullptr,
-                                                            reinterpret_cast<const f32x4*>(a.vpl), a.vsc, a.ctx_of_row);
+        ipa_attn_tile<8, (KRES > 128), true>(lds, b, tile, static_cast<unsigned>((b * a.NL + l) * NTILE + tile), a.proj, a.pair, a.R, a.t, small,
+                                             small + 512, a.feat, K / 128, a.stamps, a.esc, nullptr, nullptr, a.ctx_of_row);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // the next tile's phase 1 overwrites the image; the last tile's feature rows are complete
       }
@@ -173,7 +159,7 @@ void set_module_stagger(int ticks, int classes) {
 void set_module_stamps(void* p) { g_module_stamps = static_cast<unsigned long long*>(p); }
 
 bool ipa_module_persistent_supported(const diffab_dims* d) {
-  return fast_path_supported(d) && (d->K == 128 || d->K == 256) && d->NL >= 1 && dense_h3_enabled();  // (the kernel holds the fp16 tiles only)
+  return fast_path_supported(d) && (d->K == 128 || d->K == 256) && d->NL >= 1;
 }
 
 // planes: d->NL x ipa_layer_planes_bytes() (ipa_layer_split_weights); pair_planes: launch_pair_split() of n_ctx patches (0: d->B), state
@@ -194,8 +180,6 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
   a.pair = pair_planes + 64;
   a.esc = pair_row_scales(d, pair_planes, n_ctx);
   a.ctx_of_row = ctx_of_row;
-  const bool vpl_on = value_planes_enabled();
-  if (vpl_on) ipa_ws_value_planes(d, ws, &a.vpl, &a.vsc);
   a.R = R;
   a.t = t;
   a.planes = static_cast<const char*>(planes);
@@ -219,21 +203,16 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
   int dev = 0, ncu = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   const int grid = d->B < ncu ? d->B : ncu;  // one work-group per CU (149 KiB of LDS each); more patches than CUs: a work-group walks its queue
-#define MODULE_LAUNCH(VPL_, K_)                                                                                                     \
+#define MODULE_LAUNCH(K_)                                                                                                       \
   do {                                                                                                                            \
-    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_module_persistent_kernel<VPL_, K_>),                   \
+    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_module_persistent_kernel<K_>),                         \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kModuleLdsBytes)));        \
     timer_begin(st);                                                                                                              \
-    hipLaunchKernelGGL((ipa_module_persistent_kernel<VPL_, K_>), dim3(grid), dim3(512), kModuleLdsBytes, st, a);                  \
+    hipLaunchKernelGGL((ipa_module_persistent_kernel<K_>), dim3(grid), dim3(512), kModuleLdsBytes, st, a);                        \
     timer_end(st);                                                                                                                \
   } while (0)
-  if (d->K == 128) {
-    if (vpl_on) MODULE_LAUNCH(true, 128);
-    else MODULE_LAUNCH(false, 128);
-  } else {
-    if (vpl_on) MODULE_LAUNCH(true, 256);
-    else MODULE_LAUNCH(false, 256);
-  }
+  if (d->K == 128) MODULE_LAUNCH(128);
+  else MODULE_LAUNCH(256);
 #undef MODULE_LAUNCH
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;

@@ -1,5 +1,6 @@
-// proj_frames_b6_tile.h - the six IPA projections + local->global frames of one 128-row tile on the bf16 matrix cores (six-term split,
-// gemm_bf16x6.hip) as a device function, so that more than one kernel can run it.
+// proj_frames_b6_tile.h - the x-stationary product of one 128-row tile on the bf16 matrix cores (six-term split, gemm_bf16x6.hip) as a
+// device function: the bf16x6 form of the projections + local->global frames, now the fp32-accurate reference of the fp16 x-stationary
+// product (proj_frames_h3_tile.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -12,8 +13,7 @@ using b6tile::f32x4;
 using b6tile::bf16x8;
 using b6tile::split3;
 #define PJTILE_FENCE() asm volatile("" ::: "memory")
-constexpr int PJ_NP = 1344, PJ_GQ = 768, PJ_GK = 960, PJ_GV = 1152;  // column map of the projection buffer (ipa_attn_tile.h: ANP, OFF_*)
-constexpr int PJ_B = 96, PJ_NB = PJ_NP / PJ_B, PJ_ROWS = 128;
+constexpr int PJ_B = 96, PJ_ROWS = 128;
 constexpr int PJ_LD = 80;                                 // bf16 per staged row: 64 k + 16 pad (160 bytes)
 constexpr int PJ_STAGE_ELEMS = 3 * PJ_B * 64;             // bf16 per stage in global memory (36 864 bytes)
 constexpr int PJ_STAGE_LDS = 3 * PJ_B * PJ_LD;            // bf16 per stage in LDS (46 080 bytes)
@@ -23,18 +23,15 @@ struct __attribute__((packed, aligned(4))) pjb_f3 { float x, y, z; };
 // Geometry at run time: N output columns in NB (even) blocks of 96 (columns past N are zero planes, never stored), rows of Y ldy
 // floats apart, frames applied to blocks >= frames_from (NB: none; R, t may then be null).  The same kernel is the input-gradient
 // product of to_out: dfeat[M x 1024] = dy[M x 128] Wo, with the planes of Wo^T (xsplit_kernel).
-// PROJ: the geometry of the six projections at compile time (runtime geometry costs this kernel 11 %: 70 vs 63 us)
 // SPLIT: the blocks are shared by gridDim.y work-groups per row tile (each re-reads the x rows and streams its share of the weights):
 // twice the groups of half the length when 128-row tiles alone would leave CUs idle (B <= 128 patches of 128 residues per GPU)
-// One 128-row tile (rows tile_m * 128 ..) as a device function: the body of proj_frames_b6_kernel (gemm_bf16x6.hip) and of the
-// patch-resident module kernel (ipa_persistent.hip).  512 threads (tid: the thread index, a parameter so that a caller inside a loop
-// can hand over an opaque copy); pj_lds: PJ_LDS_BYTES of LDS, 16-byte aligned; split_i of split_n work-groups share the column blocks.
-template <bool FULL, bool PROJ, bool SPLIT = false>  // FULL: M is a multiple of 128, no row guards
+// One 128-row tile (rows tile_m * 128 ..): the body of proj_frames_b6_kernel (gemm_bf16x6.hip).  512 threads (tid: the thread index, a
+// parameter so that a caller inside a loop can hand over an opaque copy); pj_lds: PJ_LDS_BYTES of LDS, 16-byte aligned; split_i of split_n work-groups share the column blocks.
+template <bool FULL, bool SPLIT = false>  // FULL: M is a multiple of 128, no row guards
 __device__ __forceinline__ void proj_frames_b6_tile(__bf16* __restrict__ pj_lds, const int tid, const int tile_m, const int split_i,
                                                     const int split_n, const float* __restrict__ X, const __bf16* __restrict__ Wc,
                                                     const float* __restrict__ R, const float* __restrict__ t, float* __restrict__ Y,
-                                                    int M, int N_, int NB_, int ldy_, int frames_from_) {
-  const int N = PROJ ? PJ_NP : N_, NB = PROJ ? PJ_NB : NB_, ldy = PROJ ? PJ_NP : ldy_, frames_from = PROJ ? PJ_GQ / PJ_B : frames_from_;
+                                                    int M, int N, int NB, int ldy, int frames_from) {
   const int blk0 = SPLIT ? (NB * split_i) / split_n : 0;
   const int blk1 = SPLIT ? (NB * (split_i + 1)) / split_n : NB;
   // pj_lds: [2][3][96][PJ_LD] weights, then [128][12] frames (fp32)

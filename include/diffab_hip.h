@@ -193,18 +193,11 @@ int diffab_debug_set_attn_stamps(void* device_buffer);
 /* Diagnostics of the patch-resident module kernel (DIFFAB_FLAG_PERSISTENT_MODULE): its start-up stagger (work-groups of class
  * (index / 8) % classes start class x ticks late, ticks of 10 ns; default 8 x 1000: eight classes 10 us apart),
  * and a stamp buffer of (B NL 8 tiles x 8 waves x 8) + (B NL 4) uint64 filled with 100 MHz s_memrealtime stamps (NULL: off). */
-int diffab_debug_set_attn_variant(int32_t v); /* A/B switches (tests, tools; process-global): bit 0 = four-wave work-groups in the plane
-                                                 attention kernel (two per CU; measured slower), bit 2 (4) = the PairEmbedding forward / backward
-                                                 as their unfused launches where the fused kernel would apply, 8 (alone) = the six
-                                                 projections and to_out as six-term bf16 split products (rounds 3-4) instead of the
-                                                 three-term fp16 ones (and with them the backward's d feat and weight-gradient products) -
-                                                 per-layer launches only, bit 5 (32) = only the weight-gradient products of the training
-                                                 backward in the six-term bf16 form, bit 6 (64) = the PairEmbedding backward's matrix-core
-                                                 kernels (csrc/pair_chain_bwd.hip: 64-wide chain, one-hot table / coefficient sums) as the
-                                                 separate launches they replaced, bit 4 (16) = value planes: a pass after the
-                                                 projections cuts the value side (v_s, global value points) into two fp16 planes and phase 3
-                                                 of the attention tile (P x V) runs on the f16 matrix cores (parity-green, measured slower
-                                                 overall: profiles/r06_attention.md).  0 = defaults. */
+int diffab_debug_set_attn_variant(int32_t v); /* Reference paths for tests and tools (process-global): bit 2 (4) = the PairEmbedding
+                                                 forward / backward as their unfused launches where the fused kernel would apply, bit 6
+                                                 (64) = the PairEmbedding backward's matrix-core kernels (csrc/pair_chain_bwd.hip: 64-wide
+                                                 chain, one-hot table / coefficient sums) as the separate launches they replaced.  0 =
+                                                 defaults.  Any other bit: DIFFAB_ERR_ARG, the switch is left as it was. */
 int diffab_debug_set_module_stagger(int32_t ticks_10ns, int32_t classes);
 int diffab_debug_set_module_stamps(void* device_buffer);
 /* The cross-stream ordering guard described under "Streams" above: on / off (default since round 6), process-wide. */

@@ -30,6 +30,20 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in l.diffab_version()
 
 
+def test_attn_variant_switch_takes_only_the_reference_path_bits():
+    """diffab_debug_set_attn_variant keeps bits 4 (unfused PairEmbedding launches) and 64 (separate PairEmbedding backward launches);
+    any other bit is refused with DIFFAB_ERR_ARG and a message, and leaves the switch as it was (host state only: no GPU needed)."""
+    l = _hip.load_library()
+    try:
+        for v in (0, 4, 64, 68):
+            assert l.diffab_debug_set_attn_variant(v) == 0, v
+        for v in (1, 8, 16, 32):
+            assert l.diffab_debug_set_attn_variant(v) == -1, v  # DIFFAB_ERR_ARG
+            assert b"debug_set_attn_variant" in l.diffab_last_error(), v
+    finally:
+        assert l.diffab_debug_set_attn_variant(0) == 0
+
+
 def test_struct_layouts_match_header():
     assert ctypes.sizeof(_hip.Dims) == 40
     assert ctypes.sizeof(_hip.IpaLayerWeights) == 80

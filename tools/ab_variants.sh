@@ -1,7 +1,7 @@
 #!/bin/bash
 # On the GPU box: the bench's step time for several builds of the library, one line each, same box, back to back.
 # usage: tools/ab_variants.sh [-r rounds] name=path/to/libdiffab_hip.so[,bench args] ...   ("base" = the product library)
-#        e.g. novpl=diffab-pytorch_amd/lib/libdiffab_hip.so,--attn-variant,16
+#        e.g. base b128=diffab-pytorch_amd/lib/libdiffab_hip.so,--batch,128
 # Per build: the module-launch form (the headline) and the per-layer-launch form (whose timed kernel is the attention tile's own launch).
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 rounds=1
