@@ -387,6 +387,47 @@ static SampleBuffers carve_sample(const diffab_dims* d, void* ws, int n_pair = 0
   return s;
 }
 
+// The rule by which the reverse loop and design scoring choose the patch-resident module launch (given its other preconditions): K = 128
+// and a batch that fills the chip with one work-group per patch, without a mostly idle last round.
+static bool module_launch_fills_chip(const diffab_dims* d) {
+  if (!ipa_module_persistent_supported(d)) return false;
+  int dev = 0, ncu = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int rounds = (d->B + ncu - 1) / ncu;
+  // (K = 256 - two dense tiles and sixteen two-chunk attention items per patch in the same launch, round 6 - measures SLOWER than its
+  // per-layer launches at B = 512: 19.5 against 18.6 ms per step; it is bitwise the same and stays behind the explicit flag)
+  return d->K == 128 && d->B >= ncu && static_cast<double>(d->B) >= 0.85 * rounds * ncu;
+}
+
+// diffab_score_designs: the state of one chunk of d->B evaluated rows, and the step buffers of its denoiser call
+struct ScoreBuffers {
+  int* t_list;    // [kTrajRows] the caller's timestep grid (device copy)
+  float* beta;    // [B] beta[t_j] of every row
+  int* ctx_of_row;  // [B] the context of every row
+  int64_t* seq_t;
+  float *x_t, *O_t, *eps, *eps_hat;  // (B,K,3), (B,K,3,3), (B,K,3), (B,K,3)
+  float* res_ctx;  // (B,K,D) the residue context of every row (gathered per chunk)
+  void* step;
+  size_t bytes;
+};
+static ScoreBuffers carve_score(const diffab_dims* d, void* ws, int n_ctx) {
+  Carver c(ws);
+  const size_t rows = static_cast<size_t>(d->B) * d->K;
+  ScoreBuffers s;
+  s.t_list = c.take<int>(kTrajRows);
+  s.beta = c.take<float>(d->B);
+  s.ctx_of_row = c.take<int>(d->B);
+  s.seq_t = c.take<int64_t>(rows);
+  s.x_t = c.take<float>(rows * 3);
+  s.O_t = c.take<float>(rows * 9);
+  s.eps = c.take<float>(rows * 3);
+  s.eps_hat = c.take<float>(rows * 3);
+  s.res_ctx = c.take<float>(rows * d->D);
+  s.step = c.take<char>(carve_step(d, nullptr, n_ctx).bytes);
+  s.bytes = c.bytes();
+  return s;
+}
+
 }  // namespace diffab
 
 using namespace diffab;
@@ -748,14 +789,8 @@ int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weight
   // shows in the samples) when the batch fills the chip with one work-group per patch: B = 256 is 2.60 ms per step against 2.70.  Fewer
   // patches than CUs leave CUs idle for the whole module (B = 8: 2.07 ms against 0.47), a ragged last round of patches costs a module
   // time for a few of them - those shapes keep the per-layer launches.
-  if (!(flags & DIFFAB_FLAG_MULTI_LAUNCH) && pair_ready && fold && use_b6_gemm(flags) && ipa_module_persistent_supported(d)) {
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int rounds = (d->B + ncu - 1) / ncu;
-    // (K = 256 - two dense tiles and sixteen two-chunk attention items per patch in the same launch, round 6 - measures SLOWER than its
-    // per-layer launches at B = 512: 19.5 against 18.6 ms per step; it is bitwise the same and stays behind the explicit flag)
-    if (d->K == 128 && d->B >= ncu && static_cast<double>(d->B) >= 0.85 * rounds * ncu) flags |= DIFFAB_FLAG_PERSISTENT_MODULE;
-  }
+  if (!(flags & DIFFAB_FLAG_MULTI_LAUNCH) && pair_ready && fold && use_b6_gemm(flags) && module_launch_fills_chip(d))
+    flags |= DIFFAB_FLAG_PERSISTENT_MODULE;
   // DIFFAB_FLAG_SKIP_UNUSED_ROWS: the step's outputs (eps, O0, posterior) are read for GENERATED residues only (reverse_update leaves
   // the others alone), so the last layer's attention is needed only for row tiles that contain one; every other layer feeds keys and
   // values of all rows to the next.  Same trajectory, bit for bit; the work skipped depends on the mask, so bench.py's headline keeps it off.
@@ -835,6 +870,88 @@ int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weight
   if (ei != hipSuccess) {
     set_error("sample_loop: graph capture / replay failed: %s", hipGetErrorString(ei));
     return DIFFAB_ERR_HIP;
+  }
+  return DIFFAB_OK;
+}
+
+size_t diffab_score_workspace_bytes(const diffab_dims* d, int32_t n_ctx) {
+  if (check_dims(d, "score_workspace_bytes")) return 0;
+  if (n_ctx < 1 || static_cast<int64_t>(n_ctx) * d->K >= (1ll << 31)) {
+    set_error("score_workspace_bytes: need 1 <= n_ctx and n_ctx*K < 2^31 (n_ctx=%d)", n_ctx);
+    return 0;
+  }
+  return carve_score(d, nullptr, n_ctx).bytes;
+}
+
+int diffab_score_designs(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* fwd_tab,
+                         const int64_t* seq, const float* x, const float* O, const uint8_t* gen_mask, const uint8_t* res_mask,
+                         int32_t n_designs, const float* res_ctx, const float* pair_ctx, int32_t n_ctx, const int32_t* ctx_of_design,
+                         const int32_t* t_list, int32_t n_t, int32_t n_draws, uint64_t seed, int64_t first_design, float* out_terms,
+                         float* out_residue, const diffab_score_noised* noised, void* workspace, size_t workspace_bytes, uint32_t flags,
+                         void* stream) {
+  StreamOrder order_(stream);
+  // every check on the host, before anything is enqueued
+  if (int rc = check_dims(d, "score_designs")) return rc;
+  if (int rc = check_denoiser_weights(d, w)) return rc;
+  DIFFAB_REQUIRE(d->V == 21, DIFFAB_ERR_ARG, "score_designs: the sequence diffusion has 21 classes (V = %d)", d->V);
+  DIFFAB_REQUIRE(s && s->T > 0 && s->T < kTrajRows && s->alpha_bar && s->alpha_bar_sqrt && s->one_minus_alpha_bar_sqrt && s->beta,
+                 DIFFAB_ERR_ARG, "score_designs: bad schedule (need 1 <= T < %d)", kTrajRows);
+  DIFFAB_REQUIRE(fwd_tab && fwd_tab->sigmas && fwd_tab->cdf && fwd_tab->n_bins > 0 && fwd_tab->n_sigmas >= s->T + 1, DIFFAB_ERR_ARG,
+                 "score_designs: forward IGSO3 table must have T+1 rows");
+  DIFFAB_REQUIRE(seq && x && O && gen_mask && res_ctx && pair_ctx && t_list && out_terms && workspace, DIFFAB_ERR_ARG,
+                 "score_designs: null pointer (seq, x, O, gen_mask, res_ctx, pair_ctx, t_list, out_terms and workspace are required)");
+  DIFFAB_REQUIRE(n_designs >= 1, DIFFAB_ERR_ARG, "score_designs: n_designs = %d < 1", n_designs);
+  DIFFAB_REQUIRE(first_design >= 0 && first_design + n_designs <= (1ll << 32), DIFFAB_ERR_ARG,
+                 "score_designs: first_design + n_designs must lie in [0, 2^32] (Philox patch ids)");
+  DIFFAB_REQUIRE(n_t >= 1 && n_t <= s->T, DIFFAB_ERR_ARG, "score_designs: n_t = %d outside [1, T = %d]", n_t, s->T);
+  for (int j = 0; j < n_t; ++j) {
+    DIFFAB_REQUIRE(t_list[j] >= 1 && t_list[j] <= s->T, DIFFAB_ERR_ARG, "score_designs: t_list[%d] = %d outside [1, T = %d]", j, t_list[j], s->T);
+    for (int i = 0; i < j; ++i)
+      DIFFAB_REQUIRE(t_list[i] != t_list[j], DIFFAB_ERR_ARG, "score_designs: t_list[%d] = t_list[%d] = %d (duplicate step)", i, j, t_list[j]);
+  }
+  DIFFAB_REQUIRE(n_draws >= 1 && n_draws <= 65536, DIFFAB_ERR_ARG, "score_designs: n_draws = %d outside [1, 65536]", n_draws);
+  DIFFAB_REQUIRE(n_ctx >= 1 && static_cast<int64_t>(n_ctx) * d->K < (1ll << 31), DIFFAB_ERR_ARG, "score_designs: need 1 <= n_ctx, n_ctx*K < 2^31");
+  DIFFAB_REQUIRE(ctx_of_design != nullptr || n_ctx == n_designs, DIFFAB_ERR_ARG,
+                 "score_designs: without ctx_of_design n_ctx must equal n_designs (%d != %d)", n_ctx, n_designs);
+  for (int r = 0; ctx_of_design != nullptr && r < n_designs; ++r)
+    DIFFAB_REQUIRE(ctx_of_design[r] >= 0 && ctx_of_design[r] < n_ctx, DIFFAB_ERR_ARG, "score_designs: ctx_of_design[%d] = %d outside [0, %d)", r,
+                   ctx_of_design[r], n_ctx);
+  const uint32_t keep = flags & (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE);
+  DIFFAB_REQUIRE(keep != (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE), DIFFAB_ERR_ARG,
+                 "score_designs: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to score");
+  const ScoreBuffers sb = carve_score(d, workspace, n_ctx);
+  DIFFAB_REQUIRE(workspace_bytes >= sb.bytes, DIFFAB_ERR_WORKSPACE, "score_designs: workspace %zu < %zu bytes", workspace_bytes, sb.bytes);
+  // (the reverse loop's graph replay and skipped row tiles have no meaning here; the design-mode bits steer the noising and the terms)
+  flags &= ~(keep | DIFFAB_FLAG_GRAPH_SAMPLER | DIFFAB_FLAG_SKIP_UNUSED_ROWS);
+  hipStream_t st = as_stream(stream);
+  DIFFAB_HIP_CHECK(hipMemcpyAsync(sb.t_list, t_list, sizeof(int32_t) * n_t, hipMemcpyHostToDevice, st));
+  // once per call, as in diffab_sample_loop_shared: the folded weights and the fp16 pair planes of the n_ctx contexts
+  const StepBuffers b0 = carve_step(d, sb.step, n_ctx);
+  const bool fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) &&
+                    rowgemm128_ok(sb.res_ctx, d->D, b0.h1, d->D, d->B * d->K, d->D);
+  if (fold)
+    if (int rc = prepare_weights(d, w, b0, flags, st)) return rc;
+  if (!(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
+  const bool pair_ready = use_pair_planes(d, flags, pair_ctx, b0);
+  if (pair_ready)
+    if (int rc = launch_pair_split(d, pair_ctx, b0.pair, st, n_ctx)) return rc;
+  if (!(flags & DIFFAB_FLAG_MULTI_LAUNCH) && pair_ready && fold && use_b6_gemm(flags) && module_launch_fills_chip(d))
+    flags |= DIFFAB_FLAG_PERSISTENT_MODULE;
+  const diffab_score_noised out = noised ? *noised : diffab_score_noised{nullptr, nullptr, nullptr, nullptr};
+  const int64_t total = static_cast<int64_t>(n_designs) * n_t * n_draws;
+  for (int64_t q0 = 0; q0 < total; q0 += d->B) {
+    const ScoreChunk c{sb.t_list, n_t, n_draws, d->K, q0, d->B, static_cast<int>(total - q0 < d->B ? total - q0 : d->B), keep};
+    if (int rc = launch_score_noise(s, fwd_tab, c, seq, x, O, gen_mask, ctx_of_design, seed, first_design, sb.seq_t, sb.x_t, sb.O_t, sb.eps,
+                                    sb.beta, sb.ctx_of_row, out, st))
+      return rc;
+    if (int rc = launch_gather_rows(res_ctx, sb.ctx_of_row, d->B, static_cast<int64_t>(d->K) * d->D, sb.res_ctx, st)) return rc;
+    // per-row beta: the heads' folded beta columns come from the per-chunk table (launch_fold_tables on sb.beta)
+    if (int rc = denoise_step(d, w, sb.seq_t, sb.x_t, sb.O_t, sb.res_ctx, pair_ctx, sb.beta, sb.eps_hat, nullptr, nullptr, nullptr, nullptr,
+                              sb.step, flags, st, fold, pair_ready, nullptr, 0, nullptr, nullptr, true, nullptr, 0, sb.ctx_of_row, n_ctx))
+      return rc;
+    if (int rc = launch_score_losses(s, c, seq, O, gen_mask, res_mask, sb.seq_t, sb.O_t, sb.eps, sb.eps_hat, b0.vbuf, b0.logits, out_terms,
+                                     out_residue, st))
+      return rc;
   }
   return DIFFAB_OK;
 }

@@ -236,6 +236,28 @@ int launch_fill_beta(const diffab_sched* s, int t, int B, float* out, hipStream_
 int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hipStream_t st);  // [B][K / 16]: any generated residue in the tile
 // shared contexts: out[b] = src[ctx_of_row[b]] for the B rows of `row_floats` floats each (16-byte aligned rows)
 int launch_gather_rows(const float* src, const int* ctx_of_row, int B, int64_t row_floats, float* out, hipStream_t st);
+// design scoring (diffab_score_designs): a chunk of evaluated rows q = ((r n_t) + j) n_draws + m, q0 .. q0 + valid - 1, in buffers of
+// `rows` (d->B) rows; the noising kernel fills rows past `valid` with copies of the last valid row, the loss kernel reads the valid ones
+struct ScoreChunk {
+  const int* t_list;  // device [n_t]
+  int n_t, n_draws, K;
+  int64_t q0;
+  int rows, valid;
+  uint32_t keep;  // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE
+};
+constexpr int kScoreCtxMax = 256;  // designs per noising launch (their context indices are a by-value kernel argument)
+struct ScoreCtxTable {
+  int64_t r0;  // ctx[r - r0] = context of design r
+  int ctx[kScoreCtxMax];
+};
+// s_t / x_t / O_t / eps (rows, K, ...), beta_row / ctx_row (rows); ctx_of_design: HOST map, nullptr = the identity
+int launch_score_noise(const diffab_sched* s, const diffab_igso3* fwd, const ScoreChunk& c, const int64_t* seq0, const float* x0,
+                       const float* O0, const uint8_t* gm, const int32_t* ctx_of_design, uint64_t seed, int64_t first_design, int64_t* s_t,
+                       float* x_t, float* O_t, float* eps, float* beta_row, int* ctx_row, const diffab_score_noised& out, hipStream_t st);
+// out_terms (n_designs n_t n_draws, 3) and out_residue (nullable, (..., K, 3)) at rows q0 .. q0 + valid - 1; rm nullable (all true)
+int launch_score_losses(const diffab_sched* s, const ScoreChunk& c, const int64_t* seq0, const float* O0, const uint8_t* gm, const uint8_t* rm,
+                        const int64_t* s_t, const float* O_t, const float* eps, const float* eps_hat, const float* v_hat, const float* logits,
+                        float* out_terms, float* out_residue, hipStream_t st);
 int launch_set_int(int* p, int v, hipStream_t st);
 int launch_dec_int(int* p, hipStream_t st);
 

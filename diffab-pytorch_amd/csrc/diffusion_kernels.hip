@@ -791,41 +791,195 @@ __global__ void sample_init_kernel(int64_t* __restrict__ seq, float* __restrict_
 
 // Antibody optimisation: the native state of the generated residues forward-noised to step t, in place (diffusion.py:105-135 for the
 // sequence - seq_forward_prob_kernel mode 1 + categorical_draw -, coord_forward_kernel's x_t, orient_forward_kernel's O_t with the rotation
-// vector drawn as the reverse loop draws it, from row t of the forward table).  Philox streams STREAM_OPT_*, counter step = t.
+// vector drawn as the reverse loop draws it, from row t of the forward table).  Philox streams STREAM_OPT_* + sw, counter step = t
+// (sw = 0 here; design scoring's draw m uses sw = m << 16).  eps (nullable): the translation noise of the residue.
+__device__ inline void forward_noise_residue(const float* __restrict__ alpha_bar, const float* __restrict__ abs_,
+                                             const float* __restrict__ omabs, const float* __restrict__ fwd_sigmas,
+                                             const float* __restrict__ fwd_cdf, int n_bins, float thr, int t, int64_t* seq, float* x, float* O,
+                                             float* eps_out, uint64_t seed, uint32_t patch, uint32_t res, uint32_t sw, uint32_t keep) {
+  const uint32_t st = static_cast<uint32_t>(t);
+  if (!(keep & DIFFAB_FLAG_KEEP_SEQUENCE)) {
+    const float wk = alpha_bar[t], wn = 1.0f - wk;
+    const int64_t s0 = *seq;
+    float p[kV];
+    for (int v = 0; v < kV; ++v) p[v] = seq_prob(v, s0, wk, wn, true);
+    const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_OPT_SEQ + sw);
+    *seq = categorical_draw(p, kV, us.x);
+  }
+  if (keep & DIFFAB_FLAG_KEEP_STRUCTURE) return;
+  const float a = abs_[t], b = omabs[t];
+  const f32x4 eps = philox_normal4(seed, patch, res, st, STREAM_OPT_TRANS + sw);
+  const float e[3] = {eps.x, eps.y, eps.z};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) x[c] = a * x[c] + b * e[c];
+  if (eps_out != nullptr) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) eps_out[c] = e[c];
+  }
+  f32x4 ax = philox_normal4(seed, patch, res, st, STREAM_OPT_AXIS + sw);
+  const f32x4 ua = philox_uniform4(seed, patch, res, st, STREAM_OPT_ANGLE + sw);
+  const f32x4 na = normals_from_uniforms(ua);
+  const float theta = igso3_theta(fwd_cdf, n_bins, fwd_sigmas[t], thr, t, ua.x, ua.y, na.z);
+  normalize3(ax.x, ax.y, ax.z);
+  float r[9], mean[9], noise[9], o[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) r[k] = O[k];
+  so3_scale(r, a, mean);
+  so3_rotvec_to_matrix(ax.x * theta, ax.y * theta, ax.z * theta, noise);
+  mat3_mul(mean, noise, o);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) O[k] = o[k];
+}
+
 __global__ void sample_init_noised_kernel(const float* __restrict__ alpha_bar, const float* __restrict__ abs_, const float* __restrict__ omabs,
                                           const float* __restrict__ fwd_sigmas, const float* __restrict__ fwd_cdf, int n_bins, float thr, int t,
                                           int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
                                           const uint8_t* __restrict__ gm, uint64_t seed, int64_t first_patch, int B, int K, uint32_t keep) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
-  const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K), st = static_cast<uint32_t>(t);
-  if (!(keep & DIFFAB_FLAG_KEEP_SEQUENCE)) {
-    const float wk = alpha_bar[t], wn = 1.0f - wk;
-    const int64_t s0 = seq[i];
-    float p[kV];
-    for (int v = 0; v < kV; ++v) p[v] = seq_prob(v, s0, wk, wn, true);
-    const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_OPT_SEQ);
-    seq[i] = categorical_draw(p, kV, us.x);
+  const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K);
+  forward_noise_residue(alpha_bar, abs_, omabs, fwd_sigmas, fwd_cdf, n_bins, thr, t, seq + i, x + i * 3, O + i * 9, nullptr, seed, patch, res,
+                        0u, keep);
+}
+
+// ------------------------------------------------------------------ design scoring (diffab_score_designs)
+// Evaluated row q = ((r n_t) + j) M + m: design r forward-noised to t_j with draw m.  A chunk's buffers hold c.rows rows; rows past the last
+// valid one repeat it (the denoiser always runs d->B rows, so every chunk carves the same workspace), the loss kernel reads the valid ones.
+struct ScoreRow {
+  int64_t r;
+  int j, m;
+};
+__device__ inline ScoreRow score_row(int64_t q, int n_t, int M) { return {q / (static_cast<int64_t>(n_t) * M), static_cast<int>((q / M) % n_t), static_cast<int>(q % M)}; }
+
+// One thread per (row, residue): the design's native state, forward-noised exactly as sample_init_noised_kernel noises it (same helper;
+// Philox patch first_design + r, step t_j, stream word STREAM_OPT_* + (m << 16)), plus the translation noise eps (0 where not noised), the
+// row's beta[t_j] and context index.  ctx.n designs r0 .. r0 + n - 1 of the launch take their context from the by-value table (identity
+// when `identity`).
+__global__ void score_noise_kernel(const float* __restrict__ alpha_bar, const float* __restrict__ abs_, const float* __restrict__ omabs,
+                                   const float* __restrict__ beta, const float* __restrict__ fwd_sigmas, const float* __restrict__ fwd_cdf,
+                                   int n_bins, float thr, ScoreChunk c, int row_lo, int row_hi, ScoreCtxTable ctx, bool identity,
+                                   const int64_t* __restrict__ seq0, const float* __restrict__ x0, const float* __restrict__ O0,
+                                   const uint8_t* __restrict__ gm, uint64_t seed, int64_t first_design, int64_t* __restrict__ s_t,
+                                   float* __restrict__ x_t, float* __restrict__ O_t, float* __restrict__ eps, float* __restrict__ beta_row,
+                                   int* __restrict__ ctx_row, diffab_score_noised out) {
+  const int K = c.K;
+  const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+  if (i >= static_cast<int64_t>(row_hi - row_lo) * K) return;
+  const int rr = row_lo + static_cast<int>(i / K), k = static_cast<int>(i % K);  // row of the chunk, residue
+  const bool valid = rr < c.valid;
+  const int64_t q = c.q0 + (valid ? rr : c.valid - 1);
+  const ScoreRow w = score_row(q, c.n_t, c.n_draws);
+  const int t = c.t_list[w.j];
+  const int64_t src = w.r * K + k, dst = static_cast<int64_t>(rr) * K + k;
+  int64_t s = seq0[src];
+  float x[3], O[9], e[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) x[a] = x0[src * 3 + a];
+#pragma unroll
+  for (int a = 0; a < 9; ++a) O[a] = O0[src * 9 + a];
+  if (gm[src])
+    forward_noise_residue(alpha_bar, abs_, omabs, fwd_sigmas, fwd_cdf, n_bins, thr, t, &s, x, O, e, seed,
+                          static_cast<uint32_t>(first_design + w.r), static_cast<uint32_t>(k), static_cast<uint32_t>(w.m) << 16, c.keep);
+  s_t[dst] = s;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) x_t[dst * 3 + a] = x[a];
+#pragma unroll
+  for (int a = 0; a < 9; ++a) O_t[dst * 9 + a] = O[a];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) eps[dst * 3 + a] = e[a];
+  if (k == 0) {
+    beta_row[rr] = beta[t];
+    ctx_row[rr] = identity ? static_cast<int>(w.r) : ctx.ctx[w.r - ctx.r0];
   }
-  if (keep & DIFFAB_FLAG_KEEP_STRUCTURE) return;
-  const float a = abs_[t], b = omabs[t];
-  const f32x4 eps = philox_normal4(seed, patch, res, st, STREAM_OPT_TRANS);
-  const float e[3] = {eps.x, eps.y, eps.z};
+  if (!valid) return;
+  const int64_t o = q * K + k;  // the caller's (n_designs, n_t, n_draws, K, ...) copies of the noised state (tests, debugging)
+  if (out.seq_t) out.seq_t[o] = s;
+  if (out.x_t)
+    for (int a = 0; a < 3; ++a) out.x_t[o * 3 + a] = x[a];
+  if (out.O_t)
+    for (int a = 0; a < 9; ++a) out.O_t[o * 9 + a] = O[a];
+  if (out.eps)
+    for (int a = 0; a < 3; ++a) out.eps[o * 3 + a] = e[a];
+}
+
+// One work-group per evaluated row: the heads' epilogue (posterior = softmax(logits), O0 = O_t exp(hat(v)), as reverse_update_philox_kernel
+// does it), the true posterior q(s_{t-1} | s_t, s_0) (seq_posterior_kernel's formula, recomputed, not stored), the three per-residue terms of
+// losses_kernel (diffab_pytorch.py:856-880 before the reduction) and their means over the row's masked residues - each thread sums its
+// residues in order, then a fixed tree over the work-group: no atomics, the result depends on the row alone.  Kept modality: term 0.
+constexpr int kScoreLossThreads = 256;
+__global__ __launch_bounds__(kScoreLossThreads) void score_loss_kernel(const float* __restrict__ beta, const float* __restrict__ alpha_bar,
+                                                                      ScoreChunk c, const int64_t* __restrict__ seq0, const float* __restrict__ O0,
+                                                                      const uint8_t* __restrict__ gm, const uint8_t* __restrict__ rm,
+                                                                      const int64_t* __restrict__ s_t, const float* __restrict__ O_t,
+                                                                      const float* __restrict__ eps, const float* __restrict__ eps_hat,
+                                                                      const float* __restrict__ v_hat, const float* __restrict__ logits,
+                                                                      float* __restrict__ out_terms, float* __restrict__ out_residue) {
+  __shared__ float red[4][kScoreLossThreads];
+  const int K = c.K, rr = blockIdx.x;
+  const int64_t q = c.q0 + rr;
+  const ScoreRow w = score_row(q, c.n_t, c.n_draws);
+  const int t = c.t_list[w.j];
+  const float bt = beta[t], ab = alpha_bar[t - 1];
+  const bool do_seq = !(c.keep & DIFFAB_FLAG_KEEP_SEQUENCE), do_struct = !(c.keep & DIFFAB_FLAG_KEEP_STRUCTURE);
+  float a_kl = 0.f, a_mse = 0.f, a_o = 0.f, a_n = 0.f;
+  for (int k = threadIdx.x; k < K; k += kScoreLossThreads) {
+    const int64_t src = w.r * K + k, i = static_cast<int64_t>(rr) * K + k;
+    float kl = 0.f, mse = 0.f, ol = 0.f;
+    const bool masked = gm[src] && (rm == nullptr || rm[src]);
+    if (masked && do_seq) {
+      const float* lg = logits + i * kV;
+      float m = -INFINITY;
+      for (int v = 0; v < kV; ++v) m = fmaxf(m, lg[v]);
+      float se = 0.f;
+      for (int v = 0; v < kV; ++v) se += expf(lg[v] - m);
+      const float inv = 1.0f / se;
+      const int64_t ct = s_t[i], c0 = seq0[src];
+      float p[kV], sp = 0.f;
+      for (int v = 0; v < kV; ++v) {
+        p[v] = seq_prob(v, ct, 1.0f - bt, bt, true) * seq_prob(v, c0, ab, 1.0f - ab, true);
+        sp += p[v];
+      }
+      for (int v = 0; v < kV; ++v) {
+        const float qv = p[v] / sp;
+        if (qv > 0.0f) kl += qv * logf(qv) - qv * logf(expf(lg[v] - m) * inv);  // kl_div(log p, q): xlogy(q,q) - q log p
+      }
+    }
+    if (masked && do_struct) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) x[i * 3 + c] = a * x[i * 3 + c] + b * e[c];
-  f32x4 ax = philox_normal4(seed, patch, res, st, STREAM_OPT_AXIS);
-  const f32x4 ua = philox_uniform4(seed, patch, res, st, STREAM_OPT_ANGLE);
-  const f32x4 na = normals_from_uniforms(ua);
-  const float theta = igso3_theta(fwd_cdf, n_bins, fwd_sigmas[t], thr, t, ua.x, ua.y, na.z);
-  normalize3(ax.x, ax.y, ax.z);
-  float r[9], mean[9], noise[9], o[9];
+      for (int a = 0; a < 3; ++a) {
+        const float d = eps_hat[i * 3 + a] - eps[i * 3 + a];
+        mse += d * d;
+      }
+      float ex[9], ot[9], pO[9];
+      so3_rotvec_to_matrix(v_hat[i * 3], v_hat[i * 3 + 1], v_hat[i * 3 + 2], ex);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) r[k] = O[i * 9 + k];
-  so3_scale(r, a, mean);
-  so3_rotvec_to_matrix(ax.x * theta, ax.y * theta, ax.z * theta, noise);
-  mat3_mul(mean, noise, o);
+      for (int a = 0; a < 9; ++a) ot[a] = O_t[i * 9 + a];
+      mat3_mul(ot, ex, pO);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) O[i * 9 + k] = o[k];
+      for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int kk = 0; kk < 3; ++kk) {
+          float d = 0.f;
+#pragma unroll
+          for (int r = 0; r < 3; ++r) d += pO[r * 3 + j] * O0[src * 9 + r * 3 + kk];  // pred^T target (:620-622)
+          d -= (j == kk) ? 1.0f : 0.0f;
+          ol += d * d;
+        }
+    }
+    if (out_residue) {
+      float* o = out_residue + (q * K + k) * 3;
+      o[0] = kl; o[1] = mse; o[2] = ol;
+    }
+    a_kl += kl; a_mse += mse; a_o += ol; a_n += masked ? 1.0f : 0.0f;
+  }
+  red[0][threadIdx.x] = a_kl; red[1][threadIdx.x] = a_mse; red[2][threadIdx.x] = a_o; red[3][threadIdx.x] = a_n;
+  __syncthreads();
+  for (int s = kScoreLossThreads / 2; s > 0; s >>= 1) {
+    if (static_cast<int>(threadIdx.x) < s)
+      for (int a = 0; a < 4; ++a) red[a][threadIdx.x] += red[a][threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) out_terms[q * 3 + threadIdx.x] = red[threadIdx.x][0] / red[3][0];  // no masked residue: 0 / 0 = NaN, as the reference
 }
 
 __global__ void fill_beta_kernel(const float* __restrict__ beta, int t, int B, float* __restrict__ out, const int* __restrict__ t_dev) {
@@ -845,6 +999,44 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
                      post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+
+int launch_score_noise(const diffab_sched* s, const diffab_igso3* fwd, const ScoreChunk& c, const int64_t* seq0, const float* x0,
+                       const float* O0, const uint8_t* gm, const int32_t* ctx_of_design, uint64_t seed, int64_t first_design, int64_t* s_t,
+                       float* x_t, float* O_t, float* eps, float* beta_row, int* ctx_row, const diffab_score_noised& out, hipStream_t st) {
+  // the context indices of a launch's designs travel by value: a chunk whose rows span more than kScoreCtxMax designs (few rows per
+  // design) takes several launches over consecutive row ranges
+  const int64_t per = static_cast<int64_t>(c.n_t) * c.n_draws;
+  for (int lo = 0; lo < c.rows;) {
+    const int64_t r0 = (c.q0 + (lo < c.valid ? lo : c.valid - 1)) / per;
+    int hi = c.rows;
+    if (ctx_of_design != nullptr) {
+      const int64_t end = (r0 + kScoreCtxMax) * per - c.q0;  // first row of design r0 + kScoreCtxMax
+      if (end < hi && end < c.valid) hi = static_cast<int>(end);
+    }
+    ScoreCtxTable tab{};
+    tab.r0 = r0;
+    if (ctx_of_design != nullptr) {
+      const int64_t q_last = c.q0 + (hi <= c.valid ? hi : c.valid) - 1;
+      for (int64_t r = r0; r <= q_last / per; ++r) tab.ctx[r - r0] = ctx_of_design[r];
+    }
+    const int64_t n = static_cast<int64_t>(hi - lo) * c.K;
+    hipLaunchKernelGGL(score_noise_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->alpha_bar, s->alpha_bar_sqrt, s->one_minus_alpha_bar_sqrt,
+                       s->beta, fwd->sigmas, fwd->cdf, fwd->n_bins, fwd->sigma_threshold, c, lo, hi, tab, ctx_of_design == nullptr, seq0, x0, O0,
+                       gm, seed, first_design, s_t, x_t, O_t, eps, beta_row, ctx_row, out);
+    DIFFAB_LAUNCH_CHECK();
+    lo = hi;
+  }
+  return DIFFAB_OK;
+}
+
+int launch_score_losses(const diffab_sched* s, const ScoreChunk& c, const int64_t* seq0, const float* O0, const uint8_t* gm, const uint8_t* rm,
+                        const int64_t* s_t, const float* O_t, const float* eps, const float* eps_hat, const float* v_hat, const float* logits,
+                        float* out_terms, float* out_residue, hipStream_t st) {
+  hipLaunchKernelGGL(score_loss_kernel, dim3(c.valid), dim3(kScoreLossThreads), 0, st, s->beta, s->alpha_bar, c, seq0, O0, gm, rm, s_t, O_t,
+                     eps, eps_hat, v_hat, logits, out_terms, out_residue);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

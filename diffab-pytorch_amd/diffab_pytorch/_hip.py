@@ -82,6 +82,10 @@ class Igso3(C.Structure):
     _fields_ = [("n_sigmas", C.c_int32), ("n_bins", C.c_int32), ("sigmas", _fp), ("cdf", _fp), ("sigma_threshold", C.c_float)]
 
 
+class ScoreNoised(C.Structure):  # diffab_score_noised: optional copies of the noised state of every evaluated row
+    _fields_ = [(n, _fp) for n in ("seq_t", "x_t", "O_t", "eps")]
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -175,6 +179,12 @@ SYMBOLS = {
     "diffab_sample_init_ex": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
     # (sched, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, stream)
     "diffab_sample_init_noised": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
+    "diffab_score_workspace_bytes": (_sz, [_PD, _i32]),
+    # (d, w, sched, fwd_tab, seq, x, O, gen_mask, res_mask, n_designs, res_ctx, pair_ctx, n_ctx, ctx_of_design (host int32[n_designs]),
+    #  t_list (host int32[n_t]), n_t, n_draws, seed, first_design, out_terms, out_residue, noised, ws, ws_bytes, flags, stream)
+    "diffab_score_designs": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, _fp, _fp, _i32,
+                                       C.POINTER(_i32), C.POINTER(_i32), _i32, _i32, _u64, _i64, _fp, _fp, C.POINTER(ScoreNoised), _fp, _sz,
+                                       _u32, _fp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -49,6 +49,47 @@ SAMPLE_MODES = {
 }
 
 
+# DiffAb.score: evaluated rows per diffab_score_designs chunk when the caller does not choose (tools/score_bench.py, profiles/score.md)
+SCORE_ROWS_PER_LAUNCH = 256
+
+
+def _mode_settings(who: str, mode, generate_structure: bool, generate_sequence: bool):
+    """(generate_structure, generate_sequence, DIFFAB_FLAG_KEEP_* bits) of a design mode (sample() and score())."""
+    if mode is None:
+        return generate_structure, generate_sequence, 0
+    if not isinstance(mode, str) or mode not in SAMPLE_MODES:
+        raise ValueError(f"{who}: unknown mode {mode!r}; expected None or one of {sorted(SAMPLE_MODES)}")
+    if not generate_structure or not generate_sequence:
+        raise ValueError(f"{who}: mode={mode!r} sets generate_structure / generate_sequence itself; leave them at their defaults")
+    return SAMPLE_MODES[mode]
+
+
+def _context_map(who: str, context_index, n_rows: int, res_context_emb, pair_context_emb, rows: str) -> torch.Tensor:
+    """Host int32 (n_rows,) from `context_index`: the shared contexts must be given, and every entry lie in [0, n_ctx)."""
+    if res_context_emb is None or pair_context_emb is None:
+        raise ValueError(f"{who}: context_index needs res_context_emb and pair_context_emb (the n_ctx shared contexts)")
+    ci = torch.as_tensor(context_index)
+    n_ctx = res_context_emb.shape[0]
+    if pair_context_emb.shape[0] != n_ctx:
+        raise ValueError(f"{who}: res_context_emb has {n_ctx} contexts, pair_context_emb {pair_context_emb.shape[0]}")
+    if ci.dim() != 1 or ci.numel() != n_rows or ci.is_floating_point() or ci.is_complex():
+        raise ValueError(f"{who}: context_index must be an integer vector of length {n_rows} (the {rows}), "
+                         f"got shape {tuple(ci.shape)} {ci.dtype}")
+    ci = ci.detach().to("cpu", torch.int64)
+    if n_rows and (int(ci.min()) < 0 or int(ci.max()) >= n_ctx):
+        raise ValueError(f"{who}: context_index entries must lie in [0, {n_ctx})")
+    return ci.to(torch.int32)
+
+
+def _check_encode_fields(who: str, xyz, atom_mask, chain_idx) -> None:
+    need = {"atom_mask": atom_mask, "chain_idx": chain_idx}
+    missing = [k for k, v in need.items() if v is None]
+    if missing or xyz.dim() != 4:
+        raise ValueError(f"{who}: without res_context_emb / pair_context_emb the contexts are computed by encode_context, "
+                         f"which needs all-atom xyz (B,K,A,3) and the batch fields {sorted(need)}; missing: "
+                         f"{missing if missing else 'xyz is not (B,K,A,3)'}")
+
+
 def _named(module: nn.Module) -> Dict[str, torch.Tensor]:
     return dict(module.named_parameters())
 
@@ -849,6 +890,23 @@ class DiffAb(_ModuleBase):
         fused = bool(params) and all(p.is_cuda and p.is_floating_point() for p in params)
         return torch.optim.Adam(params, lr=self.lr, weight_decay=self.weight_decay, betas=self.betas, fused=fused)
 
+    def _contexts_from_batch(self, seq_idx, xyz, orientations, generation_mask, residue_mask, backbone_dihedrals, pairwise_dihedrals,
+                             distmat, atom_mask, chain_idx, residue_idx, generate_structure, generate_sequence):
+        """encode_context from the reference's batch fields as sample() and score() accept them: residue_idx and
+        residue_mask default to arange(K) and all-true; the dihedral features are taken from xyz on the device when absent."""
+        Bq, Kq = seq_idx.shape
+        if residue_mask is None:
+            residue_mask = torch.ones(Bq, Kq, dtype=torch.bool, device=seq_idx.device)
+        if backbone_dihedrals is None or pairwise_dihedrals is None:  # dihedral features from the coordinates, on the device
+            feats = _features.featurize(xyz, chain_idx, residue_mask, orientations=False, backbone_dihedrals=backbone_dihedrals is None,
+                                        pairwise_dihedrals=pairwise_dihedrals is None)
+            backbone_dihedrals = feats.get("backbone_dihedrals", backbone_dihedrals)
+            pairwise_dihedrals = feats.get("pairwise_dihedrals", pairwise_dihedrals)
+        if residue_idx is None:
+            residue_idx = torch.arange(Kq, device=seq_idx.device).unsqueeze(0)  # data.py:91
+        return self.encode_context(seq_idx, xyz, orientations, backbone_dihedrals, distmat, pairwise_dihedrals, atom_mask, chain_idx,
+                                   residue_idx, generation_mask, residue_mask, generate_structure, generate_sequence)
+
     # ------------------------------------------------------------------ reverse process (the reference has a stub, :770-776)
     @torch.no_grad()
     def sample(self, seq_idx: torch.LongTensor, xyz: torch.FloatTensor, orientations: torch.FloatTensor, *, generation_mask=None,
@@ -904,14 +962,7 @@ class DiffAb(_ModuleBase):
         with init=False and a t_start other than optimize_from raise ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
-        keep = 0  # DIFFAB_FLAG_KEEP_* of the mode
-        if mode is not None:
-            if not isinstance(mode, str) or mode not in SAMPLE_MODES:
-                raise ValueError(f"sample(): unknown mode {mode!r}; expected None or one of {sorted(SAMPLE_MODES)}")
-            if not generate_structure or not generate_sequence:
-                raise ValueError(f"sample(): mode={mode!r} sets generate_structure / generate_sequence itself; leave them at their "
-                                 "defaults")
-            generate_structure, generate_sequence, keep = SAMPLE_MODES[mode]
+        generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
         if optimize_from is not None:
             if isinstance(optimize_from, bool) or not isinstance(optimize_from, int) or not 1 <= optimize_from <= self.T:
                 raise ValueError(f"sample(): optimize_from must be an int in [1, T = {self.T}], got {optimize_from!r}")
@@ -936,19 +987,7 @@ class DiffAb(_ModuleBase):
                 if v is not None and tuple(v.shape[1:]) != tail:
                     raise ValueError(f"sample(): {name} is {tuple(v.shape)}, expected (contexts, {', '.join(map(str, tail))})")
         if context_index is not None:
-            if res_context_emb is None or pair_context_emb is None:
-                raise ValueError("sample(): context_index needs res_context_emb and pair_context_emb (the n_ctx shared contexts)")
-            ci = torch.as_tensor(context_index)
-            n_ctx = res_context_emb.shape[0]
-            if pair_context_emb.shape[0] != n_ctx:
-                raise ValueError(f"sample(): res_context_emb has {n_ctx} contexts, pair_context_emb {pair_context_emb.shape[0]}")
-            if ci.dim() != 1 or ci.numel() != n_rows or ci.is_floating_point() or ci.is_complex():
-                raise ValueError(f"sample(): context_index must be an integer vector of length {n_rows} (the state rows), "
-                                 f"got shape {tuple(ci.shape)} {ci.dtype}")
-            ci = ci.detach().to("cpu", torch.int64)
-            if n_rows and (int(ci.min()) < 0 or int(ci.max()) >= n_ctx):
-                raise ValueError(f"sample(): context_index entries must lie in [0, {n_ctx})")
-            ctx_map = ci.to(torch.int32)
+            ctx_map = _context_map("sample()", context_index, n_rows, res_context_emb, pair_context_emb, "state rows")
         elif num_samples > 1:
             for name, v in (("res_context_emb", res_context_emb), ("pair_context_emb", pair_context_emb)):
                 if v is not None and v.shape[0] != n_rows:
@@ -956,25 +995,10 @@ class DiffAb(_ModuleBase):
                                      f"seq_idx has {n_rows}")
             ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
         if res_context_emb is None or pair_context_emb is None:
-            need = {"atom_mask": atom_mask, "chain_idx": chain_idx}
-            missing = [k for k, v in need.items() if v is None]
-            if missing or xyz.dim() != 4:
-                raise ValueError("sample(): without res_context_emb / pair_context_emb the contexts are computed by encode_context, "
-                                 f"which needs all-atom xyz (B,K,A,3) and the batch fields {sorted(need)}; missing: "
-                                 f"{missing if missing else 'xyz is not (B,K,A,3)'}")
-            Bq, Kq = seq_idx.shape
-            if residue_mask is None:
-                residue_mask = torch.ones(Bq, Kq, dtype=torch.bool, device=seq_idx.device)
-            if backbone_dihedrals is None or pairwise_dihedrals is None:  # dihedral features from the coordinates, on the device
-                feats = _features.featurize(xyz, chain_idx, residue_mask, orientations=False, backbone_dihedrals=backbone_dihedrals is None,
-                                            pairwise_dihedrals=pairwise_dihedrals is None)
-                backbone_dihedrals = feats.get("backbone_dihedrals", backbone_dihedrals)
-                pairwise_dihedrals = feats.get("pairwise_dihedrals", pairwise_dihedrals)
-            if residue_idx is None:
-                residue_idx = torch.arange(Kq, device=seq_idx.device).unsqueeze(0)  # data.py:91
-            res_context_emb, pair_context_emb = self.encode_context(seq_idx, xyz, orientations, backbone_dihedrals, distmat,
-                                                                    pairwise_dihedrals, atom_mask, chain_idx, residue_idx,
-                                                                    generation_mask, residue_mask, generate_structure, generate_sequence)
+            _check_encode_fields("sample()", xyz, atom_mask, chain_idx)
+            res_context_emb, pair_context_emb = self._contexts_from_batch(seq_idx, xyz, orientations, generation_mask, residue_mask,
+                                                                          backbone_dihedrals, pairwise_dihedrals, distmat, atom_mask,
+                                                                          chain_idx, residue_idx, generate_structure, generate_sequence)
         lib = _hip.lib()
         out_dev = seq_idx.device
         seq = _hip.dev_i64(seq_idx)
@@ -1024,3 +1048,148 @@ class DiffAb(_ModuleBase):
                                                      first_patch, t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()),
                        "diffab_sample_loop_shared")
         return {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
+
+    # ------------------------------------------------------------------ design scoring (build-defined; the training objective per design)
+    @torch.no_grad()
+    def score(self, seq_idx: torch.LongTensor, xyz: torch.FloatTensor, orientations: torch.FloatTensor, *, generation_mask=None,
+              residue_mask=None, res_context_emb=None, pair_context_emb=None, context_index: Optional[torch.LongTensor] = None,
+              backbone_dihedrals=None, pairwise_dihedrals=None, distmat=None, atom_mask=None, chain_idx=None, residue_idx=None,
+              generate_structure: bool = True, generate_sequence: bool = True, t=None, num_draws: int = 1, seed: Optional[int] = None,
+              first_design: int = 0, mode: Optional[str] = None, per_residue: bool = False, return_noised: bool = False,
+              rows_per_launch: Optional[int] = None, flags: int = 0) -> Dict[str, torch.Tensor]:
+        """Per-design diffusion losses: the reference's training objective (_shared_step, diffab_pytorch.py:808-880; `loss` as
+        training_step sums it, :882-887) for each of R designs, averaged over a grid of timesteps and noise draws - a model-side signal to
+        rank designs (e.g. many `sample(num_samples=N)` CDRs per antigen) by.
+
+        Designs: seq_idx (R,K), xyz (R,K,3) CA translations or (R,K,A,3) atoms, orientations (R,K,3,3), generation_mask (R,K) - the
+        residues that are noised and scored - and residue_mask (R,K, default all true).  Contexts as in sample(): res_context_emb /
+        pair_context_emb with one context per design, or n_ctx shared contexts and ``context_index`` (R,) (design r reads context
+        context_index[r]), or neither - then encode_context runs first, once, from the batch fields sample() accepts, with the mode's
+        visibility.  ``t``: the grid, None = every step 1..T, an int, or a 1-D list / tensor of distinct steps in [1, T].
+        ``num_draws`` = M >= 1 noise draws per (design, t).
+
+        Row q = ((r n_t) + j) M + m is design r forward-noised to t_j with draw m and denoised against its context (diffab_score_designs:
+        one C-ABI call, chunks of ``rows_per_launch`` rows, no host sync).  Noise: Philox patch first_design + r, step t_j, the
+        optimisation-start streams + (m << 16) - draw 0 is exactly sample(optimize_from=t_j, t_stop=t_j, first_patch=first_design + r),
+        and scoring designs [lo, hi) with first_design = lo gives that slice of the whole call bitwise.  Per residue with
+        generation_mask & residue_mask: seq = KL(q(s_{t-1} | s_t, s_0) || softmax(logits)), translations = sum_c (eps_hat - eps)^2,
+        orientations = sum_jk (O0_hat^T O0 - I)^2; each row's terms are summed over its masked residues and divided by their count
+        (a design without one gives NaN, as 0/0 does in the reference).
+        Modes as sample(): "fixed_backbone" does not noise x and O (their terms are exactly 0 and not part of `loss`), "structure" does
+        not noise the sequence (its term is exactly 0 and not part of `loss`).
+
+        Returns seq_loss, translations_loss, orientations_loss (R,) - the mean over the grid and the draws -, loss (R,) - the sum of the
+        diffused terms -, per_step (R, n_t, M, 3) and t (n_t,); per_residue (R, n_t, M, K, 3) when asked, and with ``return_noised``
+        the noised state of every row (seq_idx_t, translations_t, orientations_t, translations_eps).  Every argument error raises
+        ValueError before any library call."""
+        who = "score()"
+        generate_structure, generate_sequence, keep = _mode_settings(who, mode, generate_structure, generate_sequence)
+        if int(flags) & (_hip.FLAG_KEEP_STRUCTURE | _hip.FLAG_KEEP_SEQUENCE):
+            raise ValueError(f"{who}: choose the design mode with mode=, not with the DIFFAB_FLAG_KEEP_* bits in flags")
+        if generation_mask is None:
+            raise ValueError(f"{who} needs generation_mask: which residues to noise and score")
+        if not torch.is_tensor(seq_idx) or seq_idx.dim() != 2 or seq_idx.is_floating_point():
+            raise ValueError(f"{who}: seq_idx must be an integer tensor (R, K), got {getattr(seq_idx, 'shape', type(seq_idx))}")
+        R, K = seq_idx.shape
+        if R < 1 or K < 1:
+            raise ValueError(f"{who}: no designs to score (seq_idx is {(R, K)})")
+        def shape_error(name, v, want):
+            return ValueError(f"{who}: {name} is {tuple(v.shape) if torch.is_tensor(v) else type(v).__name__}, expected {want}")
+
+        if not torch.is_tensor(xyz) or not (tuple(xyz.shape) == (R, K, 3) or (xyz.dim() == 4 and tuple(xyz.shape[:2]) == (R, K)
+                                                                                and xyz.shape[3] == 3)):
+            raise shape_error("xyz", xyz, f"{(R, K, 3)} or {(R, K, 'A', 3)}")
+        for name, v, want in (("orientations", orientations, (R, K, 3, 3)), ("generation_mask", generation_mask, (R, K)),
+                              ("residue_mask", residue_mask, (R, K))):
+            if (v is not None or name != "residue_mask") and (not torch.is_tensor(v) or tuple(v.shape) != want):
+                raise shape_error(name, v, want)
+        T = int(self.T)
+        if t is None:
+            grid = list(range(1, T + 1))
+        else:
+            tt = torch.as_tensor(t)
+            if tt.numel() == 0:
+                raise ValueError(f"{who}: t is empty")
+            if tt.dim() > 1 or tt.is_floating_point() or tt.is_complex() or tt.dtype == torch.bool:
+                raise ValueError(f"{who}: t must be None, an int or a 1-D integer list / tensor, got {t!r}")
+            grid = [int(v) for v in tt.reshape(-1).tolist()]
+            bad = [v for v in grid if not 1 <= v <= T]
+            if bad:
+                raise ValueError(f"{who}: every t must lie in [1, T = {T}], got {bad}")
+            if len(set(grid)) != len(grid):
+                raise ValueError(f"{who}: t has duplicate steps {sorted(v for v in set(grid) if grid.count(v) > 1)}")
+        if isinstance(num_draws, bool) or not isinstance(num_draws, int) or not 1 <= num_draws <= 65536:
+            raise ValueError(f"{who}: num_draws must be an int in [1, 65536], got {num_draws!r}")
+        if isinstance(first_design, bool) or not isinstance(first_design, int) or first_design < 0 or first_design + R > 2 ** 32:
+            raise ValueError(f"{who}: first_design must be an int >= 0 (first_design + R <= 2^32), got {first_design!r}")
+        if rows_per_launch is not None and (isinstance(rows_per_launch, bool) or not isinstance(rows_per_launch, int) or rows_per_launch < 1):
+            raise ValueError(f"{who}: rows_per_launch must be an int >= 1, got {rows_per_launch!r}")
+        dd = self.denoiser.dims
+        for name, v, tail in (("res_context_emb", res_context_emb, (K, dd["D"])), ("pair_context_emb", pair_context_emb, (K, K, dd["C"]))):
+            if v is not None and (v.dim() != len(tail) + 1 or tuple(v.shape[1:]) != tail):
+                raise ValueError(f"{who}: {name} is {tuple(v.shape)}, expected (contexts, {', '.join(map(str, tail))})")
+        ctx_map = None  # host int32 (R,): the context of every design (None: one context per design)
+        if context_index is not None:
+            ctx_map = _context_map(who, context_index, R, res_context_emb, pair_context_emb, "designs")
+        elif res_context_emb is not None or pair_context_emb is not None:
+            for name, v in (("res_context_emb", res_context_emb), ("pair_context_emb", pair_context_emb)):
+                if v is None or v.shape[0] != R:
+                    raise ValueError(f"{who}: without context_index give both contexts with one row per design ({R}); {name} is "
+                                     f"{None if v is None else tuple(v.shape)}")
+        else:
+            _check_encode_fields(who, xyz, atom_mask, chain_idx)
+        n_t, M = len(grid), num_draws
+        total = R * n_t * M
+        rows = min(total, SCORE_ROWS_PER_LAUNCH if rows_per_launch is None else rows_per_launch)
+
+        if res_context_emb is None:
+            res_context_emb, pair_context_emb = self._contexts_from_batch(seq_idx, xyz, orientations, generation_mask, residue_mask,
+                                                                          backbone_dihedrals, pairwise_dihedrals, distmat, atom_mask,
+                                                                          chain_idx, residue_idx, generate_structure, generate_sequence)
+        lib = _hip.lib()
+        n_ctx = res_context_emb.shape[0]
+        dims = self.denoiser.hip_dims(rows, K)
+        ws_bytes = lib.diffab_score_workspace_bytes(C.byref(dims), n_ctx)  # (sized by rows and n_ctx only)
+        if ws_bytes == 0:
+            raise _hip.DiffabHipError(f"diffab_score_workspace_bytes: {lib.diffab_last_error().decode()}")
+        out_dev = seq_idx.device
+        seq = _hip.dev_i64(seq_idx)
+        x = _hip.dev_f32(xyz[:, :, CA_IDX] if xyz.dim() == 4 else xyz)
+        O = _hip.dev_f32(orientations)
+        gm = _hip.dev_mask(generation_mask)
+        rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+        rc, pc = _hip.dev_f32(res_context_emb), _hip.dev_f32(pair_context_emb)
+        seed = _so3._draw_seed() if seed is None else int(seed)
+        w = self.denoiser.hip_weights()
+        sd = self._sched_on_device()
+        fwd_tab = self.orientation_diffuser.so3.struct()
+        ws = _hip.workspace(ws_bytes)
+        dev = seq.device
+        terms = torch.empty(R, n_t, M, 3, dtype=torch.float32, device=dev)
+        resid = torch.empty(R, n_t, M, K, 3, dtype=torch.float32, device=dev) if per_residue else None
+        noised = None
+        noised_struct = None
+        if return_noised:
+            noised = {"seq_idx_t": torch.empty(R, n_t, M, K, dtype=torch.int64, device=dev),
+                      "translations_t": torch.empty(R, n_t, M, K, 3, dtype=torch.float32, device=dev),
+                      "orientations_t": torch.empty(R, n_t, M, K, 3, 3, dtype=torch.float32, device=dev),
+                      "translations_eps": torch.empty(R, n_t, M, K, 3, dtype=torch.float32, device=dev)}
+            noised_struct = _hip.ScoreNoised(*[_hip.ptr(noised[k]) for k in ("seq_idx_t", "translations_t", "orientations_t",
+                                                                              "translations_eps")])
+        ctx_host = None if ctx_map is None else (C.c_int32 * R)(*ctx_map.tolist())
+        t_host = (C.c_int32 * n_t)(*grid)
+        _hip.check(lib.diffab_score_designs(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(fwd_tab), _hip.ptr(seq), _hip.ptr(x),
+                                            _hip.ptr(O), _hip.ptr(gm), _hip.ptr(rm), R, _hip.ptr(rc), _hip.ptr(pc), n_ctx, ctx_host, t_host, n_t,
+                                            M, seed, first_design, _hip.ptr(terms), _hip.ptr(resid),
+                                            None if noised_struct is None else C.byref(noised_struct), _hip.ptr(ws), ws.numel(),
+                                            int(flags) | keep, _hip.stream_ptr()), "diffab_score_designs")
+        mean = terms.mean(dim=(1, 2))
+        diffused = [keep != _hip.FLAG_KEEP_SEQUENCE, keep != _hip.FLAG_KEEP_STRUCTURE, keep != _hip.FLAG_KEEP_STRUCTURE]
+        loss = sum(mean[:, i] for i in range(3) if diffused[i])
+        out = {"seq_loss": mean[:, 0], "translations_loss": mean[:, 1], "orientations_loss": mean[:, 2], "loss": loss, "per_step": terms,
+               "t": torch.tensor(grid, dtype=torch.int64)}
+        if per_residue:
+            out["per_residue"] = resid
+        if return_noised:
+            out["noised"] = noised
+        return {k: (v.to(out_dev) if torch.is_tensor(v) else {kk: vv.to(out_dev) for kk, vv in v.items()}) for k, v in out.items()}

@@ -523,6 +523,45 @@ int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab
                               const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t,
                               uint32_t flags, void* stream);
 
+/* ---- design scoring (build-defined evaluator; reference objective diffab_pytorch.py:808-887) ----------------------------------------
+ * Per-design diffusion losses over a timestep grid: the reference's training objective (_shared_step, :808-880, summed as `loss` at
+ * :882-887) evaluated per design instead of as one batch mean at one random t per row.  Evaluated row q = ((r n_t) + j) n_draws + m is
+ * design r (of n_designs; seq (n,K), x (n,K,3), O (n,K,3,3), gen_mask / res_mask (n,K), res_mask NULL = all true) forward-noised to
+ * t_j = t_list[j] with draw m, then denoised against context ctx_of_design[r] of the n_ctx contexts in res_ctx (n_ctx,K,D) / pair_ctx
+ * (n_ctx,K,K,C) (ctx_of_design: a HOST array of n_designs entries in [0, n_ctx); NULL = the identity, n_ctx must be n_designs).
+ *   Noise: diffab_sample_init_noised's forward process (diffusion.py:105-135, 199-236, 262-294) and Philox lanes, patch first_design + r,
+ *          counter step t_j, stream word STREAM_OPT_* + (m << 16): draw 0 is bitwise sample_init_noised(t_j, first_patch = first_design +
+ *          r), and designs [lo, hi) scored with first_design = lo are bitwise that slice of the whole call.  Only generated residues are
+ *          noised; DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE leave that modality un-noised.
+ *   Denoiser: Denoiser.forward (:558-607) at beta = beta[t_j] per row, on every launch form the sampler has (the shared-context pair
+ *          stream, fp16 pair planes built once per call for the n_ctx contexts, the patch-resident module launch where
+ *          diffab_sample_loop_shared would take it).
+ *   Terms, per residue with gen_mask & res_mask (0 elsewhere), the reference's element losses (:856-880 before reduction) summed over
+ *          their trailing axes:  seq  sum_v q_v (log q_v - log p_v), q = q(s_{t-1} | s_t, s_0) (diffusion.py:168-192), p = softmax(logits);
+ *          translations  sum_c (eps_hat - eps)^2;  orientations  sum_jk ((O0_hat^T O0) - I)^2_jk, O0_hat = O_t exp(hat(v_hat)) (:594-596,
+ *          :610-625).  A kept modality's terms are exactly 0.
+ *   out_terms (n_designs, n_t, n_draws, 3): each term summed over the row's masked residues / their count (0/0 = NaN for a row without
+ *          one, as :868-878), reduced in a fixed order per row: independent of chunking, sharding and launch form.
+ *   out_residue (nullable, (n_designs, n_t, n_draws, K, 3)): the per-residue terms.  noised (nullable, and each member nullable): the
+ *          noised state of every row, for tests and debugging.
+ * The rows run in chunks of d->B consecutive rows (d->B: rows per launch, not the total), all enqueued on `stream` with no host sync.
+ * t_list is a HOST array of n_t distinct steps in [1, T] (n_t <= 1024); 1 <= n_draws <= 65536; d->V must be 21.  Every argument is
+ * checked before anything is enqueued (DIFFAB_ERR_ARG / DIFFAB_ERR_WORKSPACE with a message).  workspace: diffab_score_workspace_bytes(d,
+ * n_ctx) - sized by d->B and n_ctx, never by the number of designs, steps or draws. */
+typedef struct {
+  int64_t* seq_t; /* (n_designs, n_t, n_draws, K) */
+  float* x_t;     /* (..., K, 3) */
+  float* O_t;     /* (..., K, 3, 3) */
+  float* eps;     /* (..., K, 3) the translation noise (0 where not noised) */
+} diffab_score_noised;
+size_t diffab_score_workspace_bytes(const diffab_dims* d, int32_t n_ctx);
+int diffab_score_designs(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* fwd_tab,
+                         const int64_t* seq, const float* x, const float* O, const uint8_t* gen_mask, const uint8_t* res_mask,
+                         int32_t n_designs, const float* res_ctx, const float* pair_ctx, int32_t n_ctx, const int32_t* ctx_of_design,
+                         const int32_t* t_list, int32_t n_t, int32_t n_draws, uint64_t seed, int64_t first_design, float* out_terms,
+                         float* out_residue, const diffab_score_noised* noised, void* workspace, size_t workspace_bytes, uint32_t flags,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
