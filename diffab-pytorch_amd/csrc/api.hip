@@ -136,27 +136,32 @@ static StepBuffers carve_step(const diffab_dims* d, void* ws, int n_pair = 0) {
   return b;
 }
 
+static bool ipa_layer_weights_ok(const diffab_dims* d, const diffab_ipa_layer_weights* w) {
+  return w && w->gamma && w->wq_s && w->wk_s && w->wv_s && (w->w_bias || d->C == 0) && w->wq_p && w->wk_p && w->wv_p && w->w_out && w->b_out;
+}
+
 static int ipa_layer_dispatch(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R,
                               const float* t, float* y, float* ws, uint32_t flags, hipStream_t st, float* sp_keep = nullptr,
                               float* d2_keep = nullptr, const void* planes = nullptr, const float* pair_planes = nullptr,
                               bool taped = false,  // taped: ws is a slot of the training tape (the backward reads proj and feat)
                               const unsigned char* tile_needed = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0) {
-  DIFFAB_REQUIRE(w && w->gamma && w->wq_s && w->wk_s && w->wv_s && (w->w_bias || d->C == 0) && w->wq_p && w->wk_p && w->wv_p && w->w_out &&
-                     w->b_out,
-                 DIFFAB_ERR_ARG, "ipa layer: null weight pointer");
+  DIFFAB_REQUIRE(ipa_layer_weights_ok(d, w), DIFFAB_ERR_ARG, "ipa layer: null weight pointer");
   if (!(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d))
     return ipa_layer_fast(d, w, x, e, R, t, y, ws, st, sp_keep, d2_keep, planes, pair_planes, (flags & DIFFAB_FLAG_FP32_GEMM) != 0,
                           taped, tile_needed, ctx_of_row, n_ctx);
   return ipa_layer_generic(d, w, x, e, R, t, y, ws, st, ctx_of_row);
 }
 
-static int mlp3(const diffab_dims* d, const diffab_mlp3_weights* w, const float* cat3, float* t1, float* t2, float* out, int n_out,
-                hipStream_t st) {
-  DIFFAB_REQUIRE(w->w0 && w->b0 && w->w2 && w->b2 && w->w4 && w->b4, DIFFAB_ERR_ARG, "denoiser head: null weight pointer");
-  const int rows = d->B * d->K, D = d->D;
-  if (int rc = launch_linear(cat3, D + 3, w->w0, w->b0, t1, D, rows, D, D + 3, true, st)) return rc;
-  if (int rc = launch_linear(t1, D, w->w2, w->b2, t2, D, rows, D, D, true, st)) return rc;
-  return launch_linear(t2, D, w->w4, w->b4, out, n_out, rows, n_out, D, false, st);
+// Every weight pointer the denoiser forward reads, checked on the host before anything is enqueued.
+static int check_denoiser_weights(const diffab_dims* d, const diffab_denoiser_weights* w) {
+  DIFFAB_REQUIRE(w && w->seq_emb && w->res_w0 && w->res_b0 && w->res_w2 && w->res_b2 && (d->NL == 0 || w->layers), DIFFAB_ERR_ARG,
+                 "denoiser: null weight pointer");
+  DIFFAB_REQUIRE(d->C > 0, DIFFAB_ERR_ARG, "denoiser: C must be positive (the Denoiser's IPA layers use the pair bias, :478-492)");
+  for (const diffab_mlp3_weights* h : {&w->coord, &w->orient, &w->seq})
+    DIFFAB_REQUIRE(h->w0 && h->b0 && h->w2 && h->b2 && h->w4 && h->b4, DIFFAB_ERR_ARG, "denoiser head: null weight pointer");
+  for (int l = 0; l < d->NL; ++l)
+    DIFFAB_REQUIRE(ipa_layer_weights_ok(d, &w->layers[l]), DIFFAB_ERR_ARG, "denoiser: null weight pointer in IPA layer %d", l);
+  return DIFFAB_OK;
 }
 
 static bool use_pair_planes(const diffab_dims* d, uint32_t flags, const float* pair_ctx, const StepBuffers& b) {
@@ -165,92 +170,136 @@ static bool use_pair_planes(const diffab_dims* d, uint32_t flags, const float* p
          (reinterpret_cast<uintptr_t>(pair_ctx) & 15) == 0;
 }
 
-// Everything on the folded MFMA path that depends on the weights only: the sequence-embedding bias table and the split bf16 planes
-// of every dense weight matrix.  Once per denoise_step call - or once per trajectory (diffab_sample_loop).
-static int prepare_weights(const diffab_dims* d, const diffab_denoiser_weights* w, const StepBuffers& b, uint32_t flags, hipStream_t st) {
-  DIFFAB_REQUIRE(w->coord.w0 && w->coord.b0 && w->orient.w0 && w->orient.b0 && w->seq.w0 && w->seq.b0 && w->coord.w2 && w->orient.w2 &&
-                     w->seq.w2,
-                 DIFFAB_ERR_ARG, "denoiser head: null weight pointer");
-  if (int rc = launch_fold_tables(d, w, nullptr, b.emb_tab, nullptr, st)) return rc;
-  if (!use_b6_gemm(flags)) return DIFFAB_OK;
-  const int D = d->D;
-  for (int l = 0; l < d->NL; ++l)
-    if (int rc = ipa_layer_split_weights(&w->layers[l], b.planes + l * ipa_layer_planes_bytes(), st)) return rc;
-  char* mlp = b.planes + d->NL * ipa_layer_planes_bytes();
-  const diffab_mlp3_weights* hw[3] = {&w->coord, &w->orient, &w->seq};
-  if (int rc = launch_wsplit128(w->res_w0, 2 * D, D, mlp, st)) return rc;                        // slot 0: res_ctx half of to_res_emb[0]
-  if (int rc = launch_wsplit128(w->res_w2, D, D, mlp + mlp_planes_bytes(), st)) return rc;      // slot 1
-  for (int hd = 0; hd < 3; ++hd) {                                                              // slots 2 + 2 hd, 3 + 2 hd
-    if (int rc = launch_wsplit128(hw[hd]->w0, D + 3, D, mlp + (2 + 2 * hd) * mlp_planes_bytes(), st)) return rc;
-    if (int rc = launch_wsplit128(hw[hd]->w2, D, D, mlp + (3 + 2 * hd) * mlp_planes_bytes(), st)) return rc;
-    DIFFAB_REQUIRE(hw[hd]->w4, DIFFAB_ERR_ARG, "denoiser head: null weight pointer");
-    const int nout = hd == 2 ? d->V : 3;                                                          // slot 8 + hd: the narrow last layer
-    if (int rc = launch_wsplit128(hw[hd]->w4, D, D, mlp + (8 + hd) * mlp_planes_bytes(), st, nout)) return rc;
+// The rule by which the reverse loop and design scoring choose the patch-resident module launch (given its other preconditions): K = 128
+// and a batch that fills the chip with one work-group per patch, without a mostly idle last round.
+static bool module_launch_fills_chip(const diffab_dims* d) {
+  if (!ipa_module_persistent_supported(d)) return false;
+  int dev = 0, ncu = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  const int rounds = (d->B + ncu - 1) / ncu;
+  // (K = 256 - two dense tiles and sixteen two-chunk attention items per patch in the same launch, round 6 - measures SLOWER than its
+  // per-layer launches at B = 512: 19.5 against 18.6 ms per step; it is bitwise the same and stays behind the explicit flag)
+  return d->K == 128 && d->B >= ncu && static_cast<double>(d->B) >= 0.85 * rounds * ncu;
+}
+
+// The launch path of every denoiser forward of one call, decided once by plan_forward: prepare_forward does the call's weights-only
+// work for it, denoise_step runs it once per step.
+struct ForwardPlan {
+  uint32_t flags;  // as the IPA layers read them (DIFFAB_FLAG_FORCE_GENERIC, DIFFAB_FLAG_FP32_GEMM)
+  // Folded concatenations (MFMA path): the sequence-embedding half of to_res_emb[0] and the beta-embedding columns of the three head
+  // MLPs become bias tables, so neither cat[res_ctx, E[s]] nor cat[h, tau] is written or re-read.
+  bool fold;
+  bool b6;     // dense products of the folded path from split weight planes prepared once per call (bf16x6; the layers' f16x3)
+  bool chain;  // each MLP as one row-resident kernel (mlp_chain_b6_kernel) instead of one launch per dense layer
+  // the NL layers as one patch-resident launch (ipa_persistent.hip) - the same tile bodies, bitwise the same result; fused_mlps: the
+  // embedding MLP and the three heads run as phases of that launch, one launch per step in front of the state update
+  bool persistent, fused_mlps;
+  const float* pair_planes;               // fp16 planes of the pair embedding (launch_pair_split), or null: attention reads fp32
+  const int* ctx_of_row;                  // shared contexts: device [B] map, state row b reads context ctx_of_row[b] (null: the identity)
+  int n_ctx;                              // patches of pair_ctx and of its planes (0: d->B)
+  const unsigned char* last_layer_tiles;  // [B][K / 16] row tiles of the LAST layer whose outputs are read (null: all)
+  float* res_emb;                         // the residue embedding after the IPA module is copied here (null: not wanted)
+};
+
+// loop: the call runs many forwards (reverse sampler, design scoring).  There the pair embedding is the same tensor in every attention
+// launch, so its fp16 planes are on unless DIFFAB_FLAG_PAIR_F32, and the module launch is chosen by module_launch_fills_chip unless
+// DIFFAB_FLAG_MULTI_LAUNCH; a single forward takes both from its flags.  tiles: the reverse sampler's buffer of the row-tile map.
+static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const StepBuffers& b, const float* res_ctx, const float* pair_ctx,
+                                float* res_emb, bool loop, const int* ctx_of_row = nullptr, int n_ctx = 0, unsigned char* tiles = nullptr) {
+  const int rows = d->B * d->K, D = d->D;
+  if (loop && !(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
+  ForwardPlan p{};
+  p.flags = flags;
+  p.fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) && rowgemm128_ok(res_ctx, D, b.h1, D, rows, D);
+  p.b6 = p.fold && use_b6_gemm(flags) && rowgemm128_b6_ok(res_ctx, D, b.h1, D, rows, D);
+  p.chain = p.b6 && d->V <= 128;
+  p.pair_planes = use_pair_planes(d, flags, pair_ctx, b) ? b.pair : nullptr;
+  p.ctx_of_row = ctx_of_row;
+  p.n_ctx = n_ctx;
+  // DIFFAB_FLAG_SKIP_UNUSED_ROWS (reverse sampler): the step's outputs (eps, O0, posterior) are read for GENERATED residues only
+  // (reverse_update leaves the others alone), so the last layer's attention is needed only for row tiles that contain one; every
+  // other layer feeds keys and values of all rows to the next.  Same trajectory, bit for bit; the work skipped depends on the mask,
+  // so bench.py's headline keeps it off.
+  p.last_layer_tiles = (flags & DIFFAB_FLAG_SKIP_UNUSED_ROWS) && p.fold && d->K % 16 == 0 ? tiles : nullptr;
+  p.res_emb = res_emb;
+  // The module launch of a loop: bitwise the 3 NL launches it replaces, so the choice never shows in the results.  When the batch fills
+  // the chip with one work-group per patch it wins (B = 256: 2.60 ms per step against 2.70); fewer patches than CUs leave CUs idle for
+  // the whole module (B = 8: 2.07 ms against 0.47), a ragged last round of patches costs a module time for a few of them.
+  p.persistent = p.b6 && p.pair_planes != nullptr && ipa_module_persistent_supported(d) && p.last_layer_tiles == nullptr &&
+                 ((flags & DIFFAB_FLAG_PERSISTENT_MODULE) || (loop && !(flags & DIFFAB_FLAG_MULTI_LAUNCH) && module_launch_fills_chip(d)));
+  p.fused_mlps = p.persistent && p.chain && D == 128 && res_emb == nullptr;
+  return p;
+}
+
+// The per-step head bias: beta of every patch, or (reverse sampler: every patch is at step t, or *t_dev under graph replay) the
+// schedule's sched_beta[t], which the folded head tables read themselves; `beta` is then read by the unfolded path only.
+struct StepBias {
+  const float* beta;
+  const float* sched_beta;
+  int t;
+  const int* t_dev;
+  // chain path of the eager reverse loop: [3 heads][traj_rows steps][D] the heads' folded beta columns of EVERY step (row t this
+  // step's), built once per call by prepare_forward instead of a table per step
+  float* beta_traj;
+  int traj_rows;
+};
+
+// Everything of a call's forwards that depends on the weights and contexts only, once per call: on the folded path the
+// sequence-embedding bias table and the split planes of every dense weight matrix, the fp16 planes of the n_ctx pair embeddings, and
+// the table of every step's head columns when `bias` names one.
+static int prepare_forward(const diffab_dims* d, const diffab_denoiser_weights* w, const ForwardPlan& p, const StepBuffers& b,
+                           const float* pair_ctx, const StepBias& bias, hipStream_t st) {
+  if (p.fold)
+    if (int rc = launch_fold_embed_table(d, w, b.emb_tab, st)) return rc;
+  if (p.b6) {
+    const int D = d->D;
+    for (int l = 0; l < d->NL; ++l)
+      if (int rc = ipa_layer_split_weights(&w->layers[l], b.planes + l * ipa_layer_planes_bytes(), st)) return rc;
+    char* mlp = b.planes + d->NL * ipa_layer_planes_bytes();
+    const diffab_mlp3_weights* hw[3] = {&w->coord, &w->orient, &w->seq};
+    if (int rc = launch_wsplit128(w->res_w0, 2 * D, D, mlp, st)) return rc;                        // slot 0: res_ctx half of to_res_emb[0]
+    if (int rc = launch_wsplit128(w->res_w2, D, D, mlp + mlp_planes_bytes(), st)) return rc;      // slot 1
+    for (int hd = 0; hd < 3; ++hd) {                                                              // slots 2 + 2 hd, 3 + 2 hd
+      if (int rc = launch_wsplit128(hw[hd]->w0, D + 3, D, mlp + (2 + 2 * hd) * mlp_planes_bytes(), st)) return rc;
+      if (int rc = launch_wsplit128(hw[hd]->w2, D, D, mlp + (3 + 2 * hd) * mlp_planes_bytes(), st)) return rc;
+      const int nout = hd == 2 ? d->V : 3;                                                          // slot 8 + hd: the narrow last layer
+      if (int rc = launch_wsplit128(hw[hd]->w4, D, D, mlp + (8 + hd) * mlp_planes_bytes(), st, nout)) return rc;
+    }
+  }
+  if (p.pair_planes)
+    if (int rc = launch_pair_split(d, pair_ctx, b.pair, st, p.n_ctx)) return rc;
+  if (bias.beta_traj) {  // the same kernel and formula as the per-step table, "patch" = step
+    diffab_dims dt = *d;
+    dt.B = bias.traj_rows;
+    if (int rc = launch_fold_beta_table(&dt, w, bias.sched_beta, bias.beta_traj, st)) return rc;
   }
   return DIFFAB_OK;
 }
 
-static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, const int64_t* seq_t, const float* x_t, const float* O_t,
-                        const float* res_ctx, const float* pair_ctx, const float* beta, float* out_eps, float* out_O0, float* out_post,
-                        float* out_logits, float* out_res_emb, void* ws, uint32_t flags, hipStream_t st, bool weights_prepared = false,
-                        bool pair_prepared = false, const float* sched_beta = nullptr, int t_step = 0, const int* t_dev = nullptr,
-                        const unsigned char* last_layer_tiles = nullptr,  // row tiles of the LAST layer whose outputs are read
-                        bool skip_heads_finish = false,  // the caller finishes the heads itself from b.vbuf / b.logits (reverse sampler)
-                        const float* beta_traj = nullptr, int traj_rows = 0,  // [3 heads][traj_rows steps][D]: the heads' folded beta
-                                                                              // columns of EVERY step (row t_step is this step's)
-                        const int* ctx_of_row = nullptr, int n_ctx = 0) {  // shared contexts (reverse sampler): pair_ctx / its planes hold
-                                                                           // n_ctx patches, state row b reads context ctx_of_row[b]
-  // sched_beta (reverse sampler): every patch is at step t_step (or *t_dev): the folded head tables take beta from the schedule and
-  // `beta` is only read by the unfolded path
-  const StepBuffers b = carve_step(d, ws);
+// One denoiser forward along a prepared plan.  out_O0 == nullptr: the caller finishes the heads itself from b.vbuf / b.logits.
+static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, const ForwardPlan& p, const StepBias& bias,
+                        const int64_t* seq_t, const float* x_t, const float* O_t, const float* res_ctx, const float* pair_ctx, float* out_eps,
+                        float* out_O0, float* out_post, float* out_logits, const StepBuffers& b, hipStream_t st) {
   const int rows = d->B * d->K, D = d->D;
-  // DIFFAB_FLAG_PAIR_PLANES: the pair embedding as two fp16 planes (same bytes), attention's pair-tile products on the f16 matrix
-  // cores.  The reverse sampler splits once per trajectory (pair_prepared); a single call splits here, per call.
-  const float* pair_planes = nullptr;
-  if (use_pair_planes(d, flags, pair_ctx, b)) {
-    if (!pair_prepared)
-      if (int rc = launch_pair_split(d, pair_ctx, b.pair, st)) return rc;
-    pair_planes = b.pair;
-  }
-  // Folded concatenations (MFMA path): the sequence-embedding half of to_res_emb[0] and the beta-embedding columns of the three
-  // head MLPs become bias tables, so neither cat[res_ctx, E[s]] nor cat[h, tau] is written or re-read.
-  const bool fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) && rowgemm128_ok(res_ctx, D, b.h1, D, rows, D);
-  // dense N = 128 layers of the folded path: bf16x6 from the prepared planes (slot), or the fp32 kernel; each MLP as one row-resident
-  // kernel (mlp_chain_b6_kernel), one launch per dense layer only where the chain does not apply
-  const bool b6 = fold && use_b6_gemm(flags) && rowgemm128_b6_ok(res_ctx, D, b.h1, D, rows, D);
-  const bool chain = b6 && d->V <= 128;
-  if (!chain) beta_traj = nullptr;  // (the per-call table of every step's head columns is read by the chain kernel only)
-  if (fold) {
-    DIFFAB_REQUIRE(w->coord.w0 && w->coord.b0 && w->orient.w0 && w->orient.b0 && w->seq.w0 && w->seq.b0, DIFFAB_ERR_ARG,
-                   "denoiser head: null weight pointer");
-    if (!weights_prepared)
-      if (int rc = prepare_weights(d, w, b, flags, st)) return rc;
-    if (beta_traj == nullptr)
-      if (int rc = launch_fold_tables(d, w, beta, b.emb_tab, b.beta_tab, st, true, sched_beta, t_step, t_dev)) return rc;
-  }
-  const char* mlp = b6 ? b.planes + d->NL * ipa_layer_planes_bytes() : nullptr;
-  auto dense128 = [&](int slot, const float* X, const float* W, int ldw, const float* bias, const int64_t* bias_idx, int bias_div, float* Y,
+  if (p.fold && bias.beta_traj == nullptr)
+    if (int rc = launch_fold_beta_table(d, w, bias.beta, b.beta_tab, st, bias.sched_beta, bias.t, bias.t_dev)) return rc;
+  const char* mlp = p.b6 ? b.planes + d->NL * ipa_layer_planes_bytes() : nullptr;
+  auto dense128 = [&](int slot, const float* X, const float* W, int ldw, const float* bvec, const int64_t* bias_idx, int bias_div, float* Y,
                       bool relu) -> int {
-    if (b6) return launch_rowgemm128_b6p(X, D, mlp + slot * mlp_planes_bytes(), bias, bias_idx, bias_div, Y, D, rows, D, relu, st);
-    return launch_rowgemm128(X, D, W, ldw, bias, bias_idx, bias_div, Y, D, rows, D, relu, st);
+    if (p.b6) return launch_rowgemm128_b6p(X, D, mlp + slot * mlp_planes_bytes(), bvec, bias_idx, bias_div, Y, D, rows, D, relu, st);
+    return launch_rowgemm128(X, D, W, ldw, bvec, bias_idx, bias_div, Y, D, rows, D, relu, st);
   };
-  // DIFFAB_FLAG_PERSISTENT_MODULE: the NL layers as one patch-resident launch (ipa_persistent.hip) - the same tile bodies, bitwise the
-  // same result; needs the prepared planes of all layers, the pair planes, and K = 128.  Where the MLP chains apply too, the embedding
-  // MLP and the three heads run as phases of that launch (fused_mlps): one launch per step in front of the state update.
-  const bool persistent = (flags & DIFFAB_FLAG_PERSISTENT_MODULE) && fold && use_b6_gemm(flags) && pair_planes != nullptr &&
-                          ipa_module_persistent_supported(d) && last_layer_tiles == nullptr;
-  const bool fused_mlps = persistent && chain && D == 128 && out_res_emb == nullptr;
   float* logits = out_logits ? out_logits : b.logits;
   MlpChainSet emb_set{}, head_set{};
-  if (fold && chain) {
+  if (p.chain) {
     const void* pl[3] = {mlp, mlp + mlp_planes_bytes(), nullptr};
     const float* bs[3] = {b.emb_tab, w->res_b2, nullptr};
     float* ys[1] = {b.hA};
     const int nout1[1] = {D};
     if (int rc = make_mlp_chain_set(&emb_set, 1, pl, bs, seq_t, 0, 2, nout1, ys, nout1)) return rc;
-    if (!fused_mlps)
+    if (!p.fused_mlps)
       if (int rc = launch_mlp_chain_b6(res_ctx, D, pl, bs, seq_t, 0, 2, D, b.hA, D, rows, st)) return rc;
-  } else if (fold) {
+  } else if (p.fold) {
     if (int rc = dense128(0, res_ctx, w->res_w0, 2 * D, b.emb_tab, seq_t, 0, b.h1, true)) return rc;
     if (int rc = dense128(1, b.h1, w->res_w2, D, w->res_b2, nullptr, 0, b.hA, false)) return rc;
   } else {
@@ -264,51 +313,53 @@ static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, 
   const int nout[3] = {3, 3, d->V};
   const void* hpl[9];
   const float* hbs[9];
-  if (fold && chain) {  // the three heads read the same rows: one launch (blockIdx.y = head), or three phases of the module launch
+  // (beta_traj: one table row for every patch - "row / rows" is 0 for all of them)
+  const int head_div = bias.beta_traj ? rows : d->K;
+  if (p.chain) {  // the three heads read the same rows: one launch (blockIdx.y = head), or three phases of the module launch
     for (int hd = 0; hd < 3; ++hd) {
-      DIFFAB_REQUIRE(hw[hd]->w2 && hw[hd]->b2 && hw[hd]->w4 && hw[hd]->b4, DIFFAB_ERR_ARG, "denoiser head: null weight pointer");
       hpl[3 * hd] = mlp + (2 + 2 * hd) * mlp_planes_bytes();
       hpl[3 * hd + 1] = mlp + (3 + 2 * hd) * mlp_planes_bytes();
       hpl[3 * hd + 2] = mlp + (8 + hd) * mlp_planes_bytes();
-      hbs[3 * hd] = beta_traj ? beta_traj + (static_cast<size_t>(hd) * traj_rows + t_step) * D : b.beta_tab + static_cast<size_t>(hd) * d->B * D;
+      hbs[3 * hd] = bias.beta_traj ? bias.beta_traj + (static_cast<size_t>(hd) * bias.traj_rows + bias.t) * D
+                                   : b.beta_tab + static_cast<size_t>(hd) * d->B * D;
       hbs[3 * hd + 1] = hw[hd]->b2;
       hbs[3 * hd + 2] = hw[hd]->b4;
     }
-    // (beta_traj: one table row for every patch - "row / rows" is 0 for all of them)
-    if (int rc = make_mlp_chain_set(&head_set, 3, hpl, hbs, nullptr, beta_traj ? rows : d->K, 3, nout, outs, nout)) return rc;
+    if (int rc = make_mlp_chain_set(&head_set, 3, hpl, hbs, nullptr, head_div, 3, nout, outs, nout)) return rc;
   }
-  if (persistent) {
-    if (int rc = launch_ipa_module_persistent(d, b.hA, b.hB, O_t, x_t, b.ipa, b.planes, pair_planes, st, fused_mlps ? res_ctx : nullptr,
-                                              &emb_set, &head_set, ctx_of_row, n_ctx))
+  if (p.persistent) {
+    if (int rc = launch_ipa_module_persistent(d, b.hA, b.hB, O_t, x_t, b.ipa, b.planes, p.pair_planes, st, p.fused_mlps ? res_ctx : nullptr,
+                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx))
       return rc;
     cur = (d->NL & 1) ? b.hB : b.hA;
   }
-  for (int l = 0; l < d->NL && !persistent; ++l) {
-    const void* planes = (fold && use_b6_gemm(flags)) ? b.planes + l * ipa_layer_planes_bytes() : nullptr;
-    if (int rc = ipa_layer_dispatch(d, &w->layers[l], cur, pair_ctx, O_t, x_t, nxt, b.ipa, flags, st, nullptr, nullptr, planes, pair_planes,
-                                    false, l == d->NL - 1 ? last_layer_tiles : nullptr, ctx_of_row, n_ctx))
+  for (int l = 0; l < d->NL && !p.persistent; ++l) {
+    const void* planes = p.b6 ? b.planes + l * ipa_layer_planes_bytes() : nullptr;
+    if (int rc = ipa_layer_dispatch(d, &w->layers[l], cur, pair_ctx, O_t, x_t, nxt, b.ipa, p.flags, st, nullptr, nullptr, planes, p.pair_planes,
+                                    false, l == d->NL - 1 ? p.last_layer_tiles : nullptr, p.ctx_of_row, p.n_ctx))
       return rc;
     float* tmp = cur; cur = nxt; nxt = tmp;
   }
-  if (out_res_emb) DIFFAB_HIP_CHECK(hipMemcpyAsync(out_res_emb, cur, sizeof(float) * rows * D, hipMemcpyDeviceToDevice, st));
-  if (fold) {
-    for (int hd = 0; hd < 3; ++hd)
-      DIFFAB_REQUIRE(hw[hd]->w2 && hw[hd]->b2 && hw[hd]->w4 && hw[hd]->b4, DIFFAB_ERR_ARG, "denoiser head: null weight pointer");
-    if (chain && !fused_mlps)
-      if (int rc = launch_mlp_chains_b6(cur, D, 3, hpl, hbs, nullptr, beta_traj ? rows : d->K, 3, nout, outs, nout, rows, st)) return rc;
-    for (int hd = 0; hd < 3 && !chain; ++hd) {
+  if (p.res_emb) DIFFAB_HIP_CHECK(hipMemcpyAsync(p.res_emb, cur, sizeof(float) * rows * D, hipMemcpyDeviceToDevice, st));
+  if (p.chain) {
+    if (!p.fused_mlps)
+      if (int rc = launch_mlp_chains_b6(cur, D, 3, hpl, hbs, nullptr, head_div, 3, nout, outs, nout, rows, st)) return rc;
+  } else if (p.fold) {
+    for (int hd = 0; hd < 3; ++hd) {
       if (int rc = dense128(2 + 2 * hd, cur, hw[hd]->w0, D + 3, b.beta_tab + static_cast<size_t>(hd) * d->B * D, nullptr, d->K, b.t1, true))
         return rc;
       if (int rc = dense128(3 + 2 * hd, b.t1, hw[hd]->w2, D, hw[hd]->b2, nullptr, 0, b.t2, true)) return rc;
       if (int rc = launch_linear(b.t2, D, hw[hd]->w4, hw[hd]->b4, outs[hd], nout[hd], rows, nout[hd], D, false, st)) return rc;
     }
   } else {
-    if (int rc = launch_beta_concat(cur, beta, D, d->K, rows, b.cat3, st)) return rc;
-    if (int rc = mlp3(d, &w->coord, b.cat3, b.t1, b.t2, out_eps, 3, st)) return rc;
-    if (int rc = mlp3(d, &w->orient, b.cat3, b.t1, b.t2, b.vbuf, 3, st)) return rc;
-    if (int rc = mlp3(d, &w->seq, b.cat3, b.t1, b.t2, logits, d->V, st)) return rc;
+    if (int rc = launch_beta_concat(cur, bias.beta, D, d->K, rows, b.cat3, st)) return rc;
+    for (int hd = 0; hd < 3; ++hd) {
+      if (int rc = launch_linear(b.cat3, D + 3, hw[hd]->w0, hw[hd]->b0, b.t1, D, rows, D, D + 3, true, st)) return rc;
+      if (int rc = launch_linear(b.t1, D, hw[hd]->w2, hw[hd]->b2, b.t2, D, rows, D, D, true, st)) return rc;
+      if (int rc = launch_linear(b.t2, D, hw[hd]->w4, hw[hd]->b4, outs[hd], nout[hd], rows, nout[hd], D, false, st)) return rc;
+    }
   }
-  if (skip_heads_finish) return DIFFAB_OK;
+  if (out_O0 == nullptr) return DIFFAB_OK;
   return launch_heads_finish(b.vbuf, O_t, logits, d->V, rows, out_O0, out_post, st);
 }
 
@@ -326,7 +377,7 @@ static int denoise_step_taped(const diffab_dims* d, const diffab_denoiser_weight
   if (int rc = launch_embed_concat(res_ctx, w->seq_emb, seq_t, D, rows, tp.cat2, st)) return rc;
   if (int rc = launch_linear(tp.cat2, 2 * D, w->res_w0, w->res_b0, tp.h1, D, rows, D, 2 * D, true, st)) return rc;
   if (int rc = launch_linear(tp.h1, D, w->res_w2, w->res_b2, tp.x[0], D, rows, D, D, false, st)) return rc;
-  const bool b6 = tp.planes && use_b6_gemm(flags) && !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d);
+  const bool b6 = tp.planes && use_b6_gemm(flags) && fast_path_supported(d);
   for (int l = 0; l < d->NL; ++l) {
     if (b6)
       if (int rc = ipa_layer_split_weights(&w->layers[l], tp.planes, st)) return rc;
@@ -339,20 +390,11 @@ static int denoise_step_taped(const diffab_dims* d, const diffab_denoiser_weight
   float* outs[3] = {out_eps, tp.vbuf, tp.logits};
   const int nout[3] = {3, 3, d->V};
   for (int hd = 0; hd < 3; ++hd) {
-    DIFFAB_REQUIRE(hw[hd]->w0 && hw[hd]->b0 && hw[hd]->w2 && hw[hd]->b2 && hw[hd]->w4 && hw[hd]->b4, DIFFAB_ERR_ARG,
-                   "denoiser head: null weight pointer");
     if (int rc = launch_linear(tp.cat3, D + 3, hw[hd]->w0, hw[hd]->b0, tp.t1[hd], D, rows, D, D + 3, true, st)) return rc;
     if (int rc = launch_linear(tp.t1[hd], D, hw[hd]->w2, hw[hd]->b2, tp.t2[hd], D, rows, D, D, true, st)) return rc;
     if (int rc = launch_linear(tp.t2[hd], D, hw[hd]->w4, hw[hd]->b4, outs[hd], nout[hd], rows, nout[hd], D, false, st)) return rc;
   }
   return launch_heads_finish(tp.vbuf, O_t, tp.logits, d->V, rows, out_O0, out_post, st);
-}
-
-static int check_denoiser_weights(const diffab_dims* d, const diffab_denoiser_weights* w) {
-  DIFFAB_REQUIRE(w && w->seq_emb && w->res_w0 && w->res_b0 && w->res_w2 && w->res_b2 && (d->NL == 0 || w->layers), DIFFAB_ERR_ARG,
-                 "denoiser: null weight pointer");
-  DIFFAB_REQUIRE(d->C > 0, DIFFAB_ERR_ARG, "denoiser: C must be positive (the Denoiser's IPA layers use the pair bias, :478-492)");
-  return DIFFAB_OK;
 }
 
 constexpr int kTrajRows = 1025;  // schedules up to T = 1024 get their per-step head tables built once per call
@@ -385,18 +427,6 @@ static SampleBuffers carve_sample(const diffab_dims* d, void* ws, int n_pair = 0
   s.step = c.take<char>(step_bytes);
   s.bytes = c.bytes();
   return s;
-}
-
-// The rule by which the reverse loop and design scoring choose the patch-resident module launch (given its other preconditions): K = 128
-// and a batch that fills the chip with one work-group per patch, without a mostly idle last round.
-static bool module_launch_fills_chip(const diffab_dims* d) {
-  if (!ipa_module_persistent_supported(d)) return false;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  const int rounds = (d->B + ncu - 1) / ncu;
-  // (K = 256 - two dense tiles and sixteen two-chunk attention items per patch in the same launch, round 6 - measures SLOWER than its
-  // per-layer launches at B = 512: 19.5 against 18.6 ms per step; it is bitwise the same and stays behind the explicit flag)
-  return d->K == 128 && d->B >= ncu && static_cast<double>(d->B) >= 0.85 * rounds * ncu;
 }
 
 // diffab_score_designs: the state of one chunk of d->B evaluated rows, and the step buffers of its denoiser call
@@ -575,10 +605,13 @@ int diffab_denoise_step_fwd(const diffab_dims* d, const diffab_denoiser_weights*
   if (int rc = check_denoiser_weights(d, w)) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && res_ctx && pair_ctx && beta && out_eps && out_O0 && out_posterior && workspace, DIFFAB_ERR_ARG,
                  "denoise_step_fwd: null pointer");
-  const size_t need = carve_step(d, nullptr).bytes;
-  DIFFAB_REQUIRE(workspace_bytes >= need, DIFFAB_ERR_WORKSPACE, "denoise_step_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
-  return denoise_step(d, w, seq_t, x_t, O_t, res_ctx, pair_ctx, beta, out_eps, out_O0, out_posterior, out_logits, out_res_emb, workspace,
-                      flags, as_stream(stream));
+  const StepBuffers b = carve_step(d, workspace);
+  DIFFAB_REQUIRE(workspace_bytes >= b.bytes, DIFFAB_ERR_WORKSPACE, "denoise_step_fwd: workspace %zu < %zu bytes", workspace_bytes, b.bytes);
+  hipStream_t st = as_stream(stream);
+  const ForwardPlan p = plan_forward(d, flags, b, res_ctx, pair_ctx, out_res_emb, false);
+  const StepBias bias{beta};
+  if (int rc = prepare_forward(d, w, p, b, pair_ctx, bias, st)) return rc;
+  return denoise_step(d, w, p, bias, seq_t, x_t, O_t, res_ctx, pair_ctx, out_eps, out_O0, out_posterior, out_logits, b, st);
 }
 
 size_t diffab_train_tape_bytes(const diffab_dims* d) {
@@ -773,50 +806,23 @@ int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weight
     ctx_dev = sb.ctx_of_row;
     res_ctx = sb.res_ctx;
   }
-  // the folded sequence-embedding table depends on the weights only: once per call, not once per step (same condition as denoise_step)
   const StepBuffers b0 = carve_step(d, sb.step, n_ctx);
-  const bool fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) &&
-                    rowgemm128_ok(res_ctx, d->D, b0.h1, d->D, d->B * d->K, d->D);
-  if (fold)
-    if (int rc = prepare_weights(d, w, b0, flags, st)) return rc;
-  // the pair embedding is the same tensor in all T x NL attention launches of a trajectory: its fp16 planes are built once here, for the
-  // n_ctx contexts
-  if (!(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
-  const bool pair_ready = use_pair_planes(d, flags, pair_ctx, b0);
-  if (pair_ready)
-    if (int rc = launch_pair_split(d, pair_ctx, b0.pair, st, n_ctx)) return rc;
-  // The IPA module as ONE patch-resident launch per step (ipa_persistent.hip; bitwise the 3 NL launches it replaces, so the choice never
-  // shows in the samples) when the batch fills the chip with one work-group per patch: B = 256 is 2.60 ms per step against 2.70.  Fewer
-  // patches than CUs leave CUs idle for the whole module (B = 8: 2.07 ms against 0.47), a ragged last round of patches costs a module
-  // time for a few of them - those shapes keep the per-layer launches.
-  if (!(flags & DIFFAB_FLAG_MULTI_LAUNCH) && pair_ready && fold && use_b6_gemm(flags) && module_launch_fills_chip(d))
-    flags |= DIFFAB_FLAG_PERSISTENT_MODULE;
-  // DIFFAB_FLAG_SKIP_UNUSED_ROWS: the step's outputs (eps, O0, posterior) are read for GENERATED residues only (reverse_update leaves
-  // the others alone), so the last layer's attention is needed only for row tiles that contain one; every other layer feeds keys and
-  // values of all rows to the next.  Same trajectory, bit for bit; the work skipped depends on the mask, so bench.py's headline keeps it off.
-  const unsigned char* tiles = nullptr;
-  if ((flags & DIFFAB_FLAG_SKIP_UNUSED_ROWS) && fold && d->K % 16 == 0) {
-    if (int rc = launch_tiles_needed(gen_mask, d->B, d->K, sb.tiles, st)) return rc;
-    tiles = sb.tiles;
-  }
+  const ForwardPlan plan = plan_forward(d, flags, b0, res_ctx, pair_ctx, nullptr, true, ctx_dev, n_ctx, sb.tiles);
   // The heads' folded beta columns depend on (step, head, column) only - every patch of a reverse step has the same beta - so the table
-  // of ALL steps is built once per call (the same kernel and formula as the per-step table, "patch" = step) instead of once per step.
-  // Eager loop only: under graph replay the step index lives in device memory and the chain's bias pointer is a launch argument.
-  const bool chain_path = fold && use_b6_gemm(flags) && d->V <= 128;  // (denoise_step's `chain`)
-  const float* beta_traj = nullptr;
-  if (chain_path && s->T + 1 <= kTrajRows && !(flags & DIFFAB_FLAG_GRAPH_SAMPLER)) {
-    diffab_dims dt = *d;
-    dt.B = s->T + 1;
-    if (int rc = launch_fold_tables(&dt, w, s->beta, nullptr, sb.beta_traj, st, true)) return rc;
-    beta_traj = sb.beta_traj;
-  }
+  // of ALL steps is built once per call instead of once per step.  Eager loop only: under graph replay the step index lives in device
+  // memory and the chain's bias pointer is a launch argument.
+  StepBias bias{sb.beta, plan.fold ? s->beta : nullptr, 0, nullptr, nullptr, s->T + 1};
+  if (plan.chain && s->T + 1 <= kTrajRows && !(flags & DIFFAB_FLAG_GRAPH_SAMPLER)) bias.beta_traj = sb.beta_traj;
+  if (int rc = prepare_forward(d, w, plan, b0, pair_ctx, bias, st)) return rc;
+  if (plan.last_layer_tiles)
+    if (int rc = launch_tiles_needed(gen_mask, d->B, d->K, sb.tiles, st)) return rc;
   auto one_step = [&](int t, const int* t_dev) -> int {
-    if (!fold)  // (the folded head tables read the schedule themselves: one launch less per step)
+    if (!plan.fold)  // (the folded head tables read the schedule themselves: one launch less per step)
       if (int rc = launch_fill_beta(s, t, d->B, sb.beta, st, t_dev)) return rc;
-    if (int rc = denoise_step(d, w, seq, x, O, res_ctx, pair_ctx, sb.beta, sb.eps, sb.O0, sb.post, nullptr, nullptr, sb.step, flags, st, fold,
-                              pair_ready, fold ? s->beta : nullptr, t, t_dev, tiles, true, t_dev ? nullptr : beta_traj, s->T + 1, ctx_dev,
-                              n_ctx))
-      return rc;
+    StepBias step = bias;
+    step.t = t;
+    step.t_dev = t_dev;
+    if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
                                         t_dev, b0.vbuf, b0.logits, keep);
@@ -925,18 +931,10 @@ int diffab_score_designs(const diffab_dims* d, const diffab_denoiser_weights* w,
   flags &= ~(keep | DIFFAB_FLAG_GRAPH_SAMPLER | DIFFAB_FLAG_SKIP_UNUSED_ROWS);
   hipStream_t st = as_stream(stream);
   DIFFAB_HIP_CHECK(hipMemcpyAsync(sb.t_list, t_list, sizeof(int32_t) * n_t, hipMemcpyHostToDevice, st));
-  // once per call, as in diffab_sample_loop_shared: the folded weights and the fp16 pair planes of the n_ctx contexts
   const StepBuffers b0 = carve_step(d, sb.step, n_ctx);
-  const bool fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) &&
-                    rowgemm128_ok(sb.res_ctx, d->D, b0.h1, d->D, d->B * d->K, d->D);
-  if (fold)
-    if (int rc = prepare_weights(d, w, b0, flags, st)) return rc;
-  if (!(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
-  const bool pair_ready = use_pair_planes(d, flags, pair_ctx, b0);
-  if (pair_ready)
-    if (int rc = launch_pair_split(d, pair_ctx, b0.pair, st, n_ctx)) return rc;
-  if (!(flags & DIFFAB_FLAG_MULTI_LAUNCH) && pair_ready && fold && use_b6_gemm(flags) && module_launch_fills_chip(d))
-    flags |= DIFFAB_FLAG_PERSISTENT_MODULE;
+  const ForwardPlan plan = plan_forward(d, flags, b0, sb.res_ctx, pair_ctx, nullptr, true, sb.ctx_of_row, n_ctx);
+  const StepBias bias{sb.beta};  // per-row beta: the heads' folded beta columns come from the per-chunk table
+  if (int rc = prepare_forward(d, w, plan, b0, pair_ctx, bias, st)) return rc;
   const diffab_score_noised out = noised ? *noised : diffab_score_noised{nullptr, nullptr, nullptr, nullptr};
   const int64_t total = static_cast<int64_t>(n_designs) * n_t * n_draws;
   for (int64_t q0 = 0; q0 < total; q0 += d->B) {
@@ -945,9 +943,7 @@ int diffab_score_designs(const diffab_dims* d, const diffab_denoiser_weights* w,
                                     sb.beta, sb.ctx_of_row, out, st))
       return rc;
     if (int rc = launch_gather_rows(res_ctx, sb.ctx_of_row, d->B, static_cast<int64_t>(d->K) * d->D, sb.res_ctx, st)) return rc;
-    // per-row beta: the heads' folded beta columns come from the per-chunk table (launch_fold_tables on sb.beta)
-    if (int rc = denoise_step(d, w, sb.seq_t, sb.x_t, sb.O_t, sb.res_ctx, pair_ctx, sb.beta, sb.eps_hat, nullptr, nullptr, nullptr, nullptr,
-                              sb.step, flags, st, fold, pair_ready, nullptr, 0, nullptr, nullptr, true, nullptr, 0, sb.ctx_of_row, n_ctx))
+    if (int rc = denoise_step(d, w, plan, bias, sb.seq_t, sb.x_t, sb.O_t, sb.res_ctx, pair_ctx, sb.eps_hat, nullptr, nullptr, nullptr, b0, st))
       return rc;
     if (int rc = launch_score_losses(s, c, seq, O, gen_mask, res_mask, sb.seq_t, sb.O_t, sb.eps, sb.eps_hat, b0.vbuf, b0.logits, out_terms,
                                      out_residue, st))

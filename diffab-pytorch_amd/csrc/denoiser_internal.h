@@ -117,10 +117,11 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
                                  const MlpChainSet* heads = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0);
 void set_module_stagger(int ticks, int classes);  // diagnostics: start-up stagger of the persistent module kernel (10 ns ticks)
 void set_module_stamps(void* device_buffer);      // diagnostics: phase stamps of the persistent module kernel
-// bias tables of the folded concatenations: emb_tab[25][D] and beta_tab[3 heads][B][D] (see denoiser_fast.hip)
-int launch_fold_tables(const diffab_dims* d, const diffab_denoiser_weights* w, const float* beta, float* emb_tab, float* beta_tab,
-                       hipStream_t st, bool emb_tab_ready = false,
-                       const float* sched_beta = nullptr, int t = 0, const int* t_dev = nullptr);  // beta = sched_beta[t] for every patch  // beta == nullptr: the weights-only embedding table alone
+// bias tables of the folded concatenations (see denoiser_fast.hip): emb_tab[25][D] depends on the weights only; beta_tab[3 heads][B][D]
+// takes beta[b] per patch, or sched_beta[t] (t = *t_dev when t_dev is given) for every patch
+int launch_fold_embed_table(const diffab_dims* d, const diffab_denoiser_weights* w, float* emb_tab, hipStream_t st);
+int launch_fold_beta_table(const diffab_dims* d, const diffab_denoiser_weights* w, const float* beta, float* beta_tab, hipStream_t st,
+                           const float* sched_beta = nullptr, int t = 0, const int* t_dev = nullptr);
 
 // pair_embed_fused.hip: PairEmbedding forward as one kernel (C = 64, K % 128 == 0, A <= 16); context_kernels.hip falls back to its
 // unfused launches elsewhere.  prep: pair_embed_fused_prep_floats(d) floats (prepared planes and tables, rebuilt per call); tapes

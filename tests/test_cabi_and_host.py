@@ -52,6 +52,31 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_hip.Sched) == 48 and ctypes.sizeof(_hip.Igso3) == 32
 
 
+def test_null_denoiser_weight_is_refused_on_the_host():
+    """Every weight pointer the denoiser forward reads (embedding MLP, every IPA layer, the three heads) is checked before anything is
+    enqueued: DIFFAB_ERR_ARG with a weight message.  The workspace is given as 0 bytes, so a call whose weight check missed would stop
+    at the workspace check (DIFFAB_ERR_WORKSPACE), still on the host; no GPU is touched either way."""
+    l = _hip.load_library()
+    dims = syn.BENCH_DIMS
+    d = _hip.Dims(2, 128, dims["D"], dims["C"], dims["H"], dims["DS"], dims["PQ"], dims["PV"], 2, 21)
+    fake = 256  # never dereferenced: every call below returns before it enqueues work
+    layers = (_hip.IpaLayerWeights * 2)(*[_hip.IpaLayerWeights(*[fake] * 10) for _ in range(2)])
+    heads = [_hip.Mlp3Weights(*[fake] * 6) for _ in range(3)]
+    w = _hip.DenoiserWeights(*[fake] * 5, ctypes.cast(layers, ctypes.POINTER(_hip.IpaLayerWeights)), *heads)
+
+    def call():
+        return l.diffab_denoise_step_fwd(ctypes.byref(d), ctypes.byref(w), *[fake] * 12, 0, 0, None)  # 11 tensors + workspace
+
+    assert call() == -4  # DIFFAB_ERR_WORKSPACE: all weights present, the next check refuses the call
+    for obj, field in [(w.coord, "w0"), (w.orient, "b2"), (w.seq, "w4"), (w.seq, "b4"), (layers[1], "gamma"), (layers[0], "w_bias"),
+                       (layers[1], "b_out")]:
+        setattr(obj, field, None)
+        assert call() == -1, field  # DIFFAB_ERR_ARG
+        assert b"null weight pointer" in l.diffab_last_error(), field
+        setattr(obj, field, fake)
+    assert call() == -4
+
+
 def test_schedule_is_bit_identical_to_reference(golden):
     from diffab_pytorch.diffusion import cosine_variance_schedule
 
