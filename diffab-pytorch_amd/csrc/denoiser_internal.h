@@ -232,7 +232,8 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
                                  const float* head_v = nullptr, const float* head_logits = nullptr,  // heads' epilogue done in the kernel  // t_dev: read the timestep from device memory (graph replay)
-                                 uint32_t keep = 0);  // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
+                                 uint32_t keep = 0,   // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
+                                 const uint32_t* allowed = nullptr);  // per-residue allowed-class words of the sequence draw (nullable)
 int launch_fill_beta(const diffab_sched* s, int t, int B, float* out, hipStream_t st, const int* t_dev = nullptr);
 int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hipStream_t st);  // [B][K / 16]: any generated residue in the tile
 // shared contexts: out[b] = src[ctx_of_row[b]] for the B rows of `row_floats` floats each (16-byte aligned rows)

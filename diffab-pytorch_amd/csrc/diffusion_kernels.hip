@@ -354,6 +354,32 @@ __device__ inline int categorical_draw(const float* __restrict__ p, int V, float
   return V - 1;
 }
 
+// categorical_draw restricted to the classes v < V whose bit is set in `allowed` (sequence constraints, diffab_sample_loop_aa): the same
+// running sums over the allowed classes only, in increasing v, so with every class allowed the float operations - and the draw - are
+// categorical_draw's.  Every allowed class at probability 0: the floor(u n)-th of the n allowed classes (unit weights in the same
+// loop).  No class allowed: -1, and the caller leaves the token as it is.
+__device__ inline int categorical_draw_allowed(const float* __restrict__ p, int V, float u, uint32_t allowed) {
+  float tot = 0.0f;
+  int n = 0;
+  for (int v = 0; v < V; ++v)
+    if ((allowed >> v) & 1u) {
+      tot += p[v];
+      ++n;
+    }
+  if (n == 0) return -1;
+  const bool flat = tot == 0.0f;
+  const float thr = u * (flat ? static_cast<float>(n) : tot);
+  float acc = 0.0f;
+  int last = 0;
+  for (int v = 0; v < V; ++v)
+    if ((allowed >> v) & 1u) {
+      acc += flat ? 1.0f : p[v];
+      if (acc > thr) return v;
+      last = v;
+    }
+  return last;
+}
+
 __global__ void categorical_sample_kernel(const float* __restrict__ prob, const float* __restrict__ u, int64_t n, int V,
                                           int64_t* __restrict__ out) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -724,12 +750,15 @@ __global__ void reverse_update_kernel(const float* __restrict__ beta, const floa
 // into O0_hat / post (read back by the same thread below; no __restrict__ on the two for that reason): one launch less per step.
 // keep (DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE, uniform per launch): the kept modality is never written and its share of the epilogue
 // and the draws is skipped; the other half runs exactly as with keep = 0.
+// allowed (nullable, one word per residue of the B K rows): s_{t-1} is drawn from the posterior restricted to the residue's allowed
+// classes (categorical_draw_allowed, same uniform); nullptr is the unconstrained draw.
 __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs,
                                              int t, const float* __restrict__ rev_sigmas, const float* __restrict__ rev_cdf, int n_bins,
                                              float thr, int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
                                              const float* __restrict__ eps_hat, float* O0_hat, float* post, const uint8_t* __restrict__ gm,
                                              uint64_t seed, int64_t first_patch, int B, int K, int V, const int* __restrict__ t_dev,
-                                             const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep) {
+                                             const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep,
+                                             const uint32_t* __restrict__ allowed) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   if (t_dev != nullptr) t = *t_dev;  // graph replay: the timestep lives in device memory (one captured step serves every t)
@@ -764,18 +793,31 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
   }
   if (upd_seq) {
     const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_SEQ);
-    seq[i] = categorical_draw(post + i * V, V, us.x);
+    const int s = allowed == nullptr ? categorical_draw(post + i * V, V, us.x) : categorical_draw_allowed(post + i * V, V, us.x, allowed[i]);
+    if (s >= 0) seq[i] = s;
   }
 }
 
+// allowed (nullable): s is uniform over the residue's allowed classes other than UNK (over {UNK} when that is the whole set) - the
+// unit-weight draw of categorical_draw_allowed, which is floor(u n) clamped to n - 1, as the unconstrained min(int(u 20), 19)
 __global__ void sample_init_kernel(int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O, const uint8_t* __restrict__ gm,
-                                   uint64_t seed, int64_t first_patch, int B, int K, int T, uint32_t keep) {
+                                   uint64_t seed, int64_t first_patch, int B, int K, int T, uint32_t keep,
+                                   const uint32_t* __restrict__ allowed) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K), st = static_cast<uint32_t>(T + 1);
   if (!(keep & DIFFAB_FLAG_KEEP_SEQUENCE)) {
     const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_INIT_S);
-    seq[i] = min(static_cast<int>(us.x * 20.0f), 19);
+    if (allowed == nullptr) {
+      seq[i] = min(static_cast<int>(us.x * 20.0f), 19);
+    } else {
+      constexpr uint32_t kUnk = 1u << (kV - 1), kAll = (1u << kV) - 1u;
+      const uint32_t a = allowed[i] & kAll;
+      float ones[kV];
+      for (int v = 0; v < kV; ++v) ones[v] = 1.0f;
+      const int s = categorical_draw_allowed(ones, kV, us.x, a == kUnk ? a : a & ~kUnk);
+      if (s >= 0) seq[i] = s;
+    }
   }
   if (keep & DIFFAB_FLAG_KEEP_STRUCTURE) return;
   const f32x4 nx = philox_normal4(seed, patch, res, st, STREAM_INIT_X);
@@ -792,11 +834,13 @@ __global__ void sample_init_kernel(int64_t* __restrict__ seq, float* __restrict_
 // Antibody optimisation: the native state of the generated residues forward-noised to step t, in place (diffusion.py:105-135 for the
 // sequence - seq_forward_prob_kernel mode 1 + categorical_draw -, coord_forward_kernel's x_t, orient_forward_kernel's O_t with the rotation
 // vector drawn as the reverse loop draws it, from row t of the forward table).  Philox streams STREAM_OPT_* + sw, counter step = t
-// (sw = 0 here; design scoring's draw m uses sw = m << 16).  eps (nullable): the translation noise of the residue.
+// (sw = 0 here; design scoring's draw m uses sw = m << 16).  eps (nullable): the translation noise of the residue.  allowed (nullable,
+// the residue's word): q(s_t | s_0) restricted to the allowed classes and renormalised (categorical_draw_allowed, same uniform).
 __device__ inline void forward_noise_residue(const float* __restrict__ alpha_bar, const float* __restrict__ abs_,
                                              const float* __restrict__ omabs, const float* __restrict__ fwd_sigmas,
                                              const float* __restrict__ fwd_cdf, int n_bins, float thr, int t, int64_t* seq, float* x, float* O,
-                                             float* eps_out, uint64_t seed, uint32_t patch, uint32_t res, uint32_t sw, uint32_t keep) {
+                                             float* eps_out, uint64_t seed, uint32_t patch, uint32_t res, uint32_t sw, uint32_t keep,
+                                             const uint32_t* allowed) {
   const uint32_t st = static_cast<uint32_t>(t);
   if (!(keep & DIFFAB_FLAG_KEEP_SEQUENCE)) {
     const float wk = alpha_bar[t], wn = 1.0f - wk;
@@ -804,7 +848,8 @@ __device__ inline void forward_noise_residue(const float* __restrict__ alpha_bar
     float p[kV];
     for (int v = 0; v < kV; ++v) p[v] = seq_prob(v, s0, wk, wn, true);
     const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_OPT_SEQ + sw);
-    *seq = categorical_draw(p, kV, us.x);
+    const int s = allowed == nullptr ? categorical_draw(p, kV, us.x) : categorical_draw_allowed(p, kV, us.x, *allowed);
+    if (s >= 0) *seq = s;
   }
   if (keep & DIFFAB_FLAG_KEEP_STRUCTURE) return;
   const float a = abs_[t], b = omabs[t];
@@ -834,12 +879,13 @@ __device__ inline void forward_noise_residue(const float* __restrict__ alpha_bar
 __global__ void sample_init_noised_kernel(const float* __restrict__ alpha_bar, const float* __restrict__ abs_, const float* __restrict__ omabs,
                                           const float* __restrict__ fwd_sigmas, const float* __restrict__ fwd_cdf, int n_bins, float thr, int t,
                                           int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
-                                          const uint8_t* __restrict__ gm, uint64_t seed, int64_t first_patch, int B, int K, uint32_t keep) {
+                                          const uint8_t* __restrict__ gm, uint64_t seed, int64_t first_patch, int B, int K, uint32_t keep,
+                                          const uint32_t* __restrict__ allowed) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K);
   forward_noise_residue(alpha_bar, abs_, omabs, fwd_sigmas, fwd_cdf, n_bins, thr, t, seq + i, x + i * 3, O + i * 9, nullptr, seed, patch, res,
-                        0u, keep);
+                        0u, keep, allowed == nullptr ? nullptr : allowed + i);
 }
 
 // ------------------------------------------------------------------ design scoring (diffab_score_designs)
@@ -879,7 +925,8 @@ __global__ void score_noise_kernel(const float* __restrict__ alpha_bar, const fl
   for (int a = 0; a < 9; ++a) O[a] = O0[src * 9 + a];
   if (gm[src])
     forward_noise_residue(alpha_bar, abs_, omabs, fwd_sigmas, fwd_cdf, n_bins, thr, t, &s, x, O, e, seed,
-                          static_cast<uint32_t>(first_design + w.r), static_cast<uint32_t>(k), static_cast<uint32_t>(w.m) << 16, c.keep);
+                          static_cast<uint32_t>(first_design + w.r), static_cast<uint32_t>(k), static_cast<uint32_t>(w.m) << 16, c.keep,
+                          nullptr);
   s_t[dst] = s;
 #pragma unroll
   for (int a = 0; a < 3; ++a) x_t[dst * 3 + a] = x[a];
@@ -994,11 +1041,11 @@ __global__ void dec_int_kernel(int* __restrict__ p) { *p -= 1; }
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
-                                 const float* head_logits, uint32_t keep) {
+                                 const float* head_logits, uint32_t keep, const uint32_t* allowed) {
   const int64_t n = static_cast<int64_t>(B) * K;
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
@@ -1416,21 +1463,34 @@ int diffab_sample_init(int64_t* seq, float* x, float* O, const uint8_t* gen_mask
 
 int diffab_sample_init_ex(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, void* stream) {
+  return diffab_sample_init_aa(seq, x, O, gen_mask, seed, first_patch, B, K, T, flags, nullptr, stream);
+}
+
+int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
+                          int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream) {
   StreamOrder order_(stream);
   DIFFAB_REQUIRE(seq && x && O && gen_mask && B >= 0 && K > 0 && T > 0, DIFFAB_ERR_ARG, "sample_init: bad argument");
   const uint32_t keep = flags & (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE);
   DIFFAB_REQUIRE(keep != (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE), DIFFAB_ERR_ARG,
                  "sample_init: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to sample");
+  DIFFAB_REQUIRE(!(allowed && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
+                 "sample_init: allowed classes constrain a sequence that DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
   const int64_t n = static_cast<int64_t>(B) * K;
   if (n == 0) return DIFFAB_OK;
   hipLaunchKernelGGL(sample_init_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), seq, x, O, gen_mask, seed, first_patch, B,
-                     K, T, keep);
+                     K, T, keep, allowed);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
 
 int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O, const uint8_t* gen_mask,
                               uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t, uint32_t flags, void* stream) {
+  return diffab_sample_init_noised_aa(s, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, nullptr, stream);
+}
+
+int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
+                                 const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t, uint32_t flags,
+                                 const uint32_t* allowed, void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_sched(s)) return rc;
   DIFFAB_REQUIRE(seq && x && O && gen_mask && B >= 0 && K > 0, DIFFAB_ERR_ARG, "sample_init_noised: bad argument");
@@ -1440,11 +1500,13 @@ int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab
   const uint32_t keep = flags & (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE);
   DIFFAB_REQUIRE(keep != (DIFFAB_FLAG_KEEP_STRUCTURE | DIFFAB_FLAG_KEEP_SEQUENCE), DIFFAB_ERR_ARG,
                  "sample_init_noised: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to noise");
+  DIFFAB_REQUIRE(!(allowed && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
+                 "sample_init_noised: allowed classes constrain a sequence that DIFFAB_FLAG_KEEP_SEQUENCE does not noise");
   const int64_t n = static_cast<int64_t>(B) * K;
   if (n == 0) return DIFFAB_OK;
   hipLaunchKernelGGL(sample_init_noised_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), s->alpha_bar, s->alpha_bar_sqrt,
                      s->one_minus_alpha_bar_sqrt, fwd_tab->sigmas, fwd_tab->cdf, fwd_tab->n_bins, fwd_tab->sigma_threshold, t, seq, x, O,
-                     gen_mask, seed, first_patch, B, K, keep);
+                     gen_mask, seed, first_patch, B, K, keep, allowed);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

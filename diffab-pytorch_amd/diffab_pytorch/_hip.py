@@ -179,6 +179,11 @@ SYMBOLS = {
     "diffab_sample_init_ex": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
     # (sched, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, stream)
     "diffab_sample_init_noised": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
+    # sequence constraints: the three entries above plus `allowed` (device uint32[B*K], nullable) before the stream
+    "diffab_sample_loop_aa": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                        _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, _fp]),
+    "diffab_sample_init_aa": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
+    "diffab_sample_init_noised_aa": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
     "diffab_score_workspace_bytes": (_sz, [_PD, _i32]),
     # (d, w, sched, fwd_tab, seq, x, O, gen_mask, res_mask, n_designs, res_ctx, pair_ctx, n_ctx, ctx_of_design (host int32[n_designs]),
     #  t_list (host int32[n_t]), n_t, n_draws, seed, first_design, out_terms, out_residue, noised, ws, ws_bytes, flags, stream)

@@ -81,6 +81,38 @@ def _context_map(who: str, context_index, n_rows: int, res_context_emb, pair_con
     return ci.to(torch.int32)
 
 
+def _allowed_aa_host(who: str, allowed_aa, generation_mask, n_rows: int, K: int, V: int, keep: int) -> torch.Tensor:
+    """Host bool (n_rows, K, V) of sample()'s `allowed_aa` broadcast to the state rows, after every check made before device work."""
+    if keep & _hip.FLAG_KEEP_SEQUENCE:
+        raise ValueError(f"{who}: allowed_aa constrains the sequence, which mode='structure' does not diffuse")
+    a = torch.as_tensor(allowed_aa)
+    if a.dtype != torch.bool:
+        raise ValueError(f"{who}: allowed_aa must be a bool tensor (True = class allowed), got {a.dtype}")
+    if V > 32:
+        raise ValueError(f"{who}: allowed_aa is one 32-bit word per residue on the device; the model's vocabulary V = {V} > 32")
+    if a.dim() not in (1, 2, 3) or a.shape[-1] != V:
+        raise ValueError(f"{who}: allowed_aa must be (V,), (K, V) or (rows, K, V) with V = {V}, got {tuple(a.shape)}")
+    try:
+        a = a.detach().cpu().expand(n_rows, K, V)
+    except RuntimeError:
+        raise ValueError(f"{who}: allowed_aa {tuple(a.shape)} does not broadcast to the state rows ({n_rows}, {K}, {V})") from None
+    gm = torch.as_tensor(generation_mask).detach().cpu().bool()
+    if tuple(gm.shape) != (n_rows, K):
+        raise ValueError(f"{who}: generation_mask is {tuple(gm.shape)}, seq_idx is {(n_rows, K)}")
+    empty = (gm & ~a.any(-1)).nonzero()
+    if len(empty):
+        b, k = (int(v) for v in empty[0])
+        raise ValueError(f"{who}: allowed_aa allows no class at {len(empty)} generated residue(s), the first is row {b}, residue {k}")
+    return a
+
+
+def _pack_allowed_aa(allowed: torch.Tensor) -> torch.Tensor:
+    """(..., V) bool on the device -> (...) int32 words, bit v = class v allowed (the layout of diffab_sample_loop_aa)."""
+    bits = torch.ones((), dtype=torch.int64, device=allowed.device) << torch.arange(allowed.shape[-1], device=allowed.device)
+    words = (allowed.to(torch.int64) * bits).sum(-1)
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32).contiguous()
+
+
 def _check_encode_fields(who: str, xyz, atom_mask, chain_idx) -> None:
     need = {"atom_mask": atom_mask, "chain_idx": chain_idx}
     missing = [k for k, v in need.items() if v is None]
@@ -916,7 +948,7 @@ class DiffAb(_ModuleBase):
                t_stop: int = 0, init: bool = True, flags: int = 0, graph: Optional[bool] = None,
                skip_unused_rows: bool = False, num_samples: int = 1,
                context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
-               optimize_from: Optional[int] = None) -> Dict[str, torch.Tensor]:
+               optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -959,7 +991,18 @@ class DiffAb(_ModuleBase):
         step t on the device (`diffab_sample_init_noised`, Philox keyed like the loop, so sharding and num_samples behave as above)
         instead of re-initialised, and the loop runs t .. t_stop+1 (a few steps instead of T).  The kept modality of a mode is not
         noised.  An unknown mode, a mode with generate_structure / generate_sequence False, optimize_from outside [1, T], optimize_from
-        with init=False and a t_start other than optimize_from raise ValueError before any device work."""
+        with init=False and a t_start other than optimize_from raise ValueError before any device work.
+
+        Sequence constraints: ``allowed_aa`` is a bool tensor (V,), (K, V) or (rows, K, V) - True where class v (io.AA3 order, UNK last)
+        may appear - broadcast to the input rows (io.allowed_aa_mask builds one from one-letter codes).  Every sequence draw of a
+        generated residue is restricted to its allowed classes on the device (`diffab_sample_loop_aa` and the `_aa` init entries): the
+        reverse step draws from the posterior renormalised over them, the initial state uniformly over them (UNK only when it is the
+        only one), optimize_from's start from q(s_t | s_0) renormalised over them.  The Philox lanes are the unconstrained ones, so an
+        all-True mask is bitwise the unconstrained run and sharding / num_samples / context_index behave as above; with num_samples the
+        rows are per patch and replicated like generation_mask, with context_index they are per state row.  Combines with
+        "codesign" / "fixed_backbone" (constrained inverse folding), optimize_from, graph and the launch flags.  A dtype other than bool,
+        a shape that does not broadcast, a last dimension other than the model's V (or V > 32), a generated residue with no allowed
+        class and mode="structure" (the sequence is not diffused) raise ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
         generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
@@ -994,6 +1037,8 @@ class DiffAb(_ModuleBase):
                     raise ValueError(f"sample(): with num_samples the contexts are per patch: {name} has {v.shape[0]} rows, "
                                      f"seq_idx has {n_rows}")
             ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
+        if allowed_aa is not None:
+            _allowed_aa_host("sample()", allowed_aa, generation_mask, n_rows, K_, self.denoiser.dims["V"], keep)
         if res_context_emb is None or pair_context_emb is None:
             _check_encode_fields("sample()", xyz, atom_mask, chain_idx)
             res_context_emb, pair_context_emb = self._contexts_from_batch(seq_idx, xyz, orientations, generation_mask, residue_mask,
@@ -1005,8 +1050,13 @@ class DiffAb(_ModuleBase):
         x = _hip.dev_f32(xyz[:, :, CA_IDX] if xyz.dim() == 4 else xyz)
         O = _hip.dev_f32(orientations)
         rc, pc, gm = _hip.dev_f32(res_context_emb), _hip.dev_f32(pair_context_emb), _hip.dev_mask(generation_mask)
+        allowed = None  # int32 (rows, K) words of the allowed classes (always passed when allowed_aa is given, an all-True mask too)
+        if allowed_aa is not None:
+            allowed = _pack_allowed_aa(torch.as_tensor(allowed_aa).detach().to(seq.device).expand(n_rows, K_, self.denoiser.dims["V"]))
         if num_samples > 1:  # the state of every design: the patch's rows, replicated on the device (the contexts are not)
             seq, x, O, gm = (v.repeat_interleave(num_samples, dim=0) for v in (seq, x, O, gm))
+            if allowed is not None:
+                allowed = allowed.repeat_interleave(num_samples, dim=0)
         else:
             seq, x, O = seq.clone(), x.clone(), O.clone()
         B, K = seq.shape
@@ -1029,16 +1079,27 @@ class DiffAb(_ModuleBase):
         flags |= keep
         if init and optimize_from is not None:
             fwd_tab = self.orientation_diffuser.so3.struct()
-            _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd_tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm),
-                                                     seed, first_patch, B, K, optimize_from, keep, _hip.stream_ptr()),
-                       "diffab_sample_init_noised")
+            args = (C.byref(sd.struct), C.byref(fwd_tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K,
+                    optimize_from, keep)
+            if allowed is None:
+                _hip.check(lib.diffab_sample_init_noised(*args, _hip.stream_ptr()), "diffab_sample_init_noised")
+            else:
+                _hip.check(lib.diffab_sample_init_noised_aa(*args, _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_init_noised_aa")
+        elif init and allowed is not None:
+            _hip.check(lib.diffab_sample_init_aa(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T, keep,
+                                                 _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_init_aa")
         elif init and keep:
             _hip.check(lib.diffab_sample_init_ex(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T, keep,
                                                  _hip.stream_ptr()), "diffab_sample_init_ex")
         elif init:
             _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T,
                                               _hip.stream_ptr()), "diffab_sample_init")
-        if ctx_map is None:
+        if allowed is not None:
+            _hip.check(lib.diffab_sample_loop_aa(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                                 _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
+                                                 None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,
+                                                 _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_loop_aa")
+        elif ctx_map is None:
             _hip.check(lib.diffab_sample_loop(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
                                               _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), _hip.ptr(gm), seed, first_patch, t_start, t_stop,
                                               _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()), "diffab_sample_loop")

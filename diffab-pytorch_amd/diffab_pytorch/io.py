@@ -27,6 +27,35 @@ IDEAL_BACKBONE = {
 BACKBONE_ATOMS = ("N", "CA", "C", "O", "CB")
 AA3 = ("ALA", "ARG", "ASN", "ASP", "CYS", "GLN", "GLU", "GLY", "HIS", "ILE", "LEU", "LYS", "MET", "PHE", "PRO", "SER", "THR", "TRP",
        "TYR", "VAL", "UNK")  # index order of the 20 + UNK vocabulary (reference AA.UNK = 20)
+AA1 = "ARNDCQEGHILKMFPSTWYVX"  # one-letter codes in AA3 order, X = UNK
+
+
+def _aa_indices(letters: str, V: int, what: str) -> list:
+    out = []
+    for c in str(letters).upper():
+        i = AA1.find(c)
+        if i < 0 or i >= V:
+            raise ValueError(f"allowed_aa_mask: unknown amino-acid letter {c!r} in {what} (expected letters of {AA1[:V]!r})")
+        out.append(i)
+    return out
+
+
+def allowed_aa_mask(K: int, *, exclude: str = "", fixed: Optional[Dict[int, str]] = None, V: int = 21) -> torch.Tensor:
+    """(K, V) bool mask for ``DiffAb.sample(allowed_aa=...)`` from one-letter codes (``AA1``: ARNDCQEGHILKMFPSTWYV in AA3 order, X for
+    UNK).  Every class is allowed except the letters of ``exclude`` (e.g. "CMX": no Cys, Met or UNK); ``fixed`` maps a residue position
+    to a letter or a string of letters, and that position allows exactly those classes (the exclusion list does not apply to it).
+    Unknown letters, positions outside [0, K) and an empty set at a fixed position raise ValueError."""
+    mask = torch.ones(K, V, dtype=torch.bool)
+    mask[:, _aa_indices(exclude, V, "exclude")] = False
+    for pos, letters in (fixed or {}).items():
+        if isinstance(pos, bool) or not isinstance(pos, int) or not 0 <= pos < K:
+            raise ValueError(f"allowed_aa_mask: fixed position {pos!r} outside [0, {K})")
+        idx = _aa_indices(letters, V, f"fixed[{pos}]")
+        if not idx:
+            raise ValueError(f"allowed_aa_mask: fixed[{pos}] allows no class")
+        mask[pos] = False
+        mask[pos, idx] = True
+    return mask
 
 
 def backbone_from_frames(translations: torch.Tensor, orientations: torch.Tensor, atoms: Sequence[str] = BACKBONE_ATOMS) -> torch.Tensor:

@@ -523,6 +523,33 @@ int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab
                               const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t,
                               uint32_t flags, void* stream);
 
+/* ---- sequence constraints (build-defined): per-residue allowed amino-acid classes -------------------------------------------------
+ * `allowed` is a caller-owned DEVICE buffer of B*K uint32 words, one per (state row, residue) in the layout of gen_mask; bit v of a
+ * word allows class v (io.AA3 order: the 20 amino acids, then UNK = 20).  Bits at and above the vocabulary size are ignored.  Only
+ * GENERATED residues read their word, and only where the sequence is diffused; context residues are never written.  Every draw uses
+ * the Philox lane of the unconstrained entry, so noise keys, sharding and replicated rows behave exactly as there.  With A the
+ * residue's allowed set:
+ *   reverse step (STREAM_SEQ): tot = sum of p_v over v in A in increasing v, thr = u tot; the first v in A whose running sum exceeds
+ *     thr, else the largest v in A; tot == 0: the floor(u |A|)-th element of A.  On both posterior paths (the folded heads' softmax
+ *     in the update kernel, and the heads kernel's posterior).  A = all V classes: bitwise the unconstrained draw;
+ *   initial state (STREAM_INIT_S): uniform over A \ {UNK} (over A when A = {UNK}): its floor(u n)-th element, clamped to n - 1.
+ *     All classes: bitwise the unconstrained min(int(u 20), 19);
+ *   optimisation start (STREAM_OPT_SEQ): q(s_t | s_0) restricted to A and renormalised, drawn by the reverse-step rule (a native
+ *     token outside A is not reachable).
+ * Structure draws (x, O) and the denoiser are untouched.  A generated residue with an empty A is the caller's error (DiffAb.sample
+ * rejects it): its token is then left as it is.  allowed == NULL: exactly the entry without the suffix (which is this call with NULL).
+ * A non-NULL allowed with DIFFAB_FLAG_KEEP_SEQUENCE, or (loop) with d->V > 32: DIFFAB_ERR_ARG, nothing enqueued. */
+int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                          int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                          const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                          int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                          void* stream);
+int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
+                          int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
+int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
+                                 const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t,
+                                 uint32_t flags, const uint32_t* allowed, void* stream);
+
 /* ---- design scoring (build-defined evaluator; reference objective diffab_pytorch.py:808-887) ----------------------------------------
  * Per-design diffusion losses over a timestep grid: the reference's training objective (_shared_step, :808-880, summed as `loss` at
  * :882-887) evaluated per design instead of as one batch mean at one random t per row.  Evaluated row q = ((r n_t) + j) n_draws + m is
