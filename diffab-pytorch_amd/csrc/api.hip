@@ -777,6 +777,15 @@ int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w
                           int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx, const int32_t* ctx_of_row,
                           const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace,
                           size_t workspace_bytes, uint32_t flags, const uint32_t* allowed, void* stream) {
+  return diffab_sample_loop_rec(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start, t_stop,
+                                workspace, workspace_bytes, flags, allowed, nullptr, stream);
+}
+
+int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                           int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                           const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                           int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                           const diffab_sample_record* rec, void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
@@ -795,6 +804,31 @@ int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w
   DIFFAB_REQUIRE(!(allowed && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
                  "sample_loop: allowed classes constrain a sequence that DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
   DIFFAB_REQUIRE(!allowed || d->V <= 32, DIFFAB_ERR_ARG, "sample_loop: allowed classes are one 32-bit word per residue; V = %d > 32", d->V);
+  // trajectory recording: every slot is written by exactly one step of this call, so the record holds no stale entry
+  SampleRecordDev rdev;
+  if (rec != nullptr) {
+    DIFFAB_REQUIRE(rec->n_slots >= 1, DIFFAB_ERR_ARG, "sample_loop: record n_slots = %d < 1", rec->n_slots);
+    DIFFAB_REQUIRE(rec->slot_of_step && rec->slot_dev && rec->seq && rec->x && rec->O, DIFFAB_ERR_ARG,
+                   "sample_loop: record needs slot_of_step, slot_dev, seq, x and O");
+    const int n_pred = (rec->pred_x != nullptr) + (rec->pred_O != nullptr) + (rec->seq_probs != nullptr);
+    DIFFAB_REQUIRE(n_pred == 0 || n_pred == 3, DIFFAB_ERR_ARG, "sample_loop: record predictions are pred_x, pred_O and seq_probs, all or none");
+    DIFFAB_REQUIRE(n_pred == 0 || s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: record predictions need the schedule's alpha_bar_sqrt");
+    std::vector<int> used(rec->n_slots, 0);
+    for (int t = 0; t <= s->T; ++t) {
+      const int j = rec->slot_of_step[t];
+      if (j == -1) continue;
+      DIFFAB_REQUIRE(j >= 0 && j < rec->n_slots, DIFFAB_ERR_ARG, "sample_loop: record slot_of_step[%d] = %d outside -1, [0, %d)", t, j,
+                     rec->n_slots);
+      DIFFAB_REQUIRE(t > t_stop && t <= t_start, DIFFAB_ERR_ARG,
+                     "sample_loop: record slot_of_step[%d] = %d, but the call runs steps [%d, %d] only (the slot would never be written)", t, j,
+                     t_stop + 1, t_start);
+      DIFFAB_REQUIRE(used[j]++ == 0, DIFFAB_ERR_ARG, "sample_loop: record slot %d is given to two steps", j);
+    }
+    for (int j = 0; j < rec->n_slots; ++j)
+      DIFFAB_REQUIRE(used[j] == 1, DIFFAB_ERR_ARG, "sample_loop: record slot %d is given to no step", j);
+    rdev = SampleRecordDev{rec->slot_dev, rec->n_slots, rec->seq, rec->x, rec->O, rec->pred_x, rec->pred_O, rec->seq_probs,
+                           n_pred ? s->alpha_bar_sqrt : nullptr};
+  }
   // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
   // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
   const bool mapped = ctx_of_row != nullptr;
@@ -828,6 +862,10 @@ int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w
   if (int rc = prepare_forward(d, w, plan, b0, pair_ctx, bias, st)) return rc;
   if (plan.last_layer_tiles)
     if (int rc = launch_tiles_needed(gen_mask, d->B, d->K, sb.tiles, st)) return rc;
+  if (rec != nullptr) {  // the step -> slot table, and the residues the loop never writes, once per call
+    DIFFAB_HIP_CHECK(hipMemcpyAsync(rec->slot_dev, rec->slot_of_step, sizeof(int32_t) * (s->T + 1), hipMemcpyHostToDevice, st));
+    if (int rc = launch_record_fixed(rdev, seq, x, O, gen_mask, d->B, d->K, d->V, st)) return rc;
+  }
   auto one_step = [&](int t, const int* t_dev) -> int {
     if (!plan.fold)  // (the folded head tables read the schedule themselves: one launch less per step)
       if (int rc = launch_fill_beta(s, t, d->B, sb.beta, st, t_dev)) return rc;
@@ -837,7 +875,7 @@ int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w
     if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits, keep, allowed);
+                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is

@@ -228,12 +228,31 @@ int launch_losses_fwd(const float* pp, const float* tp, const float* pe, const f
                       float* scratch = nullptr);  // scratch: 1024 floats -> the multi-work-group two-stage reduction
 
 // diffusion_kernels.hip
+// Trajectory recording (diffab_sample_loop_rec), a by-value launch argument of the update kernel: constant for a whole call, so the
+// captured step of graph replay carries it unchanged.  slot == nullptr: nothing is recorded (one uniform branch).  Entry (b, j, k) of
+// every field is (b n_slots + j) K + k; pred_x == nullptr: the state alone.
+struct SampleRecordDev {
+  const int32_t* slot = nullptr;  // device [T + 1]: step t -> slot, -1 = not recorded
+  int32_t n_slots = 0;
+  int64_t* seq = nullptr;
+  float* x = nullptr;
+  float* O = nullptr;
+  float* pred_x = nullptr;
+  float* pred_O = nullptr;
+  float* seq_probs = nullptr;
+  const float* alpha_bar_sqrt = nullptr;  // the schedule's, for x0_hat (read with predictions only)
+};
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
                                  const float* head_v = nullptr, const float* head_logits = nullptr,  // heads' epilogue done in the kernel  // t_dev: read the timestep from device memory (graph replay)
                                  uint32_t keep = 0,   // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
-                                 const uint32_t* allowed = nullptr);  // per-residue allowed-class words of the sequence draw (nullable)
+                                 const uint32_t* allowed = nullptr,  // per-residue allowed-class words of the sequence draw (nullable)
+                                 const SampleRecordDev& rec = SampleRecordDev{});  // trajectory recording (rec.slot nullable)
+// the residues that are not generated: their (constant) state in every slot of the record, and their predictions - the given x / O and a
+// one-hot of the token - once per call
+int launch_record_fixed(const SampleRecordDev& rec, const int64_t* seq, const float* x, const float* O, const uint8_t* gm, int B, int K, int V,
+                        hipStream_t st);
 int launch_fill_beta(const diffab_sched* s, int t, int B, float* out, hipStream_t st, const int* t_dev = nullptr);
 int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hipStream_t st);  // [B][K / 16]: any generated residue in the tile
 // shared contexts: out[b] = src[ctx_of_row[b]] for the B rows of `row_floats` floats each (16-byte aligned rows)

@@ -744,6 +744,58 @@ __global__ void reverse_update_kernel(const float* __restrict__ beta, const floa
                      rotvec[i * 3], rotvec[i * 3 + 1], rotvec[i * 3 + 2], u_seq[i]);
 }
 
+// Trajectory recording, one generated residue i = b K + k at slot j of step t: the state (s_t, x_t, O_t) as read before the update, and
+// with rec.pred_x the predictions on it - x0_hat = (x_t - sqrt(1 - alpha_bar_t) eps_hat) / sqrt(alpha_bar_t), O0_hat and the posterior
+// softmax (the unrestricted one; a constrained draw renormalises it) as the epilogue left them in O0_hat / post.  A kept modality
+// writes its given values instead (x_t and O_t; a one-hot of s_t): its share of the epilogue did not run.
+__device__ inline void record_residue(const SampleRecordDev& rec, int j, int64_t i, int K, int V, int t, float omabs, const int64_t* seq,
+                                      const float* x, const float* O, const float* eps_hat, const float* O0_hat, const float* post,
+                                      bool upd_struct, bool upd_seq) {
+  const int64_t o = (i / K * rec.n_slots + j) * K + i % K;
+  const int64_t s = seq[i];
+  rec.seq[o] = s;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) rec.x[o * 3 + c] = x[i * 3 + c];
+#pragma unroll
+  for (int c = 0; c < 9; ++c) rec.O[o * 9 + c] = O[i * 9 + c];
+  if (rec.pred_x == nullptr) return;
+  if (upd_struct) {
+    const float a = rec.alpha_bar_sqrt[t];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rec.pred_x[o * 3 + c] = (x[i * 3 + c] - omabs * eps_hat[i * 3 + c]) / a;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) rec.pred_O[o * 9 + c] = O0_hat[i * 9 + c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rec.pred_x[o * 3 + c] = x[i * 3 + c];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) rec.pred_O[o * 9 + c] = O[i * 9 + c];
+  }
+  for (int c = 0; c < V; ++c) rec.seq_probs[o * V + c] = upd_seq ? post[i * V + c] : (c == s ? 1.0f : 0.0f);
+}
+
+// The residues that are not generated, every slot: their state never changes in the loop, and their predictions are that state (x, O,
+// one-hot s), so every prediction frame is a complete structure.  One thread per record entry (b, j, k), neighbouring k in neighbouring lanes.
+__global__ void record_fixed_kernel(SampleRecordDev rec, const int64_t* __restrict__ seq, const float* __restrict__ x,
+                                    const float* __restrict__ O, const uint8_t* __restrict__ gm, int B, int K, int V) {
+  const int64_t o = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+  if (o >= static_cast<int64_t>(B) * rec.n_slots * K) return;
+  const int64_t i = o / (static_cast<int64_t>(rec.n_slots) * K) * K + o % K;
+  if (gm[i]) return;
+  const int64_t s = seq[i];
+  rec.seq[o] = s;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) rec.x[o * 3 + c] = x[i * 3 + c];
+#pragma unroll
+  for (int c = 0; c < 9; ++c) rec.O[o * 9 + c] = O[i * 9 + c];
+  if (rec.pred_x == nullptr) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) rec.pred_x[o * 3 + c] = x[i * 3 + c];
+#pragma unroll
+  for (int c = 0; c < 9; ++c) rec.pred_O[o * 9 + c] = O[i * 9 + c];
+  for (int c = 0; c < V; ++c) rec.seq_probs[o * V + c] = c == s ? 1.0f : 0.0f;
+}
+
 // Same update with the noise drawn in-kernel from Philox (the production sampler).
 // head_v / head_logits != nullptr (the folded sampler path): the heads' epilogue of the row - O0 = O_t exp(hat(v)) (diffab_pytorch.py:594-596)
 // and posterior = softmax(logits) (:555), what heads_finish_kernel computes for every row - is done here, for the generated rows only,
@@ -752,13 +804,15 @@ __global__ void reverse_update_kernel(const float* __restrict__ beta, const floa
 // and the draws is skipped; the other half runs exactly as with keep = 0.
 // allowed (nullable, one word per residue of the B K rows): s_{t-1} is drawn from the posterior restricted to the residue's allowed
 // classes (categorical_draw_allowed, same uniform); nullptr is the unconstrained draw.
+// rec (trajectory recording; rec.slot == nullptr: off): when step t has a slot, the residue writes the state it is about to update and,
+// with predictions, what the epilogue made of it (record_residue), before any draw - the update itself is untouched.
 __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs,
                                              int t, const float* __restrict__ rev_sigmas, const float* __restrict__ rev_cdf, int n_bins,
                                              float thr, int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
                                              const float* __restrict__ eps_hat, float* O0_hat, float* post, const uint8_t* __restrict__ gm,
                                              uint64_t seed, int64_t first_patch, int B, int K, int V, const int* __restrict__ t_dev,
                                              const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep,
-                                             const uint32_t* __restrict__ allowed) {
+                                             const uint32_t* __restrict__ allowed, SampleRecordDev rec) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   if (t_dev != nullptr) t = *t_dev;  // graph replay: the timestep lives in device memory (one captured step serves every t)
@@ -779,6 +833,10 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
     for (int c = 0; c < V; ++c) s += expf(head_logits[i * V + c] - m);
     const float inv = 1.0f / s;
     for (int c = 0; c < V; ++c) post[i * V + c] = expf(head_logits[i * V + c] - m) * inv;
+  }
+  if (rec.slot != nullptr) {
+    const int j = rec.slot[t];
+    if (j >= 0) record_residue(rec, j, i, K, V, t, omabs[t], seq, x, O, eps_hat, O0_hat, post, upd_struct, upd_seq);
   }
   const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K), st = static_cast<uint32_t>(t);
   if (upd_struct) {
@@ -1041,11 +1099,20 @@ __global__ void dec_int_kernel(int* __restrict__ p) { *p -= 1; }
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
-                                 const float* head_logits, uint32_t keep, const uint32_t* allowed) {
+                                 const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec) {
   const int64_t n = static_cast<int64_t>(B) * K;
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+
+int launch_record_fixed(const SampleRecordDev& rec, const int64_t* seq, const float* x, const float* O, const uint8_t* gm, int B, int K, int V,
+                        hipStream_t st) {
+  const int64_t n = static_cast<int64_t>(B) * rec.n_slots * K;
+  if (n == 0) return DIFFAB_OK;
+  hipLaunchKernelGGL(record_fixed_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, rec, seq, x, O, gm, B, K, V);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

@@ -86,6 +86,11 @@ class ScoreNoised(C.Structure):  # diffab_score_noised: optional copies of the n
     _fields_ = [(n, _fp) for n in ("seq_t", "x_t", "O_t", "eps")]
 
 
+class SampleRecord(C.Structure):  # diffab_sample_record: the recorded reverse trajectory of diffab_sample_loop_rec
+    _fields_ = [("n_slots", C.c_int32), ("slot_of_step", C.POINTER(C.c_int32)), ("slot_dev", _fp)] + \
+        [(n, _fp) for n in ("seq", "x", "O", "pred_x", "pred_O", "seq_probs")]
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -184,6 +189,9 @@ SYMBOLS = {
                                         _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, _fp]),
     "diffab_sample_init_aa": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
     "diffab_sample_init_noised_aa": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
+    # trajectory recording: diffab_sample_loop_aa plus `rec` (nullable) before the stream
+    "diffab_sample_loop_rec": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                         _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), _fp]),
     "diffab_score_workspace_bytes": (_sz, [_PD, _i32]),
     # (d, w, sched, fwd_tab, seq, x, O, gen_mask, res_mask, n_designs, res_ctx, pair_ctx, n_ctx, ctx_of_design (host int32[n_designs]),
     #  t_list (host int32[n_t]), n_t, n_draws, seed, first_design, out_terms, out_residue, noised, ws, ws_bytes, flags, stream)

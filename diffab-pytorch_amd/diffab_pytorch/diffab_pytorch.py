@@ -106,6 +106,39 @@ def _allowed_aa_host(who: str, allowed_aa, generation_mask, n_rows: int, K: int,
     return a
 
 
+def _trajectory_labels(who: str, trajectory, predictions, t_start: int, t_stop: int, T: int) -> Optional[torch.Tensor]:
+    """Host int64 (n,) of sample()'s recorded steps, descending, from `trajectory` (None / False: nothing recorded), after every check
+    made before device work."""
+    if trajectory is None or trajectory is False:
+        if predictions:
+            raise ValueError(f"{who}: trajectory_predictions records predictions along a trajectory; give trajectory as well")
+        return None
+    if not T >= t_start >= t_stop >= 0:
+        raise ValueError(f"{who}: a trajectory needs T = {T} >= t_start = {t_start} >= t_stop = {t_stop} >= 0")
+    if trajectory is True:
+        labels = torch.arange(t_start, t_stop, -1, dtype=torch.int64)
+    elif isinstance(trajectory, int):
+        if trajectory < 1:
+            raise ValueError(f"{who}: a trajectory stride must be an int >= 1, got {trajectory}")
+        labels = torch.arange(t_start, t_stop, -trajectory, dtype=torch.int64)
+    elif isinstance(trajectory, float):
+        raise ValueError(f"{who}: trajectory must be True, a stride (int >= 1) or a 1-D list of steps, got the float {trajectory!r}")
+    else:
+        lt = torch.as_tensor(trajectory)
+        if lt.dim() != 1 or lt.numel() == 0 or lt.dtype == torch.bool or lt.is_floating_point() or lt.is_complex():
+            raise ValueError(f"{who}: a trajectory list must be a non-empty 1-D integer list of steps, got shape {tuple(lt.shape)} {lt.dtype}")
+        lt = lt.detach().to("cpu", torch.int64)
+        bad = lt[(lt <= t_stop) | (lt > t_start)]
+        if bad.numel():
+            raise ValueError(f"{who}: trajectory step {int(bad[0])} outside [t_stop + 1, t_start] = [{t_stop + 1}, {t_start}]")
+        if lt.unique().numel() != lt.numel():
+            raise ValueError(f"{who}: trajectory lists a step more than once")
+        labels = lt.sort(descending=True).values
+    if labels.numel() == 0:
+        raise ValueError(f"{who}: the trajectory records no step (t_start = {t_start}, t_stop = {t_stop})")
+    return labels
+
+
 def _pack_allowed_aa(allowed: torch.Tensor) -> torch.Tensor:
     """(..., V) bool on the device -> (...) int32 words, bit v = class v allowed (the layout of diffab_sample_loop_aa)."""
     bits = torch.ones((), dtype=torch.int64, device=allowed.device) << torch.arange(allowed.shape[-1], device=allowed.device)
@@ -948,7 +981,8 @@ class DiffAb(_ModuleBase):
                t_stop: int = 0, init: bool = True, flags: int = 0, graph: Optional[bool] = None,
                skip_unused_rows: bool = False, num_samples: int = 1,
                context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
-               optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+               optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None, trajectory=None,
+               trajectory_predictions: bool = False) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -1002,7 +1036,25 @@ class DiffAb(_ModuleBase):
         rows are per patch and replicated like generation_mask, with context_index they are per state row.  Combines with
         "codesign" / "fixed_backbone" (constrained inverse folding), optimize_from, graph and the launch flags.  A dtype other than bool,
         a shape that does not broadcast, a last dimension other than the model's V (or V > 32), a generated residue with no allowed
-        class and mode="structure" (the sequence is not diffused) raise ValueError before any device work."""
+        class and mode="structure" (the sequence is not diffused) raise ValueError before any device work.
+
+        Trajectory: ``trajectory=True`` records every step, an int k >= 1 the steps t_start, t_start - k, ... down to t_stop + 1, a 1-D
+        int list / tensor the distinct steps it names in [t_stop + 1, t_start]; the result gains ``"trajectory"``, a dict on the input's
+        device.  Labels are steps: ``t`` (n,) int64 in descending order, and slot j of every field holds label t[j]:
+        ``seq_idx`` (rows, n, K), ``translations`` (rows, n, K, 3), ``orientations`` (rows, n, K, 3, 3) - the state that step t denoises,
+        bitwise the result of this call with t_stop = t (same seed, first_patch, mode, optimize_from, allowed_aa, num_samples /
+        context_index, flags and graph); label t_start is the initial state.  The final state is the ordinary return value and is not
+        repeated.  ``trajectory_predictions=True`` adds what the denoiser made of that state: ``pred_translations`` x0_hat = (x_t -
+        sqrt(1 - alpha_bar_t) eps_hat) / sqrt(alpha_bar_t), ``pred_orientations`` O0_hat, and ``seq_probs`` (rows, n, K, V), the
+        softmax posterior over s_{t-1} - unrestricted: under allowed_aa the draw renormalises it over the allowed set; label 1 is the
+        distribution the returned token was drawn from.  Residues that are not generated hold their given state in every slot, and
+        their predictions are their x / O and a one-hot of their token; a kept modality of a mode appears in the predictions as its
+        given values.  Rows are outermost (row b*N + r under num_samples), so a shard's rows are that slice of the whole call's
+        trajectory.  The update kernel writes the record on the device (`diffab_sample_loop_rec`); the returned state is bitwise the
+        same with and without a trajectory, on every launch form.  Memory: 56 B of state plus 132 B of predictions (V = 21) per
+        recorded residue and label - every step of a 100-step run at 256 x 128 is about 590 MiB.  A bool / float / 2-D / empty
+        trajectory, a stride < 1, a step outside the range or named twice, and trajectory_predictions without trajectory raise
+        ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
         generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
@@ -1039,6 +1091,8 @@ class DiffAb(_ModuleBase):
             ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
         if allowed_aa is not None:
             _allowed_aa_host("sample()", allowed_aa, generation_mask, n_rows, K_, self.denoiser.dims["V"], keep)
+        labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, self.T if t_start is None else int(t_start), int(t_stop),
+                                    self.T)
         if res_context_emb is None or pair_context_emb is None:
             _check_encode_fields("sample()", xyz, atom_mask, chain_idx)
             res_context_emb, pair_context_emb = self._contexts_from_batch(seq_idx, xyz, orientations, generation_mask, residue_mask,
@@ -1094,6 +1148,30 @@ class DiffAb(_ModuleBase):
         elif init:
             _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T,
                                               _hip.stream_ptr()), "diffab_sample_init")
+        if labels is not None:
+            V = self.denoiser.dims["V"]
+            n = labels.numel()
+            slot_of_step = [-1] * (self.T + 1)
+            for j, t in enumerate(labels.tolist()):
+                slot_of_step[t] = j
+            slot_dev = torch.empty(self.T + 1, dtype=torch.int32, device=seq.device)
+            traj = {"seq_idx": torch.empty(B, n, K, dtype=torch.int64, device=seq.device),
+                    "translations": torch.empty(B, n, K, 3, device=seq.device), "orientations": torch.empty(B, n, K, 3, 3, device=seq.device)}
+            if trajectory_predictions:
+                traj.update(pred_translations=torch.empty(B, n, K, 3, device=seq.device),
+                            pred_orientations=torch.empty(B, n, K, 3, 3, device=seq.device),
+                            seq_probs=torch.empty(B, n, K, V, device=seq.device))
+            rec = _hip.SampleRecord(n, (C.c_int32 * (self.T + 1))(*slot_of_step), _hip.ptr(slot_dev),
+                                    *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
+                                                                      "pred_orientations", "seq_probs")))
+            _hip.check(lib.diffab_sample_loop_rec(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
+                                                  _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
+                                                  None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,
+                                                  _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), C.byref(rec), _hip.stream_ptr()),
+                       "diffab_sample_loop_rec")
+            out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
+            out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}
+            return out
         if allowed is not None:
             _hip.check(lib.diffab_sample_loop_aa(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
                                                  _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,

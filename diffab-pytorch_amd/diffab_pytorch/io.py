@@ -89,10 +89,8 @@ def frames_from_backbone(n: torch.Tensor, ca: torch.Tensor, c: torch.Tensor):
     return ca, torch.stack([e1, e2, e3], dim=-2)
 
 
-def write_pdb(path: str, seq_idx: torch.Tensor, translations: torch.Tensor, orientations: torch.Tensor,
-              chain_idx: Optional[torch.Tensor] = None, residue_idx: Optional[torch.Tensor] = None, residue_mask: Optional[torch.Tensor] = None,
-              b_factor: Optional[torch.Tensor] = None, atoms: Sequence[str] = ("N", "CA", "C", "O")) -> int:
-    """One patch (K residues) as ATOM records (glycine gets no CB).  chain ids 1, 2, 3 ... -> A, B, C ...; returns the atom count."""
+def _atom_lines(seq_idx, translations, orientations, chain_idx, residue_idx, residue_mask, b_factor, atoms) -> list:
+    """ATOM records of one patch (K residues; glycine gets no CB), serial numbers from 1."""
     seq_idx, translations, orientations = seq_idx.cpu(), translations.cpu().float(), orientations.cpu().float()
     K = seq_idx.shape[0]
     xyz = backbone_from_frames(translations, orientations, atoms)
@@ -110,15 +108,62 @@ def write_pdb(path: str, seq_idx: torch.Tensor, translations: torch.Tensor, orie
             x, y, z = (float(v) for v in xyz[i, a])
             lines.append(f"ATOM  {serial:5d} {name:<4s} {aa:>3s} {ch}{rn:4d}    {x:8.3f}{y:8.3f}{z:8.3f}{1.0:6.2f}{bf:6.2f}          {name[0]:>2s}")
             serial += 1
+    return lines
+
+
+def write_pdb(path: str, seq_idx: torch.Tensor, translations: torch.Tensor, orientations: torch.Tensor,
+              chain_idx: Optional[torch.Tensor] = None, residue_idx: Optional[torch.Tensor] = None, residue_mask: Optional[torch.Tensor] = None,
+              b_factor: Optional[torch.Tensor] = None, atoms: Sequence[str] = ("N", "CA", "C", "O")) -> int:
+    """One patch (K residues) as ATOM records (glycine gets no CB).  chain ids 1, 2, 3 ... -> A, B, C ...; returns the atom count."""
+    lines = _atom_lines(seq_idx, translations, orientations, chain_idx, residue_idx, residue_mask, b_factor, atoms)
+    n = len(lines)
     lines.append("END")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
-    return serial - 1
+    return n
+
+
+def write_trajectory_pdb(path: str, trajectory: Dict[str, torch.Tensor], row: int, *, predictions: bool = False,
+                         chain_idx: Optional[torch.Tensor] = None, residue_idx: Optional[torch.Tensor] = None,
+                         residue_mask: Optional[torch.Tensor] = None, atoms: Sequence[str] = ("N", "CA", "C", "O")) -> int:
+    """State row ``row`` of ``DiffAb.sample(trajectory=...)['trajectory']`` as a multi-model PDB: one MODEL / ENDMDL per label, in the
+    trajectory's label order (descending t; MODEL serial = the label t).  The frames are the recorded state (translations,
+    orientations, seq_idx), or with ``predictions=True`` the predicted clean structure (pred_translations, pred_orientations) with the
+    argmax of seq_probs as the residue.  The b-factor is the probability of the written residue under seq_probs when the trajectory has
+    that field (0 otherwise).  chain_idx / residue_idx / residue_mask are the patch's (K,), as in write_pdb.  Returns the atom count
+    of all models."""
+    if predictions and "seq_probs" not in trajectory:
+        raise ValueError("write_trajectory_pdb: predictions=True needs a trajectory recorded with trajectory_predictions=True")
+    labels = trajectory["t"].cpu()
+    if predictions:
+        probs = trajectory["seq_probs"][row].cpu().float()
+        seq = probs.argmax(-1)
+        x, O = trajectory["pred_translations"][row], trajectory["pred_orientations"][row]
+    else:
+        seq, x, O = trajectory["seq_idx"][row].cpu(), trajectory["translations"][row], trajectory["orientations"][row]
+        probs = trajectory["seq_probs"][row].cpu().float() if "seq_probs" in trajectory else None
+    lines, n = [], 0
+    for j in range(labels.numel()):
+        bf = None if probs is None else probs[j].gather(-1, seq[j].unsqueeze(-1)).squeeze(-1)
+        model = _atom_lines(seq[j], x[j], O[j], chain_idx, residue_idx, residue_mask, bf, atoms)
+        n += len(model)
+        lines += [f"MODEL     {int(labels[j]):4d}"] + model + ["ENDMDL"]
+    lines.append("END")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return n
+
+
+def _to_cpu(v):
+    if isinstance(v, dict):
+        return {k: _to_cpu(u) for k, u in v.items()}
+    return v.detach().cpu() if isinstance(v, torch.Tensor) else v
 
 
 def save_samples(path: str, samples: Dict[str, torch.Tensor], **meta) -> None:
-    """``DiffAb.sample`` output (seq_idx, translations, orientations, ...) + free-form metadata, bit-exact round trip."""
-    torch.save({"samples": {k: v.detach().cpu() for k, v in samples.items()}, "meta": meta}, path)
+    """``DiffAb.sample`` output (seq_idx, translations, orientations, ...) + free-form metadata, bit-exact round trip.  Nested dicts of
+    tensors (sample()'s ``trajectory``, score()'s ``noised``) are saved as nested dicts."""
+    torch.save({"samples": _to_cpu(samples), "meta": meta}, path)
 
 
 def load_samples(path: str):

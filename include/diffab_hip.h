@@ -544,6 +544,43 @@ int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w
                           const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
                           int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                           void* stream);
+/* ---- trajectory recording (build-defined): the reverse process, step by step ------------------------------------------------------
+ * diffab_sample_loop_aa plus `rec` (nullable) before the stream; rec == NULL is exactly diffab_sample_loop_aa (which is this call with
+ * NULL).  Labels are steps: slot j = slot_of_step[t] (a HOST table of T + 1 int32, -1 = not recorded) holds, for step t,
+ *   the state that step t denoises: s_t, x_t, O_t (label t_start: the state the call was given - diffab_sample_init*'s, or the
+ *     forward-noised native of optimize_from).  Bitwise the output of this call with t_stop = t, same seed, first_patch, flags, map and
+ *     allowed.  The final state is the call's own output and has no slot;
+ *   with pred_x / pred_O / seq_probs, what the denoiser made of that state: x0_hat = (x_t - one_minus_alpha_bar_sqrt[t] eps_hat) /
+ *     alpha_bar_sqrt[t], O0_hat = O_t exp(hat(v)), and the softmax posterior over s_{t-1} - the UNRESTRICTED one: an `allowed` draw
+ *     renormalises it over the residue's set.  Slot of step 1: the distribution the returned token was drawn from.
+ * Residues that are not generated hold their given state in every slot; their predictions are their x / O and a one-hot of their
+ * token.  A kept modality (DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE) appears in the predictions as its given values (x_t, O_t; a one-hot
+ * of s_t).  Layout, B state rows outermost so a shard's rows are one contiguous slice: seq (B, n_slots, K) int64, x / pred_x
+ * (B, n_slots, K, 3), O / pred_O (B, n_slots, K, 3, 3), seq_probs (B, n_slots, K, V), all caller-owned DEVICE buffers.  Rows [lo, hi)
+ * run with first_patch = lo record that slice of the whole call's record, bitwise.  Recording does not change the sample: the state the
+ * call returns is bitwise the same with and without `rec`, on every launch form (graph replay included: the update kernel reads
+ * slot_dev[t] with t from device memory).  Cost: one uniform branch per step without a slot; with one, 56 B of state plus 12 + 36 + 4 V
+ * B of predictions per generated residue, written by the update kernel.
+ * slot_dev: a caller-owned DEVICE array of T + 1 int32 the call fills from slot_of_step with one hipMemcpyAsync (not workspace: the
+ * workspace size is unchanged).  Checked before anything is enqueued, DIFFAB_ERR_ARG: n_slots >= 1; every entry -1 or in [0, n_slots);
+ * every slot given to exactly one step; no slot for a step outside [t_stop + 1, t_start] (it would never be written); null
+ * slot_of_step, slot_dev, seq, x or O; some but not all of pred_x, pred_O, seq_probs (and predictions need s->alpha_bar_sqrt). */
+typedef struct {
+  int32_t n_slots;
+  const int32_t* slot_of_step; /* HOST (T + 1): step t -> slot, -1 = not recorded */
+  int32_t* slot_dev;           /* DEVICE (T + 1), filled by the call */
+  int64_t* seq;                /* (B, n_slots, K) */
+  float* x;                    /* (B, n_slots, K, 3) */
+  float* O;                    /* (B, n_slots, K, 3, 3) */
+  float* pred_x;               /* (B, n_slots, K, 3), nullable (all three predictions or none) */
+  float* pred_O;               /* (B, n_slots, K, 3, 3) */
+  float* seq_probs;            /* (B, n_slots, K, V) */
+} diffab_sample_record;
+int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                           int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                           const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                           int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                           const diffab_sample_record* rec, void* stream);
 int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
 int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
