@@ -786,6 +786,15 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
                            const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
                            int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                            const diffab_sample_record* rec, void* stream) {
+  return diffab_sample_loop_steps(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
+                                  t_stop, workspace, workspace_bytes, flags, allowed, rec, nullptr, stream);
+}
+
+int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                             int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                             const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                             int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                             const diffab_sample_record* rec, const diffab_sample_steps* steps, void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
@@ -829,6 +838,40 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
     rdev = SampleRecordDev{rec->slot_dev, rec->n_slots, rec->seq, rec->x, rec->O, rec->pred_x, rec->pred_O, rec->seq_probs,
                            n_pred ? s->alpha_bar_sqrt : nullptr};
   }
+  // fewer-step sampling: the list, its jump coefficients and the record are checked here, and the device plan - next[], beta'[], alpha'[]
+  // - is packed once (copied to plan_dev below, after every check)
+  StepPlanDev pdev;
+  std::vector<int32_t> plan_host;
+  if (steps != nullptr) {
+    const int T = s->T;
+    DIFFAB_REQUIRE(steps->n_steps >= 1, DIFFAB_ERR_ARG, "sample_loop: steps n_steps = %d < 1", steps->n_steps);
+    DIFFAB_REQUIRE(steps->steps && steps->beta_jump && steps->alpha_jump && steps->plan_dev, DIFFAB_ERR_ARG,
+                   "sample_loop: steps needs steps, beta_jump, alpha_jump and plan_dev");
+    DIFFAB_REQUIRE(s->alpha_bar, DIFFAB_ERR_ARG, "sample_loop: steps need the schedule's alpha_bar");
+    DIFFAB_REQUIRE(steps->steps[0] == t_start, DIFFAB_ERR_ARG, "sample_loop: steps[0] = %d, t_start = %d", steps->steps[0], t_start);
+    std::vector<char> listed(T + 1, 0);
+    for (int j = 0; j < steps->n_steps; ++j) {
+      const int t = steps->steps[j];
+      DIFFAB_REQUIRE(t > t_stop && t <= T, DIFFAB_ERR_ARG, "sample_loop: steps[%d] = %d outside [t_stop + 1, T] = [%d, %d]", j, t, t_stop + 1, T);
+      DIFFAB_REQUIRE(j == 0 || t < steps->steps[j - 1], DIFFAB_ERR_ARG, "sample_loop: steps are not strictly descending at %d (%d after %d)", j,
+                     t, steps->steps[j - 1]);
+      const float bj = steps->beta_jump[t], aj = steps->alpha_jump[t];
+      DIFFAB_REQUIRE(bj > 0.0f && bj < 1.0f && aj > 0.0f && aj < 1.0f, DIFFAB_ERR_ARG,
+                     "sample_loop: jump coefficients at step %d outside (0, 1): beta' = %g, alpha' = %g", t, bj, aj);
+      listed[t] = 1;
+    }
+    if (rec != nullptr)
+      for (int t = 0; t <= T; ++t)
+        DIFFAB_REQUIRE(rec->slot_of_step[t] == -1 || listed[t], DIFFAB_ERR_ARG,
+                       "sample_loop: record slot_of_step[%d] = %d, but the step list does not run step %d", t, rec->slot_of_step[t], t);
+    plan_host.resize(3 * static_cast<size_t>(T + 1));
+    for (int t = 0; t <= T; ++t) plan_host[t] = t > 0 ? t - 1 : 0;
+    for (int j = 0; j < steps->n_steps; ++j) plan_host[steps->steps[j]] = j + 1 < steps->n_steps ? steps->steps[j + 1] : t_stop;
+    std::memcpy(plan_host.data() + (T + 1), steps->beta_jump, sizeof(float) * (T + 1));
+    std::memcpy(plan_host.data() + 2 * (T + 1), steps->alpha_jump, sizeof(float) * (T + 1));
+    const int32_t* pd = static_cast<const int32_t*>(steps->plan_dev);
+    pdev = StepPlanDev{pd, reinterpret_cast<const float*>(pd + (T + 1)), reinterpret_cast<const float*>(pd + 2 * (T + 1)), s->alpha_bar};
+  }
   // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
   // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
   const bool mapped = ctx_of_row != nullptr;
@@ -866,6 +909,8 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
     DIFFAB_HIP_CHECK(hipMemcpyAsync(rec->slot_dev, rec->slot_of_step, sizeof(int32_t) * (s->T + 1), hipMemcpyHostToDevice, st));
     if (int rc = launch_record_fixed(rdev, seq, x, O, gen_mask, d->B, d->K, d->V, st)) return rc;
   }
+  if (steps != nullptr)  // the step plan, once per call
+    DIFFAB_HIP_CHECK(hipMemcpyAsync(steps->plan_dev, plan_host.data(), sizeof(int32_t) * plan_host.size(), hipMemcpyHostToDevice, st));
   auto one_step = [&](int t, const int* t_dev) -> int {
     if (!plan.fold)  // (the folded head tables read the schedule themselves: one launch less per step)
       if (int rc = launch_fill_beta(s, t, d->B, sb.beta, st, t_dev)) return rc;
@@ -875,21 +920,28 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
     if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev);
+                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is
   // captured into a hipGraph that takes its timestep from device memory, and the graph is replayed for every remaining step: one host
   // call per step instead of 45.  Same kernels, same order, same arguments: bitwise the same trajectory (tested).
-  const int n_steps = t_start - t_stop;
+  // (a step list: the eager loop runs over it, and graph replay advances the device timestep through the plan's next[] table)
+  const int n_steps = steps != nullptr ? steps->n_steps : t_start - t_stop;
   const bool graph = (flags & DIFFAB_FLAG_GRAPH_SAMPLER) && n_steps >= 3 && !kernel_timer_enabled();
   if (!graph) {
+    if (steps != nullptr) {
+      for (int j = 0; j < n_steps; ++j)
+        if (int rc = one_step(steps->steps[j], nullptr)) return rc;
+      return DIFFAB_OK;
+    }
     for (int t = t_start; t > t_stop; --t)
       if (int rc = one_step(t, nullptr)) return rc;
     return DIFFAB_OK;
   }
+  const int t_second = steps != nullptr ? steps->steps[1] : t_start - 1;
   if (int rc = one_step(t_start, nullptr)) return rc;
-  if (int rc = launch_set_int(sb.t_dev, t_start - 1, st)) return rc;
+  if (int rc = launch_set_int(sb.t_dev, t_second, st)) return rc;
   // Capture and replay run on a private stream (the caller's may be the legacy default stream, which cannot be captured), ordered
   // behind the caller's stream by an event; the private stream is drained before the call returns, so later work on the caller's
   // stream sees the finished trajectory, and the executable graph outlives its launches (the only synchronisation in this library;
@@ -908,15 +960,15 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
     st = side;  // one_step enqueues on `st`
     ei = hipStreamBeginCapture(side, hipStreamCaptureModeThreadLocal);
     if (ei == hipSuccess) {
-      rc = one_step(t_start - 1, sb.t_dev);
-      if (rc == DIFFAB_OK) rc = launch_dec_int(sb.t_dev, side);
+      rc = one_step(t_second, sb.t_dev);
+      if (rc == DIFFAB_OK) rc = steps != nullptr ? launch_advance_step(sb.t_dev, pdev.next, side) : launch_dec_int(sb.t_dev, side);
       ei = hipStreamEndCapture(side, &g);
     }
     st = caller;
   }
   if (ei == hipSuccess && rc == DIFFAB_OK) ei = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
   if (ei == hipSuccess && rc == DIFFAB_OK)
-    for (int t = t_start - 1; t > t_stop && ei == hipSuccess; --t) ei = hipGraphLaunch(ge, side);
+    for (int j = 1; j < n_steps && ei == hipSuccess; ++j) ei = hipGraphLaunch(ge, side);
   if (ei == hipSuccess) ei = hipStreamSynchronize(side);
   if (ge) (void)hipGraphExecDestroy(ge);
   if (g) (void)hipGraphDestroy(g);

@@ -242,13 +242,22 @@ struct SampleRecordDev {
   float* seq_probs = nullptr;
   const float* alpha_bar_sqrt = nullptr;  // the schedule's, for x0_hat (read with predictions only)
 };
+// Fewer-step sampling (diffab_sample_loop_steps), a by-value launch argument of the update kernel like the record: next == nullptr is the
+// ordinary step t -> t - 1.  The three tables (T + 1 entries, device) are the call's plan; alpha_bar is the schedule's.
+struct StepPlanDev {
+  const int32_t* next = nullptr;  // step t -> the step s the update moves the state to
+  const float* beta = nullptr;    // beta'_t
+  const float* alpha = nullptr;   // alpha'_t
+  const float* alpha_bar = nullptr;
+};
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
                                  const float* head_v = nullptr, const float* head_logits = nullptr,  // heads' epilogue done in the kernel  // t_dev: read the timestep from device memory (graph replay)
                                  uint32_t keep = 0,   // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
                                  const uint32_t* allowed = nullptr,  // per-residue allowed-class words of the sequence draw (nullable)
-                                 const SampleRecordDev& rec = SampleRecordDev{});  // trajectory recording (rec.slot nullable)
+                                 const SampleRecordDev& rec = SampleRecordDev{},  // trajectory recording (rec.slot nullable)
+                                 const StepPlanDev& plan = StepPlanDev{});  // fewer-step sampling (plan.next nullable)
 // the residues that are not generated: their (constant) state in every slot of the record, and their predictions - the given x / O and a
 // one-hot of the token - once per call
 int launch_record_fixed(const SampleRecordDev& rec, const int64_t* seq, const float* x, const float* O, const uint8_t* gm, int B, int K, int V,
@@ -281,5 +290,6 @@ int launch_score_losses(const diffab_sched* s, const ScoreChunk& c, const int64_
                         float* out_terms, float* out_residue, hipStream_t st);
 int launch_set_int(int* p, int v, hipStream_t st);
 int launch_dec_int(int* p, hipStream_t st);
+int launch_advance_step(int* p, const int* next, hipStream_t st);  // *p = next[*p] (graph replay of a step plan)
 
 }  // namespace diffab

@@ -700,7 +700,8 @@ __global__ void angular_encoding_kernel(const float* __restrict__ x, int64_t n, 
 
 // ------------------------------------------------------------------ reverse update
 // (the design modes, DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE, run one of the two halves)
-__device__ inline void reverse_update_structure(int64_t i, int t, float beta, float alpha, float omabs, float* x, float* O,
+// noise: t > 1 for the step t -> t - 1, s > 0 for a jump t -> s (beta / alpha are then the jump's beta'_t / alpha'_t)
+__device__ inline void reverse_update_structure(int64_t i, bool noise, float beta, float alpha, float omabs, float* x, float* O,
                                                 const float* eps_hat, const float* O0_hat, float zx, float zy, float zz, float rx, float ry,
                                                 float rz) {
   const float c = beta / omabs;
@@ -709,13 +710,13 @@ __device__ inline void reverse_update_structure(int64_t i, int t, float beta, fl
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     float v = (x[i * 3 + k] - c * eps_hat[i * 3 + k]) / sa;
-    if (t > 1) v = v + sb * zn[k];
+    if (noise) v = v + sb * zn[k];
     x[i * 3 + k] = v;
   }
   float o[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) o[k] = O0_hat[i * 9 + k];
-  if (t > 1) {
+  if (noise) {
     float nz[9], r[9];
     so3_rotvec_to_matrix(rx, ry, rz, nz);
     mat3_mul(o, nz, r);
@@ -729,8 +730,66 @@ __device__ inline void reverse_update_structure(int64_t i, int t, float beta, fl
 __device__ inline void reverse_update_one(int64_t i, int t, float beta, float alpha, float omabs, int64_t* seq, float* x, float* O,
                                           const float* eps_hat, const float* O0_hat, const float* post, int V, float zx, float zy,
                                           float zz, float rx, float ry, float rz, float u_seq) {
-  reverse_update_structure(i, t, beta, alpha, omabs, x, O, eps_hat, O0_hat, zx, zy, zz, rx, ry, rz);
+  reverse_update_structure(i, t > 1, beta, alpha, omabs, x, O, eps_hat, O0_hat, zx, zy, zz, rx, ry, rz);
   seq[i] = categorical_draw(post + i * V, V, u_seq);
+}
+
+// The sequence distribution of a jump t -> s < t - 1, in double: the head posterior p = q(s_{t-1} | s_t, .) mixed
+// over p(s_0 | s_t) is inverted for that mixture pi, which is then pushed through q(s_s | s_t, s_0):
+//   A_v = alpha_t [v = s_t] + beta_t / V, c = (1 - abar_{t-1}) / V, S = sum p_v / A_v, pi~_v = (abar_{t-1} A_v + c) max(0, p_v / A_v - c S),
+//   A'_v = alpha'_t [v = s_t] + (1 - alpha'_t) / V, c' = (1 - abar_s) / V, Z'_u = abar_s A'_u + c', W = sum pi_u / Z'_u,
+//   r_v = A'_v (c' W + abar_s pi_v / Z'_v).
+// Near T abar_{t-1} is ~2e-4, and fp32 would lose ~1e-4 of pi.  A, A' and Z' take two values each (v = s_t and the rest), so the V-long
+// passes multiply by five reciprocals instead of dividing.  p and r may alias: r_v is written after the last read of p_v.
+__device__ inline void seq_jump_probs(const float* p, float* r, int V, int64_t st, double at, double bt, double ab1, double aj, double abs_) {
+  const double inv_v = 1.0 / V, c = (1.0 - ab1) * inv_v, bv = bt * inv_v;
+  const double iA_o = 1.0 / bv, iA_s = 1.0 / (at + bv);
+  const double w_o = ab1 * bv + c, w_s = ab1 * (at + bv) + c;  // abar_{t-1} A_v + c
+  double S = 0.0;
+  for (int v = 0; v < V; ++v) S += p[v] * (v == st ? iA_s : iA_o);
+  const double cS = c * S;
+  auto mix = [&](int v) {  // pi~_v
+    return v == st ? w_s * fmax(0.0, p[v] * iA_s - cS) : w_o * fmax(0.0, p[v] * iA_o - cS);
+  };
+  double tot = 0.0;
+  for (int v = 0; v < V; ++v) tot += mix(v);
+  const bool raw = !(tot > 0.0);  // pi = p
+  const double inv_tot = raw ? 1.0 : 1.0 / tot;
+  const double cj = (1.0 - abs_) * inv_v, bj = (1.0 - aj) * inv_v;
+  const double Aj_o = bj, Aj_s = aj + bj, iZ_o = 1.0 / (abs_ * Aj_o + cj), iZ_s = 1.0 / (abs_ * Aj_s + cj);
+  double W = 0.0;
+  for (int v = 0; v < V; ++v) {
+    const double pi = raw ? static_cast<double>(p[v]) : mix(v) * inv_tot;
+    W += pi * (v == st ? iZ_s : iZ_o);
+  }
+  const double cW = cj * W;
+  for (int v = 0; v < V; ++v) {
+    const double pi = raw ? static_cast<double>(p[v]) : mix(v) * inv_tot;
+    r[v] = static_cast<float>(v == st ? Aj_s * (cW + abs_ * pi * iZ_s) : Aj_o * (cW + abs_ * pi * iZ_o));
+  }
+}
+
+// Teacher-forced jump t -> s_next (diffab_reverse_update_jump): reverse_update_kernel with the jump's coefficients, the noise condition
+// s > 0 and the sequence drawn from r (written to r_out when given).  s_next = t - 1 with beta[t] / alpha[t]: reverse_update_kernel's result.
+__global__ void reverse_update_jump_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ alpha_bar,
+                                           const float* __restrict__ omabs, int t, int s_next, float bj, float aj, int64_t* __restrict__ seq,
+                                           float* __restrict__ x, float* __restrict__ O, const float* __restrict__ eps_hat,
+                                           const float* __restrict__ O0_hat, const float* __restrict__ post, const uint8_t* __restrict__ gm,
+                                           const float* __restrict__ z, const float* __restrict__ rotvec, const float* __restrict__ u_seq,
+                                           float* __restrict__ r_out, int B, int K, int V) {
+  const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
+  if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
+  reverse_update_structure(i, s_next > 0, bj, aj, omabs[t], x, O, eps_hat, O0_hat, z[i * 3], z[i * 3 + 1], z[i * 3 + 2], rotvec[i * 3],
+                           rotvec[i * 3 + 1], rotvec[i * 3 + 2]);
+  float loc[32];  // V <= 32 (checked by the entry)
+  float* r = r_out != nullptr ? r_out + i * V : loc;
+  const float* p = post + i * V;
+  if (s_next == t - 1) {
+    for (int c = 0; c < V; ++c) r[c] = p[c];
+  } else {
+    seq_jump_probs(p, r, V, seq[i], alpha[t], beta[t], alpha_bar[t - 1], aj, alpha_bar[s_next]);
+  }
+  seq[i] = categorical_draw(r, V, u_seq[i]);
 }
 
 __global__ void reverse_update_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs, int t,
@@ -806,13 +865,16 @@ __global__ void record_fixed_kernel(SampleRecordDev rec, const int64_t* __restri
 // classes (categorical_draw_allowed, same uniform); nullptr is the unconstrained draw.
 // rec (trajectory recording; rec.slot == nullptr: off): when step t has a slot, the residue writes the state it is about to update and,
 // with predictions, what the epilogue made of it (record_residue), before any draw - the update itself is untouched.
+// plan (fewer-step sampling; plan.next == nullptr: off, the step t -> t - 1 above): the state moves to s = plan.next[t] with the jump's
+// beta'_t / alpha'_t and the noise condition s > 0 (the caller's rev_sigmas / rev_cdf are then the table over sqrt(beta')); for s < t - 1
+// the sequence is drawn from the jump distribution r (seq_jump_probs), computed in place over the posterior after it was recorded.
 __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs,
                                              int t, const float* __restrict__ rev_sigmas, const float* __restrict__ rev_cdf, int n_bins,
                                              float thr, int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
                                              const float* __restrict__ eps_hat, float* O0_hat, float* post, const uint8_t* __restrict__ gm,
                                              uint64_t seed, int64_t first_patch, int B, int K, int V, const int* __restrict__ t_dev,
                                              const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep,
-                                             const uint32_t* __restrict__ allowed, SampleRecordDev rec) {
+                                             const uint32_t* __restrict__ allowed, SampleRecordDev rec, StepPlanDev plan) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   if (t_dev != nullptr) t = *t_dev;  // graph replay: the timestep lives in device memory (one captured step serves every t)
@@ -846,11 +908,21 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
     const f32x4 na = normals_from_uniforms(ua);  // .z is the Box-Muller normal of (u2,u3)
     const float theta = igso3_theta(rev_cdf, n_bins, rev_sigmas[t], thr, t, ua.x, ua.y, na.z);
     normalize3(ax.x, ax.y, ax.z);
-    reverse_update_structure(i, t, beta[t], alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z, ax.x * theta, ax.y * theta,
-                             ax.z * theta);
+    if (plan.next == nullptr)
+      reverse_update_structure(i, t > 1, beta[t], alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z, ax.x * theta, ax.y * theta,
+                               ax.z * theta);
+    else
+      reverse_update_structure(i, plan.next[t] > 0, plan.beta[t], plan.alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z,
+                               ax.x * theta, ax.y * theta, ax.z * theta);
   }
   if (upd_seq) {
     const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_SEQ);
+    if (plan.next != nullptr) {
+      const int s_next = plan.next[t];
+      if (s_next < t - 1)
+        seq_jump_probs(post + i * V, post + i * V, V, seq[i], alpha[t], beta[t], plan.alpha_bar[t - 1], plan.alpha[t],
+                       plan.alpha_bar[s_next]);
+    }
     const int s = allowed == nullptr ? categorical_draw(post + i * V, V, us.x) : categorical_draw_allowed(post + i * V, V, us.x, allowed[i]);
     if (s >= 0) seq[i] = s;
   }
@@ -1094,16 +1166,18 @@ __global__ void fill_beta_kernel(const float* __restrict__ beta, int t, int B, f
 }
 __global__ void set_int_kernel(int* __restrict__ p, int v) { *p = v; }
 __global__ void dec_int_kernel(int* __restrict__ p) { *p -= 1; }
+__global__ void advance_step_kernel(int* __restrict__ p, const int* __restrict__ next) { *p = next[*p]; }
 
 // launchers used by api.hip (sample loop)
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
-                                 const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec) {
+                                 const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec,
+                                 const StepPlanDev& plan) {
   const int64_t n = static_cast<int64_t>(B) * K;
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
@@ -1208,6 +1282,11 @@ int launch_set_int(int* p, int v, hipStream_t st) {
 }
 int launch_dec_int(int* p, hipStream_t st) {
   hipLaunchKernelGGL(dec_int_kernel, dim3(1), dim3(1), 0, st, p);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+int launch_advance_step(int* p, const int* next, hipStream_t st) {
+  hipLaunchKernelGGL(advance_step_kernel, dim3(1), dim3(1), 0, st, p, next);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
@@ -1519,6 +1598,28 @@ int diffab_reverse_update(const diffab_sched* s, int32_t t, int64_t* seq, float*
   if (n == 0) return DIFFAB_OK;
   hipLaunchKernelGGL(reverse_update_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec, u_seq, B, K, V);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+
+int diffab_reverse_update_jump(const diffab_sched* s, int32_t t, int32_t s_next, float beta_jump, float alpha_jump, int64_t* seq, float* x,
+                               float* O, const float* eps_hat, const float* O0_hat, const float* posterior, const uint8_t* gen_mask,
+                               const float* z, const float* rotvec, const float* u_seq, float* r_out, int32_t B, int32_t K, int32_t V,
+                               void* stream) {
+  StreamOrder order_(stream);
+  if (int rc = check_sched(s)) return rc;
+  DIFFAB_REQUIRE(t >= 1 && t <= s->T && s_next >= 0 && s_next < t, DIFFAB_ERR_ARG, "reverse_update_jump: need 0 <= s < t <= T (t = %d, s = %d)",
+                 t, s_next);
+  DIFFAB_REQUIRE(beta_jump > 0.0f && beta_jump < 1.0f && alpha_jump > 0.0f && alpha_jump < 1.0f, DIFFAB_ERR_ARG,
+                 "reverse_update_jump: beta' and alpha' must lie in (0, 1)");
+  DIFFAB_REQUIRE(B >= 0 && K > 0 && V > 0 && V <= 32, DIFFAB_ERR_ARG, "reverse_update_jump: need B >= 0, K > 0, 0 < V <= 32");
+  const int64_t n = static_cast<int64_t>(B) * K;
+  if (n == 0) return DIFFAB_OK;
+  DIFFAB_REQUIRE(seq && x && O && eps_hat && O0_hat && posterior && gen_mask && z && rotvec && u_seq, DIFFAB_ERR_ARG,
+                 "reverse_update_jump: null pointer");
+  hipLaunchKernelGGL(reverse_update_jump_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), s->beta, s->alpha, s->alpha_bar,
+                     s->one_minus_alpha_bar_sqrt, t, s_next, beta_jump, alpha_jump, seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec,
+                     u_seq, r_out, B, K, V);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

@@ -91,6 +91,11 @@ class SampleRecord(C.Structure):  # diffab_sample_record: the recorded reverse t
         [(n, _fp) for n in ("seq", "x", "O", "pred_x", "pred_O", "seq_probs")]
 
 
+class SampleSteps(C.Structure):  # diffab_sample_steps: the executed step list of diffab_sample_loop_steps and its jump coefficients
+    _fields_ = [("n_steps", C.c_int32), ("steps", C.POINTER(C.c_int32)), ("beta_jump", C.POINTER(C.c_float)),
+                ("alpha_jump", C.POINTER(C.c_float)), ("plan_dev", _fp)]
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -192,6 +197,13 @@ SYMBOLS = {
     # trajectory recording: diffab_sample_loop_aa plus `rec` (nullable) before the stream
     "diffab_sample_loop_rec": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
                                          _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), _fp]),
+    # fewer-step sampling: diffab_sample_loop_rec plus `steps` (nullable) before the stream
+    "diffab_sample_loop_steps": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                           _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
+                                           _fp]),
+    # (sched, t, s, beta', alpha', seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec, u_seq, r_out (nullable), B, K, V, stream)
+    "diffab_reverse_update_jump": (C.c_int, [_PS, _i32, _i32, C.c_float, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
+                                             _i32, _i32, _i32, _fp]),
     "diffab_score_workspace_bytes": (_sz, [_PD, _i32]),
     # (d, w, sched, fwd_tab, seq, x, O, gen_mask, res_mask, n_designs, res_ctx, pair_ctx, n_ctx, ctx_of_design (host int32[n_designs]),
     #  t_list (host int32[n_t]), n_t, n_draws, seed, first_design, out_terms, out_residue, noised, ws, ws_bytes, flags, stream)

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
-from .diffusion import CoordinateDiffuser, OrientationDiffuser, SequenceDiffuser, cosine_variance_schedule
+from .diffusion import CoordinateDiffuser, OrientationDiffuser, SequenceDiffuser, cosine_variance_schedule, even_steps, jump_coefficients
 from . import so3 as _so3
 from . import features as _features
 
@@ -106,16 +106,48 @@ def _allowed_aa_host(who: str, allowed_aa, generation_mask, n_rows: int, K: int,
     return a
 
 
-def _trajectory_labels(who: str, trajectory, predictions, t_start: int, t_stop: int, T: int) -> Optional[torch.Tensor]:
-    """Host int64 (n,) of sample()'s recorded steps, descending, from `trajectory` (None / False: nothing recorded), after every check
+def _sample_steps(who: str, steps, t_start: int, t_stop: int, T: int) -> Optional[torch.Tensor]:
+    """Host int64 (n,) of sample()'s executed steps, descending, from `steps` (None: every step, the ordinary loop), after every check
     made before device work."""
+    if steps is None:
+        return None
+    if not T >= t_start > t_stop >= 0:
+        raise ValueError(f"{who}: steps needs T = {T} >= t_start = {t_start} > t_stop = {t_stop} >= 0")
+    if isinstance(steps, bool) or isinstance(steps, float):
+        raise ValueError(f"{who}: steps must be an int n or a 1-D list of steps, got {steps!r}")
+    if isinstance(steps, int):
+        try:
+            return even_steps(t_start, t_stop, steps)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+    lt = torch.as_tensor(steps)
+    if lt.dim() != 1 or lt.numel() == 0 or lt.dtype == torch.bool or lt.is_floating_point() or lt.is_complex():
+        raise ValueError(f"{who}: a step list must be a non-empty 1-D integer list, got shape {tuple(lt.shape)} {lt.dtype}")
+    lt = lt.detach().to("cpu", torch.int64)
+    if int(lt[0]) != t_start:
+        raise ValueError(f"{who}: the step list starts at {int(lt[0])}, the run at t_start = {t_start}")
+    if lt.numel() > 1 and not bool((lt[1:] < lt[:-1]).all()):
+        raise ValueError(f"{who}: the step list is not strictly descending: {lt.tolist()}")
+    if int(lt[-1]) <= t_stop:
+        raise ValueError(f"{who}: step {int(lt[-1])} is not above t_stop = {t_stop}")
+    return lt
+
+
+def _trajectory_labels(who: str, trajectory, predictions, t_start: int, t_stop: int, T: int,
+                       executed: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """Host int64 (n,) of sample()'s recorded steps, descending, from `trajectory` (None / False: nothing recorded), after every check
+    made before device work.  `executed`: the steps a respaced run executes (labels are among them; a stride k is every k-th of them)."""
     if trajectory is None or trajectory is False:
         if predictions:
             raise ValueError(f"{who}: trajectory_predictions records predictions along a trajectory; give trajectory as well")
         return None
     if not T >= t_start >= t_stop >= 0:
         raise ValueError(f"{who}: a trajectory needs T = {T} >= t_start = {t_start} >= t_stop = {t_stop} >= 0")
-    if trajectory is True:
+    if executed is not None and trajectory is True:
+        labels = executed.clone()
+    elif executed is not None and isinstance(trajectory, int) and not isinstance(trajectory, bool) and trajectory >= 1:
+        labels = executed[::trajectory].clone()
+    elif trajectory is True:
         labels = torch.arange(t_start, t_stop, -1, dtype=torch.int64)
     elif isinstance(trajectory, int):
         if trajectory < 1:
@@ -133,6 +165,10 @@ def _trajectory_labels(who: str, trajectory, predictions, t_start: int, t_stop: 
             raise ValueError(f"{who}: trajectory step {int(bad[0])} outside [t_stop + 1, t_start] = [{t_stop + 1}, {t_start}]")
         if lt.unique().numel() != lt.numel():
             raise ValueError(f"{who}: trajectory lists a step more than once")
+        if executed is not None:
+            missing = [t for t in lt.tolist() if t not in set(executed.tolist())]
+            if missing:
+                raise ValueError(f"{who}: trajectory step {missing[0]} is not one of the executed steps {executed.tolist()}")
         labels = lt.sort(descending=True).values
     if labels.numel() == 0:
         raise ValueError(f"{who}: the trajectory records no step (t_start = {t_start}, t_stop = {t_stop})")
@@ -824,11 +860,13 @@ class DiffAb(_ModuleBase):
         self.coordinate_loss = nn.MSELoss(reduction="none")
         self.orientation_loss = OrientationLoss(reduction="none")
         self.T = T
+        self.beta_max = beta_max  # the schedule's clip, which the jump coefficients of a respaced sample() reuse
         self.lr = lr
         self.weight_decay = weight_decay
         self.betas = betas
         self._sched_dev: Optional[_hip.SchedOnDevice] = None
         self._rev_so3: Optional[_so3.SO3] = None
+        self._rev_so3_steps: Dict[tuple, _so3.SO3] = {}  # (executed steps, t_stop) -> the reverse table over sqrt(beta')
 
     # ------------------------------------------------------------------ device-side tables
     def _sched_on_device(self) -> _hip.SchedOnDevice:
@@ -842,6 +880,20 @@ class DiffAb(_ModuleBase):
             # (the device sampler of the reverse loop draws by inverse CDF: one table lookup per residue inside reverse_update)
             self._rev_so3 = _so3.SO3(self.sched["beta"].sqrt(), sigma_threshold=0.1, n_bins=8192, num_iters=1024, without_replacement=False)
         return self._rev_so3
+
+    def _reverse_so3_steps(self, steps: torch.Tensor, t_stop: int, beta_jump: torch.Tensor) -> _so3.SO3:
+        """Reverse IGSO3 table of a respaced run: row t over sigma_t = sqrt(beta'_t), built like _reverse_so3 (each row depends on its
+        own sigma alone, so the rows at stride-1 steps are bitwise _reverse_so3's; a run that lists every step uses that table)."""
+        if torch.equal(beta_jump, self.sched["beta"]):
+            return self._reverse_so3()
+        key = (tuple(steps.tolist()), int(t_stop))
+        tab = self._rev_so3_steps.get(key)
+        if tab is None or tab.histograms.device != _hip.device():
+            if len(self._rev_so3_steps) >= 8:  # a few step lists in use at once; 64 MiB of tables per list
+                self._rev_so3_steps.pop(next(iter(self._rev_so3_steps)))
+            tab = _so3.SO3(beta_jump.sqrt(), sigma_threshold=0.1, n_bins=8192, num_iters=1024, without_replacement=False)
+            self._rev_so3_steps[key] = tab
+        return tab
 
     # ------------------------------------------------------------------ reference API
     def encode_context(self, seq_idx_t0, xyz_t0, orientations_t0, backbone_dihedrals, distmat, pairwise_dihedrals, atom_mask, chain_idx,
@@ -982,7 +1034,7 @@ class DiffAb(_ModuleBase):
                skip_unused_rows: bool = False, num_samples: int = 1,
                context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
                optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None, trajectory=None,
-               trajectory_predictions: bool = False) -> Dict[str, torch.Tensor]:
+               trajectory_predictions: bool = False, steps=None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -1054,7 +1106,21 @@ class DiffAb(_ModuleBase):
         same with and without a trajectory, on every launch form.  Memory: 56 B of state plus 132 B of predictions (V = 21) per
         recorded residue and label - every step of a 100-step run at 256 x 128 is about 590 MiB.  A bool / float / 2-D / empty
         trajectory, a stride < 1, a step outside the range or named twice, and trajectory_predictions without trajectory raise
-        ValueError before any device work."""
+        ValueError before any device work.
+
+        Fewer-step sampling (DDPM respacing): ``steps=n`` runs n evenly spaced steps tau_j = t_start -
+        round_half_up(j (L - 1) / (n - 1)), L = t_start - t_stop (every step when n = L); a 1-D int list / tensor names them itself,
+        strictly descending from t_start (optimize_from's step with optimize_from) and above t_stop.  Step tau_j evaluates the denoiser
+        at tau_j exactly as the full loop does and moves the state to tau_{j+1} (t_stop after the last) with the jump's coefficients
+        beta'_t = clip(1 - abar_t / abar_s, 1e-5, beta_max): translations and orientations by the DDPM update with beta', the sequence
+        from sum_u p(s_0 = u | s_t) q(s_s | s_t, u), the x0 mixture recovered from the head posterior on the device in double
+        (`diffab_sample_loop_steps`).  Noise stays keyed by (seed, first_patch + b, residue, tau_j), so sharding, num_samples and
+        context_index behave as above; it combines with every mode, optimize_from, allowed_aa, graph, skip_unused_rows and the flags.
+        Listing every step is bitwise ``steps=None``, and a mixed list is bitwise the full run up to its last stride-1 step.  With a
+        trajectory, labels are executed steps: True records every executed step, an int k every k-th of them, and a list must name
+        executed steps; ``seq_probs`` is still the head posterior.  None is the ordinary loop.  A bool / float / 2-D / empty list,
+        n outside [1, L], a list that does not start at t_start, is not strictly descending or reaches t_stop, and t_start = t_stop
+        raise ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
         generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
@@ -1091,8 +1157,9 @@ class DiffAb(_ModuleBase):
             ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
         if allowed_aa is not None:
             _allowed_aa_host("sample()", allowed_aa, generation_mask, n_rows, K_, self.denoiser.dims["V"], keep)
+        executed = _sample_steps("sample()", steps, self.T if t_start is None else int(t_start), int(t_stop), self.T)
         labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, self.T if t_start is None else int(t_start), int(t_stop),
-                                    self.T)
+                                    self.T, executed)
         if res_context_emb is None or pair_context_emb is None:
             _check_encode_fields("sample()", xyz, atom_mask, chain_idx)
             res_context_emb, pair_context_emb = self._contexts_from_batch(seq_idx, xyz, orientations, generation_mask, residue_mask,
@@ -1119,7 +1186,12 @@ class DiffAb(_ModuleBase):
         dims = self.denoiser.hip_dims(B, K)
         w = self.denoiser.hip_weights()
         sd = self._sched_on_device()
-        tab = self._reverse_so3().struct()
+        if executed is None:
+            tab = self._reverse_so3().struct()
+        else:
+            beta_j, alpha_j = jump_coefficients(self.sched, executed, int(t_stop), self.beta_max)
+            rev_tab = self._reverse_so3_steps(executed, int(t_stop), beta_j)  # (held until the call has been enqueued)
+            tab = rev_tab.struct()
         if ctx_map is None:
             ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(dims)))
         else:
@@ -1148,6 +1220,7 @@ class DiffAb(_ModuleBase):
         elif init:
             _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T,
                                               _hip.stream_ptr()), "diffab_sample_init")
+        rec = None
         if labels is not None:
             V = self.denoiser.dims["V"]
             n = labels.numel()
@@ -1164,6 +1237,21 @@ class DiffAb(_ModuleBase):
             rec = _hip.SampleRecord(n, (C.c_int32 * (self.T + 1))(*slot_of_step), _hip.ptr(slot_dev),
                                     *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
                                                                       "pred_orientations", "seq_probs")))
+        if executed is not None:
+            plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=seq.device)
+            st = _hip.SampleSteps(executed.numel(), (C.c_int32 * executed.numel())(*executed.tolist()),
+                                  (C.c_float * (self.T + 1))(*beta_j.tolist()), (C.c_float * (self.T + 1))(*alpha_j.tolist()),
+                                  _hip.ptr(plan_dev))
+            _hip.check(lib.diffab_sample_loop_steps(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
+                                                    _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
+                                                    None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,
+                                                    _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), None if rec is None else C.byref(rec),
+                                                    C.byref(st), _hip.stream_ptr()), "diffab_sample_loop_steps")
+            out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
+            if labels is not None:
+                out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}
+            return out
+        if labels is not None:
             _hip.check(lib.diffab_sample_loop_rec(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
                                                   _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
                                                   None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,

@@ -40,6 +40,37 @@ def cosine_variance_schedule(T: int, s: float = 8e-3, beta_max: float = 0.999) -
     }
 
 
+def even_steps(t_start: int, t_stop: int, n: int) -> torch.Tensor:
+    """The n executed steps of a respaced reverse run, int64 (n,) descending: tau_j = t_start -
+    round_half_up(j (L - 1) / (n - 1)) with L = t_start - t_stop, i.e. n distinct steps from t_start to t_stop + 1, every step when
+    n = L, [t_start] when n = 1."""
+    L = t_start - t_stop
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= L:
+        raise ValueError(f"steps = {n!r}: need an int in [1, t_start - t_stop] = [1, {L}]")
+    if n == 1:
+        return torch.tensor([t_start], dtype=torch.int64)
+    # round_half_up(a / b) = floor((2 a + b) / (2 b)), in integers
+    return torch.tensor([t_start - (2 * j * (L - 1) + (n - 1)) // (2 * (n - 1)) for j in range(n)], dtype=torch.int64)
+
+
+def jump_coefficients(sched: Dict[str, torch.Tensor], steps: torch.Tensor, t_stop: int, beta_max: float = 0.999):
+    """(beta', alpha') fp32 (T + 1,) of the run that executes `steps` (descending) and stops at t_stop: at step tau_j, jumping to s =
+    tau_{j+1} (t_stop after the last), beta'_t = clip(1 - abar_t / abar_s, 1e-5, beta_max) and alpha'_t = 1 - beta'_t, in float64 from
+    the schedule's alpha_bar and rounded once; where s = t - 1, and at every step the run does not execute, the schedule's own beta[t] /
+    alpha[t], copied."""
+    beta, alpha = sched["beta"].clone(), sched["alpha"].clone()
+    abar = sched["alpha_bar"].double()
+    st = [int(v) for v in steps.tolist()]
+    for j, t in enumerate(st):
+        s = st[j + 1] if j + 1 < len(st) else int(t_stop)
+        if s == t - 1:
+            continue
+        b = min(max(1.0 - float(abar[t]) / float(abar[s]), 1e-5), beta_max)
+        beta[t] = b
+        alpha[t] = 1.0 - b
+    return beta, alpha
+
+
 def weighted_multinomial(p1: torch.Tensor, p2: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     """w1 * p1 + w2 * p2 with the (B,) weights broadcast over the trailing (K, V) dimensions (reference diffusion.py:38-41;
     p1 may be an int64 one-hot, promoted to float32 as upstream)."""

@@ -581,6 +581,51 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
                            const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
                            int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                            const diffab_sample_record* rec, void* stream);
+/* ---- fewer-step reverse sampling (build-defined): the reverse process on a subsequence of the steps ----------------------------------
+ * A run names the steps it executes, tau_0 = t_start > tau_1 > ... > tau_{n-1} > t_stop.  Step tau_j denoises the state at tau_j (the
+ * denoiser's time input is beta[tau_j], as always) and moves it to s = tau_{j+1}; the last step moves it to s = t_stop.  Philox noise
+ * stays keyed by (seed, first_patch + b, residue, t = tau_j) on the same streams.  With abar = alpha_bar and V the vocabulary size:
+ *   jump coefficients (HOST tables, the caller's): beta'_t = clip(1 - abar_t / abar_s, 1e-5, beta_max), alpha'_t = 1 - beta'_t,
+ *     computed in float64 and stored as fp32; when s = t - 1 they are the schedule's own beta[t] / alpha[t], copied;
+ *   translations: x_s = (x_t - beta'_t / sqrt(1 - abar_t) eps_hat) / sqrt(alpha'_t) + [s > 0] sqrt(beta'_t) z;
+ *   orientations: O_s = O0_hat exp(hat(w)) when s > 0, else O0_hat; w is drawn as always from row t of rev_tab, which for a respaced
+ *     run is the IGSO3 table over sigma_t = sqrt(beta'_t) (the caller builds it; stride-1 rows are the ordinary table's rows);
+ *   sequence: s = t - 1 draws from the head posterior p exactly as diffab_sample_loop.  s < t - 1 first recovers p(s_0 | s_t) from p,
+ *     in double: A_v = alpha_t [v = s_t] + beta_t / V, c = (1 - abar_{t-1}) / V, S = sum_v p_v / A_v,
+ *     pi~_v = (abar_{t-1} A_v + c) max(0, p_v / A_v - c S), pi = pi~ / sum pi~ (pi = p when sum pi~ = 0) - the exact inverse of
+ *     p = sum_u pi_u q(s_{t-1} | s_t, u).  Then A'_v = alpha'_t [v = s_t] + (1 - alpha'_t) / V, c' = (1 - abar_s) / V,
+ *     Z'_u = abar_s A'_u + c', W = sum_u pi_u / Z'_u and r_v = A'_v (c' W + abar_s pi_v / Z'_v) = sum_u pi_u q(s_s | s_t, u) (r = pi at
+ *     s = 0).  s_s is drawn from r (rounded to fp32) with the STREAM_SEQ uniform of step t by the reverse-step rule (restricted to the
+ *     residue's `allowed` classes when given).
+ * diffab_sample_loop_steps is diffab_sample_loop_rec plus `steps` (nullable) before the stream; steps == NULL is exactly
+ * diffab_sample_loop_rec (which is unchanged).  Listing every step t_start .. t_stop + 1 with the schedule's own beta / alpha is bitwise
+ * that call.  The eager loop runs over the list; graph replay advances the device timestep through the plan's next[] table, n - 1
+ * replays after the first step.  plan_dev: a caller-owned DEVICE buffer of 3 (T + 1) 32-bit words - next[T + 1] int32 (next[tau_j] =
+ * tau_{j+1}, t_stop after the last; t - 1 elsewhere), beta'[T + 1] and alpha'[T + 1] fp32 - the call fills it from the host fields with
+ * one hipMemcpyAsync (not workspace: the workspace size is unchanged).  Needs s->alpha_bar.  Checked before anything is
+ * enqueued, DIFFAB_ERR_ARG: n_steps < 1; a null field; steps[0] != t_start; a list that is not strictly descending; an entry <= t_stop
+ * or > T; beta'_t or alpha'_t outside (0, 1) at a listed step; a record slot for a step the list does not run. */
+typedef struct {
+  int32_t n_steps;
+  const int32_t* steps;     /* HOST (n_steps): tau_0 = t_start > ... > tau_{n-1} > t_stop */
+  const float* beta_jump;   /* HOST (T + 1): beta'_t at every listed step t (other entries unread) */
+  const float* alpha_jump;  /* HOST (T + 1): alpha'_t = 1 - beta'_t */
+  void* plan_dev;           /* DEVICE 3 (T + 1) 32-bit words, filled by the call */
+} diffab_sample_steps;
+int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                             int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                             const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                             int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                             const diffab_sample_record* rec, const diffab_sample_steps* steps, void* stream);
+/* Teacher-forced jump t -> s (the analogue of diffab_reverse_update): explicit z (B,K,3), rotvec (B,K,3), u_seq (B,K) and jump
+ * coefficients beta_jump / alpha_jump; the rule above, in place on (seq, x, O) where gen_mask is set.  r_out (B,K,V, nullable): the
+ * distribution s_s is drawn from, for the generated residues (p itself when s = t - 1).  s = t - 1 with the schedule's beta[t] / alpha[t]
+ * is bitwise diffab_reverse_update.  DIFFAB_ERR_ARG: t outside [1, T], s outside [0, t), beta_jump / alpha_jump outside (0, 1), V > 32,
+ * a null pointer, or a schedule without alpha_bar. */
+int diffab_reverse_update_jump(const diffab_sched* s, int32_t t, int32_t s_next, float beta_jump, float alpha_jump, int64_t* seq, float* x,
+                               float* O, const float* eps_hat, const float* O0_hat, const float* posterior, const uint8_t* gen_mask,
+                               const float* z, const float* rotvec, const float* u_seq, float* r_out, int32_t B, int32_t K, int32_t V,
+                               void* stream);
 int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
 int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
