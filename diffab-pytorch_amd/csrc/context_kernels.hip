@@ -911,7 +911,7 @@ static int pair_embedding_bwd_fused(const diffab_ctx_dims* d, const diffab_pair_
       // ---- forward recompute: one launch, the hidden activations (after their ReLUs) on the tape
       return rc;
     }
-    if (pair_chain_bwd_enabled() && pair_chain_bwd_supported(C, d->K, nrows)) {
+    if (pair_chain_bwd_enabled() && pair_chain_bwd_supported(C, d->K, row0, nrows)) {
       // ---- the atom-mask product, the four 64 x 64 layers' d x chain and their weight / bias gradients: ONE launch, a 128-row tile stays
       //      on the CU from d out to d h1 (pair_chain_bwd.hip); d C and d h1 leave for the steps below
       const float* Xs[4] = {m2, m1, df, h1};
@@ -957,7 +957,7 @@ static int pair_embedding_bwd_fused(const diffab_ctx_dims* d, const diffab_pair_
     } else if (int rc = bwd_gemm_tn(dC, C, enc, 20, gmw0p + 3 * C, Wp, rows, C, Wp - 3 * C, nullptr, st)) {
       return rc;
     }
-    if (pair_chain_bwd_enabled() && pair_table_mfma_supported(C, d->K, nrows, kAA, d->max_dist)) {
+    if (pair_chain_bwd_enabled() && pair_table_mfma_supported(C, d->K, row0, nrows, kAA, d->max_dist)) {
       // the table sums as one-hot products on the matrix cores (pair_chain_bwd.hip): no LDS atomics
       if (int rc = launch_pair_table_mfma(dC, seq_idx, sequence_context_mask, residue_idx, residue_idx_batch_stride, chain_idx, d->K, d->max_dist,
                                           kAA, kUNK, row0, nrows, G1, parts, st))

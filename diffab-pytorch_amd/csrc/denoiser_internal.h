@@ -204,13 +204,13 @@ int launch_pair_dist_bwd_fused(const int64_t* seq, const uint8_t* seq_m, const f
 bool pair_dist_bwd_mfma_supported(int K, int A, int64_t row0, int64_t nrows, int ld, int n_aa);
 int launch_pair_dist_bwd_mfma(const int64_t* seq, const uint8_t* seq_m, const float* distmat, const float* xyz, const float* din, const float* ddin,
                               int K, int A, int n_aa, int unk, int64_t row0, int64_t nrows, int ld, float* g_sp, hipStream_t st);
-bool pair_table_mfma_supported(int C, int K, int64_t nrows, int n_aa, int max_dist);
+bool pair_table_mfma_supported(int C, int K, int64_t row0, int64_t nrows, int n_aa, int max_dist);
 int launch_pair_table_mfma(const float* g, const int64_t* seq, const uint8_t* seq_m, const int64_t* resid, int resid_bstride, const int64_t* chain,
                            int K, int max_dist, int n_aa, int unk, int64_t row0, int64_t nrows, float* G1, float* part, hipStream_t st);
 // per-work-group partial sums -> their destinations: out[q][(i / cols[q]) ld[q] + i % cols[q]] += sum_p parts[p stride + off[q] + i], i < n[q]
 struct PartsSegs { int nseg; int off[8]; int n[8]; int cols[8]; int ld[8]; float* out[8]; };
 int launch_parts_reduce(const float* parts, int nparts, int64_t stride, const PartsSegs& sg, hipStream_t st);
-bool pair_chain_bwd_supported(int C, int K, int64_t nrows);
+bool pair_chain_bwd_supported(int C, int K, int64_t row0, int64_t nrows);
 bool pair_chain_bwd_enabled();  // false: diffab_debug_set_attn_variant bit 6 (64): the separate launches (A/B, tests)
 int launch_pair_chain_bwd(const float* d_out, const float* amask, int K, int A, int ca, int64_t row0, int64_t nrows, const float* const* X,
                           const float* const* W, const int* ldw, float* dC, float* dh1, float* const* gW, const int* ldg, float* const* gb,

@@ -755,13 +755,15 @@ int launch_parts_reduce(const float* parts, int nparts, int64_t stride, const Pa
   return DIFFAB_OK;
 }
 
-// G1[n_aa^2][64] | G2[2 max_dist + 1][64] (adjacent) += the one-hot products of g (pair_table_mfma_kernel); part: 256 slabs of the same size
-bool pair_table_mfma_supported(int C, int K, int64_t nrows, int n_aa, int max_dist) {
-  return C == PC_C && K % PC_ROWS == 0 && nrows % PC_ROWS == 0 && nrows >= PC_ROWS && n_aa * n_aa <= 28 * 16 && 2 * max_dist + 1 <= 5 * 16;
+// G1[n_aa^2][64] | G2[2 max_dist + 1][64] (adjacent) += the one-hot products of g (pair_table_mfma_kernel); part: 256 slabs of the same size.
+// Each 128-row tile must hold consecutive j of one (patch, i): K and the chunk's first row are multiples of 128.
+bool pair_table_mfma_supported(int C, int K, int64_t row0, int64_t nrows, int n_aa, int max_dist) {
+  return C == PC_C && K % PC_ROWS == 0 && row0 % PC_ROWS == 0 && nrows % PC_ROWS == 0 && nrows >= PC_ROWS && n_aa * n_aa <= 28 * 16 &&
+         2 * max_dist + 1 <= 5 * 16;
 }
 int launch_pair_table_mfma(const float* g, const int64_t* seq, const uint8_t* seq_m, const int64_t* resid, int resid_bstride, const int64_t* chain,
                            int K, int max_dist, int n_aa, int unk, int64_t row0, int64_t nrows, float* G1, float* part, hipStream_t st) {
-  DIFFAB_REQUIRE(g && seq && resid && chain && G1 && part && pair_table_mfma_supported(PC_C, K, nrows, n_aa, max_dist) &&
+  DIFFAB_REQUIRE(g && seq && resid && chain && G1 && part && pair_table_mfma_supported(PC_C, K, row0, nrows, n_aa, max_dist) &&
                      (reinterpret_cast<uintptr_t>(g) & 15) == 0,
                  DIFFAB_ERR_ARG, "pair_table_mfma: unsupported operands");
   PairTableArgs a{};
@@ -823,7 +825,10 @@ int launch_pair_dist_bwd_fused(const int64_t* seq, const uint8_t* seq_m, const f
 
 size_t pair_chain_bwd_prep_floats() { return PC_WFRAG / 2 + 64; }
 size_t pair_chain_bwd_part_floats() { return static_cast<size_t>(256) * PC_PART; }
-bool pair_chain_bwd_supported(int C, int K, int64_t nrows) { return C == PC_C && K % PC_ROWS == 0 && nrows % PC_ROWS == 0 && nrows >= PC_ROWS; }
+// (as for the table sums: each 128-row tile holds consecutive j of one (patch, i))
+bool pair_chain_bwd_supported(int C, int K, int64_t row0, int64_t nrows) {
+  return C == PC_C && K % PC_ROWS == 0 && row0 % PC_ROWS == 0 && nrows % PC_ROWS == 0 && nrows >= PC_ROWS;
+}
 
 // W: {mlp[4].W, mlp[2].W, mlp[0].W[:, 2C:3C], distance_embedding[2].W} with their leading dimensions; X: {m2, m1, df, h1}; gW / ldg / gb:
 // the matching gradients (+=).  prep: pair_chain_bwd_prep_floats() floats, 16-byte aligned, overwritten; part: pair_chain_bwd_part_floats().
@@ -831,7 +836,7 @@ int launch_pair_chain_bwd(const float* d_out, const float* amask, int K, int A, 
                           const float* const* W, const int* ldw, float* dC, float* dh1, float* const* gW, const int* ldg, float* const* gb,
                           float* prep, float* part, hipStream_t st) {
   DIFFAB_REQUIRE(d_out && amask && X && W && dC && dh1 && gW && gb && prep && part && (reinterpret_cast<uintptr_t>(prep) & 15) == 0 &&
-                     pair_chain_bwd_supported(PC_C, K, nrows) && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
+                     pair_chain_bwd_supported(PC_C, K, row0, nrows) && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(dC) & 15) == 0 && (reinterpret_cast<uintptr_t>(dh1) & 15) == 0,
                  DIFFAB_ERR_ARG, "pair_chain_bwd: unsupported operands");
   PairChainArgs a{};

@@ -130,9 +130,14 @@ def context_state_dict(d_res: int, d_pair: int, n_atoms: int = 15, max_dist: int
     return {k: torch.from_numpy(v.astype(np.float32)) for k, v in sd.items()}
 
 
-def context_batch(B: int, K: int, n_atoms: int = 15, seed: int = 0, with_distmat: bool = True) -> Dict[str, torch.Tensor]:
+def context_batch(B: int, K: int, n_atoms: int = 15, seed: int = 0, with_distmat: bool = True, max_chain: int = 3,
+                  per_patch_residue_idx: bool = False, n_pad: int = 0) -> Dict[str, torch.Tensor]:
     """Synthetic inputs of DiffAb.encode_context (reference batch dict): atoms scattered around each
-    residue's CA, real pairwise atom distances, random angles, chains 1..3, a contiguous generated segment per patch."""
+    residue's CA, real pairwise atom distances, random angles, chains 1..max_chain (sorted: contiguous chains), a contiguous generated
+    segment per patch.  residue_idx is arange(K) shared by all patches, (1, K); per_patch_residue_idx=True: a (B, K) index per patch, from
+    an offset in [0, 500) with gaps of up to 60 between ~1 in 8 neighbours.  n_pad > 0: the last n_pad residues of patch 0 are padding as
+    collate_fn pads a batch (atom mask 0, xyz 0, identity frame, chain 0, UNK, outside residue_mask and generation_mask; patch 0's
+    distances then come from its float32 xyz).  The defaults reproduce the original draws exactly."""
     out = {k: [] for k in ("seq_idx", "xyz", "orientations", "backbone_dihedrals", "distmat", "pairwise_dihedrals", "atom_mask",
                            "chain_idx", "generation_mask", "residue_mask")}
     for p in range(B):
@@ -152,7 +157,7 @@ def context_batch(B: int, K: int, n_atoms: int = 15, seed: int = 0, with_distmat
         out["distmat"].append(d.astype(np.float32))
         out["pairwise_dihedrals"].append(rng.uniform(-np.pi, np.pi, (K, K, 2)).astype(np.float32))
         out["atom_mask"].append(am.astype(np.float32))
-        out["chain_idx"].append(np.sort(rng.integers(1, 4, size=K)).astype(np.int64))
+        out["chain_idx"].append(np.sort(rng.integers(1, max_chain + 1, size=K)).astype(np.int64))
         seg = int(rng.integers(2, max(3, K // 3)))
         start = int(rng.integers(0, K - seg + 1))
         g = np.zeros(K, dtype=bool)
@@ -161,6 +166,22 @@ def context_batch(B: int, K: int, n_atoms: int = 15, seed: int = 0, with_distmat
         rm[0] = False
         out["generation_mask"].append(g)
         out["residue_mask"].append(rm)
+        if per_patch_residue_idx:  # drawn last: the draws above are those of the shared-index batch
+            steps = 1 + (rng.random(K) < 0.125) * rng.integers(1, 61, size=K)
+            out.setdefault("residue_idx", []).append(int(rng.integers(0, 500)) + np.cumsum(steps) - steps[0])
     res = {k: torch.from_numpy(np.stack(v)) for k, v in out.items()}
-    res["residue_idx"] = torch.arange(K).unsqueeze(0)
+    if not per_patch_residue_idx:
+        res["residue_idx"] = torch.arange(K).unsqueeze(0)
+    if n_pad > 0:
+        tail = slice(K - n_pad, K)
+        res["xyz"][0, tail] = 0.0
+        res["atom_mask"][0, tail] = 0.0
+        res["orientations"][0, tail] = torch.eye(3)
+        res["chain_idx"][0, tail] = 0
+        res["seq_idx"][0, tail] = 20  # UNK
+        res["residue_mask"][0, tail] = False
+        res["generation_mask"][0, tail] = False
+        if with_distmat:
+            x = res["xyz"][0].double()
+            res["distmat"][0] = (x[:, None, :, None, :] - x[None, :, None, :, :]).norm(dim=-1).float()
     return res

@@ -536,16 +536,23 @@ def angular_encoding(x, num_funcs):
     return enc.flatten(-2)
 
 
-def _mlp(x, sd, prefix, idxs):
+def _mlp(x, sd, prefix, idxs, relu_last=False, preacts=None):
+    """Linear layers with a ReLU between them (and after the last one: relu_last).  preacts (dict, optional) receives, by layer name, every
+    ReLU's pre-activation z = x W^T + b and the magnitude its rounding scales with, |x| |W|^T + |b| (both detached): tests use them to keep
+    cotangents off the rows where fp32 rounding can put z on the other side of the kink."""
     for n, i in enumerate(idxs):
-        x = x @ sd[f"{prefix}{i}.weight"].to(x.dtype).T + sd[f"{prefix}{i}.bias"].to(x.dtype)
-        if n + 1 < len(idxs):
+        xin, W, bias = x, sd[f"{prefix}{i}.weight"].to(x.dtype), sd[f"{prefix}{i}.bias"].to(x.dtype)
+        x = xin @ W.T + bias
+        if n + 1 < len(idxs) or relu_last:
+            if preacts is not None:
+                with torch.no_grad():
+                    preacts[f"{prefix}{i}"] = (x.detach(), xin.abs() @ W.abs().T + bias.abs())
             x = torch.relu(x)
     return x
 
 
 def residue_embedding(sd, seq_idx, xyz, orientation, dihedrals, chain_idx, atom_mask, structure_context_mask=None,
-                      sequence_context_mask=None, prefix="residue_context_embedding."):
+                      sequence_context_mask=None, prefix="residue_context_embedding.", preacts=None):
     """ResidueEmbedding.forward  (diffab_pytorch.py:81-183)"""
     B, L, A, _ = xyz.shape
     if sequence_context_mask is not None:
@@ -563,11 +570,11 @@ def residue_embedding(sd, seq_idx, xyz, orientation, dihedrals, chain_idx, atom_
         dih = dih * dmask[:, :, None]
     chain = sd[prefix + "chain_embedding.weight"][chain_idx]
     x = torch.cat([aa, coord, dih, chain], dim=-1)
-    return _mlp(x, sd, prefix + "mlp.", (0, 2, 4, 6))
+    return _mlp(x, sd, prefix + "mlp.", (0, 2, 4, 6), preacts=preacts)
 
 
 def pair_embedding(sd, seq_idx, distmat, dihedrals, residue_idx, chain_idx, atom_mask, structure_context_mask=None,
-                   sequence_context_mask=None, max_dist=32, prefix="pair_context_embedding."):
+                   sequence_context_mask=None, max_dist=32, prefix="pair_context_embedding.", preacts=None):
     """PairEmbedding.forward  (diffab_pytorch.py:220-312).  The structure-context mask is multiplied into `distmat` only
     after its last use (:295-301), so it does not reach the output: accepted and ignored, like the reference's effect."""
     B, L = seq_idx.shape
@@ -584,21 +591,21 @@ def pair_embedding(sd, seq_idx, distmat, dihedrals, residue_idx, chain_idx, atom
     rel_feat = sd[prefix + "relpos_embedding.weight"][rel + max_dist] * same_chain[:, :, :, None]
     coef = torch.nn.functional.softplus(sd[prefix + "pair2distcoef.weight"][sp])
     dm = torch.exp(-1 * coef * distmat.reshape(B, L, L, A * A) ** 2)
-    dist_feat = torch.relu(_mlp(dm * am_pair, sd, prefix + "distance_embedding.", (0, 2)))
+    dist_feat = _mlp(dm * am_pair, sd, prefix + "distance_embedding.", (0, 2), relu_last=True, preacts=preacts)
     dih = angular_encoding(dihedrals, 2)
     x = torch.cat([sp_feat, rel_feat.expand(B, L, L, -1), dist_feat, dih], dim=-1)
-    return _mlp(x, sd, prefix + "mlp.", (0, 2, 4)) * rmask_pair[:, :, :, None]
+    return _mlp(x, sd, prefix + "mlp.", (0, 2, 4), preacts=preacts) * rmask_pair[:, :, :, None]
 
 
-def encode_context(sd, batch, generate_structure=True, generate_sequence=True, max_dist=32):
-    """DiffAb.encode_context  (diffab_pytorch.py:680-724)"""
+def encode_context(sd, batch, generate_structure=True, generate_sequence=True, max_dist=32, preacts=None):
+    """DiffAb.encode_context  (diffab_pytorch.py:680-724); preacts: see _mlp"""
     ctx = batch["residue_mask"].bool() & (~batch["generation_mask"].bool())
     sm = ctx if generate_structure else None
     qm = ctx if generate_sequence else None
     res = residue_embedding(sd, batch["seq_idx"], batch["xyz"], batch["orientations"], batch["backbone_dihedrals"], batch["chain_idx"],
-                            batch["atom_mask"], sm, qm)
+                            batch["atom_mask"], sm, qm, preacts=preacts)
     pair = pair_embedding(sd, batch["seq_idx"], batch["distmat"], batch["pairwise_dihedrals"], batch["residue_idx"], batch["chain_idx"],
-                          batch["atom_mask"], sm, qm, max_dist)
+                          batch["atom_mask"], sm, qm, max_dist, preacts=preacts)
     return res, pair
 
 

@@ -581,6 +581,38 @@ def main():
         ol[f"{red}/value"], ol[f"{red}/cot"], ol[f"{red}/d_pred"], ol[f"{red}/d_target"] = npf(val), npf(cot), npf(pr.grad), npf(tr.grad)
     np.savez_compressed(os.path.join(GOLD, "orientation_loss_grads.npz"), pred=npf(Rp), target=npf(Rt), **ol)
 
+    # ---------------------------------------------------------------- encode_context at other n_atoms / max_dist_to_consider
+    # The DiffAb constructor's n_atoms and max_dist_to_consider, chain ids up to 9 (chain products up to 81), a (B, K) residue_idx with
+    # gaps wide enough to clamp both ways, and patch 0's tail padded as collate_fn pads it.  Runs last: the sections above are unchanged.
+    print("encode_context at n_atoms / max_dist_to_consider = 4 / 8 and 17 / 40, chains 0..9, per-patch residue_idx")
+    Dw, Cw, Kw, Bw, npad = 32, 16, 24, 2, 4
+    wide = {"meta": np.array([Bw, Kw, Dw, Cw, npad])}
+    for si, (A_, md_, seed_) in enumerate(((4, 8, 43), (17, 40, 44))):
+        ref_model = rmod.DiffAb(Dw, Cw, 1, 12, 4, 4, 8, n_atoms=A_, max_dist_to_consider=md_).eval()
+        csd = syn.context_state_dict(Dw, Cw, A_, md_, seed=seed_)
+        missing = ref_model.load_state_dict(csd, strict=False)
+        assert not missing.unexpected_keys and all(k.startswith("denoiser.") for k in missing.missing_keys)
+        cb = syn.context_batch(Bw, Kw, A_, seed=seed_, max_chain=9, per_patch_residue_idx=True, n_pad=npad)
+        span = cb["residue_idx"][:, :, None] - cb["residue_idx"][:, None, :]
+        assert int(span.max()) > md_ and not torch.equal(cb["residue_idx"][0], cb["residue_idx"][1])
+        wide[f"setting{si}"] = np.array([A_, md_, seed_])
+        for gs in (True, False):
+            for gq in (True, False):
+                with torch.no_grad():
+                    res_ref, pair_ref = ref_model.encode_context(cb["seq_idx"], cb["xyz"], cb["orientations"], cb["backbone_dihedrals"],
+                                                                 cb["distmat"].clone(), cb["pairwise_dihedrals"], cb["atom_mask"],
+                                                                 cb["chain_idx"], cb["residue_idx"], cb["generation_mask"], cb["residue_mask"],
+                                                                 generate_structure=gs, generate_sequence=gq)
+                res_o, pair_o = orc.encode_context(csd, cb, gs, gq, max_dist=md_)
+                check(f"A={A_} md={md_} res  gs={gs} gq={gq}", res_o, res_ref, 2e-6)
+                check(f"A={A_} md={md_} pair gs={gs} gq={gq}", pair_o, pair_ref, 2e-6)
+                wide[f"res_{si}_{int(gs)}{int(gq)}"] = npf(res_ref)
+                if gs:  # the structure-context mask does not reach the pair embedding (checked here): one pair output per gq
+                    wide[f"pair_{si}_{int(gq)}"] = npf(pair_ref)
+                else:
+                    assert np.array_equal(npf(pair_ref), wide[f"pair_{si}_{int(gq)}"])
+    np.savez_compressed(os.path.join(GOLD, "encode_context_wide.npz"), **wide)
+
     tot = sum(os.path.getsize(os.path.join(GOLD, f)) for f in os.listdir(GOLD))
     print(f"wrote {len(os.listdir(GOLD))} fixtures, {tot/1024:.0f} KiB, under {GOLD}")
 

@@ -173,6 +173,27 @@ def test_encode_context_oracle_vs_golden(golden):
     assert not np.allclose(g["pair_11"], g["pair_10"]) and np.array_equal(g["pair_11"], g["pair_01"])
 
 
+def test_encode_context_wide_oracle_vs_golden(golden):
+    """encode_context at the DiffAb constructor's other n_atoms / max_dist_to_consider (4 / 8 and 17 / 40), chain ids up to 9, a (B, K)
+    residue_idx with gaps, patch 0 padded: the oracle's restatement of the atom count, the relative-position clamp and the chain product
+    against the reference, 4 flag combinations (tests/golden/encode_context_wide.npz)."""
+    g = golden("encode_context_wide")
+    Bw, Kw, Dw, Cw, npad = [int(v) for v in g["meta"]]
+    for si in range(2):
+        A_, md, seed = [int(v) for v in g[f"setting{si}"]]
+        sd = syn.context_state_dict(Dw, Cw, A_, md, seed=seed)
+        cb = syn.context_batch(Bw, Kw, A_, seed=seed, max_chain=9, per_patch_residue_idx=True, n_pad=npad)
+        # the inputs reach what the fixture is for: clamping both ways, rows that differ per patch, chain products past 9
+        rel = cb["residue_idx"][:, :, None] - cb["residue_idx"][:, None, :]
+        assert int(rel.max()) > md and int(rel.min()) < -md and cb["residue_idx"].shape == (Bw, Kw)
+        assert int((cb["chain_idx"][:, :, None] * cb["chain_idx"][:, None, :]).max()) == 81 and int(cb["chain_idx"][0, -1]) == 0
+        for gs in (True, False):
+            for gq in (True, False):
+                res, pair = orc.encode_context(sd, cb, gs, gq, max_dist=md)
+                assert maxrel(res, g[f"res_{si}_{int(gs)}{int(gq)}"]) < 2e-6, (A_, md, gs, gq)
+                assert maxrel(pair, g[f"pair_{si}_{int(gq)}"]) < 2e-6, (A_, md, gs, gq)
+
+
 def test_featurize_xyz_definitions():
     """SURVEY 8 row f2 (parity with protstruc UNPINNED): the oracle's geometric definitions against known answers - frames are
     the exact inverse of io.backbone_from_frames, a trans / cis / +90 degree dihedral, and the chain-break mask."""
