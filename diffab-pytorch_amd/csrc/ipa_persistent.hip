@@ -9,6 +9,9 @@
 // started together by 18 separate launches, all 256 CUs stream their pair rows in the same 13-15 us and leave HBM idle for the next 25
 // (profiles/r03_lockstep.md); here the first items are staggered once per launch and nothing ever re-aligns them.
 //
+// K = 128: to_out hands its 128 x 128 output tile to the next layer's projections through LDS (the tile's fp32 values, read back by the
+// projections instead of from global memory); only the last layer writes it to global memory, where the heads and the caller read it.
+//
 // Same tile bodies, same arithmetic, same summation orders as the multi-launch path: results are bitwise the same (tested), and with
 // them the sampler's shard invariance.
 #include "common.h"
@@ -25,10 +28,15 @@ namespace {
 constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
 constexpr size_t kModuleLdsBytes = cmax(cmax(ipa_attn_lds_bytes(8), static_cast<size_t>(kChainLdsBytes)),
                                         cmax(static_cast<size_t>(pjh3::PJ_LDS_BYTES), static_cast<size_t>(h3tile::lds_bytes<128>())));
+// K = 128: to_out's output tile, kept for the next layer's projections, behind the LDS of both dense tiles (floats)
+constexpr size_t kXImageOffset = cmax(static_cast<size_t>(pjh3::PJ_LDS_BYTES), static_cast<size_t>(h3tile::lds_bytes<128>())) / 4;
+static_assert(kXImageOffset * 4 + h3tile::y_lds_bytes<128>() <= kModuleLdsBytes, "module LDS: no room for the x image of the dense phases");
+static_assert(kModuleLdsBytes <= 160 * 1024, "module LDS: one work-group per CU within gfx950's 160 KiB");
+static_assert(kXImageOffset % 4 == 0, "x image: 16-byte aligned rows");
 
 struct ModuleArgs {
   float* xa;                 // [B K][128]: the module's input (layer 0 reads it), then every odd layer's output
-  float* xb;                 // [B K][128]: every even layer's output; the result is in (NL odd ? xb : xa)
+  float* xb;                 // [B K][128]: every even layer's output; the result is in (NL odd ? xb : xa) (K = 128: the last layer's only)
   float* proj;               // [B K][1344] workspace
   float* feat;               // [B K][1024] workspace
   const float* pair;         // fp16 planes of the pair embedding (launch_pair_split)
@@ -91,9 +99,25 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
       for (int dt = 0; dt < DT; ++dt) {  // ---- the six projections + frames of the patch's rows, 128 at a time
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));  // (an opaque copy per phase: lane-constant addresses must not stay live across the phases)
-        pjh3::proj_frames_h3_tile<true, false>(reinterpret_cast<_Float16*>(lds), tid, b * DT + dt, 0, 1, xin,
-                                               reinterpret_cast<const _Float16*>(lp + a.pj_off), reinterpret_cast<const float*>(lp + a.wis_off),
-                                               a.R, a.t, a.proj, M);
+        if (KRES == 128) {  // x: the previous layer's to_out tile, still in LDS; layer 0 stages the module's input rows there first
+          if (l == 0) {
+            float* xl = lds + kXImageOffset;
+            for (int i = tid; i < 128 * 32; i += 512) {
+              const int row = i >> 5, c4 = 4 * (i & 31);
+              *reinterpret_cast<float4*>(xl + row * h3tile::Y_LDS_LD + c4) =
+                  *reinterpret_cast<const float4*>(xin + (static_cast<int64_t>(b) * 128 + row) * 128 + c4);
+            }
+            __syncthreads();
+          }
+          pjh3::proj_frames_h3_tile<true, false, true, true>(reinterpret_cast<_Float16*>(lds), tid, b, 0, 1, nullptr,
+                                                             reinterpret_cast<const _Float16*>(lp + a.pj_off),
+                                                             reinterpret_cast<const float*>(lp + a.wis_off), a.R, a.t, a.proj, M, 0, 0, 0,
+                                                             lds + kXImageOffset);
+        } else {
+          pjh3::proj_frames_h3_tile<true, false>(reinterpret_cast<_Float16*>(lds), tid, b * DT + dt, 0, 1, xin,
+                                                 reinterpret_cast<const _Float16*>(lp + a.pj_off), reinterpret_cast<const float*>(lp + a.wis_off),
+                                                 a.R, a.t, a.proj, M);
+        }
         if (dt + 1 < DT) {  // the next tile's weight stages overwrite this one's LDS
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           __syncthreads();
@@ -115,9 +139,15 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
       for (int dt = 0; dt < DT; ++dt) {  // ---- to_out
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        h3tile::rowgemm128_h3_tile<false, 128>(reinterpret_cast<_Float16*>(lds), tid, b * DT + dt, a.feat, AF,
-                                               reinterpret_cast<const _Float16*>(lp + a.out_off),
-                                               reinterpret_cast<const float*>(lp + a.wis_off) + ANP, small + 576, nullptr, 0, xout, 128, M, AF);
+        if (KRES == 128)  // the tile stays in LDS for the next layer; the last layer's goes to global memory only
+          h3tile::rowgemm128_h3_tile<false, 128, false, true>(reinterpret_cast<_Float16*>(lds), tid, b, a.feat, AF,
+                                                              reinterpret_cast<const _Float16*>(lp + a.out_off),
+                                                              reinterpret_cast<const float*>(lp + a.wis_off) + ANP, small + 576, nullptr, 0,
+                                                              l + 1 == a.NL ? xout : nullptr, 128, M, AF, 0, nullptr, lds + kXImageOffset);
+        else
+          h3tile::rowgemm128_h3_tile<false, 128>(reinterpret_cast<_Float16*>(lds), tid, b * DT + dt, a.feat, AF,
+                                                 reinterpret_cast<const _Float16*>(lp + a.out_off),
+                                                 reinterpret_cast<const float*>(lp + a.wis_off) + ANP, small + 576, nullptr, 0, xout, 128, M, AF);
         if (dt + 1 < DT) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
           __syncthreads();

@@ -39,13 +39,16 @@ __device__ __forceinline__ float mul1(float a, float b) {
 // One 128-row tile (rows tile_m * 128 ..).  512 threads; pj_lds: PJ_LDS_BYTES, 16-byte aligned; Wc: stage-ordered planes of pjsplit_h3
 // ([(block 2 + k half)][2 planes][96][64] fp16), wis[1344]: 1 / scale of every output column; split_i of split_n work-groups share the
 // column blocks of the tile (each re-reads the x rows).
+// X_LDS: the x rows are read from x_lds[128][h3tile::Y_LDS_LD] (LDS outside pj_lds: the image a rowgemm128_h3_tile<..., Y_LDS = true> left)
+// instead of from X.
 // PROJ = false (the backward's d feat = d y W_out, gemm_f16x3.hip launch_xstat_h3): the same x-stationary product for ANY number of output
 // columns - nb_rt blocks of 96 (planes and wis padded with zeros / ones), the first n_rt columns stored into rows of ldy_rt floats, no frames.
-template <bool FULL, bool SPLIT = false, bool PROJ = true>  // FULL: M is a multiple of 128, no row guards
+template <bool FULL, bool SPLIT = false, bool PROJ = true, bool X_LDS = false>  // FULL: M is a multiple of 128, no row guards
 __device__ __forceinline__ void proj_frames_h3_tile(_Float16* __restrict__ pj_lds, const int tid, const int tile_m, const int split_i,
                                                     const int split_n, const float* __restrict__ X, const _Float16* __restrict__ Wc,
                                                     const float* __restrict__ wis, const float* __restrict__ R, const float* __restrict__ t,
-                                                    float* __restrict__ Y, int M, const int nb_rt = 0, const int n_rt = 0, const int ldy_rt = 0) {
+                                                    float* __restrict__ Y, int M, const int nb_rt = 0, const int n_rt = 0, const int ldy_rt = 0,
+                                                    const float* __restrict__ x_lds = nullptr) {
   const int NB = PROJ ? PJ_NB : nb_rt, ldy = PROJ ? PJ_NP : ldy_rt, frames_from = PROJ ? PJ_GQ / PJ_B : NB;
   const int blk0 = SPLIT ? (NB * split_i) / split_n : 0;
   const int blk1 = SPLIT ? (NB * (split_i + 1)) / split_n : NB;
@@ -88,7 +91,8 @@ __device__ __forceinline__ void proj_frames_h3_tile(_Float16* __restrict__ pj_ld
     for (int q = 0; q < 4; ++q) {
       v[q][0] = v[q][1] = f32x4{0.f, 0.f, 0.f, 0.f};
       if (FULL || row < M) {
-        const float* xp = X + static_cast<int64_t>(row) * 128 + 32 * q + 8 * g;
+        const float* xp = X_LDS ? x_lds + (row - m0) * h3tile::Y_LDS_LD + 32 * q + 8 * g
+                                : X + static_cast<int64_t>(row) * 128 + 32 * q + 8 * g;
         v[q][0] = *reinterpret_cast<const f32x4*>(xp);
         v[q][1] = *reinterpret_cast<const f32x4*>(xp + 4);
       }

@@ -38,14 +38,20 @@ __device__ __forceinline__ void split2(float x, _Float16& h1, _Float16& h2) {
 template <int ROWS>
 constexpr int lds_bytes() { return 2 * 2 * (128 + ROWS) * BK * 2 + 2 * ROWS * 4; }  // W and X planes (two buffers), X pair scales (two pairs)
 
+// Output tile kept on chip (ipa_persistent.hip: to_out -> the next layer's projections): y_lds[ROWS][Y_LDS_LD] fp32, written by the
+// epilogue.  The stride makes the reader's ds_read_b128 of 16 rows x 16 bytes (proj_frames_h3_tile's A fragments) conflict-free.
+constexpr int Y_LDS_LD = 132;
+template <int ROWS>
+constexpr int y_lds_bytes() { return ROWS * Y_LDS_LD * 4; }
+
 // h3_lds: lds_bytes<ROWS>() bytes, 16-byte aligned; ROWS * 4 threads; Wc: planes of wsplit128_h3 ([chunk][2][128][32] fp16), wis[128]:
 // 1 / scale of the weight rows.  PARTIAL: ONE part (chunks [c_begin, c_begin + PART_CHUNKS)) as raw sums (before 2^-sw and the bias)
-// into part_out[ROWS][128].
-template <bool RELU, int ROWS, bool PARTIAL = false>
+// into part_out[ROWS][128].  Y_LDS: y also into y_lds[ROWS][Y_LDS_LD] (LDS outside h3_lds), and into Y only when Y is not null.
+template <bool RELU, int ROWS, bool PARTIAL = false, bool Y_LDS = false>
 __device__ __forceinline__ void rowgemm128_h3_tile(_Float16* h3_lds, int tid, int tile_m, const float* __restrict__ X, int ldx,
                                                    const _Float16* __restrict__ Wc, const float* __restrict__ wis, const float* __restrict__ bias,
                                                    const int64_t* __restrict__ bias_idx, int bias_div, float* __restrict__ Y, int ldy, int M, int Kd,
-                                                   int c_begin = 0, float* __restrict__ part_out = nullptr) {
+                                                   int c_begin = 0, float* __restrict__ part_out = nullptr, float* __restrict__ y_lds = nullptr) {
 #define H3TILE_FENCE() asm volatile("" ::: "memory")
   constexpr int T = ROWS * 4, NRW = ROWS / 32;
   _Float16* Ws = h3_lds;                          // [2 buf][2 planes][128][32]
@@ -199,6 +205,7 @@ __device__ __forceinline__ void rowgemm128_h3_tile(_Float16* h3_lds, int tid, in
     return;
   }
   const bool table = bias_idx != nullptr || bias_div > 0;
+  const bool y_global = !Y_LDS || Y != nullptr;
 #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
     const int col = 64 * cw + 32 * tt + l31;
@@ -214,7 +221,8 @@ __device__ __forceinline__ void rowgemm128_h3_tile(_Float16* h3_lds, int tid, in
       }
       float o = __builtin_fmaf(tot[tt][r], wi, bv);
       if (RELU) o = fmaxf(o, 0.f);
-      Y[static_cast<int64_t>(row) * ldy + col] = o;
+      if (Y_LDS) y_lds[(row - m0) * Y_LDS_LD + col] = o;
+      if (y_global) Y[static_cast<int64_t>(row) * ldy + col] = o;
     }
   }
 #undef H3TILE_FENCE

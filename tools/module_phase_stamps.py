@@ -1,0 +1,67 @@
+"""Diagnostic: the phases of the patch-resident module launch (ipa_persistent.hip) per patch and layer, from its phase stamps
+(diffab_debug_set_module_stamps: four chip-clock stamps per (patch, layer) - projections start, attention start, to_out start, to_out
+end; never enabled in production).  Runs reverse steps of the benchmark model (bench.py's geometry: B = 256, K = 128, six layers) and
+prints the per-phase times of the last step's launch in microseconds.
+usage: module_phase_stamps.py [steps] [json_out] ; DIFFAB_HIP_LIB selects the build (A/B of two builds: run this once per build)"""
+import ctypes as C
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
+import torch  # noqa: E402
+
+from diffab_pytorch import DiffAb, _hip, synthetic as syn  # noqa: E402
+
+STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+OUT = sys.argv[2] if len(sys.argv) > 2 else None
+B, K, NTILE = 256, 128, 128 // 16
+TICK_US = 0.01  # s_memrealtime: 100 MHz
+lib = _hip.lib()
+dims = dict(syn.BENCH_DIMS)
+NL = dims["NL"]
+torch.manual_seed(0)
+model = DiffAb(dims["D"], dims["C"], NL, dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
+inp = {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=0, coord_sigma=10.0).items()}
+hd, w = model.denoiser.hip_dims(B, K), model.denoiser.hip_weights()
+sd_dev, tab = model._sched_on_device(), model._reverse_so3().struct()
+ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(hd)))
+gm, rc, pc = inp["generation_mask"], inp["res_context_emb"], inp["pair_context_emb"]
+# [B NL NTILE items][8 waves][8] attention-item stamps, then [B][NL][4] phase stamps
+stamps = torch.zeros(B * NL * NTILE * 64 + B * NL * 4, dtype=torch.int64, device="cuda")
+seq, x, O = inp["seq_idx"].clone(), inp["translations"].clone(), inp["orientations"].clone()
+_hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), 2024, 0, B, K, model.T, _hip.stream_ptr()), "init")
+lib.diffab_debug_set_module_stamps(_hip.ptr(stamps))
+try:
+    # flags 0: the sampler's own choice, the module launch at this batch (checked below: a per-layer path leaves the stamps at zero)
+    _hip.check(lib.diffab_sample_loop(C.byref(hd), C.byref(w.struct), C.byref(sd_dev.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                      _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), _hip.ptr(gm), 2024, 0, model.T, model.T - STEPS, _hip.ptr(ws),
+                                      ws.numel(), 0, _hip.stream_ptr()), "sample_loop")
+    torch.cuda.synchronize()
+finally:
+    lib.diffab_debug_set_module_stamps(None)
+ph = stamps[B * NL * NTILE * 64:].view(B, NL, 4).cpu().double()
+if not bool((ph > 0).all()):
+    sys.exit("module phase stamps missing: the module launch did not run for every (patch, layer)")
+proj = (ph[:, :, 1] - ph[:, :, 0]) * TICK_US
+attn = (ph[:, :, 2] - ph[:, :, 1]) * TICK_US
+to_out = (ph[:, :, 3] - ph[:, :, 2]) * TICK_US
+layer = (ph[:, :, 3] - ph[:, :, 0]) * TICK_US
+res = {"lib": _hip.LIB_PATH, "B": B, "K": K, "NL": NL, "steps": STEPS}
+print(f"{_hip.LIB_PATH}: last of {STEPS} steps, {B} patches x {NL} layers (us per patch-layer: mean | median | p10 - p90)")
+for name, v in (("projections", proj), ("attention (8 items)", attn), ("to_out", to_out), ("dense (proj + to_out)", proj + to_out),
+                ("layer", layer)):
+    f = v.flatten()
+    q = torch.quantile(f, torch.tensor([0.1, 0.5, 0.9], dtype=f.dtype))
+    print(f"  {name:22s} {float(f.mean()):8.2f} | {float(q[1]):8.2f} | {float(q[0]):8.2f} - {float(q[2]):8.2f}")
+    res[name] = {"mean": float(f.mean()), "median": float(q[1]), "p10": float(q[0]), "p90": float(q[2]),
+                 "mean_by_layer": [float(m) for m in v.mean(0)]}
+for name in ("projections", "to_out"):
+    print(f"  {name} by layer: " + " ".join(f"{m:.2f}" for m in res[name]["mean_by_layer"]))
+launch = float(ph[:, -1, 3].max() - ph[:, 0, 0].min()) * TICK_US
+res["first_stamp_to_last_us"] = launch
+print(f"  first projections start -> last to_out end: {launch:.1f} us")
+if OUT:
+    with open(OUT, "w") as fh:
+        json.dump(res, fh, indent=1)
