@@ -11,6 +11,12 @@ all-gather of the sampled structures at the end of the timed region.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     ... bench.py --train [--gpus N]        BASELINE config 4 (training step, 128 patches per GPU, gradient all-reduce) instead
     ... bench.py --dump-outputs DIR        + what the last timed step computed, as DIR/<name>.npy (same arguments: same inputs)
+    ... bench.py --full                    + every measurement beyond the headline (below)
+
+A plain run does what its headline needs: set-up, --warmup steps, the --steps timed steps, the dump, the result line.  --full adds the
+legs that take runs or tools of their own: the rocm-smi clock readings around the timed region, the attention tile's own launch
+(`roofline_attention_launch`), and at N = 1 the other BASELINE configurations (`other_configs`) and the CPU baseline
+(`cpu_baseline`); with --train, the contexts-constant leg (`contexts_constant`).
 
 Prints ONE JSON line on rank 0 (contract: task prompt section 4).
 """
@@ -407,8 +413,8 @@ def train_bench(args, model, dims, rank, world, dist):
     """BASELINE config 4: B patches per GPU (1024 = 8 x 128), one training step = forward noise + taped denoise forward + three
     losses + HIP backward + all-reduce of the gradient buckets (in place, RCCL) + Adam.  The measured step (`value`) follows SURVEY
     8(d)'s definition: the contexts are grad-requiring inputs, so the backward also produces d pair_ctx (107 MB of algorithmic
-    traffic per patch-step).  The same step with constant contexts (no d pair_ctx: 56.6 MB per patch-step) is timed behind it and
-    reported as `contexts_constant` with its own roofline fraction."""
+    traffic per patch-step).  With --full, the same step with constant contexts (no d pair_ctx: 56.6 MB per patch-step) is timed
+    behind it and reported as `contexts_constant` with its own roofline fraction."""
     from diffab_pytorch import _hip, distributed as D, synthetic as syn
 
     B, K = args.batch, args.k
@@ -459,15 +465,14 @@ def train_bench(args, model, dims, rank, world, dist):
         grads = torch.cat([p.grad.reshape(-1) for p in model.parameters() if p.grad is not None])
         dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1), "param_grads": grads,
                                          "pair_context_grad": batch["pair_context_emb"].grad})
-    elapsed_const = timed(False)
+    elapsed_const = timed(False) if args.full else None
     in_place = all(p.grad is None or any(f is not None and p.grad.untyped_storage().data_ptr() == f.untyped_storage().data_ptr()
                                          for f in model.gradient_buckets()) for p in model.denoiser.parameters())
     if rank == 0:
         value = world * B * K * args.steps / elapsed
         by, by_c = train_bytes_per_patch(K, dims, True), train_bytes_per_patch(K, dims, False)
         achieved = value / world / K * by / 1e9
-        value_c = world * B * K * args.steps / elapsed_const
-        print(json.dumps({
+        out = {
             "metric": "CDR-residue training-steps/sec (K=128 patch, forward + backward + Adam)", "value": value, "unit": "residue-steps/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -479,12 +484,15 @@ def train_bench(args, model, dims, rank, world, dist):
             "roofline": {"kernel": "whole training step (no single dominant kernel: profiles/r04_train_kernel_stats.csv)", "bound": "hbm",
                          "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
                          "algorithmic_bytes_per_patch_step": by},
-            "contexts_constant": {"what": "the same step with constant contexts (no d pair_ctx)", "ms_per_step": elapsed_const / args.steps * 1e3,
-                                  "residue_steps_per_s": value_c, "algorithmic_bytes_per_patch_step": by_c,
-                                  "hbm_frac": value_c / world / K * by_c / 1e9 / HBM_PEAK_GBPS},
             "d_pair_ctx_computed": bool(had_dpair),
             "loss_finite": bool(torch.isfinite(loss.detach()).item()), "gradients_reduced_in_place": bool(in_place),
-        }), flush=True)
+        }
+        if elapsed_const is not None:
+            value_c = world * B * K * args.steps / elapsed_const
+            out["contexts_constant"] = {"what": "the same step with constant contexts (no d pair_ctx)", "ms_per_step": elapsed_const / args.steps * 1e3,
+                                        "residue_steps_per_s": value_c, "algorithmic_bytes_per_patch_step": by_c,
+                                        "hbm_frac": value_c / world / K * by_c / 1e9 / HBM_PEAK_GBPS}
+        print(json.dumps(out), flush=True)
 
 
 def main():
@@ -494,10 +502,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="patches per GPU")
     ap.add_argument("--k", type=int, default=128, help="residues per patch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the measurements that take runs or tools of their own: rocm-smi clocks, the attention "
+                         "launch's own roofline, the other BASELINE configurations and the CPU baseline (N=1), --train's contexts-constant leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of host time for the CPU baseline cases")
     ap.add_argument("--generic", action="store_true", help="force the generic (non-MFMA) kernels")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short BASELINE config 4 / 5 measurements (N=1 only)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short BASELINE config 4 / 5 measurements (N=1 only)")
     ap.add_argument("--train", action="store_true",
                     help="BASELINE config 4 instead of the sampling headline: training steps (noise + taped forward + 3 losses + HIP "
                          "backward + gradient all-reduce over RCCL + Adam), 128 patches per GPU unless --batch is given")
@@ -603,7 +614,7 @@ def main():
     # read before the warm-up: the GPU idles while rocm-smi runs, and the steps right after that gap are slower.  Measured with
     # --repeats 5 --steps 100: read here, the first 20-step block carries 0.3-0.5 ms more than the others; read right before the timed
     # region, 2.3 ms more (2.59 against 2.48 ms per step), which a single timed block would put straight into ms_per_step
-    clocks_before = gpu_clocks() if rank == 0 else None
+    clocks_before = gpu_clocks() if rank == 0 and args.full else None
     t_next = run_steps(args.warmup, model.T)
     if dist is not None:  # untimed: RCCL sets up its channels / buffers on the first collective of each kind
         gather_samples({"seq_idx": seq, "translations": x, "orientations": O}, dist)
@@ -632,15 +643,15 @@ def main():
     launches, total_ms = C.c_int64(0), C.c_double(0.0)
     _hip.check(lib.diffab_kernel_timer_read(C.byref(launches), C.byref(total_ms)), "kernel_timer_read")
     lib.diffab_kernel_timer_enable(0)
-    clocks_after = gpu_clocks() if rank == 0 else None
+    clocks_after = gpu_clocks() if rank == 0 and args.full else None
     assert samples["translations"].shape[0] == world * B
     finite = bool(torch.isfinite(x).all() and torch.isfinite(O).all())
     # Which kernel the timer bracketed: the sampler runs the IPA module as ONE patch-resident launch per step when the batch fills the
     # chip (csrc/ipa_persistent.hip; bitwise the per-layer launches), else one attention launch per layer.  In the first case the
-    # attention tile body is also timed as its own launch (DIFFAB_FLAG_MULTI_LAUNCH, 20 untimed-for-`value` steps) for comparison.
+    # attention tile body is also timed as its own launch (DIFFAB_FLAG_MULTI_LAUNCH, 20 untimed-for-`value` steps) for comparison (--full).
     module_form = launches.value == args.steps
     attn_alone = None
-    if module_form and rank == 0 and not args.generic:
+    if module_form and rank == 0 and not args.generic and args.full:
         fl2 = flags | _hip.FLAG_MULTI_LAUNCH
         t_ = model.T
         for n_, timed in ((5, False), (20, True)):
@@ -685,7 +696,6 @@ def main():
             "ms_per_step_runs": [r * 1e3 for r in runs],
             "ms_per_step_min": min(runs) * 1e3,
             "ms_per_step_median": step_s * 1e3,
-            "gpu_clocks": {"before": clocks_before, "after": clocks_after},
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -727,6 +737,8 @@ def main():
             "outputs_finite": finite,
             "input_gen_s": t_gen,
         }
+        if args.full:
+            out["gpu_clocks"] = {"before": clocks_before, "after": clocks_after}
         if attn_alone is not None:
             a1 = algorithmic_bytes_per_attention_launch(B, K, dims["D"], dims["C"])
             out["roofline_attention_launch"] = {
@@ -736,9 +748,9 @@ def main():
                 "frac": a1 / (attn_alone[1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, "launches": attn_alone[0], "avg_launch_ms": attn_alone[1],
                 "algorithmic_bytes_per_launch": a1, "ms_per_step_of_this_form": attn_alone[2],
             }
-        if world == 1 and not args.no_other_configs and not args.generic:
+        if args.full and world == 1 and not args.no_other_configs and not args.generic:
             out["other_configs"] = other_configs(model, dims, flags)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             torch.manual_seed(0)
             sd = {k: v.detach().cpu() for k, v in model.denoiser.state_dict().items()}
             out["cpu_baseline"] = cpu_baseline(dims, sd, K, seed=seed, budget_s=args.cpu_budget)

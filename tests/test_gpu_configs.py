@@ -394,18 +394,22 @@ def _bench_dump(tmp_path, name, *args):
 
 def test_bench_times_exactly_steps_and_dumps_the_last_timed_step(tmp_path):
     """bench.py --dump-outputs on the sampling headline at B = 256, where the sampler takes the patch-resident module launch and bench.py
-    runs 20 more steps on the same buffers after the timed region: the timed region holds exactly --steps steps (the kernel timer's
+    --full runs 20 more steps on the same buffers after the timed region: the timed region holds exactly --steps steps (the kernel timer's
     launches: one module launch per step, or NL attention launches with --multi-launch), two runs with the same arguments write the same
-    arrays bit for bit, and the per-layer form, which runs no extra steps, writes them too (the two forms are bitwise equal)."""
+    arrays bit for bit, the plain run, which runs no extra steps, writes them too, and so does the per-layer form (the two forms are
+    bitwise equal)."""
     B, K, steps, NL = 256, 128, 7, syn.BENCH_DIMS["NL"]
     common = ("--steps", str(steps), "--warmup", "2", "--batch", str(B), "--no-other-configs")
-    runs = [_bench_dump(tmp_path, "a", *common), _bench_dump(tmp_path, "b", *common),
-            _bench_dump(tmp_path, "multi", *common, "--multi-launch")]
-    for (out, _), launches in zip(runs, (steps, steps, steps * NL)):
+    runs = [_bench_dump(tmp_path, "a", *common, "--full"), _bench_dump(tmp_path, "b", *common, "--full"),
+            _bench_dump(tmp_path, "plain", *common), _bench_dump(tmp_path, "multi", *common, "--multi-launch")]
+    for (out, _), launches in zip(runs, (steps, steps, steps, steps * NL)):
         assert out["steps"] == steps and len(out["ms_per_step_runs"]) == 1 and out["outputs_finite"]
         assert out["roofline"]["launches"] == launches, (out["roofline"]["launches"], launches)
         assert abs(out["value"] - B * K / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
     assert "roofline_attention_launch" in runs[0][0]  # the extra steps after the timed region did run
+    assert "gpu_clocks" in runs[0][0]
+    for leg in ("roofline_attention_launch", "gpu_clocks", "other_configs", "cpu_baseline"):  # a plain run does only its headline
+        assert leg not in runs[2][0], leg
     a = runs[0][1]
     assert sorted(a) == ["orientations", "seq_idx", "translations"]
     assert a["seq_idx"].shape == (B, K) and a["translations"].shape == (B, K, 3) and a["orientations"].shape == (B, K, 3, 3)

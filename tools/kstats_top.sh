@@ -1,7 +1,8 @@
 #!/bin/bash
 # rocprofv3 kernel stats of a short bench run: the top kernels by total time (µs per launch).  usage: tools/kstats_top.sh [bench args]
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ks
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs "$@" > /tmp/ks_bench.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o run -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-other-configs "$@" > /tmp/ks_bench.json 2>/dev/null
 python3 - <<'PY'
 import csv, json
 rows = list(csv.DictReader(open("/tmp/ks/run_kernel_stats.csv")))

@@ -9,7 +9,7 @@ for a in "$@"; do
   case "$a" in --gpus|--gpus=*) echo "ktrace_kernel.sh: --gpus is not supported under rocprofv3" >&2; exit 2;; esac
 done
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/kt
-if ! rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o run -- python3 $R/bench.py --steps 6 --warmup 2 --repeats 1 --no-cpu-baseline --no-other-configs "$@" > /tmp/kt_bench.json 2>/tmp/kt_bench.err; then
+if ! rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o run -- python3 $R/bench.py --full --steps 6 --warmup 2 --repeats 1 --no-cpu-baseline --no-other-configs "$@" > /tmp/kt_bench.json 2>/tmp/kt_bench.err; then
   echo "ktrace_kernel.sh: the profiled bench run failed:" >&2; tail -5 /tmp/kt_bench.err >&2; exit 1
 fi
 python3 - "$pat" <<'PY'

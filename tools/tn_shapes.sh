@@ -2,7 +2,7 @@
 # On the GPU box: per-shape durations of the backward GEMM kernels in a short training run (rocprofv3 kernel trace).  usage: tools/tn_shapes.sh TAG
 R=$GRAFT_REPO_ROOT; tag=$1
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tn_$tag
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tn_$tag -o run -- python3 $R/bench.py --train --steps 3 --warmup 3 --no-cpu-baseline > /tmp/tn_$tag.log 2>&1 || { tail -5 /tmp/tn_$tag.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tn_$tag -o run -- python3 $R/bench.py --full --train --steps 3 --warmup 3 --no-cpu-baseline > /tmp/tn_$tag.log 2>&1 || { tail -5 /tmp/tn_$tag.log; exit 1; }
 python3 - <<PY
 import csv, collections
 rows=list(csv.DictReader(open('/tmp/tn_$tag/run_kernel_trace.csv')))

@@ -2,7 +2,7 @@
 # On the GPU box: grid / block sizes and mean durations of every kernel of a short training run (rocprofv3 kernel trace).  usage: tools/train_grids.sh
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tg
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tg -o run -- python3 $R/bench.py --train --steps 3 --warmup 3 --no-cpu-baseline > /tmp/tg.log 2>&1 || { tail -5 /tmp/tg.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/tg -o run -- python3 $R/bench.py --full --train --steps 3 --warmup 3 --no-cpu-baseline > /tmp/tg.log 2>&1 || { tail -5 /tmp/tg.log; exit 1; }
 python3 - <<PY
 import csv, collections
 rows=list(csv.DictReader(open('/tmp/tg/run_kernel_trace.csv')))
