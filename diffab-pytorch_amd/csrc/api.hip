@@ -614,6 +614,15 @@ int diffab_denoise_step_fwd(const diffab_dims* d, const diffab_denoiser_weights*
   return denoise_step(d, w, p, bias, seq_t, x_t, O_t, res_ctx, pair_ctx, out_eps, out_O0, out_posterior, out_logits, b, st);
 }
 
+// The taped forwards refuse dims whose backward cannot run (attn_bwd_lds_ok, the predicate run_backward checks), so that a training step
+// fails before anything is launched rather than inside the layer loop, after the heads' backward has been enqueued.
+static int check_attn_bwd_lds(const diffab_dims* d, const char* who) {
+  DIFFAB_REQUIRE(attn_bwd_lds_ok(d), DIFFAB_ERR_UNSUPPORTED,
+                 "%s: H*K = %d too large for the attention backward's LDS (%zu > %zu bytes; the forward alone reaches further)", who,
+                 d->H * d->K, attn_bwd_lds_bytes(d), kAttnBwdLdsMax);
+  return DIFFAB_OK;
+}
+
 size_t diffab_train_tape_bytes(const diffab_dims* d) {
   if (check_dims(d, "train_tape_bytes") || d->NL > kMaxLayers) return 0;
   return train_tape_floats(d) * sizeof(float);
@@ -632,6 +641,7 @@ int diffab_train_step_fwd(const diffab_dims* d, const diffab_denoiser_weights* w
   if (int rc = check_dims(d, "train_step_fwd")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
   DIFFAB_REQUIRE(d->NL <= kMaxLayers, DIFFAB_ERR_UNSUPPORTED, "train_step_fwd: at most %d IPA layers", kMaxLayers);
+  if (int rc = check_attn_bwd_lds(d, "train_step_fwd")) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && res_ctx && pair_ctx && beta && true_post && true_eps && true_O0 && gen_mask && res_mask && out_eps &&
                      out_O0 && out_posterior && losses3 && tape,
                  DIFFAB_ERR_ARG, "train_step_fwd: null pointer");
@@ -655,6 +665,7 @@ int diffab_train_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w
   if (int rc = check_denoiser_weights(d, w)) return rc;
   if (int rc = check_denoiser_weights(d, grads)) return rc;
   DIFFAB_REQUIRE(d->NL <= kMaxLayers, DIFFAB_ERR_UNSUPPORTED, "train_step_bwd: at most %d IPA layers", kMaxLayers);
+  if (int rc = check_attn_bwd_lds(d, "train_step_bwd")) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && pair_ctx && out_eps && out_O0 && out_posterior && true_post && true_eps && true_O0 && gen_mask &&
                      res_mask && upstream3 && tape && workspace,
                  DIFFAB_ERR_ARG, "train_step_bwd: null pointer");
@@ -674,6 +685,7 @@ int diffab_denoise_step_fwd_taped(const diffab_dims* d, const diffab_denoiser_we
   if (int rc = check_dims(d, "denoise_step_fwd_taped")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
   DIFFAB_REQUIRE(d->NL <= kMaxLayers, DIFFAB_ERR_UNSUPPORTED, "denoise_step_fwd_taped: at most %d IPA layers", kMaxLayers);
+  if (int rc = check_attn_bwd_lds(d, "denoise_step_fwd_taped")) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && res_ctx && pair_ctx && beta && out_eps && out_O0 && out_posterior && tape, DIFFAB_ERR_ARG,
                  "denoise_step_fwd_taped: null pointer");
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_fwd_taped: tape %zu < %zu bytes",
@@ -692,6 +704,7 @@ int diffab_denoise_step_bwd(const diffab_dims* d, const diffab_denoiser_weights*
   if (int rc = check_denoiser_weights(d, w)) return rc;
   if (int rc = check_denoiser_weights(d, grads)) return rc;
   DIFFAB_REQUIRE(d->NL <= kMaxLayers, DIFFAB_ERR_UNSUPPORTED, "denoise_step_bwd: at most %d IPA layers", kMaxLayers);
+  if (int rc = check_attn_bwd_lds(d, "denoise_step_bwd")) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && pair_ctx && out_posterior && d_res_ctx && tape && workspace, DIFFAB_ERR_ARG,
                  "denoise_step_bwd: null pointer");
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_bwd: tape too small");
@@ -724,6 +737,7 @@ int diffab_ipa_layer_fwd_taped(const diffab_dims* d, const diffab_ipa_layer_weig
   if (int rc = check_dims(d, "ipa_layer_fwd_taped")) return rc;
   DIFFAB_REQUIRE(x && (e || d->C == 0) && R && t && y && tape, DIFFAB_ERR_ARG, "ipa_layer_fwd_taped: null pointer");
   const diffab_dims d1 = one_layer(d);
+  if (int rc = check_attn_bwd_lds(&d1, "ipa_layer_fwd_taped")) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_fwd_taped: tape %zu < %zu bytes", tape_bytes,
                  train_tape_floats(&d1) * sizeof(float));
   const TrainTape tp = carve_tape(&d1, static_cast<float*>(tape));
@@ -748,6 +762,7 @@ int diffab_ipa_layer_bwd(const diffab_dims* d, const diffab_ipa_layer_weights* w
   if (int rc = check_dims(d, "ipa_layer_bwd")) return rc;
   DIFFAB_REQUIRE(w && grads && (e || d->C == 0) && R && t && dy && dx && tape && workspace, DIFFAB_ERR_ARG, "ipa_layer_bwd: null pointer");
   const diffab_dims d1 = one_layer(d);
+  if (int rc = check_attn_bwd_lds(&d1, "ipa_layer_bwd")) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_bwd: tape too small");
   DIFFAB_REQUIRE(workspace_bytes >= train_bwd_workspace_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_bwd: workspace %zu < %zu",
                  workspace_bytes, train_bwd_workspace_floats(&d1) * sizeof(float));

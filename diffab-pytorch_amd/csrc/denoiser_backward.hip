@@ -1726,6 +1726,11 @@ size_t train_bwd_workspace_floats(const diffab_dims* d) {
          bwd_planes_floats(d);
 }
 
+size_t attn_bwd_lds_bytes(const diffab_dims* d) {
+  const size_t H = d->H, F = H * d->DS + H * d->C + H * d->PV * 3 + H * d->PV;
+  return (3 * H * d->K + H * d->DS + H * d->PQ * 3 + H * d->PV * 3 + H + F) * sizeof(float);
+}
+
 // One backward driver, three roots:
 //   BWD_LOSSES      the three masked losses of diffab_pytorch.py:856-880 with upstream gradients upstream3 (the training step)
 //   BWD_COTANGENTS  arbitrary cotangents of the Denoiser outputs (cot_eps, cot_O0, cot_post; null = zero): Denoiser.forward under autograd
@@ -1840,10 +1845,11 @@ static int run_backward(int mode, const diffab_dims* d, const diffab_denoiser_we
                                    D, F, false, st, &side)) {
       return rc;
     }
-    const size_t lds = (3 * static_cast<size_t>(H) * d->K + H * DS + H * PQ * 3 + H * PV * 3 + H + F) * sizeof(float);
+    const size_t lds = attn_bwd_lds_bytes(d);
     const int vec = (DS % 4 == 0 && C % 4 == 0 && (PQ * 3) % 4 == 0 && (PV * 3) % 4 == 0 && H % 4 == 0 &&
                      (reinterpret_cast<uintptr_t>(pair_ctx) & 15) == 0 && (reinterpret_cast<uintptr_t>(lw->w_bias) & 15) == 0) ? 1 : 0;
-    DIFFAB_REQUIRE(lds <= 160 * 1024, DIFFAB_ERR_UNSUPPORTED, "attention backward: H*K too large for LDS (%zu bytes)", lds);
+    DIFFAB_REQUIRE(attn_bwd_lds_ok(d), DIFFAB_ERR_UNSUPPORTED, "attention backward: H*K too large for LDS (%zu > %zu bytes)", lds,
+                   kAttnBwdLdsMax);
     if (lds > 64 * 1024)
       DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_rows_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
@@ -1929,7 +1935,10 @@ static int run_backward(int mode, const diffab_dims* d, const diffab_denoiser_we
     } else if (d->K % JJm == 0 && JJm * lds2 <= 64 * 1024) {
       hipLaunchKernelGGL((ipa_attn_bwd_keys_mr_kernel<JJm>), dim3(rows / JJm), dim3(256), JJm * lds2, st, proj, lw->gamma, dfeat, At, Gt,
                          dogbuf, dproj, d->K, C, H, DS, PQ, PV);
-    } else {
+    } else {  // (lds2 < lds: within the limit checked above; past 64 KiB it needs the attribute, as the row kernel does)
+      if (lds2 > 64 * 1024)
+        DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_keys_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds2)));
       hipLaunchKernelGGL(ipa_attn_bwd_keys_kernel, dim3(rows), dim3(256), lds2, st, proj, lw->gamma, dfeat, At, Gt, dogbuf, dproj, d->K, C, H,
                          DS, PQ, PV);
     }

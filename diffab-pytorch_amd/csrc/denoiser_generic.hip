@@ -4,6 +4,11 @@
 // is served by the MFMA kernels in denoiser_fast.hip; this file is what every other geometry runs on
 // and the in-GPU cross-check for the fast path.
 //
+// Reach.  The forward's attention keeps one query row's H K logits in LDS: it runs while (H K + H (DS + 3 PQ + 3 PV)) floats fit in
+// 160 KiB (about H K <= 40 000).  The backward's row pass (ipa_attn_bwd_rows_kernel, denoiser_backward.hip) keeps three H K rows plus
+// the row's feature vectors (attn_bwd_lds_bytes): about H K <= 13 500 at small D.  Between the two bounds the forward (inference,
+// sampling, scoring) runs and training refuses: the taped forwards check attn_bwd_lds_ok before they launch anything.
+//
 // Reference: InvariantPointAttentionLayer.forward diffab_pytorch.py:389-465, Denoiser.forward :558-607.
 #include "common.h"
 #include "denoiser_internal.h"

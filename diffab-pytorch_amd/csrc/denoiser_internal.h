@@ -173,6 +173,11 @@ struct TrainTape {
 };
 size_t train_tape_floats(const diffab_dims* d);
 TrainTape carve_tape(const diffab_dims* d, float* base);
+// Dynamic LDS of the attention backward's row pass (ipa_attn_bwd_rows_kernel: 3 H K + the row's vectors, in bytes) and its limit.  The
+// one predicate of which dims the backward runs: run_backward refuses past it, and so do the taped forwards, before anything is launched.
+constexpr size_t kAttnBwdLdsMax = 160 * 1024;
+size_t attn_bwd_lds_bytes(const diffab_dims* d);
+inline bool attn_bwd_lds_ok(const diffab_dims* d) { return attn_bwd_lds_bytes(d) <= kAttnBwdLdsMax; }
 size_t train_bwd_workspace_floats(const diffab_dims* d);
 int train_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_denoiser_weights* g, const TrainTape& tp,
                    const int64_t* seq_t, const float* x_t, const float* O_t, const float* pair_ctx, const float* eps_hat,

@@ -839,7 +839,11 @@ class PairEmbedding(nn.Module):
 
 
 class DiffAb(_ModuleBase):
-    """Drop-in for ``diffab_pytorch.DiffAb`` on the diffusion hot path (reference diffab_pytorch.py:628-931)."""
+    """Drop-in for ``diffab_pytorch.DiffAb`` on the diffusion hot path (reference diffab_pytorch.py:628-931).
+
+    Any model dims run; the benchmark dims take the MFMA kernels, every other geometry the any-dims kernels.  The forward (denoise,
+    sample, score) reaches n_head * K of about 40 000; training (a backward) needs about three times the attention's LDS and stops at
+    n_head * K of about 13 500 (at most 16 IPA layers).  Past that the taped forward raises DiffabHipError before anything runs."""
 
     def __init__(self, d_residue_emb, d_pair_emb, n_ipa_layers, d_scalar_per_head, n_query_point_per_head, n_value_point_per_head, n_head,
                  T=100, s=0.01, beta_max=0.999, n_atoms=15, aa_vocab_size=21, max_dist_to_consider=32, lr=1e-4, weight_decay=0.0,
