@@ -810,6 +810,16 @@ int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights
                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                              const diffab_sample_record* rec, const diffab_sample_steps* steps, void* stream) {
+  return diffab_sample_loop_guided(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
+                                   t_stop, workspace, workspace_bytes, flags, allowed, rec, steps, nullptr, stream);
+}
+
+int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                              int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                              const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
+                              void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
@@ -887,6 +897,29 @@ int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights
     const int32_t* pd = static_cast<const int32_t*>(steps->plan_dev);
     pdev = StepPlanDev{pd, reinterpret_cast<const float*>(pd + (T + 1)), reinterpret_cast<const float*>(pd + 2 * (T + 1)), s->alpha_bar};
   }
+  // structure guidance: the potential's terms and per-residue tables are checked here; its kernel runs before every update
+  GuidanceDev gdev;
+  if (guidance != nullptr) {
+    if (int rc = check_guidance_terms(guidance, "sample_loop")) return rc;
+    DIFFAB_REQUIRE(guidance->max_shift > 0.0f, DIFFAB_ERR_ARG, "sample_loop: guidance max_shift = %g must be > 0 (INFINITY: no cap)",
+                   guidance->max_shift);
+    DIFFAB_REQUIRE(guidance->t_max >= 0 && guidance->t_max <= s->T, DIFFAB_ERR_ARG, "sample_loop: guidance t_max = %d outside [0, T = %d]",
+                   guidance->t_max, s->T);
+    DIFFAB_REQUIRE(guidance->shift_dev != nullptr, DIFFAB_ERR_ARG, "sample_loop: guidance needs shift_dev");
+    DIFFAB_REQUIRE(!(keep & DIFFAB_FLAG_KEEP_STRUCTURE), DIFFAB_ERR_ARG,
+                   "sample_loop: guidance moves the structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
+    DIFFAB_REQUIRE(s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: guidance needs the schedule's alpha_bar_sqrt");
+    gdev.shift = guidance->shift_dev;
+    gdev.chain = guidance->chain;
+    gdev.residue_idx = guidance->residue_idx;
+    gdev.residue_mask = guidance->residue_mask;
+    gdev.w_clash = guidance->w_clash;
+    gdev.clash_distance = guidance->clash_distance;
+    gdev.w_bond = guidance->w_bond;
+    gdev.bond_length = guidance->bond_length;
+    gdev.max_shift = guidance->max_shift;
+    gdev.t_max = guidance->t_max;
+  }
   // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
   // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
   const bool mapped = ctx_of_row != nullptr;
@@ -935,7 +968,7 @@ int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights
     if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev);
+                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev, gdev);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is

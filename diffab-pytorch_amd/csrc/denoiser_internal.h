@@ -255,6 +255,17 @@ struct StepPlanDev {
   const float* alpha = nullptr;   // alpha'_t
   const float* alpha_bar = nullptr;
 };
+// Structure guidance (diffab_sample_loop_guided), a by-value launch argument of the update kernel like the plan: shift == nullptr is
+// off.  launch_reverse_update_philox runs the guidance kernel first (Delta into shift), and the update subtracts Delta from the mean of
+// the translations at the steps t <= t_max.
+struct GuidanceDev {
+  float* shift = nullptr;                  // (B, K, 3) Delta of the step
+  const int32_t* chain = nullptr;          // (B, K)
+  const int32_t* residue_idx = nullptr;    // (B, K)
+  const uint8_t* residue_mask = nullptr;   // (B, K), nullable = all
+  float w_clash = 0.f, clash_distance = 0.f, w_bond = 0.f, bond_length = 0.f, max_shift = 0.f;
+  int32_t t_max = -1;
+};
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
@@ -262,7 +273,9 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  uint32_t keep = 0,   // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
                                  const uint32_t* allowed = nullptr,  // per-residue allowed-class words of the sequence draw (nullable)
                                  const SampleRecordDev& rec = SampleRecordDev{},  // trajectory recording (rec.slot nullable)
-                                 const StepPlanDev& plan = StepPlanDev{});  // fewer-step sampling (plan.next nullable)
+                                 const StepPlanDev& plan = StepPlanDev{},  // fewer-step sampling (plan.next nullable)
+                                 const GuidanceDev& guide = GuidanceDev{});  // structure guidance (guide.shift nullable)
+int check_guidance_terms(const diffab_sample_guidance* g, const char* who);  // weights, distances, chain / residue_idx (DIFFAB_ERR_ARG)
 // the residues that are not generated: their (constant) state in every slot of the record, and their predictions - the given x / O and a
 // one-hot of the token - once per call
 int launch_record_fixed(const SampleRecordDev& rec, const int64_t* seq, const float* x, const float* O, const uint8_t* gm, int B, int K, int V,

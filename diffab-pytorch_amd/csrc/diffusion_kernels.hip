@@ -2,6 +2,8 @@
 // All of these are per-residue elementwise work (KBs per patch): one thread per residue (or per bin),
 // coalesced loads, no LDS except the loss and CDF reductions.  Compiled with -ffp-contract=off so that
 // a*x + b*y rounds like the reference's separate ATen ops.
+#include <cmath>
+
 #include "common.h"
 #include "denoiser_internal.h"
 #include "philox.h"
@@ -701,15 +703,17 @@ __global__ void angular_encoding_kernel(const float* __restrict__ x, int64_t n, 
 // ------------------------------------------------------------------ reverse update
 // (the design modes, DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE, run one of the two halves)
 // noise: t > 1 for the step t -> t - 1, s > 0 for a jump t -> s (beta / alpha are then the jump's beta'_t / alpha'_t)
+// shift (nullable, structure guidance): Delta of the residue, subtracted from the mean before the noise is added
 __device__ inline void reverse_update_structure(int64_t i, bool noise, float beta, float alpha, float omabs, float* x, float* O,
                                                 const float* eps_hat, const float* O0_hat, float zx, float zy, float zz, float rx, float ry,
-                                                float rz) {
+                                                float rz, const float* shift = nullptr) {
   const float c = beta / omabs;
   const float sa = sqrtf(alpha), sb = sqrtf(beta);
   const float zn[3] = {zx, zy, zz};
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     float v = (x[i * 3 + k] - c * eps_hat[i * 3 + k]) / sa;
+    if (shift != nullptr) v = v - shift[i * 3 + k];
     if (noise) v = v + sb * zn[k];
     x[i * 3 + k] = v;
   }
@@ -855,6 +859,196 @@ __global__ void record_fixed_kernel(SampleRecordDev rec, const int64_t* __restri
   for (int c = 0; c < V; ++c) rec.seq_probs[o * V + c] = c == s ? 1.0f : 0.0f;
 }
 
+// ------------------------------------------------------------------ structure guidance
+// One work-group of four waves per state row.  The row is staged in LDS tiles of kGuideThreads residues: p (x0_hat of a generated
+// residue, x of any other) with a flag word in .w (bit 0 residue_mask, bit 1 generated; 0 past the end of a ragged row) in one float4,
+// chain and residue_idx in one int2.  Lane l of every wave owns residue i0 + l of each chunk of 64 residues; wave w scans the w-th
+// quarter of every tile's partners in order - all lanes read the same LDS address, a broadcast - and the four partial gradients of a
+// residue are added in wave order through LDS.  A wave whose 64 owners have nothing to compute skips the scan.  Sums run in that fixed
+// order, then in a fixed tree: no atomics, the result of a row depends on the row alone.  Plain fp32 VALU / LDS code (this file is
+// built with -ffp-contract=off).
+constexpr int kGuideThreads = 256, kGuideWaves = kGuideThreads / 64;
+
+struct GuideSums {
+  float clash = 0.f, bond = 0.f, max_dev = 0.f;
+  int n_clash = 0;
+};
+
+// p of residue i: x0_hat_i = (x_t,i - sqrt(1 - abar_t) eps_hat_i) / sqrt(abar_t) for a generated residue - record_residue's expression,
+// so the recorded pred_x is bitwise the point the potential is taken at - and x_i otherwise (eps_hat == nullptr: x for every residue)
+__device__ inline float3 guide_point(const float* x, const float* eps_hat, int64_t i, bool gen, float omabs, float a) {
+  if (eps_hat != nullptr && gen)
+    return make_float3((x[i * 3 + 0] - omabs * eps_hat[i * 3 + 0]) / a, (x[i * 3 + 1] - omabs * eps_hat[i * 3 + 1]) / a,
+                       (x[i * 3 + 2] - omabs * eps_hat[i * 3 + 2]) / a);
+  return make_float3(x[i * 3 + 0], x[i * 3 + 1], x[i * 3 + 2]);
+}
+
+// The pass over one row: g_i for every residue, handed to emit(i, gx, gy, gz) by wave 0 (0 unless generated and masked).  kEnergy:
+// every masked residue also scans, and the unordered pairs {i, j} are counted by their smaller index into `sums`.
+template <bool kEnergy, typename Emit>
+__device__ inline void guide_row(int64_t row, int K, const float* __restrict__ x, const float* __restrict__ eps_hat, float omabs, float a,
+                                 const uint8_t* __restrict__ gm, const GuidanceDev& g, GuideSums& sums, Emit emit) {
+  __shared__ float4 tp[kGuideThreads];
+  __shared__ int2 tc[kGuideThreads];
+  __shared__ float part[kGuideWaves][3][64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t base = row * K;
+  // a nonbonded pair whose d^2 is not below d0^2 (with a margin over its rounding) cannot clash: skipped before the square root
+  const float d0 = g.clash_distance, L = g.bond_length, wc2 = 2.0f * g.w_clash, wb2 = 2.0f * g.w_bond, far2 = d0 * d0 * 1.0001f;
+  for (int i0 = 0; i0 < K; i0 += 64) {
+    const int i = i0 + lane;
+    int fi = 0, ci = 0, ri = 0;
+    float3 pi = make_float3(0.f, 0.f, 0.f);
+    if (i < K) {
+      const bool gen = gm[base + i] != 0;
+      fi = (g.residue_mask == nullptr || g.residue_mask[base + i] ? 1 : 0) | (gen ? 2 : 0);
+      pi = guide_point(x, eps_hat, base + i, gen, omabs, a);
+      ci = g.chain[base + i];
+      ri = g.residue_idx[base + i];
+    }
+    const bool run = kEnergy ? (fi & 1) != 0 : fi == 3;
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    for (int j0 = 0; j0 < K; j0 += kGuideThreads) {
+      __syncthreads();  // every wave is done with the previous tile
+      const int j = j0 + tid;
+      if (j < K) {
+        const bool gen = gm[base + j] != 0;
+        const int fj = (g.residue_mask == nullptr || g.residue_mask[base + j] ? 1 : 0) | (gen ? 2 : 0);
+        const float3 pj = guide_point(x, eps_hat, base + j, gen, omabs, a);
+        tp[tid] = make_float4(pj.x, pj.y, pj.z, static_cast<float>(fj));
+        tc[tid] = make_int2(g.chain[base + j], g.residue_idx[base + j]);
+      } else {
+        tp[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+        tc[tid] = make_int2(0, 0);
+      }
+      __syncthreads();
+      if (!run) continue;
+      const int n = min(kGuideThreads, K - j0), lo = n * wave / kGuideWaves, hi = n * (wave + 1) / kGuideWaves;
+#pragma unroll 4
+      for (int jj = lo; jj < hi; ++jj) {
+        const float4 q = tp[jj];
+        const int fj = static_cast<int>(q.w);
+        if (!(fj & 1) || !((fi | fj) & 2) || j0 + jj == i) continue;
+        const int2 c = tc[jj];
+        const float dx = pi.x - q.x, dy = pi.y - q.y, dz = pi.z - q.z;
+        const float d2 = dx * dx + dy * dy + dz * dz;
+        const int64_t gap = static_cast<int64_t>(c.y) - ri;
+        const bool bonded = c.x == ci && (gap == 1 || gap == -1);
+        if (!bonded && !(d2 < far2)) continue;
+        const float d = sqrtf(d2);
+        const bool counted = kEnergy && j0 + jj > i;
+        float coef;
+        if (bonded) {
+          const float dev = d - L;
+          coef = wb2 * dev;
+          if (counted) {
+            sums.bond += dev * dev;
+            sums.max_dev = fmaxf(sums.max_dev, fabsf(dev));
+          }
+        } else {
+          if (!(d < d0)) continue;
+          const float h = d0 - d;
+          coef = -wc2 * h;
+          if (counted) {
+            sums.clash += h * h;
+            sums.n_clash += 1;
+          }
+        }
+        if ((fi & 2) && d >= 1e-6f) {
+          const float sc = coef / d;
+          gx += sc * dx;
+          gy += sc * dy;
+          gz += sc * dz;
+        }
+      }
+    }
+    part[wave][0][lane] = gx;
+    part[wave][1][lane] = gy;
+    part[wave][2][lane] = gz;
+    __syncthreads();  // (part is next written after the next chunk's first tile barrier)
+    if (wave == 0 && i < K) {
+      float sx = part[0][0][lane], sy = part[0][1][lane], sz = part[0][2][lane];
+#pragma unroll
+      for (int w = 1; w < kGuideWaves; ++w) {
+        sx += part[w][0][lane];
+        sy += part[w][1][lane];
+        sz += part[w][2][lane];
+      }
+      emit(base + i, sx, sy, sz);
+    }
+  }
+}
+
+// The sampler's pass, right before the update of step t (t from t_dev under graph replay): Delta = beta'_t g, capped at max_shift, into
+// g.shift for every residue of the row (+0 where g is 0); all 0 at a step t > t_max (the update then does not read it).
+__global__ __launch_bounds__(kGuideThreads) void guidance_shift_kernel(GuidanceDev g, const float* __restrict__ x,
+                                                                       const float* __restrict__ eps_hat, const uint8_t* __restrict__ gm,
+                                                                       const float* __restrict__ beta, const float* __restrict__ omabs,
+                                                                       const float* __restrict__ abs_, int t, const int* __restrict__ t_dev,
+                                                                       int K) {
+  if (t_dev != nullptr) t = *t_dev;
+  const int64_t row = blockIdx.x;
+  float* shift = g.shift;
+  if (t > g.t_max) {  // uniform over the work-group
+    for (int k = threadIdx.x; k < 3 * K; k += kGuideThreads) shift[row * K * 3 + k] = 0.0f;
+    return;
+  }
+  const float bt = beta[t], cap = g.max_shift;
+  GuideSums unused;
+  guide_row<false>(row, K, x, eps_hat, omabs[t], abs_[t], gm, g, unused, [&](int64_t i, float gx, float gy, float gz) {
+    float sx = bt * gx, sy = bt * gy, sz = bt * gz;
+    const float n = sqrtf(sx * sx + sy * sy + sz * sz);
+    if (n > cap) {
+      const float r = cap / n;
+      sx *= r;
+      sy *= r;
+      sz *= r;
+    }
+    shift[i * 3 + 0] = sx;
+    shift[i * 3 + 1] = sy;
+    shift[i * 3 + 2] = sz;
+  });
+}
+
+// diffab_guidance_energy: the same pass at p = x, the row's unweighted sums reduced in a fixed tree, the weighted gradient (nullable)
+__global__ __launch_bounds__(kGuideThreads) void guidance_energy_kernel(GuidanceDev g, const float* __restrict__ x,
+                                                                        const uint8_t* __restrict__ gm, int K, float* __restrict__ clash,
+                                                                        float* __restrict__ bond, int* __restrict__ n_clash,
+                                                                        float* __restrict__ max_dev, float* __restrict__ grad) {
+  __shared__ float red[3][kGuideThreads];
+  __shared__ int red_n[kGuideThreads];
+  const int64_t row = blockIdx.x;
+  GuideSums sums;
+  guide_row<true>(row, K, x, nullptr, 0.f, 1.f, gm, g, sums, [&](int64_t i, float gx, float gy, float gz) {
+    if (grad != nullptr) {
+      grad[i * 3 + 0] = gx;
+      grad[i * 3 + 1] = gy;
+      grad[i * 3 + 2] = gz;
+    }
+  });
+  const int tid = threadIdx.x;
+  red[0][tid] = sums.clash;
+  red[1][tid] = sums.bond;
+  red[2][tid] = sums.max_dev;
+  red_n[tid] = sums.n_clash;
+  __syncthreads();
+  for (int s = kGuideThreads / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      red[0][tid] += red[0][tid + s];
+      red[1][tid] += red[1][tid + s];
+      red[2][tid] = fmaxf(red[2][tid], red[2][tid + s]);
+      red_n[tid] += red_n[tid + s];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    clash[row] = red[0][0];
+    bond[row] = red[1][0];
+    max_dev[row] = red[2][0];
+    n_clash[row] = red_n[0];
+  }
+}
+
 // Same update with the noise drawn in-kernel from Philox (the production sampler).
 // head_v / head_logits != nullptr (the folded sampler path): the heads' epilogue of the row - O0 = O_t exp(hat(v)) (diffab_pytorch.py:594-596)
 // and posterior = softmax(logits) (:555), what heads_finish_kernel computes for every row - is done here, for the generated rows only,
@@ -868,13 +1062,16 @@ __global__ void record_fixed_kernel(SampleRecordDev rec, const int64_t* __restri
 // plan (fewer-step sampling; plan.next == nullptr: off, the step t -> t - 1 above): the state moves to s = plan.next[t] with the jump's
 // beta'_t / alpha'_t and the noise condition s > 0 (the caller's rev_sigmas / rev_cdf are then the table over sqrt(beta')); for s < t - 1
 // the sequence is drawn from the jump distribution r (seq_jump_probs), computed in place over the posterior after it was recorded.
+// guide (structure guidance; guide.shift == nullptr: off): at a step t <= t_max the translation mean loses guide.shift[i], the Delta
+// guidance_shift_kernel wrote just before this launch; the sample's noise, orientations and sequence are untouched.
 __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs,
                                              int t, const float* __restrict__ rev_sigmas, const float* __restrict__ rev_cdf, int n_bins,
                                              float thr, int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
                                              const float* __restrict__ eps_hat, float* O0_hat, float* post, const uint8_t* __restrict__ gm,
                                              uint64_t seed, int64_t first_patch, int B, int K, int V, const int* __restrict__ t_dev,
                                              const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep,
-                                             const uint32_t* __restrict__ allowed, SampleRecordDev rec, StepPlanDev plan) {
+                                             const uint32_t* __restrict__ allowed, SampleRecordDev rec, StepPlanDev plan,
+                                             GuidanceDev guide) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   if (t_dev != nullptr) t = *t_dev;  // graph replay: the timestep lives in device memory (one captured step serves every t)
@@ -908,12 +1105,13 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
     const f32x4 na = normals_from_uniforms(ua);  // .z is the Box-Muller normal of (u2,u3)
     const float theta = igso3_theta(rev_cdf, n_bins, rev_sigmas[t], thr, t, ua.x, ua.y, na.z);
     normalize3(ax.x, ax.y, ax.z);
+    const float* shift = guide.shift != nullptr && t <= guide.t_max ? guide.shift : nullptr;
     if (plan.next == nullptr)
       reverse_update_structure(i, t > 1, beta[t], alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z, ax.x * theta, ax.y * theta,
-                               ax.z * theta);
+                               ax.z * theta, shift);
     else
       reverse_update_structure(i, plan.next[t] > 0, plan.beta[t], plan.alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z,
-                               ax.x * theta, ax.y * theta, ax.z * theta);
+                               ax.x * theta, ax.y * theta, ax.z * theta, shift);
   }
   if (upd_seq) {
     const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_SEQ);
@@ -1173,11 +1371,16 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
                                  const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec,
-                                 const StepPlanDev& plan) {
+                                 const StepPlanDev& plan, const GuidanceDev& guide) {
   const int64_t n = static_cast<int64_t>(B) * K;
+  if (guide.shift != nullptr) {  // every launch form reaches the update through here: Delta of this step first
+    hipLaunchKernelGGL(guidance_shift_kernel, dim3(B), dim3(kGuideThreads), 0, st, guide, x, eps_hat, gm, plan.next ? plan.beta : s->beta,
+                       s->one_minus_alpha_bar_sqrt, s->alpha_bar_sqrt, t, t_dev, K);
+    DIFFAB_LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan, guide);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
@@ -1294,6 +1497,17 @@ int launch_advance_step(int* p, const int* next, hipStream_t st) {
 }  // namespace diffab
 
 using namespace diffab;
+
+// structure guidance: the checks diffab_sample_loop_guided and diffab_guidance_energy share (weights, distances, the per-residue tables)
+int diffab::check_guidance_terms(const diffab_sample_guidance* g, const char* who) {
+  DIFFAB_REQUIRE(g != nullptr, DIFFAB_ERR_ARG, "%s: guidance is null", who);
+  DIFFAB_REQUIRE(std::isfinite(g->w_clash) && g->w_clash >= 0.0f && std::isfinite(g->w_bond) && g->w_bond >= 0.0f, DIFFAB_ERR_ARG,
+                 "%s: guidance weights must be finite and >= 0 (w_clash = %g, w_bond = %g)", who, g->w_clash, g->w_bond);
+  DIFFAB_REQUIRE(std::isfinite(g->clash_distance) && g->clash_distance > 0.0f && std::isfinite(g->bond_length) && g->bond_length > 0.0f,
+                 DIFFAB_ERR_ARG, "%s: clash_distance and bond_length must be finite and > 0 (%g, %g)", who, g->clash_distance, g->bond_length);
+  DIFFAB_REQUIRE(g->chain && g->residue_idx, DIFFAB_ERR_ARG, "%s: guidance needs chain and residue_idx", who);
+  return DIFFAB_OK;
+}
 
 static int check_sched(const diffab_sched* s) {
   DIFFAB_REQUIRE(s && s->T > 0 && s->alpha && s->alpha_bar && s->alpha_bar_sqrt && s->one_minus_alpha_bar_sqrt && s->beta, DIFFAB_ERR_ARG,
@@ -1620,6 +1834,28 @@ int diffab_reverse_update_jump(const diffab_sched* s, int32_t t, int32_t s_next,
   hipLaunchKernelGGL(reverse_update_jump_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), s->beta, s->alpha, s->alpha_bar,
                      s->one_minus_alpha_bar_sqrt, t, s_next, beta_jump, alpha_jump, seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec,
                      u_seq, r_out, B, K, V);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+
+int diffab_guidance_energy(const float* x, const uint8_t* gen_mask, const diffab_sample_guidance* g, int32_t B, int32_t K, float* clash,
+                           float* bond, int32_t* n_clash, float* max_bond_deviation, float* grad, void* stream) {
+  StreamOrder order_(stream);
+  if (int rc = check_guidance_terms(g, "guidance_energy")) return rc;
+  DIFFAB_REQUIRE(B >= 0 && K >= 1 && static_cast<int64_t>(B) * K < (1ll << 31), DIFFAB_ERR_ARG, "guidance_energy: need B >= 0, K >= 1, B*K < 2^31");
+  DIFFAB_REQUIRE(x && gen_mask && clash && bond && n_clash && max_bond_deviation, DIFFAB_ERR_ARG,
+                 "guidance_energy: null pointer (x, gen_mask, clash, bond, n_clash and max_bond_deviation are required)");
+  if (B == 0) return DIFFAB_OK;
+  GuidanceDev gd;
+  gd.chain = g->chain;
+  gd.residue_idx = g->residue_idx;
+  gd.residue_mask = g->residue_mask;
+  gd.w_clash = g->w_clash;
+  gd.clash_distance = g->clash_distance;
+  gd.w_bond = g->w_bond;
+  gd.bond_length = g->bond_length;
+  hipLaunchKernelGGL(guidance_energy_kernel, dim3(B), dim3(kGuideThreads), 0, as_stream(stream), gd, x, gen_mask, K, clash, bond, n_clash,
+                     max_bond_deviation, grad);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

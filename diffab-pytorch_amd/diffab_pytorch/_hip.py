@@ -96,6 +96,11 @@ class SampleSteps(C.Structure):  # diffab_sample_steps: the executed step list o
                 ("alpha_jump", C.POINTER(C.c_float)), ("plan_dev", _fp)]
 
 
+class SampleGuidance(C.Structure):  # diffab_sample_guidance: the clash / chain-bond potential of diffab_sample_loop_guided
+    _fields_ = [(n, C.c_float) for n in ("w_clash", "clash_distance", "w_bond", "bond_length", "max_shift")] + \
+        [("t_max", C.c_int32)] + [(n, _fp) for n in ("chain", "residue_idx", "residue_mask", "shift_dev")]
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -201,6 +206,12 @@ SYMBOLS = {
     "diffab_sample_loop_steps": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
                                            _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
                                            _fp]),
+    # structure guidance: diffab_sample_loop_steps plus `guidance` (nullable) before the stream
+    "diffab_sample_loop_guided": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                            _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
+                                            C.POINTER(SampleGuidance), _fp]),
+    # (x, gen_mask, guidance, B, K, clash, bond, n_clash, max_bond_deviation, grad (nullable), stream)
+    "diffab_guidance_energy": (C.c_int, [_fp, _fp, C.POINTER(SampleGuidance), _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
     # (sched, t, s, beta', alpha', seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec, u_seq, r_out (nullable), B, K, V, stream)
     "diffab_reverse_update_jump": (C.c_int, [_PS, _i32, _i32, C.c_float, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp,
                                              _i32, _i32, _i32, _fp]),

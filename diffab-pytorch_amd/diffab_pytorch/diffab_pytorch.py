@@ -25,6 +25,7 @@ from . import _hip
 from .diffusion import CoordinateDiffuser, OrientationDiffuser, SequenceDiffuser, cosine_variance_schedule, even_steps, jump_coefficients
 from . import so3 as _so3
 from . import features as _features
+from . import guidance as _guidance
 
 try:  # LightningModule hooks when Lightning is installed; a plain nn.Module otherwise
     import pytorch_lightning as pl
@@ -1038,7 +1039,8 @@ class DiffAb(_ModuleBase):
                skip_unused_rows: bool = False, num_samples: int = 1,
                context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
                optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None, trajectory=None,
-               trajectory_predictions: bool = False, steps=None) -> Dict[str, torch.Tensor]:
+               trajectory_predictions: bool = False, steps=None,
+               guidance: Optional[_guidance.SampleGuidance] = None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -1124,7 +1126,23 @@ class DiffAb(_ModuleBase):
         trajectory, labels are executed steps: True records every executed step, an int k every k-th of them, and a list must name
         executed steps; ``seq_probs`` is still the head posterior.  None is the ordinary loop.  A bool / float / 2-D / empty list,
         n outside [1, L], a list that does not start at t_start, is not strictly descending or reaches t_stop, and t_start = t_stop
-        raise ValueError before any device work."""
+        raise ValueError before any device work.
+
+        Structure guidance: ``guidance=guidance.SampleGuidance(clash=..., bond=...)`` steers the CA translations
+        of the generated residues away from clashes and towards chain bonds while they form.  Per state row, over the pairs with
+        residue_mask on both and at least one generated residue, at p = x0_hat (the pred_translations of a trajectory record; the given
+        x for residues that are not generated): U = clash sum_nonbonded max(0, clash_distance - d)^2 + bond sum_bonded (d -
+        bond_length)^2, bonded meaning the same chain_idx and residue_idx one apart.  At every step t <= t_max (None: all) the mean of
+        the update loses Delta = beta'_t dU/dp (beta[t], or the jump's beta' with steps=), capped at length max_shift, before the noise
+        is added; the last step is guided too.  Orientations, the sequence, the Philox draws and the trajectory record are unchanged.
+        The tables are ``chain_idx`` (default one chain), ``residue_idx`` (default arange(K)) and ``residue_mask`` (default all true),
+        (K,) or (rows, K), used even when the contexts are given: per patch and replicated like generation_mask under num_samples, per
+        state row with context_index.  Both weights 0 (and t_max = 0) still run the guidance kernel and are bitwise the unguided
+        sample (`diffab_sample_loop_guided`).  Combines with every mode except "fixed_backbone" (the structure is kept), with
+        optimize_from, allowed_aa, trajectory, steps, graph, skip_unused_rows, num_samples / context_index and the flags.  Anything but
+        a SampleGuidance, a negative or non-finite weight, a non-positive distance or max_shift, t_max outside [0, T], tables of a
+        non-integer dtype or a shape that does not broadcast to the rows, and mode="fixed_backbone" raise ValueError before any device
+        work.  guidance.structure_energy counts clashes and bond deviations of finished designs."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
         generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
@@ -1161,6 +1179,12 @@ class DiffAb(_ModuleBase):
             ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
         if allowed_aa is not None:
             _allowed_aa_host("sample()", allowed_aa, generation_mask, n_rows, K_, self.denoiser.dims["V"], keep)
+        guide_tabs = None  # host (rows, K) chain / residue_idx / residue_mask of the guidance (None: unguided)
+        if guidance is not None:
+            _guidance.check_guidance("sample()", guidance, self.T)
+            if keep & _hip.FLAG_KEEP_STRUCTURE:
+                raise ValueError("sample(): guidance moves the structure, which mode='fixed_backbone' keeps as given")
+            guide_tabs = _guidance.residue_tables("sample()", chain_idx, residue_idx, residue_mask, n_rows, K_)
         executed = _sample_steps("sample()", steps, self.T if t_start is None else int(t_start), int(t_stop), self.T)
         labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, self.T if t_start is None else int(t_start), int(t_stop),
                                     self.T, executed)
@@ -1178,10 +1202,14 @@ class DiffAb(_ModuleBase):
         allowed = None  # int32 (rows, K) words of the allowed classes (always passed when allowed_aa is given, an all-True mask too)
         if allowed_aa is not None:
             allowed = _pack_allowed_aa(torch.as_tensor(allowed_aa).detach().to(seq.device).expand(n_rows, K_, self.denoiser.dims["V"]))
+        if guide_tabs is not None:
+            guide_tabs = tuple(v.to(seq.device) for v in guide_tabs)
         if num_samples > 1:  # the state of every design: the patch's rows, replicated on the device (the contexts are not)
             seq, x, O, gm = (v.repeat_interleave(num_samples, dim=0) for v in (seq, x, O, gm))
             if allowed is not None:
                 allowed = allowed.repeat_interleave(num_samples, dim=0)
+            if guide_tabs is not None:
+                guide_tabs = tuple(v.repeat_interleave(num_samples, dim=0) for v in guide_tabs)
         else:
             seq, x, O = seq.clone(), x.clone(), O.clone()
         B, K = seq.shape
@@ -1241,16 +1269,24 @@ class DiffAb(_ModuleBase):
             rec = _hip.SampleRecord(n, (C.c_int32 * (self.T + 1))(*slot_of_step), _hip.ptr(slot_dev),
                                     *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
                                                                       "pred_orientations", "seq_probs")))
-        if executed is not None:
-            plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=seq.device)
-            st = _hip.SampleSteps(executed.numel(), (C.c_int32 * executed.numel())(*executed.tolist()),
-                                  (C.c_float * (self.T + 1))(*beta_j.tolist()), (C.c_float * (self.T + 1))(*alpha_j.tolist()),
-                                  _hip.ptr(plan_dev))
-            _hip.check(lib.diffab_sample_loop_steps(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
-                                                    _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
-                                                    None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,
-                                                    _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), None if rec is None else C.byref(rec),
-                                                    C.byref(st), _hip.stream_ptr()), "diffab_sample_loop_steps")
+        if executed is not None or guide_tabs is not None:
+            st = None
+            if executed is not None:
+                plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=seq.device)
+                st = _hip.SampleSteps(executed.numel(), (C.c_int32 * executed.numel())(*executed.tolist()),
+                                      (C.c_float * (self.T + 1))(*beta_j.tolist()), (C.c_float * (self.T + 1))(*alpha_j.tolist()),
+                                      _hip.ptr(plan_dev))
+            args = (C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc),
+                    _hip.ptr(pc), B if ctx_map is None else n_ctx, None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch,
+                    t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), None if rec is None else C.byref(rec),
+                    None if st is None else C.byref(st))
+            if guide_tabs is None:
+                _hip.check(lib.diffab_sample_loop_steps(*args, _hip.stream_ptr()), "diffab_sample_loop_steps")
+            else:
+                shift = torch.empty(B, K, 3, device=seq.device)
+                t_max = self.T if guidance.t_max is None else guidance.t_max
+                gs = _guidance.c_struct(guidance, t_max, *guide_tabs, shift)
+                _hip.check(lib.diffab_sample_loop_guided(*args, C.byref(gs), _hip.stream_ptr()), "diffab_sample_loop_guided")
             out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
             if labels is not None:
                 out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}

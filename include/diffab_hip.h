@@ -626,6 +626,56 @@ int diffab_reverse_update_jump(const diffab_sched* s, int32_t t, int32_t s_next,
                                float* O, const float* eps_hat, const float* O0_hat, const float* posterior, const uint8_t* gen_mask,
                                const float* z, const float* rotvec, const float* u_seq, float* r_out, int32_t B, int32_t K, int32_t V,
                                void* stream);
+/* ---- structure guidance (build-defined): clash and chain-bond potentials on the translations --------------------
+ * Per state row, over the unordered pairs {i, j}, i != j, with residue_mask set on both and at least one of them generated:
+ *   p_i = x0_hat_i = (x_t,i - one_minus_alpha_bar_sqrt[t] eps_hat_i) / alpha_bar_sqrt[t] for a generated residue - the expression, and
+ *     so bitwise the value, of the record's pred_x - and the given x_i for one that is not generated;
+ *   bonded: chain_i == chain_j and |residue_idx_i - residue_idx_j| == 1;  d = |p_i - p_j| (Angstrom: coordinates are not scaled);
+ *   U = w_clash sum_nonbonded max(0, clash_distance - d)^2 + w_bond sum_bonded (d - bond_length)^2;
+ *   g_i = dU / dp_i for generated i (0 elsewhere); a pair with d < 1e-6 contributes no gradient (it still counts in U);
+ *   at a guided step t <= t_max: Delta_i = beta'_t g_i, beta'_t = beta[t] (the step plan's beta' in a respaced run) - the variance of the
+ *     step's Gaussian, so the guidance fades with the noise; |Delta_i| > max_shift scales Delta_i to length max_shift (INFINITY: no cap);
+ *   x_s = mu - Delta_i + [s > 0] sqrt(beta'_t) z: Delta is subtracted from the ordinary mean mu before the noise is added.  The last step
+ *     (s = 0) is guided too.  Orientations, sequence draws, Philox lanes, the record (pred_x included) are untouched.
+ * One work-group per state row stages p, chain, residue_idx and the masks in LDS tiles of 256 residues (every K); its four waves scan
+ * a quarter of the partners each for the same owners, summed in a fixed order, no atomics.  Launched right before the update of every
+ * step, on every launch form (graph replay reads t from device memory).  shift_dev: a caller-owned DEVICE (B, K, 3) fp32 buffer the
+ * call writes every step - Delta of the last step after the call (0 where not generated, and all 0 when that step had t > t_max); not
+ * workspace: the workspace size is unchanged.
+ * chain / residue_idx: DEVICE (B, K) int32 per state row; residue_mask: DEVICE (B, K) uint8, NULL = all set.
+ * Both weights 0 still runs the kernel and gives Delta = +0: bitwise the unguided run; so does t_max = 0 (no step is guided). */
+typedef struct {
+  float w_clash;              /* >= 0, finite */
+  float clash_distance;       /* d0 > 0 (3.8) */
+  float w_bond;               /* >= 0, finite */
+  float bond_length;          /* L > 0 (3.8) */
+  float max_shift;            /* > 0; INFINITY = no cap */
+  int32_t t_max;              /* steps t <= t_max are guided, in [0, T] */
+  const int32_t* chain;       /* DEVICE (B, K) */
+  const int32_t* residue_idx; /* DEVICE (B, K) */
+  const uint8_t* residue_mask;/* DEVICE (B, K), nullable = all */
+  float* shift_dev;           /* DEVICE (B, K, 3), written by the call */
+} diffab_sample_guidance;
+/* diffab_sample_loop_steps plus `guidance` (nullable) before the stream; guidance == NULL is exactly diffab_sample_loop_steps (which is
+ * unchanged).  Needs s->alpha_bar_sqrt.  Checked before anything is enqueued, DIFFAB_ERR_ARG: a negative or non-finite weight;
+ * clash_distance or bond_length <= 0 or not finite; max_shift <= 0 or NaN; t_max outside [0, T]; null chain, residue_idx or shift_dev;
+ * DIFFAB_FLAG_KEEP_STRUCTURE (the structure is not sampled). */
+int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                              int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                              const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
+                              void* stream);
+/* The potential of the rule above at given coordinates (p = x for every residue), for B rows of K residues: per row, UNWEIGHTED,
+ * clash = sum_nonbonded max(0, d0 - d)^2, bond = sum_bonded (d - L)^2, n_clash = the number of nonbonded pairs with d < d0, and
+ * max_bond_deviation = the largest |d - L| over bonded pairs (0 without one); grad (nullable, (B, K, 3)) = the WEIGHTED gradient g
+ * (w_clash, w_bond applied; 0 where not generated; neither scaled by beta nor capped).  Pairs as above (mask on both, at least one
+ * generated).  Each row is one work-group with a fixed reduction order and no atomics: the result of a row does not depend on B.  Reads
+ * w_clash, clash_distance, w_bond, bond_length, chain, residue_idx and residue_mask of `g` (max_shift, t_max, shift_dev are ignored).
+ * DIFFAB_ERR_ARG: the weight / distance checks of diffab_sample_loop_guided, B < 0, K < 1, a null x, gen_mask, g, chain, residue_idx,
+ * clash, bond, n_clash or max_bond_deviation. */
+int diffab_guidance_energy(const float* x, const uint8_t* gen_mask, const diffab_sample_guidance* g, int32_t B, int32_t K, float* clash,
+                           float* bond, int32_t* n_clash, float* max_bond_deviation, float* grad, void* stream);
 int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
 int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
