@@ -820,6 +820,16 @@ int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weight
                               int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                               const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
                               void* stream) {
+  return diffab_sample_loop_tempered(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
+                                     t_stop, workspace, workspace_bytes, flags, allowed, rec, steps, guidance, nullptr, stream);
+}
+
+int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                                int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                                const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                                int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                                const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
+                                const diffab_sample_temperature* temperature, void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
@@ -920,6 +930,17 @@ int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weight
     gdev.max_shift = guidance->max_shift;
     gdev.t_max = guidance->t_max;
   }
+  // noise scales and sequence temperature: the pointers are checked here (the per-row values are the caller's contract, like `allowed`)
+  TemperatureDev tdev;
+  if (temperature != nullptr) {
+    DIFFAB_REQUIRE(!temperature->rot_scale || temperature->rot_row, DIFFAB_ERR_ARG,
+                   "sample_loop: temperature rot_scale needs rot_row (its rows of the stacked reverse table)");
+    DIFFAB_REQUIRE(!((temperature->trans_scale || temperature->rot_scale) && (keep & DIFFAB_FLAG_KEEP_STRUCTURE)), DIFFAB_ERR_ARG,
+                   "sample_loop: noise scales act on the structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
+    DIFFAB_REQUIRE(!(temperature->seq_temp && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
+                   "sample_loop: a sequence temperature acts on the sequence, which DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
+    tdev = TemperatureDev{temperature->trans_scale, temperature->rot_scale, temperature->seq_temp, temperature->rot_row};
+  }
   // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
   // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
   const bool mapped = ctx_of_row != nullptr;
@@ -968,7 +989,7 @@ int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weight
     if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev, gdev);
+                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev, gdev, tdev);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is

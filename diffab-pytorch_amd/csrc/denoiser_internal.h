@@ -266,6 +266,15 @@ struct GuidanceDev {
   float w_clash = 0.f, clash_distance = 0.f, w_bond = 0.f, bond_length = 0.f, max_shift = 0.f;
   int32_t t_max = -1;
 };
+// Noise scales and sequence temperature (diffab_sample_loop_tempered), a by-value launch argument of the update kernel like the plan:
+// one entry per state row of the launch (i / K), each pointer nullable (null = 1 for that quantity; all null is today's update).  rot_row
+// is the row of the state row's sigma list in the stacked reverse table: step t reads table row rot_row + t.
+struct TemperatureDev {
+  const float* trans_scale = nullptr;  // lambda_x >= 0
+  const float* rot_scale = nullptr;    // lambda_O >= 0 (needs rot_row)
+  const float* seq_temp = nullptr;     // tau >= 0
+  const int32_t* rot_row = nullptr;
+};
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
@@ -274,7 +283,8 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const uint32_t* allowed = nullptr,  // per-residue allowed-class words of the sequence draw (nullable)
                                  const SampleRecordDev& rec = SampleRecordDev{},  // trajectory recording (rec.slot nullable)
                                  const StepPlanDev& plan = StepPlanDev{},  // fewer-step sampling (plan.next nullable)
-                                 const GuidanceDev& guide = GuidanceDev{});  // structure guidance (guide.shift nullable)
+                                 const GuidanceDev& guide = GuidanceDev{},  // structure guidance (guide.shift nullable)
+                                 const TemperatureDev& temp = TemperatureDev{});  // noise scales / sequence temperature (all nullable)
 int check_guidance_terms(const diffab_sample_guidance* g, const char* who);  // weights, distances, chain / residue_idx (DIFFAB_ERR_ARG)
 // the residues that are not generated: their (constant) state in every slot of the record, and their predictions - the given x / O and a
 // one-hot of the token - once per call

@@ -382,6 +382,53 @@ __device__ inline int categorical_draw_allowed(const float* __restrict__ p, int 
   return last;
 }
 
+// The tempered draw: s ~ p_v^(1/tau) / sum_u p_u^(1/tau) over the classes v < V allowed by `allowed` (every class
+// when `all`), with weights w_v = exp((log p_v - log p_max) / tau) in fp32 (p_v = 0: weight 0), p_max the largest allowed p, and the
+// running sums of categorical_draw in increasing v against u sum w.  tau = 0: the argmax, the lowest index on ties.  Every allowed class
+// at probability 0: categorical_draw_allowed's unit-weight fallback.  No class allowed: -1.  The weights are evaluated twice (total,
+// then scan) rather than kept in a V-long array - the same expression gives the same bits, and the thread keeps no indexed local array.
+// tau = 1 is not routed here: the caller keeps categorical_draw / categorical_draw_allowed for it, so it stays bitwise today's draw.
+__device__ inline int categorical_draw_tempered(const float* __restrict__ p, int V, float u, uint32_t allowed, bool all, float tau) {
+  int n = 0, arg = -1;
+  float pmax = 0.0f;
+  for (int v = 0; v < V; ++v)
+    if (all || ((allowed >> v) & 1u)) {
+      ++n;
+      if (arg < 0 || p[v] > pmax) {
+        pmax = p[v];
+        arg = v;
+      }
+    }
+  if (n == 0) return -1;
+  int last = 0;
+  if (!(pmax > 0.0f)) {  // unit weights, as categorical_draw_allowed with tot == 0
+    const float thr = u * static_cast<float>(n);
+    float acc = 0.0f;
+    for (int v = 0; v < V; ++v)
+      if (all || ((allowed >> v) & 1u)) {
+        acc += 1.0f;
+        if (acc > thr) return v;
+        last = v;
+      }
+    return last;
+  }
+  if (tau == 0.0f) return arg;
+  const float lmax = logf(pmax);
+  auto weight = [&](int v) { return p[v] > 0.0f ? expf((logf(p[v]) - lmax) / tau) : 0.0f; };
+  float tot = 0.0f;
+  for (int v = 0; v < V; ++v)
+    if (all || ((allowed >> v) & 1u)) tot += weight(v);
+  const float thr = u * tot;
+  float acc = 0.0f;
+  for (int v = 0; v < V; ++v)
+    if (all || ((allowed >> v) & 1u)) {
+      acc += weight(v);
+      if (acc > thr) return v;
+      last = v;
+    }
+  return last;
+}
+
 __global__ void categorical_sample_kernel(const float* __restrict__ prob, const float* __restrict__ u, int64_t n, int V,
                                           int64_t* __restrict__ out) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -704,23 +751,26 @@ __global__ void angular_encoding_kernel(const float* __restrict__ x, int64_t n, 
 // (the design modes, DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE, run one of the two halves)
 // noise: t > 1 for the step t -> t - 1, s > 0 for a jump t -> s (beta / alpha are then the jump's beta'_t / alpha'_t)
 // shift (nullable, structure guidance): Delta of the residue, subtracted from the mean before the noise is added
+// xs (noise scale lambda_x): the translation noise is (sqrt(beta) xs) z, skipped at xs = 0 (sqrt(beta) 1 is exact: the
+// default is today's arithmetic); rot_noise false (lambda_O = 0): O = O0_hat, no perturbation
 __device__ inline void reverse_update_structure(int64_t i, bool noise, float beta, float alpha, float omabs, float* x, float* O,
                                                 const float* eps_hat, const float* O0_hat, float zx, float zy, float zz, float rx, float ry,
-                                                float rz, const float* shift = nullptr) {
+                                                float rz, const float* shift = nullptr, float xs = 1.0f, bool rot_noise = true) {
   const float c = beta / omabs;
-  const float sa = sqrtf(alpha), sb = sqrtf(beta);
+  const float sa = sqrtf(alpha), sb = sqrtf(beta) * xs;
   const float zn[3] = {zx, zy, zz};
+  const bool noise_x = noise && xs != 0.0f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     float v = (x[i * 3 + k] - c * eps_hat[i * 3 + k]) / sa;
     if (shift != nullptr) v = v - shift[i * 3 + k];
-    if (noise) v = v + sb * zn[k];
+    if (noise_x) v = v + sb * zn[k];
     x[i * 3 + k] = v;
   }
   float o[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) o[k] = O0_hat[i * 9 + k];
-  if (noise) {
+  if (noise && rot_noise) {
     float nz[9], r[9];
     so3_rotvec_to_matrix(rx, ry, rz, nz);
     mat3_mul(o, nz, r);
@@ -1064,6 +1114,10 @@ __global__ __launch_bounds__(kGuideThreads) void guidance_energy_kernel(Guidance
 // the sequence is drawn from the jump distribution r (seq_jump_probs), computed in place over the posterior after it was recorded.
 // guide (structure guidance; guide.shift == nullptr: off): at a step t <= t_max the translation mean loses guide.shift[i], the Delta
 // guidance_shift_kernel wrote just before this launch; the sample's noise, orientations and sequence are untouched.
+// temp (noise scales / sequence temperature; every pointer nullable = 1, all null: the update above): per state row
+// i / K, the translation noise is scaled by lambda_x (0: none), theta is drawn at sigma = lambda_O sqrt(beta'_t) from row rot_row + t of
+// the stacked table (same uniforms, normal and axis; 0: O = O0_hat) and s_{t-1} is drawn at temperature tau (categorical_draw_tempered;
+// tau = 1 keeps categorical_draw / categorical_draw_allowed).  O0_hat, the posterior and the record stay the model's untempered outputs.
 __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, const float* __restrict__ alpha, const float* __restrict__ omabs,
                                              int t, const float* __restrict__ rev_sigmas, const float* __restrict__ rev_cdf, int n_bins,
                                              float thr, int64_t* __restrict__ seq, float* __restrict__ x, float* __restrict__ O,
@@ -1071,7 +1125,7 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
                                              uint64_t seed, int64_t first_patch, int B, int K, int V, const int* __restrict__ t_dev,
                                              const float* __restrict__ head_v, const float* __restrict__ head_logits, uint32_t keep,
                                              const uint32_t* __restrict__ allowed, SampleRecordDev rec, StepPlanDev plan,
-                                             GuidanceDev guide) {
+                                             GuidanceDev guide, TemperatureDev temp) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (i >= static_cast<int64_t>(B) * K || !gm[i]) return;
   if (t_dev != nullptr) t = *t_dev;  // graph replay: the timestep lives in device memory (one captured step serves every t)
@@ -1103,15 +1157,20 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
     f32x4 ax = philox_normal4(seed, patch, res, st, STREAM_AXIS);
     const f32x4 ua = philox_uniform4(seed, patch, res, st, STREAM_ANGLE);
     const f32x4 na = normals_from_uniforms(ua);  // .z is the Box-Muller normal of (u2,u3)
-    const float theta = igso3_theta(rev_cdf, n_bins, rev_sigmas[t], thr, t, ua.x, ua.y, na.z);
+    const int64_t row = i / K;
+    const float xs = temp.trans_scale == nullptr ? 1.0f : temp.trans_scale[row];
+    const float os = temp.rot_scale == nullptr ? 1.0f : temp.rot_scale[row];
+    const int trow = temp.rot_scale == nullptr ? t : temp.rot_row[row] + t;  // (rot_row is not read at lambda_O = 1 without rot_scale)
+    const bool rot_noise = os != 0.0f;
+    const float theta = rot_noise ? igso3_theta(rev_cdf, n_bins, rev_sigmas[trow], thr, trow, ua.x, ua.y, na.z) : 0.0f;
     normalize3(ax.x, ax.y, ax.z);
     const float* shift = guide.shift != nullptr && t <= guide.t_max ? guide.shift : nullptr;
     if (plan.next == nullptr)
       reverse_update_structure(i, t > 1, beta[t], alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z, ax.x * theta, ax.y * theta,
-                               ax.z * theta, shift);
+                               ax.z * theta, shift, xs, rot_noise);
     else
       reverse_update_structure(i, plan.next[t] > 0, plan.beta[t], plan.alpha[t], omabs[t], x, O, eps_hat, O0_hat, zt.x, zt.y, zt.z,
-                               ax.x * theta, ax.y * theta, ax.z * theta, shift);
+                               ax.x * theta, ax.y * theta, ax.z * theta, shift, xs, rot_noise);
   }
   if (upd_seq) {
     const f32x4 us = philox_uniform4(seed, patch, res, st, STREAM_SEQ);
@@ -1121,7 +1180,12 @@ __global__ void reverse_update_philox_kernel(const float* __restrict__ beta, con
         seq_jump_probs(post + i * V, post + i * V, V, seq[i], alpha[t], beta[t], plan.alpha_bar[t - 1], plan.alpha[t],
                        plan.alpha_bar[s_next]);
     }
-    const int s = allowed == nullptr ? categorical_draw(post + i * V, V, us.x) : categorical_draw_allowed(post + i * V, V, us.x, allowed[i]);
+    const float tau = temp.seq_temp == nullptr ? 1.0f : temp.seq_temp[i / K];
+    int s;
+    if (tau == 1.0f)
+      s = allowed == nullptr ? categorical_draw(post + i * V, V, us.x) : categorical_draw_allowed(post + i * V, V, us.x, allowed[i]);
+    else
+      s = categorical_draw_tempered(post + i * V, V, us.x, allowed == nullptr ? 0u : allowed[i], allowed == nullptr, tau);
     if (s >= 0) seq[i] = s;
   }
 }
@@ -1371,7 +1435,7 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
                                  const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec,
-                                 const StepPlanDev& plan, const GuidanceDev& guide) {
+                                 const StepPlanDev& plan, const GuidanceDev& guide, const TemperatureDev& temp) {
   const int64_t n = static_cast<int64_t>(B) * K;
   if (guide.shift != nullptr) {  // every launch form reaches the update through here: Delta of this step first
     hipLaunchKernelGGL(guidance_shift_kernel, dim3(B), dim3(kGuideThreads), 0, st, guide, x, eps_hat, gm, plan.next ? plan.beta : s->beta,
@@ -1380,7 +1444,7 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
   }
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan, guide);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan, guide, temp);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

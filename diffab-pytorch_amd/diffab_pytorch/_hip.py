@@ -101,6 +101,10 @@ class SampleGuidance(C.Structure):  # diffab_sample_guidance: the clash / chain-
         [("t_max", C.c_int32)] + [(n, _fp) for n in ("chain", "residue_idx", "residue_mask", "shift_dev")]
 
 
+class SampleTemperature(C.Structure):  # diffab_sample_temperature: per-row noise scales and sequence temperature of diffab_sample_loop_tempered
+    _fields_ = [(n, _fp) for n in ("trans_scale", "rot_scale", "seq_temp", "rot_row")]
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -210,6 +214,10 @@ SYMBOLS = {
     "diffab_sample_loop_guided": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
                                             _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
                                             C.POINTER(SampleGuidance), _fp]),
+    # noise scales / sequence temperature: diffab_sample_loop_guided plus `temperature` (nullable) before the stream
+    "diffab_sample_loop_tempered": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                              _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
+                                              C.POINTER(SampleGuidance), C.POINTER(SampleTemperature), _fp]),
     # (x, gen_mask, guidance, B, K, clash, bond, n_clash, max_bond_deviation, grad (nullable), stream)
     "diffab_guidance_energy": (C.c_int, [_fp, _fp, C.POINTER(SampleGuidance), _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
     # (sched, t, s, beta', alpha', seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec, u_seq, r_out (nullable), B, K, V, stream)

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -26,6 +26,7 @@ from .diffusion import CoordinateDiffuser, OrientationDiffuser, SequenceDiffuser
 from . import so3 as _so3
 from . import features as _features
 from . import guidance as _guidance
+from . import temperature as _temperature
 
 try:  # LightningModule hooks when Lightning is installed; a plain nn.Module otherwise
     import pytorch_lightning as pl
@@ -872,6 +873,7 @@ class DiffAb(_ModuleBase):
         self._sched_dev: Optional[_hip.SchedOnDevice] = None
         self._rev_so3: Optional[_so3.SO3] = None
         self._rev_so3_steps: Dict[tuple, _so3.SO3] = {}  # (executed steps, t_stop) -> the reverse table over sqrt(beta')
+        self._rev_so3_tempered: Dict[tuple, _so3.SO3] = {}  # (rotation scales, step list) -> the stacked reverse table
 
     # ------------------------------------------------------------------ device-side tables
     def _sched_on_device(self) -> _hip.SchedOnDevice:
@@ -898,6 +900,25 @@ class DiffAb(_ModuleBase):
                 self._rev_so3_steps.pop(next(iter(self._rev_so3_steps)))
             tab = _so3.SO3(beta_jump.sqrt(), sigma_threshold=0.1, n_bins=8192, num_iters=1024, without_replacement=False)
             self._rev_so3_steps[key] = tab
+        return tab
+
+    def _reverse_so3_tempered(self, scales: Tuple[float, ...], steps: Optional[torch.Tensor], t_stop: int,
+                              beta_jump: Optional[torch.Tensor]) -> _so3.SO3:
+        """Stacked reverse IGSO3 table of a call with rotation scales: one SO3 over the concatenated sigma lists
+        lambda_k sqrt(beta'), T + 1 entries each, row (k, t) at k (T + 1) + t; beta' is the schedule's beta, or the plan's with steps=.
+        Each row depends on its own sigma alone, so a row is bitwise the same whatever else is stacked, and the lambda = 1 rows are
+        _reverse_so3's (_reverse_so3_steps' in a respaced run).  Cached per (scales, step list): at most 4 stacks, the oldest dropped
+        first; a stack is 2 fp32 planes of n_bins = 8192 per row (64 KiB), i.e. 6.3 MiB per scale at T = 100 and 101 MiB at the
+        16-scale limit, so the cache holds at most ~404 MiB of device memory."""
+        key = (tuple(scales), None if steps is None else (tuple(steps.tolist()), int(t_stop)))
+        tab = self._rev_so3_tempered.get(key)
+        if tab is None or tab.histograms.device != _hip.device():
+            if len(self._rev_so3_tempered) >= 4:
+                self._rev_so3_tempered.pop(next(iter(self._rev_so3_tempered)))
+            base = (self.sched["beta"] if beta_jump is None else beta_jump).sqrt()
+            tab = _so3.SO3(_temperature.stacked_sigmas(base, tuple(scales)), sigma_threshold=0.1, n_bins=8192, num_iters=1024,
+                           without_replacement=False)
+            self._rev_so3_tempered[key] = tab
         return tab
 
     # ------------------------------------------------------------------ reference API
@@ -1040,7 +1061,8 @@ class DiffAb(_ModuleBase):
                context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
                optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None, trajectory=None,
                trajectory_predictions: bool = False, steps=None,
-               guidance: Optional[_guidance.SampleGuidance] = None) -> Dict[str, torch.Tensor]:
+               guidance: Optional[_guidance.SampleGuidance] = None,
+               temperature: Optional[_temperature.SampleTemperature] = None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -1142,7 +1164,23 @@ class DiffAb(_ModuleBase):
         optimize_from, allowed_aa, trajectory, steps, graph, skip_unused_rows, num_samples / context_index and the flags.  Anything but
         a SampleGuidance, a negative or non-finite weight, a non-positive distance or max_shift, t_max outside [0, T], tables of a
         non-integer dtype or a shape that does not broadcast to the rows, and mode="fixed_backbone" raise ValueError before any device
-        work.  guidance.structure_energy counts clashes and bond deviations of finished designs."""
+        work.  guidance.structure_energy counts clashes and bond deviations of finished designs.
+
+        Noise scales and sequence temperature: ``temperature=temperature.SampleTemperature(translation=...,
+        rotation=..., sequence=...)`` sets how greedy every reverse step is.  Each field is a number or a 1-D tensor with one entry per
+        output row (B * num_samples rows, row b * N + r; per state row with context_index), finite and >= 0, default 1.  The translation
+        noise is lambda_x sqrt(beta'_t) z (0: the mean, exactly); the IGSO3 angle is drawn at sigma = lambda_O sqrt(beta'_t) from a
+        table row built over that sigma with the same uniforms, normal and axis (0: O = O0_hat, exactly); s_{t-1} is drawn from
+        p^(1/tau) renormalised over the allowed classes, p the head posterior or a respaced step's jump distribution (tau = 0: the
+        argmax, lowest index on ties).  All three are applied by the update kernel (`diffab_sample_loop_tempered`), so they combine with
+        every mode that samples the modality, optimize_from, allowed_aa, trajectory, steps, guidance, graph, num_samples /
+        context_index and the flags; 1 everywhere is bitwise the untempered sample, and with init=False and every value 0 the result
+        does not depend on the seed.  Not changed: the posterior, x0_hat / O0_hat and with them the trajectory record, the initial
+        state, optimize_from's forward noise, and DiffAb.score.  A rank that owns output rows [lo, hi) passes those rows' values and
+        first_patch = lo.  The stacked IGSO3 table of the call's distinct nonzero rotation scales is built once and cached
+        (_reverse_so3_tempered).  Anything but a SampleTemperature, a shape that does not broadcast, a negative, NaN or infinite value,
+        more than 16 distinct nonzero rotation scales, a structure scale != 1 with mode="fixed_backbone" and a sequence temperature
+        != 1 with mode="structure" raise ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
         generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
@@ -1185,6 +1223,10 @@ class DiffAb(_ModuleBase):
             if keep & _hip.FLAG_KEEP_STRUCTURE:
                 raise ValueError("sample(): guidance moves the structure, which mode='fixed_backbone' keeps as given")
             guide_tabs = _guidance.residue_tables("sample()", chain_idx, residue_idx, residue_mask, n_rows, K_)
+        temp_vals = None  # host fp32 (output rows,) lambda_x, lambda_O, tau (None: untempered)
+        if temperature is not None:
+            temp_vals = _temperature.row_values("sample()", temperature, n_rows * num_samples)
+            _temperature.check_mode("sample()", temp_vals, bool(keep & _hip.FLAG_KEEP_STRUCTURE), bool(keep & _hip.FLAG_KEEP_SEQUENCE))
         executed = _sample_steps("sample()", steps, self.T if t_start is None else int(t_start), int(t_stop), self.T)
         labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, self.T if t_start is None else int(t_start), int(t_stop),
                                     self.T, executed)
@@ -1224,6 +1266,18 @@ class DiffAb(_ModuleBase):
             beta_j, alpha_j = jump_coefficients(self.sched, executed, int(t_stop), self.beta_max)
             rev_tab = self._reverse_so3_steps(executed, int(t_stop), beta_j)  # (held until the call has been enqueued)
             tab = rev_tab.struct()
+        temp = None  # diffab_sample_temperature (None: every field 1 - the untempered entries); its device tensors live in temp_dev
+        if temp_vals is not None:
+            lx, lo, tau = temp_vals
+            temp_dev = [None if bool((v == 1).all()) else v.to(seq.device) for v in (lx, lo, tau)] + [None]
+            if temp_dev[1] is not None:
+                scales = _temperature.rotation_scales(lo)
+                if scales:  # (every lambda_O = 0: the table is never read)
+                    rev_tab = self._reverse_so3_tempered(scales, executed, int(t_stop), None if executed is None else beta_j)
+                    tab = rev_tab.struct()
+                temp_dev[3] = _temperature.rotation_rows(lo, scales, self.T).to(seq.device)
+            if any(v is not None for v in temp_dev):
+                temp = _hip.SampleTemperature(*(_hip.ptr(v) for v in temp_dev))
         if ctx_map is None:
             ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(dims)))
         else:
@@ -1269,7 +1323,7 @@ class DiffAb(_ModuleBase):
             rec = _hip.SampleRecord(n, (C.c_int32 * (self.T + 1))(*slot_of_step), _hip.ptr(slot_dev),
                                     *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
                                                                       "pred_orientations", "seq_probs")))
-        if executed is not None or guide_tabs is not None:
+        if executed is not None or guide_tabs is not None or temp is not None:
             st = None
             if executed is not None:
                 plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=seq.device)
@@ -1280,12 +1334,17 @@ class DiffAb(_ModuleBase):
                     _hip.ptr(pc), B if ctx_map is None else n_ctx, None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch,
                     t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), None if rec is None else C.byref(rec),
                     None if st is None else C.byref(st))
-            if guide_tabs is None:
-                _hip.check(lib.diffab_sample_loop_steps(*args, _hip.stream_ptr()), "diffab_sample_loop_steps")
-            else:
+            gs = None
+            if guide_tabs is not None:
                 shift = torch.empty(B, K, 3, device=seq.device)
                 t_max = self.T if guidance.t_max is None else guidance.t_max
                 gs = _guidance.c_struct(guidance, t_max, *guide_tabs, shift)
+            if temp is not None:
+                _hip.check(lib.diffab_sample_loop_tempered(*args, None if gs is None else C.byref(gs), C.byref(temp), _hip.stream_ptr()),
+                           "diffab_sample_loop_tempered")
+            elif guide_tabs is None:
+                _hip.check(lib.diffab_sample_loop_steps(*args, _hip.stream_ptr()), "diffab_sample_loop_steps")
+            else:
                 _hip.check(lib.diffab_sample_loop_guided(*args, C.byref(gs), _hip.stream_ptr()), "diffab_sample_loop_guided")
             out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
             if labels is not None:

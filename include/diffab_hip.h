@@ -676,6 +676,37 @@ int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weight
  * clash, bond, n_clash or max_bond_deviation. */
 int diffab_guidance_energy(const float* x, const uint8_t* gen_mask, const diffab_sample_guidance* g, int32_t B, int32_t K, float* clash,
                            float* bond, int32_t* n_clash, float* max_bond_deviation, float* grad, void* stream);
+/* ---- noise scales and sequence temperature (build-defined): how greedy the reverse sampler is -----------------
+ * Three values per state row b: lambda_x = trans_scale[b], lambda_O = rot_scale[b], tau = seq_temp[b]; a NULL pointer is 1 for every row.
+ *   translations: x_s = mu - Delta + [s > 0] lambda_x sqrt(beta'_t) z (mu the ordinary mean, Delta the guidance shift, z the usual Philox
+ *     normal); lambda_x = 0 adds no noise term at all (x_s = mu - Delta exactly);
+ *   orientations: theta is drawn by the usual inverse CDF / Gaussian rule at sigma = lambda_O sqrt(beta'_t) from row rot_row[b] + t of
+ *     rev_tab, with the same uniforms, normal and axis (lambda_O = 1 over a row built at sqrt(beta'_t) is the ordinary draw); lambda_O = 0
+ *     skips the perturbation: O_s = O0_hat exactly;
+ *   sequence: s_{t-1} ~ p_v^(1/tau) / sum_u p_u^(1/tau), p the distribution drawn from otherwise (the head posterior, or a respaced step's
+ *     jump distribution), restricted to the allowed classes when `allowed` is given; in fp32 as w_v = exp((log p_v - log p_max) / tau),
+ *     p_v = 0 weight 0, scanned in increasing v against the usual STREAM_SEQ uniform.  tau = 0: the argmax (lowest index on ties) of the
+ *     allowed classes; every allowed class at probability 0: the unit-weight draw of the constrained sampler; tau = 1: the ordinary draw.
+ * The posterior, O0_hat and the trajectory record (predictions included) stay the model's untempered outputs; the initial state and
+ * optimize_from's forward noise are not scaled.  lambda_x = lambda_O = tau = 1 is bitwise the untempered run.
+ * Caller's contract (not checked: the values live on the device): every value finite and >= 0; with rot_scale, rot_row[b] + T is a row of
+ * rev_tab for every row b with lambda_O != 0 and rev_tab->sigmas[rot_row[b] + t] = lambda_O sqrt(beta'_t) (fp32).  The tables are
+ * read by the update kernel alone, once per generated residue and step. */
+typedef struct {
+  const float* trans_scale; /* DEVICE (B,) fp32 lambda_x, nullable */
+  const float* rot_scale;   /* DEVICE (B,) fp32 lambda_O, nullable (needs rot_row) */
+  const float* seq_temp;    /* DEVICE (B,) fp32 tau, nullable */
+  const int32_t* rot_row;   /* DEVICE (B,) int32: the row of rev_tab that holds t = 0 of the state row's sigma list */
+} diffab_sample_temperature;
+/* diffab_sample_loop_guided plus `temperature` (nullable) before the stream; temperature == NULL is exactly diffab_sample_loop_guided
+ * (which is unchanged).  Checked before anything is enqueued, DIFFAB_ERR_ARG: rot_scale without rot_row; trans_scale or rot_scale with
+ * DIFFAB_FLAG_KEEP_STRUCTURE; seq_temp with DIFFAB_FLAG_KEEP_SEQUENCE. */
+int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                                int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                                const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                                int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                                const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
+                                const diffab_sample_temperature* temperature, void* stream);
 int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
 int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
