@@ -172,6 +172,12 @@ SYMBOLS = {
     "diffab_pair_embedding_bwd_taped": (C.c_int, [C.POINTER(CtxDims), C.POINTER(PairEmbWeights), C.POINTER(PairEmbWeights), _fp, _fp, _fp, _fp,
                                                   _fp, _i32, _fp, _fp, _fp, _fp, _fp, _sz, _fp, _sz, _fp]),
     "diffab_featurize_xyz": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp, _fp]),
+    # (ca, ca_stride, residue_mask, generation_mask, anchor_mask, chain_idx, antigen_mask, B, N, k, k_antigen, K, index, patch_mask, count, stream)
+    "diffab_patch_select": (C.c_int, [_fp, _i32, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _i32, _fp, _fp, _fp, _fp]),
+    # (src, index, complex_of_row (host int32[rows], nullable), B, N, rows, K, row_bytes, dst, stream)
+    "diffab_patch_gather": (C.c_int, [_fp, _fp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i64, _fp, _fp]),
+    # (patch, index, write_mask (nullable), rows, N, K, row_bytes, dst, stream)
+    "diffab_patch_scatter": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i64, _fp, _fp]),
     "diffab_orientation_loss": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp]),
     "diffab_orientation_loss_bwd": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "diffab_frames_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),

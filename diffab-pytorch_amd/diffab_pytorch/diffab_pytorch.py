@@ -26,6 +26,7 @@ from .diffusion import CoordinateDiffuser, OrientationDiffuser, SequenceDiffuser
 from . import so3 as _so3
 from . import features as _features
 from . import guidance as _guidance
+from . import patch as _patch
 from . import temperature as _temperature
 
 try:  # LightningModule hooks when Lightning is installed; a plain nn.Module otherwise
@@ -1374,6 +1375,48 @@ class DiffAb(_ModuleBase):
                                                      first_patch, t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()),
                        "diffab_sample_loop_shared")
         return {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
+
+    # ------------------------------------------------------------------ from a whole complex (build-defined; the reference cuts patches in preprocess_pdb.py:44-58)
+    @torch.no_grad()
+    def design_complex(self, batch: Dict[str, torch.Tensor], *, k: int = 128, k_antigen: Optional[int] = None, pad_to: int = 128,
+                       **sample_kwargs) -> Dict[str, torch.Tensor]:
+        """Designs for whole complexes: ``batch`` holds the reference's batch fields for B complexes
+        of N residues each - ``seq_idx``, ``xyz`` (B,N,A,3), ``generation_mask`` and, unless ``sample_kwargs`` brings the contexts,
+        ``atom_mask`` and ``chain_idx``; optionally ``orientations`` (taken from xyz with features.featurize on the patch when absent),
+        ``residue_mask``, ``residue_idx`` (default arange(N): the complex's numbering), ``antigen_mask``, ``anchor_mask``,
+        ``backbone_dihedrals``, ``allowed_aa`` (B,N,V).  ``patch.select`` picks the K residues of each patch (k, k_antigen, pad_to as
+        there), ``patch.gather`` brings every per-residue field to patch size, ``sample`` runs on the gathered fields - so the contexts
+        are encoded once per complex, and ``num_samples`` and every other sampler option in ``sample_kwargs`` pass through untouched -
+        and ``patch.paste`` writes the designs back.  Returns sample()'s dict (patch-sized rows) plus ``"patch"``, the PatchIndex, and
+        ``"complex"``: full-length ``seq_idx`` (rows,N), ``translations``, ``orientations`` - the native complex with the generated
+        residues replaced by the design.  Bitwise what the four calls give when made by hand.  The fields sample() takes from the
+        batch cannot be given again in sample_kwargs (ValueError)."""
+        taken = ("generation_mask", "residue_mask", "atom_mask", "chain_idx", "residue_idx", "backbone_dihedrals", "pairwise_dihedrals",
+                 "distmat")
+        clash = [n for n in taken if n in sample_kwargs]
+        if clash:
+            raise ValueError(f"design_complex(): {clash} come from the batch, not from keyword arguments")
+        if not isinstance(batch, dict) or batch.get("xyz") is None or batch.get("generation_mask") is None:
+            raise ValueError("design_complex(): batch must be a dict with xyz and generation_mask (the reference's batch fields)")
+        sel = _patch.select(batch["xyz"], batch["generation_mask"], k=k, k_antigen=k_antigen, antigen_mask=batch.get("antigen_mask"),
+                            anchor_mask=batch.get("anchor_mask"), chain_idx=batch.get("chain_idx"), residue_mask=batch.get("residue_mask"),
+                            pad_to=pad_to)
+        g = _patch.gather(batch, sel)
+        full = batch
+        if g.get("orientations") is None:  # the frames of the patch and of the native complex, from the coordinates
+            g["orientations"] = _features.featurize(g["xyz"], g.get("chain_idx"), g["residue_mask"], backbone_dihedrals=False,
+                                                    pairwise_dihedrals=False)["orientations"]
+            full = dict(batch, orientations=_features.featurize(batch["xyz"], batch.get("chain_idx"), batch.get("residue_mask"),
+                                                                backbone_dihedrals=False, pairwise_dihedrals=False)["orientations"])
+        if "allowed_aa" in g and "allowed_aa" not in sample_kwargs:
+            sample_kwargs["allowed_aa"] = g["allowed_aa"]
+        out = self.sample(g["seq_idx"], g["xyz"], g["orientations"], generation_mask=g["generation_mask"], residue_mask=g["residue_mask"],
+                          atom_mask=g.get("atom_mask"), chain_idx=g.get("chain_idx"), residue_idx=g["residue_idx"],
+                          backbone_dihedrals=g.get("backbone_dihedrals"), **sample_kwargs)
+        out["patch"] = sel
+        out["complex"] = _patch.paste(full, sel, out, num_samples=sample_kwargs.get("num_samples", 1),
+                                      context_index=sample_kwargs.get("context_index"))
+        return out
 
     # ------------------------------------------------------------------ design scoring (build-defined; the training objective per design)
     @torch.no_grad()

@@ -1,5 +1,5 @@
-"""Output side of the path: backbone atoms from the sampled frames, a PDB writer and a
-round-trippable sample file.  The reference stops at frames (x, O) - it has no reconstruction or writer - so this is new,
+"""Input and output side of the path: a PDB reader for whole complexes with the Chothia CDR ranges,
+backbone atoms from the sampled frames, a PDB writer and a round-trippable sample file.  The reference stops at frames (x, O) - it has no reconstruction or writer - so this is new,
 build-defined functionality (nothing here is on the timed path); the atom reconstruction of frames that live on the device runs on
 the HIP frame kernel, file writing is host code.
 
@@ -121,6 +121,99 @@ def write_pdb(path: str, seq_idx: torch.Tensor, translations: torch.Tensor, orie
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
     return n
+
+
+# Chothia-scheme CDR ranges by author residue number, ends included (insertion codes belong to their number)
+CHOTHIA_CDRS = {"H1": (1, 26, 32), "H2": (1, 52, 56), "H3": (1, 95, 102), "L1": (2, 24, 34), "L2": (2, 50, 56), "L3": (2, 89, 97)}
+_BACKBONE_SLOTS = {"N": 0, "CA": 1, "C": 2, "O": 3}
+
+
+def read_pdb(path: str, *, heavy: Optional[str] = None, light: Optional[str] = None, antigen=None, n_atoms: int = 15) -> Dict[str, torch.Tensor]:
+    """A whole complex from a PDB file, as the per-residue fields ``patch.select`` / ``DiffAb.design_complex`` take (no batch axis:
+    stack or unsqueeze(0) them).  ATOM records of the first model; of alternate locations the first one met per atom; hydrogens and OXT
+    are left out.  ``heavy`` / ``light`` name one chain each, ``antigen`` a chain id or a sequence of them; the residues come in that
+    order (heavy, light, antigen chains as listed), ``chain_idx`` 1 heavy, 2 light, 3, 4, ... the antigen chains - write_pdb's A, B, C
+    - and ``antigen_mask`` marks the antigen.  With no chain named every chain is read in file order, numbered from 1, none antigen.
+
+    ``seq_idx`` (N,) int64 in ``AA3`` order (unknown residue names -> UNK); ``xyz`` (N, n_atoms, 3) with N, CA, C, O in slots 0-3 and
+    the side-chain heavy atoms behind them in the record's order (atoms beyond n_atoms are dropped), ``atom_mask`` (N, n_atoms)
+    float32; ``resseq`` (N,) int64 and ``icode`` (N,) uint8 (the character code, 32 = none) as read; ``residue_idx`` (N,) int64: 0
+    at the first residue, one more per residue, plus the gap where the author numbering jumps inside a chain (a new chain continues
+    one after the last); ``residue_mask`` false where N, CA or C is missing.  The slot order behind the backbone is this project's
+    own: parity with protstruc's atom order is UNPINNED.  A named chain that the file does not have raises ValueError."""
+    ag = [] if antigen is None else ([antigen] if isinstance(antigen, str) else list(antigen))
+    named = [(c, n) for c, n in ((heavy, 1), (light, 2))] + [(c, 3 + j) for j, c in enumerate(ag)]
+    named = [(c, n) for c, n in named if c is not None]
+    if n_atoms < 4:
+        raise ValueError("read_pdb: n_atoms must hold the backbone slots N, CA, C, O (>= 4)")
+    chains: Dict[str, list] = {}  # chain id -> residues in file order, each [resname, resseq, icode, {atom name: xyz}, [side-chain names]]
+    with open(path) as f:
+        for line in f:
+            rec = line[:6]
+            if rec.startswith("ENDMDL"):
+                break
+            if rec != "ATOM  " or len(line) < 54:
+                continue
+            name, element = line[12:16].strip(), line[76:78].strip().upper()
+            if element == "H" or element == "D" or (not element and name.lstrip("0123456789")[:1] in ("H", "D")) or name == "OXT":
+                continue
+            ch = line[21]
+            if named and ch not in [c for c, _ in named]:
+                continue
+            key = (line[17:20].strip().upper(), int(line[22:26]), line[26])
+            res = chains.setdefault(ch, [])
+            if not res or tuple(res[-1][:3]) != key:
+                res.append([*key, {}, []])
+            atoms, side = res[-1][3], res[-1][4]
+            if name in atoms:  # a later alternate location of an atom already read
+                continue
+            atoms[name] = (float(line[30:38]), float(line[38:46]), float(line[46:54]))
+            if name not in _BACKBONE_SLOTS:
+                side.append(name)
+    order = named if named else [(c, j + 1) for j, c in enumerate(chains)]
+    for c, _ in order:
+        if c not in chains:
+            raise ValueError(f"read_pdb: {path} has no ATOM records of chain {c!r} (chains: {sorted(chains)})")
+    n = sum(len(chains[c]) for c, _ in order)
+    out = {"seq_idx": torch.full((n,), len(AA3) - 1, dtype=torch.int64), "xyz": torch.zeros(n, n_atoms, 3),
+           "atom_mask": torch.zeros(n, n_atoms), "chain_idx": torch.zeros(n, dtype=torch.int64),
+           "residue_idx": torch.zeros(n, dtype=torch.int64), "resseq": torch.zeros(n, dtype=torch.int64),
+           "icode": torch.full((n,), 32, dtype=torch.uint8), "antigen_mask": torch.zeros(n, dtype=torch.bool),
+           "residue_mask": torch.zeros(n, dtype=torch.bool)}
+    i, ridx = 0, -1
+    for c, number in order:
+        prev = None
+        for resname, resseq, icode, atoms, side in chains[c]:
+            ridx += 1 if prev is None else max(1, resseq - prev)
+            prev = resseq
+            out["seq_idx"][i] = AA3.index(resname) if resname in AA3 else len(AA3) - 1
+            slots = [(s, a) for a, s in _BACKBONE_SLOTS.items() if a in atoms] + [(4 + j, a) for j, a in enumerate(side) if 4 + j < n_atoms]
+            for s, a in slots:
+                out["xyz"][i, s] = torch.tensor(atoms[a])
+                out["atom_mask"][i, s] = 1.0
+            out["chain_idx"][i], out["residue_idx"][i], out["resseq"][i], out["icode"][i] = number, ridx, resseq, ord(icode)
+            out["antigen_mask"][i] = bool(named) and number >= 3
+            out["residue_mask"][i] = all(a in atoms for a in ("N", "CA", "C"))
+            i += 1
+    return out
+
+
+def chothia_cdr_mask(chain_idx: torch.Tensor, resseq: torch.Tensor, cdrs: Sequence[str] = ("H1", "H2", "H3", "L1", "L2", "L3")) -> torch.Tensor:
+    """The ``generation_mask`` of a Chothia-numbered structure (such as the reference's data/all_structures/chothia): true where the
+    residue's author number lies in one of the named CDRs of its chain - heavy (chain_idx 1) H1 26-32, H2 52-56, H3 95-102; light
+    (chain_idx 2) L1 24-34, L2 50-56, L3 89-97, ends included.  An insertion code belongs to its number (100A-100C are in H3), so only
+    ``resseq`` is needed.  These are the scheme's published ranges; parity with protstruc.get_cdr_mask is UNPINNED."""
+    unknown = [c for c in cdrs if c not in CHOTHIA_CDRS]
+    if unknown:
+        raise ValueError(f"chothia_cdr_mask: unknown CDR {unknown[0]!r} (expected some of {sorted(CHOTHIA_CDRS)})")
+    chain_idx, resseq = torch.as_tensor(chain_idx), torch.as_tensor(resseq)
+    if chain_idx.shape != resseq.shape:
+        raise ValueError(f"chothia_cdr_mask: chain_idx is {tuple(chain_idx.shape)}, resseq is {tuple(resseq.shape)}")
+    mask = torch.zeros(chain_idx.shape, dtype=torch.bool, device=chain_idx.device)
+    for c in cdrs:
+        chain, lo, hi = CHOTHIA_CDRS[c]
+        mask |= (chain_idx == chain) & (resseq >= lo) & (resseq <= hi)
+    return mask
 
 
 def write_trajectory_pdb(path: str, trajectory: Dict[str, torch.Tensor], row: int, *, predictions: bool = False,

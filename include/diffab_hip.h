@@ -436,6 +436,49 @@ int diffab_featurize_xyz(const float* xyz, const int64_t* chain_idx, const uint8
                          float* orientations, float* backbone_dihedrals, uint8_t* backbone_dihedrals_mask,
                          float* pairwise_dihedrals, void* stream);
 
+/* Patch construction from a whole complex (what the reference's data layer does with protstruc before a batch exists:
+ * preprocess_pdb.py:44-58 - the nearest-k residues around the CDR anchor residues, united with the nearest-k antigen residues, then
+ * residue_masked_select).  protstruc is not part of the reference tree: the selection below is this library's own definition, and parity
+ * with protstruc's get_cdr_anchor_mask / get_topk_nearest_residue_mask is UNPINNED (as for diffab_featurize_xyz).
+ *
+ * diffab_patch_select: B complexes padded to N residues each (N <= DIFFAB_PATCH_MAX_RESIDUES).  ca: the CA of residue (b, i) is the three
+ * floats at ca[(b * N + i) * ca_stride] (ca_stride = 3 for a packed (B,N,3) array; A * 3 with ca pointing at atom slot 1 of an (B,N,A,3)
+ * array).  residue_mask (B,N) (NULL: all present), generation_mask (B,N), anchor_mask (B,N) or NULL, chain_idx (B,N) or NULL (one chain),
+ * antigen_mask (B,N) or NULL.  Outputs: index (B,K) int64, patch_mask (B,K), count (B) int32.  Per complex:
+ *   1. Anchors.  With anchor_mask NULL, residue i is an anchor when it is present, not generated, and residue i-1 or i+1 is present,
+ *      generated and has the same chain_idx (the residues flanking each generated segment); with an anchor_mask, when it is present and
+ *      marked.  "Generated" always means present and marked in generation_mask.  A complex with a generated residue and no anchor uses
+ *      the generated residues themselves as anchors.  A complex with no generated residue: count = 0.
+ *   2. Key.  key_i = min over anchors a of ((x_i-x_a)^2 + (y_i-y_a)^2) + (z_i-z_a)^2, in fp32, in exactly this association and without
+ *      contraction (the translation unit is built with -ffp-contract=off), so the value is a defined fp32 number.  Generated residues
+ *      and anchors get key -1: they are always in the patch.
+ *   3. Order.  Residues are ranked by (key, index) ascending: ties go to the lower index.  S1 = the first k present residues; S2 = the
+ *      first k_antigen present residues with antigen_mask; the patch is the union of S1 and S2.
+ *   4. Output.  index[b, :count] = the patch in ascending residue index (chain order is kept), index[b, count:] = -1, patch_mask true on
+ *      the first count slots.  count <= k + k_antigen.
+ * Refused before anything is enqueued: K < k + k_antigen, k < 1, k_antigen < 0, k_antigen > 0 with a NULL antigen_mask (DIFFAB_ERR_ARG);
+ * N > DIFFAB_PATCH_MAX_RESIDUES (DIFFAB_ERR_UNSUPPORTED).  More generated-plus-anchor residues than k cannot be known on the host: that
+ * complex gets count[b] = -1, an all-(-1) index row and an all-false patch_mask row.
+ * One work-group per complex: the packed (key, index) words of the whole complex are sorted in LDS, hence the limit on N. */
+#define DIFFAB_PATCH_MAX_RESIDUES 4096
+int diffab_patch_select(const float* ca, int32_t ca_stride, const uint8_t* residue_mask, const uint8_t* generation_mask,
+                        const uint8_t* anchor_mask, const int64_t* chain_idx, const uint8_t* antigen_mask, int32_t B, int32_t N, int32_t k,
+                        int32_t k_antigen, int32_t K, int64_t* index, uint8_t* patch_mask, int32_t* count, void* stream);
+/* diffab_patch_gather (preprocess_pdb.py:44-58, the residue_masked_select): dst (rows,K,row_bytes) = src (B,N,row_bytes) at index (rows,K);
+ * slots whose index is outside [0, N) (the -1 padding) are zero-filled.  Row r reads complex complex_of_row[r], a HOST array of rows
+ * entries in [0, B) (an entry outside: DIFFAB_ERR_ARG, nothing enqueued; it travels as launch arguments, so it may be freed on return);
+ * NULL: row r reads complex r and rows must equal B.  row_bytes is any positive size - the bytes of one residue of the field, so one
+ * entry serves every per-residue field (seq_idx 8, xyz A * 12, orientations 36, masks 1, ...); copies move 16, 4 or 1 bytes per lane,
+ * whichever the size and the two addresses allow. */
+int diffab_patch_gather(const void* src, const int64_t* index, const int32_t* complex_of_row, int32_t B, int32_t N, int32_t rows, int32_t K,
+                        int64_t row_bytes, void* dst, void* stream);
+/* diffab_patch_scatter, the inverse for results (the reference never pastes a patch back; preprocess_pdb.py:44-58 is the cut it undoes):
+ * dst[r, index[r, p]] = patch[r, p] for patch (rows,K,row_bytes), index (rows,K), into dst (rows,N,row_bytes) that the caller has
+ * pre-filled (with the native complex, one copy per design row).  Slots with an index outside [0, N) or a false write_mask (rows,K;
+ * NULL: all true) write nothing.  An index row must not name a residue twice (diffab_patch_select's rows never do). */
+int diffab_patch_scatter(const void* patch, const int64_t* index, const uint8_t* write_mask, int32_t rows, int32_t N, int32_t K,
+                         int64_t row_bytes, void* dst, void* stream);
+
 /* Backward of the two context encoders (training through encode_context, diffab_pytorch.py:843-854 under autograd).
  * d_out is the gradient w.r.t. the module output; parameter gradients ACCUMULATE (+=) into the buffers of `g`, which has the
  * layout of the weight struct (the caller zero-fills them).  Inputs other than parameters take no gradient.  Nothing is taped:
