@@ -178,6 +178,13 @@ SYMBOLS = {
     "diffab_patch_gather": (C.c_int, [_fp, _fp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i64, _fp, _fp]),
     # (patch, index, write_mask (nullable), rows, N, K, row_bytes, dst, stream)
     "diffab_patch_scatter": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _i64, _fp, _fp]),
+    # (seq_idx, points, native_seq_idx, native_points, generation_mask, residue_mask (nullable), segment_idx (nullable), rows, group_size, K, P, S,
+    #  aar, rmsd, rmsd_aligned, segment_aar, segment_rmsd, segment_rmsd_aligned, stream)
+    "diffab_metrics_vs_native": (C.c_int, [_fp] * 7 + [_i32] * 5 + [_fp] * 7),
+    # (seq_idx, points, generation_mask, residue_mask (nullable), G, N, K, P, aligned, rmsd, seq_identity, workspace, workspace_bytes, stream)
+    "diffab_metrics_pairwise": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp, _fp, _fp, _sz, _fp]),
+    # (dist, score (nullable), candidates (nullable), G, N, m, index, min_dist, count, stream)
+    "diffab_metrics_select_diverse": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp]),
     "diffab_orientation_loss": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp]),
     "diffab_orientation_loss_bwd": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "diffab_frames_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),

@@ -216,6 +216,19 @@ def chothia_cdr_mask(chain_idx: torch.Tensor, resseq: torch.Tensor, cdrs: Sequen
     return mask
 
 
+def chothia_cdr_index(chain_idx: torch.Tensor, resseq: torch.Tensor) -> torch.Tensor:
+    """int64 labels 0..5 for H1, H2, H3, L1, L2, L3 (the ranges of ``chothia_cdr_mask``) and -1 elsewhere: the ``segment_idx`` of
+    ``metrics.evaluate`` for per-CDR numbers.  ``chothia_cdr_index(...) >= 0`` equals ``chothia_cdr_mask(...)``."""
+    chain_idx, resseq = torch.as_tensor(chain_idx), torch.as_tensor(resseq)
+    if chain_idx.shape != resseq.shape:
+        raise ValueError(f"chothia_cdr_index: chain_idx is {tuple(chain_idx.shape)}, resseq is {tuple(resseq.shape)}")
+    index = torch.full(chain_idx.shape, -1, dtype=torch.int64, device=chain_idx.device)
+    for label, c in enumerate(("H1", "H2", "H3", "L1", "L2", "L3")):
+        chain, lo, hi = CHOTHIA_CDRS[c]
+        index[(chain_idx == chain) & (resseq >= lo) & (resseq <= hi)] = label
+    return index
+
+
 def write_trajectory_pdb(path: str, trajectory: Dict[str, torch.Tensor], row: int, *, predictions: bool = False,
                          chain_idx: Optional[torch.Tensor] = None, residue_idx: Optional[torch.Tensor] = None,
                          residue_mask: Optional[torch.Tensor] = None, atoms: Sequence[str] = ("N", "CA", "C", "O")) -> int:

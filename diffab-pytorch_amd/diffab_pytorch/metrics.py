@@ -1,0 +1,194 @@
+"""Design metrics on the device: what came out of ``DiffAb.sample`` next to the native and next to each other.
+
+``evaluate``        per design: amino-acid recovery, RMSD in the fixed framework and after superposition, whole row and per segment (CDR);
+``pairwise``        per patch: the N x N RMSD and sequence-identity matrices of its N designs;
+``select_diverse``  greedy farthest-point choice of m designs per patch from such a matrix.
+
+Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` returns them - ``seq_idx`` (rows,K), ``translations``
+(rows,K,3), ``orientations`` (rows,K,3,3) with ``rows = G * group_size``, row ``g * group_size + r`` = design r of patch g - and the masks
+per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
+the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` in ``include/diffab_hip.h``; every number is computed
+by the HIP kernels of ``csrc/metrics_kernels.hip`` and there is no torch fallback.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import _hip
+from .io import backbone_from_frames
+
+MAX_GROUP = 4096  # DIFFAB_METRICS_MAX_GROUP: designs per patch
+MAX_K = 4096  # DIFFAB_METRICS_MAX_K
+MAX_SEGMENTS = 8  # DIFFAB_METRICS_MAX_SEGMENTS
+ATOMS = {"ca": None, "backbone": ("N", "CA", "C", "O")}
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _check_frames(who: str, name: str, d, atoms: str):
+    """seq_idx (R,K) integer, translations (R,K,3) float, orientations (R,K,3,3) float (needed for the backbone only) -> (R, K)."""
+    if not isinstance(d, dict) or not isinstance(d.get("seq_idx"), torch.Tensor) or not isinstance(d.get("translations"), torch.Tensor):
+        raise ValueError(f"{who}: {name} must be a dict with seq_idx and translations (and orientations for atoms='backbone')")
+    seq, x = d["seq_idx"], d["translations"]
+    if seq.dim() != 2 or seq.is_floating_point() or seq.dtype == torch.bool:
+        raise ValueError(f"{who}: {name}['seq_idx'] must be an integer tensor (rows, K), got {tuple(seq.shape)} {seq.dtype}")
+    R, K = int(seq.shape[0]), int(seq.shape[1])
+    if not x.is_floating_point() or tuple(x.shape) != (R, K, 3):
+        raise ValueError(f"{who}: {name}['translations'] is {tuple(x.shape)} {x.dtype}, expected a float tensor {(R, K, 3)}")
+    if atoms == "backbone":
+        O = d.get("orientations")
+        if not isinstance(O, torch.Tensor) or not O.is_floating_point() or tuple(O.shape) != (R, K, 3, 3):
+            raise ValueError(f"{who}: {name}['orientations'] must be a float tensor {(R, K, 3, 3)} for atoms='backbone'")
+    return R, K
+
+
+def _check_common(who: str, designs, generation_mask, residue_mask, group_size, atoms):
+    if atoms not in ATOMS:
+        raise ValueError(f"{who}: atoms must be 'ca' or 'backbone', got {atoms!r}")
+    rows, K = _check_frames(who, "designs", designs, atoms)
+    if not _is_int(group_size) or group_size < 1:
+        raise ValueError(f"{who}: group_size must be an int >= 1, got {group_size!r}")
+    if group_size > MAX_GROUP:
+        raise ValueError(f"{who}: group_size = {group_size}, at most {MAX_GROUP} designs per patch")
+    if rows % group_size != 0:
+        raise ValueError(f"{who}: {rows} design rows are not a multiple of group_size = {group_size}")
+    if K < 1 or K > MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch outside [1, {MAX_K}]")
+    G = rows // group_size
+    for name, m in (("generation_mask", generation_mask), ("residue_mask", residue_mask)):
+        if m is None and name == "residue_mask":
+            continue
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.bool:
+            raise ValueError(f"{who}: {name} must be a bool tensor")
+        if tuple(m.shape) != (G, K):
+            raise ValueError(f"{who}: {name} is {tuple(m.shape)}, expected {(G, K)} (one row per patch)")
+    return rows, G, K
+
+
+def _points(d, atoms: str) -> torch.Tensor:
+    """(R,K,P,3) fp32 on the device: the CA, or N, CA, C, O from the frames through the frame kernel."""
+    x = _hip.dev_f32(d["translations"])
+    if atoms == "ca":
+        return x.unsqueeze(2).contiguous()
+    return _hip.dev_f32(backbone_from_frames(x, _hip.dev_f32(d["orientations"]), ATOMS[atoms]))
+
+
+def evaluate(designs: Dict[str, torch.Tensor], native: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
+             residue_mask: Optional[torch.Tensor] = None, segment_idx: Optional[torch.Tensor] = None, num_segments: Optional[int] = None,
+             group_size: int = 1, atoms: str = "ca") -> Dict[str, torch.Tensor]:
+    """Each design against the native of its patch, over the counted residues: ``aar`` (fraction of native tokens recovered), ``rmsd``
+    (no superposition: the framework is fixed, the patch frame is the alignment - the DiffAb number) and ``rmsd_aligned`` (the Kabsch
+    minimum over proper rotations and translations), each (rows,).  ``designs`` is the dict ``sample()`` returns (with
+    ``design_complex``, its ``out``), ``native`` holds the patch's own ``seq_idx`` (G,K), ``translations`` and ``orientations`` - the
+    fields ``sample()`` was called with - and ``group_size`` is its ``num_samples``.  ``atoms``: ``'ca'`` or ``'backbone'`` (N, CA, C,
+    O from the frames).  ``segment_idx`` (G,K) integer labels in [0, ``num_segments``) (negative: no segment; ``num_segments`` defaults
+    to the largest label + 1, at most 8) adds ``segment_aar``, ``segment_rmsd`` and ``segment_rmsd_aligned`` (rows, num_segments):
+    ``io.chothia_cdr_index`` gives the labels of the six CDRs.  One C-ABI call; results on the device of ``designs['seq_idx']``.
+
+    ValueError, naming the argument, before any device work for shapes and dtypes that do not match, rows that are no multiple of
+    ``group_size``, more than 8 segments, more than 4096 designs per patch and an unknown ``atoms``."""
+    who = "metrics.evaluate()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, atoms)
+    nG, nK = _check_frames(who, "native", native, atoms)
+    if (nG, nK) != (G, K):
+        raise ValueError(f"{who}: native['seq_idx'] is {(nG, nK)}, expected {(G, K)} (one row per patch)")
+    S = 0
+    if segment_idx is not None:
+        if not isinstance(segment_idx, torch.Tensor) or segment_idx.is_floating_point() or segment_idx.dtype == torch.bool:
+            raise ValueError(f"{who}: segment_idx must be an integer tensor")
+        if tuple(segment_idx.shape) != (G, K):
+            raise ValueError(f"{who}: segment_idx is {tuple(segment_idx.shape)}, expected {(G, K)}")
+        if num_segments is None:
+            num_segments = max(1, int(segment_idx.max()) + 1) if segment_idx.numel() else 1
+        if not _is_int(num_segments) or num_segments < 1 or num_segments > MAX_SEGMENTS:
+            raise ValueError(f"{who}: num_segments = {num_segments!r} (segment_idx labels up to it) outside [1, {MAX_SEGMENTS}]")
+        S = num_segments
+    elif num_segments is not None:
+        raise ValueError(f"{who}: num_segments without segment_idx")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    P = 1 if atoms == "ca" else len(ATOMS[atoms])
+    seq, pts = _hip.dev_i64(designs["seq_idx"]), _points(designs, atoms)
+    nseq, npts = _hip.dev_i64(native["seq_idx"]), _points(native, atoms)
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    seg = None if segment_idx is None else _hip.dev_i64(segment_idx)
+    whole = [torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(3)]
+    parts = [torch.empty(rows, S, dtype=torch.float32, device=dev) if S else None for _ in range(3)]
+    _hip.check(lib.diffab_metrics_vs_native(_hip.ptr(seq), _hip.ptr(pts), _hip.ptr(nseq), _hip.ptr(npts), _hip.ptr(gm), _hip.ptr(rm),
+                                            _hip.ptr(seg), rows, group_size, K, P, S, *[_hip.ptr(t) for t in whole + parts],
+                                            _hip.stream_ptr()), "diffab_metrics_vs_native")
+    out = dict(zip(("aar", "rmsd", "rmsd_aligned"), whole))
+    if S:
+        out.update(zip(("segment_aar", "segment_rmsd", "segment_rmsd_aligned"), parts))
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+def pairwise_workspace_bytes(G: int, N: int, K: int, P: int) -> int:
+    """DIFFAB_METRICS_PAIRWISE_WORKSPACE_BYTES of include/diffab_hip.h."""
+    return G * N * (K * P * 12 + (K + 3) // 4 * 4 + 32) + G * 4 + 1024
+
+
+def pairwise(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, residue_mask: Optional[torch.Tensor] = None,
+             group_size: int, atoms: str = "ca", aligned: bool = False) -> Dict[str, torch.Tensor]:
+    """The designs of each patch against each other, over the patch's counted residues: ``rmsd`` (G,N,N) fp32 - in place, or the Kabsch
+    minimum with ``aligned=True`` - and ``seq_identity`` (G,N,N) fp32, the fraction of counted residues with equal tokens;
+    N = ``group_size``.  Both are symmetric to the bit; the diagonal is 0 / 1 by definition (NaN for a patch without a counted
+    residue).  ``1 - seq_identity`` or ``rmsd`` is a distance matrix for ``select_diverse``.  One C-ABI call (two launches); the
+    call's workspace is about the size of the designs' points.  ValueError before any device work as for ``evaluate``."""
+    who = "metrics.pairwise()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, atoms)
+    if not isinstance(aligned, bool):
+        raise ValueError(f"{who}: aligned must be a bool, got {aligned!r}")
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    N, P = group_size, 1 if atoms == "ca" else len(ATOMS[atoms])
+    seq, pts = _hip.dev_i64(designs["seq_idx"]), _points(designs, atoms)
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    rmsd = torch.empty(G, N, N, dtype=torch.float32, device=dev)
+    ident = torch.empty(G, N, N, dtype=torch.float32, device=dev)
+    nbytes = pairwise_workspace_bytes(G, N, K, P)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_pairwise(_hip.ptr(seq), _hip.ptr(pts), _hip.ptr(gm), _hip.ptr(rm), G, N, K, P, int(aligned), _hip.ptr(rmsd),
+                                           _hip.ptr(ident), _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_pairwise")
+    return {"rmsd": rmsd.to(out_dev), "seq_identity": ident.to(out_dev)}
+
+
+def select_diverse(dist: torch.Tensor, m: int, *, score: Optional[torch.Tensor] = None,
+                   candidates: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Greedy farthest-point choice of ``m`` designs per patch from ``dist`` (G,N,N) fp32 (``pairwise``'s ``rmsd``, or
+    ``1 - seq_identity``).  The first pick is the candidate with the lowest ``score`` (G,N) (ties to the lower index; a NaN score counts
+    as +inf), or the first candidate without ``score``; every next pick is the candidate whose smallest distance to the picked ones is
+    largest (ties to the lower index, a NaN distance counts as 0).  ``candidates`` (G,N) bool restricts the choice.  Returns ``index``
+    (G,m) int64, ``min_dist`` (G,m) fp32 - that smallest distance when the design was picked, +inf for the first - and ``count`` (G,)
+    int32; with fewer than ``m`` candidates the tail is -1 / NaN.  Comparisons only: the result is a function of the fp32 matrix."""
+    who = "metrics.select_diverse()"
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 3 or dist.shape[1] != dist.shape[2]:
+        raise ValueError(f"{who}: dist must be a float32 tensor (G, N, N)")
+    G, N = int(dist.shape[0]), int(dist.shape[1])
+    if N < 1 or N > MAX_GROUP:
+        raise ValueError(f"{who}: dist has N = {N} designs per patch, outside [1, {MAX_GROUP}]")
+    if not _is_int(m) or m < 0:
+        raise ValueError(f"{who}: m must be an int >= 0, got {m!r}")
+    if score is not None and (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (G, N)):
+        raise ValueError(f"{who}: score must be a float tensor {(G, N)}")
+    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.bool
+                                   or tuple(candidates.shape) != (G, N)):
+        raise ValueError(f"{who}: candidates must be a bool tensor {(G, N)}")
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), dist.device
+    d = _hip.dev_f32(dist)
+    sc = None if score is None else _hip.dev_f32(score)
+    cand = None if candidates is None else _hip.dev_mask(candidates)
+    index = torch.empty(G, m, dtype=torch.int64, device=dev)
+    min_dist = torch.empty(G, m, dtype=torch.float32, device=dev)
+    count = torch.empty(G, dtype=torch.int32, device=dev)
+    _hip.check(lib.diffab_metrics_select_diverse(_hip.ptr(d), _hip.ptr(sc), _hip.ptr(cand), G, N, m, _hip.ptr(index), _hip.ptr(min_dist),
+                                                 _hip.ptr(count), _hip.stream_ptr()), "diffab_metrics_select_diverse")
+    return {"index": index.to(out_dev), "min_dist": min_dist.to(out_dev), "count": count.to(out_dev)}

@@ -479,6 +479,64 @@ int diffab_patch_gather(const void* src, const int64_t* index, const int32_t* co
 int diffab_patch_scatter(const void* patch, const int64_t* index, const uint8_t* write_mask, int32_t rows, int32_t N, int32_t K,
                          int64_t row_bytes, void* dst, void* stream);
 
+/* Design metrics: what a batch of designs looks like next to the native and next to each other.  The reference has
+ * no evaluation code; these are the numbers DiffAb-style evaluations report (RMSD of the designed residues in the fixed framework, amino-acid
+ * recovery) plus the Kabsch minimum and the all-pairs matrices of the designs of one patch.
+ *
+ * Common layout.  Designs are rows = G * N rows of K residues, row g * N + r = design r of group g (sample(num_samples = N)'s layout).
+ * points (rows,K,P,3) fp32: P points per residue, 1 <= P <= DIFFAB_METRICS_MAX_POINTS (P = 1: the CA; P = 4: N, CA, C, O).  Per group:
+ * generation_mask (G,K), residue_mask (G,K) or NULL (all present).  A residue COUNTS when it is generated and inside residue_mask; a row
+ * with n counted residues has m = n * P counted points, taken in ascending residue order.  A mean over an empty selection is NaN.
+ * Limits (DIFFAB_ERR_ARG, with the shape and null-pointer checks, before anything is enqueued): 1 <= N <= DIFFAB_METRICS_MAX_GROUP,
+ * 1 <= K <= DIFFAB_METRICS_MAX_K, P as above.  rows = 0 / G = 0 succeeds without looking at a pointer.
+ *
+ * diffab_metrics_vs_native: per design row against its group's native_seq_idx (G,K) and native_points (G,K,P,3):
+ *   aar          = (counted residues whose token equals the native's) / n, one fp32 division of the two integers;
+ *   rmsd         = sqrt(sum |p - q|^2 / m), no superposition (the framework is fixed: the patch frame is the alignment);
+ *   rmsd_aligned = sqrt(msd), msd = the minimum of the same over proper rotations and translations of the design: both sets centred,
+ *                  H = sum p q^T, singular values s1 >= s2 >= s3, d = sign(det H) (+1 at 0),
+ *                  msd = max(0, sum |p|^2 + sum |q|^2 - 2 (s1 + s2 + d s3)) / m.  One point gives 0; a mirror image does not align.
+ * All sums, the centroids and the solve are fp64 (one wave per row: per-lane partial sums in ascending residue order, one fixed butterfly);
+ * the singular values are the column norms of H after one-sided Jacobi (Hestenes) sweeps.  A row's numbers do not depend on the other
+ * rows of the call.  segment_idx (G,K) int64 or NULL with S = 0: labels in [0, S), S <= DIFFAB_METRICS_MAX_SEGMENTS, anything else = no
+ * segment; the same three numbers over the counted residues of each segment go to segment_* (rows,S). */
+#define DIFFAB_METRICS_MAX_GROUP 4096
+#define DIFFAB_METRICS_MAX_K 4096
+#define DIFFAB_METRICS_MAX_POINTS 5
+#define DIFFAB_METRICS_MAX_SEGMENTS 8
+int diffab_metrics_vs_native(const int64_t* seq_idx, const float* points, const int64_t* native_seq_idx, const float* native_points,
+                             const uint8_t* generation_mask, const uint8_t* residue_mask, const int64_t* segment_idx, int32_t rows,
+                             int32_t group_size, int32_t K, int32_t P, int32_t S, float* aar, float* rmsd, float* rmsd_aligned,
+                             float* segment_aar, float* segment_rmsd, float* segment_rmsd_aligned, void* stream);
+/* diffab_metrics_pairwise: for every group the symmetric matrices rmsd (G,N,N) and seq_identity (G,N,N) over the group's counted residues.
+ *   rmsd[g,i,j], aligned = 0: sqrt(acc / m) in fp32, acc = the fp32 sum over the counted points, in ascending order, of
+ *                ((acc + dx*dx) + dy*dy) + dz*dz with dx = x_i - x_j one rounded subtraction of the inputs (no |a|^2 + |b|^2 - 2ab form,
+ *                no contraction: the translation unit is built with -ffp-contract=off).
+ *   rmsd[g,i,j], aligned = 1: rmsd_aligned of diffab_metrics_vs_native with design j as the native: centroids, H (through fma) and the
+ *                spreads in fp64 from the fp32 inputs, the same fp64 solve, one rounding to fp32 at the end.
+ *   seq_identity[g,i,j] = (counted residues with equal tokens) / n in fp32.  Tokens are compared by their low 8 bits.
+ * The diagonal is defined, not computed: rmsd 0, identity 1 (NaN for an empty selection).  A pair is computed once (by j > i) and stored
+ * twice, so entry (i,j) is bitwise entry (j,i).  The in-place number is NOT bitwise diffab_metrics_vs_native's rmsd (fp32 running sum
+ * here, fp64 sums there); both are within 1e-4 relative of the exact value.
+ * workspace: DIFFAB_METRICS_PAIRWISE_WORKSPACE_BYTES(G, N, K, P) bytes of device memory, 16-byte aligned (too small: DIFFAB_ERR_WORKSPACE):
+ * the counted points and tokens of each group, compacted and with the designs along the fastest axis, and the fp64 centroids.
+ * Two launches: the packing, then one work-group per 64 x 64 (aligned: 32 x 32) tile of pairs on or above the diagonal. */
+#define DIFFAB_METRICS_PAIRWISE_WORKSPACE_BYTES(G, N, K, P) \
+  ((size_t)(G) * (size_t)(N) * ((size_t)(K) * (size_t)(P) * 12 + ((size_t)(K) + 3) / 4 * 4 + 32) + (size_t)(G) * 4 + 1024)
+int diffab_metrics_pairwise(const int64_t* seq_idx, const float* points, const uint8_t* generation_mask, const uint8_t* residue_mask,
+                            int32_t G, int32_t N, int32_t K, int32_t P, int32_t aligned, float* rmsd, float* seq_identity, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* diffab_metrics_select_diverse: greedy farthest-point choice of m designs per group from dist (G,N,N) fp32 (either matrix above, or
+ * 1 - identity).  candidates (G,N) or NULL (all); score (G,N) fp32 or NULL.
+ *   first pick: the candidate with the lowest score (a NaN score counts as +inf; ties to the lower index); without score the first one;
+ *   then:       among the candidates not picked, the one whose minimum over the picked p of dist[g,p,c] (row of the pick; a NaN distance
+ *               counts as 0) is largest, ties to the lower index.
+ * index (G,m) int64, min_dist (G,m) fp32 = that minimum at the moment of the pick (+inf for the first), count (G) int32 = picks made;
+ * with fewer than m candidates the tail is -1 / NaN.  Loads, min, max and compares only: the result is a function of the fp32 matrix.
+ * One work-group per group; N <= DIFFAB_METRICS_MAX_GROUP, m >= 0 (DIFFAB_ERR_ARG). */
+int diffab_metrics_select_diverse(const float* dist, const float* score, const uint8_t* candidates, int32_t G, int32_t N, int32_t m,
+                                  int64_t* index, float* min_dist, int32_t* count, void* stream);
+
 /* Backward of the two context encoders (training through encode_context, diffab_pytorch.py:843-854 under autograd).
  * d_out is the gradient w.r.t. the module output; parameter gradients ACCUMULATE (+=) into the buffers of `g`, which has the
  * layout of the weight struct (the caller zero-fills them).  Inputs other than parameters take no gradient.  Nothing is taped:
