@@ -216,16 +216,17 @@ static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const Step
   p.pair_planes = use_pair_planes(d, flags, pair_ctx, b) ? b.pair : nullptr;
   p.ctx_of_row = ctx_of_row;
   p.n_ctx = n_ctx;
-  // DIFFAB_FLAG_SKIP_UNUSED_ROWS (reverse sampler): the step's outputs (eps, O0, posterior) are read for GENERATED residues only
-  // (reverse_update leaves the others alone), so the last layer's attention is needed only for row tiles that contain one; every
-  // other layer feeds keys and values of all rows to the next.  Same trajectory, bit for bit; the work skipped depends on the mask,
-  // so bench.py's headline keeps it off.
-  p.last_layer_tiles = (flags & DIFFAB_FLAG_SKIP_UNUSED_ROWS) && p.fold && d->K % 16 == 0 ? tiles : nullptr;
+  // Reverse sampler (tiles != nullptr): the step's outputs (eps, O0, posterior) are read for GENERATED residues only (reverse_update,
+  // its heads epilogue, guidance and the record leave the others alone), so the last layer's attention is needed only for row tiles
+  // that contain one; every other layer feeds keys and values of all rows to the next.  Same trajectory, bit for bit, on both launch
+  // forms; DIFFAB_FLAG_ALL_ROWS keeps every tile.  (NL >= 2: a skipped tile's feature rows then hold the previous layer's values of
+  // this very forward - never an unwritten workspace.)
+  p.last_layer_tiles = tiles != nullptr && !(flags & DIFFAB_FLAG_ALL_ROWS) && p.fold && d->K % 16 == 0 && d->NL >= 2 ? tiles : nullptr;
   p.res_emb = res_emb;
   // The module launch of a loop: bitwise the 3 NL launches it replaces, so the choice never shows in the results.  When the batch fills
   // the chip with one work-group per patch it wins (B = 256: 2.60 ms per step against 2.70); fewer patches than CUs leave CUs idle for
   // the whole module (B = 8: 2.07 ms against 0.47), a ragged last round of patches costs a module time for a few of them.
-  p.persistent = p.b6 && p.pair_planes != nullptr && ipa_module_persistent_supported(d) && p.last_layer_tiles == nullptr &&
+  p.persistent = p.b6 && p.pair_planes != nullptr && ipa_module_persistent_supported(d) &&
                  ((flags & DIFFAB_FLAG_PERSISTENT_MODULE) || (loop && !(flags & DIFFAB_FLAG_MULTI_LAUNCH) && module_launch_fills_chip(d)));
   p.fused_mlps = p.persistent && p.chain && D == 128 && res_emb == nullptr;
   return p;
@@ -329,7 +330,7 @@ static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, 
   }
   if (p.persistent) {
     if (int rc = launch_ipa_module_persistent(d, b.hA, b.hB, O_t, x_t, b.ipa, b.planes, p.pair_planes, st, p.fused_mlps ? res_ctx : nullptr,
-                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx))
+                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx, p.last_layer_tiles))
       return rc;
     cur = (d->NL & 1) ? b.hB : b.hA;
   }
@@ -401,7 +402,7 @@ constexpr int kTrajRows = 1025;  // schedules up to T = 1024 get their per-step 
 struct SampleBuffers {
   float *beta, *eps, *O0, *post;
   int* t_dev;  // the current timestep in device memory (graph replay)
-  unsigned char* tiles;  // [B][K / 16]: row tiles with a generated residue (DIFFAB_FLAG_SKIP_UNUSED_ROWS)
+  unsigned char* tiles;  // [B][K / 16]: row tiles with a generated residue (the last layer's attention runs for these only)
   float* beta_traj;      // [3 heads][kTrajRows][D]: the heads' folded beta columns of every step of a schedule with T < kTrajRows
   int* ctx_of_row;       // shared contexts: [B] the context of every state row (device copy of the caller's map)
   float* res_ctx;        // shared contexts: [B][K][D] the residue context of every state row (gathered once per call)
@@ -532,6 +533,12 @@ int diffab_debug_set_module_stagger(int32_t ticks_10ns, int32_t classes) {
 int diffab_debug_set_module_stamps(void* device_buffer) {
   set_module_stamps(device_buffer);
   return DIFFAB_OK;
+}
+
+int diffab_debug_row_tiles(const uint8_t* gen_mask, int32_t B, int32_t K, uint8_t* tiles, void* stream) {
+  StreamOrder order_(stream);
+  DIFFAB_REQUIRE(gen_mask && tiles && B >= 1 && K >= 16 && K % 16 == 0, DIFFAB_ERR_ARG, "debug_row_tiles: need B >= 1 and K a multiple of 16");
+  return launch_tiles_needed(gen_mask, B, K, tiles, as_stream(stream));
 }
 
 int diffab_debug_set_attn_variant(int32_t v) { return set_attn_variant(v); }
@@ -1099,7 +1106,7 @@ int diffab_score_designs(const diffab_dims* d, const diffab_denoiser_weights* w,
   const ScoreBuffers sb = carve_score(d, workspace, n_ctx);
   DIFFAB_REQUIRE(workspace_bytes >= sb.bytes, DIFFAB_ERR_WORKSPACE, "score_designs: workspace %zu < %zu bytes", workspace_bytes, sb.bytes);
   // (the reverse loop's graph replay and skipped row tiles have no meaning here; the design-mode bits steer the noising and the terms)
-  flags &= ~(keep | DIFFAB_FLAG_GRAPH_SAMPLER | DIFFAB_FLAG_SKIP_UNUSED_ROWS);
+  flags &= ~(keep | DIFFAB_FLAG_GRAPH_SAMPLER | DIFFAB_FLAG_SKIP_UNUSED_ROWS | DIFFAB_FLAG_ALL_ROWS);
   hipStream_t st = as_stream(stream);
   DIFFAB_HIP_CHECK(hipMemcpyAsync(sb.t_list, t_list, sizeof(int32_t) * n_t, hipMemcpyHostToDevice, st));
   const StepBuffers b0 = carve_step(d, sb.step, n_ctx);

@@ -114,7 +114,8 @@ int ipa_layer_split_weights(const diffab_ipa_layer_weights* w, void* planes, hip
 bool ipa_module_persistent_supported(const diffab_dims* d);
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X = nullptr, const MlpChainSet* emb = nullptr,
-                                 const MlpChainSet* heads = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0);
+                                 const MlpChainSet* heads = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0,
+                                 const unsigned char* last_layer_tiles = nullptr);  // [B][K / 16]: as ipa_layer_fast's tile_needed
 void set_module_stagger(int ticks, int classes);  // diagnostics: start-up stagger of the persistent module kernel (10 ns ticks)
 void set_module_stamps(void* device_buffer);      // diagnostics: phase stamps of the persistent module kernel
 // bias tables of the folded concatenations (see denoiser_fast.hip): emb_tab[25][D] depends on the weights only; beta_tab[3 heads][B][D]

@@ -42,6 +42,8 @@ struct ModuleArgs {
   const float* pair;         // fp16 planes of the pair embedding (launch_pair_split)
   const float* esc;          // {s, 1 / s} per pair row
   const int* ctx_of_row;     // shared contexts: [B] context of each patch's pair rows (null: the identity)
+  // reverse sampler: [B][K / 16] row tiles of the LAST layer whose outputs are read (null: all; 4-byte aligned)
+  const unsigned char* last_layer_tiles;
   const float* R;            // [B K][9]
   const float* t;            // [B K][3]
   const char* planes;        // per layer: ipa_layer_planes_bytes() (w_bias, gamma, b_out | projection planes | to_out planes | 1 / scales)
@@ -55,6 +57,14 @@ struct ModuleArgs {
   int stagger_ticks, stagger_classes;  // the work-groups of class c = (blockIdx / 8) % classes start c * ticks (10 ns each) late
 };
 }  // namespace
+
+// Byte idx of the row-tile map through a scalar load of its aligned word (as attn_shift_pair_rows: a kernel that also stores to global
+// memory would otherwise get a vector load and a readfirstlane): the skip decision stays off the vector pipe, in an SGPR.
+__device__ __forceinline__ bool module_tile_needed(const unsigned char* __restrict__ map, const int idx) {
+  unsigned w;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(map + (idx & ~3)) : "memory");
+  return ((w >> (8 * (idx & 3))) & 0xffu) != 0;
+}
 
 // KRES: residues per patch - 128 (one 128-row dense tile per patch, single-chunk attention items) or 256 (BASELINE config 5: two dense
 // tiles, sixteen attention items of two 128-key chunks with the online softmax across them - ipa_attn_tile<8, true, ...>)
@@ -127,8 +137,15 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
       __syncthreads();
       pstamp(b, l, 1);
       // ---- attention: the eight row tiles of the patch
+      // last_layer_tiles (reverse sampler): the step's outputs are read for generated residues only, and the last layer's attention
+      // output of a row feeds that row of to_out and of the heads alone - an item of the last layer without a generated residue is
+      // skipped, barrier and all (uniform over the work-group).  Its feature rows keep what the previous layer's item wrote (the same
+      // work-group, complete since that layer's barriers): finite and deterministic; to_out and the heads still run on all rows of the
+      // patch, every product there is row-wise, and nothing reads what they make of the skipped rows.
+      const unsigned char* needed = l + 1 == a.NL ? a.last_layer_tiles : nullptr;
 #pragma unroll 1
       for (int tile = 0; tile < NTILE; ++tile) {
+        if (needed != nullptr && !module_tile_needed(needed, b * NTILE + tile)) continue;
         ipa_attn_tile<8, (KRES > 128), true>(lds, b, tile, static_cast<unsigned>((b * a.NL + l) * NTILE + tile), a.proj, a.pair, a.R, a.t, small,
                                              small + 512, a.feat, K / 128, a.stamps, a.esc, nullptr, nullptr, a.ctx_of_row);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -194,13 +211,16 @@ bool ipa_module_persistent_supported(const diffab_dims* d) {
 
 // planes: d->NL x ipa_layer_planes_bytes() (ipa_layer_split_weights); pair_planes: launch_pair_split() of n_ctx patches (0: d->B), state
 // patch b reading those of ctx_of_row[b] (null: b); xa in, result in (NL odd ? xb : xa)
+// last_layer_tiles (optional, reverse sampler): [B][K / 16] bytes, the last layer's attention runs only for the row tiles with a nonzero one
 // emb_X (optional, with emb and heads): the embedding MLP's input rows - the launch then also runs the embedding MLP (-> xa) and the three
 // heads (module output -> heads->Y[]) of every patch
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X, const MlpChainSet* emb,
-                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx) {
+                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx, const unsigned char* last_layer_tiles) {
   DIFFAB_REQUIRE(ipa_module_persistent_supported(d) && xa && xb && R && t && ws && planes && pair_planes, DIFFAB_ERR_ARG,
                  "ipa_module_persistent: unsupported operands");
+  DIFFAB_REQUIRE((reinterpret_cast<uintptr_t>(last_layer_tiles) & 3) == 0, DIFFAB_ERR_ARG,
+                 "ipa_module_persistent: the row-tile map must be 4-byte aligned");
   const size_t rows = static_cast<size_t>(d->B) * d->K;
   ModuleArgs a{};
   a.xa = xa;
@@ -210,6 +230,7 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
   a.pair = pair_planes + 64;
   a.esc = pair_row_scales(d, pair_planes, n_ctx);
   a.ctx_of_row = ctx_of_row;
+  a.last_layer_tiles = last_layer_tiles;
   a.R = R;
   a.t = t;
   a.planes = static_cast<const char*>(planes);

@@ -24,7 +24,8 @@ FLAG_PAIR_PLANES = 32  # K = 64 / 128: pair embedding as two fp16 planes, pair-t
 FLAG_GRAPH_SAMPLER = 16  # sample_loop: one captured step replayed as a hipGraph (launch-bound small batches)
 FLAG_PERSISTENT_MODULE = 512  # MFMA path, K = 128 / 256, pair planes: the IPA module as one patch-resident launch (bitwise the multi-launch result)
 FLAG_MULTI_LAUNCH = 1024  # sample_loop: never choose the patch-resident module launch (bitwise the same samples either way)
-FLAG_SKIP_UNUSED_ROWS = 256  # sample_loop: the last layer's attention only for row tiles with a generated residue (same trajectory)
+FLAG_SKIP_UNUSED_ROWS = 256  # sample_loop: accepted, no effect - the loop skips the last layer's unread row tiles by itself (same trajectory)
+FLAG_ALL_ROWS = 8192  # sample_loop: run the last layer's attention for every row tile, also those without a generated residue (same trajectory)
 FLAG_KEEP_STRUCTURE = 2048  # design mode: the sampler never writes x and O (fixed-backbone sequence design)
 FLAG_KEEP_SEQUENCE = 4096  # design mode: the sampler never writes seq (structure prediction)
 
@@ -117,6 +118,7 @@ SYMBOLS = {
     "diffab_debug_set_attn_variant": (C.c_int, [_i32]),
     "diffab_debug_set_module_stagger": (C.c_int, [_i32, _i32]),
     "diffab_debug_set_module_stamps": (C.c_int, [_fp]),
+    "diffab_debug_row_tiles": (C.c_int, [_fp, _i32, _i32, _fp, _fp]),
     "diffab_set_stream_guard": (C.c_int, [C.c_int]),
     "diffab_debug_linear128": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp]),
     "diffab_debug_gemm_tn": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),

@@ -1058,7 +1058,7 @@ class DiffAb(_ModuleBase):
                distmat=None, atom_mask=None, chain_idx=None, residue_idx=None, generate_structure: bool = True,
                generate_sequence: bool = True, seed: Optional[int] = None, first_patch: int = 0, t_start: Optional[int] = None,
                t_stop: int = 0, init: bool = True, flags: int = 0, graph: Optional[bool] = None,
-               skip_unused_rows: bool = False, num_samples: int = 1,
+               skip_unused_rows: bool = True, num_samples: int = 1,
                context_index: Optional[torch.LongTensor] = None, mode: Optional[str] = None,
                optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None, trajectory=None,
                trajectory_predictions: bool = False, steps=None,
@@ -1078,9 +1078,10 @@ class DiffAb(_ModuleBase):
         result; the call then waits for the trajectory).  Off by default: measured at BASELINE config 1 (B = 1, K = 128, 100 steps)
         it changes nothing - 145 ms eager, 146 ms replayed - because the host already runs ahead of the device there; a step is a
         chain of ~45 dependent kernels on 8-work-group grids (1.45 ms), not 45 launch overheads.
-        ``skip_unused_rows=True``: a step's outputs are used for generated residues only, so the LAST layer's attention runs only for the
-        16-row tiles that contain one (`DIFFAB_FLAG_SKIP_UNUSED_ROWS`): bitwise the same samples, less work when few residues are
-        generated (one CDR: 5-7 of the 8 row tiles of the last layer are skipped).
+        ``skip_unused_rows`` (default True): a step's outputs are used for generated residues only, so the LAST layer's attention runs only
+        for the 16-row tiles that contain one - on both launch forms of the loop, bitwise the same samples, less work when few residues
+        are generated (one CDR: 5-7 of the 8 row tiles of the last layer are skipped; a fully generated patch loses nothing).  ``False``
+        sets `DIFFAB_FLAG_ALL_ROWS`: every tile runs, the form to time the full layer with.
 
         Many designs per patch from one shared context:
         ``num_samples=N``: every per-patch input (seq_idx, xyz, orientations, generation_mask; B rows) is replicated N times on the
@@ -1287,8 +1288,8 @@ class DiffAb(_ModuleBase):
             ctx_host = (C.c_int32 * B)(*ctx_map.tolist())
         if graph:
             flags |= _hip.FLAG_GRAPH_SAMPLER
-        if skip_unused_rows:
-            flags |= _hip.FLAG_SKIP_UNUSED_ROWS
+        if not skip_unused_rows:
+            flags |= _hip.FLAG_ALL_ROWS
         flags |= keep
         if init and optimize_from is not None:
             fwd_tab = self.orientation_diffuser.so3.struct()

@@ -91,17 +91,21 @@ extern "C" {
                                          and the three heads behind the last layer: one launch per denoiser forward.  Ignored where
                                          it does not apply.  diffab_sample_loop
                                          chooses it by itself at K = 128 when the batch fills the chip (B >= number of CUs), see
-                                         DIFFAB_FLAG_MULTI_LAUNCH; with DIFFAB_FLAG_SKIP_UNUSED_ROWS the per-layer launches stay.  K = 256
+                                         DIFFAB_FLAG_MULTI_LAUNCH.  K = 256
                                          (two dense tiles, sixteen two-chunk attention items per patch; round 6) only on request:
                                          it measures 4 % slower than its per-layer launches at B = 512. */
 #define DIFFAB_FLAG_MULTI_LAUNCH 1024u /* diffab_sample_loop: keep one launch per kernel of an IPA layer even where the patch-resident module
                                           launch would be chosen (B >= number of CUs, K = 128); the two forms are bitwise equal */
-#define DIFFAB_FLAG_SKIP_UNUSED_ROWS 256u /* diffab_sample_loop (MFMA path, K % 16 == 0): a step's outputs are read for GENERATED residues
-                                         only (diffab_reverse_update leaves the others alone), so the LAST layer's attention runs only
-                                         for the 16-row tiles that contain one (every other layer feeds all rows' keys and values to the
-                                         next).  Bitwise the same trajectory; the work skipped depends on the mask - with one CDR-like
-                                         segment per patch 5-7 of the 8 row tiles of the last layer - so it is opt-in and bench.py's
-                                         headline keeps it off (reported separately). */
+#define DIFFAB_FLAG_ALL_ROWS 8192u /* diffab_sample_loop / _shared: a step's outputs are read for GENERATED residues only (the reverse
+                                     update, its heads epilogue, guidance and the trajectory record leave the others alone), so on the
+                                     MFMA path with K % 16 == 0 and NL >= 2 the loop runs the LAST layer's attention only for the 16-row
+                                     tiles that contain one (every other layer feeds all rows' keys and values to the next) - on the
+                                     module launch and on the per-layer launches alike, bitwise the same trajectory.  The work skipped
+                                     depends on the mask: with one CDR-like segment per patch 5-7 of the 8 row tiles of the last layer;
+                                     a fully generated patch skips nothing.  This bit keeps every tile: the all-rows time of a step.
+                                     The single forwards, the taped entries and diffab_score_designs always run every row. */
+#define DIFFAB_FLAG_SKIP_UNUSED_ROWS 256u /* accepted, no effect: what it asked for is what diffab_sample_loop does unless
+                                             DIFFAB_FLAG_ALL_ROWS is set */
 /* Design modes of the reverse loop (diffab_sample_loop / _shared, diffab_sample_init_ex, diffab_sample_init_noised).  With one of these
    bits set the sampler never writes that modality of the state; the other is updated exactly as without the bit, from the same Philox
    draws.  The branch is uniform per launch, on every launch form of the loop.  Both bits together: DIFFAB_ERR_ARG, nothing enqueued. */
@@ -200,6 +204,9 @@ int diffab_debug_set_attn_variant(int32_t v); /* Reference paths for tests and t
                                                  defaults.  Any other bit: DIFFAB_ERR_ARG, the switch is left as it was. */
 int diffab_debug_set_module_stagger(int32_t ticks_10ns, int32_t classes);
 int diffab_debug_set_module_stamps(void* device_buffer);
+/* Tests: the row-tile map diffab_sample_loop builds per call - tiles[b][j] (B x K / 16 bytes, device) = 1 when one of the residues
+ * 16 j .. 16 j + 15 of patch b is generated, else 0; the last layer's attention runs for the tiles with a 1 (DIFFAB_FLAG_ALL_ROWS). */
+int diffab_debug_row_tiles(const uint8_t* gen_mask, int32_t B, int32_t K, uint8_t* tiles, void* stream);
 /* The cross-stream ordering guard described under "Streams" above: on / off (default since round 6), process-wide. */
 int diffab_set_stream_guard(int on);
 /* Diagnostics / accuracy tests: Y[M x 128] = X[M x Kd] W[128 x Kd]^T + bias through ONE of the two dense kernels of the MFMA path -

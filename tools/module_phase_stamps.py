@@ -59,6 +59,16 @@ for name, v in (("projections", proj), ("attention (8 items)", attn), ("to_out",
                  "mean_by_layer": [float(m) for m in v.mean(0)]}
 for name in ("projections", "to_out"):
     print(f"  {name} by layer: " + " ".join(f"{m:.2f}" for m in res[name]["mean_by_layer"]))
+# the last layer's attention runs only for the row tiles with a generated residue (DIFFAB_FLAG_ALL_ROWS: for all): its time by tiles run
+tiles_run = gm.view(B, NTILE, 16).any(-1).sum(1).cpu()
+res["last_layer_attention_by_tiles_run"] = {}
+for n in sorted(set(tiles_run.tolist())):
+    sel = attn[:, -1][tiles_run == n]
+    res["last_layer_attention_by_tiles_run"][str(n)] = {"patches": int(sel.numel()), "mean_us": float(sel.mean())}
+    print(f"  last layer, {n} tiles with a generated residue: {int(sel.numel()):4d} patches, attention {float(sel.mean()):8.2f} us")
+own = (ph[:, -1, 3] - ph[:, 0, 0]) * TICK_US  # a work-group's module time (B <= #CUs: one patch each)
+res["work_group_us"] = {"mean": float(own.mean()), "max": float(own.max()), "min": float(own.min())}
+print(f"  work-group first stamp -> its last: mean {float(own.mean()):.1f} us, slowest {float(own.max()):.1f}, fastest {float(own.min()):.1f}")
 launch = float(ph[:, -1, 3].max() - ph[:, 0, 0].min()) * TICK_US
 res["first_stamp_to_last_us"] = launch
 print(f"  first projections start -> last to_out end: {launch:.1f} us")
