@@ -837,6 +837,16 @@ int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weig
                                 int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                                 const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
                                 const diffab_sample_temperature* temperature, void* stream) {
+  return diffab_sample_loop_steered(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
+                                    t_stop, workspace, workspace_bytes, flags, allowed, rec, steps, guidance, temperature, nullptr, stream);
+}
+
+int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                               int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                               const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                               int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                               const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
+                               const diffab_sample_temperature* temperature, const diffab_sample_steering* steering, void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
@@ -948,6 +958,57 @@ int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weig
                    "sample_loop: a sequence temperature acts on the sequence, which DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
     tdev = TemperatureDev{temperature->trans_scale, temperature->rot_scale, temperature->seq_temp, temperature->rot_row};
   }
+  // particle steering: terms, tables and buffers are checked here; its kernels run around every update (the energy before it, weights,
+  // resampling and the gather after it) and decide themselves which steps steer
+  SteeringDev sdev;
+  if (steering != nullptr) {
+    const diffab_sample_steering* q = steering;
+    diffab_sample_guidance terms{};
+    terms.w_clash = q->w_clash;
+    terms.clash_distance = q->clash_distance;
+    terms.w_bond = q->w_bond;
+    terms.bond_length = q->bond_length;
+    terms.chain = q->chain;
+    terms.residue_idx = q->residue_idx;
+    if (int rc = check_guidance_terms(&terms, "sample_loop (steering)")) return rc;
+    DIFFAB_REQUIRE(q->group_size >= 1 && q->group_size <= DIFFAB_STEER_MAX_GROUP, DIFFAB_ERR_ARG,
+                   "sample_loop: steering group_size = %d outside [1, %d]", q->group_size, DIFFAB_STEER_MAX_GROUP);
+    DIFFAB_REQUIRE(d->B % q->group_size == 0, DIFFAB_ERR_ARG, "sample_loop: %d rows are not a multiple of the steering group_size = %d", d->B,
+                   q->group_size);
+    DIFFAB_REQUIRE(std::isfinite(q->strength) && q->strength >= 0.0f, DIFFAB_ERR_ARG,
+                   "sample_loop: steering strength = %g must be finite and >= 0", q->strength);
+    DIFFAB_REQUIRE(q->ess_threshold >= 0.0f && q->ess_threshold <= 2.0f, DIFFAB_ERR_ARG, "sample_loop: steering ess_threshold = %g outside [0, 2]",
+                   q->ess_threshold);
+    DIFFAB_REQUIRE(q->t_min >= 0 && q->t_min <= q->t_max && q->t_max <= s->T, DIFFAB_ERR_ARG,
+                   "sample_loop: steering needs 0 <= t_min <= t_max <= T (t_min = %d, t_max = %d, T = %d)", q->t_min, q->t_max, s->T);
+    DIFFAB_REQUIRE(q->every >= 1, DIFFAB_ERR_ARG, "sample_loop: steering every = %d < 1", q->every);
+    DIFFAB_REQUIRE(q->logw && q->u_prev && q->energy && q->scratch, DIFFAB_ERR_ARG, "sample_loop: steering needs logw, u_prev, energy and scratch");
+    DIFFAB_REQUIRE(reinterpret_cast<uintptr_t>(q->scratch) % 8 == 0, DIFFAB_ERR_ARG, "sample_loop: steering scratch must be 8-byte aligned");
+    DIFFAB_REQUIRE(!(keep & DIFFAB_FLAG_KEEP_STRUCTURE), DIFFAB_ERR_ARG,
+                   "sample_loop: steering weighs the sampled structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
+    DIFFAB_REQUIRE(s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: steering needs the schedule's alpha_bar_sqrt");
+    sdev.logw = q->logw;
+    sdev.u_prev = q->u_prev;
+    sdev.energy = q->energy;
+    sdev.ancestors = q->ancestors;
+    sdev.scratch = q->scratch;
+    sdev.step_anc = reinterpret_cast<int32_t*>(static_cast<char*>(q->scratch) + static_cast<size_t>(d->B) * d->K * 56u);
+    sdev.chain = q->chain;
+    sdev.residue_idx = q->residue_idx;
+    sdev.residue_mask = q->residue_mask;
+    sdev.w_clash = q->w_clash;
+    sdev.clash_distance = q->clash_distance;
+    sdev.w_bond = q->w_bond;
+    sdev.bond_length = q->bond_length;
+    sdev.strength = q->strength;
+    sdev.ess_threshold = q->ess_threshold;
+    sdev.t_min = q->t_min;
+    sdev.t_max = q->t_max;
+    sdev.every = q->every;
+    sdev.group_size = q->group_size;
+    sdev.t_stop = t_stop;
+    sdev.next_host = steps != nullptr ? plan_host.data() : nullptr;
+  }
   // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
   // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
   const bool mapped = ctx_of_row != nullptr;
@@ -987,6 +1048,8 @@ int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weig
   }
   if (steps != nullptr)  // the step plan, once per call
     DIFFAB_HIP_CHECK(hipMemcpyAsync(steps->plan_dev, plan_host.data(), sizeof(int32_t) * plan_host.size(), hipMemcpyHostToDevice, st));
+  if (steering != nullptr && steering->ancestors != nullptr)  // the ancestor record: -1 wherever no steering step writes
+    DIFFAB_HIP_CHECK(hipMemsetAsync(steering->ancestors, 0xFF, sizeof(int32_t) * static_cast<size_t>(s->T + 1) * d->B, st));
   auto one_step = [&](int t, const int* t_dev) -> int {
     if (!plan.fold)  // (the folded head tables read the schedule themselves: one launch less per step)
       if (int rc = launch_fill_beta(s, t, d->B, sb.beta, st, t_dev)) return rc;
@@ -996,7 +1059,7 @@ int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weig
     if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev, gdev, tdev);
+                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev, gdev, tdev, sdev);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is

@@ -276,6 +276,32 @@ struct TemperatureDev {
   const float* seq_temp = nullptr;     // tau >= 0
   const int32_t* rot_row = nullptr;
 };
+// Particle steering (diffab_sample_loop_steered), by value like the guidance: logw == nullptr is off and today's
+// launch sequence.  Every steering kernel evaluates the steering-step predicate itself (steer_is_step), so a replayed graph needs no
+// host decision.  step_anc is the step's ancestor map (rows, group-local indices) the gather reads; ancestors the nullable record.
+struct SteeringDev {
+  float* logw = nullptr;     // (rows) accumulated log-weight
+  float* u_prev = nullptr;   // (rows) the energy the weight has seen last
+  float* energy = nullptr;   // (rows) U of the last steering step
+  int32_t* ancestors = nullptr;  // (T + 1, rows), nullable: row t is written at steering step t
+  int32_t* step_anc = nullptr;   // (rows)
+  void* scratch = nullptr;       // rows K 56 B: seq (int64) | x (3 fp32) | O (9 fp32) of the gathered residues
+  const int32_t* chain = nullptr;
+  const int32_t* residue_idx = nullptr;
+  const uint8_t* residue_mask = nullptr;
+  float w_clash = 0.f, clash_distance = 0.f, w_bond = 0.f, bond_length = 0.f, strength = 0.f, ess_threshold = 0.f;
+  int32_t t_min = 0, t_max = -1, every = 1, group_size = 1, t_stop = 0;
+  const int32_t* next_host = nullptr;  // HOST copy of a step plan's next[] (nullptr: t - 1): lets the eager loop skip the launches of a step that does not steer
+};
+// t is a steering step: t_min <= t <= t_max, (t_max - t) % every == 0 and the step's successor (t - 1, or next[t] of a step plan) above t_stop
+__host__ __device__ inline bool steer_is_step(const SteeringDev& sd, int t, int succ) {
+  return t >= sd.t_min && t <= sd.t_max && (sd.t_max - t) % sd.every == 0 && succ > sd.t_stop;
+}
+// steering_kernels.hip: U of every row at x0_hat into sd.energy (before the update); weights, resampling and the gather (after it)
+int launch_steer_energy(const SteeringDev& sd, const diffab_sched* s, const StepPlanDev& plan, int t, const int* t_dev, const float* x,
+                        const float* eps_hat, const uint8_t* gm, int B, int K, hipStream_t st);
+int launch_steer_resample_gather(const SteeringDev& sd, const StepPlanDev& plan, int t, const int* t_dev, int64_t* seq, float* x, float* O,
+                                 const uint8_t* gm, uint64_t seed, int64_t first_patch, int B, int K, bool copy_seq, hipStream_t st);
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
@@ -285,7 +311,8 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const SampleRecordDev& rec = SampleRecordDev{},  // trajectory recording (rec.slot nullable)
                                  const StepPlanDev& plan = StepPlanDev{},  // fewer-step sampling (plan.next nullable)
                                  const GuidanceDev& guide = GuidanceDev{},  // structure guidance (guide.shift nullable)
-                                 const TemperatureDev& temp = TemperatureDev{});  // noise scales / sequence temperature (all nullable)
+                                 const TemperatureDev& temp = TemperatureDev{},  // noise scales / sequence temperature (all nullable)
+                                 const SteeringDev& steer = SteeringDev{});  // particle steering (steer.logw nullable)
 int check_guidance_terms(const diffab_sample_guidance* g, const char* who);  // weights, distances, chain / residue_idx (DIFFAB_ERR_ARG)
 // the residues that are not generated: their (constant) state in every slot of the record, and their predictions - the given x / O and a
 // one-hot of the token - once per call

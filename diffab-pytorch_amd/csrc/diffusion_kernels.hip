@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "denoiser_internal.h"
+#include "guidance_row.h"
 #include "philox.h"
 #include "so3_math.h"
 
@@ -909,125 +910,7 @@ __global__ void record_fixed_kernel(SampleRecordDev rec, const int64_t* __restri
   for (int c = 0; c < V; ++c) rec.seq_probs[o * V + c] = c == s ? 1.0f : 0.0f;
 }
 
-// ------------------------------------------------------------------ structure guidance
-// One work-group of four waves per state row.  The row is staged in LDS tiles of kGuideThreads residues: p (x0_hat of a generated
-// residue, x of any other) with a flag word in .w (bit 0 residue_mask, bit 1 generated; 0 past the end of a ragged row) in one float4,
-// chain and residue_idx in one int2.  Lane l of every wave owns residue i0 + l of each chunk of 64 residues; wave w scans the w-th
-// quarter of every tile's partners in order - all lanes read the same LDS address, a broadcast - and the four partial gradients of a
-// residue are added in wave order through LDS.  A wave whose 64 owners have nothing to compute skips the scan.  Sums run in that fixed
-// order, then in a fixed tree: no atomics, the result of a row depends on the row alone.  Plain fp32 VALU / LDS code (this file is
-// built with -ffp-contract=off).
-constexpr int kGuideThreads = 256, kGuideWaves = kGuideThreads / 64;
-
-struct GuideSums {
-  float clash = 0.f, bond = 0.f, max_dev = 0.f;
-  int n_clash = 0;
-};
-
-// p of residue i: x0_hat_i = (x_t,i - sqrt(1 - abar_t) eps_hat_i) / sqrt(abar_t) for a generated residue - record_residue's expression,
-// so the recorded pred_x is bitwise the point the potential is taken at - and x_i otherwise (eps_hat == nullptr: x for every residue)
-__device__ inline float3 guide_point(const float* x, const float* eps_hat, int64_t i, bool gen, float omabs, float a) {
-  if (eps_hat != nullptr && gen)
-    return make_float3((x[i * 3 + 0] - omabs * eps_hat[i * 3 + 0]) / a, (x[i * 3 + 1] - omabs * eps_hat[i * 3 + 1]) / a,
-                       (x[i * 3 + 2] - omabs * eps_hat[i * 3 + 2]) / a);
-  return make_float3(x[i * 3 + 0], x[i * 3 + 1], x[i * 3 + 2]);
-}
-
-// The pass over one row: g_i for every residue, handed to emit(i, gx, gy, gz) by wave 0 (0 unless generated and masked).  kEnergy:
-// every masked residue also scans, and the unordered pairs {i, j} are counted by their smaller index into `sums`.
-template <bool kEnergy, typename Emit>
-__device__ inline void guide_row(int64_t row, int K, const float* __restrict__ x, const float* __restrict__ eps_hat, float omabs, float a,
-                                 const uint8_t* __restrict__ gm, const GuidanceDev& g, GuideSums& sums, Emit emit) {
-  __shared__ float4 tp[kGuideThreads];
-  __shared__ int2 tc[kGuideThreads];
-  __shared__ float part[kGuideWaves][3][64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t base = row * K;
-  // a nonbonded pair whose d^2 is not below d0^2 (with a margin over its rounding) cannot clash: skipped before the square root
-  const float d0 = g.clash_distance, L = g.bond_length, wc2 = 2.0f * g.w_clash, wb2 = 2.0f * g.w_bond, far2 = d0 * d0 * 1.0001f;
-  for (int i0 = 0; i0 < K; i0 += 64) {
-    const int i = i0 + lane;
-    int fi = 0, ci = 0, ri = 0;
-    float3 pi = make_float3(0.f, 0.f, 0.f);
-    if (i < K) {
-      const bool gen = gm[base + i] != 0;
-      fi = (g.residue_mask == nullptr || g.residue_mask[base + i] ? 1 : 0) | (gen ? 2 : 0);
-      pi = guide_point(x, eps_hat, base + i, gen, omabs, a);
-      ci = g.chain[base + i];
-      ri = g.residue_idx[base + i];
-    }
-    const bool run = kEnergy ? (fi & 1) != 0 : fi == 3;
-    float gx = 0.f, gy = 0.f, gz = 0.f;
-    for (int j0 = 0; j0 < K; j0 += kGuideThreads) {
-      __syncthreads();  // every wave is done with the previous tile
-      const int j = j0 + tid;
-      if (j < K) {
-        const bool gen = gm[base + j] != 0;
-        const int fj = (g.residue_mask == nullptr || g.residue_mask[base + j] ? 1 : 0) | (gen ? 2 : 0);
-        const float3 pj = guide_point(x, eps_hat, base + j, gen, omabs, a);
-        tp[tid] = make_float4(pj.x, pj.y, pj.z, static_cast<float>(fj));
-        tc[tid] = make_int2(g.chain[base + j], g.residue_idx[base + j]);
-      } else {
-        tp[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
-        tc[tid] = make_int2(0, 0);
-      }
-      __syncthreads();
-      if (!run) continue;
-      const int n = min(kGuideThreads, K - j0), lo = n * wave / kGuideWaves, hi = n * (wave + 1) / kGuideWaves;
-#pragma unroll 4
-      for (int jj = lo; jj < hi; ++jj) {
-        const float4 q = tp[jj];
-        const int fj = static_cast<int>(q.w);
-        if (!(fj & 1) || !((fi | fj) & 2) || j0 + jj == i) continue;
-        const int2 c = tc[jj];
-        const float dx = pi.x - q.x, dy = pi.y - q.y, dz = pi.z - q.z;
-        const float d2 = dx * dx + dy * dy + dz * dz;
-        const int64_t gap = static_cast<int64_t>(c.y) - ri;
-        const bool bonded = c.x == ci && (gap == 1 || gap == -1);
-        if (!bonded && !(d2 < far2)) continue;
-        const float d = sqrtf(d2);
-        const bool counted = kEnergy && j0 + jj > i;
-        float coef;
-        if (bonded) {
-          const float dev = d - L;
-          coef = wb2 * dev;
-          if (counted) {
-            sums.bond += dev * dev;
-            sums.max_dev = fmaxf(sums.max_dev, fabsf(dev));
-          }
-        } else {
-          if (!(d < d0)) continue;
-          const float h = d0 - d;
-          coef = -wc2 * h;
-          if (counted) {
-            sums.clash += h * h;
-            sums.n_clash += 1;
-          }
-        }
-        if ((fi & 2) && d >= 1e-6f) {
-          const float sc = coef / d;
-          gx += sc * dx;
-          gy += sc * dy;
-          gz += sc * dz;
-        }
-      }
-    }
-    part[wave][0][lane] = gx;
-    part[wave][1][lane] = gy;
-    part[wave][2][lane] = gz;
-    __syncthreads();  // (part is next written after the next chunk's first tile barrier)
-    if (wave == 0 && i < K) {
-      float sx = part[0][0][lane], sy = part[0][1][lane], sz = part[0][2][lane];
-#pragma unroll
-      for (int w = 1; w < kGuideWaves; ++w) {
-        sx += part[w][0][lane];
-        sy += part[w][1][lane];
-        sz += part[w][2][lane];
-      }
-      emit(base + i, sx, sy, sz);
-    }
-  }
-}
+// ------------------------------------------------------------------ structure guidance: the row pass is guidance_row.h
 
 // The sampler's pass, right before the update of step t (t from t_dev under graph replay): Delta = beta'_t g, capped at max_shift, into
 // g.shift for every residue of the row (+0 where g is 0); all 0 at a step t > t_max (the update then does not read it).
@@ -1065,8 +948,6 @@ __global__ __launch_bounds__(kGuideThreads) void guidance_energy_kernel(Guidance
                                                                         const uint8_t* __restrict__ gm, int K, float* __restrict__ clash,
                                                                         float* __restrict__ bond, int* __restrict__ n_clash,
                                                                         float* __restrict__ max_dev, float* __restrict__ grad) {
-  __shared__ float red[3][kGuideThreads];
-  __shared__ int red_n[kGuideThreads];
   const int64_t row = blockIdx.x;
   GuideSums sums;
   guide_row<true>(row, K, x, nullptr, 0.f, 1.f, gm, g, sums, [&](int64_t i, float gx, float gy, float gz) {
@@ -1076,26 +957,12 @@ __global__ __launch_bounds__(kGuideThreads) void guidance_energy_kernel(Guidance
       grad[i * 3 + 2] = gz;
     }
   });
-  const int tid = threadIdx.x;
-  red[0][tid] = sums.clash;
-  red[1][tid] = sums.bond;
-  red[2][tid] = sums.max_dev;
-  red_n[tid] = sums.n_clash;
-  __syncthreads();
-  for (int s = kGuideThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      red[0][tid] += red[0][tid + s];
-      red[1][tid] += red[1][tid + s];
-      red[2][tid] = fmaxf(red[2][tid], red[2][tid + s]);
-      red_n[tid] += red_n[tid + s];
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    clash[row] = red[0][0];
-    bond[row] = red[1][0];
-    max_dev[row] = red[2][0];
-    n_clash[row] = red_n[0];
+  guide_reduce(sums);
+  if (threadIdx.x == 0) {
+    clash[row] = sums.clash;
+    bond[row] = sums.bond;
+    max_dev[row] = sums.max_dev;
+    n_clash[row] = sums.n_clash;
   }
 }
 
@@ -1435,8 +1302,10 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
                                  const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec,
-                                 const StepPlanDev& plan, const GuidanceDev& guide, const TemperatureDev& temp) {
+                                 const StepPlanDev& plan, const GuidanceDev& guide, const TemperatureDev& temp, const SteeringDev& steer) {
   const int64_t n = static_cast<int64_t>(B) * K;
+  if (steer.logw != nullptr)  // particle steering: U of every row at x0_hat of this step, before any shift and before the update
+    if (int rc = launch_steer_energy(steer, s, plan, t, t_dev, x, eps_hat, gm, B, K, st)) return rc;
   if (guide.shift != nullptr) {  // every launch form reaches the update through here: Delta of this step first
     hipLaunchKernelGGL(guidance_shift_kernel, dim3(B), dim3(kGuideThreads), 0, st, guide, x, eps_hat, gm, plan.next ? plan.beta : s->beta,
                        s->one_minus_alpha_bar_sqrt, s->alpha_bar_sqrt, t, t_dev, K);
@@ -1446,6 +1315,8 @@ int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
                      post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan, guide, temp);
   DIFFAB_LAUNCH_CHECK();
+  if (steer.logw != nullptr)  // weights, resampling and the gather of the ancestors' generated residues, on the updated state
+    return launch_steer_resample_gather(steer, plan, t, t_dev, seq, x, O, gm, seed, first_patch, B, K, !(keep & DIFFAB_FLAG_KEEP_SEQUENCE), st);
   return DIFFAB_OK;
 }
 

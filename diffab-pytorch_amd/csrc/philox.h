@@ -21,6 +21,9 @@ enum PhiloxStream : uint32_t {
   STREAM_OPT_TRANS = 8,  // translation noise eps
   STREAM_OPT_AXIS = 9,   // rotation axis
   STREAM_OPT_ANGLE = 10, // rotation angle (u_bin, u_in, z via Box-Muller of lanes 2,3), as STREAM_ANGLE
+  // particle steering: lane .x is the uniform of a group's systematic resampling; counter (residue 0, patch of the
+  // group's first row, step t)
+  STREAM_STEER = 11,
 };
 
 struct u32x4 {

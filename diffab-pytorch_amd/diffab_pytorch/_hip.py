@@ -106,6 +106,12 @@ class SampleTemperature(C.Structure):  # diffab_sample_temperature: per-row nois
     _fields_ = [(n, _fp) for n in ("trans_scale", "rot_scale", "seq_temp", "rot_row")]
 
 
+class SampleSteering(C.Structure):  # diffab_sample_steering: particle steering of diffab_sample_loop_steered
+    _fields_ = [(n, C.c_float) for n in ("w_clash", "clash_distance", "w_bond", "bond_length", "strength", "ess_threshold")] + \
+        [(n, C.c_int32) for n in ("t_min", "t_max", "every", "group_size")] + \
+        [(n, _fp) for n in ("chain", "residue_idx", "residue_mask", "logw", "u_prev", "energy", "ancestors", "scratch")]
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -233,6 +239,16 @@ SYMBOLS = {
     "diffab_sample_loop_tempered": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
                                               _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
                                               C.POINTER(SampleGuidance), C.POINTER(SampleTemperature), _fp]),
+    # particle steering: diffab_sample_loop_tempered plus `steering` (nullable) before the stream
+    "diffab_sample_loop_steered": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
+                                             _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
+                                             C.POINTER(SampleGuidance), C.POINTER(SampleTemperature), C.POINTER(SampleSteering), _fp]),
+    # (x, eps_hat, gen_mask, sched, t, steering, rows, K, energy_out, stream)
+    "diffab_steer_energy": (C.c_int, [_fp, _fp, _fp, _PS, _i32, C.POINTER(SampleSteering), _i32, _i32, _fp, _fp]),
+    # (logw, u_prev, energy, u, G, N, strength, ess_threshold, ancestors_out, ess_out (double, nullable), stream)
+    "diffab_steer_resample": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, C.c_float, C.c_float, _fp, _fp, _fp]),
+    # (seq, x, O, gen_mask, ancestors, rows, K, scratch, stream)
+    "diffab_steer_gather": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _i32, _i32, _fp, _fp]),
     # (x, gen_mask, guidance, B, K, clash, bond, n_clash, max_bond_deviation, grad (nullable), stream)
     "diffab_guidance_energy": (C.c_int, [_fp, _fp, C.POINTER(SampleGuidance), _i32, _i32, _fp, _fp, _fp, _fp, _fp, _fp]),
     # (sched, t, s, beta', alpha', seq, x, O, eps_hat, O0_hat, posterior, gen_mask, z, rotvec, u_seq, r_out (nullable), B, K, V, stream)

@@ -27,6 +27,7 @@ from . import so3 as _so3
 from . import features as _features
 from . import guidance as _guidance
 from . import patch as _patch
+from . import steering as _steering
 from . import temperature as _temperature
 
 try:  # LightningModule hooks when Lightning is installed; a plain nn.Module otherwise
@@ -1063,7 +1064,8 @@ class DiffAb(_ModuleBase):
                optimize_from: Optional[int] = None, allowed_aa: Optional[torch.Tensor] = None, trajectory=None,
                trajectory_predictions: bool = False, steps=None,
                guidance: Optional[_guidance.SampleGuidance] = None,
-               temperature: Optional[_temperature.SampleTemperature] = None) -> Dict[str, torch.Tensor]:
+               temperature: Optional[_temperature.SampleTemperature] = None,
+               steering: Optional[_steering.ParticleSteering] = None) -> Dict[str, torch.Tensor]:
         """Reverse diffusion t_start .. t_stop+1 (default T .. 1) on the generated residues (the reference's `sample` is a stub,
         diffab_pytorch.py:770-776; the loop is build-defined).
 
@@ -1182,7 +1184,30 @@ class DiffAb(_ModuleBase):
         first_patch = lo.  The stacked IGSO3 table of the call's distinct nonzero rotation scales is built once and cached
         (_reverse_so3_tempered).  Anything but a SampleTemperature, a shape that does not broadcast, a negative, NaN or infinite value,
         more than 16 distinct nonzero rotation scales, a structure scale != 1 with mode="fixed_backbone" and a sequence temperature
-        != 1 with mode="structure" raise ValueError before any device work."""
+        != 1 with mode="structure" raise ValueError before any device work.
+
+        Particle steering: ``steering=steering.ParticleSteering(strength=..., ess_threshold=...)`` spends the
+        designs of a patch where they pay off.  The state rows are groups of ``group_size`` consecutive rows (default num_samples: the
+        designs of one patch).  At every steering step - the executed steps t in [t_min, t_max] with (t_max - t) % every == 0, the last
+        executed step excepted; t_max None: the first step of the call - each row is weighed by the guidance potential U (clash, bond,
+        clash_distance, bond_length as in SampleGuidance; chain_idx / residue_idx / residue_mask as for guidance) at x0_hat of that step:
+        log w += -strength (U - U at the previous steering step).  When the effective sample size (sum w)^2 / sum w^2 of a group falls
+        below ess_threshold * group_size the group is resampled systematically with one Philox uniform, keyed by the group's first
+        global row, and after the step's ordinary update the generated residues (seq, x, O) of every row are replaced by those of its
+        ancestor; the copies separate again at the next step through their own noise.  No gradient, no extra model evaluation, the mean
+        of no step moves; weights never reach the host, so it runs under graph replay and on every launch form
+        (`diffab_sample_loop_steered`).  The result gains ``"steering"``: ``log_weight`` (rows,) and ``energy`` (rows,) - the energy
+        each weight has seen last, its ancestor's after a resampling - ``t`` (n,) the steering steps in descending order, ``ancestors``
+        (n, rows) the global row each row was copied from at that step (its own index where nothing moved) and ``lineage`` (rows,), the
+        initial row every design descends from.  All rows of a group must share generation_mask, the context and the tables (checked on
+        the host before device work, which copies generation_mask to it once per call).
+        strength = 0 (ess_threshold <= 1), ess_threshold = 0 and group_size = 1 are bitwise the unsteered sample.  Combines with the
+        modes that sample the structure, optimize_from, allowed_aa, trajectory (the record of step t is written before the gather),
+        steps, guidance, temperature, graph, num_samples / context_index and the flags.  A rank passes whole groups
+        (distributed.shard_range(..., group_size=N)) and first_patch = its first row: bitwise the slice of the whole call.  Anything
+        but a ParticleSteering, a negative or non-finite strength or weight, a non-positive distance, ess_threshold outside [0, 2],
+        every < 1, t_min / t_max outside [0, T] or t_min > t_max, group_size outside [1, 1024], rows that are no whole groups, a group
+        whose rows differ in generation_mask, context or tables, and mode="fixed_backbone" raise ValueError before any device work."""
         if generation_mask is None:
             raise ValueError("sample() needs generation_mask: which residues to generate")
         generate_structure, generate_sequence, keep = _mode_settings("sample()", mode, generate_structure, generate_sequence)
@@ -1219,16 +1244,31 @@ class DiffAb(_ModuleBase):
             ctx_map = torch.arange(n_rows, dtype=torch.int32).repeat_interleave(num_samples)
         if allowed_aa is not None:
             _allowed_aa_host("sample()", allowed_aa, generation_mask, n_rows, K_, self.denoiser.dims["V"], keep)
-        guide_tabs = None  # host (rows, K) chain / residue_idx / residue_mask of the guidance (None: unguided)
+        res_tabs = None  # host (rows, K) chain / residue_idx / residue_mask of the potential, for guidance and steering alike (None: neither)
         if guidance is not None:
             _guidance.check_guidance("sample()", guidance, self.T)
             if keep & _hip.FLAG_KEEP_STRUCTURE:
                 raise ValueError("sample(): guidance moves the structure, which mode='fixed_backbone' keeps as given")
-            guide_tabs = _guidance.residue_tables("sample()", chain_idx, residue_idx, residue_mask, n_rows, K_)
+        if steering is not None:
+            _steering.check_steering("sample()", steering, self.T)
+            if keep & _hip.FLAG_KEEP_STRUCTURE:
+                raise ValueError("sample(): steering weighs the sampled structure, which mode='fixed_backbone' keeps as given")
+        if guidance is not None or steering is not None:
+            res_tabs = _guidance.residue_tables("sample()", chain_idx, residue_idx, residue_mask, n_rows, K_)
         temp_vals = None  # host fp32 (output rows,) lambda_x, lambda_O, tau (None: untempered)
         if temperature is not None:
             temp_vals = _temperature.row_values("sample()", temperature, n_rows * num_samples)
             _temperature.check_mode("sample()", temp_vals, bool(keep & _hip.FLAG_KEEP_STRUCTURE), bool(keep & _hip.FLAG_KEEP_SEQUENCE))
+        if steering is not None:  # steer_n: the group size; the groups are checked on the host (one copy of generation_mask to it)
+            if steering.t_max is None and steering.t_min > (self.T if t_start is None else int(t_start)):
+                raise ValueError(f"sample(): steering t_min = {steering.t_min} is above the first step of the call (t_max=None steers from it)")
+            steer_n = num_samples if steering.group_size is None else steering.group_size
+            per_row = lambda v: v.repeat_interleave(num_samples, dim=0) if num_samples > 1 else v
+            gm_host = torch.as_tensor(generation_mask).detach().cpu().ne(0)
+            _steering.check_groups("sample()", steer_n, n_rows * num_samples,
+                                   {"generation_mask": per_row(gm_host), "the context (context_index)": ctx_map,
+                                    "chain_idx": per_row(res_tabs[0]), "residue_idx": per_row(res_tabs[1]),
+                                    "residue_mask": per_row(res_tabs[2])})
         executed = _sample_steps("sample()", steps, self.T if t_start is None else int(t_start), int(t_stop), self.T)
         labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, self.T if t_start is None else int(t_start), int(t_stop),
                                     self.T, executed)
@@ -1246,14 +1286,14 @@ class DiffAb(_ModuleBase):
         allowed = None  # int32 (rows, K) words of the allowed classes (always passed when allowed_aa is given, an all-True mask too)
         if allowed_aa is not None:
             allowed = _pack_allowed_aa(torch.as_tensor(allowed_aa).detach().to(seq.device).expand(n_rows, K_, self.denoiser.dims["V"]))
-        if guide_tabs is not None:
-            guide_tabs = tuple(v.to(seq.device) for v in guide_tabs)
+        if res_tabs is not None:  # on the device once; guidance and steering read the same three tensors
+            res_tabs = tuple(v.to(seq.device) for v in res_tabs)
         if num_samples > 1:  # the state of every design: the patch's rows, replicated on the device (the contexts are not)
             seq, x, O, gm = (v.repeat_interleave(num_samples, dim=0) for v in (seq, x, O, gm))
             if allowed is not None:
                 allowed = allowed.repeat_interleave(num_samples, dim=0)
-            if guide_tabs is not None:
-                guide_tabs = tuple(v.repeat_interleave(num_samples, dim=0) for v in guide_tabs)
+            if res_tabs is not None:
+                res_tabs = tuple(v.repeat_interleave(num_samples, dim=0) for v in res_tabs)
         else:
             seq, x, O = seq.clone(), x.clone(), O.clone()
         B, K = seq.shape
@@ -1325,7 +1365,7 @@ class DiffAb(_ModuleBase):
             rec = _hip.SampleRecord(n, (C.c_int32 * (self.T + 1))(*slot_of_step), _hip.ptr(slot_dev),
                                     *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
                                                                       "pred_orientations", "seq_probs")))
-        if executed is not None or guide_tabs is not None or temp is not None:
+        if executed is not None or res_tabs is not None or temp is not None:
             st = None
             if executed is not None:
                 plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=seq.device)
@@ -1337,20 +1377,36 @@ class DiffAb(_ModuleBase):
                     t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), None if rec is None else C.byref(rec),
                     None if st is None else C.byref(st))
             gs = None
-            if guide_tabs is not None:
+            if guidance is not None:
                 shift = torch.empty(B, K, 3, device=seq.device)
                 t_max = self.T if guidance.t_max is None else guidance.t_max
-                gs = _guidance.c_struct(guidance, t_max, *guide_tabs, shift)
-            if temp is not None:
+                gs = _guidance.c_struct(guidance, t_max, *res_tabs, shift)
+            if steering is not None:
+                dev = seq.device
+                logw, u_prev, energy = (torch.zeros(B, device=dev) for _ in range(3))
+                anc = torch.empty(self.T + 1, B, dtype=torch.int32, device=dev)
+                scratch = torch.empty(_steering.scratch_bytes(B, K), dtype=torch.uint8, device=dev)
+                st_max = t_start if steering.t_max is None else steering.t_max
+                ss = _steering.c_struct(steering, st_max, steer_n, *res_tabs, logw, u_prev, energy, anc, scratch)
+                _hip.check(lib.diffab_sample_loop_steered(*args, None if gs is None else C.byref(gs), None if temp is None else C.byref(temp),
+                                                          C.byref(ss), _hip.stream_ptr()), "diffab_sample_loop_steered")
+            elif temp is not None:
                 _hip.check(lib.diffab_sample_loop_tempered(*args, None if gs is None else C.byref(gs), C.byref(temp), _hip.stream_ptr()),
                            "diffab_sample_loop_tempered")
-            elif guide_tabs is None:
+            elif guidance is None:
                 _hip.check(lib.diffab_sample_loop_steps(*args, _hip.stream_ptr()), "diffab_sample_loop_steps")
             else:
                 _hip.check(lib.diffab_sample_loop_guided(*args, C.byref(gs), _hip.stream_ptr()), "diffab_sample_loop_guided")
             out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
             if labels is not None:
                 out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}
+            if steering is not None:
+                ran = executed.tolist() if executed is not None else list(range(t_start, int(t_stop), -1))
+                ts = torch.tensor(_steering.steering_steps(ran, int(t_stop), steering.t_min, st_max, steering.every), dtype=torch.int64)
+                first = torch.arange(B, device=dev) // steer_n * steer_n  # group-local -> global row indices
+                glob = anc[ts.to(dev)].to(torch.int64) + first
+                out["steering"] = {"log_weight": logw.to(out_dev), "energy": u_prev.to(out_dev), "t": ts.to(out_dev),
+                                   "ancestors": glob.to(out_dev), "lineage": _steering.lineage(glob).to(out_dev)}
             return out
         if labels is not None:
             _hip.check(lib.diffab_sample_loop_rec(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),

@@ -13,11 +13,18 @@ from typing import Dict, Optional, Tuple
 import torch
 
 
-def shard_range(n_patches: int, rank: int, world: int) -> Tuple[int, int]:
-    """Contiguous, even split of [0, n_patches): the first n % world ranks get one extra patch."""
-    q, r = divmod(n_patches, world)
+def shard_range(n_patches: int, rank: int, world: int, group_size: int = 1) -> Tuple[int, int]:
+    """Contiguous, even split of [0, n_patches): the first n % world ranks get one extra patch.  ``group_size`` > 1 (particle steering,
+    DiffAb.sample(steering=...)): the rows are split in whole groups of that many consecutive rows - a group resamples among its own
+    rows, so a shard must hold all of them - and the first n_groups % world ranks get one extra group; rows that are no whole groups
+    raise ValueError.  The steered sample of a shard (first_patch = lo) is bitwise that slice of the whole call."""
+    if isinstance(group_size, bool) or not isinstance(group_size, int) or group_size < 1:
+        raise ValueError(f"shard_range(): group_size must be an int >= 1, got {group_size!r}")
+    if n_patches % group_size:
+        raise ValueError(f"shard_range(): {n_patches} rows are not a multiple of group_size = {group_size}")
+    q, r = divmod(n_patches // group_size, world)
     lo = rank * q + min(rank, r)
-    return lo, lo + q + (1 if rank < r else 0)
+    return lo * group_size, (lo + q + (1 if rank < r else 0)) * group_size
 
 
 def pack_samples(s: Dict[str, torch.Tensor]) -> torch.Tensor:

@@ -815,6 +815,84 @@ int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weig
                                 int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
                                 const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
                                 const diffab_sample_temperature* temperature, void* stream);
+/* ---- particle steering (build-defined): the rows of a group resampled by energy while they form ----------------
+ * Sequential Monte Carlo over the reverse process (Feynman-Kac steering / the twisted diffusion sampler).  The state rows are grouped
+ * as consecutive runs of group_size = N rows (rows b N .. b N + N - 1 under num_samples = N); all rows of a group share gen_mask, the
+ * context and the residue tables (the caller's contract).  Per row two fp32 values live in caller-owned device memory across the steps
+ * (and across calls): the accumulated log-weight logw and the last seen energy u_prev, both 0 at the start of a run.
+ *   Steering step: an executed step t with t_min <= t <= t_max, (t_max - t) % every == 0 and its successor s (t - 1, or the step plan's
+ *     next step) above t_stop - the last executed step never resamples, the finished designs come back with their weights.
+ *   Energy: U_r = w_clash sum_nonbonded max(0, clash_distance - d)^2 + w_bond sum_bonded (d - bond_length)^2 of the guidance rule above,
+ *     at p = x0_hat (bitwise the record's pred_x) for generated residues and x otherwise, on the state the step denoises, from that
+ *     step's eps_hat: before the update and before any guidance shift.  The two sums are bitwise diffab_guidance_energy's at those points.
+ *   Weights: logw_r += -(strength (U_r - u_prev_r)) in fp32, then u_prev_r = U_r: over a run the increments telescope to -strength U.
+ *   ESS, per group in double: w_r = exp(logw_r - max finite logw) (a non-finite logw: w_r = 0), S = sum w, ESS = S^2 / sum w^2.  The
+ *     group resamples iff S > 0 and ESS < ess_threshold N (0: never; above 1: always).  A group with every w_r = 0 does not resample
+ *     and its logw is set to 0.
+ *   Systematic resampling: one uniform u per group and step, lane x of Philox (seed, first_patch + first row of the group, residue 0,
+ *     t, STREAM_STEER = 11); C_i = (sum_{k <= i} w_k) / S in row order; a_j = the smallest i with C_i > (u + j) / N, at most the last
+ *     row with w > 0.  Then logw_j = 0 and u_prev_j = U_{a_j} for every row of the group.  A group that does not resample: a_j = j.
+ *   What moves: the update of step t runs first, on every row, with its usual noise; then seq, x and O of the generated residues of row
+ *     j become those of row a_j (propagate, then select, with the weights of x_t).  Children of one ancestor are equal after step t and
+ *     separate at the next step: the Philox noise is keyed by the row, not by the lineage.  Per-row options (temperature, allowed
+ *     classes, guidance tables) belong to the row.  The record of step t is written before the gather; the next step records the
+ *     gathered state.  DIFFAB_FLAG_KEEP_SEQUENCE leaves seq alone.
+ * strength = 0 with ess_threshold <= 1, ess_threshold = 0 and group_size = 1 are bitwise the unsteered states.
+ * Three kernels around the update of every step, on every launch form; each evaluates the steering-step predicate itself (graph replay
+ * reads t from device memory).  Buffers, all DEVICE and caller-owned (the workspace size is unchanged):
+ *   logw, u_prev (rows) fp32: read and written; energy (rows) fp32: U of the last steering step, as computed before its resampling;
+ *   ancestors ((T + 1) rows) int32, nullable: filled with -1 by the call, row t = the a_j (indices inside the group) of steering step t;
+ *   scratch: DIFFAB_STEER_SCRATCH_BYTES(rows, K) bytes, 8-byte aligned - 56 B per residue (seq 8, x 12, O 36) of the rows being
+ *     replaced, because the map is no permutation in place, and the step's ancestor map (4 B per row). */
+#define DIFFAB_STEER_MAX_GROUP 1024
+#define DIFFAB_STEER_SCRATCH_BYTES(rows, K) ((size_t)(rows) * (size_t)(K) * 56u + (size_t)(rows) * 4u)
+typedef struct {
+  float w_clash;              /* >= 0, finite */
+  float clash_distance;       /* d0 > 0 */
+  float w_bond;               /* >= 0, finite */
+  float bond_length;          /* L > 0 */
+  float strength;             /* lambda >= 0, finite */
+  float ess_threshold;        /* in [0, 2] */
+  int32_t t_min, t_max;       /* 0 <= t_min <= t_max <= T */
+  int32_t every;              /* >= 1 */
+  int32_t group_size;         /* N in [1, DIFFAB_STEER_MAX_GROUP], divides the rows */
+  const int32_t* chain;       /* DEVICE (rows, K) */
+  const int32_t* residue_idx; /* DEVICE (rows, K) */
+  const uint8_t* residue_mask;/* DEVICE (rows, K), nullable = all */
+  float* logw;                /* DEVICE (rows) */
+  float* u_prev;              /* DEVICE (rows) */
+  float* energy;              /* DEVICE (rows) */
+  int32_t* ancestors;         /* DEVICE (T + 1, rows), nullable */
+  void* scratch;              /* DEVICE DIFFAB_STEER_SCRATCH_BYTES(rows, K) */
+} diffab_sample_steering;
+/* diffab_sample_loop_tempered plus `steering` (nullable) before the stream; steering == NULL is exactly diffab_sample_loop_tempered
+ * (which is unchanged).  Needs s->alpha_bar_sqrt.  Checked before anything is enqueued, DIFFAB_ERR_ARG: rows (d->B) not a multiple of
+ * group_size; group_size < 1 or > DIFFAB_STEER_MAX_GROUP; a negative or non-finite weight or strength; a distance <= 0; ess_threshold
+ * outside [0, 2]; t_min > t_max or either outside [0, T]; every < 1; null logw, u_prev, energy, scratch, chain or residue_idx; scratch
+ * not 8-byte aligned; DIFFAB_FLAG_KEEP_STRUCTURE (the structure is not sampled). */
+int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                               int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
+                               const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
+                               int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
+                               const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
+                               const diffab_sample_temperature* temperature, const diffab_sample_steering* steering, void* stream);
+/* Teacher-forced pieces of the rule above, one launch each (the analogues of diffab_reverse_update_jump):
+ * diffab_steer_energy: U (rows) fp32 at step t in [1, T] from x (rows, K, 3) and eps_hat; reads the potential's terms and tables of
+ *   `steering` only.
+ * diffab_steer_resample: the weight update, ESS and resampling of G groups of N rows with explicit uniforms u (G) fp32 in [0, 1): logw
+ *   and u_prev (G N) are updated in place from energy (G N); ancestors_out (G N) int32, indices inside the group; ess_out (G) double,
+ *   nullable (0 for a group with no weight).
+ * diffab_steer_gather: seq / x / O of the generated residues of row j become those of row ancestors[j] (row indices of the call; an
+ *   index outside [0, rows) leaves its row alone).  gen_mask of the DESTINATION row decides which residues are replaced; the residue of
+ *   the source row is read whatever its own mask says.  scratch: rows K 56 B, 8-byte aligned.
+ * DIFFAB_ERR_ARG: a null pointer (ess_out excepted), negative extents, N outside [1, DIFFAB_STEER_MAX_GROUP], the checks of
+ * diffab_sample_loop_steered on the values given. */
+int diffab_steer_energy(const float* x, const float* eps_hat, const uint8_t* gen_mask, const diffab_sched* s, int32_t t,
+                        const diffab_sample_steering* steering, int32_t rows, int32_t K, float* energy_out, void* stream);
+int diffab_steer_resample(float* logw, float* u_prev, const float* energy, const float* u, int32_t G, int32_t N, float strength,
+                          float ess_threshold, int32_t* ancestors_out, double* ess_out, void* stream);
+int diffab_steer_gather(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, const int32_t* ancestors, int32_t rows, int32_t K,
+                        void* scratch, void* stream);
 int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
 int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
