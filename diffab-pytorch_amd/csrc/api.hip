@@ -410,7 +410,7 @@ struct SampleBuffers {
   size_t bytes;
 };
 
-// n_pair: patches of the pair embedding (0: d->B); mapped: diffab_sample_loop_shared with a context map (its two buffers)
+// n_pair: patches of the pair embedding (0: d->B); mapped: diffab_sample_loop_ex with a context map (its two buffers)
 static SampleBuffers carve_sample(const diffab_dims* d, void* ws, int n_pair = 0, bool mapped = false) {
   Carver c(ws);
   const size_t rows = static_cast<size_t>(d->B) * d->K;
@@ -777,77 +777,198 @@ int diffab_ipa_layer_bwd(const diffab_dims* d, const diffab_ipa_layer_weights* w
   return ipa_layer_bwd(&d1, w, grads, tp, R, t, e, dy, dx, d_e, static_cast<float*>(workspace), as_stream(stream), d_R, d_t);
 }
 
+// ---- the options of diffab_sample_loop_ex: one helper per option checks the caller's struct (everything on the host, before the first
+// HIP call) and fills the by-value device struct the update kernel takes.  A NULL option leaves `out` default-constructed: off.
+
+// trajectory recording: every slot is written by exactly one step of this call, so the record holds no stale entry
+static int record_option(const diffab_sample_record* rec, const diffab_sched* s, int t_start, int t_stop, SampleRecordDev* out) {
+  if (rec == nullptr) return DIFFAB_OK;
+  DIFFAB_REQUIRE(rec->n_slots >= 1, DIFFAB_ERR_ARG, "sample_loop: record n_slots = %d < 1", rec->n_slots);
+  DIFFAB_REQUIRE(rec->slot_of_step && rec->slot_dev && rec->seq && rec->x && rec->O, DIFFAB_ERR_ARG,
+                 "sample_loop: record needs slot_of_step, slot_dev, seq, x and O");
+  const int n_pred = (rec->pred_x != nullptr) + (rec->pred_O != nullptr) + (rec->seq_probs != nullptr);
+  DIFFAB_REQUIRE(n_pred == 0 || n_pred == 3, DIFFAB_ERR_ARG, "sample_loop: record predictions are pred_x, pred_O and seq_probs, all or none");
+  DIFFAB_REQUIRE(n_pred == 0 || s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: record predictions need the schedule's alpha_bar_sqrt");
+  std::vector<int> used(rec->n_slots, 0);
+  for (int t = 0; t <= s->T; ++t) {
+    const int j = rec->slot_of_step[t];
+    if (j == -1) continue;
+    DIFFAB_REQUIRE(j >= 0 && j < rec->n_slots, DIFFAB_ERR_ARG, "sample_loop: record slot_of_step[%d] = %d outside -1, [0, %d)", t, j,
+                   rec->n_slots);
+    DIFFAB_REQUIRE(t > t_stop && t <= t_start, DIFFAB_ERR_ARG,
+                   "sample_loop: record slot_of_step[%d] = %d, but the call runs steps [%d, %d] only (the slot would never be written)", t, j,
+                   t_stop + 1, t_start);
+    DIFFAB_REQUIRE(used[j]++ == 0, DIFFAB_ERR_ARG, "sample_loop: record slot %d is given to two steps", j);
+  }
+  for (int j = 0; j < rec->n_slots; ++j)
+    DIFFAB_REQUIRE(used[j] == 1, DIFFAB_ERR_ARG, "sample_loop: record slot %d is given to no step", j);
+  *out = SampleRecordDev{rec->slot_dev, rec->n_slots, rec->seq, rec->x, rec->O, rec->pred_x, rec->pred_O, rec->seq_probs,
+                         n_pred ? s->alpha_bar_sqrt : nullptr};
+  return DIFFAB_OK;
+}
+
+// fewer-step sampling: the list, its jump coefficients and the record are checked, and the device plan - next[], beta'[], alpha'[] - is
+// packed into plan_host (the loop copies it to plan_dev once, after every check)
+static int steps_option(const diffab_sample_steps* steps, const diffab_sample_record* rec, const diffab_sched* s, int t_start, int t_stop,
+                        std::vector<int32_t>* plan_host, StepPlanDev* out) {
+  if (steps == nullptr) return DIFFAB_OK;
+  const int T = s->T;
+  DIFFAB_REQUIRE(steps->n_steps >= 1, DIFFAB_ERR_ARG, "sample_loop: steps n_steps = %d < 1", steps->n_steps);
+  DIFFAB_REQUIRE(steps->steps && steps->beta_jump && steps->alpha_jump && steps->plan_dev, DIFFAB_ERR_ARG,
+                 "sample_loop: steps needs steps, beta_jump, alpha_jump and plan_dev");
+  DIFFAB_REQUIRE(s->alpha_bar, DIFFAB_ERR_ARG, "sample_loop: steps need the schedule's alpha_bar");
+  DIFFAB_REQUIRE(steps->steps[0] == t_start, DIFFAB_ERR_ARG, "sample_loop: steps[0] = %d, t_start = %d", steps->steps[0], t_start);
+  std::vector<char> listed(T + 1, 0);
+  for (int j = 0; j < steps->n_steps; ++j) {
+    const int t = steps->steps[j];
+    DIFFAB_REQUIRE(t > t_stop && t <= T, DIFFAB_ERR_ARG, "sample_loop: steps[%d] = %d outside [t_stop + 1, T] = [%d, %d]", j, t, t_stop + 1, T);
+    DIFFAB_REQUIRE(j == 0 || t < steps->steps[j - 1], DIFFAB_ERR_ARG, "sample_loop: steps are not strictly descending at %d (%d after %d)", j,
+                   t, steps->steps[j - 1]);
+    const float bj = steps->beta_jump[t], aj = steps->alpha_jump[t];
+    DIFFAB_REQUIRE(bj > 0.0f && bj < 1.0f && aj > 0.0f && aj < 1.0f, DIFFAB_ERR_ARG,
+                   "sample_loop: jump coefficients at step %d outside (0, 1): beta' = %g, alpha' = %g", t, bj, aj);
+    listed[t] = 1;
+  }
+  if (rec != nullptr)
+    for (int t = 0; t <= T; ++t)
+      DIFFAB_REQUIRE(rec->slot_of_step[t] == -1 || listed[t], DIFFAB_ERR_ARG,
+                     "sample_loop: record slot_of_step[%d] = %d, but the step list does not run step %d", t, rec->slot_of_step[t], t);
+  plan_host->resize(3 * static_cast<size_t>(T + 1));
+  int32_t* ph = plan_host->data();
+  for (int t = 0; t <= T; ++t) ph[t] = t > 0 ? t - 1 : 0;
+  for (int j = 0; j < steps->n_steps; ++j) ph[steps->steps[j]] = j + 1 < steps->n_steps ? steps->steps[j + 1] : t_stop;
+  std::memcpy(ph + (T + 1), steps->beta_jump, sizeof(float) * (T + 1));
+  std::memcpy(ph + 2 * (T + 1), steps->alpha_jump, sizeof(float) * (T + 1));
+  const int32_t* pd = static_cast<const int32_t*>(steps->plan_dev);
+  *out = StepPlanDev{pd, reinterpret_cast<const float*>(pd + (T + 1)), reinterpret_cast<const float*>(pd + 2 * (T + 1)), s->alpha_bar};
+  return DIFFAB_OK;
+}
+
+// structure guidance: the potential's terms and per-residue tables; its kernel runs before every update
+static int guidance_option(const diffab_sample_guidance* guidance, const diffab_sched* s, uint32_t keep, GuidanceDev* out) {
+  if (guidance == nullptr) return DIFFAB_OK;
+  if (int rc = check_guidance_terms(guidance, "sample_loop")) return rc;
+  DIFFAB_REQUIRE(guidance->max_shift > 0.0f, DIFFAB_ERR_ARG, "sample_loop: guidance max_shift = %g must be > 0 (INFINITY: no cap)",
+                 guidance->max_shift);
+  DIFFAB_REQUIRE(guidance->t_max >= 0 && guidance->t_max <= s->T, DIFFAB_ERR_ARG, "sample_loop: guidance t_max = %d outside [0, T = %d]",
+                 guidance->t_max, s->T);
+  DIFFAB_REQUIRE(guidance->shift_dev != nullptr, DIFFAB_ERR_ARG, "sample_loop: guidance needs shift_dev");
+  DIFFAB_REQUIRE(!(keep & DIFFAB_FLAG_KEEP_STRUCTURE), DIFFAB_ERR_ARG,
+                 "sample_loop: guidance moves the structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
+  DIFFAB_REQUIRE(s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: guidance needs the schedule's alpha_bar_sqrt");
+  out->shift = guidance->shift_dev;
+  out->chain = guidance->chain;
+  out->residue_idx = guidance->residue_idx;
+  out->residue_mask = guidance->residue_mask;
+  out->w_clash = guidance->w_clash;
+  out->clash_distance = guidance->clash_distance;
+  out->w_bond = guidance->w_bond;
+  out->bond_length = guidance->bond_length;
+  out->max_shift = guidance->max_shift;
+  out->t_max = guidance->t_max;
+  return DIFFAB_OK;
+}
+
+// noise scales and sequence temperature: the pointers are checked (the per-row values are the caller's contract, like `allowed`)
+static int temperature_option(const diffab_sample_temperature* temperature, uint32_t keep, TemperatureDev* out) {
+  if (temperature == nullptr) return DIFFAB_OK;
+  DIFFAB_REQUIRE(!temperature->rot_scale || temperature->rot_row, DIFFAB_ERR_ARG,
+                 "sample_loop: temperature rot_scale needs rot_row (its rows of the stacked reverse table)");
+  DIFFAB_REQUIRE(!((temperature->trans_scale || temperature->rot_scale) && (keep & DIFFAB_FLAG_KEEP_STRUCTURE)), DIFFAB_ERR_ARG,
+                 "sample_loop: noise scales act on the structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
+  DIFFAB_REQUIRE(!(temperature->seq_temp && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
+                 "sample_loop: a sequence temperature acts on the sequence, which DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
+  *out = TemperatureDev{temperature->trans_scale, temperature->rot_scale, temperature->seq_temp, temperature->rot_row};
+  return DIFFAB_OK;
+}
+
+// particle steering: terms, tables and buffers; its kernels run around every update (the energy before it, weights, resampling and the
+// gather after it) and decide themselves which steps steer.  next_host: the packed step plan's next[] (nullptr: t - 1)
+static int steering_option(const diffab_sample_steering* q, const diffab_dims* d, const diffab_sched* s, uint32_t keep, int t_stop,
+                           const int32_t* next_host, SteeringDev* out) {
+  if (q == nullptr) return DIFFAB_OK;
+  diffab_sample_guidance terms{};
+  terms.w_clash = q->w_clash;
+  terms.clash_distance = q->clash_distance;
+  terms.w_bond = q->w_bond;
+  terms.bond_length = q->bond_length;
+  terms.chain = q->chain;
+  terms.residue_idx = q->residue_idx;
+  if (int rc = check_guidance_terms(&terms, "sample_loop (steering)")) return rc;
+  DIFFAB_REQUIRE(q->group_size >= 1 && q->group_size <= DIFFAB_STEER_MAX_GROUP, DIFFAB_ERR_ARG,
+                 "sample_loop: steering group_size = %d outside [1, %d]", q->group_size, DIFFAB_STEER_MAX_GROUP);
+  DIFFAB_REQUIRE(d->B % q->group_size == 0, DIFFAB_ERR_ARG, "sample_loop: %d rows are not a multiple of the steering group_size = %d", d->B,
+                 q->group_size);
+  DIFFAB_REQUIRE(std::isfinite(q->strength) && q->strength >= 0.0f, DIFFAB_ERR_ARG,
+                 "sample_loop: steering strength = %g must be finite and >= 0", q->strength);
+  DIFFAB_REQUIRE(q->ess_threshold >= 0.0f && q->ess_threshold <= 2.0f, DIFFAB_ERR_ARG, "sample_loop: steering ess_threshold = %g outside [0, 2]",
+                 q->ess_threshold);
+  DIFFAB_REQUIRE(q->t_min >= 0 && q->t_min <= q->t_max && q->t_max <= s->T, DIFFAB_ERR_ARG,
+                 "sample_loop: steering needs 0 <= t_min <= t_max <= T (t_min = %d, t_max = %d, T = %d)", q->t_min, q->t_max, s->T);
+  DIFFAB_REQUIRE(q->every >= 1, DIFFAB_ERR_ARG, "sample_loop: steering every = %d < 1", q->every);
+  DIFFAB_REQUIRE(q->logw && q->u_prev && q->energy && q->scratch, DIFFAB_ERR_ARG, "sample_loop: steering needs logw, u_prev, energy and scratch");
+  DIFFAB_REQUIRE(reinterpret_cast<uintptr_t>(q->scratch) % 8 == 0, DIFFAB_ERR_ARG, "sample_loop: steering scratch must be 8-byte aligned");
+  DIFFAB_REQUIRE(!(keep & DIFFAB_FLAG_KEEP_STRUCTURE), DIFFAB_ERR_ARG,
+                 "sample_loop: steering weighs the sampled structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
+  DIFFAB_REQUIRE(s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: steering needs the schedule's alpha_bar_sqrt");
+  out->logw = q->logw;
+  out->u_prev = q->u_prev;
+  out->energy = q->energy;
+  out->ancestors = q->ancestors;
+  out->scratch = q->scratch;
+  out->step_anc = reinterpret_cast<int32_t*>(static_cast<char*>(q->scratch) + static_cast<size_t>(d->B) * d->K * 56u);
+  out->chain = q->chain;
+  out->residue_idx = q->residue_idx;
+  out->residue_mask = q->residue_mask;
+  out->w_clash = q->w_clash;
+  out->clash_distance = q->clash_distance;
+  out->w_bond = q->w_bond;
+  out->bond_length = q->bond_length;
+  out->strength = q->strength;
+  out->ess_threshold = q->ess_threshold;
+  out->t_min = q->t_min;
+  out->t_max = q->t_max;
+  out->every = q->every;
+  out->group_size = q->group_size;
+  out->t_stop = t_stop;
+  out->next_host = next_host;
+  return DIFFAB_OK;
+}
+
+// Shared contexts: state row b reads context ctx_of_row[b] of n_ctx (0: d->B).  The map is checked here, on the host, so that no kernel
+// can index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
+static int context_map_option(const diffab_dims* d, const int32_t* ctx_of_row, int* n_ctx, bool* identity) {
+  if (*n_ctx == 0) *n_ctx = d->B;
+  DIFFAB_REQUIRE(ctx_of_row != nullptr || *n_ctx == d->B, DIFFAB_ERR_ARG, "sample_loop: without ctx_of_row n_ctx must equal B (%d != %d)",
+                 *n_ctx, d->B);
+  DIFFAB_REQUIRE(*n_ctx >= 1 && static_cast<int64_t>(*n_ctx) * d->K < (1ll << 31), DIFFAB_ERR_ARG, "sample_loop: need 1 <= n_ctx, n_ctx*K < 2^31");
+  *identity = *n_ctx == d->B;
+  for (int b = 0; ctx_of_row != nullptr && b < d->B; ++b) {
+    DIFFAB_REQUIRE(ctx_of_row[b] >= 0 && ctx_of_row[b] < *n_ctx, DIFFAB_ERR_ARG, "sample_loop: ctx_of_row[%d] = %d outside [0, %d)", b,
+                   ctx_of_row[b], *n_ctx);
+    *identity = *identity && ctx_of_row[b] == b;
+  }
+  return DIFFAB_OK;
+}
+
 int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
                        int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, const uint8_t* gen_mask, uint64_t seed,
                        int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags,
                        void* stream) {
-  // one context per state row: the shared-context loop with the identity map (which launches exactly what it always did)
-  if (int rc = check_dims(d, "sample_loop")) return rc;
-  return diffab_sample_loop_shared(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, d->B, nullptr, gen_mask, seed, first_patch, t_start, t_stop,
-                                   workspace, workspace_bytes, flags, stream);
+  return diffab_sample_loop_ex(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, gen_mask, seed, first_patch, t_start, t_stop, workspace,
+                               workspace_bytes, flags, nullptr, stream);
 }
 
-int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                              int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream) {
-  return diffab_sample_loop_aa(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start, t_stop,
-                               workspace, workspace_bytes, flags, nullptr, stream);
-}
-
-int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                          int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx, const int32_t* ctx_of_row,
-                          const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace,
-                          size_t workspace_bytes, uint32_t flags, const uint32_t* allowed, void* stream) {
-  return diffab_sample_loop_rec(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start, t_stop,
-                                workspace, workspace_bytes, flags, allowed, nullptr, stream);
-}
-
-int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                           int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                           const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                           int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                           const diffab_sample_record* rec, void* stream) {
-  return diffab_sample_loop_steps(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
-                                  t_stop, workspace, workspace_bytes, flags, allowed, rec, nullptr, stream);
-}
-
-int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                             int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                             const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                             int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                             const diffab_sample_record* rec, const diffab_sample_steps* steps, void* stream) {
-  return diffab_sample_loop_guided(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
-                                   t_stop, workspace, workspace_bytes, flags, allowed, rec, steps, nullptr, stream);
-}
-
-int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                              int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                              const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
-                              void* stream) {
-  return diffab_sample_loop_tempered(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
-                                     t_stop, workspace, workspace_bytes, flags, allowed, rec, steps, guidance, nullptr, stream);
-}
-
-int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                                int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                                const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                                int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                                const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
-                                const diffab_sample_temperature* temperature, void* stream) {
-  return diffab_sample_loop_steered(d, w, s, rev_tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row, gen_mask, seed, first_patch, t_start,
-                                    t_stop, workspace, workspace_bytes, flags, allowed, rec, steps, guidance, temperature, nullptr, stream);
-}
-
-int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                               int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                               const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                               int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                               const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
-                               const diffab_sample_temperature* temperature, const diffab_sample_steering* steering, void* stream) {
+int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                          int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, const uint8_t* gen_mask, uint64_t seed,
+                          int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags,
+                          const diffab_sample_options* opt_in, void* stream) {
   StreamOrder order_(stream);
+  DIFFAB_REQUIRE(!opt_in || opt_in->struct_bytes == sizeof(diffab_sample_options), DIFFAB_ERR_ARG,
+                 "sample_loop: options struct_bytes = %u, this library's diffab_sample_options has %zu", opt_in->struct_bytes,
+                 sizeof(diffab_sample_options));
+  diffab_sample_options none{};  // NULL options: every option off, exactly the zeroed struct
+  const diffab_sample_options* opt = opt_in ? opt_in : &none;
   if (int rc = check_dims(d, "sample_loop")) return rc;
   if (int rc = check_denoiser_weights(d, w)) return rc;
   DIFFAB_REQUIRE(s && s->T > 0 && s->alpha && s->beta && s->one_minus_alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: bad schedule");
@@ -862,164 +983,27 @@ int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weigh
                  "sample_loop: DIFFAB_FLAG_KEEP_STRUCTURE and DIFFAB_FLAG_KEEP_SEQUENCE together leave nothing to sample");
   flags &= ~keep;
   // sequence constraints: one word of allowed classes per (state row, residue), read by the update kernel's draw of s_{t-1} alone
+  const uint32_t* allowed = opt->allowed;
   DIFFAB_REQUIRE(!(allowed && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
                  "sample_loop: allowed classes constrain a sequence that DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
   DIFFAB_REQUIRE(!allowed || d->V <= 32, DIFFAB_ERR_ARG, "sample_loop: allowed classes are one 32-bit word per residue; V = %d > 32", d->V);
-  // trajectory recording: every slot is written by exactly one step of this call, so the record holds no stale entry
-  SampleRecordDev rdev;
-  if (rec != nullptr) {
-    DIFFAB_REQUIRE(rec->n_slots >= 1, DIFFAB_ERR_ARG, "sample_loop: record n_slots = %d < 1", rec->n_slots);
-    DIFFAB_REQUIRE(rec->slot_of_step && rec->slot_dev && rec->seq && rec->x && rec->O, DIFFAB_ERR_ARG,
-                   "sample_loop: record needs slot_of_step, slot_dev, seq, x and O");
-    const int n_pred = (rec->pred_x != nullptr) + (rec->pred_O != nullptr) + (rec->seq_probs != nullptr);
-    DIFFAB_REQUIRE(n_pred == 0 || n_pred == 3, DIFFAB_ERR_ARG, "sample_loop: record predictions are pred_x, pred_O and seq_probs, all or none");
-    DIFFAB_REQUIRE(n_pred == 0 || s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: record predictions need the schedule's alpha_bar_sqrt");
-    std::vector<int> used(rec->n_slots, 0);
-    for (int t = 0; t <= s->T; ++t) {
-      const int j = rec->slot_of_step[t];
-      if (j == -1) continue;
-      DIFFAB_REQUIRE(j >= 0 && j < rec->n_slots, DIFFAB_ERR_ARG, "sample_loop: record slot_of_step[%d] = %d outside -1, [0, %d)", t, j,
-                     rec->n_slots);
-      DIFFAB_REQUIRE(t > t_stop && t <= t_start, DIFFAB_ERR_ARG,
-                     "sample_loop: record slot_of_step[%d] = %d, but the call runs steps [%d, %d] only (the slot would never be written)", t, j,
-                     t_stop + 1, t_start);
-      DIFFAB_REQUIRE(used[j]++ == 0, DIFFAB_ERR_ARG, "sample_loop: record slot %d is given to two steps", j);
-    }
-    for (int j = 0; j < rec->n_slots; ++j)
-      DIFFAB_REQUIRE(used[j] == 1, DIFFAB_ERR_ARG, "sample_loop: record slot %d is given to no step", j);
-    rdev = SampleRecordDev{rec->slot_dev, rec->n_slots, rec->seq, rec->x, rec->O, rec->pred_x, rec->pred_O, rec->seq_probs,
-                           n_pred ? s->alpha_bar_sqrt : nullptr};
-  }
-  // fewer-step sampling: the list, its jump coefficients and the record are checked here, and the device plan - next[], beta'[], alpha'[]
-  // - is packed once (copied to plan_dev below, after every check)
-  StepPlanDev pdev;
-  std::vector<int32_t> plan_host;
-  if (steps != nullptr) {
-    const int T = s->T;
-    DIFFAB_REQUIRE(steps->n_steps >= 1, DIFFAB_ERR_ARG, "sample_loop: steps n_steps = %d < 1", steps->n_steps);
-    DIFFAB_REQUIRE(steps->steps && steps->beta_jump && steps->alpha_jump && steps->plan_dev, DIFFAB_ERR_ARG,
-                   "sample_loop: steps needs steps, beta_jump, alpha_jump and plan_dev");
-    DIFFAB_REQUIRE(s->alpha_bar, DIFFAB_ERR_ARG, "sample_loop: steps need the schedule's alpha_bar");
-    DIFFAB_REQUIRE(steps->steps[0] == t_start, DIFFAB_ERR_ARG, "sample_loop: steps[0] = %d, t_start = %d", steps->steps[0], t_start);
-    std::vector<char> listed(T + 1, 0);
-    for (int j = 0; j < steps->n_steps; ++j) {
-      const int t = steps->steps[j];
-      DIFFAB_REQUIRE(t > t_stop && t <= T, DIFFAB_ERR_ARG, "sample_loop: steps[%d] = %d outside [t_stop + 1, T] = [%d, %d]", j, t, t_stop + 1, T);
-      DIFFAB_REQUIRE(j == 0 || t < steps->steps[j - 1], DIFFAB_ERR_ARG, "sample_loop: steps are not strictly descending at %d (%d after %d)", j,
-                     t, steps->steps[j - 1]);
-      const float bj = steps->beta_jump[t], aj = steps->alpha_jump[t];
-      DIFFAB_REQUIRE(bj > 0.0f && bj < 1.0f && aj > 0.0f && aj < 1.0f, DIFFAB_ERR_ARG,
-                     "sample_loop: jump coefficients at step %d outside (0, 1): beta' = %g, alpha' = %g", t, bj, aj);
-      listed[t] = 1;
-    }
-    if (rec != nullptr)
-      for (int t = 0; t <= T; ++t)
-        DIFFAB_REQUIRE(rec->slot_of_step[t] == -1 || listed[t], DIFFAB_ERR_ARG,
-                       "sample_loop: record slot_of_step[%d] = %d, but the step list does not run step %d", t, rec->slot_of_step[t], t);
-    plan_host.resize(3 * static_cast<size_t>(T + 1));
-    for (int t = 0; t <= T; ++t) plan_host[t] = t > 0 ? t - 1 : 0;
-    for (int j = 0; j < steps->n_steps; ++j) plan_host[steps->steps[j]] = j + 1 < steps->n_steps ? steps->steps[j + 1] : t_stop;
-    std::memcpy(plan_host.data() + (T + 1), steps->beta_jump, sizeof(float) * (T + 1));
-    std::memcpy(plan_host.data() + 2 * (T + 1), steps->alpha_jump, sizeof(float) * (T + 1));
-    const int32_t* pd = static_cast<const int32_t*>(steps->plan_dev);
-    pdev = StepPlanDev{pd, reinterpret_cast<const float*>(pd + (T + 1)), reinterpret_cast<const float*>(pd + 2 * (T + 1)), s->alpha_bar};
-  }
-  // structure guidance: the potential's terms and per-residue tables are checked here; its kernel runs before every update
-  GuidanceDev gdev;
-  if (guidance != nullptr) {
-    if (int rc = check_guidance_terms(guidance, "sample_loop")) return rc;
-    DIFFAB_REQUIRE(guidance->max_shift > 0.0f, DIFFAB_ERR_ARG, "sample_loop: guidance max_shift = %g must be > 0 (INFINITY: no cap)",
-                   guidance->max_shift);
-    DIFFAB_REQUIRE(guidance->t_max >= 0 && guidance->t_max <= s->T, DIFFAB_ERR_ARG, "sample_loop: guidance t_max = %d outside [0, T = %d]",
-                   guidance->t_max, s->T);
-    DIFFAB_REQUIRE(guidance->shift_dev != nullptr, DIFFAB_ERR_ARG, "sample_loop: guidance needs shift_dev");
-    DIFFAB_REQUIRE(!(keep & DIFFAB_FLAG_KEEP_STRUCTURE), DIFFAB_ERR_ARG,
-                   "sample_loop: guidance moves the structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
-    DIFFAB_REQUIRE(s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: guidance needs the schedule's alpha_bar_sqrt");
-    gdev.shift = guidance->shift_dev;
-    gdev.chain = guidance->chain;
-    gdev.residue_idx = guidance->residue_idx;
-    gdev.residue_mask = guidance->residue_mask;
-    gdev.w_clash = guidance->w_clash;
-    gdev.clash_distance = guidance->clash_distance;
-    gdev.w_bond = guidance->w_bond;
-    gdev.bond_length = guidance->bond_length;
-    gdev.max_shift = guidance->max_shift;
-    gdev.t_max = guidance->t_max;
-  }
-  // noise scales and sequence temperature: the pointers are checked here (the per-row values are the caller's contract, like `allowed`)
-  TemperatureDev tdev;
-  if (temperature != nullptr) {
-    DIFFAB_REQUIRE(!temperature->rot_scale || temperature->rot_row, DIFFAB_ERR_ARG,
-                   "sample_loop: temperature rot_scale needs rot_row (its rows of the stacked reverse table)");
-    DIFFAB_REQUIRE(!((temperature->trans_scale || temperature->rot_scale) && (keep & DIFFAB_FLAG_KEEP_STRUCTURE)), DIFFAB_ERR_ARG,
-                   "sample_loop: noise scales act on the structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
-    DIFFAB_REQUIRE(!(temperature->seq_temp && (keep & DIFFAB_FLAG_KEEP_SEQUENCE)), DIFFAB_ERR_ARG,
-                   "sample_loop: a sequence temperature acts on the sequence, which DIFFAB_FLAG_KEEP_SEQUENCE does not sample");
-    tdev = TemperatureDev{temperature->trans_scale, temperature->rot_scale, temperature->seq_temp, temperature->rot_row};
-  }
-  // particle steering: terms, tables and buffers are checked here; its kernels run around every update (the energy before it, weights,
-  // resampling and the gather after it) and decide themselves which steps steer
-  SteeringDev sdev;
-  if (steering != nullptr) {
-    const diffab_sample_steering* q = steering;
-    diffab_sample_guidance terms{};
-    terms.w_clash = q->w_clash;
-    terms.clash_distance = q->clash_distance;
-    terms.w_bond = q->w_bond;
-    terms.bond_length = q->bond_length;
-    terms.chain = q->chain;
-    terms.residue_idx = q->residue_idx;
-    if (int rc = check_guidance_terms(&terms, "sample_loop (steering)")) return rc;
-    DIFFAB_REQUIRE(q->group_size >= 1 && q->group_size <= DIFFAB_STEER_MAX_GROUP, DIFFAB_ERR_ARG,
-                   "sample_loop: steering group_size = %d outside [1, %d]", q->group_size, DIFFAB_STEER_MAX_GROUP);
-    DIFFAB_REQUIRE(d->B % q->group_size == 0, DIFFAB_ERR_ARG, "sample_loop: %d rows are not a multiple of the steering group_size = %d", d->B,
-                   q->group_size);
-    DIFFAB_REQUIRE(std::isfinite(q->strength) && q->strength >= 0.0f, DIFFAB_ERR_ARG,
-                   "sample_loop: steering strength = %g must be finite and >= 0", q->strength);
-    DIFFAB_REQUIRE(q->ess_threshold >= 0.0f && q->ess_threshold <= 2.0f, DIFFAB_ERR_ARG, "sample_loop: steering ess_threshold = %g outside [0, 2]",
-                   q->ess_threshold);
-    DIFFAB_REQUIRE(q->t_min >= 0 && q->t_min <= q->t_max && q->t_max <= s->T, DIFFAB_ERR_ARG,
-                   "sample_loop: steering needs 0 <= t_min <= t_max <= T (t_min = %d, t_max = %d, T = %d)", q->t_min, q->t_max, s->T);
-    DIFFAB_REQUIRE(q->every >= 1, DIFFAB_ERR_ARG, "sample_loop: steering every = %d < 1", q->every);
-    DIFFAB_REQUIRE(q->logw && q->u_prev && q->energy && q->scratch, DIFFAB_ERR_ARG, "sample_loop: steering needs logw, u_prev, energy and scratch");
-    DIFFAB_REQUIRE(reinterpret_cast<uintptr_t>(q->scratch) % 8 == 0, DIFFAB_ERR_ARG, "sample_loop: steering scratch must be 8-byte aligned");
-    DIFFAB_REQUIRE(!(keep & DIFFAB_FLAG_KEEP_STRUCTURE), DIFFAB_ERR_ARG,
-                   "sample_loop: steering weighs the sampled structure, which DIFFAB_FLAG_KEEP_STRUCTURE does not sample");
-    DIFFAB_REQUIRE(s->alpha_bar_sqrt, DIFFAB_ERR_ARG, "sample_loop: steering needs the schedule's alpha_bar_sqrt");
-    sdev.logw = q->logw;
-    sdev.u_prev = q->u_prev;
-    sdev.energy = q->energy;
-    sdev.ancestors = q->ancestors;
-    sdev.scratch = q->scratch;
-    sdev.step_anc = reinterpret_cast<int32_t*>(static_cast<char*>(q->scratch) + static_cast<size_t>(d->B) * d->K * 56u);
-    sdev.chain = q->chain;
-    sdev.residue_idx = q->residue_idx;
-    sdev.residue_mask = q->residue_mask;
-    sdev.w_clash = q->w_clash;
-    sdev.clash_distance = q->clash_distance;
-    sdev.w_bond = q->w_bond;
-    sdev.bond_length = q->bond_length;
-    sdev.strength = q->strength;
-    sdev.ess_threshold = q->ess_threshold;
-    sdev.t_min = q->t_min;
-    sdev.t_max = q->t_max;
-    sdev.every = q->every;
-    sdev.group_size = q->group_size;
-    sdev.t_stop = t_stop;
-    sdev.next_host = steps != nullptr ? plan_host.data() : nullptr;
-  }
-  // Shared contexts: state row b reads context ctx_of_row[b] of n_ctx.  The map is checked here, on the host, so that no kernel can
-  // index outside the caller's contexts; a map that is the identity launches exactly the one-context-per-row form.
+  const diffab_sample_record* rec = opt->record;
+  const diffab_sample_steps* steps = opt->steps;
+  const diffab_sample_steering* steering = opt->steering;
+  UpdateOptions uo;
+  uo.keep = keep;
+  uo.allowed = allowed;
+  std::vector<int32_t> plan_host;  // the step plan as the device reads it (empty without steps)
+  if (int rc = record_option(rec, s, t_start, t_stop, &uo.rec)) return rc;
+  if (int rc = steps_option(steps, rec, s, t_start, t_stop, &plan_host, &uo.plan)) return rc;
+  if (int rc = guidance_option(opt->guidance, s, keep, &uo.guide)) return rc;
+  if (int rc = temperature_option(opt->temperature, keep, &uo.temp)) return rc;
+  if (int rc = steering_option(steering, d, s, keep, t_stop, steps != nullptr ? plan_host.data() : nullptr, &uo.steer)) return rc;
+  const int32_t* ctx_of_row = opt->ctx_of_row;
   const bool mapped = ctx_of_row != nullptr;
-  DIFFAB_REQUIRE(mapped || n_ctx == d->B, DIFFAB_ERR_ARG, "sample_loop: without ctx_of_row n_ctx must equal B (%d != %d)", n_ctx, d->B);
-  DIFFAB_REQUIRE(n_ctx >= 1 && static_cast<int64_t>(n_ctx) * d->K < (1ll << 31), DIFFAB_ERR_ARG, "sample_loop: need 1 <= n_ctx, n_ctx*K < 2^31");
-  bool identity = n_ctx == d->B;
-  for (int b = 0; mapped && b < d->B; ++b) {
-    DIFFAB_REQUIRE(ctx_of_row[b] >= 0 && ctx_of_row[b] < n_ctx, DIFFAB_ERR_ARG, "sample_loop: ctx_of_row[%d] = %d outside [0, %d)", b,
-                   ctx_of_row[b], n_ctx);
-    identity = identity && ctx_of_row[b] == b;
-  }
+  int n_ctx = opt->n_ctx;
+  bool identity = false;
+  if (int rc = context_map_option(d, ctx_of_row, &n_ctx, &identity)) return rc;
   const SampleBuffers sb = carve_sample(d, workspace, n_ctx, mapped);
   DIFFAB_REQUIRE(workspace_bytes >= sb.bytes, DIFFAB_ERR_WORKSPACE, "sample_loop: workspace %zu < %zu bytes", workspace_bytes, sb.bytes);
   hipStream_t st = as_stream(stream);
@@ -1044,7 +1028,7 @@ int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weigh
     if (int rc = launch_tiles_needed(gen_mask, d->B, d->K, sb.tiles, st)) return rc;
   if (rec != nullptr) {  // the step -> slot table, and the residues the loop never writes, once per call
     DIFFAB_HIP_CHECK(hipMemcpyAsync(rec->slot_dev, rec->slot_of_step, sizeof(int32_t) * (s->T + 1), hipMemcpyHostToDevice, st));
-    if (int rc = launch_record_fixed(rdev, seq, x, O, gen_mask, d->B, d->K, d->V, st)) return rc;
+    if (int rc = launch_record_fixed(uo.rec, seq, x, O, gen_mask, d->B, d->K, d->V, st)) return rc;
   }
   if (steps != nullptr)  // the step plan, once per call
     DIFFAB_HIP_CHECK(hipMemcpyAsync(steps->plan_dev, plan_host.data(), sizeof(int32_t) * plan_host.size(), hipMemcpyHostToDevice, st));
@@ -1059,7 +1043,7 @@ int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weigh
     if (int rc = denoise_step(d, w, plan, step, seq, x, O, res_ctx, pair_ctx, sb.eps, nullptr, nullptr, nullptr, b0, st)) return rc;
     // (the heads' epilogue - O0 = O_t exp(hat(v)), the posterior's softmax - runs inside the update kernel, for the generated rows)
     return launch_reverse_update_philox(s, rev_tab, t, seq, x, O, sb.eps, sb.O0, sb.post, gen_mask, seed, first_patch, d->B, d->K, d->V, st,
-                                        t_dev, b0.vbuf, b0.logits, keep, allowed, rdev, pdev, gdev, tdev, sdev);
+                                        t_dev, b0.vbuf, b0.logits, uo);
   };
   // DIFFAB_FLAG_GRAPH_SAMPLER: a step is ~45 launches; at B = 1 (BASELINE config 1) their host cost (3-4 us each) is several times
   // the kernels' own time.  The first step runs eagerly (it also performs the one-time function-attribute calls), the second is
@@ -1100,7 +1084,7 @@ int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weigh
     ei = hipStreamBeginCapture(side, hipStreamCaptureModeThreadLocal);
     if (ei == hipSuccess) {
       rc = one_step(t_second, sb.t_dev);
-      if (rc == DIFFAB_OK) rc = steps != nullptr ? launch_advance_step(sb.t_dev, pdev.next, side) : launch_dec_int(sb.t_dev, side);
+      if (rc == DIFFAB_OK) rc = steps != nullptr ? launch_advance_step(sb.t_dev, uo.plan.next, side) : launch_dec_int(sb.t_dev, side);
       ei = hipStreamEndCapture(side, &g);
     }
     st = caller;

@@ -234,7 +234,7 @@ int launch_losses_fwd(const float* pp, const float* tp, const float* pe, const f
                       float* scratch = nullptr);  // scratch: 1024 floats -> the multi-work-group two-stage reduction
 
 // diffusion_kernels.hip
-// Trajectory recording (diffab_sample_loop_rec), a by-value launch argument of the update kernel: constant for a whole call, so the
+// Trajectory recording (diffab_sample_options.record), a by-value launch argument of the update kernel: constant for a whole call, so the
 // captured step of graph replay carries it unchanged.  slot == nullptr: nothing is recorded (one uniform branch).  Entry (b, j, k) of
 // every field is (b n_slots + j) K + k; pred_x == nullptr: the state alone.
 struct SampleRecordDev {
@@ -248,7 +248,7 @@ struct SampleRecordDev {
   float* seq_probs = nullptr;
   const float* alpha_bar_sqrt = nullptr;  // the schedule's, for x0_hat (read with predictions only)
 };
-// Fewer-step sampling (diffab_sample_loop_steps), a by-value launch argument of the update kernel like the record: next == nullptr is the
+// Fewer-step sampling (diffab_sample_options.steps), a by-value launch argument of the update kernel like the record: next == nullptr is the
 // ordinary step t -> t - 1.  The three tables (T + 1 entries, device) are the call's plan; alpha_bar is the schedule's.
 struct StepPlanDev {
   const int32_t* next = nullptr;  // step t -> the step s the update moves the state to
@@ -256,7 +256,7 @@ struct StepPlanDev {
   const float* alpha = nullptr;   // alpha'_t
   const float* alpha_bar = nullptr;
 };
-// Structure guidance (diffab_sample_loop_guided), a by-value launch argument of the update kernel like the plan: shift == nullptr is
+// Structure guidance (diffab_sample_options.guidance), a by-value launch argument of the update kernel like the plan: shift == nullptr is
 // off.  launch_reverse_update_philox runs the guidance kernel first (Delta into shift), and the update subtracts Delta from the mean of
 // the translations at the steps t <= t_max.
 struct GuidanceDev {
@@ -267,7 +267,7 @@ struct GuidanceDev {
   float w_clash = 0.f, clash_distance = 0.f, w_bond = 0.f, bond_length = 0.f, max_shift = 0.f;
   int32_t t_max = -1;
 };
-// Noise scales and sequence temperature (diffab_sample_loop_tempered), a by-value launch argument of the update kernel like the plan:
+// Noise scales and sequence temperature (diffab_sample_options.temperature), a by-value launch argument of the update kernel like the plan:
 // one entry per state row of the launch (i / K), each pointer nullable (null = 1 for that quantity; all null is today's update).  rot_row
 // is the row of the state row's sigma list in the stacked reverse table: step t reads table row rot_row + t.
 struct TemperatureDev {
@@ -276,7 +276,7 @@ struct TemperatureDev {
   const float* seq_temp = nullptr;     // tau >= 0
   const int32_t* rot_row = nullptr;
 };
-// Particle steering (diffab_sample_loop_steered), by value like the guidance: logw == nullptr is off and today's
+// Particle steering (diffab_sample_options.steering), by value like the guidance: logw == nullptr is off and today's
 // launch sequence.  Every steering kernel evaluates the steering-step predicate itself (steer_is_step), so a replayed graph needs no
 // host decision.  step_anc is the step's ancestor map (rows, group-local indices) the gather reads; ancestors the nullable record.
 struct SteeringDev {
@@ -302,17 +302,22 @@ int launch_steer_energy(const SteeringDev& sd, const diffab_sched* s, const Step
                         const float* eps_hat, const uint8_t* gm, int B, int K, hipStream_t st);
 int launch_steer_resample_gather(const SteeringDev& sd, const StepPlanDev& plan, int t, const int* t_dev, int64_t* seq, float* x, float* O,
                                  const uint8_t* gm, uint64_t seed, int64_t first_patch, int B, int K, bool copy_seq, hipStream_t st);
+// The options of a reverse update, constant for a whole diffab_sample_loop_ex call (host side: the launcher unpacks it into the update
+// kernel's launch arguments).  A default-constructed one is the plain update.
+struct UpdateOptions {
+  uint32_t keep = 0;                  // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
+  const uint32_t* allowed = nullptr;  // per-residue allowed-class words of the sequence draw (nullable)
+  SampleRecordDev rec;                // trajectory recording (rec.slot nullable)
+  StepPlanDev plan;                   // fewer-step sampling (plan.next nullable)
+  GuidanceDev guide;                  // structure guidance (guide.shift nullable)
+  TemperatureDev temp;                // noise scales / sequence temperature (all nullable)
+  SteeringDev steer;                  // particle steering (steer.logw nullable)
+};
+// t_dev: read the timestep from device memory (graph replay); head_v / head_logits: the heads' epilogue done in the kernel
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
-                                 int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev = nullptr,
-                                 const float* head_v = nullptr, const float* head_logits = nullptr,  // heads' epilogue done in the kernel  // t_dev: read the timestep from device memory (graph replay)
-                                 uint32_t keep = 0,   // DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE: the modality left unwritten
-                                 const uint32_t* allowed = nullptr,  // per-residue allowed-class words of the sequence draw (nullable)
-                                 const SampleRecordDev& rec = SampleRecordDev{},  // trajectory recording (rec.slot nullable)
-                                 const StepPlanDev& plan = StepPlanDev{},  // fewer-step sampling (plan.next nullable)
-                                 const GuidanceDev& guide = GuidanceDev{},  // structure guidance (guide.shift nullable)
-                                 const TemperatureDev& temp = TemperatureDev{},  // noise scales / sequence temperature (all nullable)
-                                 const SteeringDev& steer = SteeringDev{});  // particle steering (steer.logw nullable)
+                                 int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
+                                 const float* head_logits, const UpdateOptions& o);
 int check_guidance_terms(const diffab_sample_guidance* g, const char* who);  // weights, distances, chain / residue_idx (DIFFAB_ERR_ARG)
 // the residues that are not generated: their (constant) state in every slot of the record, and their predictions - the given x / O and a
 // one-hot of the token - once per call

@@ -357,7 +357,7 @@ __device__ inline int categorical_draw(const float* __restrict__ p, int V, float
   return V - 1;
 }
 
-// categorical_draw restricted to the classes v < V whose bit is set in `allowed` (sequence constraints, diffab_sample_loop_aa): the same
+// categorical_draw restricted to the classes v < V whose bit is set in `allowed` (sequence constraints, diffab_sample_options.allowed): the same
 // running sums over the allowed classes only, in increasing v, so with every class allowed the float operations - and the draw - are
 // categorical_draw's.  Every allowed class at probability 0: the floor(u n)-th of the n allowed classes (unit weights in the same
 // loop).  No class allowed: -1, and the caller leaves the token as it is.
@@ -1301,22 +1301,21 @@ __global__ void advance_step_kernel(int* __restrict__ p, const int* __restrict__
 int launch_reverse_update_philox(const diffab_sched* s, const diffab_igso3* tab, int t, int64_t* seq, float* x, float* O,
                                  const float* eps_hat, float* O0_hat, float* post, const uint8_t* gm, uint64_t seed,
                                  int64_t first_patch, int B, int K, int V, hipStream_t st, const int* t_dev, const float* head_v,
-                                 const float* head_logits, uint32_t keep, const uint32_t* allowed, const SampleRecordDev& rec,
-                                 const StepPlanDev& plan, const GuidanceDev& guide, const TemperatureDev& temp, const SteeringDev& steer) {
+                                 const float* head_logits, const UpdateOptions& o) {
   const int64_t n = static_cast<int64_t>(B) * K;
-  if (steer.logw != nullptr)  // particle steering: U of every row at x0_hat of this step, before any shift and before the update
-    if (int rc = launch_steer_energy(steer, s, plan, t, t_dev, x, eps_hat, gm, B, K, st)) return rc;
-  if (guide.shift != nullptr) {  // every launch form reaches the update through here: Delta of this step first
-    hipLaunchKernelGGL(guidance_shift_kernel, dim3(B), dim3(kGuideThreads), 0, st, guide, x, eps_hat, gm, plan.next ? plan.beta : s->beta,
+  if (o.steer.logw != nullptr)  // particle steering: U of every row at x0_hat of this step, before any shift and before the update
+    if (int rc = launch_steer_energy(o.steer, s, o.plan, t, t_dev, x, eps_hat, gm, B, K, st)) return rc;
+  if (o.guide.shift != nullptr) {  // every launch form reaches the update through here: Delta of this step first
+    hipLaunchKernelGGL(guidance_shift_kernel, dim3(B), dim3(kGuideThreads), 0, st, o.guide, x, eps_hat, gm, o.plan.next ? o.plan.beta : s->beta,
                        s->one_minus_alpha_bar_sqrt, s->alpha_bar_sqrt, t, t_dev, K);
     DIFFAB_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(reverse_update_philox_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, s->beta, s->alpha,
                      s->one_minus_alpha_bar_sqrt, t, tab->sigmas, tab->cdf, tab->n_bins, tab->sigma_threshold, seq, x, O, eps_hat, O0_hat,
-                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, keep, allowed, rec, plan, guide, temp);
+                     post, gm, seed, first_patch, B, K, V, t_dev, head_v, head_logits, o.keep, o.allowed, o.rec, o.plan, o.guide, o.temp);
   DIFFAB_LAUNCH_CHECK();
-  if (steer.logw != nullptr)  // weights, resampling and the gather of the ancestors' generated residues, on the updated state
-    return launch_steer_resample_gather(steer, plan, t, t_dev, seq, x, O, gm, seed, first_patch, B, K, !(keep & DIFFAB_FLAG_KEEP_SEQUENCE), st);
+  if (o.steer.logw != nullptr)  // weights, resampling and the gather of the ancestors' generated residues, on the updated state
+    return launch_steer_resample_gather(o.steer, o.plan, t, t_dev, seq, x, O, gm, seed, first_patch, B, K, !(o.keep & DIFFAB_FLAG_KEEP_SEQUENCE), st);
   return DIFFAB_OK;
 }
 
@@ -1399,7 +1398,7 @@ int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hip
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
-// shared contexts (diffab_sample_loop_shared): the residue context rows of every state row, once per call
+// shared contexts (diffab_sample_options.ctx_of_row): the residue context rows of every state row, once per call
 __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ ctx_of_row, int64_t row_floats, int64_t n,
                                    float* __restrict__ out) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -1433,7 +1432,7 @@ int launch_advance_step(int* p, const int* next, hipStream_t st) {
 
 using namespace diffab;
 
-// structure guidance: the checks diffab_sample_loop_guided and diffab_guidance_energy share (weights, distances, the per-residue tables)
+// structure guidance: the checks diffab_sample_loop_ex and diffab_guidance_energy share (weights, distances, the per-residue tables)
 int diffab::check_guidance_terms(const diffab_sample_guidance* g, const char* who) {
   DIFFAB_REQUIRE(g != nullptr, DIFFAB_ERR_ARG, "%s: guidance is null", who);
   DIFFAB_REQUIRE(std::isfinite(g->w_clash) && g->w_clash >= 0.0f && std::isfinite(g->w_bond) && g->w_bond >= 0.0f, DIFFAB_ERR_ARG,
@@ -1797,15 +1796,10 @@ int diffab_guidance_energy(const float* x, const uint8_t* gen_mask, const diffab
 
 int diffab_sample_init(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K,
                        int32_t T, void* stream) {
-  return diffab_sample_init_ex(seq, x, O, gen_mask, seed, first_patch, B, K, T, 0u, stream);
+  return diffab_sample_init_ex(seq, x, O, gen_mask, seed, first_patch, B, K, T, 0u, nullptr, stream);
 }
 
 int diffab_sample_init_ex(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
-                          int32_t K, int32_t T, uint32_t flags, void* stream) {
-  return diffab_sample_init_aa(seq, x, O, gen_mask, seed, first_patch, B, K, T, flags, nullptr, stream);
-}
-
-int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
                           int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream) {
   StreamOrder order_(stream);
   DIFFAB_REQUIRE(seq && x && O && gen_mask && B >= 0 && K > 0 && T > 0, DIFFAB_ERR_ARG, "sample_init: bad argument");
@@ -1823,13 +1817,8 @@ int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_m
 }
 
 int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O, const uint8_t* gen_mask,
-                              uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t, uint32_t flags, void* stream) {
-  return diffab_sample_init_noised_aa(s, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, nullptr, stream);
-}
-
-int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
-                                 const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t, uint32_t flags,
-                                 const uint32_t* allowed, void* stream) {
+                              uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t, uint32_t flags, const uint32_t* allowed,
+                              void* stream) {
   StreamOrder order_(stream);
   if (int rc = check_sched(s)) return rc;
   DIFFAB_REQUIRE(seq && x && O && gen_mask && B >= 0 && K > 0, DIFFAB_ERR_ARG, "sample_init_noised: bad argument");

@@ -113,7 +113,7 @@ __device__ __forceinline__ void attn_shift_pair_rows(FP& e, FP& esc, const int* 
 // and of the patch-resident module kernel (ipa_persistent.hip: a work-group walks the eight row tiles of ITS patch, layer after layer).
 // 512 threads; S: the dynamic LDS (ipa_attn_lds_bytes(NT)); stamp_id: the slot of this item in the diagnostic stamp buffer.
 // Eight waves: wave = head in phases 1 and 3, two query rows in phase 2.
-// ctx_of_row (shared contexts, diffab_sample_loop_shared): the pair rows (and their row scales) of state row b are those of context
+// ctx_of_row (shared contexts, diffab_sample_options.ctx_of_row): the pair rows (and their row scales) of state row b are those of context
 // ctx_of_row[b] - `e` / `esc` then hold n_ctx patches; the projections and features stay on row b.  nullptr: the identity.
 template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false>
 __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b, const int tile, const unsigned stamp_id,

@@ -87,29 +87,43 @@ class ScoreNoised(C.Structure):  # diffab_score_noised: optional copies of the n
     _fields_ = [(n, _fp) for n in ("seq_t", "x_t", "O_t", "eps")]
 
 
-class SampleRecord(C.Structure):  # diffab_sample_record: the recorded reverse trajectory of diffab_sample_loop_rec
+class SampleRecord(C.Structure):  # diffab_sample_record: the recorded reverse trajectory (SampleOptions.record)
     _fields_ = [("n_slots", C.c_int32), ("slot_of_step", C.POINTER(C.c_int32)), ("slot_dev", _fp)] + \
         [(n, _fp) for n in ("seq", "x", "O", "pred_x", "pred_O", "seq_probs")]
 
 
-class SampleSteps(C.Structure):  # diffab_sample_steps: the executed step list of diffab_sample_loop_steps and its jump coefficients
+class SampleSteps(C.Structure):  # diffab_sample_steps: the executed step list and its jump coefficients (SampleOptions.steps)
     _fields_ = [("n_steps", C.c_int32), ("steps", C.POINTER(C.c_int32)), ("beta_jump", C.POINTER(C.c_float)),
                 ("alpha_jump", C.POINTER(C.c_float)), ("plan_dev", _fp)]
 
 
-class SampleGuidance(C.Structure):  # diffab_sample_guidance: the clash / chain-bond potential of diffab_sample_loop_guided
+class SampleGuidance(C.Structure):  # diffab_sample_guidance: the clash / chain-bond potential (SampleOptions.guidance)
     _fields_ = [(n, C.c_float) for n in ("w_clash", "clash_distance", "w_bond", "bond_length", "max_shift")] + \
         [("t_max", C.c_int32)] + [(n, _fp) for n in ("chain", "residue_idx", "residue_mask", "shift_dev")]
 
 
-class SampleTemperature(C.Structure):  # diffab_sample_temperature: per-row noise scales and sequence temperature of diffab_sample_loop_tempered
+class SampleTemperature(C.Structure):  # diffab_sample_temperature: per-row noise scales and sequence temperature (SampleOptions.temperature)
     _fields_ = [(n, _fp) for n in ("trans_scale", "rot_scale", "seq_temp", "rot_row")]
 
 
-class SampleSteering(C.Structure):  # diffab_sample_steering: particle steering of diffab_sample_loop_steered
+class SampleSteering(C.Structure):  # diffab_sample_steering: particle steering (SampleOptions.steering)
     _fields_ = [(n, C.c_float) for n in ("w_clash", "clash_distance", "w_bond", "bond_length", "strength", "ess_threshold")] + \
         [(n, C.c_int32) for n in ("t_min", "t_max", "every", "group_size")] + \
         [(n, _fp) for n in ("chain", "residue_idx", "residue_mask", "logw", "u_prev", "energy", "ancestors", "scratch")]
+
+
+class SampleOptions(C.Structure):
+    """diffab_sample_options: the options of one diffab_sample_loop_ex call, by keyword (what is left out is off); struct_bytes is
+    filled in here.  The structure keeps the Python objects its pointer fields were given alive, not the device memory behind them."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_ctx", C.c_int32), ("ctx_of_row", C.POINTER(C.c_int32)), ("allowed", _fp),
+                ("record", C.POINTER(SampleRecord)), ("steps", C.POINTER(SampleSteps)), ("guidance", C.POINTER(SampleGuidance)),
+                ("temperature", C.POINTER(SampleTemperature)), ("steering", C.POINTER(SampleSteering))]
+
+    def __init__(self, **options):
+        for name in ("record", "steps", "guidance", "temperature", "steering"):  # a structure (or None) where the field is a pointer
+            if isinstance(options.get(name), C.Structure):
+                options[name] = C.pointer(options[name])
+        super().__init__(struct_bytes=C.sizeof(type(self)), **{k: v for k, v in options.items() if v is not None})
 
 
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
@@ -210,39 +224,14 @@ SYMBOLS = {
     "diffab_reverse_update": (C.c_int, [_PS, _i32, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _fp]),
     "diffab_sample_loop": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _fp, _u64, _i64, _i32,
                                      _i32, _fp, _sz, _u32, _fp]),
-    # (d, w, sched, tab, seq, x, O, res_ctx, pair_ctx, n_ctx, ctx_of_row (host int32[B]), gen_mask, seed, first_patch, t_start, t_stop,
-    #  ws, ws_bytes, flags, stream)
-    "diffab_sample_loop_shared": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                            _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp]),
+    # diffab_sample_loop's arguments plus the options (nullable) before the stream
+    "diffab_sample_loop_ex": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _fp, _u64, _i64, _i32,
+                                        _i32, _fp, _sz, _u32, C.POINTER(SampleOptions), _fp]),
     "diffab_sample_init": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _fp]),
-    # (seq, x, O, gen_mask, seed, first_patch, B, K, T, flags, stream)
-    "diffab_sample_init_ex": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
-    # (sched, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, stream)
-    "diffab_sample_init_noised": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp]),
-    # sequence constraints: the three entries above plus `allowed` (device uint32[B*K], nullable) before the stream
-    "diffab_sample_loop_aa": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                        _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, _fp]),
-    "diffab_sample_init_aa": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
-    "diffab_sample_init_noised_aa": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
-    # trajectory recording: diffab_sample_loop_aa plus `rec` (nullable) before the stream
-    "diffab_sample_loop_rec": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                         _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), _fp]),
-    # fewer-step sampling: diffab_sample_loop_rec plus `steps` (nullable) before the stream
-    "diffab_sample_loop_steps": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                           _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
-                                           _fp]),
-    # structure guidance: diffab_sample_loop_steps plus `guidance` (nullable) before the stream
-    "diffab_sample_loop_guided": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                            _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
-                                            C.POINTER(SampleGuidance), _fp]),
-    # noise scales / sequence temperature: diffab_sample_loop_guided plus `temperature` (nullable) before the stream
-    "diffab_sample_loop_tempered": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                              _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
-                                              C.POINTER(SampleGuidance), C.POINTER(SampleTemperature), _fp]),
-    # particle steering: diffab_sample_loop_tempered plus `steering` (nullable) before the stream
-    "diffab_sample_loop_steered": (C.c_int, [_PD, C.POINTER(DenoiserWeights), _PS, _PI, _fp, _fp, _fp, _fp, _fp, _i32, C.POINTER(_i32), _fp,
-                                             _u64, _i64, _i32, _i32, _fp, _sz, _u32, _fp, C.POINTER(SampleRecord), C.POINTER(SampleSteps),
-                                             C.POINTER(SampleGuidance), C.POINTER(SampleTemperature), C.POINTER(SampleSteering), _fp]),
+    # (seq, x, O, gen_mask, seed, first_patch, B, K, T, flags, allowed (device uint32[B*K], nullable), stream)
+    "diffab_sample_init_ex": (C.c_int, [_fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
+    # (sched, fwd_tab, seq, x, O, gen_mask, seed, first_patch, B, K, t, flags, allowed (nullable), stream)
+    "diffab_sample_init_noised": (C.c_int, [_PS, _PI, _fp, _fp, _fp, _fp, _u64, _i64, _i32, _i32, _i32, _u32, _fp, _fp]),
     # (x, eps_hat, gen_mask, sched, t, steering, rows, K, energy_out, stream)
     "diffab_steer_energy": (C.c_int, [_fp, _fp, _fp, _PS, _i32, C.POINTER(SampleSteering), _i32, _i32, _fp, _fp]),
     # (logw, u_prev, energy, u, G, N, strength, ess_threshold, ancestors_out, ess_out (double, nullable), stream)

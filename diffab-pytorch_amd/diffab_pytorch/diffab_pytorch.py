@@ -179,8 +179,36 @@ def _trajectory_labels(who: str, trajectory, predictions, t_start: int, t_stop: 
     return labels
 
 
+def _record_c_struct(labels: torch.Tensor, T: int, B: int, K: int, V: int, predictions: bool, device):
+    """diffab_sample_record of the recorded steps `labels` (slot j holds step labels[j]) over fresh device tensors: the struct, the
+    tensors under their names in sample()'s "trajectory", and the step -> slot table of the device (the caller keeps all three alive
+    until the call is enqueued)."""
+    n = labels.numel()
+    slot_of_step = [-1] * (T + 1)
+    for j, t in enumerate(labels.tolist()):
+        slot_of_step[t] = j
+    slot_dev = torch.empty(T + 1, dtype=torch.int32, device=device)
+    traj = {"seq_idx": torch.empty(B, n, K, dtype=torch.int64, device=device),
+            "translations": torch.empty(B, n, K, 3, device=device), "orientations": torch.empty(B, n, K, 3, 3, device=device)}
+    if predictions:
+        traj.update(pred_translations=torch.empty(B, n, K, 3, device=device), pred_orientations=torch.empty(B, n, K, 3, 3, device=device),
+                    seq_probs=torch.empty(B, n, K, V, device=device))
+    rec = _hip.SampleRecord(n, (C.c_int32 * (T + 1))(*slot_of_step), _hip.ptr(slot_dev),
+                            *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
+                                                              "pred_orientations", "seq_probs")))
+    return rec, traj, slot_dev
+
+
+def _steps_c_struct(executed: torch.Tensor, beta_jump: torch.Tensor, alpha_jump: torch.Tensor, plan_dev: torch.Tensor) -> "_hip.SampleSteps":
+    """diffab_sample_steps of the executed steps and their jump coefficients ((T + 1,) host tables); plan_dev: 3 (T + 1) int32 words on
+    the device (the caller keeps it alive until the call is enqueued)."""
+    n = executed.numel()
+    return _hip.SampleSteps(n, (C.c_int32 * n)(*executed.tolist()), (C.c_float * beta_jump.numel())(*beta_jump.tolist()),
+                            (C.c_float * alpha_jump.numel())(*alpha_jump.tolist()), _hip.ptr(plan_dev))
+
+
 def _pack_allowed_aa(allowed: torch.Tensor) -> torch.Tensor:
-    """(..., V) bool on the device -> (...) int32 words, bit v = class v allowed (the layout of diffab_sample_loop_aa)."""
+    """(..., V) bool on the device -> (...) int32 words, bit v = class v allowed (the layout of diffab_sample_options.allowed)."""
     bits = torch.ones((), dtype=torch.int64, device=allowed.device) << torch.arange(allowed.shape[-1], device=allowed.device)
     words = (allowed.to(torch.int64) * bits).sum(-1)
     return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32).contiguous()
@@ -1089,7 +1117,7 @@ class DiffAb(_ModuleBase):
         ``num_samples=N``: every per-patch input (seq_idx, xyz, orientations, generation_mask; B rows) is replicated N times on the
         device and the result has B*N rows, row b*N + r being design r of patch b.  The contexts stay B rows - given, or computed by ONE
         encode_context call over the B patches - and the sampler reads them through a row -> context map
-        (`diffab_sample_loop_shared`): no (B*N, K, K, C) copy of the pair context and no per-replica fp16 planes.  Bitwise the result
+        (`diffab_sample_loop_ex`, option `ctx_of_row`): no (B*N, K, K, C) copy of the pair context and no per-replica fp16 planes.  Bitwise the result
         of num_samples=1 on the repeat_interleave(N, dim=0) of every per-patch input with the same seed and first_patch (the replicas
         differ by their noise keys, patch id first_patch + b*N + r).
         ``context_index`` (R,) is the general form: res_context_emb / pair_context_emb hold n_ctx contexts (required), the state
@@ -1113,7 +1141,7 @@ class DiffAb(_ModuleBase):
 
         Sequence constraints: ``allowed_aa`` is a bool tensor (V,), (K, V) or (rows, K, V) - True where class v (io.AA3 order, UNK last)
         may appear - broadcast to the input rows (io.allowed_aa_mask builds one from one-letter codes).  Every sequence draw of a
-        generated residue is restricted to its allowed classes on the device (`diffab_sample_loop_aa` and the `_aa` init entries): the
+        generated residue is restricted to its allowed classes on the device (`diffab_sample_loop_ex`, option `allowed`, and `allowed` of the init entries): the
         reverse step draws from the posterior renormalised over them, the initial state uniformly over them (UNK only when it is the
         only one), optimize_from's start from q(s_t | s_0) renormalised over them.  The Philox lanes are the unconstrained ones, so an
         all-True mask is bitwise the unconstrained run and sharding / num_samples / context_index behave as above; with num_samples the
@@ -1134,7 +1162,7 @@ class DiffAb(_ModuleBase):
         distribution the returned token was drawn from.  Residues that are not generated hold their given state in every slot, and
         their predictions are their x / O and a one-hot of their token; a kept modality of a mode appears in the predictions as its
         given values.  Rows are outermost (row b*N + r under num_samples), so a shard's rows are that slice of the whole call's
-        trajectory.  The update kernel writes the record on the device (`diffab_sample_loop_rec`); the returned state is bitwise the
+        trajectory.  The update kernel writes the record on the device (`diffab_sample_loop_ex`, option `record`); the returned state is bitwise the
         same with and without a trajectory, on every launch form.  Memory: 56 B of state plus 132 B of predictions (V = 21) per
         recorded residue and label - every step of a 100-step run at 256 x 128 is about 590 MiB.  A bool / float / 2-D / empty
         trajectory, a stride < 1, a step outside the range or named twice, and trajectory_predictions without trajectory raise
@@ -1146,7 +1174,7 @@ class DiffAb(_ModuleBase):
         at tau_j exactly as the full loop does and moves the state to tau_{j+1} (t_stop after the last) with the jump's coefficients
         beta'_t = clip(1 - abar_t / abar_s, 1e-5, beta_max): translations and orientations by the DDPM update with beta', the sequence
         from sum_u p(s_0 = u | s_t) q(s_s | s_t, u), the x0 mixture recovered from the head posterior on the device in double
-        (`diffab_sample_loop_steps`).  Noise stays keyed by (seed, first_patch + b, residue, tau_j), so sharding, num_samples and
+        (`diffab_sample_loop_ex`, option `steps`).  Noise stays keyed by (seed, first_patch + b, residue, tau_j), so sharding, num_samples and
         context_index behave as above; it combines with every mode, optimize_from, allowed_aa, graph, skip_unused_rows and the flags.
         Listing every step is bitwise ``steps=None``, and a mixed list is bitwise the full run up to its last stride-1 step.  With a
         trajectory, labels are executed steps: True records every executed step, an int k every k-th of them, and a list must name
@@ -1164,7 +1192,7 @@ class DiffAb(_ModuleBase):
         The tables are ``chain_idx`` (default one chain), ``residue_idx`` (default arange(K)) and ``residue_mask`` (default all true),
         (K,) or (rows, K), used even when the contexts are given: per patch and replicated like generation_mask under num_samples, per
         state row with context_index.  Both weights 0 (and t_max = 0) still run the guidance kernel and are bitwise the unguided
-        sample (`diffab_sample_loop_guided`).  Combines with every mode except "fixed_backbone" (the structure is kept), with
+        sample (`diffab_sample_loop_ex`, option `guidance`).  Combines with every mode except "fixed_backbone" (the structure is kept), with
         optimize_from, allowed_aa, trajectory, steps, graph, skip_unused_rows, num_samples / context_index and the flags.  Anything but
         a SampleGuidance, a negative or non-finite weight, a non-positive distance or max_shift, t_max outside [0, T], tables of a
         non-integer dtype or a shape that does not broadcast to the rows, and mode="fixed_backbone" raise ValueError before any device
@@ -1176,7 +1204,7 @@ class DiffAb(_ModuleBase):
         noise is lambda_x sqrt(beta'_t) z (0: the mean, exactly); the IGSO3 angle is drawn at sigma = lambda_O sqrt(beta'_t) from a
         table row built over that sigma with the same uniforms, normal and axis (0: O = O0_hat, exactly); s_{t-1} is drawn from
         p^(1/tau) renormalised over the allowed classes, p the head posterior or a respaced step's jump distribution (tau = 0: the
-        argmax, lowest index on ties).  All three are applied by the update kernel (`diffab_sample_loop_tempered`), so they combine with
+        argmax, lowest index on ties).  All three are applied by the update kernel (`diffab_sample_loop_ex`, option `temperature`), so they combine with
         every mode that samples the modality, optimize_from, allowed_aa, trajectory, steps, guidance, graph, num_samples /
         context_index and the flags; 1 everywhere is bitwise the untempered sample, and with init=False and every value 0 the result
         does not depend on the seed.  Not changed: the posterior, x0_hat / O0_hat and with them the trajectory record, the initial
@@ -1196,7 +1224,7 @@ class DiffAb(_ModuleBase):
         global row, and after the step's ordinary update the generated residues (seq, x, O) of every row are replaced by those of its
         ancestor; the copies separate again at the next step through their own noise.  No gradient, no extra model evaluation, the mean
         of no step moves; weights never reach the host, so it runs under graph replay and on every launch form
-        (`diffab_sample_loop_steered`).  The result gains ``"steering"``: ``log_weight`` (rows,) and ``energy`` (rows,) - the energy
+        (`diffab_sample_loop_ex`, option `steering`).  The result gains ``"steering"``: ``log_weight`` (rows,) and ``energy`` (rows,) - the energy
         each weight has seen last, its ancestor's after a resampling - ``t`` (n,) the steering steps in descending order, ``ancestors``
         (n, rows) the global row each row was copied from at that step (its own index where nothing moved) and ``lineage`` (rows,), the
         initial row every design descends from.  All rows of a group must share generation_mask, the context and the tables (checked on
@@ -1220,6 +1248,7 @@ class DiffAb(_ModuleBase):
                 raise ValueError(f"sample(): t_start = {t_start} disagrees with optimize_from = {optimize_from} (the loop starts at "
                                  "optimize_from; leave t_start out)")
             t_start = optimize_from
+        t_start, t_stop = self.T if t_start is None else int(t_start), int(t_stop)
         if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
             raise ValueError(f"sample(): num_samples must be an int >= 1, got {num_samples!r}")
         if num_samples > 1 and context_index is not None:
@@ -1260,7 +1289,7 @@ class DiffAb(_ModuleBase):
             temp_vals = _temperature.row_values("sample()", temperature, n_rows * num_samples)
             _temperature.check_mode("sample()", temp_vals, bool(keep & _hip.FLAG_KEEP_STRUCTURE), bool(keep & _hip.FLAG_KEEP_SEQUENCE))
         if steering is not None:  # steer_n: the group size; the groups are checked on the host (one copy of generation_mask to it)
-            if steering.t_max is None and steering.t_min > (self.T if t_start is None else int(t_start)):
+            if steering.t_max is None and steering.t_min > t_start:
                 raise ValueError(f"sample(): steering t_min = {steering.t_min} is above the first step of the call (t_max=None steers from it)")
             steer_n = num_samples if steering.group_size is None else steering.group_size
             per_row = lambda v: v.repeat_interleave(num_samples, dim=0) if num_samples > 1 else v
@@ -1269,9 +1298,8 @@ class DiffAb(_ModuleBase):
                                    {"generation_mask": per_row(gm_host), "the context (context_index)": ctx_map,
                                     "chain_idx": per_row(res_tabs[0]), "residue_idx": per_row(res_tabs[1]),
                                     "residue_mask": per_row(res_tabs[2])})
-        executed = _sample_steps("sample()", steps, self.T if t_start is None else int(t_start), int(t_stop), self.T)
-        labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, self.T if t_start is None else int(t_start), int(t_stop),
-                                    self.T, executed)
+        executed = _sample_steps("sample()", steps, t_start, t_stop, self.T)
+        labels = _trajectory_labels("sample()", trajectory, trajectory_predictions, t_start, t_stop, self.T, executed)
         if res_context_emb is None or pair_context_emb is None:
             _check_encode_fields("sample()", xyz, atom_mask, chain_idx)
             res_context_emb, pair_context_emb = self._contexts_from_batch(seq_idx, xyz, orientations, generation_mask, residue_mask,
@@ -1298,140 +1326,83 @@ class DiffAb(_ModuleBase):
             seq, x, O = seq.clone(), x.clone(), O.clone()
         B, K = seq.shape
         seed = _so3._draw_seed() if seed is None else int(seed)
-        t_start = self.T if t_start is None else int(t_start)
         dims = self.denoiser.hip_dims(B, K)
         w = self.denoiser.hip_weights()
         sd = self._sched_on_device()
         if executed is None:
             tab = self._reverse_so3().struct()
         else:
-            beta_j, alpha_j = jump_coefficients(self.sched, executed, int(t_stop), self.beta_max)
-            rev_tab = self._reverse_so3_steps(executed, int(t_stop), beta_j)  # (held until the call has been enqueued)
+            beta_j, alpha_j = jump_coefficients(self.sched, executed, t_stop, self.beta_max)
+            rev_tab = self._reverse_so3_steps(executed, t_stop, beta_j)  # (held until the call has been enqueued)
             tab = rev_tab.struct()
-        temp = None  # diffab_sample_temperature (None: every field 1 - the untempered entries); its device tensors live in temp_dev
+        temp = None  # diffab_sample_temperature (None: every field 1 - untempered); its device tensors live in temp_dev
         if temp_vals is not None:
             lx, lo, tau = temp_vals
             temp_dev = [None if bool((v == 1).all()) else v.to(seq.device) for v in (lx, lo, tau)] + [None]
             if temp_dev[1] is not None:
                 scales = _temperature.rotation_scales(lo)
                 if scales:  # (every lambda_O = 0: the table is never read)
-                    rev_tab = self._reverse_so3_tempered(scales, executed, int(t_stop), None if executed is None else beta_j)
+                    rev_tab = self._reverse_so3_tempered(scales, executed, t_stop, None if executed is None else beta_j)
                     tab = rev_tab.struct()
                 temp_dev[3] = _temperature.rotation_rows(lo, scales, self.T).to(seq.device)
             if any(v is not None for v in temp_dev):
                 temp = _hip.SampleTemperature(*(_hip.ptr(v) for v in temp_dev))
+        opt = {}  # the fields of diffab_sample_options that are on (none: the plain loop)
         if ctx_map is None:
             ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(dims)))
         else:
             n_ctx = rc.shape[0]
             ws = _hip.workspace(lib.diffab_sample_shared_workspace_bytes(C.byref(dims), n_ctx))
-            ctx_host = (C.c_int32 * B)(*ctx_map.tolist())
+            opt.update(n_ctx=n_ctx, ctx_of_row=(C.c_int32 * B)(*ctx_map.tolist()))
         if graph:
             flags |= _hip.FLAG_GRAPH_SAMPLER
         if not skip_unused_rows:
             flags |= _hip.FLAG_ALL_ROWS
         flags |= keep
+        state = (_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K)
         if init and optimize_from is not None:
             fwd_tab = self.orientation_diffuser.so3.struct()
-            args = (C.byref(sd.struct), C.byref(fwd_tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K,
-                    optimize_from, keep)
-            if allowed is None:
-                _hip.check(lib.diffab_sample_init_noised(*args, _hip.stream_ptr()), "diffab_sample_init_noised")
-            else:
-                _hip.check(lib.diffab_sample_init_noised_aa(*args, _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_init_noised_aa")
-        elif init and allowed is not None:
-            _hip.check(lib.diffab_sample_init_aa(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T, keep,
-                                                 _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_init_aa")
-        elif init and keep:
-            _hip.check(lib.diffab_sample_init_ex(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T, keep,
-                                                 _hip.stream_ptr()), "diffab_sample_init_ex")
+            _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd_tab), *state, optimize_from, keep, _hip.ptr(allowed),
+                                                     _hip.stream_ptr()), "diffab_sample_init_noised")
+        elif init and (keep or allowed is not None):
+            _hip.check(lib.diffab_sample_init_ex(*state, self.T, keep, _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_init_ex")
         elif init:
-            _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, first_patch, B, K, self.T,
-                                              _hip.stream_ptr()), "diffab_sample_init")
-        rec = None
-        if labels is not None:
-            V = self.denoiser.dims["V"]
-            n = labels.numel()
-            slot_of_step = [-1] * (self.T + 1)
-            for j, t in enumerate(labels.tolist()):
-                slot_of_step[t] = j
-            slot_dev = torch.empty(self.T + 1, dtype=torch.int32, device=seq.device)
-            traj = {"seq_idx": torch.empty(B, n, K, dtype=torch.int64, device=seq.device),
-                    "translations": torch.empty(B, n, K, 3, device=seq.device), "orientations": torch.empty(B, n, K, 3, 3, device=seq.device)}
-            if trajectory_predictions:
-                traj.update(pred_translations=torch.empty(B, n, K, 3, device=seq.device),
-                            pred_orientations=torch.empty(B, n, K, 3, 3, device=seq.device),
-                            seq_probs=torch.empty(B, n, K, V, device=seq.device))
-            rec = _hip.SampleRecord(n, (C.c_int32 * (self.T + 1))(*slot_of_step), _hip.ptr(slot_dev),
-                                    *(_hip.ptr(traj.get(k)) for k in ("seq_idx", "translations", "orientations", "pred_translations",
-                                                                      "pred_orientations", "seq_probs")))
-        if executed is not None or res_tabs is not None or temp is not None:
-            st = None
-            if executed is not None:
-                plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=seq.device)
-                st = _hip.SampleSteps(executed.numel(), (C.c_int32 * executed.numel())(*executed.tolist()),
-                                      (C.c_float * (self.T + 1))(*beta_j.tolist()), (C.c_float * (self.T + 1))(*alpha_j.tolist()),
-                                      _hip.ptr(plan_dev))
-            args = (C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc),
-                    _hip.ptr(pc), B if ctx_map is None else n_ctx, None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch,
-                    t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), None if rec is None else C.byref(rec),
-                    None if st is None else C.byref(st))
-            gs = None
-            if guidance is not None:
-                shift = torch.empty(B, K, 3, device=seq.device)
-                t_max = self.T if guidance.t_max is None else guidance.t_max
-                gs = _guidance.c_struct(guidance, t_max, *res_tabs, shift)
-            if steering is not None:
-                dev = seq.device
-                logw, u_prev, energy = (torch.zeros(B, device=dev) for _ in range(3))
-                anc = torch.empty(self.T + 1, B, dtype=torch.int32, device=dev)
-                scratch = torch.empty(_steering.scratch_bytes(B, K), dtype=torch.uint8, device=dev)
-                st_max = t_start if steering.t_max is None else steering.t_max
-                ss = _steering.c_struct(steering, st_max, steer_n, *res_tabs, logw, u_prev, energy, anc, scratch)
-                _hip.check(lib.diffab_sample_loop_steered(*args, None if gs is None else C.byref(gs), None if temp is None else C.byref(temp),
-                                                          C.byref(ss), _hip.stream_ptr()), "diffab_sample_loop_steered")
-            elif temp is not None:
-                _hip.check(lib.diffab_sample_loop_tempered(*args, None if gs is None else C.byref(gs), C.byref(temp), _hip.stream_ptr()),
-                           "diffab_sample_loop_tempered")
-            elif guidance is None:
-                _hip.check(lib.diffab_sample_loop_steps(*args, _hip.stream_ptr()), "diffab_sample_loop_steps")
-            else:
-                _hip.check(lib.diffab_sample_loop_guided(*args, C.byref(gs), _hip.stream_ptr()), "diffab_sample_loop_guided")
-            out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
-            if labels is not None:
-                out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}
-            if steering is not None:
-                ran = executed.tolist() if executed is not None else list(range(t_start, int(t_stop), -1))
-                ts = torch.tensor(_steering.steering_steps(ran, int(t_stop), steering.t_min, st_max, steering.every), dtype=torch.int64)
-                first = torch.arange(B, device=dev) // steer_n * steer_n  # group-local -> global row indices
-                glob = anc[ts.to(dev)].to(torch.int64) + first
-                out["steering"] = {"log_weight": logw.to(out_dev), "energy": u_prev.to(out_dev), "t": ts.to(out_dev),
-                                   "ancestors": glob.to(out_dev), "lineage": _steering.lineage(glob).to(out_dev)}
-            return out
-        if labels is not None:
-            _hip.check(lib.diffab_sample_loop_rec(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
-                                                  _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
-                                                  None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,
-                                                  _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), C.byref(rec), _hip.stream_ptr()),
-                       "diffab_sample_loop_rec")
-            out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
-            out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}
-            return out
+            _hip.check(lib.diffab_sample_init(*state, self.T, _hip.stream_ptr()), "diffab_sample_init")
+        dev = seq.device
         if allowed is not None:
-            _hip.check(lib.diffab_sample_loop_aa(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
-                                                 _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), B if ctx_map is None else n_ctx,
-                                                 None if ctx_map is None else ctx_host, _hip.ptr(gm), seed, first_patch, t_start, t_stop,
-                                                 _hip.ptr(ws), ws.numel(), flags, _hip.ptr(allowed), _hip.stream_ptr()), "diffab_sample_loop_aa")
-        elif ctx_map is None:
-            _hip.check(lib.diffab_sample_loop(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
-                                              _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), _hip.ptr(gm), seed, first_patch, t_start, t_stop,
-                                              _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()), "diffab_sample_loop")
-        else:
-            _hip.check(lib.diffab_sample_loop_shared(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq),
-                                                     _hip.ptr(x), _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), n_ctx, ctx_host, _hip.ptr(gm), seed,
-                                                     first_patch, t_start, t_stop, _hip.ptr(ws), ws.numel(), flags, _hip.stream_ptr()),
-                       "diffab_sample_loop_shared")
-        return {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
+            opt["allowed"] = _hip.ptr(allowed)
+        if labels is not None:
+            opt["record"], traj, slot_dev = _record_c_struct(labels, self.T, B, K, self.denoiser.dims["V"], trajectory_predictions, dev)
+        if executed is not None:
+            plan_dev = torch.empty(3 * (self.T + 1), dtype=torch.int32, device=dev)
+            opt["steps"] = _steps_c_struct(executed, beta_j, alpha_j, plan_dev)
+        if guidance is not None:
+            shift = torch.empty(B, K, 3, device=dev)
+            opt["guidance"] = _guidance.c_struct(guidance, self.T if guidance.t_max is None else guidance.t_max, *res_tabs, shift)
+        if temp is not None:
+            opt["temperature"] = temp
+        if steering is not None:
+            logw, u_prev, energy = (torch.zeros(B, device=dev) for _ in range(3))
+            anc = torch.empty(self.T + 1, B, dtype=torch.int32, device=dev)
+            scratch = torch.empty(_steering.scratch_bytes(B, K), dtype=torch.uint8, device=dev)
+            st_max = t_start if steering.t_max is None else steering.t_max
+            opt["steering"] = _steering.c_struct(steering, st_max, steer_n, *res_tabs, logw, u_prev, energy, anc, scratch)
+        options = _hip.SampleOptions(**opt)
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(dims), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(rc), _hip.ptr(pc), _hip.ptr(gm), seed, first_patch, t_start, t_stop,
+                                             _hip.ptr(ws), ws.numel(), flags, C.byref(options) if opt else None, _hip.stream_ptr()),
+                   "diffab_sample_loop_ex")
+        out = {"seq_idx": seq.to(out_dev), "translations": x.to(out_dev), "orientations": O.to(out_dev)}
+        if labels is not None:
+            out["trajectory"] = {"t": labels.to(out_dev), **{k: v.to(out_dev) for k, v in traj.items()}}
+        if steering is not None:
+            ran = executed.tolist() if executed is not None else list(range(t_start, t_stop, -1))
+            ts = torch.tensor(_steering.steering_steps(ran, t_stop, steering.t_min, st_max, steering.every), dtype=torch.int64)
+            first = torch.arange(B, device=dev) // steer_n * steer_n  # group-local -> global row indices
+            glob = anc[ts.to(dev)].to(torch.int64) + first
+            out["steering"] = {"log_weight": logw.to(out_dev), "energy": u_prev.to(out_dev), "t": ts.to(out_dev),
+                               "ancestors": glob.to(out_dev), "lineage": _steering.lineage(glob).to(out_dev)}
+        return out
 
     # ------------------------------------------------------------------ from a whole complex (build-defined; the reference cuts patches in preprocess_pdb.py:44-58)
     @torch.no_grad()

@@ -5,7 +5,7 @@
     U = clash * sum_nonbonded max(0, clash_distance - d)^2 + bond * sum_bonded (d - bond_length)^2
 
 taken at the model's clean-structure prediction x0_hat, times the step's variance beta'_t and capped at max_shift, is subtracted from the
-mean of the translations (`diffab_sample_loop_guided`).  ``structure_energy`` evaluates the same potential at given coordinates on the
+mean of the translations (`diffab_sample_loop_ex`, option `guidance`).  ``structure_energy`` evaluates the same potential at given coordinates on the
 device (`diffab_guidance_energy`): clash and bond statistics of finished designs, and the gradient.
 """
 from __future__ import annotations

@@ -7,7 +7,7 @@ particles of a sequential Monte Carlo run over the reverse process.  At every st
 
 taken at the model's clean-structure prediction x0_hat (the potential of guidance.py), log w += -strength (U - U_previous); when the
 effective sample size of a group falls below ess_threshold N the group is resampled systematically and the generated residues of every
-row are replaced by those of its ancestor, all on the device (`diffab_sample_loop_steered`).  ``resample_oracle`` restates the weight
+row are replaced by those of its ancestor, all on the device (`diffab_sample_loop_ex`, option `steering`).  ``resample_oracle`` restates the weight
 and resampling rule in numpy float64 for the tests; it is not a fallback.
 """
 from __future__ import annotations

@@ -2,7 +2,7 @@
 
 ``SampleTemperature`` configures ``DiffAb.sample(temperature=...)``.  Per output row, the translation noise of every step is scaled by
 ``translation`` (lambda_x), the IGSO3 angle is drawn at sigma = ``rotation`` * sqrt(beta'_t) (lambda_O) and s_{t-1} is drawn from
-p^(1/``sequence``) renormalised (tau; 0 is the argmax).  The update kernel applies all three (`diffab_sample_loop_tempered`); 1 is the
+p^(1/``sequence``) renormalised (tau; 0 is the argmax).  The update kernel applies all three (`diffab_sample_loop_ex`, option `temperature`); 1 is the
 ordinary draw, bitwise.  The posterior, x0_hat / O0_hat, the trajectory record, the initial state, optimize_from's forward noise and
 ``DiffAb.score`` are untouched.
 """

@@ -96,7 +96,7 @@ extern "C" {
                                          it measures 4 % slower than its per-layer launches at B = 512. */
 #define DIFFAB_FLAG_MULTI_LAUNCH 1024u /* diffab_sample_loop: keep one launch per kernel of an IPA layer even where the patch-resident module
                                           launch would be chosen (B >= number of CUs, K = 128); the two forms are bitwise equal */
-#define DIFFAB_FLAG_ALL_ROWS 8192u /* diffab_sample_loop / _shared: a step's outputs are read for GENERATED residues only (the reverse
+#define DIFFAB_FLAG_ALL_ROWS 8192u /* diffab_sample_loop / _ex: a step's outputs are read for GENERATED residues only (the reverse
                                      update, its heads epilogue, guidance and the trajectory record leave the others alone), so on the
                                      MFMA path with K % 16 == 0 and NL >= 2 the loop runs the LAST layer's attention only for the 16-row
                                      tiles that contain one (every other layer feeds all rows' keys and values to the next) - on the
@@ -106,7 +106,7 @@ extern "C" {
                                      The single forwards, the taped entries and diffab_score_designs always run every row. */
 #define DIFFAB_FLAG_SKIP_UNUSED_ROWS 256u /* accepted, no effect: what it asked for is what diffab_sample_loop does unless
                                              DIFFAB_FLAG_ALL_ROWS is set */
-/* Design modes of the reverse loop (diffab_sample_loop / _shared, diffab_sample_init_ex, diffab_sample_init_noised).  With one of these
+/* Design modes of the reverse loop (diffab_sample_loop / _ex, diffab_sample_init_ex, diffab_sample_init_noised).  With one of these
    bits set the sampler never writes that modality of the state; the other is updated exactly as without the bit, from the same Philox
    draws.  The branch is uniform per launch, on every launch form of the loop.  Both bits together: DIFFAB_ERR_ARG, nothing enqueued. */
 #define DIFFAB_FLAG_KEEP_STRUCTURE 2048u /* fixed-backbone sequence design: x and O of the generated residues stay as given (the
@@ -297,8 +297,8 @@ int diffab_philox_fill(uint64_t seed, int64_t first_patch, int32_t B, int32_t K,
 /* ---- IPA / denoiser --------------------------------------------------------- */
 size_t diffab_denoise_workspace_bytes(const diffab_dims* d);
 size_t diffab_sample_workspace_bytes(const diffab_dims* d); /* for diffab_sample_loop */
-/* for diffab_sample_loop_shared with a context map: the fp16 pair planes and their row scales are sized by n_ctx, not d->B, plus the
- * device copy of the map and a (B,K,D) residue-context buffer.  0 (and diffab_last_error) for bad dims or n_ctx < 1. */
+/* for diffab_sample_loop_ex with a context map (diffab_sample_options.ctx_of_row): the fp16 pair planes and their row scales are
+ * sized by n_ctx, not d->B, plus the device copy of the map and a (B,K,D) residue-context buffer.  0 (and diffab_last_error) for bad dims or n_ctx < 1. */
 size_t diffab_sample_shared_workspace_bytes(const diffab_dims* d, int32_t n_ctx);
 /* diffab_pytorch.py:389-465  one InvariantPointAttentionLayer.forward */
 int diffab_ipa_layer_fwd(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x /* (B,K,D) */,
@@ -596,27 +596,14 @@ int diffab_sample_loop(const diffab_dims* d, const diffab_denoiser_weights* w, c
                        const diffab_igso3* rev_tab, int64_t* seq, float* x, float* O, const float* res_ctx,
                        const float* pair_ctx, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
                        int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, void* stream);
-/* diffab_sample_loop with contexts shared between state rows (many designs of one patch from one context): res_ctx (n_ctx,K,D) and
- * pair_ctx (n_ctx,K,K,C) hold n_ctx contexts, and state row b (seq/x/O/gen_mask are (d->B,K,...)) is denoised against context
- * ctx_of_row[b].  ctx_of_row is a HOST array of d->B entries, each in [0, n_ctx) (else DIFFAB_ERR_ARG, nothing enqueued); it is copied
- * to the workspace once per call (the call returns with the host array no longer needed).  The pair context is read through the map by
- * every attention form (planes, DIFFAB_FLAG_PAIR_F32, DIFFAB_FLAG_FORCE_GENERIC, the patch-resident module, graph replay, skipped row
- * tiles) and never expanded to B rows; its fp16 planes are built once per context.  Noise stays keyed by (seed, first_patch + b,
- * residue, t): the result is bitwise that of diffab_sample_loop on the contexts replicated row by row.  workspace:
- * diffab_sample_shared_workspace_bytes(d, n_ctx).  ctx_of_row NULL: the identity (n_ctx must be d->B; diffab_sample_workspace_bytes(d)
- * suffices) - diffab_sample_loop is exactly that call. */
-int diffab_sample_loop_shared(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s,
-                              const diffab_igso3* rev_tab, int64_t* seq, float* x, float* O, const float* res_ctx,
-                              const float* pair_ctx, int32_t n_ctx, const int32_t* ctx_of_row, const uint8_t* gen_mask,
-                              uint64_t seed, int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace,
-                              size_t workspace_bytes, uint32_t flags, void* stream);
 /* Initial state at t = T on generated residues: x ~ N(0,I), O ~ uniform SO(3), s ~ U{0..19} (Philox, step = T+1). */
 int diffab_sample_init(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch,
                        int32_t B, int32_t K, int32_t T, void* stream);
 /* diffab_sample_init with the design-mode bits of `flags`: DIFFAB_FLAG_KEEP_STRUCTURE leaves x and O, DIFFAB_FLAG_KEEP_SEQUENCE leaves
- * seq as given (other bits are ignored).  flags without either bit: bitwise diffab_sample_init. */
+ * seq as given (other bits are ignored).  flags without either bit: bitwise diffab_sample_init.  allowed (nullable): the sequence
+ * constraints of "Sampler options" below; NULL with flags = 0 is exactly diffab_sample_init (which is this call with both). */
 int diffab_sample_init_ex(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch,
-                          int32_t B, int32_t K, int32_t T, uint32_t flags, void* stream);
+                          int32_t B, int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
 /* Starting state of antibody optimisation: the given (native) state of the generated residues is forward-noised to step t, in place
  * (reference forward process, diffusion.py:105-135, 199-236, 262-294), with Philox noise keyed by (seed, first_patch + b, residue, t) on
  * its own streams (philox.h STREAM_OPT_*), so sharding and replicated rows behave as in the reverse loop:
@@ -626,12 +613,29 @@ int diffab_sample_init_ex(int64_t* seq, float* x, float* O, const uint8_t* gen_m
  *   s_t ~ q(s_t | s_0) = abar_t onehot(s_0) + (1 - abar_t) / 21, by inverse CDF.
  * Build-defined: every residue's angle is an independent inverse-CDF draw (the reference's forward noise draws a patch's histogram
  * bins without replacement, so3.py:78), as in the reverse loop.  Context residues are never written; DIFFAB_FLAG_KEEP_STRUCTURE /
- * _SEQUENCE leave that modality un-noised.  DIFFAB_ERR_ARG for t outside [1, T], a fwd_tab with fewer than T+1 rows, or both bits. */
+ * _SEQUENCE leave that modality un-noised.  allowed (nullable): the sequence constraints of "Sampler options" below.  DIFFAB_ERR_ARG
+ * for t outside [1, T], a fwd_tab with fewer than T+1 rows, or both bits. */
 int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
                               const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t,
-                              uint32_t flags, void* stream);
+                              uint32_t flags, const uint32_t* allowed, void* stream);
 
-/* ---- sequence constraints (build-defined): per-residue allowed amino-acid classes -------------------------------------------------
+/* ==== Sampler options (build-defined) ===================================================================================================
+ * Everything the reverse loop can do beyond diffab_sample_loop travels in ONE struct, diffab_sample_options (defined after the option
+ * structs below), given to diffab_sample_loop_ex.  Every field is nullable / zero = off, and the options combine freely; each block below
+ * describes one option and names the field of diffab_sample_options that carries it.
+ *
+ * ---- shared contexts: diffab_sample_options.n_ctx and .ctx_of_row -------------------------------------------------------------------
+ * Contexts shared between state rows (many designs of one patch from one context): res_ctx (n_ctx,K,D) and
+ * pair_ctx (n_ctx,K,K,C) hold n_ctx contexts, and state row b (seq/x/O/gen_mask are (d->B,K,...)) is denoised against context
+ * ctx_of_row[b].  ctx_of_row is a HOST array of d->B entries, each in [0, n_ctx) (else DIFFAB_ERR_ARG, nothing enqueued); it is copied
+ * to the workspace once per call (the call returns with the host array no longer needed).  The pair context is read through the map by
+ * every attention form (planes, DIFFAB_FLAG_PAIR_F32, DIFFAB_FLAG_FORCE_GENERIC, the patch-resident module, graph replay, skipped row
+ * tiles) and never expanded to B rows; its fp16 planes are built once per context.  Noise stays keyed by (seed, first_patch + b,
+ * residue, t): the result is bitwise that of diffab_sample_loop on the contexts replicated row by row.  workspace:
+ * diffab_sample_shared_workspace_bytes(d, n_ctx).  ctx_of_row NULL: the identity (n_ctx must be 0 or d->B; diffab_sample_workspace_bytes(d)
+ * suffices) - diffab_sample_loop is exactly that call. */
+/* ---- sequence constraints: diffab_sample_options.allowed (and `allowed` of diffab_sample_init_ex / _noised) --------------------------
+ * Per-residue allowed amino-acid classes.
  * `allowed` is a caller-owned DEVICE buffer of B*K uint32 words, one per (state row, residue) in the layout of gen_mask; bit v of a
  * word allows class v (io.AA3 order: the 20 amino acids, then UNK = 20).  Bits at and above the vocabulary size are ignored.  Only
  * GENERATED residues read their word, and only where the sequence is diffused; context residues are never written.  Every draw uses
@@ -645,16 +649,11 @@ int diffab_sample_init_noised(const diffab_sched* s, const diffab_igso3* fwd_tab
  *   optimisation start (STREAM_OPT_SEQ): q(s_t | s_0) restricted to A and renormalised, drawn by the reverse-step rule (a native
  *     token outside A is not reachable).
  * Structure draws (x, O) and the denoiser are untouched.  A generated residue with an empty A is the caller's error (DiffAb.sample
- * rejects it): its token is then left as it is.  allowed == NULL: exactly the entry without the suffix (which is this call with NULL).
+ * rejects it): its token is then left as it is.  allowed == NULL: unconstrained.
  * A non-NULL allowed with DIFFAB_FLAG_KEEP_SEQUENCE, or (loop) with d->V > 32: DIFFAB_ERR_ARG, nothing enqueued. */
-int diffab_sample_loop_aa(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                          int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                          const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                          int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                          void* stream);
-/* ---- trajectory recording (build-defined): the reverse process, step by step ------------------------------------------------------
- * diffab_sample_loop_aa plus `rec` (nullable) before the stream; rec == NULL is exactly diffab_sample_loop_aa (which is this call with
- * NULL).  Labels are steps: slot j = slot_of_step[t] (a HOST table of T + 1 int32, -1 = not recorded) holds, for step t,
+/* ---- trajectory recording: diffab_sample_options.record ----------------------------------------------------------------------------
+ * The reverse process, step by step; record == NULL: no trajectory.
+ * Labels are steps: slot j = slot_of_step[t] (a HOST table of T + 1 int32, -1 = not recorded) holds, for step t,
  *   the state that step t denoises: s_t, x_t, O_t (label t_start: the state the call was given - diffab_sample_init*'s, or the
  *     forward-noised native of optimize_from).  Bitwise the output of this call with t_stop = t, same seed, first_patch, flags, map and
  *     allowed.  The final state is the call's own output and has no slot;
@@ -684,12 +683,8 @@ typedef struct {
   float* pred_O;               /* (B, n_slots, K, 3, 3) */
   float* seq_probs;            /* (B, n_slots, K, V) */
 } diffab_sample_record;
-int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                           int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                           const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                           int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                           const diffab_sample_record* rec, void* stream);
-/* ---- fewer-step reverse sampling (build-defined): the reverse process on a subsequence of the steps ----------------------------------
+/* ---- fewer-step reverse sampling: diffab_sample_options.steps ----------------------------------------------------------------------
+ * The reverse process on a subsequence of the steps; steps == NULL: every step.
  * A run names the steps it executes, tau_0 = t_start > tau_1 > ... > tau_{n-1} > t_stop.  Step tau_j denoises the state at tau_j (the
  * denoiser's time input is beta[tau_j], as always) and moves it to s = tau_{j+1}; the last step moves it to s = t_stop.  Philox noise
  * stays keyed by (seed, first_patch + b, residue, t = tau_j) on the same streams.  With abar = alpha_bar and V the vocabulary size:
@@ -705,9 +700,8 @@ int diffab_sample_loop_rec(const diffab_dims* d, const diffab_denoiser_weights* 
  *     Z'_u = abar_s A'_u + c', W = sum_u pi_u / Z'_u and r_v = A'_v (c' W + abar_s pi_v / Z'_v) = sum_u pi_u q(s_s | s_t, u) (r = pi at
  *     s = 0).  s_s is drawn from r (rounded to fp32) with the STREAM_SEQ uniform of step t by the reverse-step rule (restricted to the
  *     residue's `allowed` classes when given).
- * diffab_sample_loop_steps is diffab_sample_loop_rec plus `steps` (nullable) before the stream; steps == NULL is exactly
- * diffab_sample_loop_rec (which is unchanged).  Listing every step t_start .. t_stop + 1 with the schedule's own beta / alpha is bitwise
- * that call.  The eager loop runs over the list; graph replay advances the device timestep through the plan's next[] table, n - 1
+ * Listing every step t_start .. t_stop + 1 with the schedule's own beta / alpha is bitwise the call with steps == NULL.
+ * The eager loop runs over the list; graph replay advances the device timestep through the plan's next[] table, n - 1
  * replays after the first step.  plan_dev: a caller-owned DEVICE buffer of 3 (T + 1) 32-bit words - next[T + 1] int32 (next[tau_j] =
  * tau_{j+1}, t_stop after the last; t - 1 elsewhere), beta'[T + 1] and alpha'[T + 1] fp32 - the call fills it from the host fields with
  * one hipMemcpyAsync (not workspace: the workspace size is unchanged).  Needs s->alpha_bar.  Checked before anything is
@@ -720,11 +714,6 @@ typedef struct {
   const float* alpha_jump;  /* HOST (T + 1): alpha'_t = 1 - beta'_t */
   void* plan_dev;           /* DEVICE 3 (T + 1) 32-bit words, filled by the call */
 } diffab_sample_steps;
-int diffab_sample_loop_steps(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                             int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                             const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                             int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                             const diffab_sample_record* rec, const diffab_sample_steps* steps, void* stream);
 /* Teacher-forced jump t -> s (the analogue of diffab_reverse_update): explicit z (B,K,3), rotvec (B,K,3), u_seq (B,K) and jump
  * coefficients beta_jump / alpha_jump; the rule above, in place on (seq, x, O) where gen_mask is set.  r_out (B,K,V, nullable): the
  * distribution s_s is drawn from, for the generated residues (p itself when s = t - 1).  s = t - 1 with the schedule's beta[t] / alpha[t]
@@ -734,7 +723,8 @@ int diffab_reverse_update_jump(const diffab_sched* s, int32_t t, int32_t s_next,
                                float* O, const float* eps_hat, const float* O0_hat, const float* posterior, const uint8_t* gen_mask,
                                const float* z, const float* rotvec, const float* u_seq, float* r_out, int32_t B, int32_t K, int32_t V,
                                void* stream);
-/* ---- structure guidance (build-defined): clash and chain-bond potentials on the translations --------------------
+/* ---- structure guidance: diffab_sample_options.guidance --------------------------------------------------------
+ * Clash and chain-bond potentials on the translations; guidance == NULL: unguided.
  * Per state row, over the unordered pairs {i, j}, i != j, with residue_mask set on both and at least one of them generated:
  *   p_i = x0_hat_i = (x_t,i - one_minus_alpha_bar_sqrt[t] eps_hat_i) / alpha_bar_sqrt[t] for a generated residue - the expression, and
  *     so bitwise the value, of the record's pred_x - and the given x_i for one that is not generated;
@@ -764,27 +754,21 @@ typedef struct {
   const uint8_t* residue_mask;/* DEVICE (B, K), nullable = all */
   float* shift_dev;           /* DEVICE (B, K, 3), written by the call */
 } diffab_sample_guidance;
-/* diffab_sample_loop_steps plus `guidance` (nullable) before the stream; guidance == NULL is exactly diffab_sample_loop_steps (which is
- * unchanged).  Needs s->alpha_bar_sqrt.  Checked before anything is enqueued, DIFFAB_ERR_ARG: a negative or non-finite weight;
+/* Needs s->alpha_bar_sqrt.  Checked before anything is enqueued, DIFFAB_ERR_ARG: a negative or non-finite weight;
  * clash_distance or bond_length <= 0 or not finite; max_shift <= 0 or NaN; t_max outside [0, T]; null chain, residue_idx or shift_dev;
  * DIFFAB_FLAG_KEEP_STRUCTURE (the structure is not sampled). */
-int diffab_sample_loop_guided(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                              int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                              const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                              int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                              const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
-                              void* stream);
 /* The potential of the rule above at given coordinates (p = x for every residue), for B rows of K residues: per row, UNWEIGHTED,
  * clash = sum_nonbonded max(0, d0 - d)^2, bond = sum_bonded (d - L)^2, n_clash = the number of nonbonded pairs with d < d0, and
  * max_bond_deviation = the largest |d - L| over bonded pairs (0 without one); grad (nullable, (B, K, 3)) = the WEIGHTED gradient g
  * (w_clash, w_bond applied; 0 where not generated; neither scaled by beta nor capped).  Pairs as above (mask on both, at least one
  * generated).  Each row is one work-group with a fixed reduction order and no atomics: the result of a row does not depend on B.  Reads
  * w_clash, clash_distance, w_bond, bond_length, chain, residue_idx and residue_mask of `g` (max_shift, t_max, shift_dev are ignored).
- * DIFFAB_ERR_ARG: the weight / distance checks of diffab_sample_loop_guided, B < 0, K < 1, a null x, gen_mask, g, chain, residue_idx,
+ * DIFFAB_ERR_ARG: the weight / distance checks of diffab_sample_options.guidance, B < 0, K < 1, a null x, gen_mask, g, chain, residue_idx,
  * clash, bond, n_clash or max_bond_deviation. */
 int diffab_guidance_energy(const float* x, const uint8_t* gen_mask, const diffab_sample_guidance* g, int32_t B, int32_t K, float* clash,
                            float* bond, int32_t* n_clash, float* max_bond_deviation, float* grad, void* stream);
-/* ---- noise scales and sequence temperature (build-defined): how greedy the reverse sampler is -----------------
+/* ---- noise scales and sequence temperature: diffab_sample_options.temperature --------------------------------
+ * How greedy the reverse sampler is; temperature == NULL: untempered.
  * Three values per state row b: lambda_x = trans_scale[b], lambda_O = rot_scale[b], tau = seq_temp[b]; a NULL pointer is 1 for every row.
  *   translations: x_s = mu - Delta + [s > 0] lambda_x sqrt(beta'_t) z (mu the ordinary mean, Delta the guidance shift, z the usual Philox
  *     normal); lambda_x = 0 adds no noise term at all (x_s = mu - Delta exactly);
@@ -806,16 +790,10 @@ typedef struct {
   const float* seq_temp;    /* DEVICE (B,) fp32 tau, nullable */
   const int32_t* rot_row;   /* DEVICE (B,) int32: the row of rev_tab that holds t = 0 of the state row's sigma list */
 } diffab_sample_temperature;
-/* diffab_sample_loop_guided plus `temperature` (nullable) before the stream; temperature == NULL is exactly diffab_sample_loop_guided
- * (which is unchanged).  Checked before anything is enqueued, DIFFAB_ERR_ARG: rot_scale without rot_row; trans_scale or rot_scale with
+/* Checked before anything is enqueued, DIFFAB_ERR_ARG: rot_scale without rot_row; trans_scale or rot_scale with
  * DIFFAB_FLAG_KEEP_STRUCTURE; seq_temp with DIFFAB_FLAG_KEEP_SEQUENCE. */
-int diffab_sample_loop_tempered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                                int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                                const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                                int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                                const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
-                                const diffab_sample_temperature* temperature, void* stream);
-/* ---- particle steering (build-defined): the rows of a group resampled by energy while they form ----------------
+/* ---- particle steering: diffab_sample_options.steering ---------------------------------------------------------
+ * The rows of a group resampled by energy while they form; steering == NULL: unsteered.
  * Sequential Monte Carlo over the reverse process (Feynman-Kac steering / the twisted diffusion sampler).  The state rows are grouped
  * as consecutive runs of group_size = N rows (rows b N .. b N + N - 1 under num_samples = N); all rows of a group share gen_mask, the
  * context and the residue tables (the caller's contract).  Per row two fp32 values live in caller-owned device memory across the steps
@@ -865,17 +843,34 @@ typedef struct {
   int32_t* ancestors;         /* DEVICE (T + 1, rows), nullable */
   void* scratch;              /* DEVICE DIFFAB_STEER_SCRATCH_BYTES(rows, K) */
 } diffab_sample_steering;
-/* diffab_sample_loop_tempered plus `steering` (nullable) before the stream; steering == NULL is exactly diffab_sample_loop_tempered
- * (which is unchanged).  Needs s->alpha_bar_sqrt.  Checked before anything is enqueued, DIFFAB_ERR_ARG: rows (d->B) not a multiple of
+/* Needs s->alpha_bar_sqrt.  Checked before anything is enqueued, DIFFAB_ERR_ARG: rows (d->B) not a multiple of
  * group_size; group_size < 1 or > DIFFAB_STEER_MAX_GROUP; a negative or non-finite weight or strength; a distance <= 0; ess_threshold
  * outside [0, 2]; t_min > t_max or either outside [0, T]; every < 1; null logw, u_prev, energy, scratch, chain or residue_idx; scratch
  * not 8-byte aligned; DIFFAB_FLAG_KEEP_STRUCTURE (the structure is not sampled). */
-int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
-                               int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, int32_t n_ctx,
-                               const int32_t* ctx_of_row, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t t_start,
-                               int32_t t_stop, void* workspace, size_t workspace_bytes, uint32_t flags, const uint32_t* allowed,
-                               const diffab_sample_record* rec, const diffab_sample_steps* steps, const diffab_sample_guidance* guidance,
-                               const diffab_sample_temperature* temperature, const diffab_sample_steering* steering, void* stream);
+/* The options of one diffab_sample_loop_ex call.  struct_bytes lets the library refuse a caller built against another layout instead of
+ * reading pointers from the wrong offsets. */
+typedef struct {
+  uint32_t struct_bytes;   /* sizeof(diffab_sample_options); anything else: DIFFAB_ERR_ARG, before any other field is read */
+  int32_t n_ctx;           /* contexts in res_ctx / pair_ctx; 0 means B; read through ctx_of_row */
+  const int32_t* ctx_of_row;                       /* host int32[B], NULL: one context per row */
+  const uint32_t* allowed;                         /* device uint32[B*K], NULL: unconstrained */
+  const diffab_sample_record* record;              /* NULL: no trajectory */
+  const diffab_sample_steps* steps;                /* NULL: every step */
+  const diffab_sample_guidance* guidance;          /* NULL: unguided */
+  const diffab_sample_temperature* temperature;    /* NULL: untempered */
+  const diffab_sample_steering* steering;          /* NULL: unsteered */
+} diffab_sample_options;
+#ifdef __cplusplus
+static_assert(sizeof(diffab_sample_options) == 64, "diffab_sample_options: 2 x 32 bits and 7 pointers");
+#else
+_Static_assert(sizeof(diffab_sample_options) == 64, "diffab_sample_options: 2 x 32 bits and 7 pointers");
+#endif
+/* diffab_sample_loop with options: its 18 arguments, and `opt` before the stream.  opt == NULL and an opt that is zero except for
+ * struct_bytes are exactly diffab_sample_loop (which is this call with NULL).  Every option is checked before anything is enqueued. */
+int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_sched* s, const diffab_igso3* rev_tab,
+                          int64_t* seq, float* x, float* O, const float* res_ctx, const float* pair_ctx, const uint8_t* gen_mask,
+                          uint64_t seed, int64_t first_patch, int32_t t_start, int32_t t_stop, void* workspace, size_t workspace_bytes,
+                          uint32_t flags, const diffab_sample_options* opt, void* stream);
 /* Teacher-forced pieces of the rule above, one launch each (the analogues of diffab_reverse_update_jump):
  * diffab_steer_energy: U (rows) fp32 at step t in [1, T] from x (rows, K, 3) and eps_hat; reads the potential's terms and tables of
  *   `steering` only.
@@ -886,18 +881,13 @@ int diffab_sample_loop_steered(const diffab_dims* d, const diffab_denoiser_weigh
  *   index outside [0, rows) leaves its row alone).  gen_mask of the DESTINATION row decides which residues are replaced; the residue of
  *   the source row is read whatever its own mask says.  scratch: rows K 56 B, 8-byte aligned.
  * DIFFAB_ERR_ARG: a null pointer (ess_out excepted), negative extents, N outside [1, DIFFAB_STEER_MAX_GROUP], the checks of
- * diffab_sample_loop_steered on the values given. */
+ * diffab_sample_options.steering on the values given. */
 int diffab_steer_energy(const float* x, const float* eps_hat, const uint8_t* gen_mask, const diffab_sched* s, int32_t t,
                         const diffab_sample_steering* steering, int32_t rows, int32_t K, float* energy_out, void* stream);
 int diffab_steer_resample(float* logw, float* u_prev, const float* energy, const float* u, int32_t G, int32_t N, float strength,
                           float ess_threshold, int32_t* ancestors_out, double* ess_out, void* stream);
 int diffab_steer_gather(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, const int32_t* ancestors, int32_t rows, int32_t K,
                         void* scratch, void* stream);
-int diffab_sample_init_aa(int64_t* seq, float* x, float* O, const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B,
-                          int32_t K, int32_t T, uint32_t flags, const uint32_t* allowed, void* stream);
-int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_tab, int64_t* seq, float* x, float* O,
-                                 const uint8_t* gen_mask, uint64_t seed, int64_t first_patch, int32_t B, int32_t K, int32_t t,
-                                 uint32_t flags, const uint32_t* allowed, void* stream);
 
 /* ---- design scoring (build-defined evaluator; reference objective diffab_pytorch.py:808-887) ----------------------------------------
  * Per-design diffusion losses over a timestep grid: the reference's training objective (_shared_step, :808-880, summed as `loss` at
@@ -911,7 +901,7 @@ int diffab_sample_init_noised_aa(const diffab_sched* s, const diffab_igso3* fwd_
  *          noised; DIFFAB_FLAG_KEEP_STRUCTURE / _SEQUENCE leave that modality un-noised.
  *   Denoiser: Denoiser.forward (:558-607) at beta = beta[t_j] per row, on every launch form the sampler has (the shared-context pair
  *          stream, fp16 pair planes built once per call for the n_ctx contexts, the patch-resident module launch where
- *          diffab_sample_loop_shared would take it).
+ *          diffab_sample_loop_ex with a context map would take it).
  *   Terms, per residue with gen_mask & res_mask (0 elsewhere), the reference's element losses (:856-880 before reduction) summed over
  *          their trailing axes:  seq  sum_v q_v (log q_v - log p_v), q = q(s_{t-1} | s_t, s_0) (diffusion.py:168-192), p = softmax(logits);
  *          translations  sum_c (eps_hat - eps)^2;  orientations  sum_jk ((O0_hat^T O0) - I)^2_jk, O0_hat = O_t exp(hat(v_hat)) (:594-596,

@@ -151,3 +151,110 @@ def test_synthetic_patches_are_shard_invariant():
     assert torch.allclose(R.transpose(-1, -2) @ R, eye, atol=1e-5)
     assert (full["generation_mask"].sum(-1) >= 5).all() and (full["generation_mask"].sum(-1) <= 20).all()
 
+
+
+# ------------------------------------------------------------------ the sampler's C ABI: two loop entries, three init entries, one options struct
+REMOVED_SAMPLER_ENTRIES = ("diffab_sample_loop_shared", "diffab_sample_loop_aa", "diffab_sample_loop_rec", "diffab_sample_loop_steps",
+                           "diffab_sample_loop_guided", "diffab_sample_loop_tempered", "diffab_sample_loop_steered", "diffab_sample_init_aa",
+                           "diffab_sample_init_noised_aa")
+OPTION_STRUCTS = {"diffab_sample_options": _hip.SampleOptions, "diffab_sample_record": _hip.SampleRecord,
+                  "diffab_sample_steps": _hip.SampleSteps, "diffab_sample_guidance": _hip.SampleGuidance,
+                  "diffab_sample_temperature": _hip.SampleTemperature, "diffab_sample_steering": _hip.SampleSteering}
+C_SCALARS = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float}
+
+
+def header_struct(name):
+    """ctypes restatement of `typedef struct { ... } name;` as include/diffab_hip.h declares it: fields in the header's order, every
+    pointer a void*, the scalars by their C type."""
+    src = open(os.path.join(REPO, "include", "diffab_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + r"\s*;", src).group(1)
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        ctype, names = re.fullmatch(r"(?:const\s+)?(\w+)\s*(.*)", decl).groups()
+        for n in names.split(","):
+            n = n.strip()
+            fields.append((n.lstrip("* "), ctypes.c_void_p if n.startswith("*") else C_SCALARS[ctype]))
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
+def test_sample_option_structs_match_the_header():
+    sizes = {"diffab_sample_options": 64, "diffab_sample_record": 72, "diffab_sample_steps": 40, "diffab_sample_guidance": 56,
+             "diffab_sample_temperature": 32, "diffab_sample_steering": 104}
+    for name, mine in OPTION_STRUCTS.items():
+        want = header_struct(name)
+        assert [f[0] for f in mine._fields_] == [f[0] for f in want._fields_], name  # the header's field order
+        assert ctypes.sizeof(mine) == ctypes.sizeof(want) == sizes[name], name
+        for field, ctype in want._fields_:
+            assert getattr(mine, field).offset == getattr(want, field).offset, (name, field)
+            assert getattr(mine, field).size == ctypes.sizeof(ctype), (name, field)
+    opt = _hip.SampleOptions(n_ctx=3, temperature=_hip.SampleTemperature())  # by keyword; struct_bytes filled in
+    assert (opt.struct_bytes, opt.n_ctx) == (64, 3) and opt.temperature and not opt.record and not opt.ctx_of_row
+
+
+def test_sampler_entries_are_two_loops_and_three_inits():
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    for name in REMOVED_SAMPLER_ENTRIES:
+        assert name not in _hip.SYMBOLS and not hasattr(lib, name), name
+    names = header_symbols()
+    assert [n for n in names if n.startswith("diffab_sample_loop")] == ["diffab_sample_loop", "diffab_sample_loop_ex"]
+    assert [n for n in names if n.startswith("diffab_sample_init")] == ["diffab_sample_init", "diffab_sample_init_ex",
+                                                                        "diffab_sample_init_noised"]
+    counts = {"diffab_sample_loop": 18, "diffab_sample_loop_ex": 19, "diffab_sample_init": 10, "diffab_sample_init_ex": 12,
+              "diffab_sample_init_noised": 14}
+    for name, n in counts.items():
+        assert len(_hip.SYMBOLS[name][1]) == n, name
+    # diffab_sample_loop's arguments plus the options (a pointer) just before the stream
+    loop, ex = _hip.SYMBOLS["diffab_sample_loop"][1], _hip.SYMBOLS["diffab_sample_loop_ex"][1]
+    assert ex[:-2] == loop[:-1] and ex[-1] == loop[-1] and ex[-2] == ctypes.POINTER(_hip.SampleOptions)
+
+
+def fake_loop_call(l, B=2):
+    """diffab_sample_loop_ex(opt) on pointers that are never dereferenced and a workspace of 0 bytes: a call that passes every argument
+    check stops at the workspace check (DIFFAB_ERR_WORKSPACE), still on the host; no GPU is touched."""
+    dims = syn.BENCH_DIMS
+    d = _hip.Dims(B, 128, dims["D"], dims["C"], dims["H"], dims["DS"], dims["PQ"], dims["PV"], 2, 21)
+    fake = 256
+    layers = (_hip.IpaLayerWeights * 2)(*[_hip.IpaLayerWeights(*[fake] * 10) for _ in range(2)])
+    w = _hip.DenoiserWeights(*[fake] * 5, ctypes.cast(layers, ctypes.POINTER(_hip.IpaLayerWeights)),
+                             *[_hip.Mlp3Weights(*[fake] * 6) for _ in range(3)])
+    sched = _hip.Sched(10, *[fake] * 5)
+    tab = _hip.Igso3(11, 64, fake, fake, 0.1)
+    head = (ctypes.byref(d), ctypes.byref(w), ctypes.byref(sched), ctypes.byref(tab), *[fake] * 6, 1, 0, 10, 7, fake, 0, 0)
+
+    def call(opt):
+        return l.diffab_sample_loop_ex(*head, None if opt is None else ctypes.byref(opt), None)
+
+    call.plain = lambda: l.diffab_sample_loop(*head, None)
+    return call
+
+
+def test_sample_options_struct_bytes_is_checked_first():
+    l = _hip.load_library()
+    call = fake_loop_call(l)
+    for n in (0, 56):
+        opt = _hip.SampleOptions()
+        opt.struct_bytes = n
+        opt.allowed = 256  # not read: the size is refused before any other field
+        assert call(opt) == -1, n  # DIFFAB_ERR_ARG
+        assert b"struct_bytes" in l.diffab_last_error(), n
+
+
+def test_sample_options_n_ctx_without_a_map_is_zero_or_b():
+    l = _hip.load_library()
+    call = fake_loop_call(l, B=2)
+    for n_ctx in (1, 3, -1):
+        assert call(_hip.SampleOptions(n_ctx=n_ctx)) == -1, n_ctx  # DIFFAB_ERR_ARG
+        assert b"without ctx_of_row n_ctx must equal B" in l.diffab_last_error(), n_ctx
+    for n_ctx in (0, 2):
+        assert call(_hip.SampleOptions(n_ctx=n_ctx)) == -4, n_ctx  # DIFFAB_ERR_WORKSPACE: the next check
+
+
+def test_null_and_zeroed_sample_options_reach_the_same_check():
+    l = _hip.load_library()
+    call = fake_loop_call(l)
+    errors = []
+    for rc in (call.plain(), call(None), call(_hip.SampleOptions())):
+        assert rc == -4  # DIFFAB_ERR_WORKSPACE at 0 bytes
+        errors.append(l.diffab_last_error())
+    assert errors[0] == errors[1] == errors[2] and b"sample_loop: workspace 0 <" in errors[0]

@@ -28,15 +28,6 @@ def test_flags_match_the_header():
     assert not {2, 4, 8} & set(values)
 
 
-def test_library_exports_the_new_entries():
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in ("diffab_sample_init_ex", "diffab_sample_init_noised"):
-        assert hasattr(lib, name), name
-        assert name in _hip.SYMBOLS, name
-    assert len(_hip.SYMBOLS["diffab_sample_init_ex"][1]) == 11
-    assert len(_hip.SYMBOLS["diffab_sample_init_noised"][1]) == 13
-
-
 def test_mode_table():
     assert SAMPLE_MODES["codesign"] == (True, True, 0)
     assert SAMPLE_MODES["fixed_backbone"] == (False, True, _hip.FLAG_KEEP_STRUCTURE)

@@ -142,7 +142,7 @@ FORMS = {"per_layer": {}, "graph": dict(graph=True), "num_samples": dict(num_sam
 
 @pytest.mark.parametrize("form", sorted(FORMS))
 def test_all_true_mask_is_bitwise_unconstrained(bench, form):
-    """From the initial state (diffab_sample_init_aa / _noised_aa) through the loop (diffab_sample_loop_aa): the masked draws with every
+    """From the initial state (diffab_sample_init_ex / _noised with `allowed`) through the loop (diffab_sample_options.allowed): the masked draws with every
     class allowed are bitwise the unconstrained ones, on each launch form of the loop."""
     dims, model = bench
     inp = patches(3, 128, dims, seed=6)
@@ -242,9 +242,9 @@ def test_one_step_vs_host_restatement(unit, bench, geometry):
 
 # ------------------------------------------------------------------ 5. initial state and optimisation start, on the entries
 def test_init_and_noised_start_vs_rules(unit):
-    """diffab_sample_init_aa: rule 2 on the STREAM_INIT_S uniforms, exactly (UNK drawn only where it is the whole set), x and O bitwise
-    diffab_sample_init's.  diffab_sample_init_noised_aa: rule 3 (q(s_t | s_0) restricted to the set) on the STREAM_OPT_SEQ uniforms with
-    the margin rule.  NULL masks are the unsuffixed entries, bitwise."""
+    """diffab_sample_init_ex with `allowed`: rule 2 on the STREAM_INIT_S uniforms, exactly (UNK drawn only where it is the whole set), x and
+    O bitwise diffab_sample_init's.  diffab_sample_init_noised with `allowed`: rule 3 (q(s_t | s_0) restricted to the set) on the
+    STREAM_OPT_SEQ uniforms with the margin rule.  NULL masks are the unconstrained entries, bitwise."""
     dims, model = unit
     lib = _hip.lib()
     P, st = _hip.ptr, _hip.stream_ptr()
@@ -264,9 +264,9 @@ def test_init_and_noised_start_vs_rules(unit):
     s0, x0, O0 = state()
     _hip.check(lib.diffab_sample_init(P(s0), P(x0), P(O0), P(gm), seed, fp, B, K, T, st), "init")
     s1, x1, O1 = state()
-    _hip.check(lib.diffab_sample_init_aa(P(s1), P(x1), P(O1), P(gm), seed, fp, B, K, T, 0, P(words), st), "init_aa")
+    _hip.check(lib.diffab_sample_init_ex(P(s1), P(x1), P(O1), P(gm), seed, fp, B, K, T, 0, P(words), st), "init_ex allowed")
     s2, x2, O2 = state()
-    _hip.check(lib.diffab_sample_init_aa(P(s2), P(x2), P(O2), P(gm), seed, fp, B, K, T, 0, None, st), "init_aa NULL")
+    _hip.check(lib.diffab_sample_init_ex(P(s2), P(x2), P(O2), P(gm), seed, fp, B, K, T, 0, None, st), "init_ex NULL")
     assert torch.equal(s2, s0) and torch.equal(x2, x0) and torch.equal(O2, O0)
     assert torch.equal(x1, x0) and torch.equal(O1, O0)
     u = uniforms(lib, seed, fp, B, K, T + 1, STREAM_INIT_S)
@@ -287,13 +287,14 @@ def test_init_and_noised_start_vs_rules(unit):
     one, c21 = torch.tensor(1.0), torch.tensor(1.0) / torch.tensor(21.0)
     for t in (1, 8, 40, 100):
         s0, x0, O0 = state()
-        _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), seed, fp, B, K, t, 0, st), t)
+        _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), seed, fp, B, K, t, 0, None,
+                                                 st), t)
         s1, x1, O1 = state()
-        _hip.check(lib.diffab_sample_init_noised_aa(C.byref(sd.struct), C.byref(fwd), P(s1), P(x1), P(O1), P(gm), seed, fp, B, K, t, 0,
-                                                    P(words), st), t)
+        _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s1), P(x1), P(O1), P(gm), seed, fp, B, K, t, 0,
+                                                 P(words), st), t)
         s2, x2, O2 = state()
-        _hip.check(lib.diffab_sample_init_noised_aa(C.byref(sd.struct), C.byref(fwd), P(s2), P(x2), P(O2), P(gm), seed, fp, B, K, t, 0,
-                                                    None, st), t)
+        _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s2), P(x2), P(O2), P(gm), seed, fp, B, K, t, 0,
+                                                 None, st), t)
         assert torch.equal(s2, s0) and torch.equal(x2, x0) and torch.equal(O2, O0), t
         assert torch.equal(x1, x0) and torch.equal(O1, O0), t
         wk = ab[t]
@@ -356,12 +357,12 @@ def test_c_abi_rejects_a_mask_with_keep_sequence(bench):
     ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(dims_c)))
     rc_, pc_ = inp["res_context_emb"], inp["pair_context_emb"]
     bad = [
-        ("init_aa", lambda: lib.diffab_sample_init_aa(P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, T, keep, P(words), st)),
-        ("noised_aa", lambda: lib.diffab_sample_init_noised_aa(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, 8,
-                                                              keep, P(words), st)),
-        ("loop_aa", lambda: lib.diffab_sample_loop_aa(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0),
-                                                      P(O0), P(rc_), P(pc_), B, None, P(gm), 3, 1, 10, 5, P(ws), ws.numel(), keep, P(words),
-                                                      st)),
+        ("init_ex", lambda: lib.diffab_sample_init_ex(P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, T, keep, P(words), st)),
+        ("noised", lambda: lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, 8,
+                                                        keep, P(words), st)),
+        ("loop_ex", lambda: lib.diffab_sample_loop_ex(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0),
+                                                      P(O0), P(rc_), P(pc_), P(gm), 3, 1, 10, 5, P(ws), ws.numel(), keep,
+                                                      C.byref(_hip.SampleOptions(n_ctx=B, allowed=P(words))), st)),
     ]
     for what, fn in bad:
         assert fn() == -1, what  # DIFFAB_ERR_ARG

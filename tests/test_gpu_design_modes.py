@@ -278,7 +278,7 @@ def test_c_abi_keep_bits_and_argument_errors(bench):
     _hip.check(lib.diffab_sample_init(P(seq), P(x), P(O), P(gm), 3, 1, B, K, T, st), "init")
     for flags in (0, _hip.FLAG_GRAPH_SAMPLER | _hip.FLAG_PAIR_F32):
         s2, x2, O2 = inp["seq_idx"].clone(), inp["translations"].clone(), inp["orientations"].clone()
-        _hip.check(lib.diffab_sample_init_ex(P(s2), P(x2), P(O2), P(gm), 3, 1, B, K, T, flags, st), "init_ex")
+        _hip.check(lib.diffab_sample_init_ex(P(s2), P(x2), P(O2), P(gm), 3, 1, B, K, T, flags, None, st), "init_ex")
         assert torch.equal(s2, seq) and torch.equal(x2, x) and torch.equal(O2, O), flags
     sd = model._sched_on_device()
     fwd = model.orientation_diffuser.so3.struct()
@@ -290,20 +290,20 @@ def test_c_abi_keep_bits_and_argument_errors(bench):
     rc_, pc_ = inp["res_context_emb"], inp["pair_context_emb"]
     s0, x0, O0 = inp["seq_idx"].clone(), inp["translations"].clone(), inp["orientations"].clone()
     bad = [
-        ("init_ex both", lambda: lib.diffab_sample_init_ex(P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, T, both, st)),
+        ("init_ex both", lambda: lib.diffab_sample_init_ex(P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, T, both, None, st)),
         ("noised both", lambda: lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, 8,
-                                                              both, st)),
+                                                              both, None, st)),
         ("noised t=0", lambda: lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, 0,
-                                                             0, st)),
+                                                             0, None, st)),
         ("noised t=T+1", lambda: lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K,
-                                                               T + 1, 0, st)),
+                                                               T + 1, 0, None, st)),
         ("noised short table", lambda: lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(short), P(s0), P(x0), P(O0), P(gm), 3, 1, B,
-                                                                     K, 8, 0, st)),
+                                                                     K, 8, 0, None, st)),
         ("loop both", lambda: lib.diffab_sample_loop(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0),
                                                      P(O0), P(rc_), P(pc_), P(gm), 3, 1, 10, 5, P(ws), ws.numel(), both, st)),
-        ("loop_shared both", lambda: lib.diffab_sample_loop_shared(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev),
-                                                                   P(s0), P(x0), P(O0), P(rc_), P(pc_), B, None, P(gm), 3, 1, 10, 5, P(ws),
-                                                                   ws.numel(), both, st)),
+        ("loop_ex both", lambda: lib.diffab_sample_loop_ex(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0),
+                                                           P(x0), P(O0), P(rc_), P(pc_), P(gm), 3, 1, 10, 5, P(ws), ws.numel(), both,
+                                                           C.byref(_hip.SampleOptions(n_ctx=B)), st)),
     ]
     for what, fn in bad:
         assert fn() == -1, what  # DIFFAB_ERR_ARG
@@ -312,6 +312,6 @@ def test_c_abi_keep_bits_and_argument_errors(bench):
     assert torch.equal(s0, inp["seq_idx"]) and torch.equal(x0, inp["translations"]) and torch.equal(O0, inp["orientations"])
     # t = T and t = 1 are inside the schedule
     for t in (1, T):
-        _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, t, 0, st), t)
+        _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), P(s0), P(x0), P(O0), P(gm), 3, 1, B, K, t, 0, None, st), t)
     torch.cuda.synchronize()
     assert torch.isfinite(x0).all() and torch.isfinite(O0).all()

@@ -1,4 +1,4 @@
-"""Structure guidance on the MI355X: DiffAb.sample(guidance=...), guidance.structure_energy, diffab_sample_loop_guided and
+"""Structure guidance on the MI355X: DiffAb.sample(guidance=...), guidance.structure_energy, diffab_sample_options.guidance and
 diffab_guidance_energy.
 
 The rule is DESIGN.md section 4.10 / include/diffab_hip.h.  The energy entry matches the float64 restatement of test_guidance_host.py at

@@ -1,4 +1,4 @@
-"""Fewer-step reverse sampling on the MI355X: DiffAb.sample(steps=...), diffab_sample_loop_steps and diffab_reverse_update_jump.
+"""Fewer-step reverse sampling on the MI355X: DiffAb.sample(steps=...), diffab_sample_options.steps and diffab_reverse_update_jump.
 
 The rule is DESIGN.md section 4.9 / include/diffab_hip.h.  Listing every step is bitwise the ordinary loop on every launch form; a mixed
 list is bitwise the ordinary run up to its last stride-1 step; one jump, teacher-forced, is the oracle denoiser followed by the float64
@@ -390,19 +390,19 @@ def test_c_abi_rejects_bad_plans(bench):
            "beta' nan": (plan(beta=setat(bj, 10, float("nan"))), None), "alpha' 0": (plan(alpha=setat(aj, 3, 0.0)), None),
            "alpha' 1": (plan(alpha=setat(aj, 3, 1.0)), None),
            "record slot off the list": (plan(), record({10: 0, 9: 1}))}
+    def loop(pl, rec):
+        return lib.diffab_sample_loop_ex(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0), P(O0), P(rc_),
+                                         P(pc_), P(gm), 3, 1, t_start, t_stop, P(ws), ws.numel(), 0,
+                                         C.byref(_hip.SampleOptions(n_ctx=B, record=rec, steps=pl)), st)
+
     for what, (pl, rec) in bad.items():
-        rc = lib.diffab_sample_loop_steps(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0), P(O0), P(rc_),
-                                          P(pc_), B, None, P(gm), 3, 1, t_start, t_stop, P(ws), ws.numel(), 0, None,
-                                          None if rec is None else C.byref(rec), C.byref(pl), st)
-        assert rc == -1, what  # DIFFAB_ERR_ARG
+        assert loop(pl, rec) == -1, what  # DIFFAB_ERR_ARG
     torch.cuda.synchronize()
     assert torch.equal(s0, inp["seq_idx"]) and torch.equal(x0, inp["translations"]) and torch.equal(O0, inp["orientations"])
     assert bool((plan_dev == 77).all()) and bool((slot_dev == 77).all())
     # the good plan runs and fills the device plan: next[] along the list, the coefficients bit for bit
     ok = plan()
-    assert lib.diffab_sample_loop_steps(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0), P(O0), P(rc_),
-                                        P(pc_), B, None, P(gm), 3, 1, t_start, t_stop, P(ws), ws.numel(), 0, None,
-                                        C.byref(record({10: 0, 5: 1})), C.byref(ok), st) == 0
+    assert loop(ok, record({10: 0, 5: 1})) == 0
     torch.cuda.synchronize()
     pd = plan_dev.cpu()
     assert pd[[10, 8, 5, 3]].tolist() == [8, 5, 3, 2]

@@ -1,10 +1,13 @@
-"""Shared-context sampling on the MI355X: DiffAb.sample(num_samples=N) and DiffAb.sample(context_index=...) (diffab_sample_loop_shared).
+"""Shared-context sampling on the MI355X: DiffAb.sample(num_samples=N) and DiffAb.sample(context_index=...)
+(diffab_sample_options.ctx_of_row).
 
 The specification is an equality: N designs of each patch from ONE copy of its context are bitwise the samples of num_samples=1 on the
 repeat_interleave(N, dim=0) of every per-patch input (same seed, same first_patch) - on every launch form of the sampler: the
 patch-resident module launch, the per-layer launches, the two-chunk K = 256 items, the fp32 pair stream, the generic kernels, graph
 replay and skipped row tiles; plus sharding by output rows, distinct designs per patch, and the memory the shared form does not hold.
 """
+import ctypes as C
+
 import pytest
 import torch
 
@@ -207,3 +210,36 @@ def test_memory_of_256_designs_from_16_contexts(hip):
     assert_bitwise(got, want, "memory run")
     print(f"in-call peak: shared {peak_shared / 2**20:.0f} MiB, replicated {peak_rep / 2**20:.0f} MiB")
     assert peak_rep - peak_shared >= 0.75 * 2**30, (peak_shared, peak_rep)
+
+
+# ------------------------------------------------------------------ the C ABI
+def test_loop_ex_without_options_is_the_plain_loop(hip):
+    """diffab_sample_loop, diffab_sample_loop_ex with NULL options and with options that are zero except for struct_bytes: three steps
+    from t_start = T = 10 on the same seed give bitwise the same seq, x and O (B = 2, K = 64, unit dims, one layer)."""
+    from diffab_pytorch import DiffAb
+
+    dims = dict(syn.UNIT_DIMS, NL=1)
+    B, K, T = 2, 64, 10
+    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
+    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=5, prefix=""))
+    inp = {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=46, coord_sigma=5.0).items() if k in STATE + CTX}
+    P, st = _hip.ptr, _hip.stream_ptr()
+    gm = _hip.dev_mask(inp["generation_mask"])
+    dims_c, w, sd = model.denoiser.hip_dims(B, K), model.denoiser.hip_weights(), model._sched_on_device()
+    rev = model._reverse_so3().struct()
+    ws = _hip.workspace(hip.diffab_sample_workspace_bytes(C.byref(dims_c)))
+
+    def run(entry, *opt):
+        seq, x, O = inp["seq_idx"].clone(), inp["translations"].clone(), inp["orientations"].clone()
+        _hip.check(hip.diffab_sample_init(P(seq), P(x), P(O), P(gm), 17, 0, B, K, T, st), "init")
+        _hip.check(entry(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(seq), P(x), P(O), P(inp["res_context_emb"]),
+                         P(inp["pair_context_emb"]), P(gm), 17, 0, T, T - 3, P(ws), ws.numel(), 0, *opt, st), "loop")
+        torch.cuda.synchronize()
+        return {"seq_idx": seq, "translations": x, "orientations": O}
+
+    want = run(hip.diffab_sample_loop)
+    assert not torch.equal(want["translations"], inp["translations"])  # the steps ran
+    assert_bitwise(run(hip.diffab_sample_loop_ex, None), want, "NULL options")
+    zeroed = _hip.SampleOptions()
+    assert zeroed.struct_bytes == 64 and bytes(zeroed)[4:] == bytes(60)
+    assert_bitwise(run(hip.diffab_sample_loop_ex, C.byref(zeroed)), want, "zeroed options")

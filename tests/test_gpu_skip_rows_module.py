@@ -113,7 +113,7 @@ def test_module_launch_skips_unread_tiles_k256(model):
 
 
 def test_shared_contexts_skip_unread_tiles(model):
-    """diffab_sample_loop_shared: N samples per context read the pair rows through ctx_of_row; the tile map is per state row"""
+    """shared contexts (diffab_sample_options.ctx_of_row): N samples per context read the pair rows through ctx_of_row; the tile map is per state row"""
     bd, m = model
     B, N = 4, 2
     bi = {k: v.cuda() for k, v in syn.patches(B, 128, bd, seed=63).items()}

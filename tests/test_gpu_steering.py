@@ -1,4 +1,4 @@
-"""Particle steering on the MI355X: DiffAb.sample(steering=...), diffab_sample_loop_steered and the three teacher-forced entries
+"""Particle steering on the MI355X: DiffAb.sample(steering=...), diffab_sample_options.steering and the three teacher-forced entries
 diffab_steer_resample, diffab_steer_gather and diffab_steer_energy.
 
 The rule is DESIGN.md section 4.14 / include/diffab_hip.h.  The resampling kernel matches steering.resample_oracle (float64 numpy) on

@@ -1,4 +1,4 @@
-"""Noise scales and sequence temperature on the MI355X: DiffAb.sample(temperature=...) and diffab_sample_loop_tempered.
+"""Noise scales and sequence temperature on the MI355X: DiffAb.sample(temperature=...) and diffab_sample_options.temperature.
 
 The rule is DESIGN.md section 4.11 / include/diffab_hip.h.  All-ones values are bitwise the untempered sample; one step is linear in the
 translation scale; the rotation angle is the inverse CDF of the scaled row of the stacked table at the Philox uniforms, about the
@@ -281,7 +281,8 @@ def test_per_row_sweep_is_each_row_alone(bench, form):
 
 # ------------------------------------------------------------------ 7. the C entry
 class Proxy:
-    """The library with diffab_sample_loop_tempered's struct argument rewritten by `edit` (None: passed as NULL); the rc is recorded."""
+    """The library with the temperature struct of diffab_sample_loop_ex's options rewritten by `edit` (None: passed as NULL); the rc is
+    recorded."""
 
     def __init__(self, lib, edit):
         self._lib, self._edit, self.rc = lib, edit, []
@@ -289,12 +290,11 @@ class Proxy:
     def __getattr__(self, name):
         return getattr(self._lib, name)
 
-    def diffab_sample_loop_tempered(self, *args):
-        args = list(args)
-        args[-2] = self._edit(args[-2]._obj if args[-2] is not None else None)
-        if args[-2] is not None:
-            args[-2] = C.byref(args[-2])
-        self.rc.append(self._lib.diffab_sample_loop_tempered(*args))
+    def diffab_sample_loop_ex(self, *args):
+        opt = args[-2]._obj  # the SampleOptions behind byref
+        t = self._edit(opt.temperature.contents if opt.temperature else None)  # (contents shares the struct's memory)
+        opt.temperature = None if t is None else C.pointer(t)
+        self.rc.append(self._lib.diffab_sample_loop_ex(*args))
         return self.rc[-1]
 
 
@@ -304,7 +304,7 @@ def test_null_struct_is_guided_and_bad_structs_enqueue_nothing(bench, monkeypatc
     inp = patches(2, 128, dims, seed=47)
     guide = SampleGuidance(clash=1.0, bond=1.0)
     kw = dict(seed=9, t_start=10, t_stop=0, init=False, guidance=guide)
-    want = sample(model, inp, **kw)  # diffab_sample_loop_guided
+    want = sample(model, inp, **kw)  # guidance alone: options.temperature NULL
     proxy = Proxy(lib, lambda s: None)
     monkeypatch.setattr(_hip, "lib", lambda: proxy)
     # (lambda_O = 1: the call passes the ordinary reverse table, which a NULL struct reads at row t)
@@ -337,7 +337,7 @@ def test_null_struct_is_guided_and_bad_structs_enqueue_nothing(bench, monkeypatc
         proxy = Proxy(lib, edit)
         monkeypatch.setattr(_hip, "lib", lambda: proxy)
         seen = {}
-        real = lib.diffab_sample_loop_tempered
+        real = lib.diffab_sample_loop_ex
 
         def spy(*args, real=real):
             state = [tensors[a.value] for a in args[4:7]]  # seq, x, O
@@ -347,7 +347,7 @@ def test_null_struct_is_guided_and_bad_structs_enqueue_nothing(bench, monkeypatc
             seen["same"] = all(torch.equal(a, b) for a, b in zip(before, state))
             return rc
 
-        proxy._lib = type("L", (), {"diffab_sample_loop_tempered": staticmethod(spy), "__getattr__": lambda s, n: getattr(lib, n)})()
+        proxy._lib = type("L", (), {"diffab_sample_loop_ex": staticmethod(spy), "__getattr__": lambda s, n: getattr(lib, n)})()
         kw2 = dict(kw, **extra)
         if extra.get("mode") == "fixed_backbone":
             kw2.pop("guidance")

@@ -1,4 +1,4 @@
-"""Trajectory recording of the sampler on the MI355X: DiffAb.sample(trajectory=...) and diffab_sample_loop_rec.
+"""Trajectory recording of the sampler on the MI355X: DiffAb.sample(trajectory=...) and diffab_sample_options.record.
 
 The specification (include/diffab_hip.h): label t holds the state that step t denoises - bitwise the same call
 with t_stop = t - and, with predictions, what the denoiser made of it (x0_hat, O0_hat, the softmax posterior over s_{t-1}).  Recording
@@ -291,18 +291,20 @@ def test_c_abi_rejects_bad_records(bench):
            "null O": record(drop=("O",)), "partial predictions": record(drop=("seq_probs",)),
            "one prediction": record(drop=("pred_x", "pred_O")), "null host table": record(host=False),
            "null device table": record(dev=False)}
+    def loop(rec):
+        return lib.diffab_sample_loop_ex(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0), P(O0), P(rc_),
+                                         P(pc_), P(gm), 3, 1, t_start, t_stop, P(ws), ws.numel(), 0,
+                                         C.byref(_hip.SampleOptions(n_ctx=B, record=rec)), st)
+
     for what, rec in bad.items():
-        rc = lib.diffab_sample_loop_rec(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0), P(O0), P(rc_),
-                                        P(pc_), B, None, P(gm), 3, 1, t_start, t_stop, P(ws), ws.numel(), 0, None, C.byref(rec), st)
-        assert rc == -1, what  # DIFFAB_ERR_ARG
+        assert loop(rec) == -1, what  # DIFFAB_ERR_ARG
     torch.cuda.synchronize()
     assert torch.equal(s0, inp["seq_idx"]) and torch.equal(x0, inp["translations"]) and torch.equal(O0, inp["orientations"])
     assert_bitwise(buf, before, "record buffers")
     assert bool((slot_dev == 77).all())
     # the good record runs, fills the device table and every slot
     ok = record()
-    assert lib.diffab_sample_loop_rec(C.byref(dims_c), C.byref(w.struct), C.byref(sd.struct), C.byref(rev), P(s0), P(x0), P(O0), P(rc_),
-                                      P(pc_), B, None, P(gm), 3, 1, t_start, t_stop, P(ws), ws.numel(), 0, None, C.byref(ok), st) == 0
+    assert loop(ok) == 0
     torch.cuda.synchronize()
     assert slot_dev[[10, 8, 6]].tolist() == [0, 1, 2] and int((slot_dev == -1).sum()) == T + 1 - 3
     assert bool(torch.isfinite(buf["pred_x"]).all()) and not bool((buf["x"] == 7.0).any())

@@ -2,7 +2,7 @@
 potential and its gradient checked against torch autograd and central differences, the argument checks that happen before any library
 call, and the C-ABI entries and struct layout.
 
-The rule is DESIGN.md section 4.10 / include/diffab_hip.h (diffab_sample_loop_guided, diffab_guidance_energy)."""
+The rule is DESIGN.md section 4.10 / include/diffab_hip.h (diffab_sample_options.guidance, diffab_guidance_energy)."""
 import ctypes
 import os
 import shutil
@@ -273,13 +273,9 @@ def test_sample_guidance_is_frozen():
 # ------------------------------------------------------------------ the C ABI
 def test_library_exports_the_guidance_entries():
     lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in ("diffab_sample_loop_guided", "diffab_guidance_energy"):
-        assert hasattr(lib, name) and name in _hip.SYMBOLS
-    args, base = _hip.SYMBOLS["diffab_sample_loop_guided"][1], _hip.SYMBOLS["diffab_sample_loop_steps"][1]
-    # diffab_sample_loop_steps's arguments plus the guidance (a pointer) just before the stream
-    assert len(args) == len(base) + 1 == 24
-    assert args[:-2] == base[:-1] and args[-1] == base[-1]
-    assert args[-2] == ctypes.POINTER(_hip.SampleGuidance)
+    assert hasattr(lib, "diffab_guidance_energy") and "diffab_guidance_energy" in _hip.SYMBOLS
+    # the guidance travels in diffab_sample_options.guidance (the loop's own ABI: test_cabi_and_host.py)
+    assert dict(_hip.SampleOptions._fields_)["guidance"] == ctypes.POINTER(_hip.SampleGuidance)
     assert _hip.SYMBOLS["diffab_guidance_energy"][1][2] == ctypes.POINTER(_hip.SampleGuidance)
 
 

@@ -1,7 +1,7 @@
 """CPU: the host side of fewer-step reverse sampling (DiffAb.sample(steps=...)) - the even step list, the jump coefficients, a float64
 restatement of the sequence jump against brute force, the argument checks that happen before any library call, and the C-ABI entries.
 
-The rule is DESIGN.md section 4.9 / include/diffab_hip.h (diffab_sample_loop_steps)."""
+The rule is DESIGN.md section 4.9 / include/diffab_hip.h (diffab_sample_options.steps)."""
 import ctypes
 import types
 
@@ -228,13 +228,9 @@ def test_trajectory_labels_of_a_respaced_run():
 # ------------------------------------------------------------------ the C ABI
 def test_library_exports_the_steps_entries():
     lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in ("diffab_sample_loop_steps", "diffab_reverse_update_jump"):
-        assert hasattr(lib, name) and name in _hip.SYMBOLS
-    args, base = _hip.SYMBOLS["diffab_sample_loop_steps"][1], _hip.SYMBOLS["diffab_sample_loop_rec"][1]
-    # diffab_sample_loop_rec's arguments plus the step list (a pointer) just before the stream
-    assert len(args) == len(base) + 1 == 23
-    assert args[:-2] == base[:-1] and args[-1] == base[-1]
-    assert args[-2] == ctypes.POINTER(_hip.SampleSteps)
+    assert hasattr(lib, "diffab_reverse_update_jump") and "diffab_reverse_update_jump" in _hip.SYMBOLS
+    # the step list travels in diffab_sample_options.steps (the loop's own ABI: test_cabi_and_host.py)
+    assert dict(_hip.SampleOptions._fields_)["steps"] == ctypes.POINTER(_hip.SampleSteps)
     jump, upd = _hip.SYMBOLS["diffab_reverse_update_jump"][1], _hip.SYMBOLS["diffab_reverse_update"][1]
     # diffab_reverse_update's arguments with (s, beta', alpha') after t and r_out after u_seq
     assert len(jump) == len(upd) + 4

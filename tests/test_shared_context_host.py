@@ -1,4 +1,4 @@
-"""CPU: the host side of shared-context sampling (DiffAb.sample(num_samples=N) / context_index, diffab_sample_loop_shared) - argument
+"""CPU: the host side of shared-context sampling (DiffAb.sample(num_samples=N) / context_index, diffab_sample_options.ctx_of_row) - argument
 validation that happens before any library call, and the workspace sizing of the shared form (host-only C-ABI calls)."""
 import ctypes as C
 import types

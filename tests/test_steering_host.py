@@ -2,7 +2,7 @@
 homogeneity and shard alignment errors, the C-ABI entries and struct layout, and the properties of the float64 restatement of the
 resampling rule (steering.resample_oracle), which tests/test_gpu_steering.py checks the kernel against.
 
-The rule is DESIGN.md section 4.14 / include/diffab_hip.h (diffab_sample_loop_steered, diffab_steer_resample)."""
+The rule is DESIGN.md section 4.14 / include/diffab_hip.h (diffab_sample_options.steering, diffab_steer_resample)."""
 import ctypes
 import os
 import shutil
@@ -244,12 +244,10 @@ def test_particle_steering_is_frozen():
 # ------------------------------------------------------------------ the C ABI
 def test_library_exports_the_steering_entries():
     lib = ctypes.CDLL(_hip.LIB_PATH)
-    for name in ("diffab_sample_loop_steered", "diffab_steer_energy", "diffab_steer_resample", "diffab_steer_gather"):
+    for name in ("diffab_steer_energy", "diffab_steer_resample", "diffab_steer_gather"):
         assert hasattr(lib, name) and name in _hip.SYMBOLS, name
-    args, base = _hip.SYMBOLS["diffab_sample_loop_steered"][1], _hip.SYMBOLS["diffab_sample_loop_tempered"][1]
-    assert len(args) == len(base) + 1 == 26  # diffab_sample_loop_tempered's arguments plus the steering (a pointer) before the stream
-    assert args[:-2] == base[:-1] and args[-1] == base[-1]
-    assert args[-2] == ctypes.POINTER(_hip.SampleSteering)
+    # the steering travels in diffab_sample_options.steering (the loop's own ABI: test_cabi_and_host.py)
+    assert dict(_hip.SampleOptions._fields_)["steering"] == ctypes.POINTER(_hip.SampleSteering)
     assert len(_hip.SYMBOLS["diffab_steer_resample"][1]) == 11 and len(_hip.SYMBOLS["diffab_steer_gather"][1]) == 9
     assert _hip.SYMBOLS["diffab_steer_energy"][1][5] == ctypes.POINTER(_hip.SampleSteering)
     src = open(os.path.join(REPO, "diffab-pytorch_amd", "csrc", "philox.h")).read()

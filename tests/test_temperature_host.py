@@ -219,14 +219,6 @@ def test_per_row_values_follow_the_output_rows(model):
 
 
 # ------------------------------------------------------------------ the C ABI
-def test_library_exports_the_tempered_entry():
-    name = "diffab_sample_loop_tempered"
-    assert name in _hip.SYMBOLS
-    args, base = _hip.SYMBOLS[name][1], _hip.SYMBOLS["diffab_sample_loop_guided"][1]
-    assert args[:-1] == base[:-1] + [ctypes.POINTER(_hip.SampleTemperature)] and args[-1] is base[-1]
-    assert hasattr(ctypes.CDLL(_hip.LIB_PATH), name)
-
-
 def test_temperature_struct_layout():
     fields = [f[0] for f in _hip.SampleTemperature._fields_]
     assert fields == ["trans_scale", "rot_scale", "seq_temp", "rot_row"]

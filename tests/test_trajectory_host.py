@@ -12,17 +12,6 @@ from diffab_pytorch.diffab_pytorch import Denoiser, _trajectory_labels
 V, T = 21, 10
 
 
-def test_library_exports_the_record_entry():
-    lib = ctypes.CDLL(_hip.LIB_PATH)
-    assert hasattr(lib, "diffab_sample_loop_rec")
-    assert "diffab_sample_loop_rec" in _hip.SYMBOLS
-    args, base = _hip.SYMBOLS["diffab_sample_loop_rec"][1], _hip.SYMBOLS["diffab_sample_loop_aa"][1]
-    # diffab_sample_loop_aa's arguments plus the record (a pointer) just before the stream
-    assert len(args) == len(base) + 1 == 22
-    assert args[:-2] == base[:-1] and args[-1] == base[-1]
-    assert args[-2] == ctypes.POINTER(_hip.SampleRecord)
-
-
 def test_record_struct_layout():
     # int32 n_slots, then eight pointers (the host table, the device table, three state and three prediction fields)
     names = [f[0] for f in _hip.SampleRecord._fields_]

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Reverse-sampler cost of the sequence constraints (diffab_sample_loop_aa), ROWS patches, K = 128, benchmark model, one context per row
+"""Reverse-sampler cost of the sequence constraints (diffab_sample_options.allowed), ROWS patches, K = 128, benchmark model, one context per row
 (256 rows fill the chip: the patch-resident module launch, what bench.py times).
 
 Cases, alternating inside one process (the order reversed every other round), each a --warmup-step untimed call and then ONE call of
 --steps steps from t = T on the re-initialised state, bracketed by hipEvents after a device synchronise (bench.py's timed block):
   free     diffab_sample_loop (no mask)
-  all      diffab_sample_loop_aa with every class allowed (the masked code, bitwise the free result - checked)
-  no_cmx   diffab_sample_loop_aa with Cys, Met and UNK forbidden on every residue
+  all      diffab_sample_loop_ex, option `allowed`, with every class allowed (the masked code, bitwise the free result - checked)
+  no_cmx   the same with Cys, Met and UNK forbidden on every residue
 Reported per case: median / min / max ms per step over --repeats rounds.  Prints one JSON document (and writes it with --json).
 --cases runs a subset (a kernel trace per case: rocprofv3 --kernel-trace --stats -- python tools/aa_constraints_bench.py --cases free).
 
@@ -90,18 +90,14 @@ def main():
 
     def init(words):
         seq.copy_(seq0), x.copy_(x0), O.copy_(O0)
-        _hip.check(lib.diffab_sample_init_aa(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, 0, R, K, T, 0, _hip.ptr(words),
-                                             _hip.stream_ptr()), "sample_init_aa")
+        _hip.check(lib.diffab_sample_init_ex(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, 0, R, K, T, 0, _hip.ptr(words),
+                                             _hip.stream_ptr()), "sample_init_ex")
 
     def loop(words, t_start, t_stop):
-        common = (C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(res),
-                  _hip.ptr(pair))
-        if words is None:
-            _hip.check(lib.diffab_sample_loop(*common, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0, _hip.stream_ptr()),
-                       "diffab_sample_loop")
-        else:
-            _hip.check(lib.diffab_sample_loop_aa(*common, R, None, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0,
-                                                 _hip.ptr(words), _hip.stream_ptr()), "diffab_sample_loop_aa")
+        opt = None if words is None else C.byref(_hip.SampleOptions(allowed=_hip.ptr(words)))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws),
+                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 

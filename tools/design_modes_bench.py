@@ -84,9 +84,10 @@ def main():
         seq.copy_(seq0), x.copy_(x0), O.copy_(O0)
         p = (_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm))
         if t_opt is None:
-            _hip.check(lib.diffab_sample_init_ex(*p, seed, 0, R, K, T, keep, _hip.stream_ptr()), "sample_init_ex")
+            _hip.check(lib.diffab_sample_init_ex(*p, seed, 0, R, K, T, keep, None, _hip.stream_ptr()), "sample_init_ex")
         else:
-            _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), *p, seed, 0, R, K, t_opt, keep, _hip.stream_ptr()),
+            _hip.check(lib.diffab_sample_init_noised(C.byref(sd.struct), C.byref(fwd), *p, seed, 0, R, K, t_opt, keep, None,
+                                                     _hip.stream_ptr()),
                        "sample_init_noised")
 
     def loop(keep, t_start, t_stop):

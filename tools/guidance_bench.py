@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Reverse-sampler cost and effect of structure guidance (diffab_sample_loop_guided), ROWS patches, K = 128, benchmark model, one context
+"""Reverse-sampler cost and effect of structure guidance (diffab_sample_options.guidance), ROWS patches, K = 128, benchmark model, one context
 per row (256 rows fill the chip: the patch-resident module launch, what bench.py times).
 
 Cases, alternating inside one process (the order reversed every other round), each a --warmup-step untimed call and then ONE call of
 --steps steps from t = T on the re-initialised state, bracketed by hipEvents after a device synchronise (bench.py's timed block):
-  free     diffab_sample_loop_steps without guidance
-  zero     diffab_sample_loop_guided with both weights 0 (the guidance kernel runs every step; bitwise the free result - checked)
-  guided   diffab_sample_loop_guided with clash = bond = 1 (d0 = L = 3.8 A, max_shift 1 A, every step)
+  free     diffab_sample_loop_ex without options
+  zero     diffab_sample_loop_ex, option `guidance`, with both weights 0 (the guidance kernel runs every step; bitwise the free result - checked)
+  guided   the same with clash = bond = 1 (d0 = L = 3.8 A, max_shift 1 A, every step)
 Reported per case: median / min / max ms per step over --repeats rounds, and for the final designs of the last round (same seeds for
 every case) the clash / bond statistics of diffab_guidance_energy over the pairs with a generated residue.  Prints one JSON document
 (and writes it with --json).  --cases runs a subset (a kernel trace per case:
@@ -98,12 +98,10 @@ def main():
                    "sample_init")
 
     def loop(gs, t_start, t_stop):
-        a = (C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(res),
-             _hip.ptr(pair), R, None, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0, None, None, None)
-        if gs is None:
-            _hip.check(lib.diffab_sample_loop_steps(*a, _hip.stream_ptr()), "diffab_sample_loop_steps")
-        else:
-            _hip.check(lib.diffab_sample_loop_guided(*a, C.byref(gs), _hip.stream_ptr()), "diffab_sample_loop_guided")
+        opt = None if gs is None else C.byref(_hip.SampleOptions(guidance=gs))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws),
+                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Design throughput of fewer-step reverse sampling (diffab_sample_loop_steps), ROWS patches, K = 128, benchmark model, one context per
+"""Design throughput of fewer-step reverse sampling (diffab_sample_options.steps), ROWS patches, K = 128, benchmark model, one context per
 row (256 rows fill the chip: the patch-resident module launch, what bench.py times).
 
 Cases, alternating inside one process (the order reversed every other round), each a --warmup-step untimed call of the ordinary loop
 and then ONE call of the whole reverse run from t = T on the initial state, bracketed by hipEvents after a device synchronise (bench.py's
 timed block):
   off    diffab_sample_loop, every step T .. 1
-  n100   diffab_sample_loop_steps listing every step (bitwise "off")
-  n50, n20, n10   diffab_sample_loop_steps with steps = n (DiffAb.sample(steps=n)'s even list and jump coefficients)
+  n100   diffab_sample_loop_ex, option `steps`, listing every step (bitwise "off")
+  n50, n20, n10   the same with steps = n (DiffAb.sample(steps=n)'s even list and jump coefficients)
 The step plans, jump coefficients and reverse IGSO3 tables are built once, outside the timed block.  Reported per case: median / min /
 max ms per call and per executed step over --repeats rounds, designs per second (rows / call time), the speed-up over "off", and
 whether n100 ended on the state of "off", bitwise.  Prints one JSON document (and writes it with --json).  --cases runs a subset (a
@@ -104,15 +104,14 @@ def main():
                    "sample_init")
 
     def loop(n, t_stop=0):
-        state = (_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair))
         if n == "off":
-            _hip.check(lib.diffab_sample_loop(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab0), *state, _hip.ptr(gm), seed, 0,
-                                              T, t_stop, _hip.ptr(ws), ws.numel(), 0, _hip.stream_ptr()), "diffab_sample_loop")
+            tab, opt = tab0, None
         else:
             st, tab = plans[n][:2]
-            _hip.check(lib.diffab_sample_loop_steps(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), *state, R, None,
-                                                    _hip.ptr(gm), seed, 0, T, 0, _hip.ptr(ws), ws.numel(), 0, None, None, C.byref(st),
-                                                    _hip.stream_ptr()), "diffab_sample_loop_steps")
+            t_stop, opt = 0, C.byref(_hip.SampleOptions(steps=st))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, T, t_stop, _hip.ptr(ws),
+                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 

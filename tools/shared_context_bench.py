@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Reverse-sampler ms/step for ROWS = B N designs drawn from B shared contexts (diffab_sample_loop_shared), K = 128, benchmark model.
+"""Reverse-sampler ms/step for ROWS = B N designs drawn from B shared contexts (diffab_sample_options.ctx_of_row), K = 128, benchmark model.
 
 The variants alternate inside one process: for each of --repeats rounds, every N of --ns runs a --warmup-step untimed call, then ONE
 call of --steps steps from t = T on the re-initialised state, bracketed by hipEvents after a device synchronise (bench.py's warm-up and
@@ -80,12 +80,10 @@ def main():
 
     def call(v, n, t_start, t_stop):
         common = (_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(v["res"]), _hip.ptr(v["pair"]))
-        tail = (seed, 0, t_start, t_stop, _hip.ptr(v["ws"]), v["ws"].numel(), 0, _hip.stream_ptr())
-        head = (C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab))
-        if n == 1:
-            _hip.check(lib.diffab_sample_loop(*head, *common, _hip.ptr(gm), *tail), "diffab_sample_loop")
-        else:
-            _hip.check(lib.diffab_sample_loop_shared(*head, *common, v["n_ctx"], v["map"], _hip.ptr(gm), *tail), "diffab_sample_loop_shared")
+        opt = None if n == 1 else C.byref(_hip.SampleOptions(n_ctx=v["n_ctx"], ctx_of_row=v["map"]))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), *common, _hip.ptr(gm), seed, 0,
+                                             t_start, t_stop, _hip.ptr(v["ws"]), v["ws"].numel(), 0, opt, _hip.stream_ptr()),
+                   "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for rep in range(args.repeats):
@@ -105,7 +103,7 @@ def main():
             v["runs"].append(ev0.elapsed_time(ev1) / args.steps)
             if not (torch.isfinite(x).all() and torch.isfinite(O).all()):
                 raise SystemExit(f"N = {n}: non-finite state")
-    out = {"what": "reverse-sampler ms per step, ROWS designs from ROWS / N shared contexts (diffab_sample_loop_shared; N = 1: "
+    out = {"what": "reverse-sampler ms per step, ROWS designs from ROWS / N shared contexts (diffab_sample_options.ctx_of_row; N = 1: "
                    "diffab_sample_loop)", "rows": R, "k": K, "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
            "device": torch.cuda.get_device_name(), "variants": []}
     ctx_row_bytes = K * dims["D"] * 4 + K * K * dims["C"] * 4

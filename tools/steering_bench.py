@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Reverse-sampler cost of particle steering (diffab_sample_loop_steered), ROWS state rows in groups of --group, K = 128, benchmark
+"""Reverse-sampler cost of particle steering (diffab_sample_options.steering), ROWS state rows in groups of --group, K = 128, benchmark
 model, one context per row (256 rows fill the chip: the patch-resident module launch, what bench.py times; the rows of a group share
 their generation mask and tables, which is all the kernels read).
 
 Cases, alternating inside one process (the order reversed every other round), each a --warmup-step untimed call and then ONE call of
 --steps steps from t = T on the re-initialised state, bracketed by hipEvents after a device synchronise (bench.py's timed block):
-  free     diffab_sample_loop_steps, unsteered
-  zero     diffab_sample_loop_steered with strength 0, ess_threshold 1 (the kernels run every step, nothing resamples; bitwise the free
+  free     diffab_sample_loop_ex without options, unsteered
+  zero     diffab_sample_loop_ex, option `steering`, with strength 0, ess_threshold 1 (the kernels run every step, nothing resamples; bitwise the free
            result - checked)
-  steered  diffab_sample_loop_steered with strength 1, ess_threshold 2: every group resamples at every step but the last
+  steered  the same with strength 1, ess_threshold 2: every group resamples at every step but the last
 Reported per case: median / min / max ms per step over --repeats rounds; for `steered` the number of resampling steps and of surviving
 initial rows.  Prints one JSON document (and writes it with --json).  --cases runs a subset (a kernel trace per case:
 rocprofv3 --kernel-trace --stats -- python tools/steering_bench.py --cases steered --repeats 1).
@@ -105,12 +105,10 @@ def main():
                    "sample_init")
 
     def loop(gs, t_start, t_stop):
-        a = (C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(res),
-             _hip.ptr(pair), R, None, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0, None, None, None)
-        if gs is None:
-            _hip.check(lib.diffab_sample_loop_steps(*a, _hip.stream_ptr()), "diffab_sample_loop_steps")
-        else:
-            _hip.check(lib.diffab_sample_loop_steered(*a, None, None, C.byref(gs), _hip.stream_ptr()), "diffab_sample_loop_steered")
+        opt = None if gs is None else C.byref(_hip.SampleOptions(steering=gs))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws),
+                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Reverse-sampler cost of noise scales and sequence temperature (diffab_sample_loop_tempered), ROWS patches, K = 128, benchmark model, one
+"""Reverse-sampler cost of noise scales and sequence temperature (diffab_sample_options.temperature), ROWS patches, K = 128, benchmark model, one
 context per row (256 rows fill the chip: the patch-resident module launch, what bench.py times).
 
 Cases, alternating inside one process (the order reversed every other round), each a --warmup-step untimed call and then ONE call of
 --steps steps from t = T on the re-initialised state, bracketed by hipEvents after a device synchronise (bench.py's timed block):
-  free     diffab_sample_loop_steps, untempered
-  ones     diffab_sample_loop_tempered with every pointer set and every value 1 (rot_row k (T + 1) over a one-scale stack: the kernel
+  free     diffab_sample_loop_ex without options, untempered
+  ones     diffab_sample_loop_ex, option `temperature`, with every pointer set and every value 1 (rot_row k (T + 1) over a one-scale stack: the kernel
            reads the values; bitwise the free result - checked)
-  sweep    diffab_sample_loop_tempered with a mixed per-row sweep: lambda_x in {0.5, 0.75, 1, 1.25}, lambda_O over 8 values (an 8-scale
+  sweep    the same with a mixed per-row sweep: lambda_x in {0.5, 0.75, 1, 1.25}, lambda_O over 8 values (an 8-scale
            stacked table) and 0, tau in {0, 0.1, 0.3, 0.5, 1, 2}, cycled over the rows
 Reported per case: median / min / max ms per step over --repeats rounds; and, once, the build time of the stacked IGSO3 tables (outside
 the timed steps): 1, 8 and 16 scales at T = 100.  Prints one JSON document (and writes it with --json).  --cases runs a subset (a kernel
@@ -120,12 +120,10 @@ def main():
 
     def loop(n, t_start, t_stop):
         tab = tabs[n].struct()
-        a = (C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(res),
-             _hip.ptr(pair), R, None, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0, None, None, None)
-        if structs[n] is None:
-            _hip.check(lib.diffab_sample_loop_steps(*a, _hip.stream_ptr()), "diffab_sample_loop_steps")
-        else:
-            _hip.check(lib.diffab_sample_loop_tempered(*a, None, C.byref(structs[n]), _hip.stream_ptr()), "diffab_sample_loop_tempered")
+        opt = None if structs[n] is None else C.byref(_hip.SampleOptions(temperature=structs[n]))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws),
+                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 

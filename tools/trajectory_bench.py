@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""Reverse-sampler cost of trajectory recording (diffab_sample_loop_rec), ROWS patches, K = 128, benchmark model, one context per row
+"""Reverse-sampler cost of trajectory recording (diffab_sample_options.record), ROWS patches, K = 128, benchmark model, one context per row
 (256 rows fill the chip: the patch-resident module launch, what bench.py times).
 
 Cases, alternating inside one process (the order reversed every other round), each a --warmup-step untimed call and then ONE call of
 --steps steps from t = T on the initial state, bracketed by hipEvents after a device synchronise (bench.py's timed block):
   off         diffab_sample_loop (no record)
-  state       diffab_sample_loop_rec, the state at every step
-  state_pred  diffab_sample_loop_rec, the state and the predictions at every step
-  pred_10     diffab_sample_loop_rec, the state and the predictions at every 10th step
+  state       diffab_sample_loop_ex, option `record`: the state at every step
+  state_pred  the same, the state and the predictions at every step
+  pred_10     the same, the state and the predictions at every 10th step
 The record buffers are allocated once, outside the timed block.  Reported per case: median / min / max ms per step over --repeats
 rounds, and whether every case ended on the state of "off", bitwise.  Prints one JSON document (and writes it with --json).
 --cases runs a subset (a kernel trace per case: rocprofv3 --kernel-trace --stats -- python tools/trajectory_bench.py --cases off).
@@ -115,14 +115,10 @@ def main():
                    "sample_init")
 
     def loop(rec, t_start, t_stop):
-        common = (C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(res),
-                  _hip.ptr(pair))
-        if rec is None:
-            _hip.check(lib.diffab_sample_loop(*common, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0, _hip.stream_ptr()),
-                       "diffab_sample_loop")
-        else:
-            _hip.check(lib.diffab_sample_loop_rec(*common, R, None, _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws), ws.numel(), 0,
-                                                  None, C.byref(rec[0]), _hip.stream_ptr()), "diffab_sample_loop_rec")
+        opt = None if rec is None else C.byref(_hip.SampleOptions(record=rec[0]))
+        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
+                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws),
+                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
