@@ -207,6 +207,13 @@ SYMBOLS = {
     "diffab_metrics_pairwise": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp, _fp, _fp, _sz, _fp]),
     # (dist, score (nullable), candidates (nullable), G, N, m, index, min_dist, count, stream)
     "diffab_metrics_select_diverse": (C.c_int, [_fp, _fp, _fp, _i32, _i32, _i32, _fp, _fp, _fp, _fp]),
+    # (points, generation_mask, residue_mask (nullable), chain, residue_idx, rows, group_size, K, bond_tolerance, phi, psi, omega, peptide_bond,
+    #  n_bonds, max_peptide_deviation, n_chain_break, n_cis, workspace, workspace_bytes, stream)
+    "diffab_metrics_backbone": (C.c_int, [_fp] * 5 + [_i32] * 3 + [C.c_float] + [_fp] * 9 + [_sz, _fp]),
+    # (points, valid, context_points, context_valid, generation_mask, residue_mask (nullable), antigen_mask (nullable), hotspot_mask (nullable),
+    #  chain, residue_idx, rows, group_size, K, P, A, clash_distance, contact_distance, n_clash, clash_score, min_distance, n_contact_pairs,
+    #  n_paratope, n_epitope, n_hotspot_contacted, n_hotspot, residue_clash, residue_contact, workspace, workspace_bytes, stream)
+    "diffab_metrics_contacts": (C.c_int, [_fp] * 10 + [_i32] * 5 + [C.c_float] * 2 + [_fp] * 11 + [_sz, _fp]),
     "diffab_orientation_loss": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp]),
     "diffab_orientation_loss_bwd": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "diffab_frames_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),

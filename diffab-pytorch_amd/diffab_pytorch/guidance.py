@@ -68,9 +68,9 @@ def residue_tables(who: str, chain_idx, residue_idx, residue_mask, n_rows: int, 
                              ("residue_mask", residue_mask, lambda: torch.ones(K, dtype=torch.bool))):
         t = default() if v is None else torch.as_tensor(v).detach().cpu()
         if t.is_floating_point() or t.is_complex() or (name != "residue_mask" and t.dtype == torch.bool):
-            raise ValueError(f"{who}: guidance needs an integer {name}" + (" (or bool)" if name == "residue_mask" else "") + f", got {t.dtype}")
+            raise ValueError(f"{who}: needs an integer {name}" + (" (or bool)" if name == "residue_mask" else "") + f", got {t.dtype}")
         if t.dim() not in (1, 2):
-            raise ValueError(f"{who}: {name} must be (K,) or (rows, K) for guidance, got {tuple(t.shape)}")
+            raise ValueError(f"{who}: {name} must be (K,) or (rows, K), got {tuple(t.shape)}")
         try:
             t = t.expand(n_rows, K)
         except RuntimeError:

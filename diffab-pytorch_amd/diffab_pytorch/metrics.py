@@ -2,27 +2,37 @@
 
 ``evaluate``        per design: amino-acid recovery, RMSD in the fixed framework and after superposition, whole row and per segment (CDR);
 ``pairwise``        per patch: the N x N RMSD and sequence-identity matrices of its N designs;
-``select_diverse``  greedy farthest-point choice of m designs per patch from such a matrix.
+``select_diverse``  greedy farthest-point choice of m designs per patch from such a matrix;
+``backbone``        per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
+``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen.
 
 Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` returns them - ``seq_idx`` (rows,K), ``translations``
 (rows,K,3), ``orientations`` (rows,K,3,3) with ``rows = G * group_size``, row ``g * group_size + r`` = design r of patch g - and the masks
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
-the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` in ``include/diffab_hip.h``; every number is computed
-by the HIP kernels of ``csrc/metrics_kernels.hip`` and there is no torch fallback.
+the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` in
+``include/diffab_hip.h``; every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip`` and ``csrc/geometry_kernels.hip``
+(the filters) and there is no torch fallback.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+import math
+from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import _hip
-from .io import backbone_from_frames
+from .guidance import residue_tables
+from .io import AA3, BACKBONE_ATOMS, backbone_from_frames
 
 MAX_GROUP = 4096  # DIFFAB_METRICS_MAX_GROUP: designs per patch
 MAX_K = 4096  # DIFFAB_METRICS_MAX_K
 MAX_SEGMENTS = 8  # DIFFAB_METRICS_MAX_SEGMENTS
 ATOMS = {"ca": None, "backbone": ("N", "CA", "C", "O")}
+MAX_CONTEXT_ATOMS = 32  # DIFFAB_METRICS_MAX_CONTEXT_ATOMS: atom slots per context residue
+CONTACTS_CHUNK_ATOMS = 1024  # DIFFAB_METRICS_CONTACTS_CHUNK_ATOMS: context atoms the contacts kernel stages in LDS per pass
+CONTACTS_CHUNK_RESIDUES = 64  # DIFFAB_METRICS_CONTACTS_CHUNK_RESIDUES: context residues per pass
+PEPTIDE_BOND = 1.329  # Angstrom, C(i) - N(i+1)
+GLY = AA3.index("GLY")
 
 
 def _is_int(v) -> bool:
@@ -192,3 +202,151 @@ def select_diverse(dist: torch.Tensor, m: int, *, score: Optional[torch.Tensor] 
     _hip.check(lib.diffab_metrics_select_diverse(_hip.ptr(d), _hip.ptr(sc), _hip.ptr(cand), G, N, m, _hip.ptr(index), _hip.ptr(min_dist),
                                                  _hip.ptr(count), _hip.stream_ptr()), "diffab_metrics_select_diverse")
     return {"index": index.to(out_dev), "min_dist": min_dist.to(out_dev), "count": count.to(out_dev)}
+
+
+# ------------------------------------------------------------------ design filters
+def _check_distance(who: str, name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"{who}: {name} must be a finite number >= 0, got {v!r}")
+    return float(v)
+
+
+def _check_patch_mask(who: str, name: str, m, G: int, K: int) -> None:
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.bool:
+        raise ValueError(f"{who}: {name} must be a bool tensor")
+    if tuple(m.shape) != (G, K):
+        raise ValueError(f"{who}: {name} is {tuple(m.shape)}, expected {(G, K)} (one row per patch)")
+
+
+def backbone_workspace_bytes(G: int, K: int) -> int:
+    """DIFFAB_METRICS_BACKBONE_WORKSPACE_BYTES of include/diffab_hip.h."""
+    return G * K * 8 + 1024
+
+
+def contacts_workspace_bytes(G: int, K: int, A: int) -> int:
+    """DIFFAB_METRICS_CONTACTS_WORKSPACE_BYTES of include/diffab_hip.h."""
+    return G * K * (A * 16 + 28) + G * 16 + 2048
+
+
+def backbone(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, chain_idx=None, residue_idx=None,
+             residue_mask: Optional[torch.Tensor] = None, group_size: int = 1, bond_tolerance: float = 0.25) -> Dict[str, torch.Tensor]:
+    """The backbone the frames of each design imply - N, CA, C of ``io.backbone_from_frames``, the atoms ``write_pdb`` writes - checked
+    where residues join.  Slots i and j are chain neighbours when ``chain_idx`` is equal, ``residue_idx[j] = residue_idx[i] + 1`` and both
+    are inside ``residue_mask`` (the bonded rule of guidance; ``chain_idx`` / ``residue_idx`` are (K,) or (G,K), default one chain and
+    ``arange(K)``).  Per residue (rows,K) fp32, NaN where the neighbour it needs does not exist: ``phi``, ``psi``, ``omega`` in radians
+    in (-pi, pi], IUPAC sign, and ``peptide_bond`` = |C_i - N_{i+1}| in Angstrom, stored at i.  Per row (rows,), over the bonds with at
+    least one generated end: ``n_bonds`` (int32), ``max_peptide_deviation`` = max |d - 1.329| (0 without a bond), ``n_chain_break`` =
+    bonds with |d - 1.329| > ``bond_tolerance``, ``n_cis`` = bonds with |omega| < pi/2.  fp64 from the fp32 points, rounded once.
+    One C-ABI call; results on the device of ``designs['seq_idx']``; ValueError naming the argument before any device work."""
+    who = "metrics.backbone()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    tol = _check_distance(who, "bond_tolerance", bond_tolerance)
+    chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    pts = _hip.dev_f32(backbone_from_frames(_hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"]), ("N", "CA", "C")))
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    chain, ridx = chain.to(dev), ridx.to(dev)
+    per_residue = [torch.empty(rows, K, dtype=torch.float32, device=dev) for _ in range(4)]
+    n_bonds, n_break, n_cis = (torch.empty(rows, dtype=torch.int32, device=dev) for _ in range(3))
+    worst = torch.empty(rows, dtype=torch.float32, device=dev)
+    nbytes = backbone_workspace_bytes(G, K)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_backbone(_hip.ptr(pts), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, tol,
+                                           *[_hip.ptr(t) for t in per_residue], _hip.ptr(n_bonds), _hip.ptr(worst), _hip.ptr(n_break),
+                                           _hip.ptr(n_cis), _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_backbone")
+    out = dict(zip(("phi", "psi", "omega", "peptide_bond"), per_residue))
+    out.update(n_bonds=n_bonds, max_peptide_deviation=worst, n_chain_break=n_break, n_cis=n_cis)
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+def _frame_atoms(seq: torch.Tensor, x: torch.Tensor, O: torch.Tensor, atoms: Sequence[str]):
+    """The frame atoms of residues (…,K) and their validity bits (uint8): every atom, without CB where the token is Gly."""
+    pts = _hip.dev_f32(backbone_from_frames(x, O, atoms))
+    bits = torch.full(seq.shape, (1 << len(atoms)) - 1, dtype=torch.uint8, device=seq.device)
+    if "CB" in atoms:
+        bits = torch.where(seq == GLY, bits & ~torch.tensor(1 << atoms.index("CB"), dtype=torch.uint8, device=seq.device), bits)
+    return pts, bits.contiguous()
+
+
+def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
+             antigen_mask: Optional[torch.Tensor] = None, hotspot_mask: Optional[torch.Tensor] = None, chain_idx=None, residue_idx=None,
+             residue_mask: Optional[torch.Tensor] = None, group_size: int = 1, clash_distance: float = 3.0, contact_distance: float = 5.0,
+             atoms: Sequence[str] = BACKBONE_ATOMS) -> Dict[str, torch.Tensor]:
+    """Atom clashes of the generated residues of each design, and their contacts with the antigen.  A generated residue has the frame
+    atoms ``atoms`` (default N, CA, C, O, CB; no CB where the design's token is Gly) of its own row; a non-generated residue has the
+    patch's real atoms, ``context['xyz']`` (G,K,A,3) where ``context['atom_mask']`` (G,K,A; bool or 0 / 1) is set, A <= 32 - ``patch.gather``'s
+    output and a batch passed to ``sample()`` carry both - shared by the designs of the patch.  Without ``context`` the non-generated
+    residues take the frame atoms of the first row of their group.  Eligible pairs: an atom of generated residue i and an atom of
+    residue j != i, both inside ``residue_mask``, j not a chain neighbour of i (``backbone``'s rule); two generated residues count once.
+
+    Per row (rows,): ``n_clash`` (int32) pairs closer than ``clash_distance``, ``clash_score`` = sum (clash_distance - d)^2 over them,
+    ``min_distance`` (+inf without a pair).  With ``antigen_mask`` (G,K) a generated residue and a non-generated antigen residue are in
+    contact when any of their atom pairs is closer than ``contact_distance``: ``n_contact_pairs``, ``n_paratope``, ``n_epitope``; with
+    ``hotspot_mask`` (a subset of the antigen) ``n_hotspot_contacted`` and ``n_hotspot``.  Per residue (rows,K) int32, ready as
+    ``b_factor`` of ``io.write_pdb``: ``residue_clash`` (clashing atom pairs the residue is part of, context residues included) and
+    ``residue_contact`` (contact partners, on both sides; with ``antigen_mask``).  The counts are exact functions of the fp32 points
+    (``include/diffab_hip.h``).  One C-ABI call; results on the device of ``designs['seq_idx']``; ValueError before any device work."""
+    who = "metrics.contacts()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    if isinstance(atoms, str) or not isinstance(atoms, Sequence) or not 1 <= len(atoms) <= len(BACKBONE_ATOMS) \
+            or any(a not in BACKBONE_ATOMS for a in atoms) or len(set(atoms)) != len(atoms):
+        raise ValueError(f"{who}: atoms must be a sequence of distinct names from {BACKBONE_ATOMS}, got {atoms!r}")
+    atoms = tuple(atoms)
+    clash = _check_distance(who, "clash_distance", clash_distance)
+    contact = _check_distance(who, "contact_distance", contact_distance)
+    if antigen_mask is not None:
+        _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    if hotspot_mask is not None:
+        if antigen_mask is None:
+            raise ValueError(f"{who}: hotspot_mask needs an antigen_mask")
+        _check_patch_mask(who, "hotspot_mask", hotspot_mask, G, K)
+    if context is not None:
+        if not isinstance(context, dict) or not isinstance(context.get("xyz"), torch.Tensor) or not isinstance(context.get("atom_mask"), torch.Tensor):
+            raise ValueError(f"{who}: context must be a dict with xyz (G,K,A,3) and atom_mask (G,K,A)")
+        xyz, am = context["xyz"], context["atom_mask"]
+        if not xyz.is_floating_point() or xyz.dim() != 4 or tuple(xyz.shape[:2]) != (G, K) or xyz.shape[3] != 3:
+            raise ValueError(f"{who}: context['xyz'] is {tuple(xyz.shape)} {xyz.dtype}, expected a float tensor {(G, K, 'A', 3)}")
+        A = int(xyz.shape[2])
+        if A < 1 or A > MAX_CONTEXT_ATOMS:
+            raise ValueError(f"{who}: context['xyz'] has A = {A} atoms per residue, outside [1, {MAX_CONTEXT_ATOMS}]")
+        if am.is_complex() or tuple(am.shape) != (G, K, A):  # (bool, or the reference batch's 0 / 1 numbers)
+            raise ValueError(f"{who}: context['atom_mask'] is {tuple(am.shape)} {am.dtype}, expected a mask {(G, K, A)}")
+    chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    P = len(atoms)
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    pts, valid = _frame_atoms(seq, x, O, atoms)
+    if context is None:
+        first = torch.arange(G, device=dev) * group_size
+        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
+        A, cvalid = P, cbits.to(torch.int32).contiguous()
+    else:
+        cpts = _hip.dev_f32(context["xyz"])
+        word = (_hip.dev_mask(context["atom_mask"]).to(torch.int64) << torch.arange(A, device=dev)).sum(-1)
+        cvalid = torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32).contiguous()  # the 32 bits of a uint32
+    gm = _hip.dev_mask(generation_mask)
+    rm, ag, hs = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask, hotspot_mask))
+    chain, ridx = chain.to(dev), ridx.to(dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = {"n_clash": i32(rows), "clash_score": torch.empty(rows, dtype=torch.float32, device=dev),
+           "min_distance": torch.empty(rows, dtype=torch.float32, device=dev)}
+    if ag is not None:
+        out.update(n_contact_pairs=i32(rows), n_paratope=i32(rows), n_epitope=i32(rows))
+    if hs is not None:
+        out.update(n_hotspot_contacted=i32(rows), n_hotspot=i32(rows))
+    out["residue_clash"] = i32(rows, K)
+    if ag is not None:
+        out["residue_contact"] = i32(rows, K)
+    nbytes = contacts_workspace_bytes(G, K, A)
+    ws = _hip.workspace(nbytes)
+    order = ("n_clash", "clash_score", "min_distance", "n_contact_pairs", "n_paratope", "n_epitope", "n_hotspot_contacted", "n_hotspot",
+             "residue_clash", "residue_contact")
+    _hip.check(lib.diffab_metrics_contacts(_hip.ptr(pts), _hip.ptr(valid), _hip.ptr(cpts), _hip.ptr(cvalid), _hip.ptr(gm), _hip.ptr(rm),
+                                           _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, P, A, clash, contact,
+                                           *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
+               "diffab_metrics_contacts")
+    return {k: v.to(out_dev) for k, v in out.items()}

@@ -544,6 +544,68 @@ int diffab_metrics_pairwise(const int64_t* seq_idx, const float* points, const u
 int diffab_metrics_select_diverse(const float* dist, const float* score, const uint8_t* candidates, int32_t G, int32_t N, int32_t m,
                                   int64_t* index, float* min_dist, int32_t* count, void* stream);
 
+/* Design filters: is a design a possible protein, and does it touch the antigen.  Rows, groups and masks as in
+ * "Common layout" above (rows = G * group_size, masks (G,K), residue_mask NULL = all present).  Both entries also take the patch's
+ * chain (G,K) int32 and residue_idx (G,K) int32.  Slots i and j of a patch are CHAIN NEIGHBOURS, j after i, when chain[i] == chain[j],
+ * residue_idx[j] == residue_idx[i] + 1 and both are inside residue_mask (the bonded rule of diffab_sample_guidance; j need not be i + 1,
+ * and a gap in residue_idx is a deleted residue: no bond).  Where several slots qualify, the successor (predecessor) of a slot is the
+ * lowest one.  Limits, DIFFAB_ERR_ARG with the shape and null-pointer checks before anything is enqueued: rows >= 0 a multiple of
+ * group_size, 1 <= group_size <= DIFFAB_METRICS_MAX_GROUP, 1 <= K <= DIFFAB_METRICS_MAX_K, finite distances >= 0, a workspace that is
+ * NULL or not 16-byte aligned (too small: DIFFAB_ERR_WORKSPACE).  rows = 0 succeeds without looking at a pointer.  The entries see
+ * points and validity bits only, never orientations or tokens.
+ *
+ * diffab_metrics_backbone: points (rows,K,3,3) fp32 = N, CA, C of every residue of every row.  With p / s the predecessor / successor of
+ * slot i, per residue (rows,K) fp32, NaN where the neighbour does not exist (or i is outside residue_mask):
+ *   phi   = dihedral(C_p, N_i, CA_i, C_i)      psi = dihedral(N_i, CA_i, C_i, N_s)      omega = dihedral(CA_i, C_i, N_s, CA_s)
+ *   peptide_bond = |C_i - N_s| in Angstrom, stored at i.
+ * dihedral(p0,p1,p2,p3) = atan2(|b2| b1.(b2 x b3), (b1 x b2).(b2 x b3)), b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2: radians in (-pi, pi],
+ * IUPAC sign (-pi is returned as pi).  Everything in fp64 from the fp32 points (differences, cross products, atan2, the root), rounded
+ * once to fp32.  Per row (rows), over the bonds i -> s with generation_mask set on at least one end:
+ *   n_bonds (int32); max_peptide_deviation = max |d - 1.329| (0 without a bond); n_chain_break = bonds with |d - 1.329| > bond_tolerance;
+ *   n_cis = bonds with |omega| < pi/2 - the comparisons on the fp64 values, bond_tolerance widened to fp64.
+ * One wave per row: integer sums and a maximum, so a row's numbers do not depend on the other rows.  Two launches (the neighbour table
+ * of every patch, then the rows).  workspace: DIFFAB_METRICS_BACKBONE_WORKSPACE_BYTES(G, K) bytes. */
+#define DIFFAB_METRICS_BACKBONE_WORKSPACE_BYTES(G, K) ((size_t)(G) * (size_t)(K) * 8 + 1024)
+int diffab_metrics_backbone(const float* points, const uint8_t* generation_mask, const uint8_t* residue_mask, const int32_t* chain,
+                            const int32_t* residue_idx, int32_t rows, int32_t group_size, int32_t K, float bond_tolerance, float* phi,
+                            float* psi, float* omega, float* peptide_bond, int32_t* n_bonds, float* max_peptide_deviation,
+                            int32_t* n_chain_break, int32_t* n_cis, void* workspace, size_t workspace_bytes, void* stream);
+/* diffab_metrics_contacts: atom clashes of the generated residues and their contacts with the antigen.
+ * Atoms.  A generated residue (generation_mask and residue_mask) of row r has the atoms points[r,k,a] (rows,K,P,3), 1 <= P <=
+ * DIFFAB_METRICS_MAX_POINTS, whose bit a is set in valid[r,k] (rows,K) uint8.  A non-generated residue inside residue_mask has the atoms
+ * context_points[g,k,a] (G,K,A,3), 1 <= A <= DIFFAB_METRICS_MAX_CONTEXT_ATOMS, whose bit a is set in context_valid[g,k] (G,K) uint32:
+ * they belong to the patch and are shared by its designs.  Bits at or above P / A are ignored.
+ * Eligible pairs: (atom a of generated residue i, atom b of residue j != i) with both residues inside residue_mask and j no chain
+ * neighbour of i in either direction; when both residues are generated the unordered residue pair counts once.
+ * d2 = (dx*dx + dy*dy) + dz*dz in fp32 with dx, dy, dz one rounded subtraction each, no contraction; every comparison is d2 against the
+ * fp32 product clash_distance * clash_distance (contact_distance likewise).  Per row (rows):
+ *   n_clash (int32) = eligible pairs with d2 < clash^2;  clash_score (fp32) = sum over them of (clash - d)^2, d = the fp32 root of d2,
+ *   the terms and the sum in fp64 in a fixed order of the row, rounded once;  min_distance = the fp32 root of the smallest eligible d2,
+ *   +inf without a pair.
+ * With antigen_mask (G,K): generated residue i and a non-generated residue j inside antigen_mask are IN CONTACT when one of their
+ * eligible atom pairs has d2 < contact^2.  n_contact_pairs = residue pairs in contact, n_paratope = generated residues with a contact,
+ * n_epitope = antigen residues with one (each (rows) int32).  With hotspot_mask (G,K; needs antigen_mask): n_hotspot = non-generated
+ * residues inside residue_mask, antigen_mask and hotspot_mask, n_hotspot_contacted = those of them with a contact.
+ * Per residue (rows,K) int32: residue_clash = clashing atom pairs the residue takes part in (both ends count, context residues too),
+ * residue_contact = its contact partners (both sides; only written with an antigen_mask).  Outputs that go with a NULL mask may be NULL.
+ * Two launches and up to two memsets: the patch's valid context atoms are compacted once into the workspace; then one work-group per
+ * (patch, 64 designs), lane = design, stages them through LDS in chunks of whole residues - at most
+ * DIFFAB_METRICS_CONTACTS_CHUNK_RESIDUES residues and DIFFAB_METRICS_CONTACTS_CHUNK_ATOMS atoms, neither a limit on K * A - and keeps
+ * every count on chip (registers, integer adds on LDS).  No float atomics.  A row's numbers do not depend on the other rows.
+ * workspace: DIFFAB_METRICS_CONTACTS_WORKSPACE_BYTES(G, K, A) bytes. */
+#define DIFFAB_METRICS_MAX_CONTEXT_ATOMS 32
+#define DIFFAB_METRICS_CONTACTS_CHUNK_ATOMS 1024
+#define DIFFAB_METRICS_CONTACTS_CHUNK_RESIDUES 64
+#define DIFFAB_METRICS_CONTACTS_WORKSPACE_BYTES(G, K, A) \
+  ((size_t)(G) * (size_t)(K) * ((size_t)(A) * 16 + 28) + (size_t)(G) * 16 + 2048)
+int diffab_metrics_contacts(const float* points, const uint8_t* valid, const float* context_points, const uint32_t* context_valid,
+                            const uint8_t* generation_mask, const uint8_t* residue_mask, const uint8_t* antigen_mask,
+                            const uint8_t* hotspot_mask, const int32_t* chain, const int32_t* residue_idx, int32_t rows, int32_t group_size,
+                            int32_t K, int32_t P, int32_t A, float clash_distance, float contact_distance, int32_t* n_clash,
+                            float* clash_score, float* min_distance, int32_t* n_contact_pairs, int32_t* n_paratope, int32_t* n_epitope,
+                            int32_t* n_hotspot_contacted, int32_t* n_hotspot, int32_t* residue_clash, int32_t* residue_contact,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the two context encoders (training through encode_context, diffab_pytorch.py:843-854 under autograd).
  * d_out is the gradient w.r.t. the module output; parameter gradients ACCUMULATE (+=) into the buffers of `g`, which has the
  * layout of the weight struct (the caller zero-fills them).  Inputs other than parameters take no gradient.  Nothing is taped:
