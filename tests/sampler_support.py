@@ -1,0 +1,268 @@
+"""What the sampler's test files share: the device fixture, models and inputs, the bitwise comparison, the Philox noise of one step and
+the oracle's reverse step built on it (GPU side); the stand-in model, the refused library and the zero-state call (host side); and the
+padded-patch / gradient helpers of the ragged-K, backward-path and any-dims tests.
+
+Not a test module and not a conftest: test files import what they need by name.  Importing it loads no library and touches no device
+(the host tests import it on machines without a GPU) - _hip.lib(), .cuda() and DiffAb are taken inside the functions that need them.
+A new sampler feature's test file starts from here and keeps per file only the fixtures whose weight seeds are its own.
+"""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import diffab_oracle as orc
+from conftest import maxrel
+from diffab_pytorch import _hip, synthetic as syn
+
+STATE = ("seq_idx", "translations", "orientations", "generation_mask")
+CTX = ("res_context_emb", "pair_context_emb")
+ARGS = ("seq_idx", "translations", "orientations", "res_context_emb", "pair_context_emb")
+UNK = 20
+TOL = 1e-4   # forward outputs (tests/test_gpu_parity.py)
+GTOL = 2e-4  # gradients (the training-step goldens' bar)
+PATCH_LENGTH_DIMS = dict(syn.BENCH_DIMS, NL=2)
+FLAGS = [0, _hip.FLAG_FORCE_GENERIC, _hip.FLAG_FP32_GEMM, _hip.FLAG_PAIR_PLANES]
+FLAG_IDS = ["dispatch", "generic", "fp32gemm", "pairplanes"]
+OUTS = ("res_emb", "aa_logits", "translations_eps", "orientations_t0", "seq_posterior")
+STREAMS_REVERSE = (orc.STREAM_SEQ, orc.STREAM_TRANS, orc.STREAM_AXIS, orc.STREAM_ANGLE)
+STREAMS_OPT = (7, 8, 9, 10)  # STREAM_OPT_SEQ, _TRANS, _AXIS, _ANGLE of csrc/philox.h: the forward-noised start and the scorer's draws
+
+
+# ====================================================================== GPU side
+@pytest.fixture(scope="module")
+def hip():
+    lib = _hip.lib()  # raises HipUnavailable when there is no gfx950 / no library: never a silent fallback
+    assert lib.diffab_device_ok() == 1
+    return lib
+
+
+def make_model(dims, seed, T=100):
+    from diffab_pytorch import DiffAb
+
+    torch.manual_seed(0)
+    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
+    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
+    return model
+
+
+def bench_model(T_steps, NL=None):
+    d = dict(syn.BENCH_DIMS)
+    if NL is not None:
+        d["NL"] = NL
+    return d, make_model(d, 0, T=T_steps)
+
+
+def unit_model(NL=2, seed=17):
+    """(dims, model, oracle state dict) at the unit dims.  The boundary modules keep whatever the global generator gives them: unlike
+    make_model this does not reseed it, and the callers' later draws depend on that."""
+    from diffab_pytorch import DiffAb
+
+    dims = dict(syn.UNIT_DIMS, NL=NL)
+    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
+    sd = syn.denoiser_state_dict(dims, seed=seed, prefix="")
+    model.denoiser.load_state_dict(sd)
+    return dims, model, {"denoiser." + k: v for k, v in sd.items()}
+
+
+def patches(B, K, dims, seed, chains=False, collapse=True):
+    """syn.patches on the device.  chains=True (the guidance and steering tests) adds two chains with a gap in residue_idx and a few
+    padded context residues, and with `collapse` puts the generated residues within ~1 A of one point (clashes and broken bonds for the
+    potential to act on)."""
+    inp = {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
+    if not chains:
+        return inp
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    gm = inp["generation_mask"]
+    if collapse:
+        x = inp["translations"]
+        centre = x[torch.arange(B), gm.float().argmax(1)][:, None, :]
+        x[:] = torch.where(gm[..., None], centre + torch.randn(x.shape, device="cuda", generator=g), x)
+    half = K // 2
+    inp["chain_idx"] = (torch.arange(K, device="cuda") >= half).long().expand(B, K).contiguous()
+    inp["residue_idx"] = (torch.arange(K, device="cuda") + 7 * (torch.arange(K, device="cuda") >= half)).expand(B, K).contiguous()
+    rm = torch.rand(B, K, device="cuda", generator=g) > 0.1
+    inp["residue_mask"] = rm | gm
+    return inp
+
+
+def device_patches(B, K, dims, seed):
+    """Seeded synthetic patches of SURVEY 8(d)'s shapes, generated on the device (the 8.6 GB pair context of config 5 would take
+    minutes through the host generator): N(0,1) contexts, N(0,10^2) A translations, uniform rotations, one CDR-like segment
+    of 5..20 generated residues per patch."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    out = {
+        "res_context_emb": torch.randn(B, K, dims["D"], device="cuda", generator=g),
+        "pair_context_emb": torch.randn(B, K, K, dims["C"], device="cuda", generator=g),
+        "translations": 10 * torch.randn(B, K, 3, device="cuda", generator=g),
+        "seq_idx": torch.randint(0, 20, (B, K), device="cuda", generator=g),
+    }
+    q = torch.randn(B, K, 4, device="cuda", generator=g)
+    out["orientations"] = orc.uniform_rotation_from_normals(q.cpu()).cuda()
+    start = torch.randint(0, K - 20, (B, 1), device="cuda", generator=g)
+    length = torch.randint(5, 21, (B, 1), device="cuda", generator=g)
+    pos = torch.arange(K, device="cuda")[None]
+    out["generation_mask"] = (pos >= start) & (pos < start + length)
+    return out
+
+
+def sample(model, inp, **kw):
+    tabs = {k: inp[k] for k in ("chain_idx", "residue_idx", "residue_mask") if k in inp}
+    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
+                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **tabs, **kw)
+
+
+def score(model, inp, **kw):
+    return model.score(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
+                       residue_mask=inp.get("residue_mask"), res_context_emb=inp.get("res_context_emb"),
+                       pair_context_emb=inp.get("pair_context_emb"), **kw)
+
+
+def rows(inp, index):
+    """Every per-patch input at the given rows (a LongTensor on the device): the replicated batch of the shared-context specification."""
+    return {k: v.index_select(0, index) for k, v in inp.items()}
+
+
+def assert_bitwise(got, want, what=""):
+    assert set(got) == set(want), (what, set(got) ^ set(want))
+    for k in want:
+        if isinstance(want[k], dict):  # the "trajectory" / "steering" records
+            assert_bitwise(got[k], want[k], (what, k))
+            continue
+        assert got[k].shape == want[k].shape, (what, k)
+        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
+
+
+def lanes(first_patch, B, K):
+    """(patch, residue) int64 (B, K): the Philox counter words of the rows first_patch .. first_patch + B of the global batch."""
+    patch = (first_patch + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
+    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
+    return patch, res
+
+
+def step_noise(seed, first_patch, B, K, t, cdf_row, sigma, streams=STREAMS_REVERSE, draw=0):
+    """Which Philox lane feeds which draw of one step, stated once: (z, rotvec, us) on the (first_patch, B, K) grid at counter step t.
+    z (B, K, 3): normals 0..2 of the translation stream (the forward process calls it eps); rotvec (B, K, 3): the IGSO3 draw about
+    normals 0..2 of the axis stream, its angle from uniforms 0, 1 (bin of the (n_bins,) CDF row, position in the bin) and normal 2 (the
+    Gaussian branch) of the angle stream, at the 0-d sigma; us (B, K): uniform 0 of the sequence stream.
+    streams = (seq, trans, axis, angle): the reverse loop's by default, STREAMS_OPT with the scorer's draw index m as `draw` (m << 16)."""
+    patch, res = lanes(first_patch, B, K)
+    s_seq, s_trans, s_axis, s_angle = (s + (draw << 16) for s in streams)
+    z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, s_trans)[:3], -1))
+    ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, s_axis)[:3], -1))
+    ua = orc.philox_uniform4(seed, patch, res, t, s_angle)
+    na = orc.philox_normal4(seed, patch, res, t, s_angle)
+    us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, s_seq)[0])
+    th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row[None, None, :].expand(B, K, -1), torch.from_numpy(ua[0])),
+                                     torch.from_numpy(ua[1]))
+    th_g = orc.igso3_theta_from_gaussian(sigma.expand(B, K), torch.from_numpy(na[2]))
+    return z, orc.igso3_rotvec(ax, th_h, th_g, sigma.expand(B)), us
+
+
+def oracle_reverse_step(sd, inp, gm, rev, sched, seed, first_patch, t, NL, H):
+    """The oracle's reverse step t -> t-1 on the sampler's Philox lanes, teacher-forced: (s1, x1, O1, den, us, edge) from the host inputs
+    `inp`, the oracle state dict `sd` and the model's reverse table `rev`.  edge (B, K) is the distance of every sequence draw's uniform
+    from the nearest edge of the oracle posterior's CDF (a draw can flip only on an edge)."""
+    B, K = inp["seq_idx"].shape
+    z, rotvec, us = step_noise(seed, first_patch, B, K, t, rev._cdf[t].cpu(), sched["beta"].sqrt()[t])
+    den = orc.denoiser(sd, *[inp[k] for k in ARGS], sched["beta"][t].expand(B), NL, H)
+    s1, x1, O1 = orc.reverse_update(t, inp["seq_idx"], inp["translations"], inp["orientations"], den, gm, sched, z, rotvec, us)
+    edge = (den["seq_posterior"].double().cumsum(-1) - us.double()[..., None]).abs().min(dim=-1).values
+    return s1, x1, O1, den, us, edge
+
+
+# ====================================================================== padded patches and gradient checks
+def n_real_of(K):
+    return K * 201 // 256  # 173 -> 135, 192 -> 150, 196 -> 153, 256 -> 201
+
+
+def padded(B, K, n_real, seed, zero_orientations=False, dims=PATCH_LENGTH_DIMS):
+    """syn.patches with patch 0 real only for its first n_real residues, as collate_fn pads a batch: the tail is outside residue_mask and
+    generation_mask, at the origin with the identity frame (or the all-zero matrix: protstruc's fill is not in the reference tree) and
+    of the unknown type; its contexts stay random (encode_context gives padded residues non-zero rows too).  The last patch is whole."""
+    inp = syn.patches(B, K, dims, seed=seed, coord_sigma=6.0)
+    pad = torch.zeros(B, K, dtype=torch.bool)
+    pad[0, n_real:] = True
+    inp["residue_mask"][pad] = False
+    inp["generation_mask"][pad] = False
+    inp["translations"][pad] = 0.0
+    inp["orientations"][pad] = torch.zeros(3, 3) if zero_orientations else torch.eye(3)
+    inp["seq_idx"][pad] = UNK
+    return inp
+
+
+def f64(v):
+    return v.detach().cpu().double()
+
+
+def leaves(sd, prefix):
+    return {prefix + k: f64(v).requires_grad_(True) for k, v in sd.items()}
+
+
+def relu_margin(sd, seq, res_ctx, want, beta):
+    """min |pre-activation| over the denoiser's ReLUs (to_res_emb.0 and the heads' first two layers) in the float64 oracle.  An element
+    within fp32 rounding of 0 flips its mask between the kernel and the oracle and moves one row of the gradient by O(10 %) (measured:
+    a pre-activation of 9e-8 at one residue gave d res_ctx 0.10 off in that row only) - a kink of the function, not an error."""
+    s = {k: v.double() for k, v in sd.items()}
+    z = [torch.cat([f64(res_ctx), s["sequence_embedding.weight"][seq]], -1) @ s["to_res_emb.0.weight"].T + s["to_res_emb.0.bias"]]
+    B, K = seq.shape
+    bt = beta.double()
+    cat = torch.cat([want["res_emb"].detach(), torch.stack([bt, bt.sin(), bt.cos()], -1)[:, None].expand(B, K, 3)], -1)
+    for hd in ("coordinate_denoising", "orientation_denoising", "sequence_denoising"):
+        z1 = cat @ s[hd + ".0.weight"].T + s[hd + ".0.bias"]
+        z += [z1, z1.relu() @ s[hd + ".2.weight"].T + s[hd + ".2.bias"]]
+    return min(float(v.abs().min()) for v in z)
+
+
+def check_params(named, ref, prefix, what):
+    worst = ("", 0.0)
+    for n, p in named:
+        assert p.grad is not None, (what, n)
+        r = maxrel(p.grad, ref[prefix + n].grad)
+        worst = max(worst, (n, r), key=lambda v: v[1])
+        assert r < GTOL, (what, n, r)
+    print(what, "worst parameter gradient:", worst)
+
+
+# ====================================================================== host side: argument checks before the library
+class ReachedTheLibrary(Exception):
+    pass
+
+
+def refuse():
+    raise ReachedTheLibrary()
+
+
+def refuse_library(monkeypatch):
+    """Every check under test must fire before the call asks for the library: any access raises ReachedTheLibrary."""
+    monkeypatch.setattr(_hip, "lib", refuse)
+    monkeypatch.setattr(_hip, "load_library", refuse)
+
+
+def stand_in(methods=("sample",), aa_vocab=21, T=10):
+    """DiffAb.<method> bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device)."""
+    from diffab_pytorch import DiffAb
+    from diffab_pytorch.diffab_pytorch import Denoiser
+
+    d = dict(syn.BENCH_DIMS, NL=1)
+    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], aa_vocab)
+    stub = types.SimpleNamespace(denoiser=den, T=T)
+    for m in methods:
+        setattr(stub, m, types.MethodType(getattr(DiffAb, m), stub))
+    return stub
+
+
+def inputs(rows, K=16, n_ctx=None, D=128, Cp=64):
+    """A zero state of `rows` designs (residues 3..7 generated) with n_ctx contexts (one per row by default)."""
+    n_ctx = rows if n_ctx is None else n_ctx
+    gm = torch.zeros(rows, K, dtype=torch.bool)
+    gm[:, 3:8] = True
+    return dict(seq_idx=torch.zeros(rows, K, dtype=torch.long), xyz=torch.zeros(rows, K, 3),
+                orientations=torch.eye(3).expand(rows, K, 3, 3).clone(), generation_mask=gm, res_context_emb=torch.zeros(n_ctx, K, D),
+                pair_context_emb=torch.zeros(n_ctx, K, K, Cp))
+
+
+def call(model, inp, method="sample", **kw):
+    inp = dict(inp)
+    return getattr(model, method)(inp.pop("seq_idx"), inp.pop("xyz"), inp.pop("orientations"), seed=1, **inp, **kw)

@@ -1,32 +1,16 @@
 """CPU: the host side of the sampler's sequence constraints (DiffAb.sample(allowed_aa=...)) - the C-ABI entries, the argument checks
 that happen before any library call, and the io.allowed_aa_mask builder."""
 import ctypes
-import types
 
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, io, synthetic as syn
-from diffab_pytorch.diffab_pytorch import Denoiser, _pack_allowed_aa
+import sampler_support as support
+from diffab_pytorch import io
+from diffab_pytorch.diffab_pytorch import _pack_allowed_aa
+from sampler_support import ReachedTheLibrary, inputs, refuse_library, stand_in
 
 V = 21
-
-
-class ReachedTheLibrary(Exception):
-    pass
-
-
-def refuse():
-    raise ReachedTheLibrary()
-
-
-def stand_in(aa_vocab=V):
-    """DiffAb.sample bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device)."""
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], aa_vocab)
-    stub = types.SimpleNamespace(denoiser=den, T=10)
-    stub.sample = types.MethodType(DiffAb.sample, stub)
-    return stub
 
 
 @pytest.fixture(scope="module")
@@ -36,21 +20,11 @@ def model():
 
 @pytest.fixture(autouse=True)
 def no_library(monkeypatch):
-    # every check must fire before sample() asks for the library
-    monkeypatch.setattr(_hip, "lib", refuse)
-    monkeypatch.setattr(_hip, "load_library", refuse)
-
-
-def inputs(B=2, K=16, D=128, Cp=64):
-    gm = torch.zeros(B, K, dtype=torch.bool)
-    gm[:, 3:8] = True
-    return dict(seq_idx=torch.zeros(B, K, dtype=torch.long), xyz=torch.zeros(B, K, 3), orientations=torch.eye(3).expand(B, K, 3, 3).clone(),
-                generation_mask=gm, res_context_emb=torch.zeros(B, K, D), pair_context_emb=torch.zeros(B, K, K, Cp))
+    refuse_library(monkeypatch)
 
 
 def call(model, **kw):
-    inp = inputs()
-    return model.sample(inp.pop("seq_idx"), inp.pop("xyz"), inp.pop("orientations"), seed=1, **inp, **kw)
+    return support.call(model, inputs(2), **kw)
 
 
 @pytest.mark.parametrize("dtype", [torch.uint8, torch.int32, torch.float32, torch.int64])
@@ -107,7 +81,7 @@ def test_structure_mode_is_rejected(model):
                                 dict(context_index=torch.tensor([1, 0, 1]))])
 def test_valid_masks_reach_the_library(model, kw):
     # the accepted combinations pass every check (and stop where sample() asks for the library)
-    inp = inputs()
+    inp = inputs(2)
     if "context_index" in kw:
         for k in ("seq_idx", "xyz", "orientations", "generation_mask"):
             inp[k] = inp[k][[0, 1, 1]]

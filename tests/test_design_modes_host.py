@@ -3,14 +3,14 @@ argument checks that happen before any library call."""
 import ctypes
 import os
 import re
-import types
 
 import pytest
-import torch
 
+import sampler_support as support
 from conftest import REPO
-from diffab_pytorch import DiffAb, _hip, synthetic as syn
-from diffab_pytorch.diffab_pytorch import SAMPLE_MODES, Denoiser
+from diffab_pytorch import _hip
+from diffab_pytorch.diffab_pytorch import SAMPLE_MODES
+from sampler_support import inputs, stand_in
 
 
 def header_defines():
@@ -36,25 +36,11 @@ def test_mode_table():
 
 @pytest.fixture(scope="module")
 def model():
-    """DiffAb.sample bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device): every check
-    below must fire before sample() touches anything else - the library above all."""
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], 21)
-    stub = types.SimpleNamespace(denoiser=den, T=10)
-    stub.sample = types.MethodType(DiffAb.sample, stub)
-    return stub
-
-
-def inputs(B=2, K=16, D=128, Cp=64):
-    gm = torch.zeros(B, K, dtype=torch.bool)
-    gm[:, 3:8] = True
-    return dict(seq_idx=torch.zeros(B, K, dtype=torch.long), xyz=torch.zeros(B, K, 3), orientations=torch.eye(3).expand(B, K, 3, 3).clone(),
-                generation_mask=gm, res_context_emb=torch.zeros(B, K, D), pair_context_emb=torch.zeros(B, K, K, Cp))
+    return stand_in()
 
 
 def call(model, **kw):
-    inp = inputs()
-    return model.sample(inp.pop("seq_idx"), inp.pop("xyz"), inp.pop("orientations"), seed=1, **inp, **kw)
+    return support.call(model, inputs(2), **kw)
 
 
 @pytest.mark.parametrize("mode", ["co-design", "Structure", "", 3])

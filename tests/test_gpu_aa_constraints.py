@@ -11,30 +11,13 @@ import pytest
 import torch
 
 from diffab_pytorch import _hip, io, synthetic as syn
+from sampler_support import CTX, STATE, assert_bitwise, hip, make_model, patches, rows, sample
 
 pytestmark = pytest.mark.gpu
 V, UNK = 21, 20
 STREAM_SEQ, STREAM_INIT_S, STREAM_OPT_SEQ = 0, 6, 7  # csrc/philox.h
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
 STRUCT = ("translations", "orientations")
 MARGIN = 1e-5  # relative to tot: how far a threshold must lie from a cumulative boundary for the draw to be decided
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
-    return model
 
 
 @pytest.fixture(scope="module")
@@ -47,26 +30,6 @@ def unit(hip):
 def bench(hip):
     dims = dict(syn.BENCH_DIMS, NL=3)
     return dims, make_model(dims, 19)
-
-
-def patches(B, K, dims, seed):
-    return {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-
-
-def sample(model, inp, **kw):
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **kw)
-
-
-def rows(inp, index):
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want)
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
 
 
 def assert_context_untouched(out, inp, what=""):

@@ -13,17 +13,11 @@ import torch
 
 from conftest import maxrel
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import hip
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
 GTOL = 2e-4  # gradients: the bar of the training-step goldens (tests/test_gpu_parity.py)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def check_grad(name, got, g, tol=GTOL):

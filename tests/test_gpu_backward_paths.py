@@ -37,19 +37,12 @@ import torch
 import diffab_oracle as orc
 from conftest import maxrel
 from diffab_pytorch import _hip, synthetic as syn
-from test_gpu_patch_lengths import GTOL, TOL, check_params, f64, leaves, n_real_of, padded, relu_margin
+from sampler_support import GTOL, TOL, check_params, f64, hip, leaves, n_real_of, padded, relu_margin
 
 pytestmark = pytest.mark.gpu
 ARGS = ("seq_idx", "translations", "orientations", "res_context_emb", "pair_context_emb")
 CDR = slice(10, 34)  # a CDR-H3-sized generated block (24 residues), inside patch 0's real residues at K = 64 (50 real)
 MARGIN = 5e-7
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def dims_of(NL):

@@ -16,47 +16,9 @@ import torch
 
 import diffab_oracle as orc
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import bench_model, device_patches, hip, oracle_reverse_step
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def device_patches(B, K, dims, seed):
-    """Seeded synthetic patches of SURVEY 8(d)'s shapes, generated on the device (the 8.6 GB pair context of config 5 would take
-    minutes through the host generator): N(0,1) contexts, N(0,10^2) A translations, uniform rotations, one CDR-like segment
-    of 5..20 generated residues per patch."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    out = {
-        "res_context_emb": torch.randn(B, K, dims["D"], device="cuda", generator=g),
-        "pair_context_emb": torch.randn(B, K, K, dims["C"], device="cuda", generator=g),
-        "translations": 10 * torch.randn(B, K, 3, device="cuda", generator=g),
-        "seq_idx": torch.randint(0, 20, (B, K), device="cuda", generator=g),
-    }
-    q = torch.randn(B, K, 4, device="cuda", generator=g)
-    out["orientations"] = orc.uniform_rotation_from_normals(q.cpu()).cuda()
-    start = torch.randint(0, K - 20, (B, 1), device="cuda", generator=g)
-    length = torch.randint(5, 21, (B, 1), device="cuda", generator=g)
-    pos = torch.arange(K, device="cuda")[None]
-    out["generation_mask"] = (pos >= start) & (pos < start + length)
-    return out
-
-
-def bench_model(T_steps, NL=None):
-    from diffab_pytorch import DiffAb
-
-    d = dict(syn.BENCH_DIMS)
-    if NL is not None:
-        d["NL"] = NL
-    torch.manual_seed(0)
-    model = DiffAb(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], T=T_steps).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(d, seed=0, prefix=""))
-    return d, model
 
 
 def check_trajectory(model, inp, seed, shard, n_steps_expected, kw=None):
@@ -96,31 +58,6 @@ def check_trajectory(model, inp, seed, shard, n_steps_expected, kw=None):
     other = model.sample(inp["seq_idx"][sl], inp["translations"][sl], inp["orientations"][sl], seed=seed + 1, first_patch=lo, **kw(sl))
     assert not torch.equal(other["translations"], part["translations"])
     return B * K * model.T / dt, dt
-
-
-def oracle_reverse_step(model, inp, sl, seed, t):
-    """The oracle's reverse step t -> t-1 for the patches `sl` (a slice) of a batch, with the Philox noise of their GLOBAL patch ids."""
-    sd = {"denoiser." + k: v.detach().cpu() for k, v in model.denoiser.state_dict().items()}
-    sched = orc.cosine_variance_schedule(model.T, s=0.01, beta_max=0.999)
-    c = {k: v[sl].cpu() for k, v in inp.items()}
-    B, K = c["seq_idx"].shape
-    patch = (sl.start + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-    z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_TRANS)[:3], -1))
-    ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_AXIS)[:3], -1))
-    ua = orc.philox_uniform4(seed, patch, res, t, orc.STREAM_ANGLE)
-    na = orc.philox_normal4(seed, patch, res, t, orc.STREAM_ANGLE)
-    us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, orc.STREAM_SEQ)[0])
-    sig = sched["beta"].sqrt()
-    cdf_row = model._reverse_so3()._cdf[t].cpu()[None, None, :].expand(B, K, -1)
-    th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row, torch.from_numpy(ua[0])), torch.from_numpy(ua[1]))
-    th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-    rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
-    den = orc.denoiser(sd, c["seq_idx"], c["translations"], c["orientations"], c["res_context_emb"], c["pair_context_emb"],
-                       sched["beta"][t].expand(B), model.denoiser.dims["NL"], model.denoiser.dims["H"])
-    # distance of every sequence draw's uniform from the nearest edge of the oracle posterior's CDF (a draw can flip only on an edge)
-    edge = (den["seq_posterior"].double().cumsum(-1) - us.double()[..., None]).abs().min(dim=-1).values
-    return orc.reverse_update(t, c["seq_idx"], c["translations"], c["orientations"], den, c["generation_mask"], sched, z, rotvec, us) + (edge,)
 
 
 def test_patch_resident_module_default_forms_are_bitwise_the_per_layer_launches(hip):
@@ -189,12 +126,16 @@ def test_config2_b256_k128_100_steps(hip):
     # smaller batches never run): one teacher-forced reverse step of all 256 patches, an 8-patch slice of it against the oracle
     from conftest import maxrel
 
+    sd = {"denoiser." + k: v.detach().cpu() for k, v in model.denoiser.state_dict().items()}
+    sched = orc.cosine_variance_schedule(model.T, s=0.01, beta_max=0.999)
     for t in (57, 3):
         got = model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], res_context_emb=inp["res_context_emb"],
                            pair_context_emb=inp["pair_context_emb"], generation_mask=inp["generation_mask"], seed=29, t_start=t, t_stop=t - 1,
                            init=False)
-        sl = slice(120, 128)
-        s1, x1, O1, edge = oracle_reverse_step(model, inp, sl, 29, t)
+        sl = slice(120, 128)  # with the Philox noise of the patches' GLOBAL ids
+        c = {k: v[sl].cpu() for k, v in inp.items()}
+        s1, x1, O1, _, _, edge = oracle_reverse_step(sd, c, c["generation_mask"], model._reverse_so3(), sched, 29, sl.start, t, dims["NL"],
+                                                     dims["H"])
         assert maxrel(got["translations"][sl], x1) < 1e-4, (t, maxrel(got["translations"][sl], x1))
         assert maxrel(got["orientations"][sl], O1) < 1e-4, (t, maxrel(got["orientations"][sl], O1))
         diff = got["seq_idx"][sl].cpu() != s1  # every flipped draw: the oracle's uniform within 1e-5 of a cumulative-probability edge
@@ -370,7 +311,6 @@ def test_two_sampler_pipelines_on_two_streams_are_bitwise_the_sequential_runs(hi
         torch.cuda.synchronize()
     assert hip.diffab_set_stream_guard(0) == 0
     assert int(bad.sum()) == 0, dict(zip(ref, bad.tolist()))
-
 
 
 def _bench_dump(tmp_path, name, *args):

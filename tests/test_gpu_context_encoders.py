@@ -46,7 +46,8 @@ import torch
 
 import diffab_oracle as orc
 from conftest import elemrel, elemrel_by_decade, maxrel
-from diffab_pytorch import _hip, synthetic as syn
+from diffab_pytorch import synthetic as syn
+from sampler_support import hip
 
 pytestmark = pytest.mark.gpu
 FMAX, FELEM = 2e-5, 1e-4  # forward: max-rel and element-wise bars (tests/conftest.py)
@@ -89,13 +90,6 @@ def _runs():
         for v in ex.get("variants", ()):
             out.append(pytest.param(name, True, True, "xyz", v, id=f"{name}-gs1gq1-xyz-variant{v}"))
     return out
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def model_for(A, md, seed):

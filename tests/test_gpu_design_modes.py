@@ -7,36 +7,17 @@ lanes, and keeps the sampler's sharding / num_samples / graph-replay equalities.
 """
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 
 import diffab_oracle as orc
 from conftest import maxrel
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import CTX, STREAMS_OPT, assert_bitwise, hip, make_model, patches, rows, sample, step_noise
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4  # as tests/test_gpu_parity.py
-STREAM_OPT_SEQ, STREAM_OPT_TRANS, STREAM_OPT_AXIS, STREAM_OPT_ANGLE = 7, 8, 9, 10  # csrc/philox.h
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
 STRUCT = ("translations", "orientations")
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
-    return model
 
 
 @pytest.fixture(scope="module")
@@ -49,26 +30,6 @@ def unit(hip):
 def bench(hip):
     dims = dict(syn.BENCH_DIMS, NL=3)
     return dims, make_model(dims, 19)
-
-
-def patches(B, K, dims, seed):
-    return {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-
-
-def sample(model, inp, **kw):
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **kw)
-
-
-def rows(inp, index):
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want)
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
 
 
 def assert_kept(out, inp, mode, what=""):
@@ -164,21 +125,11 @@ def test_forward_noised_init_vs_oracle(unit):
     cos = (inp["orientations"].diagonal(dim1=-2, dim2=-1).sum(-1) - 1) / 2
     ok = gm & ((cos - 1).abs() >= 1e-2) & ((cos + 1).abs() >= 1e-2)  # scale_rot is defined away from theta in {0, pi}
     assert ok.sum() > 0.8 * gm.sum()
-    patch = (fp + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
     flips = 0
     for t in (1, 3, 5, 6, 8, 40, 100):
         got = {k: v.cpu() for k, v in sample(model, inp, optimize_from=t, t_stop=t, seed=seed, first_patch=fp).items()}
         tt = torch.full((B,), t, dtype=torch.long)
-        eps = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, STREAM_OPT_TRANS)[:3], -1))
-        ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, STREAM_OPT_AXIS)[:3], -1))
-        ua = orc.philox_uniform4(seed, patch, res, t, STREAM_OPT_ANGLE)
-        na = orc.philox_normal4(seed, patch, res, t, STREAM_OPT_ANGLE)
-        us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, STREAM_OPT_SEQ)[0])
-        th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf[t][None, None, :].expand(B, K, -1), torch.from_numpy(ua[0])),
-                                         torch.from_numpy(ua[1]))
-        th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-        rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
+        eps, rotvec, us = step_noise(seed, fp, B, K, t, cdf[t], sig[t], streams=STREAMS_OPT)
         x1 = orc.coord_diffuse_from_t0(inp["translations"], tt, gm, eps, sched)
         O1 = orc.orient_diffuse_from_t0(inp["orientations"], gm, tt, rotvec, sched)
         p = orc.seq_forward_prob_from_t0(inp["seq_idx"], tt, gm, sched)

@@ -38,10 +38,9 @@ import torch
 import diffab_oracle as orc
 from conftest import elemrel, maxrel
 from diffab_pytorch import _hip, synthetic as syn
-from test_gpu_patch_lengths import FLAG_IDS, FLAGS, GTOL, OUTS, TOL, check_params, f64, leaves, padded, relu_margin
+from sampler_support import ARGS, FLAGS, FLAG_IDS, GTOL, OUTS, TOL, check_params, f64, hip, leaves, oracle_reverse_step, padded, relu_margin
 
 pytestmark = pytest.mark.gpu
-ARGS = ("seq_idx", "translations", "orientations", "res_context_emb", "pair_context_emb")
 MARGIN = 5e-7
 # id: B, K, D, C, H, DS, PQ, PV, NL, weight seed (a seed whose ReLU margin is > MARGIN in every mode that uses it)
 GEOMS = {
@@ -56,13 +55,6 @@ GEOMS = {
     "refused": (1, 256, 32, 4, 64, 8, 4, 4, 1, 9),
 }
 LOSS_IDS = ["odd", "odd_k5", "af2", "h4", "segs64", "d128_ds24", "lds_rows", "lds_keys"]
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def geom(gid):
@@ -300,26 +292,6 @@ def test_ipa_layer_gradients_vs_float64_oracle(hip, gid, pair_bias):
 
 
 # ------------------------------------------------------------------ 5. teacher-forced reverse step through the C ABI
-def oracle_reverse_step(sd, inp, gm, rev, sched, seed, first_patch, t, d):
-    """The oracle's reverse step t -> t-1 on the sampler's Philox lanes (tests/test_gpu_parity.py, teacher-forced form)."""
-    B, K = inp["seq_idx"].shape
-    sig = sched["beta"].sqrt()
-    patch = (first_patch + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-    z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_TRANS)[:3], -1))
-    ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_AXIS)[:3], -1))
-    ua = orc.philox_uniform4(seed, patch, res, t, orc.STREAM_ANGLE)
-    na = orc.philox_normal4(seed, patch, res, t, orc.STREAM_ANGLE)
-    us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, orc.STREAM_SEQ)[0])
-    cdf_row = rev._cdf[t].cpu()[None, None, :].expand(B, K, -1)
-    th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row, torch.from_numpy(ua[0])), torch.from_numpy(ua[1]))
-    th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-    rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
-    den = orc.denoiser(sd, *[inp[k] for k in ARGS], sched["beta"][t].expand(B), d["NL"], d["H"])
-    s1, x1, O1 = orc.reverse_update(t, inp["seq_idx"], inp["translations"], inp["orientations"], den, gm, sched, z, rotvec, us)
-    return s1, x1, O1, den, us
-
-
 @pytest.mark.parametrize("gid", ["odd", "af2"])
 def test_reverse_step_teacher_forced_vs_oracle(hip, gid):
     """One reverse step at t in {100, 57, 8, 1} (diffab_sample_loop on the generic forward) against orc.reverse_update on the same noise:
@@ -339,12 +311,11 @@ def test_reverse_step_teacher_forced_vs_oracle(hip, gid):
         got = model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], res_context_emb=inp["res_context_emb"],
                            pair_context_emb=inp["pair_context_emb"], generation_mask=gm, seed=rseed, first_patch=first, t_start=t,
                            t_stop=t - 1, init=False)
-        s1, x1, O1, den, us = oracle_reverse_step(sd, inp, gm, rev, sched, rseed, first, t, d)
+        s1, x1, O1, den, us, edge = oracle_reverse_step(sd, inp, gm, rev, sched, rseed, first, t, d["NL"], d["H"])
         assert maxrel(got["translations"], x1) < TOL, (gid, t, maxrel(got["translations"], x1))
         assert maxrel(got["orientations"], O1) < TOL, (gid, t, maxrel(got["orientations"], O1))
         diff = got["seq_idx"].cpu() != s1
         if diff.any():
-            edge = (den["seq_posterior"].double().cumsum(-1) - us.double()[..., None]).abs().min(dim=-1).values
             assert float(edge[diff].max()) < 1e-5, (gid, t, float(edge[diff].max()))
             flips += int(diff.sum())
         for k in ("seq_idx", "translations", "orientations"):

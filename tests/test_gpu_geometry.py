@@ -15,21 +15,15 @@ import numpy as np
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, io as dio, metrics, patch, synthetic as syn
+from diffab_pytorch import DiffAb, io as dio, metrics, patch, synthetic as syn
+from sampler_support import hip
 from test_geometry_host import backbone_ref, contacts_ref, frames_of, nerf_chain, wrapped
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("hip")]  # every test here needs the device, whether it names the fixture or not
 
 CHUNK_ATOMS = metrics.CONTACTS_CHUNK_ATOMS  # context atoms the contacts kernel stages in LDS per pass (include/diffab_hip.h)
 CHUNK_RESIDUES = metrics.CONTACTS_CHUNK_RESIDUES
 ATOMS5 = dio.BACKBONE_ATOMS
-
-
-@pytest.fixture(scope="module", autouse=True)
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def rotation(rng):

@@ -6,6 +6,8 @@ K = 128, 256 and an odd K; one guided step is the unguided step minus the float6
 change nothing is bitwise the unguided run; a guided run is bitwise the same on every launch form; and the potential does what it says
 on designs whose generated residues start collapsed onto one point.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -13,73 +15,19 @@ import torch
 from diffab_pytorch import _hip, synthetic as syn
 from diffab_pytorch.diffusion import jump_coefficients
 from diffab_pytorch.guidance import SampleGuidance, structure_energy
+from sampler_support import CTX, assert_bitwise, hip, make_model, patches, rows, sample
 from test_guidance_host import guidance_ref, planted_rows, shift_ref
 
 pytestmark = pytest.mark.gpu
 V = 21
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
 GUIDE = SampleGuidance(clash=2.0, bond=1.0, max_shift=0.5)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
-    return model
+patches = functools.partial(patches, chains=True)  # two chains, padded context residues, the generated residues collapsed onto one point
 
 
 @pytest.fixture(scope="module")
 def bench(hip):
     dims = dict(syn.BENCH_DIMS, NL=3)
     return dims, make_model(dims, 23)
-
-
-def patches(B, K, dims, seed, collapse=True):
-    """Synthetic patches whose generated residues sit within ~1 A of one point (clashes and broken bonds for the potential to act on),
-    two chains with a gap in residue_idx, and a few padded context residues."""
-    inp = {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    gm = inp["generation_mask"]
-    if collapse:
-        x = inp["translations"]
-        centre = x[torch.arange(B), gm.float().argmax(1)][:, None, :]
-        x[:] = torch.where(gm[..., None], centre + torch.randn(x.shape, device="cuda", generator=g), x)
-    half = K // 2
-    inp["chain_idx"] = (torch.arange(K, device="cuda") >= half).long().expand(B, K).contiguous()
-    inp["residue_idx"] = (torch.arange(K, device="cuda") + 7 * (torch.arange(K, device="cuda") >= half)).expand(B, K).contiguous()
-    rm = torch.rand(B, K, device="cuda", generator=g) > 0.1
-    inp["residue_mask"] = rm | gm
-    return inp
-
-
-def sample(model, inp, **kw):
-    tabs = {k: inp[k] for k in ("chain_idx", "residue_idx", "residue_mask") if k in inp}
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **tabs, **kw)
-
-
-def rows(inp, index):
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want), (what, set(got) ^ set(want))
-    for k in want:
-        if isinstance(want[k], dict):
-            assert_bitwise(got[k], want[k], (what, k))
-            continue
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
 
 
 # ------------------------------------------------------------------ 1. the energy entry against the float64 oracle

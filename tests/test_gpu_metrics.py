@@ -10,17 +10,11 @@ import numpy as np
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, metrics, synthetic as syn
+from diffab_pytorch import DiffAb, metrics, synthetic as syn
+from sampler_support import hip
 from test_metrics_host import evaluate_ref, pairwise_ref, rotation, select_ref
 
-pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("hip")]  # every test here needs the device, whether it names the fixture or not
 
 
 def assert_in_place(dev, ref, what):

@@ -7,15 +7,9 @@ import torch
 
 import diffab_oracle as orc
 from diffab_pytorch import DiffAb, _hip, synthetic as syn
+from sampler_support import hip
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def _model(NL):

@@ -11,17 +11,11 @@ import torch
 import diffab_oracle as orc
 from conftest import elemrel, elemrel_by_decade, maxrel
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import hip, make_model, oracle_reverse_step, unit_model
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
 TOL = 1e-4  # BASELINE.json: "aa-type logits and translations within 1e-4 rel fp32"
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()  # raises HipUnavailable when there is no gfx950 / no library: never a silent fallback
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 def well_conditioned(R):
@@ -499,50 +493,25 @@ def test_philox_matches_oracle_bitwise(hip):
     assert abs(float(big.mean())) < 0.01 and abs(float(big.std()) - 1) < 0.01
 
 
-def _unit_model(NL=2, seed=17):
-    from diffab_pytorch import DiffAb
-
-    dims = dict(syn.UNIT_DIMS, NL=NL)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
-    sd = syn.denoiser_state_dict(dims, seed=seed, prefix="")
-    model.denoiser.load_state_dict(sd)
-    return dims, model, {"denoiser." + k: v for k, v in sd.items()}
-
-
 def test_reverse_step_teacher_forced_vs_oracle(hip):
     """One reverse step t -> t-1 (denoise + Philox noise + IGSO3 draw + update) against the oracle, teacher-forced
     at realistic coordinates for several t, including the histogram branch of the reverse table (small sqrt(beta))
     and t = 1 (no noise)."""
-    dims, model, sd = _unit_model()
+    dims, model, sd = unit_model()
     sched = orc.cosine_variance_schedule(100, s=0.01, beta_max=0.999)
     B, K, seed = 3, 16, 991
     inp = syn.patches(B, K, dims, seed=4, coord_sigma=5.0)
     gm = inp["generation_mask"]
     rev = model._reverse_so3()
-    sig = sched["beta"].sqrt()
     for t in (100, 57, 8, 2, 1):
         got = model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], res_context_emb=inp["res_context_emb"],
                            pair_context_emb=inp["pair_context_emb"], generation_mask=gm, seed=seed, first_patch=10, t_start=t,
                            t_stop=t - 1, init=False)
-        patch = (10 + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-        res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-        z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_TRANS)[:3], -1))
-        ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_AXIS)[:3], -1))
-        ua = orc.philox_uniform4(seed, patch, res, t, orc.STREAM_ANGLE)
-        na = orc.philox_normal4(seed, patch, res, t, orc.STREAM_ANGLE)
-        us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, orc.STREAM_SEQ)[0])
-        cdf_row = rev._cdf[t].cpu()[None, None, :].expand(B, K, -1)
-        th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row, torch.from_numpy(ua[0])), torch.from_numpy(ua[1]))
-        th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-        rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
-        den = orc.denoiser(sd, inp["seq_idx"], inp["translations"], inp["orientations"], inp["res_context_emb"], inp["pair_context_emb"],
-                           sched["beta"][t].expand(B), dims["NL"], dims["H"])
-        s1, x1, O1 = orc.reverse_update(t, inp["seq_idx"], inp["translations"], inp["orientations"], den, gm, sched, z, rotvec, us)
+        s1, x1, O1, den, us, edge = oracle_reverse_step(sd, inp, gm, rev, sched, seed, 10, t, dims["NL"], dims["H"])
         assert maxrel(got["translations"], x1) < TOL, t
         assert maxrel(got["orientations"], O1) < TOL, t
         diff = got["seq_idx"] != s1  # a draw can flip only when u sits on an edge of the posterior's CDF
         if diff.any():
-            edge = (den["seq_posterior"].double().cumsum(-1) - us.double()[..., None]).abs().min(dim=-1).values
             assert float(edge[diff].max()) < 1e-5, (t, int(diff.sum()), float(edge[diff].max()))
         assert torch.equal(got["translations"][~gm], inp["translations"][~gm])
         assert torch.equal(got["seq_idx"][~gm], inp["seq_idx"][~gm])
@@ -555,46 +524,25 @@ def test_reverse_step_teacher_forced_at_benchmark_geometry(hip, K):
     K = 256 (chunked planes kernel), B = 2, NL = 2, t in {100, 57, 8, 2, 1}.  x and O within 1e-4; every sequence draw that differs
     from the oracle's must sit on an edge of the posterior's CDF (the draw is u < cumsum(p): a 1e-6 difference in p flips it only
     there), and their number is printed."""
-    from diffab_pytorch import DiffAb
-
     dims = dict(syn.BENCH_DIMS, NL=2)
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
-    sd0 = syn.denoiser_state_dict(dims, seed=19, prefix="")
-    model.denoiser.load_state_dict(sd0)
-    sd = {"denoiser." + k: v for k, v in sd0.items()}
+    model = make_model(dims, 19)
+    sd = {"denoiser." + k: v for k, v in syn.denoiser_state_dict(dims, seed=19, prefix="").items()}
     sched = orc.cosine_variance_schedule(100, s=0.01, beta_max=0.999)
     B, seed = 2, 4242
     inp = syn.patches(B, K, dims, seed=40 + K, coord_sigma=6.0)
     gm = inp["generation_mask"].clone()
     gm[:, : K // 2] = True  # half of every patch is generated: enough draws to see CDF-edge flips
     rev = model._reverse_so3()
-    sig = sched["beta"].sqrt()
     flips = 0
     for t in (100, 57, 8, 2, 1):
         got = model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], res_context_emb=inp["res_context_emb"],
                            pair_context_emb=inp["pair_context_emb"], generation_mask=gm, seed=seed, first_patch=3, t_start=t,
                            t_stop=t - 1, init=False)
-        patch = (3 + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-        res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-        z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_TRANS)[:3], -1))
-        ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_AXIS)[:3], -1))
-        ua = orc.philox_uniform4(seed, patch, res, t, orc.STREAM_ANGLE)
-        na = orc.philox_normal4(seed, patch, res, t, orc.STREAM_ANGLE)
-        us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, orc.STREAM_SEQ)[0])
-        cdf_row = rev._cdf[t].cpu()[None, None, :].expand(B, K, -1)
-        th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row, torch.from_numpy(ua[0])), torch.from_numpy(ua[1]))
-        th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-        rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
-        den = orc.denoiser(sd, inp["seq_idx"], inp["translations"], inp["orientations"], inp["res_context_emb"], inp["pair_context_emb"],
-                           sched["beta"][t].expand(B), dims["NL"], dims["H"])
-        s1, x1, O1 = orc.reverse_update(t, inp["seq_idx"], inp["translations"], inp["orientations"], den, gm, sched, z, rotvec, us)
+        s1, x1, O1, den, us, edge = oracle_reverse_step(sd, inp, gm, rev, sched, seed, 3, t, dims["NL"], dims["H"])
         assert maxrel(got["translations"], x1) < TOL, (K, t, maxrel(got["translations"], x1))
         assert maxrel(got["orientations"], O1) < TOL, (K, t, maxrel(got["orientations"], O1))
         diff = (got["seq_idx"].cpu() != s1)
         if diff.any():  # each flipped draw: u within 1e-5 of a cumulative-probability edge of the oracle's posterior
-            cdf = den["seq_posterior"].double().cumsum(-1)
-            edge = (cdf - us.double()[..., None]).abs().min(dim=-1).values
             assert float(edge[diff].max()) < 1e-5, (K, t, float(edge[diff].max()))
             flips += int(diff.sum())
         assert torch.equal(got["translations"].cpu()[~gm], inp["translations"][~gm])
@@ -605,7 +553,7 @@ def test_reverse_step_teacher_forced_at_benchmark_geometry(hip, K):
 def test_explicit_noise_reverse_update_vs_oracle(hip):
     import ctypes as C
 
-    dims, model, sd = _unit_model(NL=1)
+    dims, model, sd = unit_model(NL=1)
     sched = orc.cosine_variance_schedule(100, s=0.01, beta_max=0.999)
     B, K, t = 2, 16, 33
     torch.manual_seed(0)
@@ -629,7 +577,7 @@ def test_explicit_noise_reverse_update_vs_oracle(hip):
 def test_sample_loop_shard_invariance_and_determinism(hip):
     """100-step reverse loop: finite, reproducible, context untouched, and identical under any sharding of the
     batch (noise is keyed by the GLOBAL patch id) - the N>1 correctness property on one device."""
-    dims, model, _ = _unit_model()
+    dims, model, _ = unit_model()
     B, K = 6, 16
     inp = syn.patches(B, K, dims, seed=8, coord_sigma=5.0)
     kw = dict(res_context_emb=inp["res_context_emb"], pair_context_emb=inp["pair_context_emb"], generation_mask=inp["generation_mask"])
@@ -687,7 +635,7 @@ def test_graph_sampler_is_bitwise_the_eager_sampler(hip):
     for bit, on the generic path (unit dims) and on the MFMA path at BASELINE config 1's shape (B = 1, K = 128, 100 steps)."""
     from diffab_pytorch import DiffAb
 
-    dims, model, _ = _unit_model()
+    dims, model, _ = unit_model()
     inp = syn.patches(3, 16, dims, seed=21, coord_sigma=5.0)
     kw = dict(res_context_emb=inp["res_context_emb"], pair_context_emb=inp["pair_context_emb"], generation_mask=inp["generation_mask"], seed=77)
     eager = model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], graph=False, **kw)
@@ -718,7 +666,7 @@ def test_graph_sampler_is_bitwise_the_eager_sampler(hip):
 
 
 def test_shared_step_and_add_noise(hip):
-    dims, model, sd = _unit_model()
+    dims, model, sd = unit_model()
     B, K = 4, 16
     inp = syn.patches(B, K, dims, seed=2, coord_sigma=5.0)
     t = torch.tensor([1, 30, 60, 100])
@@ -868,7 +816,7 @@ def test_bench_geometry_gradients_vs_reference_goldens(hip, golden):
 
 def test_training_step_runs_and_learns(hip):
     """DiffAb.training_step + Adam (configure_optimizers, reference :925-931) on a fixed synthetic batch: loss decreases."""
-    dims, model, _ = _unit_model()
+    dims, model, _ = unit_model()
     B, K = 4, 16
     inp = syn.patches(B, K, dims, seed=3, coord_sigma=5.0)
     batch = {"seq_idx": inp["seq_idx"].cuda(), "xyz": inp["translations"].cuda(), "orientations": inp["orientations"].cuda(),
@@ -1367,4 +1315,3 @@ def test_pair_planes_outlier_stays_in_its_row(hip):
     print(f"pair planes with a 1e4 x outlier: outlier-free rows {err_clean:.2e}, the outlier's row {err_row:.2e} (of the output maximum)")
     assert err_clean < 2e-6, err_clean
     assert err_row < TOL, err_row
-

@@ -14,18 +14,12 @@ import torch
 
 from diffab_pytorch import _hip, patch, synthetic as syn
 from diffab_pytorch.guidance import SampleGuidance
+from sampler_support import hip, make_model
 from test_patch_host import select_ref
 
 pytestmark = pytest.mark.gpu
 LIMIT = patch.MAX_RESIDUES
 FIELDS = ("residue_mask", "anchor_mask", "chain", "antigen")
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 # ------------------------------------------------------------------ complexes
@@ -251,12 +245,8 @@ def test_many_rows_through_the_row_map(hip):
 
 
 # ------------------------------------------------------------------ python layer and end to end
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
+def model_with_encoders(dims, seed):
+    model = make_model(dims, seed)
     model.load_state_dict(syn.context_state_dict(dims["D"], dims["C"], 15, 32, seed=3), strict=False)
     return model
 
@@ -311,7 +301,7 @@ def test_python_select_and_gather_match_the_oracle_and_torch(hip):
 
 def test_design_complex_end_to_end(hip):
     dims = dict(syn.BENCH_DIMS, NL=2)
-    model = make_model(dims, 9)
+    model = model_with_encoders(dims, 9)
     batch = complexes()
     kw = dict(seed=31, num_samples=4, t_start=12, t_stop=5)
     out = model.design_complex(batch, **kw)
@@ -363,7 +353,7 @@ def test_the_sampler_sees_the_numbering_of_the_complex(hip):
     """A numbering gap inside the generated segment: under bond guidance the design differs from the same call made with
     residue_idx = arange(K), and is bitwise the hand-made call that passes the gathered numbering."""
     dims = dict(syn.BENCH_DIMS, NL=2)
-    model = make_model(dims, 9)
+    model = model_with_encoders(dims, 9)
     batch = complexes()
     ridx = torch.arange(600).repeat(2, 1)
     for b in range(2):

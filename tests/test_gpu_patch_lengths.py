@@ -22,44 +22,13 @@ import torch
 
 import diffab_oracle as orc
 from conftest import elemrel, maxrel
-from diffab_pytorch import _hip, synthetic as syn
+from diffab_pytorch import synthetic as syn
+from sampler_support import (ARGS, FLAGS, FLAG_IDS, GTOL, OUTS, PATCH_LENGTH_DIMS, TOL, UNK, check_params, f64, hip, leaves, make_model,
+                             n_real_of, oracle_reverse_step, padded, relu_margin)
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-4   # forward outputs (tests/test_gpu_parity.py)
-GTOL = 2e-4  # gradients (the training-step goldens' bar)
-DIMS = dict(syn.BENCH_DIMS, NL=2)
+DIMS = PATCH_LENGTH_DIMS
 KS = [173, 192, 196, 256]
-UNK = 20
-FLAGS = [0, _hip.FLAG_FORCE_GENERIC, _hip.FLAG_FP32_GEMM, _hip.FLAG_PAIR_PLANES]
-FLAG_IDS = ["dispatch", "generic", "fp32gemm", "pairplanes"]
-OUTS = ("res_emb", "aa_logits", "translations_eps", "orientations_t0", "seq_posterior")
-ARGS = ("seq_idx", "translations", "orientations", "res_context_emb", "pair_context_emb")
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def n_real_of(K):
-    return K * 201 // 256  # 173 -> 135, 192 -> 150, 196 -> 153, 256 -> 201
-
-
-def padded(B, K, n_real, seed, zero_orientations=False, dims=DIMS):
-    """syn.patches with patch 0 real only for its first n_real residues, as collate_fn pads a batch: the tail is outside residue_mask and
-    generation_mask, at the origin with the identity frame (or the all-zero matrix: protstruc's fill is not in the reference tree) and
-    of the unknown type; its contexts stay random (encode_context gives padded residues non-zero rows too).  The last patch is whole."""
-    inp = syn.patches(B, K, dims, seed=seed, coord_sigma=6.0)
-    pad = torch.zeros(B, K, dtype=torch.bool)
-    pad[0, n_real:] = True
-    inp["residue_mask"][pad] = False
-    inp["generation_mask"][pad] = False
-    inp["translations"][pad] = 0.0
-    inp["orientations"][pad] = torch.zeros(3, 3) if zero_orientations else torch.eye(3)
-    inp["seq_idx"][pad] = UNK
-    return inp
 
 
 def denoiser(seed):
@@ -73,22 +42,7 @@ def denoiser(seed):
 
 
 def diffab(seed):
-    from diffab_pytorch import DiffAb
-
-    d = DIMS
-    torch.manual_seed(0)
-    model = DiffAb(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"]).cuda()
-    sd = syn.denoiser_state_dict(d, seed=seed, prefix="")
-    model.denoiser.load_state_dict(sd)
-    return model, sd
-
-
-def f64(v):
-    return v.detach().cpu().double()
-
-
-def leaves(sd, prefix):
-    return {prefix + k: f64(v).requires_grad_(True) for k, v in sd.items()}
+    return make_model(DIMS, seed), syn.denoiser_state_dict(DIMS, seed=seed, prefix="")
 
 
 # ------------------------------------------------------------------ 1. forward parity
@@ -146,31 +100,6 @@ def gradient_inputs(K):
     gm |= inp["generation_mask"]
     inp["generation_mask"] = gm & inp["residue_mask"]
     return inp
-
-
-def relu_margin(sd, seq, res_ctx, want, beta):
-    """min |pre-activation| over the denoiser's ReLUs (to_res_emb.0 and the heads' first two layers) in the float64 oracle.  An element
-    within fp32 rounding of 0 flips its mask between the kernel and the oracle and moves one row of the gradient by O(10 %) (measured:
-    a pre-activation of 9e-8 at one residue gave d res_ctx 0.10 off in that row only) - a kink of the function, not an error."""
-    s = {k: v.double() for k, v in sd.items()}
-    z = [torch.cat([f64(res_ctx), s["sequence_embedding.weight"][seq]], -1) @ s["to_res_emb.0.weight"].T + s["to_res_emb.0.bias"]]
-    B, K = seq.shape
-    bt = beta.double()
-    cat = torch.cat([want["res_emb"].detach(), torch.stack([bt, bt.sin(), bt.cos()], -1)[:, None].expand(B, K, 3)], -1)
-    for hd in ("coordinate_denoising", "orientation_denoising", "sequence_denoising"):
-        z1 = cat @ s[hd + ".0.weight"].T + s[hd + ".0.bias"]
-        z += [z1, z1.relu() @ s[hd + ".2.weight"].T + s[hd + ".2.bias"]]
-    return min(float(v.abs().min()) for v in z)
-
-
-def check_params(named, ref, prefix, what):
-    worst = ("", 0.0)
-    for n, p in named:
-        assert p.grad is not None, (what, n)
-        r = maxrel(p.grad, ref[prefix + n].grad)
-        worst = max(worst, (n, r), key=lambda v: v[1])
-        assert r < GTOL, (what, n, r)
-    print(what, "worst parameter gradient:", worst)
 
 
 @pytest.mark.parametrize("K", KS)
@@ -252,26 +181,6 @@ def test_ipa_layer_gradients_vs_float64_oracle(hip, K):
 
 
 # ------------------------------------------------------------------ 3. sampler and scorer at ragged K
-def oracle_reverse_step(sd, inp, gm, rev, sched, seed, first_patch, t):
-    """The oracle's reverse step t -> t-1 on the sampler's Philox lanes (tests/test_gpu_parity.py, teacher-forced form)."""
-    B, K = inp["seq_idx"].shape
-    sig = sched["beta"].sqrt()
-    patch = (first_patch + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-    z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_TRANS)[:3], -1))
-    ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_AXIS)[:3], -1))
-    ua = orc.philox_uniform4(seed, patch, res, t, orc.STREAM_ANGLE)
-    na = orc.philox_normal4(seed, patch, res, t, orc.STREAM_ANGLE)
-    us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, orc.STREAM_SEQ)[0])
-    cdf_row = rev._cdf[t].cpu()[None, None, :].expand(B, K, -1)
-    th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row, torch.from_numpy(ua[0])), torch.from_numpy(ua[1]))
-    th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-    rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
-    den = orc.denoiser(sd, *[inp[k] for k in ARGS], sched["beta"][t].expand(B), DIMS["NL"], DIMS["H"])
-    s1, x1, O1 = orc.reverse_update(t, inp["seq_idx"], inp["translations"], inp["orientations"], den, gm, sched, z, rotvec, us)
-    return s1, x1, O1, den, us
-
-
 @pytest.mark.parametrize("K", [173, 196])
 def test_reverse_step_teacher_forced_at_ragged_k(hip, K):
     """One reverse step at t in {100, 57, 8, 1} (the generic forward inside diffab_sample_loop) against the oracle: x and O within 1e-4, a
@@ -290,12 +199,11 @@ def test_reverse_step_teacher_forced_at_ragged_k(hip, K):
         got = model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], res_context_emb=inp["res_context_emb"],
                            pair_context_emb=inp["pair_context_emb"], generation_mask=gm, seed=seed, first_patch=first, t_start=t,
                            t_stop=t - 1, init=False)
-        s1, x1, O1, den, us = oracle_reverse_step(sd, inp, gm, rev, sched, seed, first, t)
+        s1, x1, O1, den, us, edge = oracle_reverse_step(sd, inp, gm, rev, sched, seed, first, t, DIMS["NL"], DIMS["H"])
         assert maxrel(got["translations"], x1) < TOL, (K, t, maxrel(got["translations"], x1))
         assert maxrel(got["orientations"], O1) < TOL, (K, t, maxrel(got["orientations"], O1))
         diff = got["seq_idx"].cpu() != s1
         if diff.any():
-            edge = (den["seq_posterior"].double().cumsum(-1) - us.double()[..., None]).abs().min(dim=-1).values
             assert float(edge[diff].max()) < 1e-5, (K, t, float(edge[diff].max()))
             flips += int(diff.sum())
         for k in ("seq_idx", "translations", "orientations"):

@@ -15,59 +15,19 @@ import diffab_oracle as orc
 from conftest import maxrel
 from diffab_pytorch import _hip, synthetic as syn
 from diffab_pytorch.diffusion import jump_coefficients
+from sampler_support import CTX, STATE, assert_bitwise, hip, make_model, patches, rows, sample, step_noise, unit_model
 from test_respaced_host import posterior_ref, seq_jump_ref
 
 pytestmark = pytest.mark.gpu
 V = 21
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
 REC_STATE = ("seq_idx", "translations", "orientations")
 TOL = 1e-4
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
-    return model
 
 
 @pytest.fixture(scope="module")
 def bench(hip):
     dims = dict(syn.BENCH_DIMS, NL=3)
     return dims, make_model(dims, 19)
-
-
-def patches(B, K, dims, seed):
-    return {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-
-
-def sample(model, inp, **kw):
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **kw)
-
-
-def rows(inp, index):
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want), (what, set(got) ^ set(want))
-    for k in want:
-        if isinstance(want[k], dict):
-            assert_bitwise(got[k], want[k], (what, k))
-            continue
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
 
 
 def final(out):
@@ -181,21 +141,11 @@ def test_even_steps_run_on_every_mode(bench, n):
 
 
 # ------------------------------------------------------------------ 3. one jump, teacher-forced, against the oracle
-def _unit_model(NL=2, seed=17):
-    from diffab_pytorch import DiffAb
-
-    dims = dict(syn.UNIT_DIMS, NL=NL)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
-    sd = syn.denoiser_state_dict(dims, seed=seed, prefix="")
-    model.denoiser.load_state_dict(sd)
-    return dims, model, {"denoiser." + k: v for k, v in sd.items()}
-
-
 @pytest.mark.parametrize("t, s", [(100, 80), (57, 20), (8, 0), (30, 1)])
 def test_jump_teacher_forced_vs_oracle(hip, t, s):
     """sample(t_start=t, steps=[t], t_stop=s, init=False) against oracle.denoiser at beta_t, the host Philox / IGSO3 draws (row t of the
     jump table over sqrt(beta')) and the float64 jump: x and O within 1e-4; a sequence draw may differ only on an edge of r's CDF."""
-    dims, model, sd = _unit_model()
+    dims, model, sd = unit_model()
     sched = orc.cosine_variance_schedule(100, s=0.01, beta_max=0.999)
     B, K, seed = 3, 16, 991
     inp = syn.patches(B, K, dims, seed=4, coord_sigma=5.0)
@@ -206,18 +156,7 @@ def test_jump_teacher_forced_vs_oracle(hip, t, s):
     steps = torch.tensor([t])
     bj, aj = jump_coefficients(model.sched, steps, s, 0.999)
     rev = model._reverse_so3_steps(steps, s, bj)
-    sig = bj.sqrt()
-    patch = (10 + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-    z = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_TRANS)[:3], -1))
-    ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, orc.STREAM_AXIS)[:3], -1))
-    ua = orc.philox_uniform4(seed, patch, res, t, orc.STREAM_ANGLE)
-    na = orc.philox_normal4(seed, patch, res, t, orc.STREAM_ANGLE)
-    us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, orc.STREAM_SEQ)[0])
-    cdf_row = rev._cdf[t].cpu()[None, None, :].expand(B, K, -1)
-    th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf_row, torch.from_numpy(ua[0])), torch.from_numpy(ua[1]))
-    th_g = orc.igso3_theta_from_gaussian(sig[t].expand(B, K), torch.from_numpy(na[2]))
-    rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(B))
+    z, rotvec, us = step_noise(seed, 10, B, K, t, rev._cdf[t].cpu(), bj.sqrt()[t])
     den = orc.denoiser(sd, inp["seq_idx"], inp["translations"], inp["orientations"], inp["res_context_emb"], inp["pair_context_emb"],
                        sched["beta"][t].expand(B), dims["NL"], dims["H"])
     c = bj[t] / sched["one_minus_alpha_bar_sqrt"][t]

@@ -6,36 +6,17 @@ state; and the result is bitwise invariant under chunking, launch form, shared c
 """
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
 
 import diffab_oracle as orc
 from conftest import elemrel, maxrel
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import CTX, STATE, STREAMS_OPT, hip, make_model, patches, score, step_noise
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4  # as tests/test_gpu_parity.py
-STREAM_OPT_SEQ, STREAM_OPT_TRANS, STREAM_OPT_AXIS, STREAM_OPT_ANGLE = 7, 8, 9, 10  # csrc/philox.h
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
 NOISED = ("seq_idx_t", "translations_t", "orientations_t", "translations_eps")
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
-    return model
 
 
 @pytest.fixture(scope="module")
@@ -48,16 +29,6 @@ def unit(hip):
 def bench(hip):
     dims = dict(syn.BENCH_DIMS, NL=3)
     return dims, make_model(dims, 19)
-
-
-def patches(B, K, dims, seed):
-    return {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-
-
-def score(model, inp, **kw):
-    return model.score(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                       residue_mask=inp.get("residue_mask"), res_context_emb=inp.get("res_context_emb"),
-                       pair_context_emb=inp.get("pair_context_emb"), **kw)
 
 
 def assert_bitwise(got, want, what=""):
@@ -107,22 +78,11 @@ def test_noised_state_vs_oracle(unit):
     sig = sched["one_minus_alpha_bar_sqrt"]
     cos = (cpu["orientations"].diagonal(dim1=-2, dim2=-1).sum(-1) - 1) / 2
     ok = gm & ((cos - 1).abs() >= 1e-2) & ((cos + 1).abs() >= 1e-2)  # scale_rot is defined away from theta in {0, pi}
-    patch = (fd + np.arange(R))[:, None] + np.zeros((R, K), dtype=np.int64)
-    res = np.zeros((R, K), dtype=np.int64) + np.arange(K)[None, :]
     flips = 0
     for j, t in enumerate(grid):
         for m in range(M):
-            sw = m << 16
             tt = torch.full((R,), t, dtype=torch.long)
-            eps = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, STREAM_OPT_TRANS + sw)[:3], -1))
-            ax = torch.from_numpy(np.stack(orc.philox_normal4(seed, patch, res, t, STREAM_OPT_AXIS + sw)[:3], -1))
-            ua = orc.philox_uniform4(seed, patch, res, t, STREAM_OPT_ANGLE + sw)
-            na = orc.philox_normal4(seed, patch, res, t, STREAM_OPT_ANGLE + sw)
-            us = torch.from_numpy(orc.philox_uniform4(seed, patch, res, t, STREAM_OPT_SEQ + sw)[0])
-            th_h = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf[t][None, None, :].expand(R, K, -1), torch.from_numpy(ua[0])),
-                                             torch.from_numpy(ua[1]))
-            th_g = orc.igso3_theta_from_gaussian(sig[t].expand(R, K), torch.from_numpy(na[2]))
-            rotvec = orc.igso3_rotvec(ax, th_h, th_g, sig[t].expand(R))
+            eps, rotvec, us = step_noise(seed, fd, R, K, t, cdf[t], sig[t], streams=STREAMS_OPT, draw=m)
             x1 = orc.coord_diffuse_from_t0(cpu["translations"], tt, gm, eps, sched)
             O1 = orc.orient_diffuse_from_t0(cpu["orientations"], gm, tt, rotvec, sched)
             p = orc.seq_forward_prob_from_t0(cpu["seq_idx"], tt, gm, sched)

@@ -11,69 +11,10 @@ import ctypes as C
 import pytest
 import torch
 
-import diffab_oracle as orc
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import CTX, STATE, assert_bitwise, bench_model, device_patches, hip, rows, sample
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def device_patches(B, K, dims, seed):
-    """Seeded synthetic patches generated on the device (test_gpu_configs.py's generator): N(0,1) contexts, N(0,10^2) A translations,
-    uniform rotations, one CDR-like segment of 5..20 generated residues per patch."""
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    out = {
-        "res_context_emb": torch.randn(B, K, dims["D"], device="cuda", generator=g),
-        "pair_context_emb": torch.randn(B, K, K, dims["C"], device="cuda", generator=g),
-        "translations": 10 * torch.randn(B, K, 3, device="cuda", generator=g),
-        "seq_idx": torch.randint(0, 20, (B, K), device="cuda", generator=g),
-    }
-    q = torch.randn(B, K, 4, device="cuda", generator=g)
-    out["orientations"] = orc.uniform_rotation_from_normals(q.cpu()).cuda()
-    start = torch.randint(0, K - 20, (B, 1), device="cuda", generator=g)
-    length = torch.randint(5, 21, (B, 1), device="cuda", generator=g)
-    pos = torch.arange(K, device="cuda")[None]
-    out["generation_mask"] = (pos >= start) & (pos < start + length)
-    return out
-
-
-def bench_model(T_steps, NL=None):
-    from diffab_pytorch import DiffAb
-
-    d = dict(syn.BENCH_DIMS)
-    if NL is not None:
-        d["NL"] = NL
-    torch.manual_seed(0)
-    model = DiffAb(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], T=T_steps).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(d, seed=0, prefix=""))
-    return d, model
-
-
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
-
-
-def rows(inp, index):
-    """Every per-patch input at the given rows (a LongTensor on the device): the replicated batch of the specification."""
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def sample(model, inp, **kw):
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **kw)
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want)
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
 
 
 def shared_vs_replicated(model, inp, N, **kw):

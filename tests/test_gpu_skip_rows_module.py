@@ -8,16 +8,10 @@ import pytest
 import torch
 
 from diffab_pytorch import DiffAb, _hip, synthetic as syn
+from sampler_support import hip
 
 pytestmark = pytest.mark.gpu
 STATE = ("seq_idx", "translations", "orientations")
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 @pytest.fixture(scope="module")

@@ -7,6 +7,7 @@ nothing is bitwise the unsteered run on every launch form; one resampling step i
 collapsed starts steered designs end with less clash and bond energy than unsteered ones.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -16,18 +17,12 @@ from diffab_pytorch import _hip, synthetic as syn
 from diffab_pytorch.guidance import SampleGuidance, structure_energy
 from diffab_pytorch.steering import ParticleSteering, c_struct, resample_oracle
 from diffab_pytorch.temperature import SampleTemperature
-from test_gpu_guidance import CTX, assert_bitwise, make_model, patches, rows, sample
+from sampler_support import CTX, assert_bitwise, hip, make_model, patches, rows, sample
 from test_guidance_host import guidance_ref, planted_rows
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
+patches = functools.partial(patches, chains=True)  # as tests/test_gpu_guidance.py: collapsed generated residues, two chains
 
 
 @pytest.fixture(scope="module")

@@ -17,59 +17,17 @@ from diffab_pytorch import _hip, so3 as _so3, synthetic as syn
 from diffab_pytorch.diffusion import jump_coefficients
 from diffab_pytorch.guidance import SampleGuidance
 from diffab_pytorch.temperature import SampleTemperature, tempered_draw
+from sampler_support import assert_bitwise, hip, lanes, make_model, patches, rows, sample
 from test_respaced_host import seq_jump_ref
 
 pytestmark = pytest.mark.gpu
 V = 21
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
-
-
-@pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
 
 
 @pytest.fixture(scope="module")
 def bench(hip):
-    from diffab_pytorch import DiffAb
-
     dims = dict(syn.BENCH_DIMS, NL=3)
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=100).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=31, prefix=""))
-    return dims, model
-
-
-def patches(B, K, dims, seed):
-    return {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-
-
-def sample(model, inp, **kw):
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **kw)
-
-
-def rows(inp, index):
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want), (what, set(got) ^ set(want))
-    for k in want:
-        if isinstance(want[k], dict):
-            assert_bitwise(got[k], want[k], (what, k))
-            continue
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
-
-
-def philox_grid(seed, first_patch, B, K, t, stream):
-    patch = (first_patch + np.arange(B))[:, None] + np.zeros((B, K), dtype=np.int64)
-    res = np.zeros((B, K), dtype=np.int64) + np.arange(K)[None, :]
-    return orc.philox_uniform4(seed, patch, res, t, stream)
+    return dims, make_model(dims, 31)
 
 
 def rotation_of(O0, O):
@@ -152,7 +110,7 @@ def test_rotation_draw_at_half_scale(bench):
     # the angle: host inverse CDF of the device table's lambda = 0.5 row at the Philox uniforms of the step
     stack = model._rev_so3_tempered[((0.5,), None)]
     row = 0 * (model.T + 1) + t
-    ua = philox_grid(seed, 0, B, K, t, orc.STREAM_ANGLE)
+    ua = orc.philox_uniform4(seed, *lanes(0, B, K), t, orc.STREAM_ANGLE)
     cdf = stack._cdf[row].cpu()
     m = gm.cpu()
     th_ref = orc.igso3_theta_from_hist(orc.igso3_bin_from_cdf(cdf, torch.from_numpy(ua[0])[m]), torch.from_numpy(ua[1])[m]).double()
@@ -190,7 +148,7 @@ def test_tau_half_is_the_float64_restatement(bench):
     allowed = torch.rand(K, V, generator=torch.Generator().manual_seed(4)) < 0.6
     allowed[:, 0] = True
     gm = inp["generation_mask"].cpu().numpy()
-    us = philox_grid(seed, 0, B, K, t, orc.STREAM_SEQ)[0]
+    us = orc.philox_uniform4(seed, *lanes(0, B, K), t, orc.STREAM_SEQ)[0]
     for al in (None, allowed):
         kw = dict(seed=seed, t_start=t, t_stop=t - 1, init=False, trajectory=True, trajectory_predictions=True, allowed_aa=al)
         out = sample(model, inp, temperature=SampleTemperature(sequence=0.5), **kw)

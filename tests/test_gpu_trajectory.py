@@ -12,56 +12,19 @@ import torch
 
 from conftest import maxrel
 from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import CTX, STATE, assert_bitwise, hip, make_model, patches, rows, sample
 
 pytestmark = pytest.mark.gpu
 V = 21
-STATE = ("seq_idx", "translations", "orientations", "generation_mask")
-CTX = ("res_context_emb", "pair_context_emb")
 REC_STATE = ("seq_idx", "translations", "orientations")
 REC_PRED = ("pred_translations", "pred_orientations", "seq_probs")
 DENOISE_TOL = 1e-5  # loop vs model.denoise on the same state: the same kernels up to summation order (test_gpu_aa_constraints' margin)
 
 
 @pytest.fixture(scope="module")
-def hip():
-    lib = _hip.lib()
-    assert lib.diffab_device_ok() == 1
-    return lib
-
-
-def make_model(dims, seed, T=100):
-    from diffab_pytorch import DiffAb
-
-    torch.manual_seed(0)
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"], T=T).cuda()
-    model.denoiser.load_state_dict(syn.denoiser_state_dict(dims, seed=seed, prefix=""))
-    return model
-
-
-@pytest.fixture(scope="module")
 def bench(hip):
     dims = dict(syn.BENCH_DIMS, NL=3)
     return dims, make_model(dims, 19)
-
-
-def patches(B, K, dims, seed):
-    return {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-
-
-def sample(model, inp, **kw):
-    return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],
-                        res_context_emb=inp.get("res_context_emb"), pair_context_emb=inp.get("pair_context_emb"), **kw)
-
-
-def rows(inp, index):
-    return {k: v.index_select(0, index) for k, v in inp.items()}
-
-
-def assert_bitwise(got, want, what=""):
-    assert set(got) == set(want), (what, set(got) ^ set(want))
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, int((got[k] != want[k]).sum()))
 
 
 def final(out):

@@ -7,15 +7,15 @@ import ctypes
 import os
 import shutil
 import subprocess
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, synthetic as syn
-from diffab_pytorch.diffab_pytorch import Denoiser
+import sampler_support as support
+from diffab_pytorch import _hip
 from diffab_pytorch.guidance import SampleGuidance, structure_energy
+from sampler_support import ReachedTheLibrary, inputs, refuse_library, stand_in
 
 V, T = 21, 10
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,35 +159,18 @@ def test_shift_cap():
 
 
 # ------------------------------------------------------------------ argument checks before the library
-class ReachedTheLibrary(Exception):
-    pass
-
-
-def refuse():
-    raise ReachedTheLibrary()
-
-
 @pytest.fixture(scope="module")
 def model():
-    """DiffAb.sample bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device)."""
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], V)
-    stub = types.SimpleNamespace(denoiser=den, T=T)
-    stub.sample = types.MethodType(DiffAb.sample, stub)
-    return stub
+    return stand_in(T=T)
 
 
 @pytest.fixture(autouse=True)
 def no_library(monkeypatch):
-    monkeypatch.setattr(_hip, "lib", refuse)
-    monkeypatch.setattr(_hip, "load_library", refuse)
+    refuse_library(monkeypatch)
 
 
 def call(model, B=2, K=16, **kw):
-    gm = torch.zeros(B, K, dtype=torch.bool)
-    gm[:, 3:8] = True
-    return model.sample(torch.zeros(B, K, dtype=torch.long), torch.zeros(B, K, 3), torch.eye(3).expand(B, K, 3, 3).clone(), seed=1,
-                        generation_mask=gm, res_context_emb=torch.zeros(B, K, 128), pair_context_emb=torch.zeros(B, K, K, 64), **kw)
+    return support.call(model, inputs(B, K), **kw)
 
 
 @pytest.mark.parametrize("bad, match", [

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from diffab_pytorch import DiffAb, _hip, io as dio, patch
+from sampler_support import ReachedTheLibrary, refuse_library
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -150,18 +151,9 @@ def test_host_side_refusals_touch_no_gpu():
 
 
 # ------------------------------------------------------------------ argument errors before any device work
-class ReachedTheLibrary(AssertionError):
-    pass
-
-
-def refuse():
-    raise ReachedTheLibrary()
-
-
 @pytest.fixture
 def no_library(monkeypatch):
-    monkeypatch.setattr(_hip, "lib", refuse)
-    monkeypatch.setattr(_hip, "load_library", refuse)
+    refuse_library(monkeypatch)
 
 
 def small_batch(B=2, N=20):

@@ -3,50 +3,28 @@ validation that happens before any library call, and the workspace sizing (host-
 import ctypes as C
 import os
 import re
-import types
 
 import pytest
 import torch
 
+import sampler_support as support
 from conftest import REPO
-from diffab_pytorch import DiffAb, _hip, synthetic as syn
-from diffab_pytorch.diffab_pytorch import Denoiser
-
-
-class LibraryTouched(Exception):
-    pass
+from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import ReachedTheLibrary, inputs, refuse_library, stand_in
 
 
 @pytest.fixture(scope="module")
 def model():
-    """DiffAb.score bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device)."""
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], 21)
-    stub = types.SimpleNamespace(denoiser=den, T=10)
-    stub.score = types.MethodType(DiffAb.score, stub)
-    return stub
+    return stand_in(("score",))
 
 
 @pytest.fixture
 def no_library(monkeypatch):
-    """Every check must fire before score() reaches the library: any library access fails the test."""
-    def touched():
-        raise LibraryTouched("score() reached the library")
-
-    monkeypatch.setattr(_hip, "lib", touched)
-
-
-def inputs(R, K=16, n_ctx=None, D=128, Cp=64):
-    n_ctx = R if n_ctx is None else n_ctx
-    gm = torch.zeros(R, K, dtype=torch.bool)
-    gm[:, 3:8] = True
-    return dict(seq_idx=torch.zeros(R, K, dtype=torch.long), xyz=torch.zeros(R, K, 3), orientations=torch.eye(3).expand(R, K, 3, 3).clone(),
-                generation_mask=gm, res_context_emb=torch.zeros(n_ctx, K, D), pair_context_emb=torch.zeros(n_ctx, K, K, Cp))
+    refuse_library(monkeypatch)
 
 
 def call(model, inp, **kw):
-    inp = dict(inp)
-    return model.score(inp.pop("seq_idx"), inp.pop("xyz"), inp.pop("orientations"), seed=1, **inp, **kw)
+    return support.call(model, inp, method="score", **kw)
 
 
 def test_score_entries_are_exported_and_registered():
@@ -139,12 +117,12 @@ def test_score_asks_for_a_workspace_independent_of_designs_and_steps(model, monk
     class Fake:
         def diffab_score_workspace_bytes(self, dims, n_ctx):
             seen.append((dims._obj.B, dims._obj.K, n_ctx))
-            raise LibraryTouched()
+            raise ReachedTheLibrary()
 
     monkeypatch.setattr(_hip, "lib", lambda: Fake())
     for R, n_ctx, t, M, rows in ((8, 2, None, 4, None), (64, 2, None, 4, None), (64, 2, [1, 2], 1, None), (64, 4, None, 4, 100),
                                  (3, 3, [4], 1, 512)):
         inp = inputs(R, n_ctx=n_ctx)
-        with pytest.raises(LibraryTouched):
+        with pytest.raises(ReachedTheLibrary):
             call(model, inp, context_index=torch.arange(R) % n_ctx, t=t, num_draws=M, rows_per_launch=rows)
     assert seen == [(256, 16, 2), (256, 16, 2), (128, 16, 2), (100, 16, 4), (3, 16, 3)]

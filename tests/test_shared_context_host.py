@@ -1,37 +1,17 @@
 """CPU: the host side of shared-context sampling (DiffAb.sample(num_samples=N) / context_index, diffab_sample_options.ctx_of_row) - argument
 validation that happens before any library call, and the workspace sizing of the shared form (host-only C-ABI calls)."""
 import ctypes as C
-import types
 
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, synthetic as syn
-from diffab_pytorch.diffab_pytorch import Denoiser
+from diffab_pytorch import _hip, synthetic as syn
+from sampler_support import call, inputs, stand_in
 
 
 @pytest.fixture(scope="module")
 def model():
-    """DiffAb.sample bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device): every check
-    below must fire before sample() touches anything else - the library above all."""
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], 21)
-    stub = types.SimpleNamespace(denoiser=den, T=10)
-    stub.sample = types.MethodType(DiffAb.sample, stub)
-    return stub
-
-
-def inputs(B, K=16, n_ctx=None, D=128, Cp=64):
-    n_ctx = B if n_ctx is None else n_ctx
-    gm = torch.zeros(B, K, dtype=torch.bool)
-    gm[:, 3:8] = True
-    return dict(seq_idx=torch.zeros(B, K, dtype=torch.long), xyz=torch.zeros(B, K, 3), orientations=torch.eye(3).expand(B, K, 3, 3).clone(),
-                generation_mask=gm, res_context_emb=torch.zeros(n_ctx, K, D), pair_context_emb=torch.zeros(n_ctx, K, K, Cp))
-
-
-def call(model, inp, **kw):
-    inp = dict(inp)
-    return model.sample(inp.pop("seq_idx"), inp.pop("xyz"), inp.pop("orientations"), seed=1, **inp, **kw)
+    return stand_in()
 
 
 @pytest.mark.parametrize("n", [0, -3])

@@ -7,15 +7,15 @@ import ctypes
 import os
 import shutil
 import subprocess
-import types
 
 import numpy as np
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, distributed, synthetic as syn
-from diffab_pytorch.diffab_pytorch import Denoiser
+import sampler_support as support
+from diffab_pytorch import _hip, distributed
 from diffab_pytorch.steering import ParticleSteering, check_groups, check_steering, lineage, resample_oracle, steering_steps
+from sampler_support import ReachedTheLibrary, inputs, refuse_library, stand_in
 
 V, T = 21, 10
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,36 +116,19 @@ def test_steering_steps_and_lineage():
 
 
 # ------------------------------------------------------------------ argument checks before the library
-class ReachedTheLibrary(Exception):
-    pass
-
-
-def refuse():
-    raise ReachedTheLibrary()
-
-
 @pytest.fixture(scope="module")
 def model():
-    """DiffAb.sample bound to a stand-in with the model's dimensions only (a DiffAb builds its IGSO3 tables on the device)."""
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], V)
-    stub = types.SimpleNamespace(denoiser=den, T=T)
-    stub.sample = types.MethodType(DiffAb.sample, stub)
-    return stub
+    return stand_in(T=T)
 
 
 @pytest.fixture()
 def no_library(monkeypatch):
-    monkeypatch.setattr(_hip, "lib", refuse)
-    monkeypatch.setattr(_hip, "load_library", refuse)
+    refuse_library(monkeypatch)
 
 
 def call(model, B=2, K=16, gm=None, **kw):
-    if gm is None:
-        gm = torch.zeros(B, K, dtype=torch.bool)
-        gm[:, 3:8] = True
-    return model.sample(torch.zeros(B, K, dtype=torch.long), torch.zeros(B, K, 3), torch.eye(3).expand(B, K, 3, 3).clone(), seed=1,
-                        generation_mask=gm, res_context_emb=torch.zeros(B, K, 128), pair_context_emb=torch.zeros(B, K, K, 64), **kw)
+    inp = inputs(B, K)
+    return support.call(model, inp if gm is None else dict(inp, generation_mask=gm), **kw)
 
 
 BAD = [

@@ -3,15 +3,15 @@ broadcasting of the per-row values, the float64 restatement of the tempered draw
 and the C-ABI binding.  The device side is tests/test_gpu_temperature.py."""
 import ctypes
 import math
-import types
 
 import pytest
 import torch
 
-from diffab_pytorch import DiffAb, _hip, synthetic as syn
-from diffab_pytorch.diffab_pytorch import Denoiser
+import sampler_support as support
+from diffab_pytorch import _hip
 from diffab_pytorch.temperature import (MAX_ROTATION_SCALES, SampleTemperature, check_mode, row_values, rotation_rows, rotation_scales,
                                         stacked_sigmas, tempered_draw)
+from sampler_support import ReachedTheLibrary, inputs, refuse_library, stand_in
 
 V, T = 21, 100
 
@@ -148,35 +148,18 @@ def test_rotation_scales_are_keyed_by_their_fp32_value():
 
 
 # ------------------------------------------------------------------ DiffAb.sample: every check before device work
-class ReachedTheLibrary(Exception):
-    pass
-
-
-def refuse():
-    raise ReachedTheLibrary()
-
-
 @pytest.fixture(scope="module")
 def model():
-    d = dict(syn.BENCH_DIMS, NL=1)
-    den = Denoiser(d["D"], d["C"], d["NL"], d["DS"], d["PQ"], d["PV"], d["H"], V)
-    stub = types.SimpleNamespace(denoiser=den, T=T)
-    stub.sample = types.MethodType(DiffAb.sample, stub)
-    return stub
+    return stand_in(T=T)
 
 
 @pytest.fixture(autouse=True)
 def no_library(monkeypatch):
-    monkeypatch.setattr(_hip, "lib", refuse)
-    monkeypatch.setattr(_hip, "load_library", refuse)
+    refuse_library(monkeypatch)
 
 
 def call(model, B=2, K=16, n_ctx=None, **kw):
-    gm = torch.zeros(B, K, dtype=torch.bool)
-    gm[:, 3:8] = True
-    n_ctx = B if n_ctx is None else n_ctx
-    return model.sample(torch.zeros(B, K, dtype=torch.long), torch.zeros(B, K, 3), torch.eye(3).expand(B, K, 3, 3).clone(), seed=1,
-                        generation_mask=gm, res_context_emb=torch.zeros(n_ctx, K, 128), pair_context_emb=torch.zeros(n_ctx, K, K, 64), **kw)
+    return support.call(model, inputs(B, K, n_ctx), **kw)
 
 
 @pytest.mark.parametrize("temp, kw, match", [

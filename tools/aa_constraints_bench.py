@@ -12,116 +12,49 @@ Reported per case: median / min / max ms per step over --repeats rounds.  Prints
 
     python tools/aa_constraints_bench.py [--steps 100 --warmup 5 --repeats 5 --rows 256 --k 128] [--cases free,all,no_cmx] [--json OUT]
 """
-import argparse
-import ctypes as C
-import json
-import os
-import sys
+import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
-
-import torch  # noqa: E402
+from sampler_bench_common import SamplerRun, bench_model, case_names, emit, parser, rounds, stats
 
 CASES = ("free", "all", "no_cmx")
 
 
-def random_rotations(n, g):
-    q = torch.randn(n, 4, device="cuda", generator=g)
-    w, x, y, z = (q / q.norm(dim=-1, keepdim=True)).unbind(-1)
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                        2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).view(n, 3, 3)
-
-
-def stats(runs):
-    s = sorted(runs)
-    med = s[len(s) // 2]
-    return med, {"median": round(med, 4), "min": round(s[0], 4), "max": round(s[-1], 4), "spread_pct": round(100 * (s[-1] - s[0]) / med, 2),
-                 "runs": [round(r, 4) for r in runs]}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--rows", type=int, default=256, help="patches (state rows) per call")
-    ap.add_argument("--k", type=int, default=128)
-    ap.add_argument("--cases", default=",".join(CASES), help=f"comma-separated subset of {','.join(CASES)}")
-    ap.add_argument("--json", help="also write the result here")
-    args = ap.parse_args()
+    args = parser(CASES).parse_args()
     R, K = args.rows, args.k
-    names = args.cases.split(",")
-    if not names or any(n not in CASES for n in names):
-        raise SystemExit(f"--cases: expected a comma-separated subset of {','.join(CASES)}")
+    names = case_names(args, CASES)
 
-    from diffab_pytorch import DiffAb, _hip, io, synthetic as syn
+    from diffab_pytorch import _hip, io
     from diffab_pytorch.diffab_pytorch import _pack_allowed_aa
 
-    lib = _hip.lib()
-    dims = dict(syn.BENCH_DIMS)
-    torch.manual_seed(0)  # bench.py's model: default init of the boundary module
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
+    dims, model = bench_model()
     T = model.T
     if not (1 <= args.steps <= T and 0 <= args.warmup <= T and args.repeats >= 1):
         raise SystemExit(f"need 1 <= --steps <= T = {T}, 0 <= --warmup <= T and --repeats >= 1")
-    g = torch.Generator(device="cuda").manual_seed(0)
-    res = torch.randn(R, K, dims["D"], device="cuda", generator=g)
-    pair = torch.randn(R, K, K, dims["C"], device="cuda", generator=g)
-    seq0 = torch.randint(0, 20, (R, K), device="cuda", generator=g)
-    x0 = 10 * torch.randn(R, K, 3, device="cuda", generator=g)
-    O0 = random_rotations(R * K, g).view(R, K, 3, 3).contiguous()
-    start = torch.randint(0, K - 20, (R, 1), device="cuda", generator=g)
-    length = torch.randint(5, 21, (R, 1), device="cuda", generator=g)
-    pos = torch.arange(K, device="cuda")[None]
-    gm = ((pos >= start) & (pos < start + length)).contiguous()
+    run = SamplerRun(model, dims, R, K)
+    gm = run.gm
     V = model.denoiser.dims["V"]
     masks = {"free": None, "all": _pack_allowed_aa(torch.ones(R, K, V, dtype=torch.bool, device="cuda")),
              "no_cmx": _pack_allowed_aa(io.allowed_aa_mask(K, exclude="CMX", V=V).cuda().expand(R, K, V))}
 
-    hd = model.denoiser.hip_dims(R, K)
-    w = model.denoiser.hip_weights()
-    sd = model._sched_on_device()
-    tab = model._reverse_so3().struct()
-    ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(hd)))
-    seed = 2024
-    seq, x, O = seq0.clone(), x0.clone(), O0.clone()
-
     def init(words):
-        seq.copy_(seq0), x.copy_(x0), O.copy_(O0)
-        _hip.check(lib.diffab_sample_init_ex(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, 0, R, K, T, 0, _hip.ptr(words),
-                                             _hip.stream_ptr()), "sample_init_ex")
+        run.reset()
+        _hip.check(run.lib.diffab_sample_init_ex(*run.state_ptrs(), run.seed, 0, R, K, T, 0, _hip.ptr(words), _hip.stream_ptr()),
+                   "sample_init_ex")
 
     def loop(words, t_start, t_stop):
-        opt = None if words is None else C.byref(_hip.SampleOptions(allowed=_hip.ptr(words)))
-        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
-                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, t_start, t_stop, _hip.ptr(ws),
-                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
-
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        ev0.record()
-        fn()
-        ev1.record()
-        torch.cuda.synchronize()
-        if not (torch.isfinite(x).all() and torch.isfinite(O).all()):
-            raise SystemExit("non-finite state")
-        return ev0.elapsed_time(ev1)
+        run.loop(t_start, t_stop, None if words is None else dict(allowed=_hip.ptr(words)))
 
     runs = {n: [] for n in names}
     final = {}
-    for rep in range(args.repeats):
-        for n in (names if rep % 2 == 0 else names[::-1]):
-            words = masks[n]
-            init(words)
-            if args.warmup:
-                loop(words, T, T - args.warmup)
-            init(words)
-            runs[n].append(timed(lambda: loop(words, T, T - args.steps)) / args.steps)
-            final[n] = seq.clone()
+    for _, n in rounds(names, args.repeats):
+        words = masks[n]
+        init(words)
+        if args.warmup:
+            loop(words, T, T - args.warmup)
+        init(words)
+        runs[n].append(run.timed(lambda: loop(words, T, T - args.steps)) / args.steps)
+        final[n] = run.seq.clone()
     out = {"what": "reverse sampler with sequence constraints: ms per step, unconstrained / all-true mask / C, M, UNK excluded",
            "rows": R, "k": K, "T": T, "steps": args.steps, "warmup": args.warmup, "repeats": args.repeats,
            "device": torch.cuda.get_device_name(), "cases": []}
@@ -133,10 +66,7 @@ def main():
     for n in names:
         med, st = stats(runs[n])
         out["cases"].append({"case": n, "ms_per_step": st, f"vs_{names[0]}_pct": round(100 * (med - ref) / ref, 2)})
-    print(json.dumps(out))
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
+    emit(out, args.json)
 
 
 if __name__ == "__main__":

@@ -27,7 +27,8 @@ sys.path.insert(0, os.path.join(REPO, "tools"))
 
 import torch  # noqa: E402
 
-from metrics_bench import designs_of, stats  # noqa: E402
+from metrics_bench import designs_of  # noqa: E402
+from sampler_bench_common import stats_ms, timed  # noqa: E402
 
 ATOMS = ("N", "CA", "C", "O", "CB")
 GLY = 7  # index of GLY in io.AA3
@@ -87,21 +88,11 @@ def torch_backbone(designs):
             dih(ca[:, :-1], c[:, :-1], n[:, 1:], ca[:, 1:]), (c[:, :-1] - n[:, 1:]).norm(dim=-1).float())
 
 
-def once(fn):
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
-
-
 def alternate(hip, other, warmup, repeats):
     for _ in range(warmup):
         hip()
         other()
-    runs = [(once(hip), once(other)) for _ in range(repeats)]
+    runs = [(timed(hip), timed(other)) for _ in range(repeats)]
     return [r[0] for r in runs], [r[1] for r in runs]
 
 
@@ -131,11 +122,11 @@ def main():
         out = hip_c()
         ref = torch_contacts(designs, gm, ctx, antigen, N, tr)
         pairs = float(args.counted * 5 * int((ctx["atom_mask"] & ~gm[..., None]).sum()) / G) * rows
-        c = {"hip": stats(c_hip), "torch": dict(stats(c_torch, rows / tr), measured_on_rows=tr), "context_distances": pairs}
+        c = {"hip": stats_ms(c_hip), "torch": dict(stats_ms(c_torch, rows / tr), measured_on_rows=tr), "context_distances": pairs}
         c["torch_over_hip"] = round(c["torch"]["median_ms"] / c["hip"]["median_ms"], 2)
         c["context_distances_per_s"] = round(pairs / (c["hip"]["median_ms"] * 1e-3), 0)
         c["rows_where_torch_contact_pairs_differ"] = int((ref[3] != out["n_contact_pairs"][:tr]).sum())
-        b = {"hip": stats(b_hip), "torch": stats(b_torch)}
+        b = {"hip": stats_ms(b_hip), "torch": stats_ms(b_torch)}
         b["torch_over_hip"] = round(b["torch"]["median_ms"] / b["hip"]["median_ms"], 2)
         for r in (c, b):
             r["hip_over_sampler_step"] = round(r["hip"]["median_ms"] / args.step_ms, 3) if args.step_ms else "not measured"

@@ -24,6 +24,8 @@ sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
 
 import torch  # noqa: E402
 
+from sampler_bench_common import stats_ms, timed_repeats  # noqa: E402
+
 HBM_PEAK = 8.0e12  # B/s, the figure the output-write floor is set against
 
 
@@ -83,28 +85,10 @@ def torch_aligned(designs, gm, N, atoms, groups, chunk=128):
     return rmsd
 
 
-def timed(fn, repeats):
-    out = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
-
-
-def stats(runs, scale=1.0):
-    s = sorted(r * scale for r in runs)
-    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "max_ms": round(s[-1], 4), "repeats": len(s)}
-
-
 def measure(fn, warmup, repeats, scale=1.0):
     for _ in range(warmup):
         fn()
-    return stats(timed(fn, repeats), scale)
+    return stats_ms(timed_repeats(fn, repeats), scale)
 
 
 def main():

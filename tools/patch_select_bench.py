@@ -21,6 +21,8 @@ sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
 
 import torch  # noqa: E402
 
+from sampler_bench_common import stats_ms, timed_repeats  # noqa: E402
+
 FIELDS = ("seq_idx", "xyz", "orientations", "backbone_dihedrals", "atom_mask", "chain_idx", "residue_mask", "generation_mask", "antigen_mask")
 
 
@@ -73,24 +75,6 @@ def torch_gather(batch, index):
     return {n: batch[n][rows, safe] * live.view(*live.shape, *([1] * (batch[n].dim() - 2))).to(batch[n].dtype) for n in FIELDS}
 
 
-def timed(fn, repeats):
-    out = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b))
-    return out
-
-
-def stats(runs):
-    s = sorted(runs)
-    return {"median_ms": round(s[len(s) // 2], 4), "min_ms": round(s[0], 4), "max_ms": round(s[-1], 4), "repeats": len(s)}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, default=256)
@@ -122,8 +106,8 @@ def main():
                 fn()
         for r in range(args.repeats):  # alternate the cases, the order reversed every other round
             for n in (list(cases) if r % 2 == 0 else list(cases)[::-1]):
-                runs[n] += timed(cases[n], 1)
-        res["cases"][f"N={N}"] = {"index_slots_equal_to_torch_expression": round(same, 6), **{n: stats(v) for n, v in runs.items()}}
+                runs[n] += timed_repeats(cases[n], 1)
+        res["cases"][f"N={N}"] = {"index_slots_equal_to_torch_expression": round(same, 6), **{n: stats_ms(v) for n, v in runs.items()}}
         g = patch.gather({n: v[:16] for n, v in batch.items()}, patch.PatchIndex(sel.index[:16], sel.mask[:16], sel.count[:16]))
     # for scale: one encode_context call on 16 of the gathered patches (K = 256), benchmark dimensions
     d = syn.BENCH_DIMS
@@ -135,7 +119,7 @@ def main():
     with torch.no_grad():
         for _ in range(args.warmup):
             enc()
-        res["encode_context_16_patches_K256"] = stats(timed(enc, args.repeats))
+        res["encode_context_16_patches_K256"] = stats_ms(timed_repeats(enc, args.repeats))
     print(json.dumps(res, indent=1))
     if args.json:
         with open(args.json, "w") as f:

@@ -15,78 +15,28 @@ kernel trace per case: rocprofv3 --kernel-trace --stats -- python tools/respaced
 
     python tools/respaced_bench.py [--warmup 5 --repeats 5 --rows 256 --k 128] [--cases off,n100,...] [--json OUT]
 """
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
+import torch
 
-import torch  # noqa: E402
+from sampler_bench_common import SamplerRun, bench_model, case_names, emit, parser, rounds, stats
 
 CASES = ("off", "n100", "n50", "n20", "n10")
 
 
-def random_rotations(n, g):
-    q = torch.randn(n, 4, device="cuda", generator=g)
-    w, x, y, z = (q / q.norm(dim=-1, keepdim=True)).unbind(-1)
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                        2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).view(n, 3, 3)
-
-
-def stats(runs, nd=4):
-    s = sorted(runs)
-    med = s[len(s) // 2]
-    return med, {"median": round(med, nd), "min": round(s[0], nd), "max": round(s[-1], nd),
-                 "spread_pct": round(100 * (s[-1] - s[0]) / med, 2), "runs": [round(r, nd) for r in runs]}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--rows", type=int, default=256, help="patches (state rows) per call")
-    ap.add_argument("--k", type=int, default=128)
-    ap.add_argument("--cases", default=",".join(CASES), help=f"comma-separated subset of {','.join(CASES)}")
-    ap.add_argument("--json", help="also write the result here")
-    args = ap.parse_args()
+    args = parser(CASES, steps=False).parse_args()
     R, K = args.rows, args.k
-    names = args.cases.split(",")
-    if not names or any(n not in CASES for n in names):
-        raise SystemExit(f"--cases: expected a comma-separated subset of {','.join(CASES)}")
+    names = case_names(args, CASES)
 
-    from diffab_pytorch import DiffAb, _hip, synthetic as syn
+    from diffab_pytorch import _hip
     from diffab_pytorch.diffusion import even_steps, jump_coefficients
 
-    lib = _hip.lib()
-    dims = dict(syn.BENCH_DIMS)
-    torch.manual_seed(0)  # bench.py's model: default init of the boundary module
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
+    dims, model = bench_model()
     T = model.T
     if not (0 <= args.warmup <= T and args.repeats >= 1):
         raise SystemExit(f"need 0 <= --warmup <= T = {T} and --repeats >= 1")
-    g = torch.Generator(device="cuda").manual_seed(0)
-    res = torch.randn(R, K, dims["D"], device="cuda", generator=g)
-    pair = torch.randn(R, K, K, dims["C"], device="cuda", generator=g)
-    seq0 = torch.randint(0, 20, (R, K), device="cuda", generator=g)
-    x0 = 10 * torch.randn(R, K, 3, device="cuda", generator=g)
-    O0 = random_rotations(R * K, g).view(R, K, 3, 3).contiguous()
-    start = torch.randint(0, K - 20, (R, 1), device="cuda", generator=g)
-    length = torch.randint(5, 21, (R, 1), device="cuda", generator=g)
-    pos = torch.arange(K, device="cuda")[None]
-    gm = ((pos >= start) & (pos < start + length)).contiguous()
-
-    hd = model.denoiser.hip_dims(R, K)
-    w = model.denoiser.hip_weights()
-    sd = model._sched_on_device()
-    tab0 = model._reverse_so3().struct()
-    ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(hd)))
-    seed = 2024
-    seq, x, O = seq0.clone(), x0.clone(), O0.clone()
-
+    run = SamplerRun(model, dims, R, K)
     plans = {}
     for n in names:
         if n == "off":
@@ -98,48 +48,27 @@ def main():
         host = ((C.c_int32 * steps.numel())(*steps.tolist()), (C.c_float * (T + 1))(*bj.tolist()), (C.c_float * (T + 1))(*aj.tolist()))
         plans[n] = (_hip.SampleSteps(steps.numel(), *host, _hip.ptr(plan_dev)), so3.struct(), steps.numel(), (host, plan_dev, so3))
 
-    def init():
-        seq.copy_(seq0), x.copy_(x0), O.copy_(O0)
-        _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), seed, 0, R, K, T, _hip.stream_ptr()),
-                   "sample_init")
-
     def loop(n, t_stop=0):
         if n == "off":
-            tab, opt = tab0, None
+            run.loop(T, t_stop)
         else:
             st, tab = plans[n][:2]
-            t_stop, opt = 0, C.byref(_hip.SampleOptions(steps=st))
-        _hip.check(lib.diffab_sample_loop_ex(C.byref(hd), C.byref(w.struct), C.byref(sd.struct), C.byref(tab), _hip.ptr(seq), _hip.ptr(x),
-                                             _hip.ptr(O), _hip.ptr(res), _hip.ptr(pair), _hip.ptr(gm), seed, 0, T, t_stop, _hip.ptr(ws),
-                                             ws.numel(), 0, opt, _hip.stream_ptr()), "diffab_sample_loop_ex")
-
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        ev0.record()
-        fn()
-        ev1.record()
-        torch.cuda.synchronize()
-        if not (torch.isfinite(x).all() and torch.isfinite(O).all()):
-            raise SystemExit("non-finite state")
-        return ev0.elapsed_time(ev1)
+            run.loop(T, 0, dict(steps=st), tab=tab)
 
     runs = {n: [] for n in names}
     final = {}
-    for rep in range(args.repeats):
-        for n in (names if rep % 2 == 0 else names[::-1]):
-            if args.warmup:
-                init()
-                loop("off", T - args.warmup)
-            init()
-            runs[n].append(timed(lambda: loop(n)))
-            final[n] = (seq.clone(), x.clone(), O.clone())
+    for _, n in rounds(names, args.repeats):
+        if args.warmup:
+            run.init()
+            loop("off", T - args.warmup)
+        run.init()
+        runs[n].append(run.timed(lambda: loop(n)))
+        final[n] = run.final()
     out = {"what": "fewer-step reverse sampling: ms per call of a whole reverse run from t = T, ms per executed step, designs per second",
-           "rows": R, "k": K, "T": T, "warmup": args.warmup, "repeats": args.repeats, "generated_residues": int(gm.sum()),
+           "rows": R, "k": K, "T": T, "warmup": args.warmup, "repeats": args.repeats, "generated_residues": int(run.gm.sum()),
            "device": torch.cuda.get_device_name(), "cases": []}
     if "off" in final and "n100" in final:
-        out["n100_final_state_bitwise_off"] = all(torch.equal(a, b) for a, b in zip(final["n100"], final["off"]))
+        out["n100_final_state_bitwise_off"] = all(torch.equal(final["n100"][k], final["off"][k]) for k in final["off"])
     ref = stats(runs[names[0]])[0]
     for n in names:
         med, st_call = stats(runs[n], 3)
@@ -147,10 +76,7 @@ def main():
         _, st_step = stats([r / n_exec for r in runs[n]])
         out["cases"].append({"case": n, "executed_steps": n_exec, "ms_per_call": st_call, "ms_per_step": st_step,
                              "designs_per_s": round(R / (med / 1e3), 1), f"speedup_vs_{names[0]}": round(ref / med, 3)})
-    print(json.dumps(out))
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
+    emit(out, args.json)
 
 
 if __name__ == "__main__":

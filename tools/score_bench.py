@@ -14,38 +14,10 @@ Reported per variant: median / min / max over --repeats rounds.  Prints one JSON
 import argparse
 import ctypes as C
 import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
+import torch
 
-import torch  # noqa: E402
-
-
-def random_rotations(n, g):
-    q = torch.randn(n, 4, device="cuda", generator=g)
-    w, x, y, z = (q / q.norm(dim=-1, keepdim=True)).unbind(-1)
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                        2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).view(n, 3, 3)
-
-
-def stats(runs):
-    s = sorted(runs)
-    med = s[len(s) // 2]
-    return med, {"median": round(med, 4), "min": round(s[0], 4), "max": round(s[-1], 4), "spread_pct": round(100 * (s[-1] - s[0]) / med, 2),
-                 "runs": [round(r, 4) for r in runs]}
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b)
+from sampler_bench_common import bench_model, device_inputs, stats, timed
 
 
 def main():
@@ -63,25 +35,14 @@ def main():
     K, n_ctx, N = args.k, args.contexts, args.designs
     R = n_ctx * N
 
-    from diffab_pytorch import DiffAb, _hip, synthetic as syn
+    from diffab_pytorch import _hip
 
     lib = _hip.lib()
-    dims = dict(syn.BENCH_DIMS)
-    torch.manual_seed(0)  # bench.py's model: default init of the boundary module
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
+    dims, model = bench_model()
     T = model.T
     grid = list(range(1, T + 1, args.grid_step))
-    g = torch.Generator(device="cuda").manual_seed(0)
-    res = torch.randn(n_ctx, K, dims["D"], device="cuda", generator=g)
-    pair = torch.randn(n_ctx, K, K, dims["C"], device="cuda", generator=g)
+    res, pair, seq0, x0, O0, gm = device_inputs(dims, R, K, n_ctx=n_ctx).values()
     ci = torch.arange(n_ctx).repeat_interleave(N)
-    seq0 = torch.randint(0, 20, (R, K), device="cuda", generator=g)
-    x0 = 10 * torch.randn(R, K, 3, device="cuda", generator=g)
-    O0 = random_rotations(R * K, g).view(R, K, 3, 3).contiguous()
-    start = torch.randint(0, K - 20, (R, 1), device="cuda", generator=g)
-    length = torch.randint(5, 21, (R, 1), device="cuda", generator=g)
-    pos = torch.arange(K, device="cuda")[None]
-    gm = ((pos >= start) & (pos < start + length)).contiguous()
     rows_total = R * len(grid)
 
     def score(rows, shared=True):

@@ -12,21 +12,10 @@ residue-steps/s at the median, the workspace bytes and the context bytes held.  
 import argparse
 import ctypes as C
 import json
-import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(REPO, "diffab-pytorch_amd"))
+import torch
 
-import torch  # noqa: E402
-
-
-def random_rotations(n, g):
-    q = torch.randn(n, 4, device="cuda", generator=g)
-    w, x, y, z = (q / q.norm(dim=-1, keepdim=True)).unbind(-1)
-    return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
-                        2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).view(n, 3, 3)
+from sampler_bench_common import bench_model, device_inputs
 
 
 def main():
@@ -44,25 +33,14 @@ def main():
     if any(R % n for n in ns) or args.steps < 1 or args.warmup < 0:
         raise SystemExit(f"every N of --ns must divide --rows {R}; --steps >= 1")
 
-    from diffab_pytorch import DiffAb, _hip, synthetic as syn
+    from diffab_pytorch import _hip
 
     lib = _hip.lib()
-    dims = dict(syn.BENCH_DIMS)
-    torch.manual_seed(0)  # bench.py's model: default init of the boundary module
-    model = DiffAb(dims["D"], dims["C"], dims["NL"], dims["DS"], dims["PQ"], dims["PV"], dims["H"]).cuda()
+    dims, model = bench_model()
     if args.steps > model.T or args.warmup > model.T:
         raise SystemExit(f"--steps and --warmup must be <= T = {model.T}")
-    g = torch.Generator(device="cuda").manual_seed(0)
     # R contexts (variant N uses the first R / N) and one seeded state of R rows, shared by every variant
-    res_all = torch.randn(R, K, dims["D"], device="cuda", generator=g)
-    pair_all = torch.randn(R, K, K, dims["C"], device="cuda", generator=g)
-    seq0 = torch.randint(0, 20, (R, K), device="cuda", generator=g)
-    x0 = 10 * torch.randn(R, K, 3, device="cuda", generator=g)
-    O0 = random_rotations(R * K, g).view(R, K, 3, 3).contiguous()
-    start = torch.randint(0, K - 20, (R, 1), device="cuda", generator=g)
-    length = torch.randint(5, 21, (R, 1), device="cuda", generator=g)
-    pos = torch.arange(K, device="cuda")[None]
-    gm = ((pos >= start) & (pos < start + length)).contiguous()
+    res_all, pair_all, seq0, x0, O0, gm = device_inputs(dims, R, K).values()
 
     hd = model.denoiser.hip_dims(R, K)
     w = model.denoiser.hip_weights()
