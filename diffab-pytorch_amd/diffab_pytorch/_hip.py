@@ -214,6 +214,9 @@ SYMBOLS = {
     #  chain, residue_idx, rows, group_size, K, P, A, clash_distance, contact_distance, n_clash, clash_score, min_distance, n_contact_pairs,
     #  n_paratope, n_epitope, n_hotspot_contacted, n_hotspot, residue_clash, residue_contact, workspace, workspace_bytes, stream)
     "diffab_metrics_contacts": (C.c_int, [_fp] * 10 + [_i32] * 5 + [C.c_float] * 2 + [_fp] * 11 + [_sz, _fp]),
+    # (seq_idx, points, generation_mask, residue_mask (nullable), weights (nullable), G, N, K, P, V, pseudocount, aa_freq, entropy, consensus,
+    #  mean_points, rmsf, log_prob, consensus_identity, rmsd_to_mean, n_eff, central (each nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_ensemble": (C.c_int, [_fp] * 5 + [_i32] * 5 + [C.c_double] + [_fp] * 11 + [_sz, _fp]),
     "diffab_orientation_loss": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp]),
     "diffab_orientation_loss_bwd": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "diffab_frames_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),

@@ -4,14 +4,16 @@
 ``pairwise``        per patch: the N x N RMSD and sequence-identity matrices of its N designs;
 ``select_diverse``  greedy farthest-point choice of m designs per patch from such a matrix;
 ``backbone``        per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
-``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen.
+``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
+``ensemble``        per patch: its N designs as a distribution - amino-acid frequencies, entropy, consensus, mean structure, RMSF, and
+                    how typical each design is of its siblings (``csrc/ensemble_kernels.hip``).
 
 Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` returns them - ``seq_idx`` (rows,K), ``translations``
 (rows,K,3), ``orientations`` (rows,K,3,3) with ``rows = G * group_size``, row ``g * group_size + r`` = design r of patch g - and the masks
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
-the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` in
-``include/diffab_hip.h``; every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip`` and ``csrc/geometry_kernels.hip``
-(the filters) and there is no torch fallback.
+the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` in
+``include/diffab_hip.h``; every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip``
+(the filters) and ``csrc/ensemble_kernels.hip``, and there is no torch fallback.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ from .io import AA3, BACKBONE_ATOMS, backbone_from_frames
 MAX_GROUP = 4096  # DIFFAB_METRICS_MAX_GROUP: designs per patch
 MAX_K = 4096  # DIFFAB_METRICS_MAX_K
 MAX_SEGMENTS = 8  # DIFFAB_METRICS_MAX_SEGMENTS
+MAX_CLASSES = 32  # DIFFAB_METRICS_MAX_CLASSES: amino-acid classes of ensemble
 ATOMS = {"ca": None, "backbone": ("N", "CA", "C", "O")}
 MAX_CONTEXT_ATOMS = 32  # DIFFAB_METRICS_MAX_CONTEXT_ATOMS: atom slots per context residue
 CONTACTS_CHUNK_ATOMS = 1024  # DIFFAB_METRICS_CONTACTS_CHUNK_ATOMS: context atoms the contacts kernel stages in LDS per pass
@@ -349,4 +352,59 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
                                            _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, P, A, clash, contact,
                                            *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
                "diffab_metrics_contacts")
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ design ensembles
+def ensemble_workspace_bytes(G: int, N: int, K: int, P: int, V: int) -> int:
+    """DIFFAB_METRICS_ENSEMBLE_WORKSPACE_BYTES of include/diffab_hip.h."""
+    return G * 8 * ((N + 127) // 128 * K * (V + 3 * P + 1) + K * (V + 3 * P) + N * ((K + 63) // 64) * 3 + 1) + G * 4 * (K + 1) + 4096
+
+
+def ensemble(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, group_size: int, residue_mask: Optional[torch.Tensor] = None,
+             weights: Optional[torch.Tensor] = None, atoms: str = "ca", num_classes: int = 21,
+             pseudocount: float = 0.0) -> Dict[str, torch.Tensor]:
+    """The N = ``group_size`` designs of each patch as a distribution.  ``designs``, the masks and ``atoms`` as for ``pairwise``;
+    ``weights`` (G,N) or (rows,) float, finite and >= 0 (default all ones; a negative or non-finite weight counts as 0) - for instance
+    ``torch.softmax(samples['steering']['log_weight'].view(G, N), 1)`` of a steered run, or a 0 / 1 mask of the designs that passed
+    ``backbone`` / ``contacts`` or belong to one cluster.  V = ``num_classes`` in [1, 32]; ``pseudocount`` a >= 0.
+
+    Per position, at the positions inside ``residue_mask`` (elsewhere NaN / -1): ``aa_freq`` (G,K,V) = (c_v + a/V) / (W_k + a) with c_v
+    the weight of the designs whose token is v (a token outside [0, V) is in no class) and W_k their sum, NaN where W_k + a = 0;
+    ``entropy`` (G,K) in nats; ``consensus`` (G,K) int64, the smallest most frequent class, -1 where W_k = 0; ``mean_points``
+    (G,K,P,3), the weighted mean in the patch frame (nothing is superposed), NaN where all weights are 0; ``rmsf`` (G,K) =
+    sqrt(sum_r w_r sum_a |p - mean|^2 / (W P)).  Per design (rows,), over the counted positions of its patch (NaN without one):
+    ``log_prob`` = the mean of ln aa_freq at the design's own tokens (-inf where that frequency is 0), ``consensus_identity``,
+    ``rmsd_to_mean``.  Per patch: ``n_eff`` (G,) = W^2 / sum w^2, and ``central`` (G,) int64, the design of positive weight closest to
+    the mean (lowest ``rmsd_to_mean``, ties to the lower index; -1 without one).  The definition is the comment of
+    ``diffab_metrics_ensemble`` in ``include/diffab_hip.h``: fp64 sums in a fixed order, rounded once.  One C-ABI call (four launches);
+    results on the device of ``designs['seq_idx']``; ValueError naming the argument before any device work."""
+    who = "metrics.ensemble()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, atoms)
+    N = group_size
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or not weights.is_floating_point():
+            raise ValueError(f"{who}: weights must be a float tensor {(G, N)} or {(rows,)}")
+        if tuple(weights.shape) not in ((G, N), (rows,)):
+            raise ValueError(f"{who}: weights is {tuple(weights.shape)}, expected {(G, N)} or {(rows,)}")
+    if not _is_int(num_classes) or num_classes < 1 or num_classes > MAX_CLASSES:
+        raise ValueError(f"{who}: num_classes = {num_classes!r} outside [1, {MAX_CLASSES}]")
+    if isinstance(pseudocount, bool) or not isinstance(pseudocount, (int, float)) or not math.isfinite(pseudocount) or pseudocount < 0:
+        raise ValueError(f"{who}: pseudocount must be a finite number >= 0, got {pseudocount!r}")
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    P, V = 1 if atoms == "ca" else len(ATOMS[atoms]), num_classes
+    seq, pts = _hip.dev_i64(designs["seq_idx"]), _points(designs, atoms)
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    w = None if weights is None else _hip.dev_f32(weights).reshape(rows)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = {"aa_freq": f32(G, K, V), "entropy": f32(G, K), "consensus": torch.empty(G, K, dtype=torch.int64, device=dev),
+           "mean_points": f32(G, K, P, 3), "rmsf": f32(G, K), "log_prob": f32(rows), "consensus_identity": f32(rows),
+           "rmsd_to_mean": f32(rows), "n_eff": f32(G), "central": torch.empty(G, dtype=torch.int64, device=dev)}
+    nbytes = ensemble_workspace_bytes(G, N, K, P, V)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_ensemble(_hip.ptr(seq), _hip.ptr(pts), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(w), G, N, K, P, V, float(pseudocount),
+                                           *[_hip.ptr(t) for t in out.values()], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
+               "diffab_metrics_ensemble")
     return {k: v.to(out_dev) for k, v in out.items()}

@@ -606,6 +606,53 @@ int diffab_metrics_contacts(const float* points, const uint8_t* valid, const flo
                             int32_t* n_hotspot_contacted, int32_t* n_hotspot, int32_t* residue_clash, int32_t* residue_contact,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Design ensembles: the N designs of a patch as a distribution.  Rows, groups, points and masks as in "Common
+ * layout" above (rows = G * N, row g * N + r = design r of group g, points (rows,K,P,3), masks (G,K)).
+ * diffab_metrics_ensemble: weights (rows) fp32 or NULL (all 1): one weight w_r per design, the caller's contract like other per-row device
+ * data (softmax of steering's log_weight, or a 0 / 1 mask of the designs that passed a filter); a negative or non-finite weight is 0, and a
+ * design of weight 0 is not read for the sums over designs.  V classes, 1 <= V <= DIFFAB_METRICS_MAX_CLASSES; a = pseudocount, finite, >= 0.
+ * A position (g,k) is INSIDE when residue_mask[g,k] holds (NULL: every position) and COUNTED when it is inside and generated.  Every sum
+ * over designs, residues or atoms is taken in fp64 from the fp32 / int64 inputs; every float output is that fp64 rounded once to fp32.
+ *
+ * Per position, defined at inside positions (elsewhere the float outputs are NaN and consensus is -1):
+ *   c_v = sum_r w_r [s_rk = v] for v in [0, V) - a token outside [0, V) is in no class - and W_k = sum_v c_v;
+ *   aa_freq (G,K,V) fp32: f_v = (c_v + a / V) / (W_k + a); all V entries NaN where W_k + a = 0;
+ *   entropy (G,K) fp32:   - sum_v f_v ln f_v in nats with 0 ln 0 = 0; NaN where f is NaN;
+ *   consensus (G,K) int64: the smallest v with the largest c_v; -1 where W_k = 0;
+ *   mean_points (G,K,P,3) fp32: m = sum_r w_r p_r / W with W = sum_r w_r over the group's designs; NaN where W = 0;
+ *   rmsf (G,K) fp32: sqrt(sum_r w_r sum_a |p_rka - m_ka|^2 / (W P)) with m the fp64 mean before rounding and the sum taken in a second
+ *                    pass over the designs (never sum p^2 - (sum p)^2, which cancels).
+ * Per design (rows) fp32, over the n counted positions of the design's patch; NaN for a patch without a counted position:
+ *   log_prob           = the mean of ln f_k(s_rk) with the fp64 f; a term is -inf where the token is outside [0, V) or f is 0, and NaN
+ *                        where the token is a class and f is NaN;
+ *   consensus_identity = (float)count / (float)n, count = counted positions with s_rk = consensus_k (a position without a consensus,
+ *                        W_k = 0, matches no token);
+ *   rmsd_to_mean       = sqrt(sum_k sum_a |p - m|^2 / (n P)); NaN where W = 0.
+ * Per patch:
+ *   n_eff (G) fp32:    W^2 / sum_r w_r^2; NaN where W = 0;
+ *   central (G) int64: the design r in [0, N) with w_r > 0 whose fp32 rmsd_to_mean is smallest, ties to the lower r, a NaN never wins;
+ *                      -1 if there is none.
+ * Nothing is superposed before the average (the framework is fixed: the in-place number is the meaningful one, as for rmsd above).
+ * residue_mask and weights may be NULL; any output pointer may be NULL (that output is not wanted; without rmsf, the three per-design
+ * outputs and central the second pass is not run).  Limits, DIFFAB_ERR_ARG before anything is enqueued: N, K, P as in "Common layout",
+ * V and a as above, null seq_idx / points / generation_mask, a workspace that is NULL or not 16-byte aligned (too small:
+ * DIFFAB_ERR_WORKSPACE).  G = 0 succeeds without looking at a pointer.
+ * Fixed reduction order, no atomics: N is cut into slices of 128 designs and K into chunks of 64 residues; a work-group of four waves
+ * takes one (group, slice, chunk), lane = residue, wave w the designs w, w + 4, ... of the slice; the waves are added in wave order, the
+ * slices in slice order, the chunks in chunk order, the lanes of a wave through one fixed butterfly.  A group's results depend on that
+ * group alone.  Four launches: accumulate, finish, deviations, rows.
+ * workspace: DIFFAB_METRICS_ENSEMBLE_WORKSPACE_BYTES(G, N, K, P, V) bytes: the slices' partial sums, ln f and the mean in fp64, and the
+ * per-design partial sums of every chunk. */
+#define DIFFAB_METRICS_MAX_CLASSES (32)
+#define DIFFAB_METRICS_ENSEMBLE_WORKSPACE_BYTES(G, N, K, P, V)                                                                    \
+  ((size_t)(G) * 8 * ((((size_t)(N) + 127) / 128) * (size_t)(K) * ((size_t)(V) + 3 * (size_t)(P) + 1) +                          \
+                      (size_t)(K) * ((size_t)(V) + 3 * (size_t)(P)) + (size_t)(N) * (((size_t)(K) + 63) / 64) * 3 + 1) +          \
+   (size_t)(G) * 4 * ((size_t)(K) + 1) + 4096)
+int diffab_metrics_ensemble(const int64_t* seq_idx, const float* points, const uint8_t* generation_mask, const uint8_t* residue_mask,
+                            const float* weights, int32_t G, int32_t N, int32_t K, int32_t P, int32_t V, double pseudocount, float* aa_freq,
+                            float* entropy, int64_t* consensus, float* mean_points, float* rmsf, float* log_prob, float* consensus_identity,
+                            float* rmsd_to_mean, float* n_eff, int64_t* central, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the two context encoders (training through encode_context, diffab_pytorch.py:843-854 under autograd).
  * d_out is the gradient w.r.t. the module output; parameter gradients ACCUMULATE (+=) into the buffers of `g`, which has the
  * layout of the weight struct (the caller zero-fills them).  Inputs other than parameters take no gradient.  Nothing is taped:
