@@ -217,6 +217,11 @@ SYMBOLS = {
     # (seq_idx, points, generation_mask, residue_mask (nullable), weights (nullable), G, N, K, P, V, pseudocount, aa_freq, entropy, consensus,
     #  mean_points, rmsf, log_prob, consensus_identity, rmsd_to_mean, n_eff, central (each nullable), workspace, workspace_bytes, stream)
     "diffab_metrics_ensemble": (C.c_int, [_fp] * 5 + [_i32] * 5 + [C.c_double] + [_fp] * 11 + [_sz, _fp]),
+    # (points, native_points, generation_mask, residue_mask (nullable), antigen_mask (nullable), segment_idx (nullable), chain (nullable),
+    #  residue_idx (nullable), rows, group_size, K, P, S, inclusion_radius, contact_distance, n_pairs, n_pairs_interface, preserved,
+    #  preserved_interface, lddt_residue, lddt, lddt_thresholds, ilddt_residue, ilddt, lddt_segment, n_native, native_contacts_residue, n_design,
+    #  n_kept, fnat, fnonnat, kept_residue, stream)
+    "diffab_metrics_similarity": (C.c_int, [_fp] * 8 + [_i32] * 5 + [C.c_float] * 2 + [_fp] * 18),
     "diffab_orientation_loss": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp]),
     "diffab_orientation_loss_bwd": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "diffab_frames_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),

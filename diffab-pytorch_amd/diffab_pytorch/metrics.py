@@ -6,14 +6,17 @@
 ``backbone``        per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
 ``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
 ``ensemble``        per patch: its N designs as a distribution - amino-acid frequencies, entropy, consensus, mean structure, RMSF, and
-                    how typical each design is of its siblings (``csrc/ensemble_kernels.hip``).
+                    how typical each design is of its siblings (DESIGN section 4.16, ``csrc/ensemble_kernels.hip``);
+``similarity``      per design, without a superposition: lDDT against the native per residue, per design and per segment, and the
+                    recovery of the native residue contacts, Fnat (``csrc/similarity_kernels.hip``).
 
 Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` returns them - ``seq_idx`` (rows,K), ``translations``
 (rows,K,3), ``orientations`` (rows,K,3,3) with ``rows = G * group_size``, row ``g * group_size + r`` = design r of patch g - and the masks
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
-the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` in
-``include/diffab_hip.h``; every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip``
-(the filters) and ``csrc/ensemble_kernels.hip``, and there is no torch fallback.
+the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
+``_similarity`` in ``include/diffab_hip.h``; every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``,
+``csrc/geometry_kernels.hip`` (the filters), ``csrc/ensemble_kernels.hip`` and ``csrc/similarity_kernels.hip``, and
+there is no torch fallback.
 """
 from __future__ import annotations
 
@@ -34,6 +37,9 @@ ATOMS = {"ca": None, "backbone": ("N", "CA", "C", "O")}
 MAX_CONTEXT_ATOMS = 32  # DIFFAB_METRICS_MAX_CONTEXT_ATOMS: atom slots per context residue
 CONTACTS_CHUNK_ATOMS = 1024  # DIFFAB_METRICS_CONTACTS_CHUNK_ATOMS: context atoms the contacts kernel stages in LDS per pass
 CONTACTS_CHUNK_RESIDUES = 64  # DIFFAB_METRICS_CONTACTS_CHUNK_RESIDUES: context residues per pass
+SIMILARITY_MAX_POINTS = 1024  # DIFFAB_METRICS_SIMILARITY_MAX_POINTS: K * P of one patch, staged on chip
+LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)  # Angstrom
+CONTACT_DISTANCE = {"ca": 8.0, "backbone": 5.0}  # similarity's default per atom set
 PEPTIDE_BOND = 1.329  # Angstrom, C(i) - N(i+1)
 GLY = AA3.index("GLY")
 
@@ -408,3 +414,95 @@ def ensemble(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
                                            *[_hip.ptr(t) for t in out.values()], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
                "diffab_metrics_ensemble")
     return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ design similarity
+def _check_positive(who: str, name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v <= 0:
+        raise ValueError(f"{who}: {name} must be a finite number > 0, got {v!r}")
+    return float(v)
+
+
+def similarity(designs: Dict[str, torch.Tensor], native: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, group_size: int = 1,
+               atoms: str = "ca", residue_mask: Optional[torch.Tensor] = None, antigen_mask: Optional[torch.Tensor] = None,
+               segment_idx: Optional[torch.Tensor] = None, num_segments: Optional[int] = None, chain_idx=None, residue_idx=None,
+               inclusion_radius: float = 15.0, contact_distance: Optional[float] = None) -> Dict[str, torch.Tensor]:
+    """Each design against the native of its patch without a superposition: lDDT and the recovery of the native residue contacts.
+    ``designs``, the masks, ``group_size``, ``atoms`` and ``segment_idx`` / ``num_segments`` as for ``evaluate``; ``native`` holds the
+    patch's own ``translations`` (and ``orientations`` for the backbone), one row per patch (G,K,...) - or one per design row, the batch
+    ``sample()`` ran on, of which the first row of every group is read.  A residue is present inside ``residue_mask`` and counted when
+    it is also generated.  K * P <= 1024 points per patch (K <= 256 with the backbone).
+
+    lDDT (thresholds 0.5, 1, 2, 4 A): for a point of a counted residue i and a point of a present residue j != i, the pair is scored when
+    its native distance is below ``inclusion_radius`` and preserved at a threshold when the design's distance differs by less.
+    ``n_pairs`` (G,K) int32, ``preserved`` (rows,K,4) int32, ``lddt_residue`` (rows,K) (NaN where nothing is scored or the residue is not
+    counted), ``lddt`` (rows,), ``lddt_thresholds`` (rows,4); with ``segment_idx`` ``lddt_segment`` (rows,S); with ``antigen_mask`` (G,K)
+    the same over the pairs whose j is an antigen residue: ``n_pairs_interface``, ``preserved_interface``, ``ilddt_residue``, ``ilddt``.
+
+    Native contacts: a counted residue i and a present partner j != i - an antigen residue with ``antigen_mask``, else a residue not
+    bonded to i (|i - j| > 1 by position, or ``guidance``'s bonded rule when ``chain_idx`` / ``residue_idx``, (K,) or (G,K), are given) - are in contact
+    when their closest points are nearer than ``contact_distance`` (default 8 A for ``'ca'``, 5 A for ``'backbone'``).  ``n_native`` (G,),
+    ``native_contacts_residue`` (G,K), ``n_design``, ``n_kept`` (rows,) int32, ``fnat`` = n_kept / n_native, ``fnonnat`` = (n_design -
+    n_kept) / n_design (NaN on a zero denominator) and ``kept_residue`` (rows,K) int32, ready as ``b_factor`` of ``io.write_pdb``.
+
+    The counts are exact functions of the fp32 points and every ratio is one fp32 division of two of them (``include/diffab_hip.h``).
+    One C-ABI call, one launch, no workspace; results on the device of ``designs['seq_idx']``; ValueError before any device work."""
+    who = "metrics.similarity()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, atoms)
+    if not isinstance(native, dict) or not isinstance(native.get("translations"), torch.Tensor):
+        raise ValueError(f"{who}: native must be a dict with translations (and orientations for atoms='backbone')")
+    nx = native["translations"]
+    if not nx.is_floating_point() or nx.dim() != 3 or tuple(nx.shape[1:]) != (K, 3) or int(nx.shape[0]) not in (G, rows):
+        raise ValueError(f"{who}: native['translations'] is {tuple(nx.shape)} {nx.dtype}, expected a float tensor {(G, K, 3)} or {(rows, K, 3)}")
+    nR = int(nx.shape[0])
+    if atoms == "backbone":
+        nO = native.get("orientations")
+        if not isinstance(nO, torch.Tensor) or not nO.is_floating_point() or tuple(nO.shape) != (nR, K, 3, 3):
+            raise ValueError(f"{who}: native['orientations'] must be a float tensor {(nR, K, 3, 3)} for atoms='backbone'")
+    P = 1 if atoms == "ca" else len(ATOMS[atoms])
+    if K * P > SIMILARITY_MAX_POINTS:
+        raise ValueError(f"{who}: K * P = {K} * {P} points per patch, at most {SIMILARITY_MAX_POINTS} are staged on chip")
+    if antigen_mask is not None:
+        _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    S = 0
+    if segment_idx is not None:
+        if not isinstance(segment_idx, torch.Tensor) or segment_idx.is_floating_point() or segment_idx.dtype == torch.bool:
+            raise ValueError(f"{who}: segment_idx must be an integer tensor")
+        if tuple(segment_idx.shape) != (G, K):
+            raise ValueError(f"{who}: segment_idx is {tuple(segment_idx.shape)}, expected {(G, K)}")
+        if num_segments is None:
+            num_segments = max(1, int(segment_idx.max()) + 1) if segment_idx.numel() else 1
+        if not _is_int(num_segments) or num_segments < 1 or num_segments > MAX_SEGMENTS:
+            raise ValueError(f"{who}: num_segments = {num_segments!r} (segment_idx labels up to it) outside [1, {MAX_SEGMENTS}]")
+        S = num_segments
+    elif num_segments is not None:
+        raise ValueError(f"{who}: num_segments without segment_idx")
+    radius = _check_positive(who, "inclusion_radius", inclusion_radius)
+    cutoff = _check_positive(who, "contact_distance", CONTACT_DISTANCE[atoms] if contact_distance is None else contact_distance)
+    chain = ridx = None
+    if chain_idx is not None or residue_idx is not None:  # (checked, and unused with an antigen_mask: the partners are the antigen residues)
+        chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    pts = _points(designs, atoms)
+    first = None if nR == G else torch.arange(G) * group_size  # a native per design row: the first row of every group
+    npts = _points({k: (v if first is None else v[first.to(v.device)]) for k, v in native.items()
+                    if k in ("translations", "orientations") and isinstance(v, torch.Tensor)}, atoms)
+    gm = _hip.dev_mask(generation_mask)
+    rm, ag = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask))
+    seg = None if segment_idx is None else _hip.dev_i64(segment_idx)
+    if chain is not None:
+        chain, ridx = chain.to(dev), ridx.to(dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    with_ag, with_seg = ag is not None, S > 0
+    out = {"n_pairs": i32(G, K), "n_pairs_interface": i32(G, K) if with_ag else None, "preserved": i32(rows, K, 4),
+           "preserved_interface": i32(rows, K, 4) if with_ag else None, "lddt_residue": f32(rows, K), "lddt": f32(rows),
+           "lddt_thresholds": f32(rows, 4), "ilddt_residue": f32(rows, K) if with_ag else None, "ilddt": f32(rows) if with_ag else None,
+           "lddt_segment": f32(rows, S) if with_seg else None, "n_native": i32(G), "native_contacts_residue": i32(G, K),
+           "n_design": i32(rows), "n_kept": i32(rows), "fnat": f32(rows), "fnonnat": f32(rows), "kept_residue": i32(rows, K)}
+    _hip.check(lib.diffab_metrics_similarity(_hip.ptr(pts), _hip.ptr(npts), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(ag), _hip.ptr(seg), _hip.ptr(chain),
+                                             _hip.ptr(ridx), rows, group_size, K, P, S, radius, cutoff, *[_hip.ptr(t) for t in out.values()],
+                                             _hip.stream_ptr()), "diffab_metrics_similarity")
+    return {k: v.to(out_dev) for k, v in out.items() if v is not None}

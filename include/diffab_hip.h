@@ -653,6 +653,59 @@ int diffab_metrics_ensemble(const int64_t* seq_idx, const float* points, const u
                             float* entropy, int64_t* consensus, float* mean_points, float* rmsf, float* log_prob, float* consensus_identity,
                             float* rmsd_to_mean, float* n_eff, int64_t* central, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Design similarity: the two superposition-free comparisons of a design with the native of its patch, lDDT and the
+ * recovery of the native residue contacts (Fnat).  Rows, groups, points and masks as in "Common layout" above (rows = G * group_size,
+ * points (rows,K,P,3), masks (G,K), residue_mask NULL = all present); native_points (G,K,P,3) are the same points of the patch's native.
+ * A residue is PRESENT when it is inside residue_mask and COUNTED when it is present and generated.  This is the project's own statement of
+ * the published definitions (lDDT: Mariani et al. 2013, thresholds 0.5, 1, 2, 4 A; Fnat as in CAPRI / DockQ, on residue pairs).
+ *
+ * Arithmetic.  The distance of two points is d = sqrtf(((dx*dx) + dy*dy) + dz*dz) in fp32, dx, dy, dz one rounded subtraction each, no
+ * contraction; d_nat(a,b) is taken between two native points and d_des(a,b) between the same two points of the design row - the context
+ * residues of the design are whatever the row holds.  Every comparison is made in fp32 on those values, against inclusion_radius,
+ * contact_distance and the thresholds as fp32.  Every accumulator is an integer: a row's numbers depend on neither the order of the sums
+ * nor the other rows of the call, and the per-patch integers are the same whichever design they are computed beside.  Every ratio is ONE
+ * fp32 division of two integers converted to fp32, NaN where the denominator is 0.
+ *
+ * lDDT.  For a point a of a counted residue i and every point b of a present residue j != i: the pair is SCORED when d_nat < inclusion_radius
+ * and PRESERVED AT tau when it is scored and |d_des - d_nat| < tau (one rounded subtraction), tau = 0.5, 1, 2, 4.
+ *   n_pairs (G,K) int32:        the scored pairs of residue i - a property of the native; 0 where i is not counted;
+ *   preserved (rows,K,4) int32: the pairs of residue i preserved at each tau; 0 where i is not counted;
+ *   lddt_residue (rows,K):      (sum_tau preserved) / (4 n_pairs); NaN where n_pairs = 0 or i is not counted;
+ *   lddt (rows):                (sum_i sum_tau preserved) / (4 sum_i n_pairs) over the counted residues - a pair of two counted residues is
+ *                               counted from both sides;
+ *   lddt_thresholds (rows,4):   (sum_i preserved_tau) / (sum_i n_pairs);
+ *   lddt_segment (rows,S):      lddt over the counted residues with segment_idx = s.  segment_idx (G,K) int64 or NULL with S = 0: labels in
+ *                               [0, S), S <= DIFFAB_METRICS_MAX_SEGMENTS, anything else = no segment.
+ * With antigen_mask (G,K) a second set of integer counters takes the scored pairs whose j is inside antigen_mask: n_pairs_interface (G,K),
+ * preserved_interface (rows,K,4), ilddt_residue (rows,K), ilddt (rows), the same ratios.  Without antigen_mask those four may be NULL.
+ *
+ * Native contacts.  A residue pair is a counted residue i and a PARTNER j != i: a present residue that, with antigen_mask, is inside
+ * antigen_mask, and without it is not bonded to i.  Bonded: chain[i] == chain[j] and |residue_idx[i] - residue_idx[j]| = 1 (chain,
+ * residue_idx (G,K) int32, the rule of diffab_sample_guidance); with chain = residue_idx = NULL, |i - j| = 1 by position in the patch.
+ * The pair is IN CONTACT in a structure when one of its P x P point distances is < contact_distance (the smallest one is).
+ *   native_contacts_residue (G,K) int32: the partners of residue i in contact in the native; 0 where i is not counted;
+ *   n_native (G) int32:         their sum over the counted residues (a pair of two counted residues is counted from both sides);
+ *   n_design (rows) int32:      the same sum in the design row;
+ *   n_kept (rows) int32:        pairs in contact in both;  kept_residue (rows,K) int32: those of residue i, 0 where i is not counted;
+ *   fnat (rows) = n_kept / n_native;  fnonnat (rows) = (n_design - n_kept) / n_design.
+ *
+ * One launch: one work-group of four waves per (patch, four designs), one wave per design.  The native points of the patch and the four
+ * design rows are staged in LDS, 15 (K | 1) P floats and 3 K bytes, which has to fit 64 KiB: K * P <= DIFFAB_METRICS_SIMILARITY_MAX_POINTS
+ * = 1024 (K <= 256 for the backbone, K <= 1024 for the CA).  A patch without a counted residue stages nothing.
+ * Limits, DIFFAB_ERR_ARG before anything is enqueued: rows >= 0 a multiple of group_size, 1 <= group_size <= DIFFAB_METRICS_MAX_GROUP,
+ * 1 <= K <= DIFFAB_METRICS_MAX_K, 1 <= P <= DIFFAB_METRICS_MAX_POINTS, K * P as above, 0 <= S <= DIFFAB_METRICS_MAX_SEGMENTS with
+ * segment_idx and lddt_segment exactly when S > 0, inclusion_radius and contact_distance finite and > 0, chain without residue_idx or the
+ * reverse, a null points, native_points, generation_mask or output (the interface outputs: with antigen_mask).  rows = 0 succeeds without
+ * looking at a pointer. */
+#define DIFFAB_METRICS_SIMILARITY_MAX_POINTS 1024
+int diffab_metrics_similarity(const float* points, const float* native_points, const uint8_t* generation_mask, const uint8_t* residue_mask,
+                              const uint8_t* antigen_mask, const int64_t* segment_idx, const int32_t* chain, const int32_t* residue_idx,
+                              int32_t rows, int32_t group_size, int32_t K, int32_t P, int32_t S, float inclusion_radius,
+                              float contact_distance, int32_t* n_pairs, int32_t* n_pairs_interface, int32_t* preserved,
+                              int32_t* preserved_interface, float* lddt_residue, float* lddt, float* lddt_thresholds, float* ilddt_residue,
+                              float* ilddt, float* lddt_segment, int32_t* n_native, int32_t* native_contacts_residue, int32_t* n_design,
+                              int32_t* n_kept, float* fnat, float* fnonnat, int32_t* kept_residue, void* stream);
+
 /* Backward of the two context encoders (training through encode_context, diffab_pytorch.py:843-854 under autograd).
  * d_out is the gradient w.r.t. the module output; parameter gradients ACCUMULATE (+=) into the buffers of `g`, which has the
  * layout of the weight struct (the caller zero-fills them).  Inputs other than parameters take no gradient.  Nothing is taped:
