@@ -198,14 +198,17 @@ struct ForwardPlan {
   const int* ctx_of_row;                  // shared contexts: device [B] map, state row b reads context ctx_of_row[b] (null: the identity)
   int n_ctx;                              // patches of pair_ctx and of its planes (0: d->B)
   const unsigned char* last_layer_tiles;  // [B][K / 16] row tiles of the LAST layer whose outputs are read (null: all)
+  const int* last_layer_rows;             // the module launch's form of the same: launch_row_plan (null with last_layer_tiles)
   float* res_emb;                         // the residue embedding after the IPA module is copied here (null: not wanted)
 };
 
 // loop: the call runs many forwards (reverse sampler, design scoring).  There the pair embedding is the same tensor in every attention
 // launch, so its fp16 planes are on unless DIFFAB_FLAG_PAIR_F32, and the module launch is chosen by module_launch_fills_chip unless
-// DIFFAB_FLAG_MULTI_LAUNCH; a single forward takes both from its flags.  tiles: the reverse sampler's buffer of the row-tile map.
+// DIFFAB_FLAG_MULTI_LAUNCH; a single forward takes both from its flags.  tiles, row_plan: the reverse sampler's buffers of the row-tile
+// map and of the row plan.
 static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const StepBuffers& b, const float* res_ctx, const float* pair_ctx,
-                                float* res_emb, bool loop, const int* ctx_of_row = nullptr, int n_ctx = 0, unsigned char* tiles = nullptr) {
+                                float* res_emb, bool loop, const int* ctx_of_row = nullptr, int n_ctx = 0, unsigned char* tiles = nullptr,
+                                int* row_plan = nullptr) {
   const int rows = d->B * d->K, D = d->D;
   if (loop && !(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
   ForwardPlan p{};
@@ -229,6 +232,9 @@ static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const Step
   p.persistent = p.b6 && p.pair_planes != nullptr && ipa_module_persistent_supported(d) &&
                  ((flags & DIFFAB_FLAG_PERSISTENT_MODULE) || (loop && !(flags & DIFFAB_FLAG_MULTI_LAUNCH) && module_launch_fills_chip(d)));
   p.fused_mlps = p.persistent && p.chain && D == 128 && res_emb == nullptr;
+  // The module launch walks the last layer's rows by the row plan (16-row windows from the generated rows: fewer items than aligned
+  // tiles); the per-layer launches keep the tile map.
+  p.last_layer_rows = p.persistent && p.last_layer_tiles != nullptr ? row_plan : nullptr;
   return p;
 }
 
@@ -330,7 +336,7 @@ static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, 
   }
   if (p.persistent) {
     if (int rc = launch_ipa_module_persistent(d, b.hA, b.hB, O_t, x_t, b.ipa, b.planes, p.pair_planes, st, p.fused_mlps ? res_ctx : nullptr,
-                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx, p.last_layer_tiles))
+                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx, p.last_layer_rows))
       return rc;
     cur = (d->NL & 1) ? b.hB : b.hA;
   }
@@ -403,6 +409,7 @@ struct SampleBuffers {
   float *beta, *eps, *O0, *post;
   int* t_dev;  // the current timestep in device memory (graph replay)
   unsigned char* tiles;  // [B][K / 16]: row tiles with a generated residue (the last layer's attention runs for these only)
+  int* row_plan;         // [B][2 + K / 16]: the module launch's items of the last layer (launch_row_plan)
   float* beta_traj;      // [3 heads][kTrajRows][D]: the heads' folded beta columns of every step of a schedule with T < kTrajRows
   int* ctx_of_row;       // shared contexts: [B] the context of every state row (device copy of the caller's map)
   float* res_ctx;        // shared contexts: [B][K][D] the residue context of every state row (gathered once per call)
@@ -421,6 +428,7 @@ static SampleBuffers carve_sample(const diffab_dims* d, void* ws, int n_pair = 0
   s.post = c.take<float>(rows * d->V);
   s.t_dev = c.take<int>(64);
   s.tiles = c.take<unsigned char>(static_cast<size_t>(d->B) * ((d->K + 15) / 16));
+  s.row_plan = c.take<int>(static_cast<size_t>(d->B) * (2 + (d->K + 15) / 16));
   s.beta_traj = c.take<float>(static_cast<size_t>(3) * kTrajRows * d->D);
   s.ctx_of_row = mapped ? c.take<int>(d->B) : nullptr;
   s.res_ctx = mapped ? c.take<float>(rows * d->D) : nullptr;  // 256-byte aligned: the folded embedding MLP takes it as it takes the caller's
@@ -539,6 +547,13 @@ int diffab_debug_row_tiles(const uint8_t* gen_mask, int32_t B, int32_t K, uint8_
   StreamOrder order_(stream);
   DIFFAB_REQUIRE(gen_mask && tiles && B >= 1 && K >= 16 && K % 16 == 0, DIFFAB_ERR_ARG, "debug_row_tiles: need B >= 1 and K a multiple of 16");
   return launch_tiles_needed(gen_mask, B, K, tiles, as_stream(stream));
+}
+
+int diffab_debug_row_plan(const uint8_t* gen_mask, int32_t B, int32_t K, int32_t* plan, void* stream) {
+  StreamOrder order_(stream);
+  DIFFAB_REQUIRE(gen_mask && plan && B >= 1 && K >= 16 && K <= 1024 && K % 16 == 0, DIFFAB_ERR_ARG,
+                 "debug_row_plan: need B >= 1 and K a multiple of 16 in 16 .. 1024");
+  return launch_row_plan(gen_mask, B, K, plan, as_stream(stream));
 }
 
 int diffab_debug_set_attn_variant(int32_t v) { return set_attn_variant(v); }
@@ -1017,7 +1032,7 @@ int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w
     res_ctx = sb.res_ctx;
   }
   const StepBuffers b0 = carve_step(d, sb.step, n_ctx);
-  const ForwardPlan plan = plan_forward(d, flags, b0, res_ctx, pair_ctx, nullptr, true, ctx_dev, n_ctx, sb.tiles);
+  const ForwardPlan plan = plan_forward(d, flags, b0, res_ctx, pair_ctx, nullptr, true, ctx_dev, n_ctx, sb.tiles, sb.row_plan);
   // The heads' folded beta columns depend on (step, head, column) only - every patch of a reverse step has the same beta - so the table
   // of ALL steps is built once per call instead of once per step.  Eager loop only: under graph replay the step index lives in device
   // memory and the chain's bias pointer is a launch argument.
@@ -1026,6 +1041,8 @@ int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w
   if (int rc = prepare_forward(d, w, plan, b0, pair_ctx, bias, st)) return rc;
   if (plan.last_layer_tiles)
     if (int rc = launch_tiles_needed(gen_mask, d->B, d->K, sb.tiles, st)) return rc;
+  if (plan.last_layer_rows)
+    if (int rc = launch_row_plan(gen_mask, d->B, d->K, sb.row_plan, st)) return rc;
   if (rec != nullptr) {  // the step -> slot table, and the residues the loop never writes, once per call
     DIFFAB_HIP_CHECK(hipMemcpyAsync(rec->slot_dev, rec->slot_of_step, sizeof(int32_t) * (s->T + 1), hipMemcpyHostToDevice, st));
     if (int rc = launch_record_fixed(uo.rec, seq, x, O, gen_mask, d->B, d->K, d->V, st)) return rc;

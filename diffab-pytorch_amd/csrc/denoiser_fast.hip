@@ -368,7 +368,7 @@ __global__ __launch_bounds__(512) void ipa_attn_fast_kernel(const float* __restr
   // tile_needed (reverse sampler, last layer; all tiles with DIFFAB_FLAG_ALL_ROWS): the outputs of this layer are read for generated residues
   // only - a row tile without one leaves at once (uniform; its feature rows keep the previous layer's values, which nothing reads)
   if (tile_needed != nullptr && !tile_needed[b * ntile + tile]) return;
-  ipa_attn_tile<NT, MULTI, PLANES, TAPE>(S, b, tile, bid, proj, e, R, t, Wb, gamma, feat, NC_arg, stamps, esc, tape_p, tape_d2, ctx_of_row);
+  ipa_attn_tile<NT, MULTI, PLANES, TAPE>(S, b, tile * TI, bid, proj, e, R, t, Wb, gamma, feat, NC_arg, stamps, esc, tape_p, tape_d2, ctx_of_row);
 }
 
 static unsigned long long* g_attn_stamps = nullptr;  // diagnostics only (diffab_debug_set_attn_stamps)

@@ -115,7 +115,7 @@ bool ipa_module_persistent_supported(const diffab_dims* d);
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X = nullptr, const MlpChainSet* emb = nullptr,
                                  const MlpChainSet* heads = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0,
-                                 const unsigned char* last_layer_tiles = nullptr);  // [B][K / 16]: as ipa_layer_fast's tile_needed
+                                 const int* last_layer_rows = nullptr);  // launch_row_plan's [B][2 + K / 16] ints
 void set_module_stagger(int ticks, int classes);  // diagnostics: start-up stagger of the persistent module kernel (10 ns ticks)
 void set_module_stamps(void* device_buffer);      // diagnostics: phase stamps of the persistent module kernel
 // bias tables of the folded concatenations (see denoiser_fast.hip): emb_tab[25][D] depends on the weights only; beta_tab[3 heads][B][D]
@@ -325,6 +325,12 @@ int launch_record_fixed(const SampleRecordDev& rec, const int64_t* seq, const fl
                         hipStream_t st);
 int launch_fill_beta(const diffab_sched* s, int t, int B, float* out, hipStream_t st, const int* t_dev = nullptr);
 int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hipStream_t st);  // [B][K / 16]: any generated residue in the tile
+// The last layer's row plan of the module launch, per patch 2 + K / 16 ints: {n_items, slab bits, start row of item 0 .. n_items - 1 (-1
+// behind them)}.  Items are 16-row windows chosen greedily - s = min(first generated row not yet covered, K - 16) covers [s, s + 16) - so
+// there are never more than aligned tiles with a generated residue; bit j of the slab word: a generated residue in rows 32 j .. 32 j + 31
+// ((K + 31) / 32 slabs, the last one short when K % 32 != 0: K = 16 is one slab).  K % 16 == 0, 16 <= K <= 1024.
+constexpr int row_plan_ints(int K) { return 2 + K / 16; }
+int launch_row_plan(const uint8_t* gm, int B, int K, int* out, hipStream_t st);
 // shared contexts: out[b] = src[ctx_of_row[b]] for the B rows of `row_floats` floats each (16-byte aligned rows)
 int launch_gather_rows(const float* src, const int* ctx_of_row, int B, int64_t row_floats, float* out, hipStream_t st);
 // design scoring (diffab_score_designs): a chunk of evaluated rows q = ((r n_t) + j) n_draws + m, q0 .. q0 + valid - 1, in buffers of

@@ -1398,6 +1398,29 @@ int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hip
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
+__global__ void row_plan_kernel(const uint8_t* __restrict__ gm, int B, int K, int* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per patch: K <= 1024 rows, once per call
+  if (b >= B) return;
+  int* p = out + static_cast<int64_t>(b) * row_plan_ints(K);
+  int n = 0, covered = 0;  // rows below `covered` are inside an item
+  unsigned slabs = 0;
+  for (int i = 0; i < K; ++i) {
+    if (!gm[static_cast<int64_t>(b) * K + i]) continue;
+    slabs |= 1u << (i >> 5);
+    if (i < covered) continue;
+    const int s = i < K - 16 ? i : K - 16;
+    p[2 + n++] = s;  // (n <= K / 16: the aligned tiles are a covering, the greedy one is minimal)
+    covered = s + 16;
+  }
+  for (int j = n; j < K / 16; ++j) p[2 + j] = -1;
+  p[0] = n;
+  p[1] = static_cast<int>(slabs);
+}
+int launch_row_plan(const uint8_t* gm, int B, int K, int* out, hipStream_t st) {
+  hipLaunchKernelGGL(row_plan_kernel, dim3(static_cast<unsigned>((B + 63) / 64)), dim3(64), 0, st, gm, B, K, out);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
 // shared contexts (diffab_sample_options.ctx_of_row): the residue context rows of every state row, once per call
 __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ ctx_of_row, int64_t row_floats, int64_t n,
                                    float* __restrict__ out) {

@@ -109,14 +109,17 @@ __device__ __forceinline__ void attn_shift_pair_rows(FP& e, FP& esc, const int* 
   if constexpr (PLANES) esc += 2 * shift;
 }
 
-// One (patch b, 16-row tile) item of the fused attention: the body of ipa_attn_fast_kernel (denoiser_fast.hip: one item per work-group)
-// and of the patch-resident module kernel (ipa_persistent.hip: a work-group walks the eight row tiles of ITS patch, layer after layer).
+// One (patch b, 16 query rows from i0) item of the fused attention: the body of ipa_attn_fast_kernel (denoiser_fast.hip: one item per
+// work-group) and of the patch-resident module kernel (ipa_persistent.hip: a work-group walks the eight row tiles of ITS patch, layer after
+// layer).  i0 (wave-uniform, 0 <= i0 <= K - 16) need not be a multiple of 16: every address of the item - query rows, pair rows and their
+// scales, R / t, feature rows - is linear in it, and every output row depends on its own A-operand row alone in all three phases, so the
+// bits of a row do not depend on the item that carries it (the module kernel's last layer of a reverse step starts items at generated rows).
 // 512 threads; S: the dynamic LDS (ipa_attn_lds_bytes(NT)); stamp_id: the slot of this item in the diagnostic stamp buffer.
 // Eight waves: wave = head in phases 1 and 3, two query rows in phase 2.
 // ctx_of_row (shared contexts, diffab_sample_options.ctx_of_row): the pair rows (and their row scales) of state row b are those of context
 // ctx_of_row[b] - `e` / `esc` then hold n_ctx patches; the projections and features stay on row b.  nullptr: the identity.
 template <int NT, bool MULTI, bool PLANES = false, bool TAPE = false>
-__device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b, const int tile, const unsigned stamp_id,
+__device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b, const int i0, const unsigned stamp_id,
                                               const float* __restrict__ proj, const float* __restrict__ e,
                                               const float* __restrict__ R, const float* __restrict__ t,
                                               const float* __restrict__ Wb, const float* __restrict__ gamma,
@@ -149,7 +152,6 @@ __device__ __forceinline__ void ipa_attn_tile(float* __restrict__ S, const int b
     }
   };
   stamp(0);
-  const int i0 = tile * TI;
   const int tid = threadIdx.x, lane0 = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   // (the wave index as a scalar: the addresses built from it stay in SGPRs, which takes the chunked instantiations from 13 spilled VGPRs
   // + 56 B of scratch to none)

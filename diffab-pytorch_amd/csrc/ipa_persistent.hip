@@ -42,13 +42,15 @@ struct ModuleArgs {
   const float* pair;         // fp16 planes of the pair embedding (launch_pair_split)
   const float* esc;          // {s, 1 / s} per pair row
   const int* ctx_of_row;     // shared contexts: [B] context of each patch's pair rows (null: the identity)
-  // reverse sampler: [B][K / 16] row tiles of the LAST layer whose outputs are read (null: all; 4-byte aligned)
-  const unsigned char* last_layer_tiles;
+  // reverse sampler: the row plan of the LAST layer (launch_row_plan: per patch {items, slab bits, start row of each item}; null: the
+  // K / 16 aligned tiles)
+  const int* last_layer_rows;
   const float* R;            // [B K][9]
   const float* t;            // [B K][3]
   const char* planes;        // per layer: ipa_layer_planes_bytes() (w_bias, gamma, b_out | projection planes | to_out planes | 1 / scales)
   size_t layer_stride, pj_off, out_off, wis_off, small_off;  // offsets of the fp16 planes, 1 / scale vectors and small vectors in a layer's block
-  unsigned long long* stamps;  // diagnostics (null in production): [item][wave][8] of the attention tiles + [B][NL][4] phase stamps behind them
+  // diagnostics (null in production): [item][wave][8] of the attention tiles + [B][NL][4] phase stamps behind them + [B] the end of the heads
+  unsigned long long* stamps;
   // the denoiser's MLPs as phases of the same launch (null emb_X: not fused): the embedding MLP of the patch's rows in front of layer 0
   // (emb_X -> xa), the three heads behind the last layer (module output -> heads.Y[]); mlp_chain_tile.h, bitwise mlp_chain_b6_kernel
   const float* emb_X;
@@ -58,12 +60,12 @@ struct ModuleArgs {
 };
 }  // namespace
 
-// Byte idx of the row-tile map through a scalar load of its aligned word (as attn_shift_pair_rows: a kernel that also stores to global
-// memory would otherwise get a vector load and a readfirstlane): the skip decision stays off the vector pipe, in an SGPR.
-__device__ __forceinline__ bool module_tile_needed(const unsigned char* __restrict__ map, const int idx) {
-  unsigned w;
-  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(map + (idx & ~3)) : "memory");
-  return ((w >> (8 * (idx & 3))) & 0xffu) != 0;
+// Word idx of the row plan through a scalar load (as attn_shift_pair_rows: a kernel that also stores to global memory would otherwise
+// get a vector load and a readfirstlane): the item count and the start rows stay off the vector pipe, in SGPRs.
+__device__ __forceinline__ int module_plan_word(const int* __restrict__ plan, const int idx) {
+  int w;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(plan + idx) : "memory");
+  return w;
 }
 
 // KRES: residues per patch - 128 (one 128-row dense tile per patch, single-chunk attention items) or 256 (BASELINE config 5: two dense
@@ -137,16 +139,20 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
       __syncthreads();
       pstamp(b, l, 1);
       // ---- attention: the eight row tiles of the patch
-      // last_layer_tiles (reverse sampler): the step's outputs are read for generated residues only, and the last layer's attention
-      // output of a row feeds that row of to_out and of the heads alone - an item of the last layer without a generated residue is
-      // skipped, barrier and all (uniform over the work-group).  Its feature rows keep what the previous layer's item wrote (the same
-      // work-group, complete since that layer's barriers): finite and deterministic; to_out and the heads still run on all rows of the
-      // patch, every product there is row-wise, and nothing reads what they make of the skipped rows.
-      const unsigned char* needed = l + 1 == a.NL ? a.last_layer_tiles : nullptr;
+      // last_layer_rows (reverse sampler): the step's outputs are read for generated residues only, and the last layer's attention
+      // output of a row feeds that row of to_out and of the heads alone - the last layer runs the plan's items instead: 16-row windows
+      // that start at the first generated row not yet covered (clamped to K - 16), never more than the aligned tiles with a generated
+      // residue and often fewer (a segment of up to 16 rows across a tile boundary is one item).  The rows of no item keep in their
+      // feature rows what the previous layer's item wrote (the same work-group, complete since that layer's barriers): finite and
+      // deterministic; to_out still runs on all rows of the patch and the heads on the 32-row slabs with a generated residue (below),
+      // every product there is row-wise, and nothing reads what they make of those rows.  A row's bits do not depend on the item that
+      // carries it (ipa_attn_tile.h).
+      const int* rows = l + 1 == a.NL ? a.last_layer_rows : nullptr;
+      const int n_items = rows != nullptr ? module_plan_word(rows, b * (2 + NTILE)) : NTILE;
 #pragma unroll 1
-      for (int tile = 0; tile < NTILE; ++tile) {
-        if (needed != nullptr && !module_tile_needed(needed, b * NTILE + tile)) continue;
-        ipa_attn_tile<8, (KRES > 128), true>(lds, b, tile, static_cast<unsigned>((b * a.NL + l) * NTILE + tile), a.proj, a.pair, a.R, a.t, small,
+      for (int item = 0; item < n_items; ++item) {
+        const int i0 = rows != nullptr ? module_plan_word(rows, b * (2 + NTILE) + 2 + item) : item * TI;
+        ipa_attn_tile<8, (KRES > 128), true>(lds, b, i0, static_cast<unsigned>((b * a.NL + l) * NTILE + item), a.proj, a.pair, a.R, a.t, small,
                                              small + 512, a.feat, K / 128, a.stamps, a.esc, nullptr, nullptr, a.ctx_of_row);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // the next tile's phase 1 overwrites the image; the last tile's feature rows are complete
@@ -179,17 +185,25 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
 #pragma unroll 1
       for (int hdt = 0; hdt < 3 * DT; ++hdt) {
         const int hd = hdt / DT, dt = hdt % DT;
+        // reverse sampler: only the 32-row slabs with a generated residue (the plan's slab bits) - the heads of the other rows are never
+        // read and keep what the workspace held.  Waves 2 s and 2 s + 1 own slab s (mlp_chain_tile<true>): the one or two wanted slabs
+        // of a CDR then keep all four SIMDs' matrix pipes busy instead of queueing both waves of a slab on one.
+        const unsigned hslabs =
+            a.last_layer_rows != nullptr ? static_cast<unsigned>(module_plan_word(a.last_layer_rows, b * (2 + NTILE) + 1)) : ~0u;
+        const unsigned tslabs = (hslabs >> (4 * dt)) & 15u;
+        if (tslabs == 0) continue;
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
 #define HSEL(f) (hd == 0 ? a.heads.c[0].f : hd == 1 ? a.heads.c[1].f : a.heads.c[2].f)
-        chaintile::mlp_chain_tile(reinterpret_cast<__bf16*>(lds), tid, b * DT + dt, xfin, 128, HSEL(planes[0]), HSEL(planes[1]), HSEL(planes[2]),
+        chaintile::mlp_chain_tile<true>(reinterpret_cast<__bf16*>(lds), tid, b * DT + dt, xfin, 128, HSEL(planes[0]), HSEL(planes[1]), HSEL(planes[2]),
                                   HSEL(bias[0]), HSEL(bias[1]), HSEL(bias[2]), HSEL(bias_idx0), HSEL(bias_div0), 3, HSEL(n_out),
                                   hd == 0 ? a.heads.Y[0] : hd == 1 ? a.heads.Y[1] : a.heads.Y[2],
-                                  hd == 0 ? a.heads.ldy[0] : hd == 1 ? a.heads.ldy[1] : a.heads.ldy[2], M);
+                                  hd == 0 ? a.heads.ldy[0] : hd == 1 ? a.heads.ldy[1] : a.heads.ldy[2], M, tslabs);
 #undef HSEL
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // the next chain (or the next patch's first phase) overwrites the image
       }
+      if (pstamps != nullptr && threadIdx.x == 0) pstamps[static_cast<size_t>(a.B) * a.NL * 4 + b] = __builtin_amdgcn_s_memrealtime();
     }
   }
 }
@@ -211,16 +225,17 @@ bool ipa_module_persistent_supported(const diffab_dims* d) {
 
 // planes: d->NL x ipa_layer_planes_bytes() (ipa_layer_split_weights); pair_planes: launch_pair_split() of n_ctx patches (0: d->B), state
 // patch b reading those of ctx_of_row[b] (null: b); xa in, result in (NL odd ? xb : xa)
-// last_layer_tiles (optional, reverse sampler): [B][K / 16] bytes, the last layer's attention runs only for the row tiles with a nonzero one
+// last_layer_rows (optional, reverse sampler): the row plan of launch_row_plan ([B][2 + K / 16] ints), the last layer's attention runs
+// its items only and the heads (when fused) its slabs only
 // emb_X (optional, with emb and heads): the embedding MLP's input rows - the launch then also runs the embedding MLP (-> xa) and the three
 // heads (module output -> heads->Y[]) of every patch
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X, const MlpChainSet* emb,
-                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx, const unsigned char* last_layer_tiles) {
+                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx, const int* last_layer_rows) {
   DIFFAB_REQUIRE(ipa_module_persistent_supported(d) && xa && xb && R && t && ws && planes && pair_planes, DIFFAB_ERR_ARG,
                  "ipa_module_persistent: unsupported operands");
-  DIFFAB_REQUIRE((reinterpret_cast<uintptr_t>(last_layer_tiles) & 3) == 0, DIFFAB_ERR_ARG,
-                 "ipa_module_persistent: the row-tile map must be 4-byte aligned");
+  DIFFAB_REQUIRE((reinterpret_cast<uintptr_t>(last_layer_rows) & 3) == 0, DIFFAB_ERR_ARG,
+                 "ipa_module_persistent: the row plan must be 4-byte aligned");
   const size_t rows = static_cast<size_t>(d->B) * d->K;
   ModuleArgs a{};
   a.xa = xa;
@@ -230,7 +245,7 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
   a.pair = pair_planes + 64;
   a.esc = pair_row_scales(d, pair_planes, n_ctx);
   a.ctx_of_row = ctx_of_row;
-  a.last_layer_tiles = last_layer_tiles;
+  a.last_layer_rows = last_layer_rows;
   a.R = R;
   a.t = t;
   a.planes = static_cast<const char*>(planes);

@@ -43,25 +43,38 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define CHAIN_FENCE() asm volatile("" ::: "memory")
 
 // cl: kChainLdsBytes of LDS, 16-byte aligned; 512 threads; rows tile_m * 128 .. of X[M x 128] (ldx floats apart) -> Y[M x n_out]
+// slabs (work-group uniform): bit s = the rows 32 s .. 32 s + 31 of the tile are wanted.  Every product of the chain is row-wise and a
+// wave's rows are one slab in all three layers, so a wave whose slab is not wanted skips its share of the image staging, its MFMAs and
+// its epilogues (its rows of Y keep what they held); weight staging and the barriers stay with all 512 threads.  The rows that are
+// computed go through the same instructions in the same order: bitwise the full tile's.
+// SPREAD: waves 2 s and 2 s + 1 own slab s (instead of waves s and s + 4, which share a SIMD): a lone wanted slab's two 32 x 64 wave
+// tiles then run on two SIMDs.  Which wave computes a wave tile does not enter its arithmetic: bitwise the same.
+template <bool SPREAD = false>
 __device__ __forceinline__ void mlp_chain_tile(__bf16* cl, const int tid, const int tile_m, const float* __restrict__ X, int ldx,
                                                const __bf16* pl0, const __bf16* pl1, const __bf16* pl2, const float* bs0, const float* bs1,
                                                const float* bs2, const int64_t* bias_idx0, int bias_div0, int nlayers, int n_out,
-                                               float* __restrict__ Y, int ldy, int M) {
+                                               float* __restrict__ Y, int ldy, int M, const unsigned slabs = ~0u) {
   struct { const int64_t* bias_idx0; int bias_div0, nlayers, n_out; } ch{bias_idx0, bias_div0, nlayers, n_out};
   auto planes_of = [&](int L) { return L == 0 ? pl0 : L == 1 ? pl1 : pl2; };
   auto bias_of = [&](int L) { return L == 0 ? bs0 : L == 1 ? bs1 : bs2; };
   __bf16* Ws = cl;                        // [2][3][128][32]
   __bf16* img = cl + 2 * 3 * 128 * BK;    // [4][3][128][32]
   const int lane = tid & 63, wv = tid >> 6;
-  const int l31 = lane & 31, hk = lane >> 5, rw = wv & 3, cw = wv >> 2;  // wave tile 32 rows x 64 columns (32x32x16 MFMA)
+  const int l31 = lane & 31, hk = lane >> 5;
+  const int rw = SPREAD ? wv >> 1 : wv & 3, cw = SPREAD ? wv & 1 : wv >> 2;  // wave tile 32 rows x 64 columns (32x32x16 MFMA)
   const int m0 = tile_m * 128;
+  const int wv_u = __builtin_amdgcn_readfirstlane(wv);  // (scalar: the slab tests below are scalar branches)
+  const bool wanted = (slabs >> (SPREAD ? wv_u >> 1 : wv_u & 3)) & 1u;
   typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
   // ---- X -> image: thread (rows tid / 8 and 64 + tid / 8, 16-byte part tid % 8) of each of the four 32-k chunks
   {
     const int xa_row = tid >> 3, xa_part = tid & 7;
     f32x4 xr[4][2];
+    // (the wave's eight rows of group j lie in one slab)
+    const bool stage[2] = {((slabs >> (wv_u >> 2)) & 1u) != 0, ((slabs >> (2 + (wv_u >> 2))) & 1u) != 0};
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
+      if (!stage[j]) continue;
       int row = m0 + xa_row + 64 * j;
       row = row < M ? row : M - 1;  // clamped (never stored)
       const float* src = X + static_cast<int64_t>(row) * ldx + 4 * xa_part;
@@ -72,6 +85,7 @@ __device__ __forceinline__ void mlp_chain_tile(__bf16* cl, const int tid, const 
     for (int c = 0; c < 4; ++c)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
+        if (!stage[j]) continue;
         bf16x4 h, m, l;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -122,6 +136,7 @@ __device__ __forceinline__ void mlp_chain_tile(__bf16* cl, const int tid, const 
       const __bf16* wl = Ws + buf * (3 * 128 * BK) + w_off;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
+        if (!wanted) break;
         const int so = 8 * ((2 * ks + hk) ^ fx);
         bf16x8 a[3], b[2][3];
 #pragma unroll
@@ -146,6 +161,7 @@ __device__ __forceinline__ void mlp_chain_tile(__bf16* cl, const int tid, const 
       }
       __syncthreads();
     }
+    if (!wanted) continue;
     // ---- epilogue.  D^T 32x32: row = lane & 31 (+ 32 rw), column = (r & 3) + 8 (r >> 2) + 4 hk (+ 32 tt + 64 cw)
     const bool table = L == 0 && (ch.bias_idx0 != nullptr || ch.bias_div0 > 0);
     const int lrow = 32 * rw + l31, row = m0 + lrow;

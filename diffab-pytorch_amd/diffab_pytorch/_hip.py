@@ -139,6 +139,7 @@ SYMBOLS = {
     "diffab_debug_set_module_stagger": (C.c_int, [_i32, _i32]),
     "diffab_debug_set_module_stamps": (C.c_int, [_fp]),
     "diffab_debug_row_tiles": (C.c_int, [_fp, _i32, _i32, _fp, _fp]),
+    "diffab_debug_row_plan": (C.c_int, [_fp, _i32, _i32, _fp, _fp]),
     "diffab_set_stream_guard": (C.c_int, [C.c_int]),
     "diffab_debug_linear128": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, _fp, C.c_size_t, _fp]),
     "diffab_debug_gemm_tn": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp]),

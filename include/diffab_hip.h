@@ -196,7 +196,8 @@ int diffab_kernel_timer_enable(int on);
 int diffab_debug_set_attn_stamps(void* device_buffer);
 /* Diagnostics of the patch-resident module kernel (DIFFAB_FLAG_PERSISTENT_MODULE): its start-up stagger (work-groups of class
  * (index / 8) % classes start class x ticks late, ticks of 10 ns; default 8 x 1000: eight classes 10 us apart),
- * and a stamp buffer of (B NL 8 tiles x 8 waves x 8) + (B NL 4) uint64 filled with 100 MHz s_memrealtime stamps (NULL: off). */
+ * and a stamp buffer of (B NL 8 tiles x 8 waves x 8) + (B NL 4) + (B) uint64 filled with 100 MHz s_memrealtime stamps (NULL: off; the
+ * last B: the end of each patch's heads). */
 int diffab_debug_set_attn_variant(int32_t v); /* Reference paths for tests and tools (process-global): bit 2 (4) = the PairEmbedding
                                                  forward / backward as their unfused launches where the fused kernel would apply, bit 6
                                                  (64) = the PairEmbedding backward's matrix-core kernels (csrc/pair_chain_bwd.hip: 64-wide
@@ -207,6 +208,11 @@ int diffab_debug_set_module_stamps(void* device_buffer);
 /* Tests: the row-tile map diffab_sample_loop builds per call - tiles[b][j] (B x K / 16 bytes, device) = 1 when one of the residues
  * 16 j .. 16 j + 15 of patch b is generated, else 0; the last layer's attention runs for the tiles with a 1 (DIFFAB_FLAG_ALL_ROWS). */
 int diffab_debug_row_tiles(const uint8_t* gen_mask, int32_t B, int32_t K, uint8_t* tiles, void* stream);
+/* Tests: the row plan diffab_sample_loop builds per call for the module launch - plan[b] (B x (2 + K / 16) int32, device) =
+ * {n_items, slab bits, start rows}: the last layer's attention runs n_items 16-row items, item j on rows start[j] .. start[j] + 15
+ * (start = min(first generated row not yet covered, K - 16); entries behind n_items are -1); bit s of the slab word is set when one of
+ * the residues 32 s .. 32 s + 31 is generated ((K + 31) / 32 slabs: K = 16 is one slab).  K a multiple of 16 in 16 .. 1024. */
+int diffab_debug_row_plan(const uint8_t* gen_mask, int32_t B, int32_t K, int32_t* plan, void* stream);
 /* The cross-stream ordering guard described under "Streams" above: on / off (default since round 6), process-wide. */
 int diffab_set_stream_guard(int on);
 /* Diagnostics / accuracy tests: Y[M x 128] = X[M x Kd] W[128 x Kd]^T + bias through ONE of the two dense kernels of the MFMA path -
