@@ -126,6 +126,16 @@ class SampleOptions(C.Structure):
         super().__init__(struct_bytes=C.sizeof(type(self)), **{k: v for k, v in options.items() if v is not None})
 
 
+class RefineOptions(C.Structure):
+    """diffab_refine_options: iterations, step, the five weights and the clash distance of diffab_refine_backbone; struct_bytes is filled
+    in here."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("iterations", C.c_int32)] + \
+        [(n, C.c_float) for n in ("step", "w_bond", "w_angle", "w_trans", "w_clash", "w_tether", "clash_distance")]
+
+    def __init__(self, *args, **kw):
+        super().__init__(C.sizeof(type(self)), *args, **kw)
+
+
 # every symbol include/diffab_hip.h declares: name -> (restype, argtypes)
 _i32, _i64, _u32, _u64, _sz = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_size_t
 _PD, _PS, _PI = C.POINTER(Dims), C.POINTER(Sched), C.POINTER(Igso3)
@@ -223,6 +233,10 @@ SYMBOLS = {
     #  preserved_interface, lddt_residue, lddt, lddt_thresholds, ilddt_residue, ilddt, lddt_segment, n_native, native_contacts_residue, n_design,
     #  n_kept, fnat, fnonnat, kept_residue, stream)
     "diffab_metrics_similarity": (C.c_int, [_fp] * 8 + [_i32] * 5 + [C.c_float] * 2 + [_fp] * 18),
+    # (translations, orientations, generation_mask, residue_mask (nullable), chain, residue_idx, rows, group_size, K, options (nullable),
+    #  out_translations, out_orientations, energy_before, energy_after, terms_after, max_shift (the last four nullable), workspace,
+    #  workspace_bytes, stream)
+    "diffab_refine_backbone": (C.c_int, [_fp] * 6 + [_i32] * 3 + [C.POINTER(RefineOptions)] + [_fp] * 6 + [_fp, _sz, _fp]),
     "diffab_orientation_loss": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp]),
     "diffab_orientation_loss_bwd": (C.c_int, [_fp, _fp, _i64, _fp, _fp, _fp, _fp, _fp]),
     "diffab_frames_apply": (C.c_int, [_fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32, _fp]),

@@ -27,6 +27,7 @@ from . import so3 as _so3
 from . import features as _features
 from . import guidance as _guidance
 from . import patch as _patch
+from . import refine as _refine
 from . import steering as _steering
 from . import temperature as _temperature
 
@@ -1407,7 +1408,7 @@ class DiffAb(_ModuleBase):
     # ------------------------------------------------------------------ from a whole complex (build-defined; the reference cuts patches in preprocess_pdb.py:44-58)
     @torch.no_grad()
     def design_complex(self, batch: Dict[str, torch.Tensor], *, k: int = 128, k_antigen: Optional[int] = None, pad_to: int = 128,
-                       **sample_kwargs) -> Dict[str, torch.Tensor]:
+                       refine: Optional["_refine.Refinement"] = None, **sample_kwargs) -> Dict[str, torch.Tensor]:
         """Designs for whole complexes: ``batch`` holds the reference's batch fields for B complexes
         of N residues each - ``seq_idx``, ``xyz`` (B,N,A,3), ``generation_mask`` and, unless ``sample_kwargs`` brings the contexts,
         ``atom_mask`` and ``chain_idx``; optionally ``orientations`` (taken from xyz with features.featurize on the patch when absent),
@@ -1418,7 +1419,12 @@ class DiffAb(_ModuleBase):
         and ``patch.paste`` writes the designs back.  Returns sample()'s dict (patch-sized rows) plus ``"patch"``, the PatchIndex, and
         ``"complex"``: full-length ``seq_idx`` (rows,N), ``translations``, ``orientations`` - the native complex with the generated
         residues replaced by the design.  Bitwise what the four calls give when made by hand.  The fields sample() takes from the
-        batch cannot be given again in sample_kwargs (ValueError)."""
+        batch cannot be given again in sample_kwargs (ValueError).  ``refine``: a ``refine.Refinement`` sends the patch designs through
+        ``refine.backbone`` with the gathered patch's chain_idx / residue_idx / residue_mask before they are
+        pasted - the returned frames and ``"complex"`` are the refined ones, and ``energy_before`` / ``energy_after`` / ``terms`` /
+        ``max_shift`` are added; None (the default) leaves the call as it is without the argument."""
+        if refine is not None and not isinstance(refine, _refine.Refinement):
+            raise ValueError(f"design_complex(): refine must be a refine.Refinement or None, got {type(refine).__name__}")
         taken = ("generation_mask", "residue_mask", "atom_mask", "chain_idx", "residue_idx", "backbone_dihedrals", "pairwise_dihedrals",
                  "distmat")
         clash = [n for n in taken if n in sample_kwargs]
@@ -1441,6 +1447,14 @@ class DiffAb(_ModuleBase):
         out = self.sample(g["seq_idx"], g["xyz"], g["orientations"], generation_mask=g["generation_mask"], residue_mask=g["residue_mask"],
                           atom_mask=g.get("atom_mask"), chain_idx=g.get("chain_idx"), residue_idx=g["residue_idx"],
                           backbone_dihedrals=g.get("backbone_dihedrals"), **sample_kwargs)
+        if refine is not None:
+            tabs = {n: g.get(n) for n in ("generation_mask", "chain_idx", "residue_idx", "residue_mask")}
+            tabs.update({n: tabs[n].ne(0) for n in ("generation_mask", "residue_mask") if tabs[n] is not None})
+            ci = sample_kwargs.get("context_index")
+            if ci is not None:  # one row per design, each with the fields of its own complex
+                tabs = {n: None if v is None else v.index_select(0, torch.as_tensor(ci, device=v.device).long()) for n, v in tabs.items()}
+            out.update(_refine.backbone(out, tabs.pop("generation_mask"), group_size=1 if ci is not None else sample_kwargs.get("num_samples", 1),
+                                        options=refine, **tabs))
         out["patch"] = sel
         out["complex"] = _patch.paste(full, sel, out, num_samples=sample_kwargs.get("num_samples", 1),
                                       context_index=sample_kwargs.get("context_index"))

@@ -712,6 +712,75 @@ int diffab_metrics_similarity(const float* points, const float* native_points, c
                               float* ilddt, float* lddt_segment, int32_t* n_native, int32_t* native_contacts_residue, int32_t* n_design,
                               int32_t* n_kept, float* fnat, float* fnonnat, int32_t* kept_residue, void* stream);
 
+/* Backbone refinement: close the peptide bonds between the rigid frames of finished designs.  Model-free; rows,
+ * groups and masks as in "Common layout" above (rows = G * group_size, masks, chain and residue_idx (G,K), residue_mask NULL = all
+ * present).  translations (rows,K,3) and orientations (rows,K,3,3) fp32 are the frames sample() returns: rows of O are the local axes.
+ *
+ * Atoms.  N = t + (-0.525 O0 + 1.363 O1), CA = t, C = t + 1.526 O0 (O0, O1 the first two rows of O): io.IDEAL_BACKBONE.
+ * Moving residues.  A residue MOVES when generation_mask is set and it is inside residue_mask.  Every other residue is fixed: its
+ * output is its input's bits.  A fixed residue inside residue_mask still exerts forces.
+ * Chain neighbours.  succ(i) / pred(i) as for diffab_metrics_backbone: the lowest slot with the same chain and residue_idx + 1 / - 1,
+ * both inside residue_mask.  (With two slots of one (chain, residue_idx) key a residue feels its own two links only.)
+ * Energy of a design: a sum of terms w (|a - b| - d0)^2,
+ *   bond   w_bond  (|C_i  - N_s|  - DIFFAB_REFINE_BOND)^2                                 s = succ(i), for every link i -> s of which
+ *   angle  w_angle (|CA_i - N_s|  - DIFFAB_REFINE_CA_N)^2 + w_angle (|C_i - CA_s| - DIFFAB_REFINE_C_CA)^2      at least one end moves
+ *   trans  w_trans (|CA_i - CA_s| - DIFFAB_REFINE_CA_CA)^2
+ *   clash  w_clash (clash_distance - |CA_i - CA_j|)^2 where the distance is below clash_distance, once per unordered pair {i, j} inside
+ *          residue_mask of which at least one moves, not chain neighbours (equal chain and residue_idx differing by exactly 1)
+ *   tether w_tether |CA_i - CA_i of the input|^2 over the moving residues.
+ * DIFFAB_REFINE_CA_N / _C_CA are the third sides of the triangles (1.526, 1.329, 116.2 degrees) and (1.329, |N - CA| = 1.46061...,
+ * 121.7 degrees), computed in double.  A cis peptide is pulled to trans by the CA - CA term.
+ * One iteration is a Jacobi step: every moving residue k reads the state before the step.
+ *   force on a of a term with partner b: ((-2 w) (d - d0) / d) (a - b), d = |a - b| = sqrt((dx dx + dy dy) + dz dz); none where d < 1e-6.
+ *   f_C  = bond(C_k, N_s) + angle(C_k, CA_s);        f_N = bond(N_k, C_p) + angle(N_k, CA_p)                 p = pred(k), s = succ(k)
+ *   f_CA = angle(CA_k, N_s) + trans(CA_k, CA_s) + angle(CA_k, C_p) + trans(CA_k, CA_p) + clash + tether, added in this order;
+ *          clash = sum over the partners j of ((2 w_clash) (clash_distance - d) / d) (CA_k - CA_j), 1e-6 <= d < clash_distance: four
+ *          partial sums over j = l, l + 4, l + 8, ... (l = 0..3, ascending), combined as (0 + 1) + (2 + 3);
+ *          tether = (-2 w_tether) (CA_k - CA_k of the input).
+ *   F = (f_N + f_CA) + f_C;    torque = (N_k - CA_k) x f_N + (C_k - CA_k) x f_C
+ *   t <- t + step F  (kept as it is where F is exactly zero)
+ *   O <- O Exp(w)^T, w = (step / DIFFAB_REFINE_INERTIA) torque  (kept where w is exactly zero); Exp(w) = I + a hat(w) + b (w w^T - |w|^2 I),
+ *        a = sin|w| / |w|, b = (1 - cos|w|) / |w|^2 (Rodrigues; a = 1, b = 1/2 where |w| < 1e-6); then N and C are placed again.
+ * After the last step the rows of every O that was rotated at least once are orthonormalised: e1 = O0 / |O0|, e2 = the normalised
+ * O1 - (e1 . O1) e1, e3 = e1 x e2 (the order of io.frames_from_backbone), and N and C are placed once more.  With iterations = 0, or all
+ * weights 0, every output bit is the input's.  All of this is fp32, one rounding per operation as written (no contraction), in an order
+ * that depends on K alone: a design alone gives the bits it gives in a batch, and group_size changes no bits.
+ * Outputs.  out_translations / out_orientations: the refined frames.  Each of the following may be NULL: energy_before / energy_after
+ * (rows): the energy of the input and of the output frames; terms_after (rows,5): bond, angle, trans, clash, tether of the output;
+ * each term in fp32, summed in fp64 in a fixed order of the row and rounded once.  max_shift (rows): the largest |CA - CA of the
+ * input| over the moving residues, 0 without one.
+ * One work-group of 256 threads per row for all iterations, the row's atoms in DIFFAB_REFINE_LDS_BYTES(K) bytes of LDS; a launch before
+ * it finds the chain neighbours of every patch.  A row without a moving residue is copied and its energies (0) reported.
+ * opt: NULL means DIFFAB_REFINE_DEFAULTS.  Refused before anything is enqueued, DIFFAB_ERR_ARG with a message: struct_bytes other than
+ * sizeof(diffab_refine_options) (checked before any other field); rows < 0, group_size < 1, rows no multiple of group_size, K outside
+ * [1, DIFFAB_REFINE_MAX_K]; iterations outside [0, DIFFAB_REFINE_MAX_ITERATIONS]; a step or clash_distance that is not finite and > 0; a
+ * weight that is not finite and >= 0; step x the largest weight (the product in double of the fp32 values) above
+ * DIFFAB_REFINE_MAX_STEP_WEIGHT (0.1 and a float rounding: the energy fell monotonically at 0.08 and not at 0.12); a null input or frame
+ * output; an output that is its input; a workspace that is NULL or not 16-byte aligned (smaller than
+ * DIFFAB_REFINE_WORKSPACE_BYTES(G, K): DIFFAB_ERR_WORKSPACE).  rows = 0 succeeds without looking at a pointer. */
+#define DIFFAB_REFINE_MAX_K 256
+#define DIFFAB_REFINE_MAX_ITERATIONS 100000
+#define DIFFAB_REFINE_BOND 1.329f
+#define DIFFAB_REFINE_CA_N 2.4260487261296753f
+#define DIFFAB_REFINE_C_CA 2.437145924677046f
+#define DIFFAB_REFINE_CA_CA 3.8f
+#define DIFFAB_REFINE_INERTIA 4.45f
+#define DIFFAB_REFINE_MAX_STEP_WEIGHT 0.1000001
+#define DIFFAB_REFINE_WORKSPACE_BYTES(G, K) ((size_t)(G) * (size_t)(K) * 8 + 1024)
+#define DIFFAB_REFINE_LDS_BYTES(K) ((size_t)(K) * 148)
+typedef struct {
+  uint32_t struct_bytes; /* sizeof(diffab_refine_options); anything else: DIFFAB_ERR_ARG, before any other field is read */
+  int32_t iterations;
+  float step;
+  float w_bond, w_angle, w_trans, w_clash, w_tether;
+  float clash_distance;
+} diffab_refine_options;
+#define DIFFAB_REFINE_DEFAULTS {(uint32_t)sizeof(diffab_refine_options), 200, 0.05f, 1.0f, 1.0f, 1.0f, 1.0f, 0.0f, 3.8f}
+int diffab_refine_backbone(const float* translations, const float* orientations, const uint8_t* generation_mask, const uint8_t* residue_mask,
+                           const int32_t* chain, const int32_t* residue_idx, int32_t rows, int32_t group_size, int32_t K,
+                           const diffab_refine_options* opt, float* out_translations, float* out_orientations, float* energy_before,
+                           float* energy_after, float* terms_after, float* max_shift, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Backward of the two context encoders (training through encode_context, diffab_pytorch.py:843-854 under autograd).
  * d_out is the gradient w.r.t. the module output; parameter gradients ACCUMULATE (+=) into the buffers of `g`, which has the
  * layout of the weight struct (the caller zero-fills them).  Inputs other than parameters take no gradient.  Nothing is taped:
