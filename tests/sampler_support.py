@@ -66,13 +66,19 @@ def unit_model(NL=2, seed=17):
     return dims, model, {"denoiser." + k: v for k, v in sd.items()}
 
 
-def patches(B, K, dims, seed, chains=False, collapse=True):
+def patches(B, K, dims, seed, chains=False, collapse=True, generation_mask=None):
     """syn.patches on the device.  chains=True (the guidance and steering tests) adds two chains with a gap in residue_idx and a few
     padded context residues, and with `collapse` puts the generated residues within ~1 A of one point (clashes and broken bonds for the
-    potential to act on)."""
+    potential to act on).  generation_mask (B, K) replaces the synthetic one (before the collapse)."""
     inp = {k: v.cuda() for k, v in syn.patches(B, K, dims, seed=seed, coord_sigma=6.0).items() if k in STATE + CTX}
-    if not chains:
-        return inp
+    if generation_mask is not None:
+        inp["generation_mask"] = generation_mask.cuda()
+    return add_chains(inp, seed, collapse) if chains else inp
+
+
+def add_chains(inp, seed, collapse=True):
+    """The chains=True part of `patches`, on device inputs of any origin (in place, and returned)."""
+    B, K = inp["seq_idx"].shape
     g = torch.Generator(device="cuda").manual_seed(seed)
     gm = inp["generation_mask"]
     if collapse:

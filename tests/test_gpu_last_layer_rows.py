@@ -12,6 +12,8 @@ import torch
 
 from diffab_pytorch import _hip, synthetic as syn
 from diffab_pytorch.guidance import SampleGuidance
+from diffab_pytorch.steering import ParticleSteering
+from diffab_pytorch.temperature import SampleTemperature
 from sampler_support import assert_bitwise, hip, make_model, patches, sample
 
 pytestmark = pytest.mark.gpu
@@ -203,13 +205,22 @@ def test_graph_then_another_mask_on_the_same_workspace(models, inputs8):
                    _run(model, inp, gm2, _hip.FLAG_MULTI_LAUNCH, skip_unused_rows=False, **kw), "graph, second mask")
 
 
-@pytest.mark.parametrize("option", ["guidance", "trajectory", "allowed_aa"])
+@pytest.mark.parametrize("option", ["guidance", "trajectory", "allowed_aa", "temperature", "steps", "steering"])
 def test_options_that_read_the_step_outputs(models, option):
-    """guidance reads x0_hat, the record the predictions, allowed_aa the posterior - each behind the generation mask"""
+    """guidance reads x0_hat, the record the predictions, allowed_aa the posterior, temperature O0_hat and the posterior, a jump the
+    posterior (rewritten in place) and steering eps_hat for its energy - each behind the generation mask"""
     dims, model = models[3]
-    inp = patches(8, 128, dims, seed=171, chains=option == "guidance")
+    inp = patches(8, 128, dims, seed=171, chains=option in ("guidance", "steering"))
+    mix = lambda v: torch.tensor(v * 2)  # per row: lambda_x, lambda_O (two stacked tables and a zero row), tau
     kw = {"guidance": dict(guidance=SampleGuidance(clash=2.0, bond=1.0, max_shift=0.5)),
           "trajectory": dict(trajectory=True, trajectory_predictions=True),
-          "allowed_aa": dict(allowed_aa=torch.rand(8, 128, 21, generator=torch.Generator().manual_seed(3)) < 0.6)}[option]
+          "allowed_aa": dict(allowed_aa=torch.rand(8, 128, 21, generator=torch.Generator().manual_seed(3)) < 0.6),
+          "temperature": dict(temperature=SampleTemperature(mix([1.5, 0.0, 1.0, 0.5]), mix([0.0, 0.3, 0.6, 1.0]), mix([0.5, 1.0, 0.0, 2.0]))),
+          "steps": dict(steps=[60, 58, 57, 54], t_stop=53),
+          "steering": dict(num_samples=2, steering=ParticleSteering(strength=0.05, ess_threshold=2.0))}[option]
+    moved = 0
     for gm in (inp["generation_mask"].cpu(), _segment(8, 128, [(110, 128)])):
-        _three_ways(model, inp, gm, option, **kw)
+        out = _three_ways(model, inp, gm, option, **kw)
+        if option == "steering":
+            moved += int((out["steering"]["ancestors"].cpu() != torch.arange(16)).sum())
+    assert option != "steering" or moved > 0, "some row must move for this case to say anything"
