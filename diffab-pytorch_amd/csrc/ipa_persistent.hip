@@ -21,6 +21,7 @@
 #include "proj_frames_h3_tile.h"
 #include "rowgemm_h3_tile.h"
 #include "mlp_chain_tile.h"
+#include "mlp_chain_slab.h"
 
 namespace diffab {
 
@@ -50,6 +51,7 @@ struct ModuleArgs {
   const char* planes;        // per layer: ipa_layer_planes_bytes() (w_bias, gamma, b_out | projection planes | to_out planes | 1 / scales)
   size_t layer_stride, pj_off, out_off, wis_off, small_off;  // offsets of the fp16 planes, 1 / scale vectors and small vectors in a layer's block
   // diagnostics (null in production): [item][wave][8] of the attention tiles + [B][NL][4] phase stamps behind them + [B] the end of the heads
+  // + [B] the start of the patch
   unsigned long long* stamps;
   // the denoiser's MLPs as phases of the same launch (null emb_X: not fused): the embedding MLP of the patch's rows in front of layer 0
   // (emb_X -> xa), the three heads behind the last layer (module output -> heads.Y[]); mlp_chain_tile.h, bitwise mlp_chain_b6_kernel
@@ -88,6 +90,8 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
   };
 #pragma unroll 1
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    // (the start of the patch: what lies between it and layer 0's first stamp is the embedding MLP)
+    if (pstamps != nullptr && threadIdx.x == 0) pstamps[static_cast<size_t>(a.B) * a.NL * 4 + a.B + b] = __builtin_amdgcn_s_memrealtime();
     if (a.emb_X != nullptr) {  // ---- to_res_emb of the patch's rows (diffab_pytorch.py:519-523, folded concatenation)
 #pragma unroll 1
       for (int dt = 0; dt < DT; ++dt) {
@@ -182,6 +186,25 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
     }
     if (a.emb_X != nullptr) {  // ---- the three heads on the module's output rows (:525-533, beta columns folded into bias tables)
       const float* xfin = (a.NL & 1) ? a.xb : a.xa;
+      if (KRES == 128 && a.last_layer_rows != nullptr) {
+        // reverse sampler, K = 128: the three heads of the 32-row slabs with a generated residue (the plan's slab bits), two slabs to a
+        // pass of the slab form (mlp_chain_slab.h: the units of the three chains side by side on six waves, weight fragments straight
+        // from global memory and shared by the two slabs, two barriers per layer) instead of three chain tiles behind one another.
+        // The heads of the other rows are never read and keep what the workspace held.  Bitwise the chain tile's rows.
+        unsigned rest = static_cast<unsigned>(module_plan_word(a.last_layer_rows, b * (2 + NTILE) + 1)) & 15u;
+#pragma unroll 1
+        while (rest != 0) {
+          const int s0 = __builtin_ctz(rest);
+          rest &= rest - 1;
+          const int ns = rest != 0 ? 2 : 1;
+          const int s1 = rest != 0 ? __builtin_ctz(rest) : s0;
+          rest &= rest - 1;  // (0 stays 0)
+          int tid = threadIdx.x;
+          asm volatile("" : "+v"(tid));
+          chainslab::mlp_chain_slabs<3>(reinterpret_cast<__bf16*>(lds), tid, ns, b * 128 + 32 * s0, b * 128 + 32 * s1, xfin, 128, a.heads, M);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the barrier behind the last layer is the slab form's own)
+      } else {
 #pragma unroll 1
       for (int hdt = 0; hdt < 3 * DT; ++hdt) {
         const int hd = hdt / DT, dt = hdt % DT;
@@ -202,6 +225,7 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
 #undef HSEL
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // the next chain (or the next patch's first phase) overwrites the image
+      }
       }
       if (pstamps != nullptr && threadIdx.x == 0) pstamps[static_cast<size_t>(a.B) * a.NL * 4 + b] = __builtin_amdgcn_s_memrealtime();
     }

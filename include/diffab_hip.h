@@ -196,8 +196,9 @@ int diffab_kernel_timer_enable(int on);
 int diffab_debug_set_attn_stamps(void* device_buffer);
 /* Diagnostics of the patch-resident module kernel (DIFFAB_FLAG_PERSISTENT_MODULE): its start-up stagger (work-groups of class
  * (index / 8) % classes start class x ticks late, ticks of 10 ns; default 8 x 1000: eight classes 10 us apart),
- * and a stamp buffer of (B NL 8 tiles x 8 waves x 8) + (B NL 4) + (B) uint64 filled with 100 MHz s_memrealtime stamps (NULL: off; the
- * last B: the end of each patch's heads). */
+ * and a stamp buffer of (B NL 8 tiles x 8 waves x 8) + (B NL 4) + (2 B) uint64 filled with 100 MHz s_memrealtime stamps (NULL: off; of
+ * the last 2 B the first B: the end of each patch's heads, the second B: the start of each patch, in front of the embedding MLP).  The
+ * kernel writes ALL of it: a buffer sized for an earlier library (which ended with one B) is B uint64 too short for this one. */
 int diffab_debug_set_attn_variant(int32_t v); /* Reference paths for tests and tools (process-global): bit 2 (4) = the PairEmbedding
                                                  forward / backward as their unfused launches where the fused kernel would apply, bit 6
                                                  (64) = the PairEmbedding backward's matrix-core kernels (csrc/pair_chain_bwd.hip: 64-wide

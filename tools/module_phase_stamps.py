@@ -1,6 +1,6 @@
 """Diagnostic: the phases of the patch-resident module launch (ipa_persistent.hip) per patch and layer, from its phase stamps
 (diffab_debug_set_module_stamps: four chip-clock stamps per (patch, layer) - projections start, attention start, to_out start, to_out
-end - and one per patch at the end of its heads; never enabled in production).  Runs reverse steps of the benchmark model (bench.py's geometry: B = 256, K = 128, six layers) and
+end - one per patch at the end of its heads and one at its start, in front of the embedding MLP; never enabled in production).  Runs reverse steps of the benchmark model (bench.py's geometry: B = 256, K = 128, six layers) and
 prints the per-phase times of the last step's launch in microseconds.
 usage: module_phase_stamps.py [steps] [json_out] ; DIFFAB_HIP_LIB selects the build (A/B of two builds: run this once per build)"""
 import ctypes as C
@@ -28,9 +28,9 @@ hd, w = model.denoiser.hip_dims(B, K), model.denoiser.hip_weights()
 sd_dev, tab = model._sched_on_device(), model._reverse_so3().struct()
 ws = _hip.workspace(lib.diffab_sample_workspace_bytes(C.byref(hd)))
 gm, rc, pc = inp["generation_mask"], inp["res_context_emb"], inp["pair_context_emb"]
-# [B NL NTILE items][8 waves][8] attention-item stamps, then [B][NL][4] phase stamps, then [B] the end of the heads (a build from before
-# that stamp leaves it at zero: its heads are then not reported)
-stamps = torch.zeros(B * NL * NTILE * 64 + B * NL * 4 + B, dtype=torch.int64, device="cuda")
+# [B NL NTILE items][8 waves][8] attention-item stamps, then [B][NL][4] phase stamps, then [B] the end of the heads and [B] the start of
+# the patch (a build from before one of these stamps leaves it at zero: its heads / its embedding are then not reported)
+stamps = torch.zeros(B * NL * NTILE * 64 + B * NL * 4 + 2 * B, dtype=torch.int64, device="cuda")
 seq, x, O = inp["seq_idx"].clone(), inp["translations"].clone(), inp["orientations"].clone()
 _hip.check(lib.diffab_sample_init(_hip.ptr(seq), _hip.ptr(x), _hip.ptr(O), _hip.ptr(gm), 2024, 0, B, K, model.T, _hip.stream_ptr()), "init")
 lib.diffab_debug_set_module_stamps(_hip.ptr(stamps))
@@ -43,7 +43,8 @@ try:
 finally:
     lib.diffab_debug_set_module_stamps(None)
 ph = stamps[B * NL * NTILE * 64:B * NL * NTILE * 64 + B * NL * 4].view(B, NL, 4).cpu().double()
-heads_end = stamps[B * NL * NTILE * 64 + B * NL * 4:].cpu().double()
+heads_end = stamps[B * NL * NTILE * 64 + B * NL * 4:B * NL * NTILE * 64 + B * NL * 4 + B].cpu().double()
+patch_start = stamps[B * NL * NTILE * 64 + B * NL * 4 + B:].cpu().double()
 if not bool((ph > 0).all()):
     sys.exit("module phase stamps missing: the module launch did not run for every (patch, layer)")
 proj = (ph[:, :, 1] - ph[:, :, 0]) * TICK_US
@@ -72,10 +73,12 @@ for n in sorted(set(tiles_run.tolist())):
 last = {"attention": attn[:, -1], "to_out": to_out[:, -1]}
 if bool((heads_end > 0).all()):
     last["heads (end of to_out -> end of the work-group)"] = (heads_end - ph[:, -1, 3]) * TICK_US
+if bool((patch_start > 0).all()):
+    last["embedding (start of the patch -> layer 0's projections)"] = (ph[:, 0, 0] - patch_start) * TICK_US
 res["last_layer"] = {}
 for name, v in last.items():
     res["last_layer"][name] = {"mean_us": float(v.mean()), "max_us": float(v.max())}
-    print(f"  last layer {name}: mean {float(v.mean()):.2f} us, slowest {float(v.max()):.2f}")
+    print(f"  {'' if name.startswith('embedding') else 'last layer '}{name}: mean {float(v.mean()):.2f} us, slowest {float(v.max()):.2f}")
 own = (ph[:, -1, 3] - ph[:, 0, 0]) * TICK_US  # a work-group's module time (B <= #CUs: one patch each)
 res["work_group_us"] = {"mean": float(own.mean()), "max": float(own.max()), "min": float(own.min())}
 print(f"  work-group first stamp -> its last: mean {float(own.mean()):.1f} us, slowest {float(own.max()):.1f}, fastest {float(own.min()):.1f}")
