@@ -384,7 +384,7 @@ static int denoise_step_taped(const diffab_dims* d, const diffab_denoiser_weight
   if (int rc = launch_embed_concat(res_ctx, w->seq_emb, seq_t, D, rows, tp.cat2, st)) return rc;
   if (int rc = launch_linear(tp.cat2, 2 * D, w->res_w0, w->res_b0, tp.h1, D, rows, D, 2 * D, true, st)) return rc;
   if (int rc = launch_linear(tp.h1, D, w->res_w2, w->res_b2, tp.x[0], D, rows, D, D, false, st)) return rc;
-  const bool b6 = tp.planes && use_b6_gemm(flags) && fast_path_supported(d);
+  const bool b6 = plan_backward(d).fast && use_b6_gemm(flags);  // the layers' dense products from the tape's weight planes
   for (int l = 0; l < d->NL; ++l) {
     if (b6)
       if (int rc = ipa_layer_split_weights(&w->layers[l], tp.planes, st)) return rc;
@@ -694,9 +694,17 @@ int diffab_train_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "train_step_bwd: tape too small");
   DIFFAB_REQUIRE(workspace_bytes >= train_bwd_workspace_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "train_step_bwd: workspace %zu < %zu",
                  workspace_bytes, train_bwd_workspace_floats(d) * sizeof(float));
-  const TrainTape tp = carve_tape(d, static_cast<float*>(const_cast<void*>(tape)));
-  return train_step_bwd(d, w, grads, tp, seq_t, x_t, O_t, pair_ctx, out_eps, out_O0, out_posterior, true_post, true_eps, true_O0, gen_mask,
-                        res_mask, upstream3, d_res_ctx, d_pair_ctx, static_cast<float*>(workspace), as_stream(stream));
+  BackwardArgs a{};
+  a.root = BWD_LOSSES;
+  a.d = d; a.w = w; a.g = grads;
+  a.tp = carve_tape(d, static_cast<float*>(const_cast<void*>(tape)));
+  a.ws = static_cast<float*>(workspace); a.st = as_stream(stream);
+  a.seq_t = seq_t; a.trans = x_t; a.rot = O_t; a.pair_ctx = pair_ctx;
+  a.eps_hat = out_eps; a.O0_hat = out_O0; a.post_hat = out_posterior;
+  a.true_post = true_post; a.true_eps = true_eps; a.true_O0 = true_O0;
+  a.gm = gen_mask; a.rm = res_mask; a.upstream3 = upstream3;
+  a.d_res_ctx = d_res_ctx; a.d_pair_ctx = d_pair_ctx;
+  return run_backward(a);
 }
 
 /* ---- Denoiser.forward / InvariantPointAttentionLayer.forward under autograd: taped forward + backward from arbitrary cotangents ---- */
@@ -732,9 +740,16 @@ int diffab_denoise_step_bwd(const diffab_dims* d, const diffab_denoiser_weights*
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_bwd: tape too small");
   DIFFAB_REQUIRE(workspace_bytes >= train_bwd_workspace_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_bwd: workspace %zu < %zu",
                  workspace_bytes, train_bwd_workspace_floats(d) * sizeof(float));
-  const TrainTape tp = carve_tape(d, static_cast<float*>(const_cast<void*>(tape)));
-  return denoise_step_bwd(d, w, grads, tp, seq_t, x_t, O_t, pair_ctx, out_posterior, d_eps, d_O0, d_posterior, d_res_ctx, d_pair_ctx,
-                          static_cast<float*>(workspace), as_stream(stream), d_x_t, d_O_t);
+  BackwardArgs a{};
+  a.root = BWD_COTANGENTS;
+  a.d = d; a.w = w; a.g = grads;
+  a.tp = carve_tape(d, static_cast<float*>(const_cast<void*>(tape)));
+  a.ws = static_cast<float*>(workspace); a.st = as_stream(stream);
+  a.seq_t = seq_t; a.trans = x_t; a.rot = O_t; a.pair_ctx = pair_ctx;
+  a.post_hat = out_posterior;
+  a.cot_eps = d_eps; a.cot_O0 = d_O0; a.cot_post = d_posterior;
+  a.d_res_ctx = d_res_ctx; a.d_pair_ctx = d_pair_ctx; a.d_trans = d_x_t; a.d_rot = d_O_t;
+  return run_backward(a);
 }
 
 static diffab_dims one_layer(const diffab_dims* d) {
@@ -767,7 +782,7 @@ int diffab_ipa_layer_fwd_taped(const diffab_dims* d, const diffab_ipa_layer_weig
   const size_t nb = sizeof(float) * static_cast<size_t>(d->B) * d->K * d->D;
   DIFFAB_HIP_CHECK(hipMemcpyAsync(tp.x[0], x, nb, hipMemcpyDeviceToDevice, st));
   flags = taped_flags(flags);
-  const bool b6 = tp.planes && use_b6_gemm(flags) && fast_path_supported(&d1);
+  const bool b6 = plan_backward(&d1).fast && use_b6_gemm(flags);
   if (b6)
     if (int rc = ipa_layer_split_weights(w, tp.planes, st)) return rc;
   if (int rc = ipa_layer_dispatch(&d1, w, tp.x[0], e, R, t, tp.x[1], tp.ipa_ws[0], flags, st, tp.sp[0], tp.d2[0], b6 ? tp.planes : nullptr,
@@ -788,8 +803,19 @@ int diffab_ipa_layer_bwd(const diffab_dims* d, const diffab_ipa_layer_weights* w
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_bwd: tape too small");
   DIFFAB_REQUIRE(workspace_bytes >= train_bwd_workspace_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_bwd: workspace %zu < %zu",
                  workspace_bytes, train_bwd_workspace_floats(&d1) * sizeof(float));
-  const TrainTape tp = carve_tape(&d1, static_cast<float*>(const_cast<void*>(tape)));
-  return ipa_layer_bwd(&d1, w, grads, tp, R, t, e, dy, dx, d_e, static_cast<float*>(workspace), as_stream(stream), d_R, d_t);
+  // One IPA layer backward: the one-layer tape of the taped layer forward (x[0] = the layer input), dy -> dx, d_e += ..
+  diffab_denoiser_weights w1{}, g1{};
+  w1.layers = w;
+  g1.layers = grads;
+  BackwardArgs a{};
+  a.root = BWD_LAYER;
+  a.d = &d1; a.w = &w1; a.g = &g1;
+  a.tp = carve_tape(&d1, static_cast<float*>(const_cast<void*>(tape)));
+  a.ws = static_cast<float*>(workspace); a.st = as_stream(stream);
+  a.trans = t; a.rot = R; a.pair_ctx = e;
+  a.layer_dy = dy; a.layer_dx = dx;
+  a.d_pair_ctx = d_e; a.d_trans = d_t; a.d_rot = d_R;
+  return run_backward(a);
 }
 
 // ---- the options of diffab_sample_loop_ex: one helper per option checks the caller's struct (everything on the host, before the first

@@ -60,19 +60,20 @@ class StreamOrder {
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Bump allocator over the caller's workspace (256-B aligned carves).
+// Bump allocator over the caller's workspace: a null base gives null pointers and the size.  Carves are 256-B aligned; align =
+// sizeof(float) packs float buffers back to back (the training tape and the backward's workspace, whose offsets pick kernels).
 struct Carver {
   char* base;
-  size_t off = 0;
-  explicit Carver(void* p) : base(static_cast<char*>(p)) {}
+  size_t align, off = 0;
+  explicit Carver(void* p, size_t align_ = 256) : base(static_cast<char*>(p)), align(align_) {}
   template <typename T>
   T* take(size_t n) {
-    off = align_up(off, 256);
+    off = align_up(off, align);
     T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
     off += n * sizeof(T);
     return r;
   }
-  size_t bytes() const { return align_up(off, 256); }
+  size_t bytes() const { return align_up(off, align); }
 };
 
 }  // namespace diffab

@@ -1661,395 +1661,428 @@ __global__ void embed_bwd_kernel(const float* __restrict__ dcat2, const int64_t*
 }
 
 // ------------------------------------------------------------------ orchestration
-size_t train_tape_floats(const diffab_dims* d) {
-  const size_t rows = static_cast<size_t>(d->B) * d->K, D = d->D;
-  const size_t NP = 3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3;
-  const size_t F = d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV;
-  const size_t keep = (fast_path_supported(d) && attention_split_supported(d)) ? 2 * static_cast<size_t>(d->B) * d->H * d->K * d->K : 0;
-  return rows * (2 * D + D + D) + static_cast<size_t>(d->NL) * (rows * (NP + F + D) + keep) + rows * (D + 3) + 6 * rows * D + rows * 3 +
-         rows * d->V + 1024 + (fast_path_supported(d) ? ipa_layer_planes_bytes() / sizeof(float) + 64 : 0);
+BackwardPlan plan_backward(const diffab_dims* d) {
+  BackwardPlan p{};
+  p.fast = fast_path_supported(d);
+  p.probs_on_tape = p.fast && attention_split_supported(d);
+  p.de_slots = p.probs_on_tape && d->NL <= kDeLayersMax;
+  p.split_planes = d->D == 128 && use_b6_gemm();
+  return p;
 }
 
+// The tape and the workspace are carved float by float (Carver at float granularity): the launch choices below test pointer alignment,
+// so every buffer keeps its offset.  A buffer that must start on a 256-byte boundary is taken with kAlignSlack floats more and rounded up.
+constexpr size_t kAlignSlack = 64;
+static void* round_up_256(float* raw) { return reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(raw) + 255) & ~static_cast<uintptr_t>(255)); }
+
 TrainTape carve_tape(const diffab_dims* d, float* base) {
-  const size_t rows = static_cast<size_t>(d->B) * d->K, D = d->D;
-  const size_t NP = 3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3;
-  const size_t F = d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV;
+  const Geometry geo(d);
+  const BackwardPlan plan = plan_backward(d);
+  const size_t D = d->D;
+  Carver c(base, sizeof(float));
   TrainTape t;
-  float* p = base;
-  auto take = [&](size_t n) { float* r = p; p += n; return r; };
-  t.cat2 = take(rows * 2 * D);
-  t.h1 = take(rows * D);
-  t.x[0] = take(rows * D);
-  const bool keep = fast_path_supported(d) && attention_split_supported(d);
-  const size_t HKK = static_cast<size_t>(d->B) * d->H * d->K * d->K;
+  t.cat2 = c.take<float>(geo.per_row(2 * D));
+  t.h1 = c.take<float>(geo.per_row(D));
+  t.x[0] = c.take<float>(geo.per_row(D));
   for (int l = 0; l < kMaxLayers; ++l) t.sp[l] = t.d2[l] = nullptr;
   for (int l = 0; l < d->NL; ++l) {
-    t.ipa_ws[l] = take(rows * (NP + F));
-    t.x[l + 1] = take(rows * D);
-    if (keep) {
-      t.sp[l] = take(HKK);
-      t.d2[l] = take(HKK);
+    t.ipa_ws[l] = c.take<float>(geo.per_row(geo.NP + geo.F));
+    t.x[l + 1] = c.take<float>(geo.per_row(D));
+    if (plan.probs_on_tape) {
+      t.sp[l] = c.take<float>(geo.HKK);
+      t.d2[l] = c.take<float>(geo.HKK);
     }
   }
-  t.cat3 = take(rows * (D + 3));
-  for (int hd = 0; hd < 3; ++hd) { t.t1[hd] = take(rows * D); t.t2[hd] = take(rows * D); }
-  t.vbuf = take(rows * 3);
-  t.logits = take(rows * d->V);
-  t.scratch = take(1024);  // (the +1024 of train_tape_floats)
-  t.planes = nullptr;
-  if (fast_path_supported(d)) {  // split bf16 planes of one layer's dense weights, re-filled by every layer's forward (stream order)
-    float* raw = take(ipa_layer_planes_bytes() / sizeof(float) + 64);
-    t.planes = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(raw) + 255) & ~static_cast<uintptr_t>(255));
-  }
+  t.cat3 = c.take<float>(geo.per_row(D + 3));
+  for (int hd = 0; hd < 3; ++hd) { t.t1[hd] = c.take<float>(geo.per_row(D)); t.t2[hd] = c.take<float>(geo.per_row(D)); }
+  t.vbuf = c.take<float>(geo.per_row(3));
+  t.logits = c.take<float>(geo.per_row(d->V));
+  t.scratch = c.take<float>(1024);
+  // split bf16 planes of one layer's dense weights, re-filled by every layer's forward (stream order)
+  t.planes = plan.fast ? round_up_256(c.take<float>(ipa_layer_planes_bytes() / sizeof(float) + kAlignSlack)) : nullptr;
+  t.floats = c.bytes() / sizeof(float);
   return t;
 }
 
 // split bf16 planes of one transposed weight operand at a time (bf16x6 input-gradient products; stream-ordered reuse)
 static size_t bwd_planes_floats(const diffab_dims* d) {
   if (d->D != 128) return 0;
-  const size_t NP = 3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3;
-  const size_t F = d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV;
-  const size_t kmax = ((NP > F ? NP : F) + 31) / 32 * 32;
-  const size_t a = rowgemm128_b6_scratch_bytes(static_cast<int>(kmax)), c = xstat_h3_scratch_bytes(static_cast<int>(F));
-  return (a > c ? a : c) / sizeof(float) + 128;
+  const Geometry geo(d);
+  const size_t kmax = static_cast<size_t>((max(geo.NP, geo.F) + 31) / 32 * 32);
+  const size_t a = rowgemm128_b6_scratch_bytes(static_cast<int>(kmax)), c = xstat_h3_scratch_bytes(geo.F);
+  return (a > c ? a : c) / sizeof(float) + 2 * kAlignSlack;  // (the round-up, and as much again that no kernel is known to touch: the size is the callers')
 }
-size_t train_bwd_workspace_floats(const diffab_dims* d) {
-  const size_t rows = static_cast<size_t>(d->B) * d->K, D = d->D;
-  const size_t NP = 3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3;
-  const size_t F = d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV;
-  const size_t HKK = static_cast<size_t>(d->B) * d->H * d->K * d->K;
-  return rows * (d->V + 3 + 3) + rows * (D + 3) + 6 * rows * D + 2 * rows * D + rows * F + 2 * rows * NP + rows * 2 * D + 64 + 2 * HKK +
-         rows * d->H * d->PV * 3 + rows * (d->H * d->C + d->H) + 64 +
-         ((fast_path_supported(d) && attention_split_supported(d)) ? 3 * HKK : 0) +  // probabilities / g, squared distances, dA_kv
-         ((fast_path_supported(d) && attention_split_supported(d) && d->NL <= kDeLayersMax)
-              ? static_cast<size_t>(d->NL) * (HKK + rows * d->H * d->C) + 64 : 0) +  // g and d o_e of every layer (d pair_ctx in one pass)
-         bwd_planes_floats(d);
+
+struct BwdWorkspace {
+  float* cnt;                       // 64: the masks' counts (BWD_LOSSES)
+  float *d_logits, *d_eps, *d_v;    // gradients of the three heads' outputs
+  float* dcat3;                     // rows x (D + 3): accumulates over the heads
+  float *dt2s[3], *dt1s[3];         // per head: the weight-gradient products beside the chain read them while the next head runs
+  float *dxa, *dxb;                 // d x of the layer chain, ping-pong
+  float* dfeat;                     // rows x F
+  float* dprojs[2];                 // rows x NP, by layer parity (same reason as dt2s)
+  float* dcat2;                     // rows x 2 D
+  float *At, *Gt;                   // transposed probabilities and g [b][h][j][i] of the VALU row passes, for their key passes
+  float* dogbuf;                    // rows x H PV 3: gradient of the global value-point sums
+  float* wb_part;                   // per-row partials of d w_bias (H C) and d gamma (H)
+  // BackwardPlan::probs_on_tape.  Pn and D2g held recomputed probabilities and squared distances before every taped forward kept them;
+  // nothing writes them now, the slots stay so that the buffers behind them keep their offsets and the callers' sizes hold
+  float *Pn, *D2g;
+  float* dAkv;                      // [b][h][i][j]: d A_kv, then g, of the current layer
+  float *g_keep, *doe_keep;         // BackwardPlan::de_slots: g and the o_e columns of d feat of EVERY layer
+  void* planes;                     // BackwardPlan::split_planes: 256-byte aligned
+  size_t floats;
+};
+
+static BwdWorkspace carve_bwd_workspace(const diffab_dims* d, const BackwardPlan& plan, float* base) {
+  const Geometry geo(d);
+  const size_t D = d->D, H = d->H;
+  Carver c(base, sizeof(float));
+  BwdWorkspace w{};
+  w.cnt = c.take<float>(64);
+  w.d_logits = c.take<float>(geo.per_row(d->V));
+  w.d_eps = c.take<float>(geo.per_row(3));
+  w.d_v = c.take<float>(geo.per_row(3));
+  w.dcat3 = c.take<float>(geo.per_row(D + 3));
+  for (int hd = 0; hd < 3; ++hd) {
+    w.dt2s[hd] = c.take<float>(geo.per_row(D));
+    w.dt1s[hd] = c.take<float>(geo.per_row(D));
+  }
+  w.dxa = c.take<float>(geo.per_row(D));
+  w.dxb = c.take<float>(geo.per_row(D));
+  w.dfeat = c.take<float>(geo.per_row(geo.F));
+  for (float*& dproj : w.dprojs) dproj = c.take<float>(geo.per_row(geo.NP));
+  w.dcat2 = c.take<float>(geo.per_row(2 * D));
+  w.At = c.take<float>(geo.HKK);
+  w.Gt = c.take<float>(geo.HKK);
+  w.dogbuf = c.take<float>(geo.per_row(H * d->PV * 3));
+  w.wb_part = c.take<float>(geo.per_row(H * d->C + H));
+  if (plan.probs_on_tape) {
+    w.Pn = c.take<float>(geo.HKK);
+    w.D2g = c.take<float>(geo.HKK);
+    w.dAkv = c.take<float>(geo.HKK);
+  }
+  if (plan.de_slots) {  // (the slots exist whether or not the call asks for d pair_ctx: the size depends on the dims alone)
+    w.g_keep = c.take<float>(d->NL * geo.HKK);
+    w.doe_keep = c.take<float>(d->NL * geo.per_row(H * d->C) + kAlignSlack);  // (slack no kernel is known to touch, like the tail's)
+  }
+  float* raw = c.take<float>(bwd_planes_floats(d));
+  w.planes = plan.split_planes ? round_up_256(raw) : nullptr;
+  c.take<float>(kAlignSlack);  // tail: no kernel is known to run past its buffer; the total is the one callers have always allocated
+  w.floats = c.bytes() / sizeof(float);
+  return w;
 }
+size_t train_bwd_workspace_floats(const diffab_dims* d) { return carve_bwd_workspace(d, plan_backward(d), nullptr).floats; }
 
 size_t attn_bwd_lds_bytes(const diffab_dims* d) {
-  const size_t H = d->H, F = H * d->DS + H * d->C + H * d->PV * 3 + H * d->PV;
-  return (3 * H * d->K + H * d->DS + H * d->PQ * 3 + H * d->PV * 3 + H + F) * sizeof(float);
+  const size_t H = d->H;
+  return (3 * H * d->K + H * d->DS + H * d->PQ * 3 + H * d->PV * 3 + H + Geometry(d).F) * sizeof(float);
 }
 
-// One backward driver, three roots:
-//   BWD_LOSSES      the three masked losses of diffab_pytorch.py:856-880 with upstream gradients upstream3 (the training step)
-//   BWD_COTANGENTS  arbitrary cotangents of the Denoiser outputs (cot_eps, cot_O0, cot_post; null = zero): Denoiser.forward under autograd
-//   BWD_LAYER       one IPA layer from d y (layer_dy) to d x (layer_dx): InvariantPointAttentionLayer.forward under autograd; `w` / `g`
-//                   then carry only layers[0] and `tp` is a one-layer tape
-enum { BWD_LOSSES = 0, BWD_COTANGENTS = 1, BWD_LAYER = 2 };
-static int run_backward(int mode, const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_denoiser_weights* g, const TrainTape& tp,
-                        const int64_t* seq_t, const float* x_t, const float* O_t, const float* pair_ctx, const float* eps_hat,
-                        const float* O0_hat, const float* post_hat, const float* true_post, const float* true_eps, const float* true_O0,
-                        const uint8_t* gm, const uint8_t* rm, const float* upstream3, const float* cot_eps, const float* cot_O0,
-                        const float* cot_post, const float* layer_dy, float* layer_dx, float* d_res_ctx, float* d_pair_ctx, float* ws,
-                        hipStream_t st, float* d_x_t = nullptr, float* d_O_t = nullptr) {
-  // d_x_t (rows x 3) / d_O_t (rows x 9), nullable: gradients with respect to the frames (translations_t, orientations_t), which the
-  // reference's forward is differentiable in (:315-336, :594-596); the training step never asks for them
-  const int rows = d->B * d->K, D = d->D, H = d->H, DS = d->DS, PQ = d->PQ, PV = d->PV, C = d->C, V = d->V;
-  const int NP = 3 * H * DS + 2 * H * PQ * 3 + H * PV * 3;
-  const int F = H * DS + H * C + H * PV * 3 + H * PV;
-  float* p = ws;
-  auto take = [&](size_t n) { float* r = p; p += n; return r; };
-  float* cnt = take(64);
-  float* d_logits = take(static_cast<size_t>(rows) * V);
-  float* d_eps = take(static_cast<size_t>(rows) * 3);
-  float* d_v = take(static_cast<size_t>(rows) * 3);
-  float* dcat3 = take(static_cast<size_t>(rows) * (D + 3));
-  float *dt2s[3], *dt1s[3];  // per head: the weight-gradient products beside the chain read them while the next head runs
-  for (int hd = 0; hd < 3; ++hd) {
-    dt2s[hd] = take(static_cast<size_t>(rows) * D);
-    dt1s[hd] = take(static_cast<size_t>(rows) * D);
-  }
-  float* dxa = take(static_cast<size_t>(rows) * D);
-  float* dxb = take(static_cast<size_t>(rows) * D);
-  float* dfeat = take(static_cast<size_t>(rows) * F);
-  float* dprojs[2] = {take(static_cast<size_t>(rows) * NP), take(static_cast<size_t>(rows) * NP)};  // by layer parity (same reason)
-  float* dcat2 = take(static_cast<size_t>(rows) * 2 * D);
-  const size_t HKK = static_cast<size_t>(d->B) * H * d->K * d->K;
-  float* At = take(HKK);
-  float* Gt = take(HKK);
-  float* dogbuf = take(static_cast<size_t>(rows) * H * PV * 3);
-  float* wb_part = take(static_cast<size_t>(rows) * (H * C + H));  // per-row partials of d w_bias (H*C) and d gamma (H)
-  const bool mfma_probs = fast_path_supported(d) && attention_split_supported(d);
-  float* Pn = mfma_probs ? take(HKK) : nullptr;
-  float* D2g = mfma_probs ? take(HKK) : nullptr;
-  float* dAkv = mfma_probs ? take(HKK) : nullptr;
-  // d pair_ctx in ONE pass behind the layer loop (launch_pair_de_layers) instead of a read-modify-write of the whole gradient per layer:
-  // needs g and the o_e columns of d feat of every layer kept, and the probabilities of every layer on the tape
-  bool defer_de = mfma_probs && d_pair_ctx != nullptr && mode != BWD_LAYER && d->NL <= kDeLayersMax && C == 64 && H == 8 &&
-                  fast_path_supported(d) && attention_split_supported(d);
-  for (int l = 0; l < d->NL && defer_de; ++l) defer_de = tp.sp[l] != nullptr;
-  float* g_keep = nullptr;
-  float* doe_keep = nullptr;
-  if (mfma_probs && fast_path_supported(d) && attention_split_supported(d) && d->NL <= kDeLayersMax) {  // (the slots exist either way: the size
-    g_keep = take(static_cast<size_t>(d->NL) * HKK);                                                     //  function does not know d_pair_ctx)
-    doe_keep = take(static_cast<size_t>(d->NL) * rows * H * C + 64);
-  }
-  void* planes = nullptr;  // bf16x6 input-gradient products (D = 128): the transposed weights as split planes, one operand at a time
-  if (bwd_planes_floats(d) > 0 && use_b6_gemm())
-    planes = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(take(bwd_planes_floats(d))) + 255) & ~static_cast<uintptr_t>(255));
+// The kernels of one layer's attention backward.  Row side (d logits through the softmax; d q on the VALU forms): the one-row kernel,
+// four query rows per work-group, or the MFMA path from the tape's probabilities.  Key side (d k, d v; d q on the MFMA forms): done with
+// the MFMA row side - keys_tn_b6 + keys_nn_b6 at K = 128, three keys_mfma launches straight from the [b][h][i][j] images at K = 64 -
+// or, behind a VALU row side, two keys_mfma launches from its transposed images, four keys per work-group, or the one-key kernel.
+enum class RowPass { kOneRow, kRows4, kMfma };
+enum class KeyPass { kOneKey, kKeys4, kMfma2, kMfma3, kB6 };
+struct AttnBwdKernels { RowPass rows; KeyPass keys; };
+constexpr int kRowsMr = 4, kKeysMr = 4;  // query rows / keys per work-group of the multi-row / multi-key kernels
+static size_t attn_bwd_lds_mr(const diffab_dims* d) {
+  return kRowsMr * ((attn_bwd_lds_bytes(d) / sizeof(float) + 3) & ~static_cast<size_t>(3)) * sizeof(float);
+}
+static size_t attn_bwd_lds_keys(const diffab_dims* d) { return 2 * static_cast<size_t>(d->H) * d->K * sizeof(float); }
+static size_t attn_bwd_lds_km(const diffab_dims* d) { return static_cast<size_t>(d->K) * KM_LD * sizeof(float); }
+// vec: 16-byte loads of the pair rows and of w_bias are possible - w_bias is this layer's, so the choice is made per layer
+static AttnBwdKernels choose_attn_bwd(const diffab_dims* d, const BackwardPlan& plan, bool vec) {
+  const bool multi_row = vec && d->H <= 8 && d->K % kRowsMr == 0 && attn_bwd_lds_mr(d) <= 160 * 1024;
+  if (multi_row && plan.probs_on_tape) return {RowPass::kMfma, d->K == 128 ? KeyPass::kB6 : KeyPass::kMfma3};
+  const RowPass rows = multi_row ? RowPass::kRows4 : RowPass::kOneRow;
+  if (plan.fast && d->K % 64 == 0 && attn_bwd_lds_km(d) <= 64 * 1024) return {rows, KeyPass::kMfma2};
+  if (d->K % kKeysMr == 0 && kKeysMr * attn_bwd_lds_keys(d) <= 64 * 1024) return {rows, KeyPass::kKeys4};
+  return {rows, KeyPass::kOneKey};
+}
 
-  float* dcur = dxa;
-  float* dnxt = dxb;
-  SideRun side(st);  // weight / bias gradients beside the chain; joined when it goes out of scope (every return path)
-  if (mode == BWD_LOSSES) {
-    hipLaunchKernelGGL(count_mask_kernel, dim3(1), dim3(1024), 0, st, gm, rm, static_cast<int64_t>(rows), cnt);
+static float* mut(const float* p) { return const_cast<float*>(p); }  // (the gradients come in the weights' struct of const pointers)
+
+// One backward and what its steps share.  The weight / bias gradients run beside the chain on `side`, which is joined when the run
+// goes out of scope (every return path).
+struct BwdRun {
+  struct Layer {  // layer l: its weights and gradients, its slots of the tape, its d proj buffer
+    int l;
+    const diffab_ipa_layer_weights *w, *g;
+    const float *proj, *feat, *xin;
+    float* dproj;
+  };
+  const BackwardArgs& a;
+  const diffab_dims* const d;
+  const TrainTape& tp;
+  const Geometry geo;
+  const BackwardPlan plan;
+  const BwdWorkspace ws;
+  // d pair_ctx in ONE pass behind the layer loop (launch_pair_de_layers) instead of a read-modify-write of the whole gradient per layer:
+  // g and the o_e columns of d feat of every layer are kept for it
+  const bool defer_de;
+  const hipStream_t st;
+  SideRun side;
+  float *dcur, *dnxt;  // d x: of the current step's output, of its input
+  const int rows, NP, F, D, H, DS, PQ, PV, C;
+  explicit BwdRun(const BackwardArgs& args)
+      : a(args), d(args.d), tp(args.tp), geo(d), plan(plan_backward(d)), ws(carve_bwd_workspace(d, plan, args.ws)),
+        defer_de(plan.de_slots && args.d_pair_ctx != nullptr && args.root != BWD_LAYER), st(args.st), side(args.st), dcur(ws.dxa),
+        dnxt(ws.dxb), rows(geo.rows), NP(geo.NP), F(geo.F), D(d->D), H(d->H), DS(d->DS), PQ(d->PQ), PV(d->PV), C(d->C) {}
+  int seed();
+  int heads();
+  int to_out(const Layer& L);
+  int attention(const Layer& L);
+  int attn_keys(const Layer& L, KeyPass keys, const float* G, const float* P);
+  int projections(const Layer& L);
+  int pair_de();
+  int embed_mlp();
+  int run();
+};
+
+// The root's gradients: of the heads' outputs (denoiser roots) or of the layer's output; the frame gradients start from zero
+int BwdRun::seed() {
+  const int64_t n = rows;
+  if (a.root == BWD_LOSSES) {
+    hipLaunchKernelGGL(count_mask_kernel, dim3(1), dim3(1024), 0, st, a.gm, a.rm, n, ws.cnt);
     DIFFAB_LAUNCH_CHECK();
-    if (int rc = launch_losses_bwd(post_hat, true_post, eps_hat, true_eps, O0_hat, true_O0, O_t, tp.vbuf, gm, rm, cnt, upstream3, V,
-                                   static_cast<int64_t>(rows), d_logits, d_eps, d_v, st))
+    if (int rc = launch_losses_bwd(a.post_hat, a.true_post, a.eps_hat, a.true_eps, a.O0_hat, a.true_O0, a.rot, tp.vbuf, a.gm, a.rm, ws.cnt,
+                                   a.upstream3, d->V, n, ws.d_logits, ws.d_eps, ws.d_v, st))
       return rc;
-  } else if (mode == BWD_COTANGENTS) {
-    if (int rc = launch_heads_cotangent(post_hat, cot_post, cot_eps, cot_O0, O_t, tp.vbuf, V, static_cast<int64_t>(rows), d_logits, d_eps, d_v,
-                                        d_O_t, st))
+  } else if (a.root == BWD_COTANGENTS) {
+    if (int rc = launch_heads_cotangent(a.post_hat, a.cot_post, a.cot_eps, a.cot_O0, a.rot, tp.vbuf, d->V, n, ws.d_logits, ws.d_eps, ws.d_v,
+                                        a.d_rot, st))
       return rc;
   } else {
-    DIFFAB_HIP_CHECK(hipMemcpyAsync(dcur, layer_dy, sizeof(float) * rows * D, hipMemcpyDeviceToDevice, st));
+    DIFFAB_HIP_CHECK(hipMemcpyAsync(dcur, a.layer_dy, sizeof(float) * n * D, hipMemcpyDeviceToDevice, st));
   }
-  if (d_O_t && mode != BWD_COTANGENTS) DIFFAB_HIP_CHECK(hipMemsetAsync(d_O_t, 0, sizeof(float) * rows * 9, st));  // (the heads kernel wrote it above)
-  if (d_x_t) DIFFAB_HIP_CHECK(hipMemsetAsync(d_x_t, 0, sizeof(float) * rows * 3, st));
-  // ---- heads (Linear-ReLU-Linear-ReLU-Linear), gradients into cat3 accumulate over the three heads
-  const diffab_mlp3_weights* hw[3] = {&w->coord, &w->orient, &w->seq};
-  const diffab_mlp3_weights* hg[3] = {&g->coord, &g->orient, &g->seq};
-  const float* dy[3] = {d_eps, d_v, d_logits};
-  const int nout[3] = {3, 3, V};
-  for (int hd = 0; hd < 3 && mode != BWD_LAYER; ++hd) {
-    float *dt2 = dt2s[hd], *dt1 = dt1s[hd];
-    if (int rc = linear_bwd(dy[hd], nout[hd], tp.t2[hd], D, hw[hd]->w4, const_cast<float*>(hg[hd]->w4), const_cast<float*>(hg[hd]->b4), dt2,
-                            D, rows, nout[hd], D, false, st, &side)) return rc;
+  if (a.d_rot && a.root != BWD_COTANGENTS) DIFFAB_HIP_CHECK(hipMemsetAsync(a.d_rot, 0, sizeof(float) * n * 9, st));  // (the heads kernel wrote it above)
+  if (a.d_trans) DIFFAB_HIP_CHECK(hipMemsetAsync(a.d_trans, 0, sizeof(float) * n * 3, st));
+  return DIFFAB_OK;
+}
+
+// heads (Linear-ReLU-Linear-ReLU-Linear), gradients into cat3 accumulate over the three heads; dcur = d h = dcat3[:, :D]
+int BwdRun::heads() {
+  const diffab_mlp3_weights* hw[3] = {&a.w->coord, &a.w->orient, &a.w->seq};
+  const diffab_mlp3_weights* hg[3] = {&a.g->coord, &a.g->orient, &a.g->seq};
+  const float* dy[3] = {ws.d_eps, ws.d_v, ws.d_logits};
+  const int nout[3] = {3, 3, d->V};
+  for (int hd = 0; hd < 3; ++hd) {
+    float *dt2 = ws.dt2s[hd], *dt1 = ws.dt1s[hd];
+    if (int rc = linear_bwd(dy[hd], nout[hd], tp.t2[hd], D, hw[hd]->w4, mut(hg[hd]->w4), mut(hg[hd]->b4), dt2, D, rows, nout[hd], D, false, st,
+                            &side)) return rc;
     if (int rc = relu_mask(dt2, tp.t2[hd], static_cast<int64_t>(rows) * D, st)) return rc;
-    if (int rc = linear_bwd(dt2, D, tp.t1[hd], D, hw[hd]->w2, const_cast<float*>(hg[hd]->w2), const_cast<float*>(hg[hd]->b2), dt1, D, rows,
-                            D, D, false, st, &side)) return rc;
+    if (int rc = linear_bwd(dt2, D, tp.t1[hd], D, hw[hd]->w2, mut(hg[hd]->w2), mut(hg[hd]->b2), dt1, D, rows, D, D, false, st, &side)) return rc;
     if (int rc = relu_mask(dt1, tp.t1[hd], static_cast<int64_t>(rows) * D, st)) return rc;
-    if (int rc = linear_bwd(dt1, D, tp.cat3, D + 3, hw[hd]->w0, const_cast<float*>(hg[hd]->w0), const_cast<float*>(hg[hd]->b0), dcat3,
-                            D + 3, rows, D, D + 3, hd > 0, st, &side)) return rc;
+    if (int rc = linear_bwd(dt1, D, tp.cat3, D + 3, hw[hd]->w0, mut(hg[hd]->w0), mut(hg[hd]->b0), ws.dcat3, D + 3, rows, D, D + 3, hd > 0, st,
+                            &side)) return rc;
   }
-  // dh = dcat3[:, :D] (leading dimension D+3)
-  if (mode != BWD_LAYER)
-    DIFFAB_HIP_CHECK(hipMemcpy2DAsync(dcur, sizeof(float) * D, dcat3, sizeof(float) * (D + 3), sizeof(float) * D, rows,
-                                      hipMemcpyDeviceToDevice, st));
-  // ---- IPA layers, last to first
-  for (int l = d->NL - 1; l >= 0; --l) {
-    const diffab_ipa_layer_weights* lw = &w->layers[l];
-    const diffab_ipa_layer_weights* lg = &g->layers[l];
-    const float* proj = tp.ipa_ws[l];
-    const float* feat = tp.ipa_ws[l] + static_cast<size_t>(rows) * NP;
-    const float* xin = tp.x[l];
-    float* dproj = dprojs[l & 1];
-    side.before_write(dproj);  // the projection weight gradient of layer l + 2 (beside the chain) read this buffer
-    // to_out
-    if (planes && (reinterpret_cast<uintptr_t>(dcur) & 15) == 0) {  // d feat = d y W_out on the x-stationary kernel (fp16 x 3)
-      if (int rc = linear_bwd(dcur, D, feat, F, lw->w_out, const_cast<float*>(lg->w_out), const_cast<float*>(lg->b_out), nullptr, F, rows, D,
-                              F, false, st, &side)) return rc;
-      if (int rc = launch_xstat_h3(dcur, lw->w_out, 1, F, dfeat, F, rows, F, planes, st)) return rc;
-    } else if (int rc = linear_bwd(dcur, D, feat, F, lw->w_out, const_cast<float*>(lg->w_out), const_cast<float*>(lg->b_out), dfeat, F, rows,
-                                   D, F, false, st, &side)) {
-      return rc;
-    }
-    const size_t lds = attn_bwd_lds_bytes(d);
-    const int vec = (DS % 4 == 0 && C % 4 == 0 && (PQ * 3) % 4 == 0 && (PV * 3) % 4 == 0 && H % 4 == 0 &&
-                     (reinterpret_cast<uintptr_t>(pair_ctx) & 15) == 0 && (reinterpret_cast<uintptr_t>(lw->w_bias) & 15) == 0) ? 1 : 0;
-    DIFFAB_REQUIRE(attn_bwd_lds_ok(d), DIFFAB_ERR_UNSUPPORTED, "attention backward: H*K too large for LDS (%zu > %zu bytes)", lds,
-                   kAttnBwdLdsMax);
-    if (lds > 64 * 1024)
-      DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_rows_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
-    bool keys_done = false;  // the MFMA path below also does the key-side pass
-    int wb_rows = rows;       // rows of the d w_bias / d gamma partials (the MFMA path writes one per 32 query rows)
-    constexpr int RRm = 4;  // query rows per work-group of the multi-row kernel
-    const size_t slot = ((3 * static_cast<size_t>(H) * d->K + H * DS + H * PQ * 3 + H * PV * 3 + H + F) + 3) & ~static_cast<size_t>(3);
-    const size_t lds_mr = RRm * slot * sizeof(float);
-    if (vec && H <= 8 && d->K % RRm == 0 && lds_mr <= 160 * 1024) {
-      if (mfma_probs) {
-        // MFMA path: probabilities and squared distances by the forward's kernels, the key/value part of dA as a batched GEMM; the
-        // row pass keeps what needs the pair row (do_e . e, softmax backward, d e, d w_bias, d gamma) and hands g to two more GEMMs
-        const size_t lds_km = static_cast<size_t>(d->K) * KM_LD * sizeof(float);
-        const dim3 grid_km(d->B * H * (d->K / 64));
-        const int64_t ndog = static_cast<int64_t>(rows) * H * PV;
-        hipLaunchKernelGGL(ipa_dog_kernel, dim3(static_cast<unsigned>((ndog + 255) / 256)), dim3(256), 0, st, feat, dfeat, O_t, H, C, DS, PV,
-                           static_cast<int64_t>(rows), dogbuf);
-        DIFFAB_LAUNCH_CHECK();
-        if (tp.sp[l] != nullptr) {  // saved by the taped forward
-          Pn = tp.sp[l];
-          D2g = tp.d2[l];
-        } else if (int rc = launch_attention_probs(d, proj, pair_ctx, lw->w_bias, lw->gamma, Pn, D2g, st)) {
-          return rc;
-        }
-        float* Gl = defer_de ? g_keep + static_cast<size_t>(l) * HKK : dAkv;  // d A_kv, then g, of this layer
-        hipLaunchKernelGGL(ipa_attn_bwd_dakv_mfma_kernel, grid_km, dim3(256), lds_km, st, proj, dfeat, dogbuf, Gl, d->K);
-        DIFFAB_LAUNCH_CHECK();
-        // Gl holds g afterwards.  d pair_ctx: accumulated by the same kernel (a read-modify-write of the whole gradient per layer), or -
-        // defer_de - left to ONE pass behind the layer loop, for which this layer's g (Gl is its own slot) and d o_e are kept
-        if (int rc = launch_pair_stream_bwd(d, pair_ctx, Pn, Gl, D2g, dfeat, wb_part, lw->w_bias, defer_de ? nullptr : d_pair_ctx, st)) return rc;
-        if (defer_de)
-          DIFFAB_HIP_CHECK(hipMemcpy2DAsync(doe_keep + static_cast<size_t>(l) * rows * H * C, sizeof(float) * H * C, dfeat + H * DS,
-                                            sizeof(float) * F, sizeof(float) * H * C, rows, hipMemcpyDeviceToDevice, st));
-        keys_done = true;
-        DIFFAB_REQUIRE(rows % 32 == 0, DIFFAB_ERR_UNSUPPORTED, "attention backward (MFMA path): B K = %d must be a multiple of 32", rows);
-        wb_rows = rows / 32;  // one partial row per 32 query rows (launch_pair_stream_bwd)
-        // key side straight from the [b][h][i][j] images (g in dAkv, P in Pn): no transposed copies, no VALU row pass at all
-        if (d->K == 128) {  // bf16 matrix cores: d k and d v (transposed products), d q
-          hipLaunchKernelGGL(ipa_attn_bwd_keys_tn_b6_kernel, dim3(d->B * H * 2), dim3(256), 0, st, proj, lw->gamma, dfeat, Gl, Pn, dogbuf,
-                             dproj, d->B);
-          hipLaunchKernelGGL(ipa_attn_bwd_keys_nn_b6_kernel, dim3(d->B * H), dim3(256), 0, st, proj, lw->gamma, Gl, dproj, d->B);
-        } else {
-        hipLaunchKernelGGL((ipa_attn_bwd_keys_mfma_kernel<0, false>), grid_km, dim3(256), lds_km, st, proj, lw->gamma, dfeat, Gl, dogbuf,
-                           dproj, d->K);
-        hipLaunchKernelGGL((ipa_attn_bwd_keys_mfma_kernel<1, false>), grid_km, dim3(256), lds_km, st, proj, lw->gamma, dfeat, Pn, dogbuf,
-                           dproj, d->K);
-        hipLaunchKernelGGL(ipa_attn_bwd_keys_mfma_kernel<2>, grid_km, dim3(256), lds_km, st, proj, lw->gamma, dfeat, Gl, dogbuf, dproj, d->K);
-        }
-      } else {
-        DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_rows_mr_kernel<RRm, 0>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_mr)));
-        hipLaunchKernelGGL((ipa_attn_bwd_rows_mr_kernel<RRm, 0>), dim3(rows / RRm), dim3(512), lds_mr, st, proj, pair_ctx, O_t,
-                           lw->w_bias, lw->gamma, feat, dfeat, dproj, d_pair_ctx, At, Gt, dogbuf, wb_part, d->K, C, H, DS, PQ, PV, nullptr,
-                           nullptr, nullptr);
-      }
-    } else
-    {
-      hipLaunchKernelGGL(ipa_attn_bwd_rows_kernel, dim3(rows), dim3(256), lds, st, proj, pair_ctx, O_t, lw->w_bias, lw->gamma, feat, dfeat,
-                         dproj, d_pair_ctx, const_cast<float*>(lg->w_bias), const_cast<float*>(lg->gamma), At, Gt, dogbuf, wb_part, d->K, C, H,
-                         DS, PQ, PV, vec);
-    }
-    DIFFAB_LAUNCH_CHECK();
-    // d w_bias[h][c] += sum_rows partial, d gamma[h] += sum_rows partial (one column sum over the [rows][H*C + H] partials)
-    if (keys_done && C > 0) {  // both sums in ONE launch (per-work-group partial rows -> two destinations; two colsum launches of 12.5 us before)
-      PartsSegs sg{};
-      sg.nseg = 2;
-      sg.off[0] = 0; sg.n[0] = H * C; sg.cols[0] = H * C; sg.ld[0] = H * C; sg.out[0] = const_cast<float*>(lg->w_bias);
-      sg.off[1] = H * C; sg.n[1] = H; sg.cols[1] = H; sg.ld[1] = H; sg.out[1] = const_cast<float*>(lg->gamma);
-      if (int rc = launch_parts_reduce(wb_part, wb_rows, H * C + H, sg, st)) return rc;
-    } else {
-      if (C > 0)  // (use_pair_bias = False: no pair bias, no d w_bias)
-        if (int rc = colsum(wb_part, H * C + H, wb_rows, H * C, const_cast<float*>(lg->w_bias), st)) return rc;
-      if (int rc = colsum(wb_part + H * C, H * C + H, wb_rows, H, const_cast<float*>(lg->gamma), st)) return rc;
-    }
-    const size_t lds2 = 2 * static_cast<size_t>(H) * d->K * sizeof(float);
-    constexpr int JJm = 4;  // keys per work-group of the multi-key kernel
-    if (keys_done) {
-    } else if (fast_path_supported(d) && d->K % 64 == 0 && static_cast<size_t>(d->K) * KM_LD * sizeof(float) <= 64 * 1024) {
-      const size_t lds_km = static_cast<size_t>(d->K) * KM_LD * sizeof(float);
-      const dim3 grid_km(d->B * H * (d->K / 64));
-      hipLaunchKernelGGL(ipa_attn_bwd_keys_mfma_kernel<0>, grid_km, dim3(256), lds_km, st, proj, lw->gamma, dfeat, Gt, dogbuf, dproj, d->K);
-      hipLaunchKernelGGL(ipa_attn_bwd_keys_mfma_kernel<1>, grid_km, dim3(256), lds_km, st, proj, lw->gamma, dfeat, At, dogbuf, dproj, d->K);
-    } else if (d->K % JJm == 0 && JJm * lds2 <= 64 * 1024) {
-      hipLaunchKernelGGL((ipa_attn_bwd_keys_mr_kernel<JJm>), dim3(rows / JJm), dim3(256), JJm * lds2, st, proj, lw->gamma, dfeat, At, Gt,
-                         dogbuf, dproj, d->K, C, H, DS, PQ, PV);
-    } else {  // (lds2 < lds: within the limit checked above; past 64 KiB it needs the attribute, as the row kernel does)
+  DIFFAB_HIP_CHECK(hipMemcpy2DAsync(dcur, sizeof(float) * D, ws.dcat3, sizeof(float) * (D + 3), sizeof(float) * D, rows,
+                                    hipMemcpyDeviceToDevice, st));
+  return DIFFAB_OK;
+}
+
+// to_out: d feat = d y W_out, d W_out += d y^T feat
+int BwdRun::to_out(const Layer& L) {
+  const bool xstat = ws.planes && (reinterpret_cast<uintptr_t>(dcur) & 15) == 0;  // d feat on the x-stationary kernel (fp16 x 3)
+  if (int rc = linear_bwd(dcur, D, L.feat, F, L.w->w_out, mut(L.g->w_out), mut(L.g->b_out), xstat ? nullptr : ws.dfeat, F, rows, D, F, false, st,
+                          &side)) return rc;
+  return xstat ? launch_xstat_h3(dcur, L.w->w_out, 1, F, ws.dfeat, F, rows, F, ws.planes, st) : DIFFAB_OK;
+}
+
+// G, P: g and the probabilities - [b][h][i][j] for kMfma3 / kB6, transposed for the others
+int BwdRun::attn_keys(const Layer& L, KeyPass keys, const float* G, const float* P) {
+  const float *dfeat = ws.dfeat, *dogbuf = ws.dogbuf, *gamma = L.w->gamma;
+  const size_t lds_km = attn_bwd_lds_km(d), lds2 = attn_bwd_lds_keys(d);
+  const dim3 grid_km(d->B * H * (d->K / 64));
+  switch (keys) {
+    case KeyPass::kB6:  // bf16 matrix cores: d k and d v (transposed products), d q
+      hipLaunchKernelGGL(ipa_attn_bwd_keys_tn_b6_kernel, dim3(d->B * H * 2), dim3(256), 0, st, L.proj, gamma, dfeat, G, P, dogbuf, L.dproj, d->B);
+      hipLaunchKernelGGL(ipa_attn_bwd_keys_nn_b6_kernel, dim3(d->B * H), dim3(256), 0, st, L.proj, gamma, G, L.dproj, d->B);
+      break;
+    case KeyPass::kMfma3:  // no transposed copies, no VALU row pass at all
+      hipLaunchKernelGGL((ipa_attn_bwd_keys_mfma_kernel<0, false>), grid_km, dim3(256), lds_km, st, L.proj, gamma, dfeat, G, dogbuf, L.dproj, d->K);
+      hipLaunchKernelGGL((ipa_attn_bwd_keys_mfma_kernel<1, false>), grid_km, dim3(256), lds_km, st, L.proj, gamma, dfeat, P, dogbuf, L.dproj, d->K);
+      hipLaunchKernelGGL(ipa_attn_bwd_keys_mfma_kernel<2>, grid_km, dim3(256), lds_km, st, L.proj, gamma, dfeat, G, dogbuf, L.dproj, d->K);
+      break;
+    case KeyPass::kMfma2:
+      hipLaunchKernelGGL(ipa_attn_bwd_keys_mfma_kernel<0>, grid_km, dim3(256), lds_km, st, L.proj, gamma, dfeat, G, dogbuf, L.dproj, d->K);
+      hipLaunchKernelGGL(ipa_attn_bwd_keys_mfma_kernel<1>, grid_km, dim3(256), lds_km, st, L.proj, gamma, dfeat, P, dogbuf, L.dproj, d->K);
+      break;
+    case KeyPass::kKeys4:
+      hipLaunchKernelGGL((ipa_attn_bwd_keys_mr_kernel<kKeysMr>), dim3(rows / kKeysMr), dim3(256), kKeysMr * lds2, st, L.proj, gamma, dfeat, P, G,
+                         dogbuf, L.dproj, d->K, C, H, DS, PQ, PV);
+      break;
+    case KeyPass::kOneKey:  // (lds2 < the row pass's: within the limit checked there; past 64 KiB it needs the attribute, as the row kernel does)
       if (lds2 > 64 * 1024)
         DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_keys_kernel),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds2)));
-      hipLaunchKernelGGL(ipa_attn_bwd_keys_kernel, dim3(rows), dim3(256), lds2, st, proj, lw->gamma, dfeat, At, Gt, dogbuf, dproj, d->K, C, H,
-                         DS, PQ, PV);
-    }
-    DIFFAB_LAUNCH_CHECK();
-    if (d_x_t || d_O_t) {  // frame gradients of this layer, from the GLOBAL point gradients (before points_bwd_kernel rewrites dproj)
-      if (int rc = launch_ipa_frames_bwd(proj, dproj, NP, 3 * H * DS, 2 * H * PQ + H * PV, feat, dfeat, F, H * DS + H * C,
-                                         H * DS + H * C + H * PV * 3, H * PV, O_t, x_t, d_O_t, d_x_t, rows, st))
-        return rc;
-    }
-    // global-point gradients -> local-point gradients (three point blocks)
-    {  // the three point blocks (q, k, v) are adjacent columns of dproj: one launch over all of a row's points
-      const int npts = 2 * H * PQ + H * PV;
-      const int64_t n = static_cast<int64_t>(rows) * npts;
-      hipLaunchKernelGGL(points_bwd_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, dproj, NP, 3 * H * DS, npts, O_t,
-                         static_cast<int64_t>(rows));
-      DIFFAB_LAUNCH_CHECK();
-    }
-    // projections: dx = sum_seg dproj_seg W_seg, dW_seg += dproj_seg^T x_in
-    const float* Ws[6] = {lw->wq_s, lw->wk_s, lw->wv_s, lw->wq_p, lw->wk_p, lw->wv_p};
-    float* dWs[6] = {const_cast<float*>(lg->wq_s), const_cast<float*>(lg->wk_s), const_cast<float*>(lg->wv_s),
-                     const_cast<float*>(lg->wq_p), const_cast<float*>(lg->wk_p), const_cast<float*>(lg->wv_p)};
-    const int Ns[6] = {H * DS, H * DS, H * DS, H * PQ * 3, H * PQ * 3, H * PV * 3};
-    bool segs_ok = D % 4 == 0 && NP % 4 == 0 && D % 64 == 0 && (reinterpret_cast<uintptr_t>(xin) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(dproj) & 15) == 0 && (reinterpret_cast<uintptr_t>(dnxt) & 15) == 0;
-    GemmSegs gw{}, gd{};
-    gw.nseg = gd.nseg = 6;
-    int col = 0;
-    for (int q = 0; q < 6; ++q) {
-      col += Ns[q];
-      gw.p[q] = const_cast<float*>(Ws[q]);
-      gd.p[q] = dWs[q];
-      gw.n_end[q] = gd.n_end[q] = col;
-      segs_ok = segs_ok && Ns[q] % 64 == 0 && (reinterpret_cast<uintptr_t>(Ws[q]) & 15) == 0;
-    }
-    side.before_write(dnxt);  // (to_out's weight gradient of layer l + 1 read it as its d y)
-    if (segs_ok) {  // the six projections as ONE weight-gradient product and ONE input-gradient product over the 1344-wide dproj
-      if (int rc = gemm_tn(dproj, NP, xin, D, nullptr, D, rows, NP, D, side.begin(), &gd)) return rc;
-      side.reads(dproj);
-      if (planes && NP % 32 == 0 && rowgemm128_b6_ok(dproj, NP, dnxt, D, rows, NP)) {
-        // dx = dproj [W_q_s; ...; W_v_p] as Y = X W'^T with W'[n][k] = W_seg[k - k0][n]: six strided splits into one set of planes
-        if (int rc = launch_wsplit128_segs(Ws, gw.n_end, 6, planes, st)) return rc;
-        if (int rc = launch_rowgemm128_b6p(dproj, NP, planes, nullptr, nullptr, 0, dnxt, D, rows, NP, false, st)) return rc;
-      } else if (int rc = gemm_nn(dproj, NP, nullptr, D, dnxt, D, rows, D, NP, false, st, &gw)) {
-        return rc;
-      }
-    } else {
-      col = 0;
-      for (int q = 0; q < 6; ++q) {
-        if (int rc = linear_bwd(dproj + col, NP, xin, D, Ws[q], dWs[q], nullptr, dnxt, D, rows, Ns[q], D, q > 0, st)) return rc;  // (generic dims: on the chain)
-        col += Ns[q];
-      }
-    }
-    float* tmp = dcur; dcur = dnxt; dnxt = tmp;
+      hipLaunchKernelGGL(ipa_attn_bwd_keys_kernel, dim3(rows), dim3(256), lds2, st, L.proj, gamma, dfeat, P, G, dogbuf, L.dproj, d->K, C, H, DS,
+                         PQ, PV);
+      break;
   }
-  if (defer_de) {  // d pair_ctx += the pair-bias and o_e terms of all layers, one pass (attention_split.hip)
-    const float* Ps[kDeLayersMax];
-    const float* Gs[kDeLayersMax];
-    const float* Es[kDeLayersMax];
-    const float* Wbs[kDeLayersMax];
-    for (int l = 0; l < d->NL; ++l) {
-      Ps[l] = tp.sp[l];
-      Gs[l] = g_keep + static_cast<size_t>(l) * HKK;
-      Es[l] = doe_keep + static_cast<size_t>(l) * rows * H * C;
-      Wbs[l] = w->layers[l].w_bias;
-    }
-    if (int rc = launch_pair_de_layers(d, d->NL, Ps, Gs, Es, Wbs, d_pair_ctx, st)) return rc;
-  }
-  if (mode == BWD_LAYER) {
-    DIFFAB_HIP_CHECK(hipMemcpyAsync(layer_dx, dcur, sizeof(float) * rows * D, hipMemcpyDeviceToDevice, st));
-    return DIFFAB_OK;
-  }
-  // ---- to_res_emb (Linear-ReLU-Linear) and the sequence embedding
-  side.before_write(dnxt);
-  if (int rc = linear_bwd(dcur, D, tp.h1, D, w->res_w2, const_cast<float*>(g->res_w2), const_cast<float*>(g->res_b2), dnxt, D, rows, D, D,
-                          false, st, &side)) return rc;
-  if (int rc = relu_mask(dnxt, tp.h1, static_cast<int64_t>(rows) * D, st)) return rc;
-  if (int rc = linear_bwd(dnxt, D, tp.cat2, 2 * D, w->res_w0, const_cast<float*>(g->res_w0), const_cast<float*>(g->res_b0), dcat2, 2 * D,
-                          rows, D, 2 * D, false, st, &side)) return rc;
-  hipLaunchKernelGGL(embed_bwd_kernel, dim3(rows), dim3(128), 0, st, dcat2, seq_t, D, static_cast<int64_t>(rows), d_res_ctx,
-                     const_cast<float*>(g->seq_emb));
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
 
-int train_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_denoiser_weights* g, const TrainTape& tp,
-                   const int64_t* seq_t, const float* x_t, const float* O_t, const float* pair_ctx, const float* eps_hat,
-                   const float* O0_hat, const float* post_hat, const float* true_post, const float* true_eps, const float* true_O0,
-                   const uint8_t* gm, const uint8_t* rm, const float* upstream3, float* d_res_ctx, float* d_pair_ctx, float* ws,
-                   hipStream_t st) {
-  return run_backward(BWD_LOSSES, d, w, g, tp, seq_t, x_t, O_t, pair_ctx, eps_hat, O0_hat, post_hat, true_post, true_eps, true_O0, gm, rm,
-                      upstream3, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_ctx, d_pair_ctx, ws, st);
+// attention: d feat -> d proj (points as local-point gradients), d w_bias, d gamma, d pair_ctx, the frame gradients
+int BwdRun::attention(const Layer& L) {
+  const size_t lds = attn_bwd_lds_bytes(d);
+  const int vec = (DS % 4 == 0 && C % 4 == 0 && (PQ * 3) % 4 == 0 && (PV * 3) % 4 == 0 && H % 4 == 0 &&
+                   (reinterpret_cast<uintptr_t>(a.pair_ctx) & 15) == 0 && (reinterpret_cast<uintptr_t>(L.w->w_bias) & 15) == 0) ? 1 : 0;
+  DIFFAB_REQUIRE(attn_bwd_lds_ok(d), DIFFAB_ERR_UNSUPPORTED, "attention backward: H*K too large for LDS (%zu > %zu bytes)", lds,
+                 kAttnBwdLdsMax);
+  if (lds > 64 * 1024)
+    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_rows_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
+  const AttnBwdKernels k = choose_attn_bwd(d, plan, vec != 0);
+  float* dfeat = ws.dfeat;
+  if (k.rows == RowPass::kMfma) {
+    // MFMA path: probabilities and squared distances from the tape, the key/value part of dA as a batched GEMM; the row pass keeps
+    // what needs the pair row (do_e . e, softmax backward, d e, d w_bias, d gamma) and hands g to the key side's GEMMs
+    const int64_t ndog = static_cast<int64_t>(rows) * H * PV;
+    hipLaunchKernelGGL(ipa_dog_kernel, dim3(static_cast<unsigned>((ndog + 255) / 256)), dim3(256), 0, st, L.feat, dfeat, a.rot, H, C, DS, PV,
+                       static_cast<int64_t>(rows), ws.dogbuf);
+    DIFFAB_LAUNCH_CHECK();
+    const float* P = tp.sp[L.l];
+    float* G = defer_de ? ws.g_keep + L.l * geo.HKK : ws.dAkv;  // d A_kv, then g, of this layer
+    hipLaunchKernelGGL(ipa_attn_bwd_dakv_mfma_kernel, dim3(d->B * H * (d->K / 64)), dim3(256), attn_bwd_lds_km(d), st, L.proj, dfeat, ws.dogbuf,
+                       G, d->K);
+    DIFFAB_LAUNCH_CHECK();
+    // G holds g afterwards.  d pair_ctx: accumulated by the same kernel (a read-modify-write of the whole gradient per layer), or -
+    // defer_de - left to ONE pass behind the layer loop, for which this layer's g (G is its own slot) and d o_e are kept
+    if (int rc = launch_pair_stream_bwd(d, a.pair_ctx, P, G, tp.d2[L.l], dfeat, ws.wb_part, L.w->w_bias, defer_de ? nullptr : a.d_pair_ctx, st))
+      return rc;
+    if (defer_de)
+      DIFFAB_HIP_CHECK(hipMemcpy2DAsync(ws.doe_keep + L.l * geo.per_row(H * C), sizeof(float) * H * C, dfeat + H * DS, sizeof(float) * F,
+                                        sizeof(float) * H * C, rows, hipMemcpyDeviceToDevice, st));
+    if (int rc = attn_keys(L, k.keys, G, P)) return rc;
+    // d w_bias and d gamma from one partial row per 32 query rows (launch_pair_stream_bwd; K = 64 / 128, so 32 divides rows), both sums
+    // in ONE launch (two colsum launches of 12.5 us before)
+    PartsSegs sg{};
+    sg.nseg = 2;
+    sg.off[0] = 0; sg.n[0] = H * C; sg.cols[0] = H * C; sg.ld[0] = H * C; sg.out[0] = mut(L.g->w_bias);
+    sg.off[1] = H * C; sg.n[1] = H; sg.cols[1] = H; sg.ld[1] = H; sg.out[1] = mut(L.g->gamma);
+    if (int rc = launch_parts_reduce(ws.wb_part, rows / 32, H * C + H, sg, st)) return rc;
+  } else {
+    if (k.rows == RowPass::kRows4) {
+      const size_t lds_mr = attn_bwd_lds_mr(d);
+      DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_attn_bwd_rows_mr_kernel<kRowsMr, 0>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_mr)));
+      hipLaunchKernelGGL((ipa_attn_bwd_rows_mr_kernel<kRowsMr, 0>), dim3(rows / kRowsMr), dim3(512), lds_mr, st, L.proj, a.pair_ctx, a.rot,
+                         L.w->w_bias, L.w->gamma, L.feat, dfeat, L.dproj, a.d_pair_ctx, ws.At, ws.Gt, ws.dogbuf, ws.wb_part, d->K, C, H, DS, PQ,
+                         PV, nullptr, nullptr, nullptr);
+    } else {
+      hipLaunchKernelGGL(ipa_attn_bwd_rows_kernel, dim3(rows), dim3(256), lds, st, L.proj, a.pair_ctx, a.rot, L.w->w_bias, L.w->gamma, L.feat,
+                         dfeat, L.dproj, a.d_pair_ctx, mut(L.g->w_bias), mut(L.g->gamma), ws.At, ws.Gt, ws.dogbuf, ws.wb_part, d->K, C, H, DS, PQ,
+                         PV, vec);
+    }
+    DIFFAB_LAUNCH_CHECK();
+    // d w_bias[h][c] += sum_rows partial, d gamma[h] += sum_rows partial (one column sum over the [rows][H*C + H] partials)
+    if (C > 0)  // (use_pair_bias = False: no pair bias, no d w_bias)
+      if (int rc = colsum(ws.wb_part, H * C + H, rows, H * C, mut(L.g->w_bias), st)) return rc;
+    if (int rc = colsum(ws.wb_part + H * C, H * C + H, rows, H, mut(L.g->gamma), st)) return rc;
+    if (int rc = attn_keys(L, k.keys, ws.Gt, ws.At)) return rc;
+  }
+  if (a.d_trans || a.d_rot) {  // frame gradients of this layer, from the GLOBAL point gradients (before points_bwd_kernel rewrites dproj)
+    if (int rc = launch_ipa_frames_bwd(L.proj, L.dproj, NP, 3 * H * DS, 2 * H * PQ + H * PV, L.feat, dfeat, F, H * DS + H * C,
+                                       H * DS + H * C + H * PV * 3, H * PV, a.rot, a.trans, a.d_rot, a.d_trans, rows, st))
+      return rc;
+  }
+  // global-point gradients -> local-point gradients: the three point blocks (q, k, v) are adjacent columns of dproj, one launch over
+  // all of a row's points
+  const int npts = 2 * H * PQ + H * PV;
+  const int64_t n = static_cast<int64_t>(rows) * npts;
+  hipLaunchKernelGGL(points_bwd_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, st, L.dproj, NP, 3 * H * DS, npts, a.rot,
+                     static_cast<int64_t>(rows));
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
 }
 
-// Denoiser.forward backward from arbitrary cotangents of (eps-hat, O0-hat, posterior); null cotangents are zeros
-int denoise_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_denoiser_weights* g, const TrainTape& tp,
-                     const int64_t* seq_t, const float* x_t, const float* O_t, const float* pair_ctx, const float* post_hat,
-                     const float* cot_eps, const float* cot_O0, const float* cot_post, float* d_res_ctx, float* d_pair_ctx, float* ws,
-                     hipStream_t st, float* d_x_t, float* d_O_t) {
-  return run_backward(BWD_COTANGENTS, d, w, g, tp, seq_t, x_t, O_t, pair_ctx, nullptr, nullptr, post_hat, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, cot_eps, cot_O0, cot_post, nullptr, nullptr, d_res_ctx, d_pair_ctx, ws, st, d_x_t, d_O_t);
+// projections: dx = sum_seg dproj_seg W_seg into dnxt, dW_seg += dproj_seg^T x_in
+int BwdRun::projections(const Layer& L) {
+  float* dproj = L.dproj;
+  const float* Ws[6] = {L.w->wq_s, L.w->wk_s, L.w->wv_s, L.w->wq_p, L.w->wk_p, L.w->wv_p};
+  float* dWs[6] = {mut(L.g->wq_s), mut(L.g->wk_s), mut(L.g->wv_s), mut(L.g->wq_p), mut(L.g->wk_p), mut(L.g->wv_p)};
+  const int Ns[6] = {H * DS, H * DS, H * DS, H * PQ * 3, H * PQ * 3, H * PV * 3};
+  bool segs_ok = D % 4 == 0 && NP % 4 == 0 && D % 64 == 0 && (reinterpret_cast<uintptr_t>(L.xin) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(dproj) & 15) == 0 && (reinterpret_cast<uintptr_t>(dnxt) & 15) == 0;
+  GemmSegs gw{}, gd{};
+  gw.nseg = gd.nseg = 6;
+  int col = 0;
+  for (int q = 0; q < 6; ++q) {
+    col += Ns[q];
+    gw.p[q] = mut(Ws[q]);
+    gd.p[q] = dWs[q];
+    gw.n_end[q] = gd.n_end[q] = col;
+    segs_ok = segs_ok && Ns[q] % 64 == 0 && (reinterpret_cast<uintptr_t>(Ws[q]) & 15) == 0;
+  }
+  side.before_write(dnxt);  // (to_out's weight gradient of layer l + 1 read it as its d y)
+  if (segs_ok) {  // the six projections as ONE weight-gradient product and ONE input-gradient product over the 1344-wide dproj
+    if (int rc = gemm_tn(dproj, NP, L.xin, D, nullptr, D, rows, NP, D, side.begin(), &gd)) return rc;
+    side.reads(dproj);
+    if (ws.planes && NP % 32 == 0 && rowgemm128_b6_ok(dproj, NP, dnxt, D, rows, NP)) {
+      // dx = dproj [W_q_s; ...; W_v_p] as Y = X W'^T with W'[n][k] = W_seg[k - k0][n]: six strided splits into one set of planes
+      if (int rc = launch_wsplit128_segs(Ws, gw.n_end, 6, ws.planes, st)) return rc;
+      return launch_rowgemm128_b6p(dproj, NP, ws.planes, nullptr, nullptr, 0, dnxt, D, rows, NP, false, st);
+    }
+    return gemm_nn(dproj, NP, nullptr, D, dnxt, D, rows, D, NP, false, st, &gw);
+  }
+  col = 0;
+  for (int q = 0; q < 6; ++q) {
+    if (int rc = linear_bwd(dproj + col, NP, L.xin, D, Ws[q], dWs[q], nullptr, dnxt, D, rows, Ns[q], D, q > 0, st)) return rc;  // (generic dims: on the chain)
+    col += Ns[q];
+  }
+  return DIFFAB_OK;
 }
 
-// One IPA layer backward: tp is the one-layer tape of the taped layer forward (x[0] = the layer input), dy -> dx, d pair_ctx += ..
-int ipa_layer_bwd(const diffab_dims* d1, const diffab_ipa_layer_weights* lw, const diffab_ipa_layer_weights* lg, const TrainTape& tp,
-                  const float* R, const float* t, const float* pair_ctx, const float* dy, float* dx, float* d_pair_ctx, float* ws,
-                  hipStream_t st, float* d_R, float* d_t) {
-  diffab_denoiser_weights w{}, g{};
-  w.layers = lw;
-  g.layers = lg;
-  return run_backward(BWD_LAYER, d1, &w, &g, tp, nullptr, t, R, pair_ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      nullptr, nullptr, nullptr, nullptr, nullptr, dy, dx, nullptr, d_pair_ctx, ws, st, d_t, d_R);
+// d pair_ctx += the pair-bias and o_e terms of all layers, one pass (attention_split.hip)
+int BwdRun::pair_de() {
+  const float *Ps[kDeLayersMax], *Gs[kDeLayersMax], *Es[kDeLayersMax], *Wbs[kDeLayersMax];
+  for (int l = 0; l < d->NL; ++l) {
+    Ps[l] = tp.sp[l];
+    Gs[l] = ws.g_keep + l * geo.HKK;
+    Es[l] = ws.doe_keep + l * geo.per_row(H * C);
+    Wbs[l] = a.w->layers[l].w_bias;
+  }
+  return launch_pair_de_layers(d, d->NL, Ps, Gs, Es, Wbs, a.d_pair_ctx, st);
 }
+
+// to_res_emb (Linear-ReLU-Linear) and the sequence embedding
+int BwdRun::embed_mlp() {
+  side.before_write(dnxt);
+  if (int rc = linear_bwd(dcur, D, tp.h1, D, a.w->res_w2, mut(a.g->res_w2), mut(a.g->res_b2), dnxt, D, rows, D, D, false, st, &side)) return rc;
+  if (int rc = relu_mask(dnxt, tp.h1, static_cast<int64_t>(rows) * D, st)) return rc;
+  if (int rc = linear_bwd(dnxt, D, tp.cat2, 2 * D, a.w->res_w0, mut(a.g->res_w0), mut(a.g->res_b0), ws.dcat2, 2 * D, rows, D, 2 * D, false, st,
+                          &side)) return rc;
+  hipLaunchKernelGGL(embed_bwd_kernel, dim3(rows), dim3(128), 0, st, ws.dcat2, a.seq_t, D, static_cast<int64_t>(rows), a.d_res_ctx,
+                     mut(a.g->seq_emb));
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
+
+int BwdRun::run() {
+  if (int rc = seed()) return rc;
+  if (a.root != BWD_LAYER)
+    if (int rc = heads()) return rc;
+  for (int l = d->NL - 1; l >= 0; --l) {  // IPA layers, last to first
+    const float* slot = tp.ipa_ws[l];     // proj | feat
+    const Layer L{l, &a.w->layers[l], &a.g->layers[l], slot, slot + geo.per_row(NP), tp.x[l], ws.dprojs[l & 1]};
+    side.before_write(L.dproj);  // the projection weight gradient of layer l + 2 (beside the chain) read this buffer
+    if (int rc = to_out(L)) return rc;
+    if (int rc = attention(L)) return rc;
+    if (int rc = projections(L)) return rc;
+    float* tmp = dcur; dcur = dnxt; dnxt = tmp;
+  }
+  if (defer_de)
+    if (int rc = pair_de()) return rc;
+  if (a.root == BWD_LAYER) {
+    DIFFAB_HIP_CHECK(hipMemcpyAsync(a.layer_dx, dcur, sizeof(float) * geo.per_row(D), hipMemcpyDeviceToDevice, st));
+    return DIFFAB_OK;
+  }
+  return embed_mlp();
+}
+int run_backward(const BackwardArgs& a) { return BwdRun(a).run(); }
 
 }  // namespace diffab

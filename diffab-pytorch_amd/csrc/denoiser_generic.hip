@@ -212,18 +212,15 @@ __global__ __launch_bounds__(256) void ipa_attn_generic_kernel(const float* __re
 }
 
 size_t ipa_generic_workspace_floats(const diffab_dims* d) {
-  const size_t rows = static_cast<size_t>(d->B) * d->K;
-  const size_t NP = 3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3;
-  const size_t F = d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV;
-  return rows * (NP + F) + 128;
+  const Geometry geo(d);
+  return geo.per_row(geo.NP + geo.F) + 128;
 }
 
 int ipa_layer_generic(const diffab_dims* d, const diffab_ipa_layer_weights* w, const float* x, const float* e, const float* R, const float* t,
                       float* y, float* ws, hipStream_t st, const int* ctx_of_row) {
-  const int rows = d->B * d->K;
+  const Geometry geo(d);
+  const int rows = geo.rows, NP = geo.NP, F = geo.F;
   const int H = d->H, DS = d->DS, PQ = d->PQ, PV = d->PV, D = d->D, C = d->C;
-  const int NP = 3 * H * DS + 2 * H * PQ * 3 + H * PV * 3;
-  const int F = H * DS + H * C + H * PV * 3 + H * PV;
   float* proj = ws;
   float* feat = ws + static_cast<size_t>(rows) * NP;
   int col = 0;

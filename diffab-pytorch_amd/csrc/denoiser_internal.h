@@ -162,37 +162,72 @@ void timer_begin(hipStream_t st);
 void timer_end(hipStream_t st);
 bool kernel_timer_enabled();
 
-// denoiser_backward.hip: saved activations of one training forward (every buffer written by the forward kernels themselves)
+// Derived widths of a call's dims, host side (the kernels keep their own copies): rows = B K, NP = the columns of a projection row
+// [q_s | k_s | v_s | q_pts | k_pts | v_pts], F = the columns of a feature row [o_s | o_e | o_l | o_n], HKK = one [B][H][K][K] image
+struct Geometry {
+  int rows, NP, F;
+  size_t HKK;
+  explicit Geometry(const diffab_dims* d)
+      : rows(d->B * d->K), NP(3 * d->H * d->DS + 2 * d->H * d->PQ * 3 + d->H * d->PV * 3),
+        F(d->H * d->DS + d->H * d->C + d->H * d->PV * 3 + d->H * d->PV), HKK(static_cast<size_t>(d->B) * d->H * d->K * d->K) {}
+  size_t per_row(size_t n) const { return static_cast<size_t>(rows) * n; }  // floats of a [rows][n] buffer
+};
+
+// denoiser_backward.hip: what a taped forward and its backward do, decided once per call by plan_backward.  The tape layout, the
+// backward's workspace layout, the taped forwards (api.hip) and run_backward all read it.
 constexpr int kMaxLayers = 16;
+struct BackwardPlan {
+  bool fast;           // benchmark geometry (fast_path_supported): the taped layers run the MFMA kernels, the tape ends in their weight planes
+  bool probs_on_tape;  // ... and K = 64 / 128: the three-launch attention leaves P and d2 of every layer on the tape, the backward reads them
+  bool de_slots;       // ... and NL <= kDeLayersMax: g and d o_e of every layer have workspace slots - d pair_ctx can be one pass (C = 64, H = 8)
+  bool split_planes;   // D = 128: the input-gradient products of to_out and of the projections read the weights as split bf16 planes
+};
+BackwardPlan plan_backward(const diffab_dims* d);
+// saved activations of one training forward (every buffer written by the forward kernels themselves)
 struct TrainTape {
   float *cat2, *h1, *x[kMaxLayers + 1], *ipa_ws[kMaxLayers], *cat3, *t1[3], *t2[3], *vbuf, *logits;
   float* scratch;  // 1024 floats: partial sums of the loss reduction
   void* planes;    // ipa_layer_planes_bytes(): the current layer's split weights for the bf16x6 forward GEMMs (null off the MFMA path)
-  // per layer, benchmark geometry with K = 64 / 128 only (else null): the attention probabilities and the squared point distances
-  // [b][h][i][j], saved by the three-launch forward so that the backward does not recompute them
+  // per layer with BackwardPlan::probs_on_tape (else null): the attention probabilities and the squared point distances [b][h][i][j]
   float *sp[kMaxLayers], *d2[kMaxLayers];
+  size_t floats;   // of the whole tape
 };
-size_t train_tape_floats(const diffab_dims* d);
+// base == nullptr: null pointers and the size, as Carver does.  d->NL <= kMaxLayers (the entry points refuse more before they call)
 TrainTape carve_tape(const diffab_dims* d, float* base);
+inline size_t train_tape_floats(const diffab_dims* d) { return carve_tape(d, nullptr).floats; }
 // Dynamic LDS of the attention backward's row pass (ipa_attn_bwd_rows_kernel: 3 H K + the row's vectors, in bytes) and its limit.  The
 // one predicate of which dims the backward runs: run_backward refuses past it, and so do the taped forwards, before anything is launched.
 constexpr size_t kAttnBwdLdsMax = 160 * 1024;
 size_t attn_bwd_lds_bytes(const diffab_dims* d);
 inline bool attn_bwd_lds_ok(const diffab_dims* d) { return attn_bwd_lds_bytes(d) <= kAttnBwdLdsMax; }
 size_t train_bwd_workspace_floats(const diffab_dims* d);
-int train_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_denoiser_weights* g, const TrainTape& tp,
-                   const int64_t* seq_t, const float* x_t, const float* O_t, const float* pair_ctx, const float* eps_hat,
-                   const float* O0_hat, const float* post_hat, const float* true_post, const float* true_eps, const float* true_O0,
-                   const uint8_t* gm, const uint8_t* rm, const float* upstream3, float* d_res_ctx, float* d_pair_ctx, float* ws,
-                   hipStream_t st);
-// the same backward from arbitrary cotangents of the Denoiser outputs (null = zero), and one IPA layer's backward (one-layer tape)
-int denoise_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w, const diffab_denoiser_weights* g, const TrainTape& tp,
-                     const int64_t* seq_t, const float* x_t, const float* O_t, const float* pair_ctx, const float* post_hat,
-                     const float* cot_eps, const float* cot_O0, const float* cot_post, float* d_res_ctx, float* d_pair_ctx, float* ws,
-                     hipStream_t st, float* d_x_t = nullptr, float* d_O_t = nullptr);  // frame gradients (nullable)
-int ipa_layer_bwd(const diffab_dims* d1, const diffab_ipa_layer_weights* lw, const diffab_ipa_layer_weights* lg, const TrainTape& tp,
-                  const float* R, const float* t, const float* pair_ctx, const float* dy, float* dx, float* d_pair_ctx, float* ws,
-                  hipStream_t st, float* d_R = nullptr, float* d_t = nullptr);  // frame gradients (nullable)
+// One backward driver, three roots:
+//   BWD_LOSSES      the three masked losses of diffab_pytorch.py:856-880 with upstream gradients upstream3 (the training step)
+//   BWD_COTANGENTS  arbitrary cotangents of the Denoiser outputs (cot_eps, cot_O0, cot_post; null = zero): Denoiser.forward under autograd
+//   BWD_LAYER       one IPA layer from d y (layer_dy) to d x (layer_dx): InvariantPointAttentionLayer.forward under autograd; `w` / `g`
+//                   then carry only layers[0] and `tp` is a one-layer tape
+enum BwdRoot { BWD_LOSSES, BWD_COTANGENTS, BWD_LAYER };
+struct BackwardArgs {  // fields a root does not name stay null
+  BwdRoot root;
+  const diffab_dims* d;
+  const diffab_denoiser_weights *w, *g;  // weights; gradients (+=)
+  TrainTape tp;
+  float* ws;  // train_bwd_workspace_floats(d)
+  hipStream_t st;
+  // inputs of the forward.  The frames: x_t / O_t of the denoiser entries, t / R of the layer entry
+  const int64_t* seq_t;
+  const float *trans, *rot, *pair_ctx;
+  // BWD_LOSSES: the forward's outputs, the targets, the masks and the three upstream gradients
+  const float *eps_hat, *O0_hat, *true_post, *true_eps, *true_O0, *upstream3;
+  const uint8_t *gm, *rm;
+  const float* post_hat;                      // BWD_LOSSES, BWD_COTANGENTS
+  const float *cot_eps, *cot_O0, *cot_post;  // BWD_COTANGENTS (each nullable = zero)
+  const float* layer_dy;                      // BWD_LAYER
+  // outputs.  d_trans (rows x 3) / d_rot (rows x 9), nullable: gradients with respect to the frames, which the reference's forward is
+  // differentiable in (:315-336, :594-596) - d_x_t / d_O_t of the denoiser, d_t / d_R of the layer; the training step never asks
+  float *layer_dx, *d_res_ctx, *d_pair_ctx, *d_trans, *d_rot;
+};
+int run_backward(const BackwardArgs& a);
 // Y = act(X W^T + b) backward: dW += dY^T X (W is N x Kd, row-major), db += colsum dY (nullable), dX (+)= dY W (nullable).
 // dY must already carry the activation mask (bwd_relu_mask: dY *= act > 0, in place).  bwd_gemm_nn: C (+)= A[M,K] B[K,N].
 int bwd_linear(const float* dY, int ldy, const float* X, int ldx, const float* W, float* dW, float* db, float* dX, int lddx, int M, int N,

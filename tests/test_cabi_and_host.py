@@ -77,6 +77,31 @@ def test_null_denoiser_weight_is_refused_on_the_host():
     assert call() == -4
 
 
+# (B, K, D, C, H, DS, PQ, PV, NL, V) -> train_tape_bytes, train_workspace_bytes, ipa_layer_tape_bytes, ipa_layer_bwd_workspace_bytes
+TRAIN_LAYOUT_BYTES = [
+    ((2, 128, 128, 64, 8, 32, 8, 8, 3, 21), (16654080, 16997632, 7347968, 13851904)),  # fast path, split attention (K = 128)
+    ((3, 64, 128, 64, 8, 32, 8, 8, 2, 21), (7734272, 9074432, 5030912, 8288000)),  # ... K = 64
+    ((1, 64, 128, 64, 8, 32, 8, 8, 16, 21), (16010752, 3189248, 2493952, 3451648)),  # the deepest tape, NL > kDeLayersMax
+    ((2, 128, 128, 64, 8, 32, 8, 8, 7, 21), (35266304, 12278784, 7347968, 13851904)),  # NL just past kDeLayersMax
+    ((2, 192, 128, 64, 8, 32, 8, 8, 2, 21), (11097344, 14755840, 7263488, 14755840)),  # fast path without the split attention
+    ((2, 7, 20, 6, 3, 5, 2, 3, 2, 21), (39992, 35512, 28960, 35512)),  # generic dims
+    ((1, 5, 12, 0, 2, 4, 3, 2, 1, 21), (9436, 7792, 9436, 7792)),  # C = 0
+]
+
+
+def test_training_tape_and_workspace_sizes_are_pinned():
+    """The training tape and the backward's workspace are each described once, by the function that carves them; the sizing entries are
+    that function with a null base.  Their totals are the ones callers have always allocated (host arithmetic only: no GPU needed), and
+    a tape of more than 16 layers is still refused."""
+    l = _hip.load_library()
+    entries = [l.diffab_train_tape_bytes, l.diffab_train_workspace_bytes, l.diffab_ipa_layer_tape_bytes,
+               l.diffab_ipa_layer_bwd_workspace_bytes]
+    for dims, want in TRAIN_LAYOUT_BYTES:
+        d = _hip.Dims(*dims)
+        assert tuple(int(f(ctypes.byref(d))) for f in entries) == want, dims
+    assert l.diffab_train_tape_bytes(ctypes.byref(_hip.Dims(1, 64, 128, 64, 8, 32, 8, 8, 17, 21))) == 0
+
+
 def test_schedule_is_bit_identical_to_reference(golden):
     from diffab_pytorch.diffusion import cosine_variance_schedule
 

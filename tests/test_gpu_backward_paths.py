@@ -1,6 +1,7 @@
 """The training backward (csrc/denoiser_backward.hip, run_backward) at the K, depth and frozen-context branches no other test compares.
 
-run_backward picks its kernels from K, the layer count NL, which gradients were asked for and the buffers it reuses across layers.  At the
+run_backward picks its kernels (plan_backward once per call, choose_attn_bwd once per layer) from K, the layer count NL, which gradients
+were asked for and the buffers of its workspace (BwdWorkspace) it reuses across layers.  At the
 benchmark dims (D = 128, C = 64, H = 8, DS = 32, PQ = PV = 8) every case below is compared with the float64 oracle
 (oracle/diffab_oracle.py under torch autograd on the host): the losses (rtol 5e-5), the forward outputs where the mode returns them (TOL),
 every input gradient and every denoiser parameter (GTOL, max-rel).

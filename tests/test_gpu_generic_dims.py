@@ -1,7 +1,8 @@
 """The any-dims denoiser, its backward and the sampler step at model dims other than the unit and benchmark ones, against the float64 oracle.
 
 Every geometry that is not the benchmark one (fast_path_supported: D = 128, C = 64, H = 8, DS = 32, PQ = PV = 8, K % 64 == 0) runs on
-denoiser_generic.hip, the launch_linear MLP kernels and the generic half of run_backward (csrc/denoiser_backward.hip).  Those branch on
+denoiser_generic.hip, the launch_linear MLP kernels and the generic half of run_backward (csrc/denoiser_backward.hip: the VALU row and
+key passes of choose_attn_bwd).  Those branch on
 H, on PQ against PV, on DS / C / 3 PQ / 3 PV modulo 4 and on the attention's LDS need; the cases below pick each branch (confirmed by a
 kernel trace, profiles/generic_dims.md):
 
