@@ -39,6 +39,19 @@
  *     not be captured into a hipGraph from a stream other than the last one used.  NOTE for callers: the hardware behaviour applies to
  *     YOUR kernels too - a caller's own VALU kernel holding that packed form can miscompute beside this library's f16 / bf16 MFMA
  *     kernels on another stream (tools/isa_hazard_lint.py checks any gfx950 object file or shared library).
+ *   - Workspaces and tapes: what a workspace or a tape holds ON ENTRY is ignored - it may be zeros, NaN bit patterns or the leftover of a
+ *     call at another shape, mask or flag selection, and the result is the same to the bit (for the gradients below: to their stated
+ *     accuracy).  What a workspace holds ON EXIT is unspecified.  Nothing outside [p, p + bytes) of the stated *_workspace_bytes /
+ *     *_tape_bytes is written.  A tape is fully defined by its forward call: the backward reads nothing of it that the forward of the
+ *     same dims and flags did not write.  Every element of an OUTPUT tensor is written, unless its entry says otherwise (the record of
+ *     diffab_sample_record is written in every slot; the steering ancestors table is filled with -1 by the call, then written in the
+ *     rows of the steered steps; row 0 of the chain embedding's gradient - padding_idx = 0 - stays the caller's zero).  Buffers the
+ *     library ACCUMULATES into (float atomics, order-dependent in the last bits) are the only ones the caller must zero-fill first:
+ *     every buffer of a `grads` / `g` weight struct (diffab_train_step_bwd, diffab_denoise_step_bwd, diffab_ipa_layer_bwd,
+ *     diffab_residue_embedding_bwd, diffab_pair_embedding_bwd / _bwd_taped), d_pair_ctx of the two denoiser backwards and d_e of
+ *     diffab_ipa_layer_bwd (each NULL to skip); and the steering state logw / u_prev, 0 at the start of a run.  d_res_ctx, d_x_t,
+ *     d_O_t, d x, d R, d t are written, not accumulated.  tests/test_gpu_scratch_contract.py holds every hot-path entry to this with
+ *     zero, 0xFF and random fills behind guard bytes, and with the previous call's leftover.
  *   - empty problems (a count or extent of 0) return 0 before any pointer is looked at: an empty tensor's data pointer is NULL;
  *   - return 0 on success, a negative DIFFAB_ERR_* otherwise (never throws);
  *     diffab_last_error() gives the thread's last message.

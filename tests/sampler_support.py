@@ -113,6 +113,29 @@ def device_patches(B, K, dims, seed):
     return out
 
 
+def segment_mask(B, K, spans):
+    """(B, K) generation mask with the residues lo .. hi - 1 of every span generated in every patch."""
+    gm = torch.zeros(B, K, dtype=torch.bool)
+    for lo, hi in spans:
+        gm[:, lo:hi] = True
+    return gm
+
+
+def slab_mask(name, B, K, synthetic_mask):
+    """The generation masks of the row-plan tests by name, over the 32-row slabs of a K >= 128 patch."""
+    if name == "mixed":  # patch 0 nothing, patch 1 everything, the rest the synthetic segments
+        gm = synthetic_mask.clone()
+        gm[0], gm[1] = False, True
+        return gm
+    return {"one_slab": segment_mask(B, K, [(12, 21)]),
+            "two_adjacent_slabs": segment_mask(B, K, [(31, 33)]),
+            "slabs_0_and_3": segment_mask(B, K, [(5, 12), (K - 30, K - 18)]),
+            "three_slabs": segment_mask(B, K, [(5, 12), (40, 46), (100, 106)]),  # slabs 0, 1, 3: a two-slab pass, then a one-slab pass
+            "row_127": segment_mask(B, K, [(K - 1, K)]),
+            "none": torch.zeros(B, K, dtype=torch.bool),
+            "all": torch.ones(B, K, dtype=torch.bool)}[name]
+
+
 def sample(model, inp, **kw):
     tabs = {k: inp[k] for k in ("chain_idx", "residue_idx", "residue_mask") if k in inp}
     return model.sample(inp["seq_idx"], inp["translations"], inp["orientations"], generation_mask=inp["generation_mask"],

@@ -9,7 +9,7 @@ import torch
 
 from diffab_pytorch import _hip, synthetic as syn
 from diffab_pytorch.steering import ParticleSteering
-from sampler_support import assert_bitwise, hip, make_model, patches, sample  # noqa: F401 (hip: the device fixture)
+from sampler_support import assert_bitwise, hip, make_model, patches, sample, segment_mask, slab_mask  # noqa: F401 (hip: the device fixture)
 
 pytestmark = pytest.mark.gpu
 MODULE = _hip.FLAG_PERSISTENT_MODULE
@@ -30,27 +30,6 @@ def models(hip):
 @pytest.fixture(scope="module")
 def inputs8(models):
     return {NL: patches(8, K, models[NL][0], seed=240 + NL) for NL in models}
-
-
-def _segment(B, spans):
-    gm = torch.zeros(B, K, dtype=torch.bool)
-    for lo, hi in spans:
-        gm[:, lo:hi] = True
-    return gm
-
-
-def _mask(name, B, synthetic_mask):
-    if name == "mixed":  # patch 0 nothing, patch 1 everything, the rest the synthetic segments
-        gm = synthetic_mask.clone()
-        gm[0], gm[1] = False, True
-        return gm
-    return {"one_slab": _segment(B, [(12, 21)]),
-            "two_adjacent_slabs": _segment(B, [(31, 33)]),
-            "slabs_0_and_3": _segment(B, [(5, 12), (K - 30, K - 18)]),
-            "three_slabs": _segment(B, [(5, 12), (40, 46), (100, 106)]),  # slabs 0, 1, 3: a two-slab pass, then a one-slab pass
-            "row_127": _segment(B, [(K - 1, K)]),
-            "none": torch.zeros(B, K, dtype=torch.bool),
-            "all": torch.ones(B, K, dtype=torch.bool)}[name]
 
 
 def _run(model, inp, gm, flags, **kw):
@@ -76,7 +55,7 @@ def _three_ways(model, inp, gm, what, **kw):
 def test_heads_on_live_slabs(models, inputs8, NL, name):
     _, model = models[NL]
     inp = inputs8[NL]
-    gm = _mask(name, 8, inp["generation_mask"].cpu())
+    gm = slab_mask(name, 8, K, inp["generation_mask"].cpu())
     out = _three_ways(model, inp, gm, (NL, name))
     for k in ("translations", "seq_idx", "orientations"):
         assert torch.equal(out[k].cpu()[~gm], inp[k].cpu()[~gm]), (NL, name, k)
@@ -105,7 +84,7 @@ def test_second_call_on_the_same_workspace(models, inputs8, graph):
     first = _run(model, inp, gm1, MODULE, graph=graph, **kw)
     fresh = make_model(dims, 41 + 3)
     assert_bitwise(first, _run(fresh, inp, gm1, _hip.FLAG_MULTI_LAUNCH, skip_unused_rows=False, **kw), ("first call", graph))
-    gm2 = _segment(8, [(40, 52), (110, 128)])
+    gm2 = segment_mask(8, K, [(40, 52), (110, 128)])
     inp2 = dict(inp, seq_idx=(inp["seq_idx"] + 7) % 20)  # every row's type moves, the fixed rows' with it
     second = _run(model, inp2, gm2, MODULE, graph=graph, **kw)
     assert_bitwise(second, _run(fresh, inp2, gm2, _hip.FLAG_MULTI_LAUNCH, skip_unused_rows=False, **kw), ("second call", graph))
@@ -115,7 +94,7 @@ def test_second_call_on_the_same_workspace(models, inputs8, graph):
 def test_shared_contexts(models):
     dims, model = models[3]
     inp = patches(4, K, dims, seed=263)
-    for gm in (inp["generation_mask"].cpu(), _segment(4, [(31, 33)])):
+    for gm in (inp["generation_mask"].cpu(), segment_mask(4, K, [(31, 33)])):
         out = _three_ways(model, inp, gm, "shared contexts", num_samples=2)
         assert out["translations"].shape[0] == 8
         assert not torch.equal(out["translations"][0], out["translations"][1])  # two designs of patch 0
@@ -127,7 +106,7 @@ def test_steering_moves_whole_rows(models):
     inp = patches(8, K, dims, seed=271, chains=True)
     kw = dict(num_samples=2, steering=ParticleSteering(strength=0.05, ess_threshold=2.0))
     moved = 0
-    for gm in (inp["generation_mask"].cpu(), _segment(8, [(110, 128)])):
+    for gm in (inp["generation_mask"].cpu(), segment_mask(8, K, [(110, 128)])):
         out = _three_ways(model, inp, gm, "steering", **kw)
         moved += int((out["steering"]["ancestors"].cpu() != torch.arange(16)).sum())
     assert moved > 0, "some ancestor must differ from the identity for this case to say anything"
@@ -138,5 +117,5 @@ def test_allowed_aa_reads_the_posterior(models):
     dims, model = models[3]
     inp = patches(8, K, dims, seed=277)
     allowed = torch.rand(8, K, 21, generator=torch.Generator().manual_seed(5)) < 0.6
-    for gm in (inp["generation_mask"].cpu(), _segment(8, [(31, 33)])):
+    for gm in (inp["generation_mask"].cpu(), segment_mask(8, K, [(31, 33)])):
         _three_ways(model, inp, gm, "allowed_aa", allowed_aa=allowed)
