@@ -164,6 +164,35 @@ static int check_denoiser_weights(const diffab_dims* d, const diffab_denoiser_we
   return DIFFAB_OK;
 }
 
+// Operand alignment of a weight (or gradient) table: every float buffer of it, named `group.field` in the message.  The denoiser, layer,
+// training, sampler and scoring entries refuse a float operand that is not 16-byte aligned (their tiles load and store float4), on the
+// host and before anything is enqueued; int64 indices and masks are read element by element and need their natural alignment only.
+static int check_layer_aligned(const char* who, const char* group, int l, const diffab_ipa_layer_weights* w) {
+  const Operand fs[] = {{"gamma", w->gamma}, {"wq_s", w->wq_s}, {"wk_s", w->wk_s}, {"wv_s", w->wv_s}, {"w_bias", w->w_bias},
+                        {"wq_p", w->wq_p},   {"wk_p", w->wk_p}, {"wv_p", w->wv_p}, {"w_out", w->w_out}, {"b_out", w->b_out}};
+  for (const Operand& f : fs)
+    DIFFAB_REQUIRE(aligned16(f.p), DIFFAB_ERR_ARG, "%s: operand %s.layers[%d].%s must be 16-byte aligned (see \"Operand alignment\" in diffab_hip.h)",
+                   who, group, l, f.name);
+  return DIFFAB_OK;
+}
+static int check_denoiser_aligned(const char* who, const char* group, const diffab_dims* d, const diffab_denoiser_weights* w) {
+  const Operand fs[] = {{"seq_emb", w->seq_emb}, {"res_w0", w->res_w0}, {"res_b0", w->res_b0}, {"res_w2", w->res_w2}, {"res_b2", w->res_b2}};
+  for (const Operand& f : fs)
+    DIFFAB_REQUIRE(aligned16(f.p), DIFFAB_ERR_ARG, "%s: operand %s.%s must be 16-byte aligned (see \"Operand alignment\" in diffab_hip.h)", who,
+                   group, f.name);
+  const diffab_mlp3_weights* hw[3] = {&w->coord, &w->orient, &w->seq};
+  const char* hn[3] = {"coord", "orient", "seq"};
+  for (int hd = 0; hd < 3; ++hd) {
+    const Operand hs[] = {{"w0", hw[hd]->w0}, {"b0", hw[hd]->b0}, {"w2", hw[hd]->w2}, {"b2", hw[hd]->b2}, {"w4", hw[hd]->w4}, {"b4", hw[hd]->b4}};
+    for (const Operand& f : hs)
+      DIFFAB_REQUIRE(aligned16(f.p), DIFFAB_ERR_ARG, "%s: operand %s.%s.%s must be 16-byte aligned (see \"Operand alignment\" in diffab_hip.h)",
+                     who, group, hn[hd], f.name);
+  }
+  for (int l = 0; l < d->NL; ++l)
+    if (int rc = check_layer_aligned(who, group, l, &w->layers[l])) return rc;
+  return DIFFAB_OK;
+}
+
 static bool use_pair_planes(const diffab_dims* d, uint32_t flags, const float* pair_ctx, const StepBuffers& b) {
   const uint32_t other = DIFFAB_FLAG_FORCE_GENERIC | DIFFAB_FLAG_PAIR_F32;
   return (flags & DIFFAB_FLAG_PAIR_PLANES) && !(flags & other) && b.pair != nullptr && pair_planes_supported(d) &&
@@ -491,6 +520,7 @@ int diffab_debug_linear128(const float* X, const float* W, const float* bias, fl
   DIFFAB_REQUIRE(X && W && Y && M >= 1 && M < (1LL << 31) && Kd >= 32 && Kd % 32 == 0, DIFFAB_ERR_ARG, "debug_linear128: bad operands");
   hipStream_t st = as_stream(stream);
   if (mode == 0) return launch_linear(X, Kd, W, bias, Y, 128, static_cast<int>(M), 128, Kd, false, st);  // rowgemm128 / tiled f32 MFMA
+  if (int rc = require_aligned16("debug_linear128", {{"X", X}, {"W", W}, {"bias", bias}, {"Y", Y}})) return rc;  // (modes 1 and 2)
   if (mode == 2) {  // fp16 x 3 (gemm_f16x3.hip): planes | 1 / scale of the 128 weight rows
     const size_t pb = (rowgemm128_h3_planes_bytes(Kd) + 255) & ~static_cast<size_t>(255);
     DIFFAB_REQUIRE(Kd % 64 == 0, DIFFAB_ERR_ARG, "debug_linear128: mode 2 (fp16 x 3) needs Kd %% 64 == 0 (its chunks of 32 k are joined in pairs)");
@@ -512,6 +542,7 @@ int diffab_debug_xstat128(const float* X, const float* W, float* Y, int64_t M, i
   DIFFAB_REQUIRE(X && W && Y && scratch && M >= 1 && M < (1LL << 31) && N >= 1 && (mode == 1 || mode == 2), DIFFAB_ERR_ARG,
                  "debug_xstat128: bad operands");
   const size_t need = mode == 1 ? xstat_b6_scratch_bytes(N) : xstat_h3_scratch_bytes(N);
+  if (int rc = require_aligned16("debug_xstat128", {{"X", X}, {"W", W}, {"Y", Y}})) return rc;
   DIFFAB_REQUIRE(scratch_bytes >= need && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0,
                  DIFFAB_ERR_ARG, "debug_xstat128: needs 16-byte aligned X / scratch and %zu bytes of scratch", need);
   hipStream_t st = as_stream(stream);
@@ -608,6 +639,9 @@ int diffab_ipa_layer_fwd(const diffab_dims* d, const diffab_ipa_layer_weights* w
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "ipa_layer_fwd")) return rc;
   DIFFAB_REQUIRE(x && (e || d->C == 0) && R && t && y && workspace, DIFFAB_ERR_ARG, "ipa_layer_fwd: null pointer");
+  if (int rc = require_aligned16("ipa_layer_fwd", {{"x", x}, {"e", e}, {"R", R}, {"t", t}, {"y", y}})) return rc;
+  if (w != nullptr)  // (a null table or field is the dispatch's refusal, behind the workspace check as before)
+    if (int rc = check_layer_aligned("ipa_layer_fwd", "w", 0, w)) return rc;
   const StepBuffers b = carve_step(d, workspace);
   DIFFAB_REQUIRE(workspace_bytes >= b.bytes, DIFFAB_ERR_WORKSPACE, "ipa_layer_fwd: workspace %zu < %zu bytes", workspace_bytes, b.bytes);
   const float* pair_planes = nullptr;
@@ -627,6 +661,11 @@ int diffab_denoise_step_fwd(const diffab_dims* d, const diffab_denoiser_weights*
   if (int rc = check_denoiser_weights(d, w)) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && res_ctx && pair_ctx && beta && out_eps && out_O0 && out_posterior && workspace, DIFFAB_ERR_ARG,
                  "denoise_step_fwd: null pointer");
+  if (int rc = require_aligned16("denoise_step_fwd", {{"x_t", x_t}, {"O_t", O_t}, {"res_ctx", res_ctx}, {"pair_ctx", pair_ctx}, {"beta", beta},
+                                                      {"out_eps", out_eps}, {"out_O0", out_O0}, {"out_posterior", out_posterior},
+                                                      {"out_logits", out_logits}, {"out_res_emb", out_res_emb}}))
+    return rc;
+  if (int rc = check_denoiser_aligned("denoise_step_fwd", "w", d, w)) return rc;
   const StepBuffers b = carve_step(d, workspace);
   DIFFAB_REQUIRE(workspace_bytes >= b.bytes, DIFFAB_ERR_WORKSPACE, "denoise_step_fwd: workspace %zu < %zu bytes", workspace_bytes, b.bytes);
   hipStream_t st = as_stream(stream);
@@ -667,6 +706,11 @@ int diffab_train_step_fwd(const diffab_dims* d, const diffab_denoiser_weights* w
   DIFFAB_REQUIRE(seq_t && x_t && O_t && res_ctx && pair_ctx && beta && true_post && true_eps && true_O0 && gen_mask && res_mask && out_eps &&
                      out_O0 && out_posterior && losses3 && tape,
                  DIFFAB_ERR_ARG, "train_step_fwd: null pointer");
+  if (int rc = require_aligned16("train_step_fwd", {{"x_t", x_t}, {"O_t", O_t}, {"res_ctx", res_ctx}, {"pair_ctx", pair_ctx}, {"beta", beta},
+                                                    {"true_post", true_post}, {"true_eps", true_eps}, {"true_O0", true_O0}, {"out_eps", out_eps},
+                                                    {"out_O0", out_O0}, {"out_posterior", out_posterior}, {"losses3", losses3}}))
+    return rc;
+  if (int rc = check_denoiser_aligned("train_step_fwd", "w", d, w)) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "train_step_fwd: tape %zu < %zu bytes", tape_bytes,
                  train_tape_floats(d) * sizeof(float));
   const TrainTape tp = carve_tape(d, static_cast<float*>(tape));
@@ -691,6 +735,13 @@ int diffab_train_step_bwd(const diffab_dims* d, const diffab_denoiser_weights* w
   DIFFAB_REQUIRE(seq_t && x_t && O_t && pair_ctx && out_eps && out_O0 && out_posterior && true_post && true_eps && true_O0 && gen_mask &&
                      res_mask && upstream3 && tape && workspace,
                  DIFFAB_ERR_ARG, "train_step_bwd: null pointer");
+  if (int rc = require_aligned16("train_step_bwd", {{"x_t", x_t}, {"O_t", O_t}, {"pair_ctx", pair_ctx}, {"out_eps", out_eps}, {"out_O0", out_O0},
+                                                    {"out_posterior", out_posterior}, {"true_post", true_post}, {"true_eps", true_eps},
+                                                    {"true_O0", true_O0}, {"upstream3", upstream3}, {"d_res_ctx", d_res_ctx},
+                                                    {"d_pair_ctx", d_pair_ctx}}))
+    return rc;
+  if (int rc = check_denoiser_aligned("train_step_bwd", "w", d, w)) return rc;
+  if (int rc = check_denoiser_aligned("train_step_bwd", "grads", d, grads)) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "train_step_bwd: tape too small");
   DIFFAB_REQUIRE(workspace_bytes >= train_bwd_workspace_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "train_step_bwd: workspace %zu < %zu",
                  workspace_bytes, train_bwd_workspace_floats(d) * sizeof(float));
@@ -718,6 +769,11 @@ int diffab_denoise_step_fwd_taped(const diffab_dims* d, const diffab_denoiser_we
   if (int rc = check_attn_bwd_lds(d, "denoise_step_fwd_taped")) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && res_ctx && pair_ctx && beta && out_eps && out_O0 && out_posterior && tape, DIFFAB_ERR_ARG,
                  "denoise_step_fwd_taped: null pointer");
+  if (int rc = require_aligned16("denoise_step_fwd_taped", {{"x_t", x_t}, {"O_t", O_t}, {"res_ctx", res_ctx}, {"pair_ctx", pair_ctx},
+                                                            {"beta", beta}, {"out_eps", out_eps}, {"out_O0", out_O0},
+                                                            {"out_posterior", out_posterior}}))
+    return rc;
+  if (int rc = check_denoiser_aligned("denoise_step_fwd_taped", "w", d, w)) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_fwd_taped: tape %zu < %zu bytes",
                  tape_bytes, train_tape_floats(d) * sizeof(float));
   const TrainTape tp = carve_tape(d, static_cast<float*>(tape));
@@ -737,6 +793,12 @@ int diffab_denoise_step_bwd(const diffab_dims* d, const diffab_denoiser_weights*
   if (int rc = check_attn_bwd_lds(d, "denoise_step_bwd")) return rc;
   DIFFAB_REQUIRE(seq_t && x_t && O_t && pair_ctx && out_posterior && d_res_ctx && tape && workspace, DIFFAB_ERR_ARG,
                  "denoise_step_bwd: null pointer");
+  if (int rc = require_aligned16("denoise_step_bwd", {{"x_t", x_t}, {"O_t", O_t}, {"pair_ctx", pair_ctx}, {"out_posterior", out_posterior},
+                                                      {"d_eps", d_eps}, {"d_O0", d_O0}, {"d_posterior", d_posterior}, {"d_res_ctx", d_res_ctx},
+                                                      {"d_pair_ctx", d_pair_ctx}, {"d_x_t", d_x_t}, {"d_O_t", d_O_t}}))
+    return rc;
+  if (int rc = check_denoiser_aligned("denoise_step_bwd", "w", d, w)) return rc;
+  if (int rc = check_denoiser_aligned("denoise_step_bwd", "grads", d, grads)) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_bwd: tape too small");
   DIFFAB_REQUIRE(workspace_bytes >= train_bwd_workspace_floats(d) * sizeof(float), DIFFAB_ERR_WORKSPACE, "denoise_step_bwd: workspace %zu < %zu",
                  workspace_bytes, train_bwd_workspace_floats(d) * sizeof(float));
@@ -773,6 +835,9 @@ int diffab_ipa_layer_fwd_taped(const diffab_dims* d, const diffab_ipa_layer_weig
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "ipa_layer_fwd_taped")) return rc;
   DIFFAB_REQUIRE(x && (e || d->C == 0) && R && t && y && tape, DIFFAB_ERR_ARG, "ipa_layer_fwd_taped: null pointer");
+  if (int rc = require_aligned16("ipa_layer_fwd_taped", {{"x", x}, {"e", e}, {"R", R}, {"t", t}, {"y", y}})) return rc;
+  if (w != nullptr)  // (a null table or field is the dispatch's refusal, behind the workspace check as before)
+    if (int rc = check_layer_aligned("ipa_layer_fwd_taped", "w", 0, w)) return rc;
   const diffab_dims d1 = one_layer(d);
   if (int rc = check_attn_bwd_lds(&d1, "ipa_layer_fwd_taped")) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_fwd_taped: tape %zu < %zu bytes", tape_bytes,
@@ -798,6 +863,10 @@ int diffab_ipa_layer_bwd(const diffab_dims* d, const diffab_ipa_layer_weights* w
   StreamOrder order_(stream);
   if (int rc = check_dims(d, "ipa_layer_bwd")) return rc;
   DIFFAB_REQUIRE(w && grads && (e || d->C == 0) && R && t && dy && dx && tape && workspace, DIFFAB_ERR_ARG, "ipa_layer_bwd: null pointer");
+  if (int rc = require_aligned16("ipa_layer_bwd", {{"e", e}, {"R", R}, {"t", t}, {"dy", dy}, {"dx", dx}, {"d_e", d_e}, {"d_R", d_R}, {"d_t", d_t}}))
+    return rc;
+  if (int rc = check_layer_aligned("ipa_layer_bwd", "w", 0, w)) return rc;
+  if (int rc = check_layer_aligned("ipa_layer_bwd", "grads", 0, grads)) return rc;
   const diffab_dims d1 = one_layer(d);
   if (int rc = check_attn_bwd_lds(&d1, "ipa_layer_bwd")) return rc;
   DIFFAB_REQUIRE(tape_bytes >= train_tape_floats(&d1) * sizeof(float), DIFFAB_ERR_WORKSPACE, "ipa_layer_bwd: tape too small");
@@ -1016,6 +1085,8 @@ int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w
   DIFFAB_REQUIRE(rev_tab && rev_tab->sigmas && rev_tab->cdf && rev_tab->n_sigmas >= s->T + 1 && rev_tab->n_bins > 0, DIFFAB_ERR_ARG,
                  "sample_loop: reverse IGSO3 table must have T+1 rows");
   DIFFAB_REQUIRE(seq && x && O && res_ctx && pair_ctx && gen_mask && workspace, DIFFAB_ERR_ARG, "sample_loop: null pointer");
+  if (int rc = require_aligned16("sample_loop", {{"x", x}, {"O", O}, {"res_ctx", res_ctx}, {"pair_ctx", pair_ctx}})) return rc;
+  if (int rc = check_denoiser_aligned("sample_loop", "w", d, w)) return rc;
   DIFFAB_REQUIRE(t_start <= s->T && t_stop >= 0 && t_stop <= t_start, DIFFAB_ERR_ARG, "sample_loop: need T >= t_start >= t_stop >= 0");
   // design modes: the modality a KEEP bit names is never written by the update kernel (the only writer of the state in the loop); the
   // bits mean nothing to the denoiser, which sees the state as it is
@@ -1174,6 +1245,8 @@ int diffab_score_designs(const diffab_dims* d, const diffab_denoiser_weights* w,
                  "score_designs: forward IGSO3 table must have T+1 rows");
   DIFFAB_REQUIRE(seq && x && O && gen_mask && res_ctx && pair_ctx && t_list && out_terms && workspace, DIFFAB_ERR_ARG,
                  "score_designs: null pointer (seq, x, O, gen_mask, res_ctx, pair_ctx, t_list, out_terms and workspace are required)");
+  if (int rc = require_aligned16("score_designs", {{"res_ctx", res_ctx}, {"pair_ctx", pair_ctx}})) return rc;
+  if (int rc = check_denoiser_aligned("score_designs", "w", d, w)) return rc;
   DIFFAB_REQUIRE(n_designs >= 1, DIFFAB_ERR_ARG, "score_designs: n_designs = %d < 1", n_designs);
   DIFFAB_REQUIRE(first_design >= 0 && first_design + n_designs <= (1ll << 32), DIFFAB_ERR_ARG,
                  "score_designs: first_design + n_designs must lie in [0, 2^32] (Philox patch ids)");

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "../../include/diffab_hip.h"
 
@@ -57,6 +58,21 @@ class StreamOrder {
  private:
   int dev_;
 };
+
+// Operand alignment (include/diffab_hip.h, "Operand alignment"): an entry whose kernels read or write a data operand with 16-byte vector
+// accesses refuses it here - on the host, among its argument checks, before anything is enqueued - when the pointer is not 16-byte
+// aligned.  A NULL operand (an optional one left out) passes.  The message names the entry and the operand.
+struct Operand {
+  const char* name;
+  const void* p;
+};
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline int require_aligned16(const char* who, std::initializer_list<Operand> ops) {
+  for (const Operand& o : ops)
+    DIFFAB_REQUIRE(aligned16(o.p), DIFFAB_ERR_ARG, "%s: operand %s must be 16-byte aligned (see \"Operand alignment\" in diffab_hip.h)", who,
+                   o.name);
+  return DIFFAB_OK;
+}
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

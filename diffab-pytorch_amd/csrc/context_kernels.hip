@@ -290,6 +290,8 @@ __global__ void featurize_residue_kernel(const float* __restrict__ xyz, const in
 
 // one thread per residue pair (i, j): phi_ij = (C_i, N_j, CA_j, C_j), psi_ij = (N_i, CA_i, C_i, N_j)   (data.py:78-80:
 // pairwise_dihedrals(atoms_i=["C"], atoms_j=["N","CA","C"]) and (atoms_i=["N","CA","C"], atoms_j=["N"]))
+// kVec: `out` is 8-byte aligned and takes one float2 store per pair; otherwise (a caller's view at a 4-byte offset) two float stores
+template <bool kVec>
 __global__ void featurize_pair_kernel(const float* __restrict__ xyz, int K, int A, int64_t pairs, float* __restrict__ out) {
   const int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
   if (g >= pairs) return;
@@ -300,7 +302,11 @@ __global__ void featurize_pair_kernel(const float* __restrict__ xyz, int K, int 
   float2 o;
   o.x = dihedral4(ai + 6, aj, aj + 3, aj + 6);
   o.y = dihedral4(ai, ai + 3, ai + 6, aj);
-  reinterpret_cast<float2*>(out)[g] = o;
+  if constexpr (kVec) {
+    reinterpret_cast<float2*>(out)[g] = o;
+  } else {
+    out[2 * g] = o.x; out[2 * g + 1] = o.y;
+  }
 }
 
 // ------------------------------------------------------------------ backward (training through encode_context)
@@ -639,6 +645,26 @@ static int check_ctx(const diffab_ctx_dims* d, const char* who) {
   return DIFFAB_OK;
 }
 
+// Operand alignment (include/diffab_hip.h): the encoders' dense products and fused kernels load and store float4, so every float operand
+// and every buffer of a weight or gradient table is refused here, before anything is enqueued, unless it is 16-byte aligned.
+static int check_residue_weights_aligned(const char* who, const char* group, const diffab_residue_emb_weights* w) {
+  const Operand fs[] = {{"aa_emb", w->aa_emb}, {"chain_emb", w->chain_emb}, {"w0", w->w0}, {"b0", w->b0}, {"w2", w->w2},
+                        {"b2", w->b2},         {"w4", w->w4},               {"b4", w->b4}, {"w6", w->w6}, {"b6", w->b6}};
+  for (const Operand& f : fs)
+    DIFFAB_REQUIRE(aligned16(f.p), DIFFAB_ERR_ARG, "%s: operand %s.%s must be 16-byte aligned (see \"Operand alignment\" in diffab_hip.h)", who,
+                   group, f.name);
+  return DIFFAB_OK;
+}
+static int check_pair_weights_aligned(const char* who, const char* group, const diffab_pair_emb_weights* w) {
+  const Operand fs[] = {{"aa_pair_emb", w->aa_pair_emb}, {"relpos_emb", w->relpos_emb}, {"pair2distcoef", w->pair2distcoef},
+                        {"dw0", w->dw0}, {"db0", w->db0}, {"dw2", w->dw2}, {"db2", w->db2}, {"mw0", w->mw0}, {"mb0", w->mb0},
+                        {"mw2", w->mw2}, {"mb2", w->mb2}, {"mw4", w->mw4}, {"mb4", w->mb4}};
+  for (const Operand& f : fs)
+    DIFFAB_REQUIRE(aligned16(f.p), DIFFAB_ERR_ARG, "%s: operand %s.%s must be 16-byte aligned (see \"Operand alignment\" in diffab_hip.h)", who,
+                   group, f.name);
+  return DIFFAB_OK;
+}
+
 size_t diffab_residue_embedding_workspace_bytes(const diffab_ctx_dims* d) {
   if (check_ctx(d, "residue_embedding_workspace_bytes")) return 0;
   const size_t rows = static_cast<size_t>(d->B) * d->K, Din = 2 * d->D + kAA * d->A * 3 + 39;
@@ -655,6 +681,10 @@ int diffab_residue_embedding_fwd(const diffab_ctx_dims* d, const diffab_residue_
                  "residue_embedding_fwd: null weight");
   DIFFAB_REQUIRE(seq_idx && xyz && orientations && dihedrals && chain_idx && atom_mask && out && workspace, DIFFAB_ERR_ARG,
                  "residue_embedding_fwd: null pointer");
+  if (int rc = require_aligned16("residue_embedding_fwd", {{"xyz", xyz}, {"orientations", orientations}, {"dihedrals", dihedrals},
+                                                           {"atom_mask", atom_mask}, {"out", out}}))
+    return rc;
+  if (int rc = check_residue_weights_aligned("residue_embedding_fwd", "w", w)) return rc;
   DIFFAB_REQUIRE(workspace_bytes >= diffab_residue_embedding_workspace_bytes(d), DIFFAB_ERR_WORKSPACE, "residue_embedding_fwd: workspace");
   hipStream_t st = as_stream(stream);
   const int rows = d->B * d->K, D = d->D, Din = 2 * D + kAA * d->A * 3 + 39;
@@ -706,6 +736,10 @@ static int pair_embedding_impl(const diffab_ctx_dims* d, const diffab_pair_emb_w
                  DIFFAB_ERR_ARG, "pair_embedding_fwd: null weight");
   DIFFAB_REQUIRE(seq_idx && (distmat || xyz) && pairwise_dihedrals && residue_idx && chain_idx && atom_mask && out && workspace,
                  DIFFAB_ERR_ARG, "pair_embedding_fwd: null pointer");
+  if (int rc = require_aligned16("pair_embedding_fwd", {{"distmat", distmat}, {"xyz", xyz}, {"pairwise_dihedrals", pairwise_dihedrals},
+                                                        {"atom_mask", atom_mask}, {"out", out}}))
+    return rc;
+  if (int rc = check_pair_weights_aligned("pair_embedding_fwd", "w", w)) return rc;
   DIFFAB_REQUIRE(workspace_bytes >= diffab_pair_embedding_workspace_bytes(d), DIFFAB_ERR_WORKSPACE, "pair_embedding_fwd: workspace");
   hipStream_t st = as_stream(stream);
   if (pair_embed_fused_supported(d))  // C = 64, K % 128 == 0: the whole forward as one kernel (pair_embed_fused.hip)
@@ -784,6 +818,11 @@ int diffab_residue_embedding_bwd(const diffab_ctx_dims* d, const diffab_residue_
                  "residue_embedding_bwd: null gradient buffer");
   DIFFAB_REQUIRE(seq_idx && xyz && orientations && dihedrals && chain_idx && atom_mask && d_out && workspace, DIFFAB_ERR_ARG,
                  "residue_embedding_bwd: null pointer");
+  if (int rc = require_aligned16("residue_embedding_bwd", {{"xyz", xyz}, {"orientations", orientations}, {"dihedrals", dihedrals},
+                                                           {"atom_mask", atom_mask}, {"d_out", d_out}}))
+    return rc;
+  if (int rc = check_residue_weights_aligned("residue_embedding_bwd", "w", w)) return rc;
+  if (int rc = check_residue_weights_aligned("residue_embedding_bwd", "g", g)) return rc;
   DIFFAB_REQUIRE(workspace_bytes >= diffab_residue_embedding_bwd_workspace_bytes(d), DIFFAB_ERR_WORKSPACE, "residue_embedding_bwd: workspace");
   hipStream_t st = as_stream(stream);
   const int rows = d->B * d->K, D = d->D, Din = 2 * D + kAA * d->A * 3 + 39;
@@ -1033,6 +1072,11 @@ int diffab_pair_embedding_bwd(const diffab_ctx_dims* d, const diffab_pair_emb_we
                  DIFFAB_ERR_ARG, "pair_embedding_bwd: null gradient buffer");
   DIFFAB_REQUIRE(seq_idx && (distmat || xyz) && pairwise_dihedrals && residue_idx && chain_idx && atom_mask && d_out && workspace,
                  DIFFAB_ERR_ARG, "pair_embedding_bwd: null pointer");
+  if (int rc = require_aligned16("pair_embedding_bwd", {{"distmat", distmat}, {"xyz", xyz}, {"pairwise_dihedrals", pairwise_dihedrals},
+                                                        {"atom_mask", atom_mask}, {"d_out", d_out}}))
+    return rc;
+  if (int rc = check_pair_weights_aligned("pair_embedding_bwd", "w", w)) return rc;
+  if (int rc = check_pair_weights_aligned("pair_embedding_bwd", "g", g)) return rc;
   DIFFAB_REQUIRE(workspace_bytes >= diffab_pair_embedding_bwd_workspace_bytes(d), DIFFAB_ERR_WORKSPACE, "pair_embedding_bwd: workspace");
   hipStream_t st = as_stream(stream);
   if (pair_embed_fused_supported(d))
@@ -1132,8 +1176,11 @@ int diffab_featurize_xyz(const float* xyz, const int64_t* chain_idx, const uint8
   }
   if (pairwise_dihedrals) {
     const int64_t pairs = rows * K;
-    hipLaunchKernelGGL(featurize_pair_kernel, dim3(static_cast<unsigned>((pairs + 255) / 256)), dim3(256), 0, st, xyz, K, A, pairs,
-                       pairwise_dihedrals);
+    const dim3 grid(static_cast<unsigned>((pairs + 255) / 256));
+    if ((reinterpret_cast<uintptr_t>(pairwise_dihedrals) & 7) == 0)
+      hipLaunchKernelGGL(featurize_pair_kernel<true>, grid, dim3(256), 0, st, xyz, K, A, pairs, pairwise_dihedrals);
+    else
+      hipLaunchKernelGGL(featurize_pair_kernel<false>, grid, dim3(256), 0, st, xyz, K, A, pairs, pairwise_dihedrals);
     DIFFAB_LAUNCH_CHECK();
   }
   return DIFFAB_OK;
@@ -1170,6 +1217,10 @@ int diffab_pair_embedding_fwd_taped(const diffab_ctx_dims* d, const diffab_pair_
   DIFFAB_REQUIRE(seq_idx && ((distmat != nullptr) != (xyz != nullptr)) && pairwise_dihedrals && residue_idx && chain_idx && atom_mask && out &&
                      tape && workspace && (reinterpret_cast<uintptr_t>(tape) & 15) == 0,
                  DIFFAB_ERR_ARG, "pair_embedding_fwd_taped: null pointer (exactly one of distmat / xyz), or a tape that is not 16-byte aligned");
+  if (int rc = require_aligned16("pair_embedding_fwd_taped", {{"distmat", distmat}, {"xyz", xyz}, {"pairwise_dihedrals", pairwise_dihedrals},
+                                                              {"atom_mask", atom_mask}, {"out", out}}))
+    return rc;
+  if (int rc = check_pair_weights_aligned("pair_embedding_fwd_taped", "w", w)) return rc;
   DIFFAB_REQUIRE(tape_bytes >= diffab_pair_embedding_tape_bytes(d), DIFFAB_ERR_WORKSPACE, "pair_embedding_fwd_taped: tape");
   DIFFAB_REQUIRE(workspace_bytes >= diffab_pair_embedding_workspace_bytes(d), DIFFAB_ERR_WORKSPACE, "pair_embedding_fwd_taped: workspace");
   const int64_t rows = static_cast<int64_t>(d->B) * d->K * d->K;
@@ -1194,6 +1245,11 @@ int diffab_pair_embedding_bwd_taped(const diffab_ctx_dims* d, const diffab_pair_
   DIFFAB_REQUIRE(seq_idx && (distmat || xyz) && pairwise_dihedrals && residue_idx && chain_idx && atom_mask && d_out && tape && workspace &&
                      (reinterpret_cast<uintptr_t>(tape) & 15) == 0,
                  DIFFAB_ERR_ARG, "pair_embedding_bwd_taped: null pointer");
+  if (int rc = require_aligned16("pair_embedding_bwd_taped", {{"distmat", distmat}, {"xyz", xyz}, {"pairwise_dihedrals", pairwise_dihedrals},
+                                                              {"atom_mask", atom_mask}, {"d_out", d_out}}))
+    return rc;
+  if (int rc = check_pair_weights_aligned("pair_embedding_bwd_taped", "w", w)) return rc;
+  if (int rc = check_pair_weights_aligned("pair_embedding_bwd_taped", "g", g)) return rc;
   DIFFAB_REQUIRE(tape_bytes >= diffab_pair_embedding_tape_bytes(d), DIFFAB_ERR_WORKSPACE, "pair_embedding_bwd_taped: tape");
   DIFFAB_REQUIRE(workspace_bytes >= diffab_pair_embedding_bwd_workspace_bytes(d), DIFFAB_ERR_WORKSPACE, "pair_embedding_bwd_taped: workspace");
   return pair_embedding_bwd_fused(d, w, g, seq_idx, distmat, xyz, pairwise_dihedrals, residue_idx, residue_idx_batch_stride, chain_idx, atom_mask,

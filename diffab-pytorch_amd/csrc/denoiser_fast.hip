@@ -160,8 +160,6 @@ static int launch_linear_bn(const float* X, int ldx, const LinearSegs& segs, con
   return DIFFAB_OK;
 }
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ================================================================== Y[M x 128] = act(X[M x K] W^T + b), K % 128 == 0
 // The to_out projection (K = 1024) and the 128-wide MLP layers.  With N = 128 the tiled kernel above has one 4-wave work-group
 // per CU (a 1 x M/128 grid) and nothing to hide latency with.  Here a work-group of 8 waves owns 128 rows and ALL 128 columns:

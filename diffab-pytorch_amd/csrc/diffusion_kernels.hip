@@ -473,6 +473,8 @@ __global__ void orient_forward_kernel(const float* __restrict__ abs_, int T, con
 }
 
 // ------------------------------------------------------------------ Philox fill (tests / explicit-noise callers)
+// kVec: `out` is 16-byte aligned and takes one float4 store per residue; otherwise (a caller's view at a 4-byte offset) four float stores
+template <bool kVec>
 __global__ void philox_fill_kernel(uint64_t seed, int64_t first_patch, int B, int K, int step, int stream_id, int kind,
                                    float* __restrict__ out) {
   const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -480,7 +482,11 @@ __global__ void philox_fill_kernel(uint64_t seed, int64_t first_patch, int B, in
   const uint32_t patch = static_cast<uint32_t>(first_patch + i / K), res = static_cast<uint32_t>(i % K);
   const f32x4 u = philox_uniform4(seed, patch, res, static_cast<uint32_t>(step), static_cast<uint32_t>(stream_id));
   const f32x4 r = kind == 0 ? normals_from_uniforms(u) : u;
-  reinterpret_cast<float4*>(out)[i] = make_float4(r.x, r.y, r.z, r.w);
+  if constexpr (kVec) {
+    reinterpret_cast<float4*>(out)[i] = make_float4(r.x, r.y, r.z, r.w);
+  } else {
+    out[i * 4 + 0] = r.x; out[i * 4 + 1] = r.y; out[i * 4 + 2] = r.z; out[i * 4 + 3] = r.w;
+  }
 }
 
 // ------------------------------------------------------------------ losses
@@ -1651,8 +1657,12 @@ int diffab_philox_fill(uint64_t seed, int64_t first_patch, int32_t B, int32_t K,
   const int64_t n = static_cast<int64_t>(B) * K;
   if (n == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(out, DIFFAB_ERR_ARG, "philox_fill: null pointer");
-  hipLaunchKernelGGL(philox_fill_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), seed, first_patch, B, K, step, stream_id,
-                     kind, out);
+  if (aligned16(out))
+    hipLaunchKernelGGL(philox_fill_kernel<true>, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), seed, first_patch, B, K, step,
+                       stream_id, kind, out);
+  else
+    hipLaunchKernelGGL(philox_fill_kernel<false>, dim3(blocks_for(n)), dim3(kThreads), 0, as_stream(stream), seed, first_patch, B, K, step,
+                       stream_id, kind, out);
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }

@@ -331,9 +331,17 @@ def ptr(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def aligned16(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when its storage starts on a 16-byte boundary, else a copy in an allocation of its own (which does).  A contiguous view
+    can start anywhere - a parameter inside a flat parameter vector, a batch slice at a ragged patch length - and the library's vector
+    kernels refuse such a float operand (include/diffab_hip.h, "Operand alignment"); the front end never does."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def dev_f32(t: torch.Tensor) -> torch.Tensor:
-    """float32, contiguous, on the current HIP device (copying only if needed)."""
-    return t.detach().to(device=device(), dtype=torch.float32).contiguous()
+    """float32, contiguous, 16-byte aligned, on the current HIP device (copying only if needed).  Read-only use: what the library writes
+    goes to tensors the front end allocates itself."""
+    return aligned16(t.detach().to(device=device(), dtype=torch.float32).contiguous())
 
 
 def dev_i64(t: torch.Tensor) -> torch.Tensor:
@@ -381,7 +389,9 @@ def mlp3_weights(params: Dict[str, torch.Tensor], prefix: str, keep: list) -> Ml
 
 
 class DenoiserWeightsOnDevice:
-    """Pointer table over a Denoiser's parameters (no copies when they already live on the device)."""
+    """Pointer table over a Denoiser's parameters.  No copies when they live on the device and start on 16-byte boundaries (every
+    parameter with an allocation of its own); a parameter that is a misaligned view - behind the 3-wide coordinate_denoising.4.bias of
+    a flat parameter vector, 12 of the 43 - is copied for the call (dev_f32), on every call."""
 
     def __init__(self, params: Dict[str, torch.Tensor], n_layers: int):
         self.keep: list = []

@@ -52,6 +52,42 @@
  *     diffab_ipa_layer_bwd (each NULL to skip); and the steering state logw / u_prev, 0 at the start of a run.  d_res_ctx, d_x_t,
  *     d_O_t, d x, d R, d t are written, not accumulated.  tests/test_gpu_scratch_contract.py holds every hot-path entry to this with
  *     zero, 0xFF and random fills behind guard bytes, and with the previous call's leftover.
+ *   - Operand alignment.  A contiguous tensor can start anywhere: a parameter that is a view of one flat parameter vector behind a 3-wide
+ *     bias, a batch slice x[1:3] at a ragged patch length (K = 173: +12 bytes).  DATA operands - state, contexts, masks, schedule and
+ *     IGSO3 tables, option tables, weights, cotangents, gradient buffers, outputs - need their NATURAL alignment only (4 bytes float /
+ *     int32 / uint32, 8 bytes int64 / double, 1 byte masks).  Workspaces, tapes and scratch keep the 16- or 256-byte rule stated at
+ *     their entry (a *_workspace_bytes workspace and a tape: 256 bytes, as torch allocates; the debug GEMM scratch, the PairEmbedding
+ *     tape: 16 bytes; the steering scratch: 8).  For every entry, every data operand that meets its natural alignment has exactly one of
+ *     two outcomes:
+ *       ACCEPTED - the result contract of the entry, as with 16-byte aligned operands (possibly on a slower kernel);
+ *       REFUSED  - DIFFAB_ERR_ARG, diffab_last_error() = "<entry>: operand <name> must be 16-byte aligned ...", decided on the host among
+ *                  the argument checks, before anything is enqueued: outputs, in-place state and accumulating gradient buffers are
+ *                  untouched to the bit, and the next call on the same workspace is as correct as any.
+ *     Nothing else happens: no kernel makes a vector access through a caller's pointer that the entry has not checked, and no refusal
+ *     comes after the first launch.  Which is which:
+ *       REFUSED unless 16-byte aligned - every FLOAT operand, and every buffer of a weights / grads table (`w`, `grads`, `g`), of the
+ *         entries whose kernels read and write float4: diffab_ipa_layer_fwd, diffab_denoise_step_fwd, diffab_train_step_fwd / _bwd,
+ *         diffab_denoise_step_fwd_taped / diffab_denoise_step_bwd, diffab_ipa_layer_fwd_taped / diffab_ipa_layer_bwd,
+ *         diffab_residue_embedding_fwd / _bwd, diffab_pair_embedding_fwd / _xyz_fwd / _bwd / _fwd_taped / _bwd_taped (operand names as in
+ *         the prototypes; a table's buffer is named w.res_w0, w.coord.b4, grads.layers[1].w_bias, g.mw0, ...); of
+ *         diffab_sample_loop / _ex: x, O, res_ctx, pair_ctx and the weights; of diffab_score_designs: res_ctx, pair_ctx and the weights;
+ *         of the diagnostics diffab_debug_linear128 (modes 1 and 2): X, W, bias, Y, and of diffab_debug_xstat128: X, W, Y.
+ *         (The kernel launchers behind these entries keep alignment preconditions of their own - "rowgemm128: unsupported operands",
+ *         "ipa_layer_fast: x and the projection weights must be 16-byte aligned", "gemm_nn: ... needs the aligned path" and the like.
+ *         They are internal invariants: every pointer they look at is either an operand the entry has already refused unless aligned, or
+ *         a buffer carved from a workspace or tape at offsets that keep 16 bytes.  No caller pointer reaches one of them misaligned, so
+ *         none can fire behind a launch because of an operand's alignment; one that fires is a defect of the library.)
+ *       ACCEPTED at natural alignment - everything else: the int64 and mask operands of the entries above; of diffab_sample_loop / _ex
+ *         also seq, the schedule, the IGSO3 table and every table of the options struct; of diffab_score_designs also seq, x, O, the
+ *         schedule, the table, out_terms, out_residue and the `noised` copies; and every operand of every other entry (SO(3) maps,
+ *         IGSO3 tables and draws, the three forward diffusers, diffab_philox_fill, the losses, frames, the angular encoding,
+ *         diffab_featurize_xyz, the reverse updates, the sampler's initialisers, guidance and steering, patch selection / gather /
+ *         scatter, the metrics, the refinement, diffab_debug_linear128 mode 0, diffab_debug_gemm_tn, diffab_debug_row_tiles / _plan).
+ *         Their kernels address caller memory element by element; three of them pick a vector form from the pointer itself
+ *         (diffab_philox_fill's float4 store, diffab_featurize_xyz's float2 store of the pairwise dihedrals, the 16- / 4- / 1-byte lanes
+ *         of diffab_patch_gather / _scatter) and write the same values either way.
+ *     The Python front end never refuses: _hip.dev_f32 hands the library a 16-byte aligned copy of a misaligned tensor, and everything
+ *     the library writes goes to tensors the front end allocates.  tests/test_gpu_operand_alignment.py pins this table.
  *   - empty problems (a count or extent of 0) return 0 before any pointer is looked at: an empty tensor's data pointer is NULL;
  *   - return 0 on success, a negative DIFFAB_ERR_* otherwise (never throws);
  *     diffab_last_error() gives the thread's last message.

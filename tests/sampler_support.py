@@ -6,6 +6,8 @@ Not a test module and not a conftest: test files import what they need by name. 
 (the host tests import it on machines without a GPU) - _hip.lib(), .cuda() and DiffAb are taken inside the functions that need them.
 A new sampler feature's test file starts from here and keeps per file only the fixtures whose weight seeds are its own.
 """
+import os
+import re
 import types
 
 import numpy as np
@@ -13,7 +15,7 @@ import pytest
 import torch
 
 import diffab_oracle as orc
-from conftest import maxrel
+from conftest import REPO, maxrel
 from diffab_pytorch import _hip, synthetic as syn
 
 STATE = ("seq_idx", "translations", "orientations", "generation_mask")
@@ -252,6 +254,259 @@ def check_params(named, ref, prefix, what):
         worst = max(worst, (n, r), key=lambda v: v[1])
         assert r < GTOL, (what, n, r)
     print(what, "worst parameter gradient:", worst)
+
+
+# ====================================================================== operands that are only 4-byte aligned
+def misaligned(t, nbytes):
+    """A contiguous view holding t's values (same shape, dtype and device) with data_ptr() % 16 == nbytes, cut out of a larger buffer of
+    its own.  nbytes is a multiple of the element size: 4, 8 or 12 for float32, 8 for int64, any of 1 .. 15 for masks.  What such a view is
+    in practice: a parameter behind a 3-wide bias in a flat parameter vector, a batch slice at a ragged patch length."""
+    item = t.element_size()
+    assert 0 < nbytes < 16 and nbytes % item == 0, (nbytes, t.dtype)
+    buf = torch.empty(t.numel() * item + 32, dtype=torch.uint8, device=t.device)
+    off = (nbytes - buf.data_ptr()) % 16  # (a fresh allocation is 16-byte aligned, but nothing here relies on it)
+    view = buf[off:off + t.numel() * item].view(t.dtype).view(t.shape)
+    view.copy_(t)
+    return view
+
+
+def flat_parameters(module, shift_floats=1):
+    """Rebind every parameter of `module` to a view of ONE flat float32 vector that starts `shift_floats` floats behind a 16-byte
+    boundary and packs the parameters back to back in named_parameters() order, as torch.nn.utils.parameters_to_vector and the
+    flat-parameter wrappers lay them out; the values are kept.  Returns (flat, {name: data_ptr() % 16})."""
+    ps = list(module.named_parameters())
+    total = sum(p.numel() for _, p in ps)
+    flat = misaligned(torch.zeros(total, dtype=torch.float32, device=ps[0][1].device), 4 * shift_floats)
+    at, offs = 0, {}
+    for n, p in ps:
+        v = flat[at:at + p.numel()].view(p.shape)
+        v.copy_(p.data)
+        p.data = v
+        offs[n] = p.data_ptr() % 16
+        at += p.numel()
+    return flat, offs
+
+
+def misalign_parameters(module, select, nbytes=4):
+    """Rebind the parameters whose name `select` accepts to misaligned views of their own (values kept); returns their names."""
+    hit = []
+    for n, p in module.named_parameters():
+        if select(n):
+            p.data = misaligned(p.data, nbytes)
+            hit.append(n)
+    return hit
+
+
+class MisalignedABI:
+    """Everything between __enter__ and __exit__ reaches the C ABI through pointers that are only naturally aligned.
+
+    Stands in for the library (_hip.lib(), and as the `hip` argument of a test function): an entry of `entries` is called with every
+    device pointer that was made by _hip.ptr - direct arguments and the pointer fields of structs passed by reference - replaced by the
+    pointer of a misaligned copy of the tensor (float32 at `f32` bytes behind a 16-byte boundary, 8-byte types at 8, 4-byte integers at
+    4, masks at 1), and what the call wrote is copied back into the caller's tensor behind it on the same stream.  `positions`
+    ({entry: argument indices}) restricts an entry to some of its arguments (the accepted operands of an entry that refuses others),
+    `when` ({entry: predicate of the arguments}) to some of its calls.
+    Workspaces (_hip.workspace) and uint8 scratch keep their own alignment rule and are passed as they are.  counts[entry] is the number
+    of pointers replaced, so a caller can assert that an entry really ran misaligned.  The Python wrappers, and test functions written
+    for aligned tensors, run unchanged on top of it."""
+
+    def __init__(self, entries, f32=4, positions=None, when=None):
+        import ctypes
+
+        self.C, self.entries, self.f32, self.positions = ctypes, set(entries), f32, positions or {}
+        self.when = when or {}  # {entry: predicate of the argument tuple}: the calls of an entry that are misaligned (default: all)
+        self.counts, self.tensors, self.scratch, self.saved = {}, {}, set(), None
+
+    def __enter__(self):
+        self.real = _hip.lib()
+        self.saved = (_hip.lib, _hip.ptr, _hip.workspace)
+        real_ptr, real_ws = _hip.ptr, _hip.workspace
+
+        def ptr(t):
+            if t is not None and t.is_cuda and t.numel():
+                self.tensors[t.data_ptr()] = t  # (held: the address cannot be given to another tensor meanwhile)
+            return real_ptr(t)
+
+        def workspace(nbytes):
+            w = real_ws(nbytes)
+            self.scratch.add(w.data_ptr())
+            return w
+
+        _hip.lib, _hip.ptr, _hip.workspace = (lambda: self), ptr, workspace
+        return self
+
+    def __exit__(self, *exc):
+        _hip.lib, _hip.ptr, _hip.workspace = self.saved
+        self.tensors.clear()
+        return False
+
+    def _shadow(self, address, made):
+        t = self.tensors.get(address)
+        if t is None or address in self.scratch or t.dtype == torch.uint8 or not t.is_contiguous():
+            return None
+        if address not in made:
+            off = {8: 8, 4: self.f32 if t.dtype == torch.float32 else 4, 2: 2, 1: 1}[t.element_size()]
+            made[address] = (misaligned(t, off), t)
+        return made[address][0].data_ptr()
+
+    def __getattr__(self, name):
+        fn = getattr(self.real, name)
+        if name not in self.entries:
+            return fn
+        C = self.C
+
+        def call(*args):
+            if name in self.when and not self.when[name](args):
+                return fn(*args)
+            made, restore, out = {}, [], []
+            only = self.positions.get(name)
+            for i, a in enumerate(args):
+                if only is not None and i not in only:
+                    out.append(a)
+                    continue
+                struct = getattr(a, "_obj", None) if not isinstance(a, C.c_void_p) else None
+                if struct is None and hasattr(a, "contents") and a:
+                    struct = a.contents
+                if isinstance(a, C.c_void_p) and a.value:
+                    new = self._shadow(a.value, made)
+                    out.append(a if new is None else C.c_void_p(new))
+                elif isinstance(struct, C.Structure):
+                    for field, ftype in struct._fields_:
+                        v = getattr(struct, field)
+                        if ftype is C.c_void_p and v:
+                            new = self._shadow(v, made)
+                            if new is not None:
+                                restore.append((struct, field, v))
+                                setattr(struct, field, new)
+                    out.append(a)
+                else:
+                    out.append(a)
+            rc = fn(*out)
+            for struct, field, v in restore:
+                setattr(struct, field, v)
+            for shadow, t in made.values():
+                t.copy_(shadow)
+            self.counts[name] = self.counts.get(name, 0) + len(made)
+            return rc
+
+        return call
+
+
+# ====================================================================== the operand-alignment table (include/diffab_hip.h, "Operand alignment")
+# Mirrored from the header: tests/test_operand_alignment_host.py drives it through the C ABI without a device,
+# tests/test_gpu_operand_alignment.py on the device.
+NO_DATA, ACCEPTS, REFUSES = "no data operand", "accepts natural alignment", "refuses misaligned float operands"
+
+ENTRIES = {n: NO_DATA for n in (
+    "diffab_version", "diffab_last_error", "diffab_device_ok", "diffab_kernel_timer_enable", "diffab_kernel_timer_read",
+    "diffab_debug_set_attn_stamps", "diffab_debug_set_attn_variant", "diffab_debug_set_module_stagger", "diffab_debug_set_module_stamps",
+    "diffab_set_stream_guard", "diffab_denoise_workspace_bytes", "diffab_sample_workspace_bytes", "diffab_sample_shared_workspace_bytes",
+    "diffab_train_tape_bytes", "diffab_train_workspace_bytes", "diffab_ipa_layer_tape_bytes", "diffab_ipa_layer_bwd_workspace_bytes",
+    "diffab_residue_embedding_workspace_bytes", "diffab_pair_embedding_workspace_bytes", "diffab_residue_embedding_bwd_workspace_bytes",
+    "diffab_pair_embedding_bwd_workspace_bytes", "diffab_pair_embedding_tape_bytes", "diffab_score_workspace_bytes")}
+ENTRIES.update({n: ACCEPTS for n in (
+    "diffab_debug_row_tiles", "diffab_debug_row_plan", "diffab_debug_gemm_tn", "diffab_so3_log", "diffab_so3_exp",
+    "diffab_so3_matrix_to_rotvec", "diffab_so3_rotvec_to_matrix", "diffab_so3_scale_rot", "diffab_igso3_table_build",
+    "diffab_igso3_table_build_accurate", "diffab_igso3_cdf_build", "diffab_igso3_sample", "diffab_igso3_bins_without_replacement",
+    "diffab_igso3_sample_bins", "diffab_weighted_multinomial", "diffab_seq_forward_prob", "diffab_seq_posterior",
+    "diffab_categorical_sample", "diffab_coord_forward", "diffab_orient_forward", "diffab_philox_fill", "diffab_losses_fwd",
+    "diffab_orientation_loss", "diffab_orientation_loss_bwd", "diffab_frames_apply", "diffab_frames_invert", "diffab_frames_bwd",
+    "diffab_angular_encoding", "diffab_angular_encoding_bwd", "diffab_featurize_xyz", "diffab_patch_select", "diffab_patch_gather",
+    "diffab_patch_scatter", "diffab_metrics_vs_native", "diffab_metrics_pairwise", "diffab_metrics_select_diverse",
+    "diffab_metrics_backbone", "diffab_metrics_contacts", "diffab_metrics_ensemble", "diffab_metrics_similarity", "diffab_refine_backbone",
+    "diffab_reverse_update", "diffab_reverse_update_jump", "diffab_sample_init", "diffab_sample_init_ex", "diffab_sample_init_noised",
+    "diffab_guidance_energy", "diffab_steer_energy", "diffab_steer_resample", "diffab_steer_gather")})
+
+# name:kind in prototype order.  f: float operand, refused unless 16-byte aligned; fa: float operand, accepted; i64, m: accepted;
+# W / G, LW / LG, RW / RG, PW / PG: denoiser, layer, ResidueEmbedding, PairEmbedding weights / gradients (every buffer refused);
+# S, I: schedule and IGSO3 structs (their tables accepted); N: the optional struct of noised copies (accepted; the host test passes
+# NULL); ws: workspace / tape / scratch; a number or null: passed as it is.
+_DEN_IN = "seq_t:i64 x_t:f O_t:f res_ctx:f pair_ctx:f beta:f"
+_PAIR_IN = "pairwise_dihedrals:f residue_idx:i64 stride:0 chain_idx:i64 atom_mask:f sequence_context_mask:m"
+_LOOP = ("d:dims w:W s:S rev_tab:I seq:i64 x:f O:f res_ctx:f pair_ctx:f gen_mask:m seed:1 first_patch:0 t_start:5 t_stop:4 "
+         "workspace:ws workspace_bytes:0 flags:0")
+SIGNATURES = {
+    "diffab_ipa_layer_fwd": "d:dims w:LW x:f e:f R:f t:f y:f workspace:ws workspace_bytes:0 flags:0 stream:null",
+    "diffab_denoise_step_fwd": f"d:dims w:W {_DEN_IN} out_eps:f out_O0:f out_posterior:f out_logits:f out_res_emb:f workspace:ws "
+                               "workspace_bytes:0 flags:0 stream:null",
+    "diffab_train_step_fwd": f"d:dims w:W {_DEN_IN} true_post:f true_eps:f true_O0:f gen_mask:m res_mask:m out_eps:f out_O0:f "
+                             "out_posterior:f losses3:f tape:ws tape_bytes:0 flags:0 stream:null",
+    "diffab_train_step_bwd": "d:dims w:W grads:G seq_t:i64 x_t:f O_t:f pair_ctx:f out_eps:f out_O0:f out_posterior:f true_post:f true_eps:f "
+                             "true_O0:f gen_mask:m res_mask:m upstream3:f d_res_ctx:f d_pair_ctx:f tape:ws tape_bytes:0 workspace:ws "
+                             "workspace_bytes:0 stream:null",
+    "diffab_denoise_step_fwd_taped": f"d:dims w:W {_DEN_IN} out_eps:f out_O0:f out_posterior:f tape:ws tape_bytes:0 flags:0 stream:null",
+    "diffab_denoise_step_bwd": "d:dims w:W grads:G seq_t:i64 x_t:f O_t:f pair_ctx:f out_posterior:f d_eps:f d_O0:f d_posterior:f "
+                               "d_res_ctx:f d_pair_ctx:f d_x_t:f d_O_t:f tape:ws tape_bytes:0 workspace:ws workspace_bytes:0 stream:null",
+    "diffab_ipa_layer_fwd_taped": "d:dims w:LW x:f e:f R:f t:f y:f tape:ws tape_bytes:0 flags:0 stream:null",
+    "diffab_ipa_layer_bwd": "d:dims w:LW grads:LG e:f R:f t:f dy:f dx:f d_e:f d_R:f d_t:f tape:ws tape_bytes:0 workspace:ws "
+                            "workspace_bytes:0 stream:null",
+    "diffab_sample_loop": _LOOP + " stream:null",
+    "diffab_sample_loop_ex": _LOOP + " options:null stream:null",
+    "diffab_score_designs": "d:dims w:W s:S fwd_tab:I seq:i64 x:fa O:fa gen_mask:m res_mask:m n_designs:1 res_ctx:f pair_ctx:f n_ctx:1 "
+                            "ctx_of_design:null t_list:tlist n_t:1 n_draws:1 seed:1 first_design:0 out_terms:fa out_residue:fa noised:N "
+                            "workspace:ws workspace_bytes:0 flags:0 stream:null",
+    "diffab_residue_embedding_fwd": "d:cdims w:RW seq_idx:i64 xyz:f orientations:f dihedrals:f chain_idx:i64 atom_mask:f "
+                                    "structure_context_mask:m sequence_context_mask:m out:f workspace:ws workspace_bytes:0 stream:null",
+    "diffab_residue_embedding_bwd": "d:cdims w:RW g:RG seq_idx:i64 xyz:f orientations:f dihedrals:f chain_idx:i64 atom_mask:f "
+                                    "structure_context_mask:m sequence_context_mask:m d_out:f workspace:ws workspace_bytes:0 stream:null",
+    "diffab_pair_embedding_fwd": f"d:cdims w:PW seq_idx:i64 distmat:f {_PAIR_IN} out:f workspace:ws workspace_bytes:0 stream:null",
+    "diffab_pair_embedding_xyz_fwd": f"d:cdims w:PW seq_idx:i64 xyz:f {_PAIR_IN} out:f workspace:ws workspace_bytes:0 stream:null",
+    "diffab_pair_embedding_bwd": f"d:cdims w:PW g:PG seq_idx:i64 distmat:f xyz:null {_PAIR_IN} d_out:f workspace:ws workspace_bytes:0 "
+                                 "stream:null",
+    "diffab_pair_embedding_fwd_taped": f"d:cdims w:PW seq_idx:i64 distmat:f xyz:null {_PAIR_IN} out:f tape:ws tape_bytes:0 workspace:ws "
+                                       "workspace_bytes:0 stream:null",
+    "diffab_pair_embedding_bwd_taped": f"d:cdims w:PW g:PG seq_idx:i64 distmat:f xyz:null {_PAIR_IN} d_out:f tape:ws tape_bytes:0 "
+                                       "workspace:ws workspace_bytes:0 stream:null",
+}
+ENTRIES.update({n: REFUSES for n in SIGNATURES})
+# The two diagnostics that refuse (their own entry comments give the rule; the messages of their scratch checks come first, so the host
+# test does not drive them): X, W, bias, Y of diffab_debug_linear128 in modes 1 and 2, X, W, Y of diffab_debug_xstat128.
+DEBUG_REFUSES = {"diffab_debug_linear128": ("X", "W", "bias", "Y"), "diffab_debug_xstat128": ("X", "W", "Y")}
+ENTRIES.update({n: REFUSES for n in DEBUG_REFUSES})
+# the name an entry gives itself in its messages, where it is not its symbol without "diffab_"
+MESSAGE_NAME = {"diffab_sample_loop_ex": "sample_loop", "diffab_pair_embedding_xyz_fwd": "pair_embedding_fwd"}
+
+LAYER_FIELDS = tuple(n for n, _ in _hip.IpaLayerWeights._fields_)
+MLP3_FIELDS = tuple(n for n, _ in _hip.Mlp3Weights._fields_)
+TABLE_FIELDS = {"RW": tuple(n for n, _ in _hip.ResidueEmbWeights._fields_), "PW": tuple(n for n, _ in _hip.PairEmbWeights._fields_)}
+TABLE_FIELDS["RG"], TABLE_FIELDS["PG"] = TABLE_FIELDS["RW"], TABLE_FIELDS["PW"]
+HOST_NL = 2  # layers of the tables the host test builds
+
+
+def signature(entry):
+    return [tuple(a.split(":")) for a in SIGNATURES[entry].split()]
+
+
+def table_operands(name, kind, NL=HOST_NL):
+    """The buffers of a weight / gradient table as the library names them: w.res_w0, grads.coord.b4, w.layers[1].w_bias, g.mw0."""
+    if kind in ("W", "G"):
+        base = [f"{name}.{f}" for f in ("seq_emb", "res_w0", "res_b0", "res_w2", "res_b2")]
+        heads = [f"{name}.{h}.{f}" for h in ("coord", "orient", "seq") for f in MLP3_FIELDS]
+        return base + heads + [f"{name}.layers[{l}].{f}" for l in range(NL) for f in LAYER_FIELDS]
+    if kind in ("LW", "LG"):
+        return [f"{name}.layers[0].{f}" for f in LAYER_FIELDS]
+    return [f"{name}.{f}" for f in TABLE_FIELDS[kind]]
+
+
+def refused(NL=HOST_NL):
+    """{entry: operand names} - every (entry, operand) pair that may be refused, as the header lists them."""
+    out = {}
+    for entry in SIGNATURES:
+        ops = []
+        for name, kind in signature(entry):
+            if kind == "f":
+                ops.append(name)
+            elif kind in ("W", "G", "LW", "LG", "RW", "RG", "PW", "PG"):
+                ops += table_operands(name, kind, NL)
+        out[entry] = ops
+    return out
+
+
+def header_exports():
+    src = open(os.path.join(REPO, "include", "diffab_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"\b(diffab_[a-z0-9_]+)\s*\(", src)))
+
 
 
 # ====================================================================== host side: argument checks before the library
