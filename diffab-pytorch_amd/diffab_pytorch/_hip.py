@@ -1,4 +1,4 @@
-"""ctypes binding of libdiffab_hip.so (C ABI: include/diffab_hip.h).
+"""ctypes binding of libdiffab_hip.so (C ABI: include/diffab_hip.h and include/diffab_hip_analysis.h).
 
 torch is used here only as the owner of device memory and streams: every call
 passes raw device pointers, sizes and the current HIP stream handle.  There is
@@ -281,6 +281,18 @@ SYMBOLS = {
                                        _u32, _fp]),
 }
 
+# every symbol include/diffab_hip_analysis.h declares (the model-free analysis entries added after the export list of diffab_hip.h was
+# pinned): same library, same conventions, a table of its own
+ANALYSIS_SYMBOLS = {
+    # (points, valid, point_radius (HOST float[P]), context_points, context_valid, context_radius (nullable), generation_mask,
+    #  residue_mask (nullable), antigen_mask (nullable), hotspot_mask (nullable), sphere, rows, group_size, K, P, A, S, probe,
+    #  context_radius_default, free_points, bound_points, design_buried_points, free_area, bound_area, design_buried_area, residue_buried,
+    #  bsa_paratope, bsa_epitope, bsa_design_epitope, n_paratope_buried, n_epitope_buried, n_hotspot, n_hotspot_buried,
+    #  hotspot_buried_area (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_surface": (C.c_int, [_fp, _fp, C.POINTER(C.c_float)] + [_fp] * 8 + [_i32] * 6 + [C.c_float] * 2 + [_fp] * 15
+                               + [_fp, _sz, _fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -293,8 +305,8 @@ def load_library() -> C.CDLL:
                 f"{LIB_PATH} is missing - build it with `make -C diffab-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()); there is no CPU fallback for this path")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)  # AttributeError if the header and the library drift apart
+        for name, (res, args) in list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()):
+            fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib

@@ -5,6 +5,8 @@
 ``select_diverse``  greedy farthest-point choice of m designs per patch from such a matrix;
 ``backbone``        per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
 ``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
+``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
+                    each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
 ``ensemble``        per patch: its N designs as a distribution - amino-acid frequencies, entropy, consensus, mean structure, RMSF, and
                     how typical each design is of its siblings (DESIGN section 4.16, ``csrc/ensemble_kernels.hip``);
 ``similarity``      per design, without a superposition: lDDT against the native per residue, per design and per segment, and the
@@ -14,12 +16,14 @@ Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` retur
 (rows,K,3), ``orientations`` (rows,K,3,3) with ``rows = G * group_size``, row ``g * group_size + r`` = design r of patch g - and the masks
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
 the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
-``_similarity`` in ``include/diffab_hip.h``; every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``,
-``csrc/geometry_kernels.hip`` (the filters), ``csrc/ensemble_kernels.hip`` and ``csrc/similarity_kernels.hip``, and
-there is no torch fallback.
+``_similarity`` in ``include/diffab_hip.h`` and of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h``; every number is
+computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters),
+``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip`` and ``csrc/surface_kernels.hip``, and there is no torch fallback.
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 import math
 from typing import Dict, Optional, Sequence
 
@@ -42,6 +46,9 @@ LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)  # Angstrom
 CONTACT_DISTANCE = {"ca": 8.0, "backbone": 5.0}  # similarity's default per atom set
 PEPTIDE_BOND = 1.329  # Angstrom, C(i) - N(i+1)
 GLY = AA3.index("GLY")
+SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256  # DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
+# surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
+ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
 
 
 def _is_int(v) -> bool:
@@ -227,6 +234,34 @@ def _check_patch_mask(who: str, name: str, m, G: int, K: int) -> None:
         raise ValueError(f"{who}: {name} is {tuple(m.shape)}, expected {(G, K)} (one row per patch)")
 
 
+def _check_atoms(who: str, atoms) -> tuple:
+    if isinstance(atoms, str) or not isinstance(atoms, Sequence) or not 1 <= len(atoms) <= len(BACKBONE_ATOMS) \
+            or any(a not in BACKBONE_ATOMS for a in atoms) or len(set(atoms)) != len(atoms):
+        raise ValueError(f"{who}: atoms must be a sequence of distinct names from {BACKBONE_ATOMS}, got {atoms!r}")
+    return tuple(atoms)
+
+
+def _check_context(who: str, context, G: int, K: int) -> int:
+    """A patch's real atoms, xyz (G,K,A,3) and atom_mask (G,K,A) -> A."""
+    if not isinstance(context, dict) or not isinstance(context.get("xyz"), torch.Tensor) or not isinstance(context.get("atom_mask"), torch.Tensor):
+        raise ValueError(f"{who}: context must be a dict with xyz (G,K,A,3) and atom_mask (G,K,A)")
+    xyz, am = context["xyz"], context["atom_mask"]
+    if not xyz.is_floating_point() or xyz.dim() != 4 or tuple(xyz.shape[:2]) != (G, K) or xyz.shape[3] != 3:
+        raise ValueError(f"{who}: context['xyz'] is {tuple(xyz.shape)} {xyz.dtype}, expected a float tensor {(G, K, 'A', 3)}")
+    A = int(xyz.shape[2])
+    if A < 1 or A > MAX_CONTEXT_ATOMS:
+        raise ValueError(f"{who}: context['xyz'] has A = {A} atoms per residue, outside [1, {MAX_CONTEXT_ATOMS}]")
+    if am.is_complex() or tuple(am.shape) != (G, K, A):  # (bool, or the reference batch's 0 / 1 numbers)
+        raise ValueError(f"{who}: context['atom_mask'] is {tuple(am.shape)} {am.dtype}, expected a mask {(G, K, A)}")
+    return A
+
+
+def _valid_word(atom_mask: torch.Tensor, A: int, dev) -> torch.Tensor:
+    """atom_mask (G,K,A) -> (G,K) int32 holding the A bits of a uint32."""
+    word = (_hip.dev_mask(atom_mask).to(torch.int64) << torch.arange(A, device=dev)).sum(-1)
+    return torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32).contiguous()
+
+
 def backbone_workspace_bytes(G: int, K: int) -> int:
     """DIFFAB_METRICS_BACKBONE_WORKSPACE_BYTES of include/diffab_hip.h."""
     return G * K * 8 + 1024
@@ -299,10 +334,7 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
     (``include/diffab_hip.h``).  One C-ABI call; results on the device of ``designs['seq_idx']``; ValueError before any device work."""
     who = "metrics.contacts()"
     rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
-    if isinstance(atoms, str) or not isinstance(atoms, Sequence) or not 1 <= len(atoms) <= len(BACKBONE_ATOMS) \
-            or any(a not in BACKBONE_ATOMS for a in atoms) or len(set(atoms)) != len(atoms):
-        raise ValueError(f"{who}: atoms must be a sequence of distinct names from {BACKBONE_ATOMS}, got {atoms!r}")
-    atoms = tuple(atoms)
+    atoms = _check_atoms(who, atoms)
     clash = _check_distance(who, "clash_distance", clash_distance)
     contact = _check_distance(who, "contact_distance", contact_distance)
     if antigen_mask is not None:
@@ -312,16 +344,7 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
             raise ValueError(f"{who}: hotspot_mask needs an antigen_mask")
         _check_patch_mask(who, "hotspot_mask", hotspot_mask, G, K)
     if context is not None:
-        if not isinstance(context, dict) or not isinstance(context.get("xyz"), torch.Tensor) or not isinstance(context.get("atom_mask"), torch.Tensor):
-            raise ValueError(f"{who}: context must be a dict with xyz (G,K,A,3) and atom_mask (G,K,A)")
-        xyz, am = context["xyz"], context["atom_mask"]
-        if not xyz.is_floating_point() or xyz.dim() != 4 or tuple(xyz.shape[:2]) != (G, K) or xyz.shape[3] != 3:
-            raise ValueError(f"{who}: context['xyz'] is {tuple(xyz.shape)} {xyz.dtype}, expected a float tensor {(G, K, 'A', 3)}")
-        A = int(xyz.shape[2])
-        if A < 1 or A > MAX_CONTEXT_ATOMS:
-            raise ValueError(f"{who}: context['xyz'] has A = {A} atoms per residue, outside [1, {MAX_CONTEXT_ATOMS}]")
-        if am.is_complex() or tuple(am.shape) != (G, K, A):  # (bool, or the reference batch's 0 / 1 numbers)
-            raise ValueError(f"{who}: context['atom_mask'] is {tuple(am.shape)} {am.dtype}, expected a mask {(G, K, A)}")
+        A = _check_context(who, context, G, K)
     chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
 
     lib = _hip.lib()
@@ -335,8 +358,7 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
         A, cvalid = P, cbits.to(torch.int32).contiguous()
     else:
         cpts = _hip.dev_f32(context["xyz"])
-        word = (_hip.dev_mask(context["atom_mask"]).to(torch.int64) << torch.arange(A, device=dev)).sum(-1)
-        cvalid = torch.where(word >= 2 ** 31, word - 2 ** 32, word).to(torch.int32).contiguous()  # the 32 bits of a uint32
+        cvalid = _valid_word(context["atom_mask"], A, dev)
     gm = _hip.dev_mask(generation_mask)
     rm, ag, hs = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask, hotspot_mask))
     chain, ridx = chain.to(dev), ridx.to(dev)
@@ -358,6 +380,131 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
                                            _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, P, A, clash, contact,
                                            *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
                "diffab_metrics_contacts")
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ accessible and buried surface
+@functools.lru_cache(maxsize=None)
+def _sphere_table(n: int) -> torch.Tensor:
+    golden = math.pi * (3.0 - math.sqrt(5.0))
+    rows = []
+    for k in range(n):
+        z = 1.0 - (2 * k + 1) / n
+        r = math.sqrt(1.0 - z * z)
+        rows.append((r * math.cos(k * golden), r * math.sin(k * golden), z))
+    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
+def sphere_points(n: int) -> torch.Tensor:
+    """(n,3) fp32 unit vectors on the golden spiral: z_k = 1 - (2k+1)/n, phi_k = k pi (3 - sqrt 5), u_k = (sqrt(1 - z_k^2) cos phi_k,
+    sqrt(1 - z_k^2) sin phi_k, z_k), built in float64 and rounded to fp32.  The table ``surface`` hands the kernels."""
+    if not _is_int(n) or not SURFACE_MIN_POINTS <= n <= SURFACE_MAX_POINTS:
+        raise ValueError(f"metrics.sphere_points(): n must be an int in [{SURFACE_MIN_POINTS}, {SURFACE_MAX_POINTS}], got {n!r}")
+    return _sphere_table(n).clone()
+
+
+def surface_workspace_bytes(G: int, K: int, A: int, S: int) -> int:
+    """DIFFAB_METRICS_SURFACE_WORKSPACE_BYTES of include/diffab_hip_analysis.h."""
+    return G * K * (A * (16 + 16 * ((S + 63) // 64)) + 20) + G * 32 + 2048
+
+
+def surface(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
+            antigen_mask: Optional[torch.Tensor] = None, hotspot_mask: Optional[torch.Tensor] = None,
+            residue_mask: Optional[torch.Tensor] = None, group_size: int = 1, probe: float = 1.4, n_points: int = 96,
+            atoms: Sequence[str] = BACKBONE_ATOMS, atom_radius=None, context_radius: float = 1.8) -> Dict[str, torch.Tensor]:
+    """Solvent-accessible surface of the generated residues and of the antigen, and the area they bury on each other (Shrake-Rupley:
+    ``n_points`` points of ``sphere_points`` on every atom's sphere of radius + ``probe``; a point another atom's sphere holds is covered).
+    Atoms as in ``contacts``: a generated residue has the frame atoms ``atoms`` of its own row (no CB where its token is Gly), a
+    non-generated residue the patch's real atoms ``context['xyz']`` / ``context['atom_mask']``, shared by the designs of the patch -
+    without ``context``, the frame atoms of the first row of its group.  Radii in Angstrom: the frame atoms take ``atom_radius`` (one
+    number per name of ``atoms``, as a sequence or a dict; default the united-atom values ``ATOM_RADIUS`` - N 1.65, CA 1.87, C 1.76,
+    O 1.40, CB 1.87, this project's own choice, no parity with any tool is claimed); the context atoms take ``context['atom_radius']``
+    (G,K,A) where given, else the one number ``context_radius`` (``read_pdb`` keeps no element per atom slot) - or, without ``context``,
+    the frame atoms' radii.  Non-generated residues are antigen where ``antigen_mask`` (G,K) is set and framework otherwise; framework
+    atoms only occlude.  Chain neighbours cover like any other atom.
+
+    A point of a generated atom is free when nothing of the antibody (the row's generated residues and the framework) covers it, bound
+    when the antigen does not cover it either.  A point of an antigen atom is free when no antigen atom covers it, bound when nothing
+    covers it, design-buried when only the generated residues cover it.  Returned per residue (rows,K): ``free_points`` (int32),
+    ``free_area`` (fp32, A^2 = sum over atoms of points * 4 pi R^2 / n_points) - and, with ``antigen_mask``: ``bound_points``,
+    ``design_buried_points``, ``bound_area``, ``design_buried_area`` and ``residue_buried`` (free - bound on a generated residue, the
+    design-buried area on an antigen residue; ready as ``b_factor`` of ``io.write_pdb``); per row (rows,): ``bsa_paratope`` and
+    ``bsa_epitope`` (free - bound area summed over the generated / the antigen residues), ``bsa_design_epitope`` (the design-buried
+    area), ``n_paratope_buried`` (generated residues that lose a point), ``n_epitope_buried`` (antigen residues with a design-buried
+    point); with ``hotspot_mask`` (a subset of the antigen) ``n_hotspot``, ``n_hotspot_buried`` and ``hotspot_buried_area``.  A row
+    whose patch has no generated residue gives zeros.  Every count is an exact function of the fp32 atoms
+    (``include/diffab_hip_analysis.h``).  One C-ABI call; results on the device of ``designs['seq_idx']``; ValueError before any
+    device work."""
+    who = "metrics.surface()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    atoms = _check_atoms(who, atoms)
+    probe = _check_distance(who, "probe", probe)
+    ctx_default = _check_distance(who, "context_radius", context_radius)
+    if not _is_int(n_points) or not SURFACE_MIN_POINTS <= n_points <= SURFACE_MAX_POINTS:
+        raise ValueError(f"{who}: n_points must be an int in [{SURFACE_MIN_POINTS}, {SURFACE_MAX_POINTS}], got {n_points!r}")
+    if atom_radius is None:
+        radii = [ATOM_RADIUS[a] for a in atoms]
+    elif isinstance(atom_radius, dict):
+        if any(a not in atom_radius for a in atoms):
+            raise ValueError(f"{who}: atom_radius must give a radius for every name of atoms = {atoms}, got {sorted(atom_radius)}")
+        radii = [atom_radius[a] for a in atoms]
+    else:
+        if isinstance(atom_radius, (str, torch.Tensor)) or not isinstance(atom_radius, Sequence) or len(atom_radius) != len(atoms):
+            raise ValueError(f"{who}: atom_radius must be a dict or a sequence of {len(atoms)} numbers, one per name of atoms, got {atom_radius!r}")
+        radii = list(atom_radius)
+    radii = [_check_distance(who, f"atom_radius of {a}", r) for a, r in zip(atoms, radii)]
+    if antigen_mask is not None:
+        _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    if hotspot_mask is not None:
+        if antigen_mask is None:
+            raise ValueError(f"{who}: hotspot_mask needs an antigen_mask")
+        _check_patch_mask(who, "hotspot_mask", hotspot_mask, G, K)
+    ctx_radius = None
+    if context is not None:
+        A = _check_context(who, context, G, K)
+        ctx_radius = context.get("atom_radius")
+        if ctx_radius is not None:
+            if not isinstance(ctx_radius, torch.Tensor) or not ctx_radius.is_floating_point() or tuple(ctx_radius.shape) != (G, K, A):
+                raise ValueError(f"{who}: context['atom_radius'] must be a float tensor {(G, K, A)}")
+            if not bool(torch.isfinite(ctx_radius).all()) or bool((ctx_radius < 0).any()):
+                raise ValueError(f"{who}: context['atom_radius'] must be finite and >= 0 everywhere")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    P = len(atoms)
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    pts, valid = _frame_atoms(seq, x, O, atoms)
+    if context is None:
+        first = torch.arange(G, device=dev) * group_size
+        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
+        A, cvalid = P, cbits.to(torch.int32).contiguous()
+        crad = torch.tensor(radii, dtype=torch.float32, device=dev).expand(G, K, P).contiguous()
+    else:
+        cpts = _hip.dev_f32(context["xyz"])
+        cvalid = _valid_word(context["atom_mask"], A, dev)
+        crad = None if ctx_radius is None else _hip.dev_f32(ctx_radius)
+    gm = _hip.dev_mask(generation_mask)
+    rm, ag, hs = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask, hotspot_mask))
+    table = _hip.dev_f32(_sphere_table(n_points))
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = {"free_points": i32(rows, K), "free_area": f32(rows, K)}
+    if ag is not None:
+        out.update(bound_points=i32(rows, K), design_buried_points=i32(rows, K), bound_area=f32(rows, K), design_buried_area=f32(rows, K),
+                   residue_buried=f32(rows, K), bsa_paratope=f32(rows), bsa_epitope=f32(rows), bsa_design_epitope=f32(rows),
+                   n_paratope_buried=i32(rows), n_epitope_buried=i32(rows))
+    if hs is not None:
+        out.update(n_hotspot=i32(rows), n_hotspot_buried=i32(rows), hotspot_buried_area=f32(rows))
+    nbytes = surface_workspace_bytes(G, K, A, n_points)
+    ws = _hip.workspace(nbytes)
+    order = ("free_points", "bound_points", "design_buried_points", "free_area", "bound_area", "design_buried_area", "residue_buried",
+             "bsa_paratope", "bsa_epitope", "bsa_design_epitope", "n_paratope_buried", "n_epitope_buried", "n_hotspot", "n_hotspot_buried",
+             "hotspot_buried_area")
+    host_radii = (ctypes.c_float * P)(*radii)
+    _hip.check(lib.diffab_metrics_surface(_hip.ptr(pts), _hip.ptr(valid), host_radii, _hip.ptr(cpts), _hip.ptr(cvalid), _hip.ptr(crad),
+                                          _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(table), rows, group_size, K, P, A,
+                                          n_points, probe, ctx_default, *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes,
+                                          _hip.stream_ptr()), "diffab_metrics_surface")
     return {k: v.to(out_dev) for k, v in out.items()}
 
 
