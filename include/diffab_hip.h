@@ -88,6 +88,22 @@
  *         of diffab_patch_gather / _scatter) and write the same values either way.
  *     The Python front end never refuses: _hip.dev_f32 hands the library a 16-byte aligned copy of a misaligned tensor, and everything
  *     the library writes goes to tensors the front end allocates.  tests/test_gpu_operand_alignment.py pins this table.
+ *   - Operand extents.  An operand's EXTENT is the shape its prototype comment gives, at the dims of the call (x_t: B K 3 floats; a
+ *     table's buffer: its parameter's shape; out_terms: n_designs n_t n_draws 3), from the pointer, contiguous.  Behind it may lie a
+ *     neighbour - the next gradient of a flat vector, the next rows of the batch an operand is a slice of, the rest of a larger result -
+ *     so an entry writes NOTHING outside the extents of the operands it declares writable.  Writable are: the non-const pointer
+ *     parameters; the non-const pointer fields of the option and record structs (diffab_sample_record, diffab_sample_steps.plan_dev,
+ *     diffab_sample_guidance.shift_dev, the steering state and scratch, diffab_score_noised); every buffer of a `grads` / `g` table (the
+ *     weights struct again, so its fields read const float*: accumulated into all the same); and the in-place state (seq, x, O of the
+ *     samplers, the updates, the initialisers and diffab_steer_gather; logw / u_prev of diffab_steer_resample).  Every const operand is
+ *     bit-for-bit unchanged on return: the inputs, the buffers of `w`, the schedule and IGSO3 tables, the option tables (allowed, chain,
+ *     residue_idx, residue_mask, the temperature tables), a tape in its backward.  An entry may ISSUE a load past the end of an operand
+ *     only where the address is clamped inside it (a ragged last tile reads its last valid row again); no result depends on memory
+ *     outside an operand, whatever it holds.  Two operands may alias only where an entry says so (diffab_reverse_update_jump:
+ *     posterior / r_out).  tests/test_gpu_operand_extents.py holds every entry with a data operand to this: its own reference test
+ *     again with every operand between two 64 KiB guards, under two guard fills (NaN / 0, and 1), the guards and the const operands
+ *     compared to the byte afterwards; tests/sampler_support.py WRITES is the table of writable operands, checked against this header
+ *     and include/diffab_hip_analysis.h by tests/test_operand_extents_host.py.
  *   - empty problems (a count or extent of 0) return 0 before any pointer is looked at: an empty tensor's data pointer is NULL;
  *   - return 0 on success, a negative DIFFAB_ERR_* otherwise (never throws);
  *     diffab_last_error() gives the thread's last message.

@@ -17,6 +17,7 @@ import torch
 import diffab_oracle as orc
 from conftest import REPO, maxrel
 from diffab_pytorch import _hip, synthetic as syn
+from scratch_poison import GuardDamaged, raw_bytes
 
 STATE = ("seq_idx", "translations", "orientations", "generation_mask")
 CTX = ("res_context_emb", "pair_context_emb")
@@ -270,21 +271,55 @@ def misaligned(t, nbytes):
     return view
 
 
-def flat_parameters(module, shift_floats=1):
+def flat_parameters(module, shift_floats=1, grads=None, align_floats=1):
     """Rebind every parameter of `module` to a view of ONE flat float32 vector that starts `shift_floats` floats behind a 16-byte
     boundary and packs the parameters back to back in named_parameters() order, as torch.nn.utils.parameters_to_vector and the
-    flat-parameter wrappers lay them out; the values are kept.  Returns (flat, {name: data_ptr() % 16})."""
+    flat-parameter wrappers lay them out; the values are kept.  Returns (flat, {name: data_ptr() % 16}).
+    align_floats: every view starts at a multiple of that many floats from the vector's start (4 with shift_floats = 0: every view on a
+    16-byte boundary, which the entries that take weight and gradient tables ask for; a view whose size is a multiple of 4 floats is
+    then followed directly by its neighbour, a 3-wide bias by one float of padding).
+    grads=<fill>: every .grad becomes a zero-filled view of a second flat vector of the same layout (what a flat-gradient wrapper
+    hands the optimiser).  Every byte of both vectors' storage outside the views - the padding, and at least 16 bytes in front of the
+    first and behind the last view - holds the float `grads`.  Returns (flat, offsets, flat_grads, outside): outside(flat_vector) is
+    the flat uint8 tensor of those bytes."""
     ps = list(module.named_parameters())
-    total = sum(p.numel() for _, p in ps)
-    flat = misaligned(torch.zeros(total, dtype=torch.float32, device=ps[0][1].device), 4 * shift_floats)
-    at, offs = 0, {}
-    for n, p in ps:
+    starts, total = [], 0
+    for _, p in ps:
+        total = (total + align_floats - 1) // align_floats * align_floats
+        starts.append(total)
+        total += p.numel()
+    dev = ps[0][1].device
+
+    def vector():
+        if grads is None:
+            return misaligned(torch.zeros(total, dtype=torch.float32, device=dev), 4 * shift_floats)
+        buf = torch.empty(4 * total + 64, dtype=torch.uint8, device=dev)  # (a multiple of 4 bytes; a fresh allocation is 4-byte aligned)
+        buf.view(torch.float32).fill_(grads)
+        off = 16 + (4 * shift_floats - buf.data_ptr()) % 16
+        return buf[off:off + 4 * total].view(torch.float32)
+
+    flat, gflat = vector(), None if grads is None else vector()
+    inside = torch.zeros(total, dtype=torch.bool, device=dev)
+    offs = {}
+    for at, (n, p) in zip(starts, ps):
         v = flat[at:at + p.numel()].view(p.shape)
         v.copy_(p.data)
         p.data = v
         offs[n] = p.data_ptr() % 16
-        at += p.numel()
-    return flat, offs
+        if gflat is not None:
+            p.grad = gflat[at:at + p.numel()].view(p.shape).zero_()
+            inside[at:at + p.numel()] = True
+    if grads is None:
+        return flat, offs
+
+    def outside(vector):
+        raw = raw_bytes(vector)
+        keep = torch.ones(raw.numel(), dtype=torch.bool, device=dev)
+        lo = 4 * vector.storage_offset()  # (of the float32 view, in floats)
+        keep[lo:lo + 4 * total] = ~inside.repeat_interleave(4)
+        return raw[keep]
+
+    return flat, offs, gflat, outside
 
 
 def misalign_parameters(module, select, nbytes=4):
@@ -315,7 +350,7 @@ class MisalignedABI:
 
         self.C, self.entries, self.f32, self.positions = ctypes, set(entries), f32, positions or {}
         self.when = when or {}  # {entry: predicate of the argument tuple}: the calls of an entry that are misaligned (default: all)
-        self.counts, self.tensors, self.scratch, self.saved = {}, {}, set(), None
+        self.counts, self.tensors, self.scratch, self.saved = {}, {}, {}, None
 
     def __enter__(self):
         self.real = _hip.lib()
@@ -325,11 +360,13 @@ class MisalignedABI:
         def ptr(t):
             if t is not None and t.is_cuda and t.numel():
                 self.tensors[t.data_ptr()] = t  # (held: the address cannot be given to another tensor meanwhile)
+                if self.scratch.get(t.data_ptr()) not in (None, t.numel() if t.dtype == torch.uint8 else -1):
+                    del self.scratch[t.data_ptr()]  # a freed workspace's address, given to an operand of a later call
             return real_ptr(t)
 
         def workspace(nbytes):
             w = real_ws(nbytes)
-            self.scratch.add(w.data_ptr())
+            self.scratch[w.data_ptr()] = w.numel()
             return w
 
         _hip.lib, _hip.ptr, _hip.workspace = (lambda: self), ptr, workspace
@@ -415,7 +452,8 @@ ENTRIES.update({n: ACCEPTS for n in (
     "diffab_patch_scatter", "diffab_metrics_vs_native", "diffab_metrics_pairwise", "diffab_metrics_select_diverse",
     "diffab_metrics_backbone", "diffab_metrics_contacts", "diffab_metrics_ensemble", "diffab_metrics_similarity", "diffab_refine_backbone",
     "diffab_reverse_update", "diffab_reverse_update_jump", "diffab_sample_init", "diffab_sample_init_ex", "diffab_sample_init_noised",
-    "diffab_guidance_energy", "diffab_steer_energy", "diffab_steer_resample", "diffab_steer_gather")})
+    "diffab_guidance_energy", "diffab_steer_energy", "diffab_steer_resample", "diffab_steer_gather",
+    "diffab_metrics_surface")})  # (the last: include/diffab_hip_analysis.h)
 
 # name:kind in prototype order.  f: float operand, refused unless 16-byte aligned; fa: float operand, accepted; i64, m: accepted;
 # W / G, LW / LG, RW / RG, PW / PG: denoiser, layer, ResidueEmbedding, PairEmbedding weights / gradients (every buffer refused);
@@ -502,10 +540,413 @@ def refused(NL=HOST_NL):
     return out
 
 
-def header_exports():
-    src = open(os.path.join(REPO, "include", "diffab_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(diffab_[a-z0-9_]+)\s*\(", src)))
+HEADERS = ("diffab_hip.h", "diffab_hip_analysis.h")
+
+
+def header_source(headers=HEADERS):
+    """The headers' declarations as one string: no comments, no preprocessor lines (continued ones included)."""
+    src = "\n".join(open(os.path.join(REPO, "include", h)).read() for h in headers)
+    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S).replace("\\\n", " ")
+    return re.sub(r"^[ \t]*#.*$", "", src, flags=re.M)
+
+
+def header_exports(headers=HEADERS):
+    return sorted(set(re.findall(r"\b(diffab_[a-z0-9_]+)\s*\(", header_source(headers))))
+
+
+def _declarators(decl):
+    """`const float *w0, *b0` -> [(name, base type, is a pointer, points to const)]; `int32_t B, K` likewise."""
+    first, *more = [p.strip() for p in decl.split(",")]
+    m = re.fullmatch(r"(const\s+)?([A-Za-z_][A-Za-z0-9_ ]*?)\s*(\*?)\s*([A-Za-z_][A-Za-z0-9_]*)", first)
+    assert m, decl
+    const, base = bool(m.group(1)), m.group(2).strip()
+    out = [(m.group(4), base, bool(m.group(3)), const)]
+    for p in more:
+        out.append((p.lstrip("* "), base, p.startswith("*"), const))
+    return out
+
+
+def header_prototypes(headers=HEADERS):
+    """(structs, prototypes) as the headers declare them.  structs: {typedef name: [(field, base type, pointer, const)]};
+    prototypes: {export: [(parameter, base type, pointer, const)]}.  `const` is the pointee's (const float* x); a struct member that
+    is a struct by value (diffab_mlp3_weights coord) is a non-pointer field whose base type is in `structs`."""
+    src = header_source(headers)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*([a-z0-9_]+)\s*;", src, flags=re.S):
+        structs[name] = [f for decl in body.split(";") if decl.strip() for f in _declarators(" ".join(decl.split()))]
+    src = re.sub(r"typedef\s+struct\s*\{.*?\}\s*[a-z0-9_]+\s*;", "", src, flags=re.S)
+    protos = {}
+    for name, params in re.findall(r"\b(diffab_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = " ".join(params.split())
+        protos[name] = [] if params in ("", "void") else [_declarators(p)[0] for p in params.split(",")]
+    return structs, protos
+
+
+# ====================================================================== the operand-extent table (include/diffab_hip.h, "Operand extents")
+def typed_writes(headers=HEADERS):
+    """{export: operands its C types leave writable}: non-const pointer parameters, and the non-const pointer fields of struct
+    parameters by path (options.record.seq, noised.x_t, g.shift_dev).  `stream` is a handle, not memory."""
+    structs, protos = header_prototypes(headers)
+
+    def fields(path, struct):
+        out = []
+        for f, base, pointer, const in structs[struct]:
+            if base in structs:  # a struct by value or by pointer
+                out += fields(f"{path}.{f}", base)
+            elif pointer and not const:
+                out.append(f"{path}.{f}")
+        return out
+
+    out = {}
+    for name, params in protos.items():
+        ops = []
+        for p, base, pointer, const in params:
+            if p != "stream":
+                ops += fields(p, base) if base in structs else [p] if pointer and not const else []
+        out[name] = ops
+    return out
+
+
+# What the C types cannot say: a gradient table is the weights struct again (const float* fields), and every buffer of it is
+# accumulated into.  "grads.*" in WRITES.
+GRADIENT_TABLES = {"diffab_train_step_bwd": "grads", "diffab_denoise_step_bwd": "grads", "diffab_ipa_layer_bwd": "grads",
+                   "diffab_residue_embedding_bwd": "g", "diffab_pair_embedding_bwd": "g", "diffab_pair_embedding_bwd_taped": "g"}
+_RECORD = " ".join("opt.record." + f for f in ("slot_dev", "seq", "x", "O", "pred_x", "pred_O", "seq_probs"))
+_STEERING = " ".join("{}." + f for f in ("logw", "u_prev", "energy", "ancestors", "scratch"))
+_OPTIONS = f"{_RECORD} opt.steps.plan_dev opt.guidance.shift_dev {_STEERING.format(*['opt.steering'] * 5)}"
+_SURFACE = ("free_points bound_points design_buried_points free_area bound_area design_buried_area residue_buried bsa_paratope bsa_epitope "
+            "bsa_design_epitope n_paratope_buried n_epitope_buried n_hotspot n_hotspot_buried hotspot_buried_area workspace")
+# entry -> the operands it may write, by the prototype's names (every export of both headers; "" = none).  Mirrored from the headers:
+# tests/test_operand_extents_host.py holds it against typed_writes() + GRADIENT_TABLES, both ways.
+WRITES = {n: "" for n in (
+    "diffab_version", "diffab_last_error", "diffab_device_ok", "diffab_kernel_timer_enable", "diffab_debug_set_attn_variant",
+    "diffab_debug_set_module_stagger", "diffab_set_stream_guard", "diffab_denoise_workspace_bytes", "diffab_sample_workspace_bytes",
+    "diffab_sample_shared_workspace_bytes", "diffab_train_tape_bytes", "diffab_train_workspace_bytes", "diffab_ipa_layer_tape_bytes",
+    "diffab_ipa_layer_bwd_workspace_bytes", "diffab_residue_embedding_workspace_bytes", "diffab_pair_embedding_workspace_bytes",
+    "diffab_residue_embedding_bwd_workspace_bytes", "diffab_pair_embedding_bwd_workspace_bytes", "diffab_pair_embedding_tape_bytes",
+    "diffab_score_workspace_bytes")}
+WRITES.update({
+    "diffab_debug_set_attn_stamps": "device_buffer", "diffab_debug_set_module_stamps": "device_buffer",
+    "diffab_kernel_timer_read": "launches total_ms",  # (host pointers)
+    "diffab_debug_row_tiles": "tiles", "diffab_debug_row_plan": "plan",
+    "diffab_debug_linear128": "Y scratch", "diffab_debug_xstat128": "Y scratch", "diffab_debug_gemm_tn": "C db",
+    "diffab_so3_log": "S", "diffab_so3_exp": "R", "diffab_so3_matrix_to_rotvec": "v", "diffab_so3_rotvec_to_matrix": "R",
+    "diffab_so3_scale_rot": "out", "diffab_igso3_table_build": "pdf", "diffab_igso3_table_build_accurate": "pdf",
+    "diffab_igso3_cdf_build": "cdf", "diffab_igso3_sample": "rotvec", "diffab_igso3_bins_without_replacement": "bins",
+    "diffab_igso3_sample_bins": "rotvec", "diffab_weighted_multinomial": "out", "diffab_seq_forward_prob": "prob",
+    "diffab_seq_posterior": "post", "diffab_categorical_sample": "out", "diffab_coord_forward": "xt", "diffab_orient_forward": "Ot",
+    "diffab_philox_fill": "out", "diffab_losses_fwd": "losses3",
+    "diffab_ipa_layer_fwd": "y workspace",
+    "diffab_denoise_step_fwd": "out_eps out_O0 out_posterior out_logits out_res_emb workspace",
+    "diffab_train_step_fwd": "out_eps out_O0 out_posterior losses3 tape",
+    "diffab_train_step_bwd": "grads.* d_res_ctx d_pair_ctx workspace",
+    "diffab_orientation_loss": "elems sum1", "diffab_orientation_loss_bwd": "d_pred d_target",
+    "diffab_frames_apply": "out", "diffab_frames_invert": "out", "diffab_frames_bwd": "dR dt",
+    "diffab_angular_encoding": "out", "diffab_angular_encoding_bwd": "dx",
+    "diffab_denoise_step_fwd_taped": "out_eps out_O0 out_posterior tape",
+    "diffab_denoise_step_bwd": "grads.* d_res_ctx d_pair_ctx d_x_t d_O_t workspace",
+    "diffab_ipa_layer_fwd_taped": "y tape", "diffab_ipa_layer_bwd": "grads.* dx d_e d_R d_t workspace",
+    "diffab_residue_embedding_fwd": "out workspace", "diffab_pair_embedding_fwd": "out workspace",
+    "diffab_pair_embedding_xyz_fwd": "out workspace",
+    "diffab_residue_embedding_bwd": "g.* workspace", "diffab_pair_embedding_bwd": "g.* workspace",
+    "diffab_pair_embedding_fwd_taped": "out tape workspace", "diffab_pair_embedding_bwd_taped": "g.* workspace",
+    "diffab_featurize_xyz": "orientations backbone_dihedrals backbone_dihedrals_mask pairwise_dihedrals",
+    "diffab_patch_select": "index patch_mask count", "diffab_patch_gather": "dst", "diffab_patch_scatter": "dst",
+    "diffab_metrics_vs_native": "aar rmsd rmsd_aligned segment_aar segment_rmsd segment_rmsd_aligned",
+    "diffab_metrics_pairwise": "rmsd seq_identity workspace", "diffab_metrics_select_diverse": "index min_dist count",
+    "diffab_metrics_backbone": "phi psi omega peptide_bond n_bonds max_peptide_deviation n_chain_break n_cis workspace",
+    "diffab_metrics_contacts": "n_clash clash_score min_distance n_contact_pairs n_paratope n_epitope n_hotspot_contacted n_hotspot "
+                               "residue_clash residue_contact workspace",
+    "diffab_metrics_ensemble": "aa_freq entropy consensus mean_points rmsf log_prob consensus_identity rmsd_to_mean n_eff central workspace",
+    "diffab_metrics_similarity": "n_pairs n_pairs_interface preserved preserved_interface lddt_residue lddt lddt_thresholds ilddt_residue "
+                                 "ilddt lddt_segment n_native native_contacts_residue n_design n_kept fnat fnonnat kept_residue",
+    "diffab_metrics_surface": _SURFACE,
+    "diffab_refine_backbone": "out_translations out_orientations energy_before energy_after terms_after max_shift workspace",
+    "diffab_reverse_update": "seq x O", "diffab_reverse_update_jump": "seq x O r_out",
+    "diffab_sample_init": "seq x O", "diffab_sample_init_ex": "seq x O", "diffab_sample_init_noised": "seq x O",
+    "diffab_sample_loop": "seq x O workspace", "diffab_sample_loop_ex": f"seq x O workspace {_OPTIONS}",
+    "diffab_guidance_energy": "g.shift_dev clash bond n_clash max_bond_deviation grad",
+    "diffab_steer_energy": f"{_STEERING.format(*['steering'] * 5)} energy_out",
+    "diffab_steer_resample": "logw u_prev ancestors_out ess_out", "diffab_steer_gather": "seq x O scratch",
+    "diffab_score_designs": "out_terms out_residue noised.seq_t noised.x_t noised.O_t noised.eps workspace",
+})
+# A non-null device pointer that resolves to no contiguous tensor the harness knows, and may pass as it is: (entry, operand) -> why.
+UNGUARDED = {("diffab_patch_select", "ca"): "ca / ca_stride address a strided view (atom slot 1 of a (B,N,A,3) array): no contiguous extent "
+                                            "that a copy could stand in for"}
+GUARD_BYTES = 64 * 1024  # one 128 x 128 fp32 tile
+GUARD_FILLS = ("nan0", "ones")
+
+
+def writable(entry, operand):
+    ops = WRITES[entry].split()
+    return operand in ops or any(o.endswith(".*") and operand.startswith(o[:-1]) for o in ops)
+
+
+class ConstOperandChanged(AssertionError):
+    pass
+
+
+class UnresolvedPointer(AssertionError):
+    pass
+
+
+def tensors_of(*things, depth=3):
+    """Every tensor reachable from `things`: tensors, modules (parameters, their .grad, buffers, and what their attributes cache - the
+    schedule and IGSO3 tables of a DiffAb), pointer tables (_hip.SchedOnDevice.tensors, DenoiserWeightsOnDevice.keep), dicts, lists."""
+    out, seen = [], set()
+
+    def walk(v, d):
+        if id(v) in seen or d < 0:
+            return
+        seen.add(id(v))
+        if isinstance(v, torch.Tensor):
+            out.append(v)
+            if v.grad is not None:
+                out.append(v.grad)
+        elif isinstance(v, torch.nn.Module):
+            for m in v.modules():
+                for t in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False)):
+                    walk(t, d)
+                for k, a in vars(m).items():
+                    if k not in ("_parameters", "_buffers", "_modules"):
+                        walk(a, d - 1)
+        elif isinstance(v, dict):
+            for a in v.values():
+                walk(a, d - 1)
+        elif isinstance(v, (list, tuple, set)):
+            for a in v:
+                walk(a, d - 1)
+        elif hasattr(v, "__dict__") and not isinstance(v, (type, types.ModuleType, types.FunctionType)):
+            for a in vars(v).values():
+                walk(a, d - 1)
+
+    for v in things:
+        walk(v, depth)
+    return out
+
+
+def bytes_of(t):
+    """A contiguous tensor's own bytes as a flat uint8 view (raw_bytes is the whole storage)."""
+    return t.detach().reshape(-1).view(torch.uint8)
+
+
+class GuardedABI:
+    """Everything between __enter__ and __exit__ reaches the C ABI through operands that stand between two guards: the harness of the
+    operand-extent contract (include/diffab_hip.h, "Operand extents").
+
+    Stands in for the library like MisalignedABI (_hip.lib(), _hip.ptr, _hip.workspace; the same `entries`, `positions`, `when` and
+    `counts`).  An entry of `entries` is called with every device pointer - direct arguments, void* fields of structs passed by
+    reference, structs nested by value (w.coord), structs behind pointer fields (options.record, noised) and the host array
+    w.layers[NL], NL from the dims argument - replaced by a pointer into the interior of a fresh uint8 buffer: the interior holds the
+    tensor's bytes and starts at the original's address modulo 256 (every entry picks the kernel it would have picked, nothing is newly
+    refused), and GUARD_BYTES of guard lie directly in front of it and directly behind its last byte.  The guards hold `fill`:
+    "nan0" = NaN (0xFF bytes) in float operands and 0 in integer and mask operands, "ones" = the value 1 of the type.  Both are valid
+    wherever an integer is an index, a stray store cannot equal both, a float read past the end that is used turns the result into NaN
+    under "nan0", a mask read past the end flips under "ones" - so every case runs under both.  One address has one shadow: aliased
+    operands stay aliased.  Buffers from _hip.workspace pass as they are (tests/scratch_poison.py owns them).
+
+    After the call the device is synchronised, and (a) a guard byte that changed raises GuardDamaged with the entry, the operand, the
+    side and the element offset of the first damaged byte; (b) an operand the entry may not write (WRITES) whose interior differs from
+    the caller's tensor raises ConstOperandChanged; (c) the others are copied back into the caller's tensor.  Struct fields are put back.
+
+    A pointer is resolved through the tensors _hip.ptr saw inside the context and those of `known` (tensors_of: what was built before -
+    cached schedule and IGSO3 structs, weight tables).  A non-null device pointer that resolves to none of them raises UnresolvedPointer
+    unless UNGUARDED names it.  `lib` and `argtypes` replace the library and _hip's symbol table (tests/test_operand_extents_host.py
+    drives the harness with Python stand-ins on CPU tensors).  Does not mix with an outer torch.cuda.graph capture (the copies, fills
+    and checks are launches of their own); DIFFAB_FLAG_GRAPH_SAMPLER captures inside the call and is fine."""
+
+    def __init__(self, entries, fill, known=(), positions=None, when=None, lib=None, argtypes=None):
+        import ctypes
+
+        if fill not in GUARD_FILLS:
+            raise ValueError(f"fill must be one of {GUARD_FILLS}, not {fill!r}")
+        self.C, self.entries, self.fill, self.positions, self.when = ctypes, set(entries), fill, positions or {}, when or {}
+        self.real, self.argtypes = lib, argtypes
+        self.counts, self.tensors, self.known, self.scratch, self.saved, self.patterns, self.last = {}, {}, {}, {}, None, {}, {}
+        for t in tensors_of(*known):
+            self._see(t, self.known)  # (a tensor _hip.ptr sees inside the context goes first: the operand itself, not a buffer it is cut from)
+
+    def _see(self, t, table=None):
+        if t is not None and t.numel():
+            table, had = self.tensors if table is None else table, None if table is None else table.get(t.data_ptr())
+            if had is None or t.numel() * t.element_size() < had.numel() * had.element_size():  # of two known= tensors at one address the
+                table[t.data_ptr()] = t  # smaller: a guard too near is reported, one too far is not.  (Held: the address stays its own.)
+            if self.scratch.get(t.data_ptr()) not in (None, t.numel() if t.dtype == torch.uint8 else -1):
+                del self.scratch[t.data_ptr()]  # a freed workspace's address, given to an operand of a later call
+
+    def __enter__(self):
+        if self.real is None:
+            self.real = _hip.lib()
+        if self.argtypes is None:
+            self.argtypes = {n: a for n, (_, a) in list(_hip.SYMBOLS.items()) + list(_hip.ANALYSIS_SYMBOLS.items())}
+        self.params = {n: [p[0] for p in ps] for n, ps in header_prototypes()[1].items()}
+        self.saved = (_hip.lib, _hip.ptr, _hip.workspace)
+        real_ptr, real_ws = _hip.ptr, _hip.workspace
+
+        def ptr(t):
+            self._see(t)
+            return real_ptr(t)
+
+        def workspace(nbytes):
+            w = real_ws(nbytes)
+            self.scratch[w.data_ptr()] = w.numel()
+            return w
+
+        _hip.lib, _hip.ptr, _hip.workspace = (lambda: self), ptr, workspace
+        return self
+
+    def __exit__(self, *exc):
+        _hip.lib, _hip.ptr, _hip.workspace = self.saved
+        self.tensors.clear()
+        self.known.clear()
+        self.last.clear()
+        return False
+
+    # ------------------------------------------------------------------ shadows
+    def _guard(self, part, dtype):
+        """Fill the guard bytes `part` (a uint8 view) with the fill's value of `dtype`."""
+        if dtype.is_floating_point and self.fill == "nan0":
+            part.fill_(0xFF)
+        elif dtype in (torch.bool, torch.uint8):
+            part.fill_(0 if self.fill == "nan0" else 1)
+        else:
+            part.view(dtype).fill_(0 if self.fill == "nan0" else 1)
+
+    def _pattern(self, dtype, device):
+        key = (dtype, device)
+        if key not in self.patterns:
+            self.patterns[key] = torch.empty(GUARD_BYTES, dtype=torch.uint8, device=device)
+            self._guard(self.patterns[key], dtype)
+        return self.patterns[key]
+
+    def _shadow(self, entry, operand, address, made):
+        """The shadow pointer of `address`, or None for a pointer that passes as it is."""
+        if address in self.scratch:
+            return None
+        t = self.tensors.get(address, self.known.get(address))
+        if t is None or not t.is_contiguous():
+            if (entry, operand) in UNGUARDED:
+                return None
+            raise UnresolvedPointer(f"{entry}: operand {operand} = {address:#x} is not the data pointer of a contiguous tensor the harness "
+                                    "has seen (register it with known=, or name it in UNGUARDED with the reason)")
+        if address not in made:
+            n = t.numel() * t.element_size()
+            buf = torch.empty(n + 2 * GUARD_BYTES + 256, dtype=torch.uint8, device=t.device)
+            lo = GUARD_BYTES + (address - buf.data_ptr() - GUARD_BYTES) % 256
+            self._guard(buf[lo - GUARD_BYTES:lo], t.dtype)
+            self._guard(buf[lo + n:lo + n + GUARD_BYTES], t.dtype)
+            buf[lo:lo + n].copy_(bytes_of(t))
+            made[address] = dict(buf=buf, lo=lo, n=n, t=t, names=[], writable=False)
+        s = made[address]
+        s["names"].append(operand)
+        s["writable"] |= writable(entry, operand)
+        return s["buf"].data_ptr() + s["lo"]
+
+    def _struct_pointers(self, struct, path, NL, visit):
+        C = self.C
+        for field, ftype in struct._fields_:
+            v, p = getattr(struct, field), f"{path}.{field}"
+            if ftype is C.c_void_p:
+                if v:
+                    visit(struct, field, v, p)
+            elif isinstance(ftype, type) and issubclass(ftype, C.Structure):  # by value: w.coord
+                self._struct_pointers(v, p, NL, visit)
+            elif isinstance(getattr(ftype, "_type_", None), type) and issubclass(ftype._type_, C.Structure) and v:  # options.record, w.layers
+                if field == "layers":
+                    for l in range(NL):
+                        self._struct_pointers(v[l], f"{p}[{l}]", NL, visit)
+                else:
+                    self._struct_pointers(v.contents, p, NL, visit)
+            # (everything else is a number or a HOST array: slot_of_step, steps, ctx_of_row)
+
+    def _check(self, entry, made):
+        devices = {s["buf"].device for s in made.values()}
+        for d in devices:
+            if d.type == "cuda":
+                torch.cuda.synchronize(d)
+        fine = []  # the common case, one synchronisation per call: every guard and every const interior compared on the device
+        for s in made.values():
+            buf, lo, n, t = s["buf"], s["lo"], s["n"], s["t"]
+            want = self._pattern(t.dtype, buf.device)
+            fine += [(buf[lo - GUARD_BYTES:lo] == want).all(), (buf[lo + n:lo + n + GUARD_BYTES] == want).all()]
+            if not s["writable"]:
+                fine.append((buf[lo:lo + n] == bytes_of(t)).all())
+        if all(bool(torch.stack([f for f in fine if f.device == d]).all()) for d in devices):
+            for s in made.values():
+                if s["writable"]:
+                    bytes_of(s["t"]).copy_(s["buf"][s["lo"]:s["lo"] + s["n"]])
+            return
+        for s in made.values():
+            buf, lo, n, t = s["buf"], s["lo"], s["n"], s["t"]
+            item, name = t.element_size(), " / ".join(dict.fromkeys(s["names"]))
+            want = self._pattern(t.dtype, buf.device)
+            for side, part in (("in front of", buf[lo - GUARD_BYTES:lo]), ("behind", buf[lo + n:lo + n + GUARD_BYTES])):
+                if not torch.equal(part, want):
+                    bad = (part != want).nonzero().flatten()
+                    first = int(bad[0])
+                    if side == "behind":
+                        where = f"element {first // item} behind its end (operand of {t.numel()} elements, {tuple(t.shape)})"
+                    else:
+                        where = f"element {(first - GUARD_BYTES) // item} from its start (negative: in front of it)"
+                    raise GuardDamaged(f"{entry}: operand {name} ({t.dtype}) was written out of bounds {side} it: first damaged guard byte at "
+                                       f"{where}, {int(bad.numel())} damaged bytes on that side, value 0x{int(part[first]):02x}, "
+                                       f'guard fill "{self.fill}"')
+            inner, own = buf[lo:lo + n], bytes_of(t)
+            if s["writable"]:
+                own.copy_(inner)
+            elif not torch.equal(inner, own):
+                first = int((inner != own).nonzero().flatten()[0])
+                raise ConstOperandChanged(f"{entry}: operand {name} is not writable (WRITES) and changed: first changed element {first // item} "
+                                          f"of {t.numel()}")
+
+    def __getattr__(self, name):
+        fn = getattr(self.real, name)
+        if name not in self.entries:
+            return fn
+        C = self.C
+
+        def call(*args):
+            if name in self.when and not self.when[name](args):
+                return fn(*args)
+            made, restore, out = {}, [], []
+            only, types_, names = self.positions.get(name), self.argtypes[name], self.params[name]
+            assert len(args) == len(types_) == len(names), (name, len(args), len(types_), len(names))
+            dims = [getattr(a, "_obj", None) or (a.contents if hasattr(a, "contents") and a else None) for a in args]
+            NL = next((int(v.NL) for v in dims if isinstance(v, _hip.Dims)), 1)
+
+            def visit(struct, field, v, path):
+                new = self._shadow(name, path, v, made)
+                if new is not None:
+                    restore.append((struct, field, v))
+                    setattr(struct, field, new)
+
+            try:
+                for i, (a, at, pname) in enumerate(zip(args, types_, names)):
+                    if (only is not None and i not in only) or pname == "stream":
+                        out.append(a)
+                    elif at is C.c_void_p:
+                        v = a.value if isinstance(a, C.c_void_p) else a
+                        new = self._shadow(name, pname, int(v), made) if v else None
+                        out.append(a if new is None else C.c_void_p(new))
+                    elif isinstance(getattr(at, "_type_", None), type) and issubclass(at._type_, C.Structure):
+                        struct = getattr(a, "_obj", None) if a is not None else None
+                        if struct is None and a is not None and hasattr(a, "contents") and a:
+                            struct = a.contents
+                        if struct is not None:
+                            self._struct_pointers(struct, pname, NL, visit)
+                        out.append(a)
+                    else:
+                        out.append(a)
+                self.last = made  # (for the host tests' stand-ins: the shadows of the call in flight)
+                rc = fn(*out)
+            finally:
+                for struct, field, v in restore:
+                    setattr(struct, field, v)
+            self._check(name, made)
+            self.counts[name] = self.counts.get(name, 0) + len(made)
+            return rc
+
+        return call
 
 
 

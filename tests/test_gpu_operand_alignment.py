@@ -113,12 +113,13 @@ FORWARD_CASES = [  # id, B, K, flags, dims
 def test_denoiser_forward_with_misaligned_groups_vs_float64_oracle(hip, B, K, flags, dims_name):
     """Denoiser.forward with each operand group misaligned in turn (every offset of its type), then everything at once with the weights
     as views of one flat vector: all five outputs against the float64 oracle.  The outputs are the front end's own allocations; a
-    misaligned OUTPUT exists at the C ABI only (test_denoise_step_fwd_refusals_and_accepted_operand).  B = 8 repeats the two patches."""
+    misaligned OUTPUT exists at the C ABI only (test_denoise_step_fwd_refusals_and_accepted_operand).  B = 8 repeats the two patches
+    (row b is patch b % 2; tests/test_gpu_operand_extents.py also asks for B = 3)."""
     dims, sd, inp2, beta2, want2 = forward_case(K, dims_name)
-    rep = B // 2
-    host = {k: v.repeat(rep, *[1] * (v.dim() - 1)) for k, v in inp2.items()}
-    host["beta"] = beta2.repeat(rep)
-    want = {k: v.repeat(rep, *[1] * (v.dim() - 1)) for k, v in want2.items()}
+    idx = torch.arange(B) % 2
+    host = {k: v[idx].contiguous() for k, v in inp2.items()}
+    host["beta"] = beta2[idx].contiguous()
+    want = {k: v[idx] for k, v in want2.items()}
     dev = {k: v.cuda() for k, v in host.items()}
     names = ARGS + ("beta", "generation_mask", "residue_mask")
 
@@ -887,6 +888,8 @@ RERUNS = {
     "score_designs_noised": (("diffab_score_designs",), "test_gpu_score", "test_noised_state_vs_oracle", ("score_unit",), (), (4, 12)),
     "score_designs_terms": (("diffab_score_designs",), "test_gpu_score", "test_terms_vs_oracle_unit", ("score_unit",), (), (4, 12)),
     "sample_loop": (("diffab_sample_loop_ex",), "test_gpu_parity", "test_reverse_step_teacher_forced_vs_oracle", ("hip",), (), (4, 12)),
+    # the analysis header's entry (include/diffab_hip_analysis.h), at the smallest parametrisation of its oracle test
+    "metrics_surface": (("diffab_metrics_surface",), "test_gpu_surface", "test_surface_equals_the_oracle", (), (24, 8, False, 1, 33), (4, 12)),
 }
 # diffab_debug_row_tiles / _row_plan read a mask byte by byte and write bytes / int32 (diffusion_kernels.hip tiles_needed_kernel, row_plan):
 # the sample loop's own calls of the same launchers run in every reverse-step case; the debug exports have no misaligned case
@@ -924,7 +927,7 @@ def test_entries_rerun_their_own_reference_test_with_misaligned_pointers(request
 
 
 def test_every_export_is_in_the_table():
-    """The table is the header's list of exports: one missing from it, or one it names that the header no longer has, fails here
+    """The table is the two headers' list of exports: one missing from it, or one it names that the headers no longer have, fails here
     (no GPU needed).  Every ACCEPTS entry runs misaligned on the device, in a sweep or a rerun; UNSWEPT names the two that do not."""
     exports = header_exports()
     assert sorted(ENTRIES) == exports, (sorted(set(exports) - set(ENTRIES)), sorted(set(ENTRIES) - set(exports)))
