@@ -242,8 +242,12 @@ static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const Step
   if (loop && !(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
   ForwardPlan p{};
   p.flags = flags;
-  p.fold = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d) && rowgemm128_ok(res_ctx, D, b.h1, D, rows, D);
-  p.b6 = p.fold && use_b6_gemm(flags) && rowgemm128_b6_ok(res_ctx, D, b.h1, D, rows, D);
+  // The split-precision MLPs take any row count; only the fp32 kernel of the folded path needs a whole 128-row group (rowgemm128_ok).
+  // That M >= 128 must not gate the split-precision path: one patch of 64 residues would run its embedding MLP and heads on other kernels
+  // than the same patch in a larger batch, and its bits would depend on the batch (tests/test_gpu_launch_forms.py, K = 64, B = 1).
+  const bool mfma = !(flags & DIFFAB_FLAG_FORCE_GENERIC) && fast_path_supported(d);
+  p.b6 = mfma && use_b6_gemm(flags) && rowgemm128_b6_ok(res_ctx, D, b.h1, D, rows, D);
+  p.fold = mfma && (p.b6 || rowgemm128_ok(res_ctx, D, b.h1, D, rows, D));
   p.chain = p.b6 && d->V <= 128;
   p.pair_planes = use_pair_planes(d, flags, pair_ctx, b) ? b.pair : nullptr;
   p.ctx_of_row = ctx_of_row;
@@ -548,6 +552,18 @@ int diffab_debug_xstat128(const float* X, const float* W, float* Y, int64_t M, i
   hipStream_t st = as_stream(stream);
   if (mode == 1) return launch_xstat_b6(X, W, 1, N, Y, N, static_cast<int>(M), N, scratch, st);
   return launch_xstat_h3(X, W, 1, N, Y, N, static_cast<int>(M), N, scratch, st);
+}
+
+int diffab_debug_dense_forms(int64_t rows, int32_t nblocks, int32_t has_parts, int32_t* out5) {
+  DIFFAB_REQUIRE(out5 && rows >= 1 && rows < (1LL << 31) && nblocks >= 1, DIFFAB_ERR_ARG, "debug_dense_forms: bad operands");
+  const int M = static_cast<int>(rows);
+  const int group = rowgemm128_rows_per_group(M, has_parts != 0);
+  out5[0] = group;
+  out5[1] = M % (group == 0 ? 64 : group) != 0;
+  out5[2] = dense_tile_full(M);
+  out5[3] = dense_tile_nsplit(M, nblocks);
+  out5[4] = M - (M - 1) / kDenseTileRows * kDenseTileRows;
+  return DIFFAB_OK;
 }
 
 int diffab_debug_gemm_tn(const float* A, const float* B, float* C, float* db, int64_t M, int32_t N1, int32_t N2, int32_t mode, void* stream) {

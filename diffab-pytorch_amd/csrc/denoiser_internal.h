@@ -26,6 +26,27 @@ int launch_ipa_frames_bwd(const float* proj, const float* dproj, int NP, int pt_
                           int ol_col0, int on_col0, int n_vpts, const float* R, const float* t, float* dR, float* dt, int rows,
                           hipStream_t st);
 
+// The launch forms of the dense tiles of the MFMA path.  Each launcher picks its kernel instantiation from the row count rows = B K
+// alone, through these functions (host arithmetic; diffab_debug_dense_forms reports them, tests/test_launch_forms_host.py pins both
+// sides of every threshold and DESIGN 4.3 has the table).  kDenseFillGroups is a constant of this code, not the device's CU count.
+constexpr int kDenseTileRows = 128;    // rows of a projection / x-stationary tile and of an MLP-chain group
+constexpr int kDenseFillGroups = 256;  // "the groups fill the chip"
+constexpr int kPartsTilesMax = 64;     // 64-row tiles up to which the row GEMM takes its (row tile, k part) form
+// launch_rowgemm128_h3p / _b6p: rows per work-group - 0: the (row tile, k part) form (parts_usable: the caller gave 16-byte aligned
+// parts scratch and the contraction has more than one part), 128 when 128-row groups fill the chip, else 64
+inline int rowgemm128_rows_per_group(int M, bool parts_usable) {
+  if (parts_usable && (M + 63) / 64 <= kPartsTilesMax) return 0;
+  return (M + kDenseTileRows - 1) / kDenseTileRows >= kDenseFillGroups ? 128 : 64;
+}
+// the FULL instantiations (no row guards): launch_proj_frames_h3p / _f32, launch_xstat_h3, launch_xstat (b6)
+inline bool dense_tile_full(int rows) { return rows % kDenseTileRows == 0; }
+// launch_proj_frames_h3p, launch_xstat_h3, launch_xstat (b6): work-groups per row tile, each with its share of the nblocks column
+// blocks - half the chip or less: several (the SPLIT instantiations are nsplit > 1)
+inline int dense_tile_nsplit(int rows, int nblocks) {
+  const int ntiles = (rows + kDenseTileRows - 1) / kDenseTileRows, nsplit = kDenseFillGroups / ntiles;
+  return nsplit < 1 ? 1 : (nsplit > nblocks ? nblocks : nsplit);
+}
+
 // MFMA path for the benchmark geometry (D=128, C=64, H=8, DS=32, PQ=PV=8, K % 16 == 0)
 bool fast_path_supported(const diffab_dims* d);
 size_t ipa_fast_workspace_floats(const diffab_dims* d);

@@ -239,7 +239,8 @@ int launch_rowgemm128_b6p(const float* X, int ldx, const void* planes, const flo
                  "rowgemm128_b6: unsupported operands");
   const __bf16* Wc = static_cast<const __bf16*>(planes);
   const int tiles64 = (M + 63) / 64, nparts = (Kd / b6tile::BK + b6tile::PART_CHUNKS - 1) / b6tile::PART_CHUNKS;
-  if (parts && nparts > 1 && tiles64 <= 64 && (reinterpret_cast<uintptr_t>(parts) & 15) == 0) {  // up to 32 patches of 128 residues
+  const int rows_env = rowgemm128_rows_per_group(M, parts && nparts > 1 && (reinterpret_cast<uintptr_t>(parts) & 15) == 0);
+  if (rows_env == 0) {  // up to 32 patches of 128 residues
     DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm128_b6_parts_kernel<64>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, b6_lds_bytes<64>()));
     hipLaunchKernelGGL((rowgemm128_b6_parts_kernel<64>), dim3(tiles64, nparts), dim3(256), b6_lds_bytes<64>(), st, X, ldx, Wc, M, Kd, parts);
@@ -251,7 +252,6 @@ int launch_rowgemm128_b6p(const float* X, int ldx, const void* planes, const flo
   }
   // 128-row work-groups when they fill the chip (measured at 256 groups: 47 us against 53 for 64-row groups, K = 1024), 64-row
   // groups below that (B <= 128 patches of 128 residues per GPU: twice the groups)
-  const int rows_env = (M + 127) / 128 >= 256 ? 128 : 64;
 #define B6_LAUNCH(RELU_, ROWS_)                                                                                                         \
   do {                                                                                                                                  \
     DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm128_b6_kernel<RELU_, ROWS_>),                              \
@@ -298,14 +298,14 @@ __global__ __launch_bounds__(512) void proj_frames_b6_kernel(const float* __rest
 
 static int launch_xstat(const float* x, const void* planes, const float* R, const float* t, float* Y, int rows, int N, int NB, int ldy,
                         int frames_from, hipStream_t st) {
+  static_assert(PJ_ROWS == kDenseTileRows, "dense_tile_full() / dense_tile_nsplit() speak of this tile's rows");
   DIFFAB_REQUIRE(planes && (reinterpret_cast<uintptr_t>(planes) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(Y) & 3) == 0 && rows >= 1 && NB % 2 == 0 && NB * PJ_B >= N,
                  DIFFAB_ERR_ARG, "proj_frames_b6: unsupported operands");
   const __bf16* Wc = static_cast<const __bf16*>(planes);
   const int ntiles = (rows + PJ_ROWS - 1) / PJ_ROWS;
   // half the chip or less: several groups per row tile, each with its share of the column blocks (B = 1: one block per group)
-  int nsplit = 256 / ntiles;
-  nsplit = nsplit < 1 ? 1 : (nsplit > NB ? NB : nsplit);
+  const int nsplit = dense_tile_nsplit(rows, NB);
   const bool split = nsplit > 1;
   const dim3 grid2(ntiles, nsplit);
 #define XSTAT_LAUNCH(FULL_, SPLIT_)                                                                                                      \
@@ -320,7 +320,7 @@ static int launch_xstat(const float* x, const void* planes, const float* R, cons
     if (split) XSTAT_LAUNCH(FULL_, true); \
     else XSTAT_LAUNCH(FULL_, false);      \
   } while (0)
-  if (rows % PJ_ROWS == 0) XSTAT_PICK(true);
+  if (dense_tile_full(rows)) XSTAT_PICK(true);
   else XSTAT_PICK(false);
 #undef XSTAT_PICK
 #undef XSTAT_LAUNCH

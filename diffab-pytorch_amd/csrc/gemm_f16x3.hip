@@ -98,7 +98,7 @@ int launch_wsplit128_h3(const float* W, int ldw, int Kd, void* planes, float* wi
 // scratch of the (row tile, k part) form: 0 when M is past the few row tiles that form is for
 size_t rowgemm128_h3_parts_floats(int M, int Kd) {
   const size_t tiles64 = static_cast<size_t>((M + 63) / 64);
-  return tiles64 <= 64 ? tiles64 * ((Kd / BK + h3tile::PART_CHUNKS - 1) / h3tile::PART_CHUNKS) * 64 * 128 : 0;
+  return tiles64 <= kPartsTilesMax ? tiles64 * ((Kd / BK + h3tile::PART_CHUNKS - 1) / h3tile::PART_CHUNKS) * 64 * 128 : 0;
 }
 // Y[M x 128] = act(X[:, 0:Kd] W[:, 0:Kd]^T + bias row), W as launch_wsplit128_h3 planes + scales; parts (optional): scratch of
 // rowgemm128_h3_parts_floats(M, Kd) floats for the (row tile, k part) form of few row tiles
@@ -108,7 +108,8 @@ int launch_rowgemm128_h3p(const float* X, int ldx, const void* planes, const flo
                  "rowgemm128_h3: unsupported operands");
   const _Float16* Wc = static_cast<const _Float16*>(planes);
   const int tiles64 = (M + 63) / 64, nparts = (Kd / BK + h3tile::PART_CHUNKS - 1) / h3tile::PART_CHUNKS;
-  if (parts && nparts > 1 && tiles64 <= 64 && (reinterpret_cast<uintptr_t>(parts) & 15) == 0) {  // up to 32 patches of 128 residues
+  const int rows_wg = rowgemm128_rows_per_group(M, parts && nparts > 1 && (reinterpret_cast<uintptr_t>(parts) & 15) == 0);
+  if (rows_wg == 0) {  // up to 32 patches of 128 residues
     DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm128_h3_parts_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          h3tile::lds_bytes<64>()));
     hipLaunchKernelGGL((rowgemm128_h3_parts_kernel<64>), dim3(tiles64, nparts), dim3(256), h3tile::lds_bytes<64>(), st, X, ldx, Wc, M, Kd, parts);
@@ -118,7 +119,7 @@ int launch_rowgemm128_h3p(const float* X, int ldx, const void* planes, const flo
     DIFFAB_LAUNCH_CHECK();
     return DIFFAB_OK;
   }
-  const int rows_wg = (M + 127) / 128 >= 256 ? 128 : 64;  // 128-row groups when they fill the chip, 64-row groups below that
+  // 128-row groups when they fill the chip, 64-row groups below that
 #define H3_LAUNCH(RELU_, ROWS_)                                                                                                          \
   do {                                                                                                                                   \
     DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm128_h3_kernel<RELU_, ROWS_>),                               \
@@ -230,13 +231,13 @@ int launch_pjsplit_h3(const float* const* W6, void* planes, float* wis, hipStrea
 int launch_proj_frames_h3p(const float* x, const void* planes, const float* wis, const float* R, const float* t, float* proj, int rows,
                            hipStream_t st) {
   using namespace pjh3;
+  static_assert(PJ_ROWS == kDenseTileRows, "dense_tile_full() / dense_tile_nsplit() speak of this tile's rows");
   DIFFAB_REQUIRE(planes && wis && R && t && (reinterpret_cast<uintptr_t>(planes) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(proj) & 3) == 0 && rows >= 1,
                  DIFFAB_ERR_ARG, "proj_frames_h3: unsupported operands");
   const _Float16* Wc = static_cast<const _Float16*>(planes);
   const int ntiles = (rows + PJ_ROWS - 1) / PJ_ROWS;
-  int nsplit = 256 / ntiles;  // half the chip or less: several groups per row tile, each with its share of the column blocks
-  nsplit = nsplit < 1 ? 1 : (nsplit > PJ_NB ? PJ_NB : nsplit);
+  const int nsplit = dense_tile_nsplit(rows, PJ_NB);  // half the chip or less: several groups per row tile, each with its share of the column blocks
   const dim3 grid(ntiles, nsplit);
 #define PJH3_LAUNCH(FULL_, SPLIT_)                                                                                                    \
   do {                                                                                                                                \
@@ -244,7 +245,7 @@ int launch_proj_frames_h3p(const float* x, const void* planes, const float* wis,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, PJ_LDS_BYTES));                                   \
     hipLaunchKernelGGL((proj_frames_h3_kernel<FULL_, SPLIT_>), grid, dim3(512), PJ_LDS_BYTES, st, x, Wc, wis, R, t, proj, rows);        \
   } while (0)
-  if (rows % PJ_ROWS == 0) {
+  if (dense_tile_full(rows)) {
     if (nsplit > 1) PJH3_LAUNCH(true, true);
     else PJH3_LAUNCH(true, false);
   } else {
@@ -575,8 +576,7 @@ int launch_xstat_h3(const float* X, const float* W, int64_t sn, int64_t sk, floa
   hipLaunchKernelGGL(xsplit_h3_kernel, dim3(NB * PJ_B), dim3(64), 0, st, W, sn, sk, N, Wc, wis);
   DIFFAB_LAUNCH_CHECK();
   const int ntiles = (rows + PJ_ROWS - 1) / PJ_ROWS;
-  int nsplit = 256 / ntiles;
-  nsplit = nsplit < 1 ? 1 : (nsplit > NB ? NB : nsplit);
+  const int nsplit = dense_tile_nsplit(rows, NB);
   const dim3 grid(ntiles, nsplit);
 #define XSH3_LAUNCH(FULL_, SPLIT_)                                                                                              \
   do {                                                                                                                          \
@@ -584,7 +584,7 @@ int launch_xstat_h3(const float* X, const float* W, int64_t sn, int64_t sk, floa
                                          hipFuncAttributeMaxDynamicSharedMemorySize, PJ_LDS_BYTES));                             \
     hipLaunchKernelGGL((xstat_h3_kernel<FULL_, SPLIT_>), grid, dim3(512), PJ_LDS_BYTES, st, X, Wc, wis, Y, rows, NB, N, ldy);     \
   } while (0)
-  if (rows % PJ_ROWS == 0) {
+  if (dense_tile_full(rows)) {
     if (nsplit > 1) XSH3_LAUNCH(true, true);
     else XSH3_LAUNCH(true, false);
   } else {

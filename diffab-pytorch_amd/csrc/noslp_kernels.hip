@@ -188,6 +188,7 @@ __global__ __launch_bounds__(512) void proj_frames_kernel(const float* __restric
 }
 
 int launch_proj_frames_f32(const float* x, const float* const* W6, const float* R, const float* t, float* proj, int rows, hipStream_t st) {
+  static_assert(PJROWS == kDenseTileRows, "dense_tile_full() speaks of this tile's rows");
   const size_t pj_lds = (2 * PJB * PJLD + PJROWS * 12) * sizeof(float);
 #define PROJ_LAUNCH(FULL_)                                                                                                        \
   do {                                                                                                                            \
@@ -196,7 +197,7 @@ int launch_proj_frames_f32(const float* x, const float* const* W6, const float* 
     hipLaunchKernelGGL((proj_frames_kernel<FULL_>), dim3((rows + PJROWS - 1) / PJROWS), dim3(512), pj_lds, st, x, W6[0], W6[1],   \
                        W6[2], W6[3], W6[4], W6[5], R, t, proj, rows);                                                             \
   } while (0)
-  if (rows % PJROWS == 0) PROJ_LAUNCH(true);
+  if (dense_tile_full(rows)) PROJ_LAUNCH(true);
   else PROJ_LAUNCH(false);
 #undef PROJ_LAUNCH
   DIFFAB_LAUNCH_CHECK();

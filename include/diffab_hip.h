@@ -298,6 +298,15 @@ int diffab_debug_xstat128(const float* X, const float* W, float* Y, int64_t M, i
  * mode 1: bf16 matrix cores, six-term split (gemm_tn_b6_kernel), mode 2: f16 matrix cores, three-term split with one power-of-two
  * scale per (32-row slab, operand) (gemm_tn_h3_kernel).  db (nullable): db[N1] += column sums of A.  Any M, N1, N2 >= 1. */
 int diffab_debug_gemm_tn(const float* A, const float* B, float* C, float* db, int64_t M, int32_t N1, int32_t N2, int32_t mode, void* stream);
+/* Tests: the launch forms the dense tiles of the MFMA path pick at a row count rows = B K (the launchers call the same host functions,
+ * csrc/denoiser_internal.h).  Host only, enqueues nothing, out5 is a HOST array of 5: out5[0] = rows per work-group of the row GEMM
+ * (to_out, the MLP layers, diffab_debug_linear128 modes 1 and 2) - 0: the (row tile, k part) form, taken with has_parts (the launcher
+ * was given parts scratch and the contraction has more than one part) up to 64 tiles of 64 rows; else 128 when ceil(rows / 128) >= 256,
+ * else 64; out5[1] = 1 if the last group of that form is ragged; out5[2] = FULL (rows a multiple of 128: the projection and
+ * x-stationary tiles, also the fp32 projection tile, run without row guards); out5[3] = nsplit of the x-stationary / projection tile
+ * with nblocks column blocks = clamp(256 / ceil(rows / 128), 1, nblocks) (work-groups per row tile; SPLIT = nsplit > 1); out5[4] = rows
+ * of its last tile (1 .. 128; also of the last group of the MLP chains). */
+int diffab_debug_dense_forms(int64_t rows, int32_t nblocks, int32_t has_parts, int32_t* out5);
 int diffab_kernel_timer_read(int64_t* launches, double* total_ms);
 /* ---- SO(3) maps, n matrices/vectors each --------------------------------- */
 /* so3.py:146-162  log R = theta/(2 sin theta) (R - R^T); NaN at theta = 0 like the reference */

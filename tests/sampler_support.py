@@ -440,7 +440,8 @@ ENTRIES = {n: NO_DATA for n in (
     "diffab_set_stream_guard", "diffab_denoise_workspace_bytes", "diffab_sample_workspace_bytes", "diffab_sample_shared_workspace_bytes",
     "diffab_train_tape_bytes", "diffab_train_workspace_bytes", "diffab_ipa_layer_tape_bytes", "diffab_ipa_layer_bwd_workspace_bytes",
     "diffab_residue_embedding_workspace_bytes", "diffab_pair_embedding_workspace_bytes", "diffab_residue_embedding_bwd_workspace_bytes",
-    "diffab_pair_embedding_bwd_workspace_bytes", "diffab_pair_embedding_tape_bytes", "diffab_score_workspace_bytes")}
+    "diffab_pair_embedding_bwd_workspace_bytes", "diffab_pair_embedding_tape_bytes", "diffab_score_workspace_bytes",
+    "diffab_debug_dense_forms")}
 ENTRIES.update({n: ACCEPTS for n in (
     "diffab_debug_row_tiles", "diffab_debug_row_plan", "diffab_debug_gemm_tn", "diffab_so3_log", "diffab_so3_exp",
     "diffab_so3_matrix_to_rotvec", "diffab_so3_rotvec_to_matrix", "diffab_so3_scale_rot", "diffab_igso3_table_build",
@@ -627,7 +628,7 @@ WRITES = {n: "" for n in (
     "diffab_score_workspace_bytes")}
 WRITES.update({
     "diffab_debug_set_attn_stamps": "device_buffer", "diffab_debug_set_module_stamps": "device_buffer",
-    "diffab_kernel_timer_read": "launches total_ms",  # (host pointers)
+    "diffab_kernel_timer_read": "launches total_ms", "diffab_debug_dense_forms": "out5",  # (host pointers)
     "diffab_debug_row_tiles": "tiles", "diffab_debug_row_plan": "plan",
     "diffab_debug_linear128": "Y scratch", "diffab_debug_xstat128": "Y scratch", "diffab_debug_gemm_tn": "C db",
     "diffab_so3_log": "S", "diffab_so3_exp": "R", "diffab_so3_matrix_to_rotvec": "v", "diffab_so3_rotvec_to_matrix": "R",

@@ -99,9 +99,10 @@ def test_patch_resident_module_default_forms_are_bitwise_the_per_layer_launches(
 
 
 def test_ipa_layer_bits_do_not_depend_on_the_launch_form(hip):
-    """One IPA layer on the first patches of batches of 1, 8, 40, 128 and 256 patches: the dense products pick a launch form by batch
-    size - (row tile, 64-k part) work-groups, 64-row groups, 128-row groups, projections split over column blocks - and all of them
-    have to produce the same bits for the same patch (the sampler's shard invariance rests on it)."""
+    """One IPA layer on the first patches of batches of 1, 8, 40, 45, 52, 70, 128 and 256 patches: the dense products pick a launch form
+    by batch size - (row tile, 64-k part) work-groups, 64-row groups, 128-row groups, projections split over column blocks (B = 45, 52,
+    70: 5, 4 and 3 groups per row tile, whose shares of the 14 blocks reach 4 and 5, beside the 1, 2, 3, 7 and 14 of the others) - and
+    all of them have to produce the same bits for the same patch (the sampler's shard invariance rests on it)."""
     from diffab_pytorch.diffab_pytorch import InvariantPointAttentionLayer
 
     d, K = syn.BENCH_DIMS, 128
@@ -109,7 +110,7 @@ def test_ipa_layer_bits_do_not_depend_on_the_launch_form(hip):
     layer = InvariantPointAttentionLayer(d["D"], d["C"], d["DS"], d["PQ"], d["PV"], d["H"]).cuda().requires_grad_(False)
     inp = device_patches(256, K, d, seed=77)
     outs = {}
-    for B in (1, 8, 40, 128, 256):
+    for B in (1, 8, 40, 45, 52, 70, 128, 256):
         args = [inp[k][:B].contiguous() for k in ("res_context_emb", "pair_context_emb", "orientations", "translations")]
         outs[B] = layer(*args, flags=_hip.FLAG_PAIR_PLANES)[: min(B, 8)].clone()
     for B, o in outs.items():
