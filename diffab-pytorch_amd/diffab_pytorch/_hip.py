@@ -294,6 +294,15 @@ ANALYSIS_SYMBOLS = {
                                + [_fp, _sz, _fp]),
 }
 
+# every symbol include/diffab_hip_hbonds.h declares (both export lists above are pinned by their tests): same library, a third table
+HBOND_SYMBOLS = {
+    # (points, donor_off, context_points, context_valid, context_donor_off, generation_mask, residue_mask (nullable), antigen_mask
+    #  (nullable), hotspot_mask (nullable), chain, residue_idx, rows, group_size, K, A, O, H, nh_o_partner, nh_o_energy, o_hn_partner,
+    #  o_hn_energy, bridge_partner, bridge_parallel, ss, residue_hbonds, n_hbonds, n_hbonds_internal, n_hbonds_antigen, n_hbonds_framework,
+    #  n_hotspot_bonded, n_hotspot, hbond_energy, ss_count (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_hbonds": (C.c_int, [_fp] * 11 + [_i32] * 4 + [_fp] * 18 + [_fp, _sz, _fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -306,7 +315,7 @@ def load_library() -> C.CDLL:
                 f"{LIB_PATH} is missing - build it with `make -C diffab-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()); there is no CPU fallback for this path")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items()):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -7,6 +7,8 @@
 ``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
+``hbonds``          per design: Kabsch-Sander backbone hydrogen bonds with the peptide-plane O and the amide H they need, the bonds to
+                    antigen and framework, and the secondary structure of every residue (DESIGN section 4.20, ``csrc/hbond_kernels.hip``);
 ``ensemble``        per patch: its N designs as a distribution - amino-acid frequencies, entropy, consensus, mean structure, RMSF, and
                     how typical each design is of its siblings (DESIGN section 4.16, ``csrc/ensemble_kernels.hip``);
 ``similarity``      per design, without a superposition: lDDT against the native per residue, per design and per segment, and the
@@ -16,9 +18,11 @@ Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` retur
 (rows,K,3), ``orientations`` (rows,K,3,3) with ``rows = G * group_size``, row ``g * group_size + r`` = design r of patch g - and the masks
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
 the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
-``_similarity`` in ``include/diffab_hip.h`` and of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h``; every number is
+``_similarity`` in ``include/diffab_hip.h``, of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h`` and of ``diffab_metrics_hbonds`` in
+``include/diffab_hip_hbonds.h``; every number is
 computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters),
-``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip`` and ``csrc/surface_kernels.hip``, and there is no torch fallback.
+``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip`` and ``csrc/hbond_kernels.hip``, and there is
+no torch fallback.
 """
 from __future__ import annotations
 
@@ -46,6 +50,9 @@ LDDT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)  # Angstrom
 CONTACT_DISTANCE = {"ca": 8.0, "backbone": 5.0}  # similarity's default per atom set
 PEPTIDE_BOND = 1.329  # Angstrom, C(i) - N(i+1)
 GLY = AA3.index("GLY")
+PRO = AA3.index("PRO")  # hbonds(): no amide hydrogen
+HBONDS_MAX_K = 512  # DIFFAB_HBONDS_MAX_K: hbonds keeps the K x K bond bits of a row on chip
+SS_LETTERS = " HBEGITS"  # hbonds()['ss']: none, alpha helix, lone bridge, ladder, 3-10 helix, pi helix, turn, bend
 SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256  # DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
@@ -505,6 +512,101 @@ def surface(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, 
                                           _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(table), rows, group_size, K, P, A,
                                           n_points, probe, ctx_default, *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes,
                                           _hip.stream_ptr()), "diffab_metrics_surface")
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ backbone hydrogen bonds, secondary structure
+def hbonds_workspace_bytes(G: int, K: int, A: int) -> int:
+    """DIFFAB_METRICS_HBONDS_WORKSPACE_BYTES of include/diffab_hip_hbonds.h."""
+    return G * K * (8 + 4 * ((K + 31) // 32)) + 1024
+
+
+def ss_strings(ss: torch.Tensor) -> list:
+    """``hbonds()['ss']`` (rows,K) (or one row, (K,)) as one string of ``SS_LETTERS`` per row."""
+    if not isinstance(ss, torch.Tensor) or ss.is_floating_point() or ss.dtype == torch.bool or ss.dim() not in (1, 2):
+        raise ValueError(f"metrics.ss_strings(): ss must be an integer tensor (rows, K) or (K,) of codes 0..{len(SS_LETTERS) - 1}")
+    codes = ss.detach().cpu().to(torch.int64).reshape(-1, ss.shape[-1])
+    if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) >= len(SS_LETTERS)):
+        raise ValueError(f"metrics.ss_strings(): codes outside 0..{len(SS_LETTERS) - 1}")
+    return ["".join(SS_LETTERS[c] for c in row) for row in codes.tolist()]
+
+
+def hbonds(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
+           antigen_mask: Optional[torch.Tensor] = None, hotspot_mask: Optional[torch.Tensor] = None, chain_idx=None, residue_idx=None,
+           residue_mask: Optional[torch.Tensor] = None, group_size: int = 1) -> Dict[str, torch.Tensor]:
+    """Backbone hydrogen bonds (Kabsch-Sander's electrostatic energy, E < -0.5 kcal/mol) and the secondary structure built on them, of
+    every design.  A generated residue has N, CA, C of its own row's frame; a non-generated residue the patch's real N, CA, C, O -
+    slots 0..3 of ``context['xyz']`` (G,K,A,3), A >= 4, where ``context['atom_mask']`` is set, the order of ``io.read_pdb`` and
+    ``patch.gather`` - shared by the designs of the patch; without ``context``, N, CA, C of the first row of its group and no real O.
+    The carbonyl O the frames do not determine is built in the peptide plane from the next residue's N (at a chain end, the ideal
+    placement of ``io.IDEAL_BACKBONE``), the amide H from the previous residue's C=O; a Pro token (the design's own, or for a
+    non-generated residue that of the first row of the group) has no H.  Chain neighbours by ``chain_idx`` / ``residue_idx`` as in
+    ``backbone``.  K <= 512.
+
+    Per residue: ``O``, ``H`` (rows,K,3), NaN where absent - the atoms ``contacts`` and ``surface`` only approximate;
+    ``nh_o_partner`` / ``nh_o_energy`` and ``o_hn_partner`` / ``o_hn_energy`` (rows,K,2), the two best bonds of the residue's N-H and of
+    its C=O (-1 / 0 where fewer); ``bridge_partner`` (rows,K,2) int32 and ``bridge_parallel`` (rows,K,2) bool; ``ss`` (rows,K) uint8,
+    the code of ``SS_LETTERS`` = " HBEGITS" (``ss_strings`` gives the strings); ``residue_hbonds`` (rows,K) int32, the bonds with a
+    generated end the residue is part of, ready as ``b_factor`` of ``io.write_pdb``.  Per row (rows,), over the bonds with at least one
+    generated end: ``n_hbonds``, ``n_hbonds_internal``, ``n_hbonds_framework``, ``hbond_energy``, ``ss_count`` (rows,8) over the
+    generated residues; with ``antigen_mask`` ``n_hbonds_antigen``; with ``hotspot_mask`` ``n_hotspot_bonded`` and ``n_hotspot``.
+    Every bond, partner and state is an exact function of the fp32 inputs (``include/diffab_hip_hbonds.h``; no parity with mkdssp is
+    claimed: no bulge linking, I after H).  One C-ABI call; results on the device of ``designs['seq_idx']``; ValueError naming the
+    argument before any device work."""
+    who = "metrics.hbonds()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    if K > HBONDS_MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch, at most {HBONDS_MAX_K} (the bond matrix of a row stays on chip)")
+    if antigen_mask is not None:
+        _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    if hotspot_mask is not None:
+        if antigen_mask is None:
+            raise ValueError(f"{who}: hotspot_mask needs an antigen_mask")
+        _check_patch_mask(who, "hotspot_mask", hotspot_mask, G, K)
+    A = 4
+    if context is not None:
+        A = _check_context(who, context, G, K)
+        if A < 4:
+            raise ValueError(f"{who}: context['xyz'] has A = {A} atoms per residue, N, CA, C, O (at least 4) are needed")
+    chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    pts = _hip.dev_f32(backbone_from_frames(x, O, ("N", "CA", "C")))
+    pro = seq.eq(PRO).contiguous()
+    first = torch.arange(G, device=dev) * group_size
+    cpro = pro[first].contiguous()
+    if context is None:
+        cpts = torch.zeros(G, K, 4, 3, dtype=torch.float32, device=dev)
+        cpts[:, :, :3] = pts[first]
+        cvalid = torch.full((G, K), 7, dtype=torch.int32, device=dev)
+    else:
+        cpts = _hip.dev_f32(context["xyz"])
+        cvalid = _valid_word(context["atom_mask"], A, dev)
+    gm = _hip.dev_mask(generation_mask)
+    rm, ag, hs = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask, hotspot_mask))
+    chain, ridx = chain.to(dev), ridx.to(dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = {"O": f32(rows, K, 3), "H": f32(rows, K, 3), "nh_o_partner": i32(rows, K, 2), "nh_o_energy": f32(rows, K, 2),
+           "o_hn_partner": i32(rows, K, 2), "o_hn_energy": f32(rows, K, 2), "bridge_partner": i32(rows, K, 2),
+           "bridge_parallel": torch.empty(rows, K, 2, dtype=torch.bool, device=dev), "ss": torch.empty(rows, K, dtype=torch.uint8, device=dev),
+           "residue_hbonds": i32(rows, K), "n_hbonds": i32(rows), "n_hbonds_internal": i32(rows)}
+    if ag is not None:
+        out["n_hbonds_antigen"] = i32(rows)
+    out["n_hbonds_framework"] = i32(rows)
+    if hs is not None:
+        out.update(n_hotspot_bonded=i32(rows), n_hotspot=i32(rows))
+    out.update(hbond_energy=f32(rows), ss_count=i32(rows, 8))
+    nbytes = hbonds_workspace_bytes(G, K, A)
+    ws = _hip.workspace(nbytes)
+    order = ("O", "H", "nh_o_partner", "nh_o_energy", "o_hn_partner", "o_hn_energy", "bridge_partner", "bridge_parallel", "ss", "residue_hbonds",
+             "n_hbonds", "n_hbonds_internal", "n_hbonds_antigen", "n_hbonds_framework", "n_hotspot_bonded", "n_hotspot", "hbond_energy", "ss_count")
+    _hip.check(lib.diffab_metrics_hbonds(_hip.ptr(pts), _hip.ptr(pro), _hip.ptr(cpts), _hip.ptr(cvalid), _hip.ptr(cpro), _hip.ptr(gm),
+                                         _hip.ptr(rm), _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, A,
+                                         *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
+               "diffab_metrics_hbonds")
     return {k: v.to(out_dev) for k, v in out.items()}
 
 
