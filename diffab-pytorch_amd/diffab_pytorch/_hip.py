@@ -303,6 +303,14 @@ HBOND_SYMBOLS = {
     "diffab_metrics_hbonds": (C.c_int, [_fp] * 11 + [_i32] * 4 + [_fp] * 18 + [_fp, _sz, _fp]),
 }
 
+# every symbol include/diffab_hip_cluster.h declares (the three export lists above are pinned by their tests): same library, a fourth
+# table, open to the next entry that reads a patch's pairwise matrix
+CLUSTER_SYMBOLS = {
+    # (dist, cutoff (G) device, score (nullable), candidates (nullable), G, N, M, label, center_dist (nullable), center, size, count,
+    #  n_unassigned (nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_cluster": (C.c_int, [_fp] * 4 + [_i32] * 3 + [_fp] * 6 + [_fp, _sz, _fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -315,7 +323,8 @@ def load_library() -> C.CDLL:
                 f"{LIB_PATH} is missing - build it with `make -C diffab-pytorch_amd/csrc` "
                 "(or __graft_entry__.build()); there is no CPU fallback for this path")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items()):
+        for name, (res, args) in (list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items())
+                                   + list(CLUSTER_SYMBOLS.items())):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

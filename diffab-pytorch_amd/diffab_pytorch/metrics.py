@@ -3,6 +3,9 @@
 ``evaluate``        per design: amino-acid recovery, RMSD in the fixed framework and after superposition, whole row and per segment (CDR);
 ``pairwise``        per patch: the N x N RMSD and sequence-identity matrices of its N designs;
 ``select_diverse``  greedy farthest-point choice of m designs per patch from such a matrix;
+``cluster``         per patch: its designs grouped into families by neighbour count at a distance cutoff of such a matrix - labels, centres,
+                    sizes, one representative each; ``cluster_weights`` turns a family into ``ensemble``'s weights (DESIGN section 4.21,
+                    ``csrc/cluster_kernels.hip``);
 ``backbone``        per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
 ``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
@@ -19,10 +22,10 @@ Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` retur
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
 the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
 ``_similarity`` in ``include/diffab_hip.h``, of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h`` and of ``diffab_metrics_hbonds`` in
-``include/diffab_hip_hbonds.h``; every number is
+``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` in ``include/diffab_hip_cluster.h``; every number is
 computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters),
-``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip`` and ``csrc/hbond_kernels.hip``, and there is
-no torch fallback.
+``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip`` and
+``csrc/cluster_kernels.hip``, and there is no torch fallback.
 """
 from __future__ import annotations
 
@@ -53,6 +56,7 @@ GLY = AA3.index("GLY")
 PRO = AA3.index("PRO")  # hbonds(): no amide hydrogen
 HBONDS_MAX_K = 512  # DIFFAB_HBONDS_MAX_K: hbonds keeps the K x K bond bits of a row on chip
 SS_LETTERS = " HBEGITS"  # hbonds()['ss']: none, alpha helix, lone bridge, ladder, 3-10 helix, pi helix, turn, bend
+CLUSTER_LDS_MAX_N = 1024  # DIFFAB_METRICS_CLUSTER_LDS_MAX_N: up to here cluster keeps the N x N neighbour bits of a patch on chip
 SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256  # DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
@@ -225,6 +229,94 @@ def select_diverse(dist: torch.Tensor, m: int, *, score: Optional[torch.Tensor] 
     _hip.check(lib.diffab_metrics_select_diverse(_hip.ptr(d), _hip.ptr(sc), _hip.ptr(cand), G, N, m, _hip.ptr(index), _hip.ptr(min_dist),
                                                  _hip.ptr(count), _hip.stream_ptr()), "diffab_metrics_select_diverse")
     return {"index": index.to(out_dev), "min_dist": min_dist.to(out_dev), "count": count.to(out_dev)}
+
+
+# ------------------------------------------------------------------ design clusters
+def cluster_workspace_bytes(G: int, N: int) -> int:
+    """DIFFAB_METRICS_CLUSTER_WORKSPACE_BYTES of include/diffab_hip_cluster.h."""
+    Np = (N + 63) // 64 * 64
+    return G * (Np * Np // 8 + (N + 255) // 256 * Np * 4) + 1024
+
+
+def cluster(dist: torch.Tensor, cutoff, *, candidates: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
+            max_clusters: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """The designs of each patch grouped into families: Daura / GROMOS neighbour-count clustering of ``dist`` (G,N,N) fp32
+    (``pairwise``'s ``rmsd``, or ``1 - seq_identity``) at ``cutoff``, a number or a (G,) tensor.  j is a neighbour of i when
+    ``dist[g,i,j] <= cutoff[g]`` (the row of i; a NaN is no neighbour; every design is its own).  The open set starts as
+    ``candidates`` (G,N) bool (all without it); while it is not empty and fewer than ``max_clusters`` (an int in [0, N]; None = N)
+    clusters are made, the open design with the most open neighbours - ties to the lower ``score`` (G,N) (a NaN counts as +inf), then
+    to the lower index - becomes a centre, and it and its open neighbours leave as one cluster.
+
+    Returns ``label`` (G,N) int32, the cluster of every design (-1: not a candidate, or still open when ``max_clusters`` was
+    reached), ``center_dist`` (G,N) fp32, its distance from its centre as stored in the centre's row (0 for the centre, NaN where the
+    label is -1), ``center`` (G,M) int64 and ``size`` (G,M) int32 per cluster, largest first (-1 / 0 past ``count``), ``count`` (G,)
+    int32, ``n_unassigned`` (G,) int32, the candidates still open, and ``representative`` (G,N) bool, true at the centres - ready as
+    ``select_diverse(candidates=...)`` or as a filter; ``cluster_weights`` makes ``ensemble``'s weights of one cluster.  Compares,
+    popcounts and integer adds only: the result is a function of the fp32 matrix.  One C-ABI call (two launches); results on
+    ``dist``'s device; ValueError naming the argument before any device work."""
+    who = "metrics.cluster()"
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 3 or dist.shape[1] != dist.shape[2]:
+        raise ValueError(f"{who}: dist must be a float32 tensor (G, N, N)")
+    G, N = int(dist.shape[0]), int(dist.shape[1])
+    if N < 1 or N > MAX_GROUP:
+        raise ValueError(f"{who}: dist has N = {N} designs per patch, outside [1, {MAX_GROUP}]")
+    if isinstance(cutoff, torch.Tensor):
+        if not cutoff.is_floating_point() or tuple(cutoff.shape) != (G,):
+            raise ValueError(f"{who}: cutoff must be a number or a float tensor {(G,)}")
+    elif isinstance(cutoff, bool) or not isinstance(cutoff, (int, float)):
+        raise ValueError(f"{who}: cutoff must be a number or a float tensor {(G,)}, got {cutoff!r}")
+    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.bool
+                                   or tuple(candidates.shape) != (G, N)):
+        raise ValueError(f"{who}: candidates must be a bool tensor {(G, N)}")
+    if score is not None and (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (G, N)):
+        raise ValueError(f"{who}: score must be a float tensor {(G, N)}")
+    M = N if max_clusters is None else max_clusters
+    if not _is_int(M) or M < 0 or M > N:
+        raise ValueError(f"{who}: max_clusters must be an int in [0, N = {N}] or None, got {max_clusters!r}")
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), dist.device
+    d = _hip.dev_f32(dist)
+    cut = _hip.dev_f32(cutoff) if isinstance(cutoff, torch.Tensor) else torch.full((G,), float(cutoff), dtype=torch.float32, device=dev)
+    sc = None if score is None else _hip.dev_f32(score)
+    cand = None if candidates is None else _hip.dev_mask(candidates)
+    label = torch.empty(G, N, dtype=torch.int32, device=dev)
+    center_dist = torch.empty(G, N, dtype=torch.float32, device=dev)
+    center = torch.empty(G, M, dtype=torch.int64, device=dev)
+    size = torch.empty(G, M, dtype=torch.int32, device=dev)
+    count = torch.empty(G, dtype=torch.int32, device=dev)
+    left = torch.empty(G, dtype=torch.int32, device=dev)
+    nbytes = cluster_workspace_bytes(G, N)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_cluster(_hip.ptr(d), _hip.ptr(cut), _hip.ptr(sc), _hip.ptr(cand), G, N, M, _hip.ptr(label),
+                                          _hip.ptr(center_dist), _hip.ptr(center), _hip.ptr(size), _hip.ptr(count), _hip.ptr(left),
+                                          _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_cluster")
+    rep = torch.zeros(G, N + 1, dtype=torch.bool, device=dev)  # (column N takes the -1 padding of center)
+    rep.scatter_(1, torch.where(center < 0, N, center), True)
+    out = {"label": label, "center_dist": center_dist, "center": center, "size": size, "count": count, "n_unassigned": left,
+           "representative": rep[:, :N].contiguous()}
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+def cluster_weights(clusters: Dict[str, torch.Tensor], cluster=0) -> torch.Tensor:
+    """(G,N) fp32 weights, 1 on the designs of one cluster of ``cluster()``'s result and 0 elsewhere: the mask ``ensemble(weights=...)``
+    takes.  ``cluster`` is one index >= 0 for every patch (0: the largest family) or a (G,) integer tensor of indices; an index past a
+    patch's ``count`` gives that patch all zeros."""
+    who = "metrics.cluster_weights()"
+    label = clusters.get("label") if isinstance(clusters, dict) else None
+    if not isinstance(label, torch.Tensor) or label.dim() != 2 or label.is_floating_point() or label.dtype == torch.bool:
+        raise ValueError(f"{who}: clusters must be the dict metrics.cluster() returns, with an integer label (G, N)")
+    G = int(label.shape[0])
+    if isinstance(cluster, torch.Tensor):
+        if cluster.is_floating_point() or cluster.dtype == torch.bool or tuple(cluster.shape) != (G,):
+            raise ValueError(f"{who}: cluster must be an int >= 0 or an integer tensor {(G,)}")
+        if G and int(cluster.min()) < 0:
+            raise ValueError(f"{who}: cluster holds a negative index (label -1 marks the designs of no cluster)")
+        which = cluster.to(device=label.device, dtype=label.dtype)[:, None]
+    elif not _is_int(cluster) or cluster < 0:
+        raise ValueError(f"{who}: cluster must be an int >= 0 or an integer tensor {(G,)}, got {cluster!r}")
+    else:
+        which = cluster
+    return label.eq(which).to(torch.float32)
 
 
 # ------------------------------------------------------------------ design filters (DESIGN section 4.15)
