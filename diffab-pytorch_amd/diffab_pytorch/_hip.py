@@ -309,6 +309,10 @@ CLUSTER_SYMBOLS = {
     # (dist, cutoff (G) device, score (nullable), candidates (nullable), G, N, M, label, center_dist (nullable), center, size, count,
     #  n_unassigned (nullable), workspace, workspace_bytes, stream)
     "diffab_metrics_cluster": (C.c_int, [_fp] * 4 + [_i32] * 3 + [_fp] * 6 + [_fp, _sz, _fp]),
+    # (objectives, maximize (M) device (nullable), violation (nullable), score (nullable), candidates (nullable), G, N, M, F, rank,
+    #  n_dominators (nullable), n_dominated (nullable), front_size, count, n_unranked (nullable), order (nullable), workspace,
+    #  workspace_bytes, stream)
+    "diffab_metrics_pareto": (C.c_int, [_fp] * 5 + [_i32] * 4 + [_fp] * 7 + [_fp, _sz, _fp]),
 }
 
 _lib: Optional[C.CDLL] = None

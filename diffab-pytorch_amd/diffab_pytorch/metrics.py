@@ -6,7 +6,10 @@
 ``cluster``         per patch: its designs grouped into families by neighbour count at a distance cutoff of such a matrix - labels, centres,
                     sizes, one representative each; ``cluster_weights`` turns a family into ``ensemble``'s weights (DESIGN section 4.21,
                     ``csrc/cluster_kernels.hip``);
-``backbone``        per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
+``pareto``          per patch: its designs ranked into non-dominated fronts over several objectives at once, some minimised, some
+                    maximised, with hard limits by constrained domination - ranks, front sizes, domination counts, a best-first
+                    order and the mask of front 0 (DESIGN section 4.22, ``csrc/pareto_kernels.hip``);
+``backbone``      per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
 ``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
@@ -22,10 +25,10 @@ Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` retur
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
 the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
 ``_similarity`` in ``include/diffab_hip.h``, of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h`` and of ``diffab_metrics_hbonds`` in
-``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` in ``include/diffab_hip_cluster.h``; every number is
-computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters),
-``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip`` and
-``csrc/cluster_kernels.hip``, and there is no torch fallback.
+``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` and ``diffab_metrics_pareto`` in ``include/diffab_hip_cluster.h``;
+every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters, DESIGN
+section 4.15), ``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip``,
+``csrc/cluster_kernels.hip`` and ``csrc/pareto_kernels.hip``, and there is no torch fallback.
 """
 from __future__ import annotations
 
@@ -57,7 +60,8 @@ PRO = AA3.index("PRO")  # hbonds(): no amide hydrogen
 HBONDS_MAX_K = 512  # DIFFAB_HBONDS_MAX_K: hbonds keeps the K x K bond bits of a row on chip
 SS_LETTERS = " HBEGITS"  # hbonds()['ss']: none, alpha helix, lone bridge, ladder, 3-10 helix, pi helix, turn, bend
 CLUSTER_LDS_MAX_N = 1024  # DIFFAB_METRICS_CLUSTER_LDS_MAX_N: up to here cluster keeps the N x N neighbour bits of a patch on chip
-SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256  # DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
+PARETO_MAX_OBJECTIVES = 16  # DIFFAB_METRICS_PARETO_MAX_OBJECTIVES: objectives of pareto
+SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256 # DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
 
@@ -317,6 +321,109 @@ def cluster_weights(clusters: Dict[str, torch.Tensor], cluster=0) -> torch.Tenso
     else:
         which = cluster
     return label.eq(which).to(torch.float32)
+
+
+# ------------------------------------------------------------------ Pareto fronts
+def pareto_workspace_bytes(G: int, N: int) -> int:
+    """DIFFAB_METRICS_PARETO_WORKSPACE_BYTES of include/diffab_hip_cluster.h."""
+    Np = (N + 63) // 64 * 64
+    return G * (Np * Np // 8 + (N + 255) // 256 * Np * 4 + Np // 64 * Np * 4) + 1024
+
+
+def _objective_table(who: str, objectives, group_size) -> torch.Tensor:
+    """(G,N,M) from a (G,N,M) float32 tensor, or from a sequence of M per-design tensors of G * N elements each."""
+    if isinstance(objectives, torch.Tensor):
+        if objectives.dtype != torch.float32 or objectives.dim() != 3:
+            raise ValueError(f"{who}: objectives must be a float32 tensor (G, N, M) or a sequence of per-design tensors, got a "
+                             f"{tuple(objectives.shape)} {objectives.dtype} tensor")
+        if group_size is not None and (not _is_int(group_size) or group_size != objectives.shape[1]):
+            raise ValueError(f"{who}: group_size = {group_size!r} does not match objectives {tuple(objectives.shape)}")
+        return objectives
+    if not isinstance(objectives, (list, tuple)) or len(objectives) == 0 or not all(isinstance(o, torch.Tensor) for o in objectives):
+        raise ValueError(f"{who}: objectives must be a float32 tensor (G, N, M) or a non-empty sequence of per-design tensors")
+    if len(objectives) > PARETO_MAX_OBJECTIVES:
+        raise ValueError(f"{who}: objectives holds M = {len(objectives)} objectives, outside [1, {PARETO_MAX_OBJECTIVES}]")
+    first = objectives[0]
+    for m, o in enumerate(objectives):
+        if o.dtype == torch.bool or o.is_complex() or o.dim() not in (1, 2):
+            raise ValueError(f"{who}: objectives[{m}] must be a float or integer tensor (G * N,) or (G, N), got {tuple(o.shape)} {o.dtype}")
+        if tuple(o.shape) != tuple(first.shape):
+            raise ValueError(f"{who}: objectives[{m}] is {tuple(o.shape)}, objectives[0] is {tuple(first.shape)}")
+    if first.dim() == 2:
+        if group_size is not None and (not _is_int(group_size) or group_size != first.shape[1]):
+            raise ValueError(f"{who}: group_size = {group_size!r} does not match objectives[0] {tuple(first.shape)}")
+        G, N = int(first.shape[0]), int(first.shape[1])
+    else:
+        if not _is_int(group_size) or group_size < 1:
+            raise ValueError(f"{who}: group_size must be an int >= 1 for flat per-design objectives, got {group_size!r}")
+        if first.shape[0] % group_size != 0:
+            raise ValueError(f"{who}: {first.shape[0]} design rows are not a multiple of group_size = {group_size}")
+        G, N = int(first.shape[0]) // group_size, group_size
+    return torch.stack([o.to(device=first.device, dtype=torch.float32).reshape(G, N) for o in objectives], dim=-1)
+
+
+def pareto(objectives, *, group_size: Optional[int] = None, maximize=None, violation: Optional[torch.Tensor] = None,
+           score: Optional[torch.Tensor] = None, candidates: Optional[torch.Tensor] = None,
+           max_fronts: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """The designs of each patch ranked into non-dominated fronts over M objectives: Pareto ranking with Deb's constrained domination.
+    ``objectives`` is a float32 (G,N,M) tensor, or a sequence of M per-design tensors of G * N elements each, shaped (G * N,) as the
+    filters return them (then ``group_size`` = N is required) or (G,N); integer tensors are converted.  Every objective is minimised
+    unless ``maximize``, a bool or a sequence of M bools, says otherwise; a NaN is the worst value of its objective.  ``violation``
+    (G,N) float is a hard limit's overshoot: values <= 0 are feasible, a smaller violation dominates whatever the objectives say, and a
+    NaN is the largest.  i dominates j when both are ``candidates`` (G,N) bool (all without it) and i violates less, or they violate
+    alike and i is no worse in every objective and better in one; equal designs share a front.  Front 0 is every candidate nobody
+    dominates, front 1 the same among the rest, and so on up to ``max_fronts`` (an int in [0, N]; None = N).
+
+    Returns ``rank`` (G,N) int32 (-1: not a candidate, or still open after ``max_fronts``), ``n_dominators`` and ``n_dominated`` (G,N)
+    int32 over all candidates (-1 for a non-candidate), ``front_size`` (G,F) int32 (0 past ``count``), ``count`` (G,) int32,
+    ``n_unranked`` (G,) int32, ``order`` (G,N) int64 - a permutation, best first, by (front, ``score`` (G,N) with NaN = +inf, more
+    designs dominated first, index), unranked candidates and then non-candidates last, so front r is a slice of it - and ``front``
+    (G,N) bool, true where ``rank == 0``: ready for ``select_diverse(candidates=...)`` and, as ``front.float()``, for
+    ``ensemble(weights=...)``.  Compares, popcounts and integer adds only: the result is a function of the fp32 inputs.  One C-ABI
+    call (two launches); results on the objectives' device; ValueError naming the argument before any device work."""
+    who = "metrics.pareto()"
+    obj = _objective_table(who, objectives, group_size)
+    G, N, M = (int(v) for v in obj.shape)
+    if N < 1 or N > MAX_GROUP:
+        raise ValueError(f"{who}: objectives has N = {N} designs per patch, outside [1, {MAX_GROUP}]")
+    if M < 1 or M > PARETO_MAX_OBJECTIVES:
+        raise ValueError(f"{who}: objectives holds M = {M} objectives, outside [1, {PARETO_MAX_OBJECTIVES}]")
+    if maximize is None or isinstance(maximize, bool):
+        flags = [bool(maximize)] * M
+    elif isinstance(maximize, (list, tuple)) and len(maximize) == M and all(isinstance(b, bool) for b in maximize):
+        flags = list(maximize)
+    else:
+        raise ValueError(f"{who}: maximize must be a bool or a sequence of M = {M} bools, got {maximize!r}")
+    if violation is not None and (not isinstance(violation, torch.Tensor) or not violation.is_floating_point()
+                                  or tuple(violation.shape) != (G, N)):
+        raise ValueError(f"{who}: violation must be a float tensor {(G, N)}")
+    if score is not None and (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (G, N)):
+        raise ValueError(f"{who}: score must be a float tensor {(G, N)}")
+    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.bool
+                                   or tuple(candidates.shape) != (G, N)):
+        raise ValueError(f"{who}: candidates must be a bool tensor {(G, N)}")
+    F = N if max_fronts is None else max_fronts
+    if not _is_int(F) or F < 0 or F > N:
+        raise ValueError(f"{who}: max_fronts must be an int in [0, N = {N}] or None, got {max_fronts!r}")
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), obj.device
+    o = _hip.dev_f32(obj)
+    mx = torch.tensor(flags, dtype=torch.bool, device=dev) if any(flags) else None
+    vio = None if violation is None else _hip.dev_f32(violation)
+    sc = None if score is None else _hip.dev_f32(score)
+    cand = None if candidates is None else _hip.dev_mask(candidates)
+    i32 = dict(dtype=torch.int32, device=dev)
+    rank, by, of = (torch.empty(G, N, **i32) for _ in range(3))
+    front_size, count, left = torch.empty(G, F, **i32), torch.empty(G, **i32), torch.empty(G, **i32)
+    order = torch.empty(G, N, dtype=torch.int64, device=dev)
+    nbytes = pareto_workspace_bytes(G, N)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_pareto(_hip.ptr(o), _hip.ptr(mx), _hip.ptr(vio), _hip.ptr(sc), _hip.ptr(cand), G, N, M, F, _hip.ptr(rank),
+                                         _hip.ptr(by), _hip.ptr(of), _hip.ptr(front_size), _hip.ptr(count), _hip.ptr(left), _hip.ptr(order),
+                                         _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_pareto")
+    out = {"rank": rank, "n_dominators": by, "n_dominated": of, "front_size": front_size, "count": count, "n_unranked": left,
+           "order": order, "front": rank.eq(0)}
+    return {k: v.to(out_dev) for k, v in out.items()}
 
 
 # ------------------------------------------------------------------ design filters (DESIGN section 4.15)
