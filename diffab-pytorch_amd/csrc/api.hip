@@ -8,6 +8,7 @@
 #include "common.h"
 #include "denoiser_internal.h"
 #include "mlp_chain_tile.h"
+#include "../../include/diffab_hip_debug.h"
 
 namespace diffab {
 
@@ -229,15 +230,18 @@ struct ForwardPlan {
   const unsigned char* last_layer_tiles;  // [B][K / 16] row tiles of the LAST layer whose outputs are read (null: all)
   const int* last_layer_rows;             // the module launch's form of the same: launch_row_plan (null with last_layer_tiles)
   float* res_emb;                         // the residue embedding after the IPA module is copied here (null: not wanted)
+  // reverse sampler, module launch with a row plan: [B] the start class of every patch by its last-layer work (launch_start_classes;
+  // null: the static classes)
+  const unsigned char* start_class;
 };
 
 // loop: the call runs many forwards (reverse sampler, design scoring).  There the pair embedding is the same tensor in every attention
 // launch, so its fp16 planes are on unless DIFFAB_FLAG_PAIR_F32, and the module launch is chosen by module_launch_fills_chip unless
 // DIFFAB_FLAG_MULTI_LAUNCH; a single forward takes both from its flags.  tiles, row_plan: the reverse sampler's buffers of the row-tile
-// map and of the row plan.
+// map and of the row plan; start_class: its buffer of the work-groups' start classes.
 static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const StepBuffers& b, const float* res_ctx, const float* pair_ctx,
                                 float* res_emb, bool loop, const int* ctx_of_row = nullptr, int n_ctx = 0, unsigned char* tiles = nullptr,
-                                int* row_plan = nullptr) {
+                                int* row_plan = nullptr, unsigned char* start_class = nullptr) {
   const int rows = d->B * d->K, D = d->D;
   if (loop && !(flags & DIFFAB_FLAG_PAIR_F32)) flags |= DIFFAB_FLAG_PAIR_PLANES;
   ForwardPlan p{};
@@ -268,6 +272,11 @@ static ForwardPlan plan_forward(const diffab_dims* d, uint32_t flags, const Step
   // The module launch walks the last layer's rows by the row plan (16-row windows from the generated rows: fewer items than aligned
   // tiles); the per-layer launches keep the tile map.
   p.last_layer_rows = p.persistent && p.last_layer_tiles != nullptr ? row_plan : nullptr;
+  // The plan says what a patch's last layer costs: the launch starts the heaviest patches first (timing only).  K = 128 only, where
+  // it was measured; K = 256 keeps the static classes.
+  p.start_class = p.last_layer_rows != nullptr && d->K == 128 && module_stagger_classes() > 1 && module_stagger_classes() <= 256
+                      ? start_class
+                      : nullptr;
   return p;
 }
 
@@ -369,7 +378,7 @@ static int denoise_step(const diffab_dims* d, const diffab_denoiser_weights* w, 
   }
   if (p.persistent) {
     if (int rc = launch_ipa_module_persistent(d, b.hA, b.hB, O_t, x_t, b.ipa, b.planes, p.pair_planes, st, p.fused_mlps ? res_ctx : nullptr,
-                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx, p.last_layer_rows))
+                                              &emb_set, &head_set, p.ctx_of_row, p.n_ctx, p.last_layer_rows, p.start_class))
       return rc;
     cur = (d->NL & 1) ? b.hB : b.hA;
   }
@@ -443,6 +452,7 @@ struct SampleBuffers {
   int* t_dev;  // the current timestep in device memory (graph replay)
   unsigned char* tiles;  // [B][K / 16]: row tiles with a generated residue (the last layer's attention runs for these only)
   int* row_plan;         // [B][2 + K / 16]: the module launch's items of the last layer (launch_row_plan)
+  unsigned char* start_class;  // [B] (whole words): the module launch's start class of every patch (launch_start_classes)
   float* beta_traj;      // [3 heads][kTrajRows][D]: the heads' folded beta columns of every step of a schedule with T < kTrajRows
   int* ctx_of_row;       // shared contexts: [B] the context of every state row (device copy of the caller's map)
   float* res_ctx;        // shared contexts: [B][K][D] the residue context of every state row (gathered once per call)
@@ -467,6 +477,8 @@ static SampleBuffers carve_sample(const diffab_dims* d, void* ws, int n_pair = 0
   s.res_ctx = mapped ? c.take<float>(rows * d->D) : nullptr;  // 256-byte aligned: the folded embedding MLP takes it as it takes the caller's
   const size_t step_bytes = carve_step(d, nullptr, n_pair).bytes;
   s.step = c.take<char>(step_bytes);
+  // (behind everything else: no other buffer of the workspace moves for it - the pair planes keep their place relative to the base)
+  s.start_class = c.take<unsigned char>((static_cast<size_t>(d->B) + 3) & ~static_cast<size_t>(3));
   s.bytes = c.bytes();
   return s;
 }
@@ -601,6 +613,17 @@ int diffab_debug_row_plan(const uint8_t* gen_mask, int32_t B, int32_t K, int32_t
   DIFFAB_REQUIRE(gen_mask && plan && B >= 1 && K >= 16 && K <= 1024 && K % 16 == 0, DIFFAB_ERR_ARG,
                  "debug_row_plan: need B >= 1 and K a multiple of 16 in 16 .. 1024");
   return launch_row_plan(gen_mask, B, K, plan, as_stream(stream));
+}
+
+int diffab_debug_start_classes(const int32_t* plan, int32_t B, int32_t K, int32_t classes, uint8_t* out, int32_t on_device, void* stream) {
+  DIFFAB_REQUIRE(plan && out && B >= 1 && K >= 16 && K <= 1024 && K % 16 == 0 && classes >= 1 && classes <= 256, DIFFAB_ERR_ARG,
+                 "debug_start_classes: need B >= 1, K a multiple of 16 in 16 .. 1024 and 1 .. 256 classes");
+  if (on_device) {  // the sampler's own launch, on device buffers
+    StreamOrder order_(stream);
+    return launch_start_classes(plan, B, K, classes, out, as_stream(stream));
+  }
+  for (int b = 0; b < B; ++b) out[b] = static_cast<uint8_t>(start_class_of(plan, B, K, classes, b));  // (the device kernel's function, on the host)
+  return DIFFAB_OK;
 }
 
 int diffab_debug_set_attn_variant(int32_t v) { return set_attn_variant(v); }
@@ -1145,7 +1168,8 @@ int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w
     res_ctx = sb.res_ctx;
   }
   const StepBuffers b0 = carve_step(d, sb.step, n_ctx);
-  const ForwardPlan plan = plan_forward(d, flags, b0, res_ctx, pair_ctx, nullptr, true, ctx_dev, n_ctx, sb.tiles, sb.row_plan);
+  const ForwardPlan plan = plan_forward(d, flags, b0, res_ctx, pair_ctx, nullptr, true, ctx_dev, n_ctx, sb.tiles, sb.row_plan,
+                                        sb.start_class);
   // The heads' folded beta columns depend on (step, head, column) only - every patch of a reverse step has the same beta - so the table
   // of ALL steps is built once per call instead of once per step.  Eager loop only: under graph replay the step index lives in device
   // memory and the chain's bias pointer is a launch argument.
@@ -1156,6 +1180,8 @@ int diffab_sample_loop_ex(const diffab_dims* d, const diffab_denoiser_weights* w
     if (int rc = launch_tiles_needed(gen_mask, d->B, d->K, sb.tiles, st)) return rc;
   if (plan.last_layer_rows)
     if (int rc = launch_row_plan(gen_mask, d->B, d->K, sb.row_plan, st)) return rc;
+  if (plan.start_class)
+    if (int rc = launch_start_classes(sb.row_plan, d->B, d->K, module_stagger_classes(), sb.start_class, st)) return rc;
   if (rec != nullptr) {  // the step -> slot table, and the residues the loop never writes, once per call
     DIFFAB_HIP_CHECK(hipMemcpyAsync(rec->slot_dev, rec->slot_of_step, sizeof(int32_t) * (s->T + 1), hipMemcpyHostToDevice, st));
     if (int rc = launch_record_fixed(uo.rec, seq, x, O, gen_mask, d->B, d->K, d->V, st)) return rc;

@@ -136,7 +136,9 @@ bool ipa_module_persistent_supported(const diffab_dims* d);
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X = nullptr, const MlpChainSet* emb = nullptr,
                                  const MlpChainSet* heads = nullptr, const int* ctx_of_row = nullptr, int n_ctx = 0,
-                                 const int* last_layer_rows = nullptr);  // launch_row_plan's [B][2 + K / 16] ints
+                                 const int* last_layer_rows = nullptr,  // launch_row_plan's [B][2 + K / 16] ints
+                                 const unsigned char* start_class = nullptr);  // launch_start_classes (null: the static classes)
+int module_stagger_classes();  // the classes the module launch spreads its work-groups' starts over (<= 1: no stagger)
 void set_module_stagger(int ticks, int classes);  // diagnostics: start-up stagger of the persistent module kernel (10 ns ticks)
 void set_module_stamps(void* device_buffer);      // diagnostics: phase stamps of the persistent module kernel
 // bias tables of the folded concatenations (see denoiser_fast.hip): emb_tab[25][D] depends on the weights only; beta_tab[3 heads][B][D]
@@ -387,6 +389,27 @@ int launch_tiles_needed(const uint8_t* gm, int B, int K, unsigned char* out, hip
 // ((K + 31) / 32 slabs, the last one short when K % 32 != 0: K = 16 is one slab).  K % 16 == 0, 16 <= K <= 1024.
 constexpr int row_plan_ints(int K) { return 2 + K / 16; }
 int launch_row_plan(const uint8_t* gm, int B, int K, int* out, hipStream_t st);
+// The start class of patch b's work-group in the module launch, from the row plan: the launch staggers its work-groups' starts over
+// `classes` classes (ipa_persistent.hip), and what a patch's LAST layer costs is known from its plan (items first, then live slabs) -
+// the patches with the most start first, so that the extra items end inside the launch instead of at its end.  Patches ranked by
+// descending (items, slabs), ties by the static class (b / 8) % classes and then by b; class = rank * classes / B: every class keeps
+// B / classes patches (floor or ceiling), the spread of the starts is what it was.  Timing only: no result depends on it.
+__host__ __device__ inline int start_class_of(const int* plan, int B, int K, int classes, int b) {
+  const int n = row_plan_ints(K);
+  auto key = [&](int i) {  // larger: more work in the last layer; then the earlier static class
+    const int* p = plan + static_cast<int64_t>(i) * n;
+    return ((p[0] * 64 + __builtin_popcount(static_cast<unsigned>(p[1]))) * classes) + (classes - 1 - (i >> 3) % classes);
+  };
+  const int kb = key(b);
+  int64_t rank = 0;
+  for (int i = 0; i < B; ++i) {
+    const int ki = key(i);
+    rank += ki > kb || (ki == kb && i < b);
+  }
+  return static_cast<int>(rank * classes / B);
+}
+// out[b] = start_class_of(plan, ..., b), one byte per patch (classes <= 256); out holds B bytes rounded up to a multiple of 4
+int launch_start_classes(const int* plan, int B, int K, int classes, unsigned char* out, hipStream_t st);
 // shared contexts: out[b] = src[ctx_of_row[b]] for the B rows of `row_floats` floats each (16-byte aligned rows)
 int launch_gather_rows(const float* src, const int* ctx_of_row, int B, int64_t row_floats, float* out, hipStream_t st);
 // design scoring (diffab_score_designs): a chunk of evaluated rows q = ((r n_t) + j) n_draws + m, q0 .. q0 + valid - 1, in buffers of

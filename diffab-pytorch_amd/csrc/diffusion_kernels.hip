@@ -1427,6 +1427,16 @@ int launch_row_plan(const uint8_t* gm, int B, int K, int* out, hipStream_t st) {
   DIFFAB_LAUNCH_CHECK();
   return DIFFAB_OK;
 }
+__global__ void start_classes_kernel(const int* __restrict__ plan, int B, int K, int classes, unsigned char* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per patch, B plan reads each: once per call
+  if (b < B) out[b] = static_cast<unsigned char>(start_class_of(plan, B, K, classes, b));
+}
+int launch_start_classes(const int* plan, int B, int K, int classes, unsigned char* out, hipStream_t st) {
+  DIFFAB_REQUIRE(classes >= 1 && classes <= 256, DIFFAB_ERR_ARG, "start_classes: %d classes outside 1 .. 256", classes);
+  hipLaunchKernelGGL(start_classes_kernel, dim3(static_cast<unsigned>((B + 63) / 64)), dim3(64), 0, st, plan, B, K, classes, out);
+  DIFFAB_LAUNCH_CHECK();
+  return DIFFAB_OK;
+}
 // shared contexts (diffab_sample_options.ctx_of_row): the residue context rows of every state row, once per call
 __global__ void gather_rows_kernel(const float* __restrict__ src, const int* __restrict__ ctx_of_row, int64_t row_floats, int64_t n,
                                    float* __restrict__ out) {

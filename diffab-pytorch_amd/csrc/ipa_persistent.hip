@@ -59,6 +59,9 @@ struct ModuleArgs {
   MlpChainSet emb, heads;
   int B, NL;
   int stagger_ticks, stagger_classes;  // the work-groups of class c = (blockIdx / 8) % classes start c * ticks (10 ns each) late
+  // reverse sampler, K = 128 with a row plan: the start class of every patch's work-group by its last-layer work (launch_start_classes),
+  // read by the PLANNED_START form of the kernel alone (last: the other arguments keep their places)
+  const unsigned char* start_class;
 };
 }  // namespace
 
@@ -72,7 +75,10 @@ __device__ __forceinline__ int module_plan_word(const int* __restrict__ plan, co
 
 // KRES: residues per patch - 128 (one 128-row dense tile per patch, single-chunk attention items) or 256 (BASELINE config 5: two dense
 // tiles, sixteen attention items of two 128-key chunks with the online softmax across them - ipa_attn_tile<8, true, ...>)
-template <int KRES>
+// PLANNED_START: the start class of a work-group is the byte of its first patch in a.start_class instead of the static one.  Its own
+// instantiation: every launch without the bytes (no plan, DIFFAB_FLAG_ALL_ROWS, diffab_denoise_step_fwd, scoring, K = 256) runs the
+// code it ran before, instruction for instruction.
+template <int KRES, bool PLANNED_START = false>
 __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const ModuleArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int K = KRES, NTILE = K / TI, DT = K / 128;  // DT: dense 128-row tiles per patch
@@ -81,7 +87,11 @@ __global__ __launch_bounds__(512) void ipa_module_persistent_kernel(const Module
   if (a.stagger_ticks > 0 && a.stagger_classes > 1) {
     // (every wave waits for itself: no barrier needed, the first phase starts with loads only)
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long wait = static_cast<unsigned long long>((blockIdx.x >> 3) % a.stagger_classes) * a.stagger_ticks;
+    // (the class byte through a scalar load of its word, as the plan's words)
+    const int cls = PLANNED_START
+                        ? (module_plan_word(reinterpret_cast<const int*>(a.start_class), blockIdx.x >> 2) >> (8 * (blockIdx.x & 3))) & 255
+                        : static_cast<int>((blockIdx.x >> 3) % a.stagger_classes);
+    const unsigned long long wait = static_cast<unsigned long long>(cls) * a.stagger_ticks;
     while (__builtin_amdgcn_s_memrealtime() - t0 < wait) __builtin_amdgcn_s_sleep(32);
   }
   unsigned long long* pstamps = a.stamps ? a.stamps + static_cast<size_t>(a.B) * a.NL * NTILE * 64 : nullptr;
@@ -242,6 +252,7 @@ void set_module_stagger(int ticks, int classes) {
   g_stagger_classes = classes;
 }
 void set_module_stamps(void* p) { g_module_stamps = static_cast<unsigned long long*>(p); }
+int module_stagger_classes() { return g_stagger_ticks > 0 ? g_stagger_classes : 1; }
 
 bool ipa_module_persistent_supported(const diffab_dims* d) {
   return fast_path_supported(d) && (d->K == 128 || d->K == 256) && d->NL >= 1;
@@ -253,9 +264,11 @@ bool ipa_module_persistent_supported(const diffab_dims* d) {
 // its items only and the heads (when fused) its slabs only
 // emb_X (optional, with emb and heads): the embedding MLP's input rows - the launch then also runs the embedding MLP (-> xa) and the three
 // heads (module output -> heads->Y[]) of every patch
+// start_class (optional, with a row plan): launch_start_classes' byte per patch, the start class of its work-group
 int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, const float* R, const float* t, float* ws, const void* planes,
                                  const float* pair_planes, hipStream_t st, const float* emb_X, const MlpChainSet* emb,
-                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx, const int* last_layer_rows) {
+                                 const MlpChainSet* heads, const int* ctx_of_row, int n_ctx, const int* last_layer_rows,
+                                 const unsigned char* start_class) {
   DIFFAB_REQUIRE(ipa_module_persistent_supported(d) && xa && xb && R && t && ws && planes && pair_planes, DIFFAB_ERR_ARG,
                  "ipa_module_persistent: unsupported operands");
   DIFFAB_REQUIRE((reinterpret_cast<uintptr_t>(last_layer_rows) & 3) == 0, DIFFAB_ERR_ARG,
@@ -290,18 +303,24 @@ int launch_ipa_module_persistent(const diffab_dims* d, float* xa, float* xb, con
   a.NL = d->NL;
   a.stagger_ticks = g_stagger_ticks;
   a.stagger_classes = g_stagger_classes;
+  DIFFAB_REQUIRE((reinterpret_cast<uintptr_t>(start_class) & 3) == 0, DIFFAB_ERR_ARG,
+                 "ipa_module_persistent: the start classes must be 4-byte aligned");
+  DIFFAB_REQUIRE(start_class == nullptr || (d->K == 128 && last_layer_rows != nullptr), DIFFAB_ERR_ARG,
+                 "ipa_module_persistent: start classes go with K = 128 and a row plan");
+  a.start_class = start_class;
   int dev = 0, ncu = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   const int grid = d->B < ncu ? d->B : ncu;  // one work-group per CU (149 KiB of LDS each); more patches than CUs: a work-group walks its queue
-#define MODULE_LAUNCH(K_)                                                                                                       \
+#define MODULE_LAUNCH(...)                                                                                                       \
   do {                                                                                                                            \
-    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_module_persistent_kernel<K_>),                         \
+    DIFFAB_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(ipa_module_persistent_kernel<__VA_ARGS__>),                \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kModuleLdsBytes)));        \
     timer_begin(st);                                                                                                              \
-    hipLaunchKernelGGL((ipa_module_persistent_kernel<K_>), dim3(grid), dim3(512), kModuleLdsBytes, st, a);                        \
+    hipLaunchKernelGGL((ipa_module_persistent_kernel<__VA_ARGS__>), dim3(grid), dim3(512), kModuleLdsBytes, st, a);               \
     timer_end(st);                                                                                                                \
   } while (0)
-  if (d->K == 128) MODULE_LAUNCH(128);
+  if (d->K == 128 && a.start_class != nullptr) MODULE_LAUNCH(128, true);
+  else if (d->K == 128) MODULE_LAUNCH(128);
   else MODULE_LAUNCH(256);
 #undef MODULE_LAUNCH
   DIFFAB_LAUNCH_CHECK();

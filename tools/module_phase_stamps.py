@@ -85,6 +85,31 @@ print(f"  work-group first stamp -> its last: mean {float(own.mean()):.1f} us, s
 launch = float(ph[:, -1, 3].max() - ph[:, 0, 0].min()) * TICK_US
 res["first_stamp_to_last_us"] = launch
 print(f"  first projections start -> last to_out end: {launch:.1f} us")
+if bool((heads_end > 0).all()) and bool((patch_start > 0).all()):
+    # the whole launch as its work-groups see it: the start of a patch (behind its start delay) to the end of its heads
+    whole = (heads_end - patch_start) * TICK_US
+    end = float(heads_end.max() - patch_start.min()) * TICK_US
+    res["launch_us"] = {"own_mean": float(whole.mean()), "own_max": float(whole.max()), "end": end,
+                        "last_start": float(patch_start.max() - patch_start.min()) * TICK_US}
+    print(f"  patch start -> end of its heads: mean {float(whole.mean()):.1f} us, slowest {float(whole.max()):.1f}; "
+          f"first start -> last finish (the launch's end): {end:.1f} us; last start {res['launch_us']['last_start']:.1f} us behind the first")
+    # the launch's end by last-layer work: when the patches of each (items, live slabs) finish, behind the first start
+    plan_items = []
+    for b in range(B):
+        rows_b = gm[b].nonzero().flatten().tolist()
+        n, covered = 0, 0
+        for i in rows_b:
+            if i >= covered:
+                covered = min(i, K - 16) + 16
+                n += 1
+        plan_items.append(n)
+    items = torch.tensor(plan_items)
+    fin = (heads_end - patch_start.min()) * TICK_US
+    res["finish_by_items"] = {}
+    for n in sorted(set(plan_items)):
+        sel = fin[items == n]
+        res["finish_by_items"][str(n)] = {"patches": int(sel.numel()), "mean_us": float(sel.mean()), "max_us": float(sel.max())}
+        print(f"  {n} items in the last layer: {int(sel.numel()):4d} patches finish at mean {float(sel.mean()):8.1f} us, last {float(sel.max()):8.1f}")
 if OUT:
     with open(OUT, "w") as fh:
         json.dump(res, fh, indent=1)
