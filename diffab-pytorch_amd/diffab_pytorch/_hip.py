@@ -315,6 +315,16 @@ CLUSTER_SYMBOLS = {
     "diffab_metrics_pareto": (C.c_int, [_fp] * 5 + [_i32] * 4 + [_fp] * 7 + [_fp, _sz, _fp]),
 }
 
+# every symbol include/diffab_hip_interface.h declares (the four export lists above are pinned by their tests, and the cluster header's
+# test allows no float parameter): same library, a fifth table, for the entries that produce or compare packed bit sets per design
+INTERFACE_SYMBOLS = {
+    # (points, valid, context_points, context_valid, generation_mask, residue_mask (nullable), antigen_mask, chain, residue_idx, rows,
+    #  group_size, K, P, A, contact_distance, bits, n_contacts, workspace, workspace_bytes, stream)
+    "diffab_metrics_contact_bits": (C.c_int, [_fp] * 9 + [_i32] * 5 + [C.c_float] + [_fp] * 2 + [_fp, _sz, _fp]),
+    # (bits, G, N, L, n_set, n_common, fcc, jaccard (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_pairwise_bits": (C.c_int, [_fp] + [_i32] * 3 + [_fp] * 4 + [_fp, _sz, _fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -328,7 +338,7 @@ def load_library() -> C.CDLL:
                 "(or __graft_entry__.build()); there is no CPU fallback for this path")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items())
-                                   + list(CLUSTER_SYMBOLS.items())):
+                                   + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items())):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

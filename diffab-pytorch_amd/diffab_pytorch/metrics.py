@@ -11,6 +11,10 @@
                     order and the mask of front 0 (DESIGN section 4.22, ``csrc/pareto_kernels.hip``);
 ``backbone``      per design: phi, psi, omega and the peptide-bond lengths of the frames' own N, CA, C, chain breaks and cis bonds;
 ``contacts``        per design: atom clashes of the generated residues against the patch, and their contacts with the antigen;
+``contact_map``     per design: the same contacts as data - which generated residue touches which antigen residue, packed as bits;
+``pairwise_bits``   per patch: the overlap of such bit sets between all its designs - common contacts, the fraction of common contacts
+                    (FCC) and Jaccard, the matrix ``cluster`` turns into binding-mode families (DESIGN section 4.23,
+                    ``csrc/interface_kernels.hip``);
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
 ``hbonds``          per design: Kabsch-Sander backbone hydrogen bonds with the peptide-plane O and the amide H they need, the bonds to
@@ -25,10 +29,12 @@ Model-free: nothing here needs a ``DiffAb``.  Designs come as ``sample()`` retur
 per patch, (G,K).  A residue counts when it is generated and inside ``residue_mask``; a mean over no residue is NaN.  The definitions are
 the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
 ``_similarity`` in ``include/diffab_hip.h``, of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h`` and of ``diffab_metrics_hbonds`` in
-``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` and ``diffab_metrics_pareto`` in ``include/diffab_hip_cluster.h``;
+``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` and ``diffab_metrics_pareto`` in ``include/diffab_hip_cluster.h``
+and of ``diffab_metrics_contact_bits`` and ``diffab_metrics_pairwise_bits`` in ``include/diffab_hip_interface.h``;
 every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters, DESIGN
 section 4.15), ``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip``,
-``csrc/cluster_kernels.hip`` and ``csrc/pareto_kernels.hip``, and there is no torch fallback.
+``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip`` and ``csrc/interface_kernels.hip``, and there is no torch fallback
+(``unpack_contact_map`` is plain torch: it reads bits, it computes nothing).
 """
 from __future__ import annotations
 
@@ -61,7 +67,9 @@ HBONDS_MAX_K = 512  # DIFFAB_HBONDS_MAX_K: hbonds keeps the K x K bond bits of a
 SS_LETTERS = " HBEGITS"  # hbonds()['ss']: none, alpha helix, lone bridge, ladder, 3-10 helix, pi helix, turn, bend
 CLUSTER_LDS_MAX_N = 1024  # DIFFAB_METRICS_CLUSTER_LDS_MAX_N: up to here cluster keeps the N x N neighbour bits of a patch on chip
 PARETO_MAX_OBJECTIVES = 16  # DIFFAB_METRICS_PARETO_MAX_OBJECTIVES: objectives of pareto
-SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256 # DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
+INTERFACE_MAX_K = 512  # DIFFAB_INTERFACE_MAX_K: residues per patch of a contact map
+INTERFACE_MAX_WORDS = 8192  # DIFFAB_INTERFACE_MAX_WORDS: 32-bit words per design of pairwise_bits (a contact map at K = 512)
+SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256# DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
 
@@ -586,6 +594,122 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
                                            _hip.ptr(ag), _hip.ptr(hs), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, P, A, clash, contact,
                                            *[_hip.ptr(out.get(k)) for k in order], _hip.ptr(ws), nbytes, _hip.stream_ptr()),
                "diffab_metrics_contacts")
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ binding modes: contact maps and their overlap
+def contact_bits_workspace_bytes(G: int, K: int, A: int) -> int:
+    """DIFFAB_METRICS_CONTACT_BITS_WORKSPACE_BYTES of include/diffab_hip_interface.h."""
+    return G * K * (A * 16 + 28) + G * ((K + 31) // 32 * 4 + 24) + 2048
+
+
+def pairwise_bits_workspace_bytes(G: int, N: int, L: int) -> int:
+    """DIFFAB_METRICS_PAIRWISE_BITS_WORKSPACE_BYTES of include/diffab_hip_interface.h."""
+    Np = (N + 63) // 64 * 64
+    return G * (L * Np * 4 + Np // 64 * L * 4 + L * 4 + 4) + 2048
+
+
+def contact_map(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
+                antigen_mask: Optional[torch.Tensor] = None, chain_idx=None, residue_idx=None, residue_mask: Optional[torch.Tensor] = None,
+                group_size: int = 1, contact_distance: float = 5.0, atoms: Sequence[str] = BACKBONE_ATOMS) -> Dict[str, torch.Tensor]:
+    """The contacts of each design with the antigen as data: which generated residue touches which antigen residue.  Every argument
+    means what it means in ``contacts`` and is checked as there; ``antigen_mask`` (G,K) is required and K is at most 512.  Contact is
+    decided by exactly the rule by which ``contacts`` counts ``n_contact_pairs`` - the same atoms (``atoms`` of the design's own frames,
+    no CB where its token is Gly; ``context``'s real atoms, or the frame atoms of the first row of the group, on the antigen side), the
+    same eligibility (``residue_mask``, no chain neighbours, non-generated antigen residues only) and the same fp32 comparison.
+
+    Returns ``bits`` (rows,K,W) int32 with W = ceil(K / 32): bit ``j & 31`` of word ``j >> 5`` of row ``i`` is set iff generated residue
+    i and antigen residue j are in contact, every other bit is 0; and ``n_contacts`` (rows,) int32, the number of set bits
+    (= ``contacts(...)['n_contact_pairs']``).  ``unpack_contact_map`` turns the words into a bool matrix; ``pairwise_bits`` compares
+    the maps of a patch's designs.  One C-ABI call (two launches, ``include/diffab_hip_interface.h``); results on the device of
+    ``designs['seq_idx']``; ValueError naming the argument before any device work."""
+    who = "metrics.contact_map()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    if K > INTERFACE_MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch, at most {INTERFACE_MAX_K} for a contact map")
+    atoms = _check_atoms(who, atoms)
+    contact = _check_distance(who, "contact_distance", contact_distance)
+    if antigen_mask is None:
+        raise ValueError(f"{who}: antigen_mask is required: the columns of a contact map are the antigen residues")
+    _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    if context is not None:
+        A = _check_context(who, context, G, K)
+    chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    P = len(atoms)
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    pts, valid = _frame_atoms(seq, x, O, atoms)
+    if context is None:
+        first = torch.arange(G, device=dev) * group_size
+        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
+        A, cvalid = P, cbits.to(torch.int32).contiguous()
+    else:
+        cpts = _hip.dev_f32(context["xyz"])
+        cvalid = _valid_word(context["atom_mask"], A, dev)
+    gm, ag = _hip.dev_mask(generation_mask), _hip.dev_mask(antigen_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    chain, ridx = chain.to(dev), ridx.to(dev)
+    bits = torch.empty(rows, K, (K + 31) // 32, dtype=torch.int32, device=dev)
+    n_contacts = torch.empty(rows, dtype=torch.int32, device=dev)
+    nbytes = contact_bits_workspace_bytes(G, K, A)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_contact_bits(_hip.ptr(pts), _hip.ptr(valid), _hip.ptr(cpts), _hip.ptr(cvalid), _hip.ptr(gm), _hip.ptr(rm),
+                                               _hip.ptr(ag), _hip.ptr(chain), _hip.ptr(ridx), rows, group_size, K, P, A, contact,
+                                               _hip.ptr(bits), _hip.ptr(n_contacts), _hip.ptr(ws), nbytes, _hip.stream_ptr()),
+               "diffab_metrics_contact_bits")
+    return {"bits": bits.to(out_dev), "n_contacts": n_contacts.to(out_dev)}
+
+
+def unpack_contact_map(bits: torch.Tensor, K: int) -> torch.Tensor:
+    """``contact_map``'s ``bits`` (rows,K,W) int32 -> (rows,K,K) bool: entry [r,i,j] is bit ``j & 31`` of word ``j >> 5`` of row i.
+    Plain torch, for inspection and tests."""
+    who = "metrics.unpack_contact_map()"
+    if not _is_int(K) or K < 1:
+        raise ValueError(f"{who}: K must be an int >= 1, got {K!r}")
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or bits.dim() != 3 or tuple(bits.shape[1:]) != (K, (K + 31) // 32):
+        raise ValueError(f"{who}: bits must be an int32 tensor (rows, K = {K}, W = {(K + 31) // 32})")
+    j = torch.arange(K, device=bits.device)
+    return ((bits[:, :, j >> 5] >> (j & 31)) & 1).ne(0)
+
+
+def pairwise_bits(bits: torch.Tensor, *, group_size: int) -> Dict[str, torch.Tensor]:
+    """The overlap of the bit sets of the N = ``group_size`` designs of every patch, all pairs.  ``bits`` is an int32 tensor
+    (G * N, ...), read as L words per design (L at most 8192) - ``contact_map``'s ``bits`` goes in as it comes out, and any other packed
+    set (the epitope residues of a design, say) works the same way; all 32 bits of a word are data, the sign bit included.
+
+    Returns ``n_set`` (G,N) int32, the popcount of each design; ``n_common`` (G,N,N) int32, |A & B|, symmetric, its diagonal ``n_set``;
+    ``fcc`` (G,N,N) fp32, ``n_common[a,b] / n_set[a]``, the fraction of a's contacts that b shares (the fraction of common contacts,
+    asymmetric; 1 where a's set is empty); ``jaccard`` (G,N,N) fp32, |A & B| / |A | B|, symmetric to the bit (1 where both sets are
+    empty).  Each quotient is one correctly rounded fp32 division of two exact integers.  ``cluster(1 - jaccard, cutoff)`` gives the
+    binding-mode families.  One C-ABI call (four launches over the live word columns only, ``include/diffab_hip_interface.h``); results
+    on ``bits``' device; ValueError naming the argument before any device work."""
+    who = "metrics.pairwise_bits()"
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or bits.dim() < 2:
+        raise ValueError(f"{who}: bits must be an int32 tensor (G * N, ...), one row of packed words per design")
+    if not _is_int(group_size) or group_size < 1:
+        raise ValueError(f"{who}: group_size must be an int >= 1, got {group_size!r}")
+    if group_size > MAX_GROUP:
+        raise ValueError(f"{who}: group_size = {group_size}, at most {MAX_GROUP} designs per patch")
+    rows, N = int(bits.shape[0]), group_size
+    if rows % N != 0:
+        raise ValueError(f"{who}: {rows} design rows are not a multiple of group_size = {N}")
+    L = math.prod(int(v) for v in bits.shape[1:])
+    if L < 1 or L > INTERFACE_MAX_WORDS:
+        raise ValueError(f"{who}: bits has L = {L} words per design, outside [1, {INTERFACE_MAX_WORDS}]")
+    G = rows // N
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), bits.device
+    b = bits.detach().to(device=dev).contiguous()
+    n_set = torch.empty(G, N, dtype=torch.int32, device=dev)
+    n_common = torch.empty(G, N, N, dtype=torch.int32, device=dev)
+    fcc, jaccard = (torch.empty(G, N, N, dtype=torch.float32, device=dev) for _ in range(2))
+    nbytes = pairwise_bits_workspace_bytes(G, N, L)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_pairwise_bits(_hip.ptr(b), G, N, L, _hip.ptr(n_set), _hip.ptr(n_common), _hip.ptr(fcc), _hip.ptr(jaccard),
+                                                _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_pairwise_bits")
+    out = {"n_set": n_set, "n_common": n_common, "fcc": fcc, "jaccard": jaccard}
     return {k: v.to(out_dev) for k, v in out.items()}
 
 
