@@ -325,6 +325,19 @@ INTERFACE_SYMBOLS = {
     "diffab_metrics_pairwise_bits": (C.c_int, [_fp] + [_i32] * 3 + [_fp] * 4 + [_fp, _sz, _fp]),
 }
 
+# every symbol include/diffab_hip_develop.h declares (the five export lists above are pinned by their tests): same library, a sixth
+# table, for the entries that read a design's coordinates and its sequence together
+DEVELOP_SYMBOLS = {
+    # (sites, context_sites, tokens, generation_mask, residue_mask (nullable), antigen_mask (nullable), exposed_in (nullable),
+    #  hydrophobicity, charge, rows, group_size, K, V, neighbour_distance, max_neighbours, vicinity_distance, patch_distance, min_distance,
+    #  psh, ppc, pnc, charge_generated, charge_scope, n_scope, n_exposed, n_pairs, residue_psh, residue_ppc, residue_pnc, n_neighbours,
+    #  state (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_patches": (C.c_int, [_fp] * 9 + [_i32] * 4 + [C.c_float, _i32] + [C.c_float] * 3 + [_fp] * 13 + [_fp, _sz, _fp]),
+    # (tokens, generation_mask, residue_mask (nullable), chain, residue_idx, motifs (HOST int32[M * 4]), rows, group_size, K, M,
+    #  motif_count, n_motifs, motif_start (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_motifs": (C.c_int, [_fp] * 6 + [_i32] * 4 + [_fp] * 3 + [_fp, _sz, _fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -338,7 +351,7 @@ def load_library() -> C.CDLL:
                 "(or __graft_entry__.build()); there is no CPU fallback for this path")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items())
-                                   + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items())):
+                                   + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items()) + list(DEVELOP_SYMBOLS.items())):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -15,6 +15,11 @@
 ``pairwise_bits``   per patch: the overlap of such bit sets between all its designs - common contacts, the fraction of common contacts
                     (FCC) and Jaccard, the matrix ``cluster`` turns into binding-mode families (DESIGN section 4.23,
                     ``csrc/interface_kernels.hip``);
+``patches``         per design: hydrophobic and charged surface patches of the CDRs and of what they sit on, on one site per residue -
+                    the aggregation and polyspecificity side of developability;
+``liabilities``     per design: sequence motifs along the chain that do not survive production (N-glycosylation sequons, deamidation,
+                    isomerisation and fragmentation sites, free Cys, Met), counted where they touch the design; ``motif_masks`` parses
+                    the patterns (DESIGN section 4.24, ``csrc/develop_kernels.hip``);
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
 ``hbonds``          per design: Kabsch-Sander backbone hydrogen bonds with the peptide-plane O and the amide H they need, the bonds to
@@ -30,11 +35,12 @@ per patch, (G,K).  A residue counts when it is generated and inside ``residue_ma
 the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse`` / ``_backbone`` / ``_contacts`` / ``_ensemble`` /
 ``_similarity`` in ``include/diffab_hip.h``, of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h`` and of ``diffab_metrics_hbonds`` in
 ``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` and ``diffab_metrics_pareto`` in ``include/diffab_hip_cluster.h``
-and of ``diffab_metrics_contact_bits`` and ``diffab_metrics_pairwise_bits`` in ``include/diffab_hip_interface.h``;
+and of ``diffab_metrics_contact_bits`` and ``diffab_metrics_pairwise_bits`` in ``include/diffab_hip_interface.h``
+and of ``diffab_metrics_patches`` and ``diffab_metrics_motifs`` in ``include/diffab_hip_develop.h``;
 every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters, DESIGN
 section 4.15), ``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip``,
-``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip`` and ``csrc/interface_kernels.hip``, and there is no torch fallback
-(``unpack_contact_map`` is plain torch: it reads bits, it computes nothing).
+``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip`` and ``csrc/develop_kernels.hip``, and there is
+no torch fallback (``unpack_contact_map`` is plain torch: it reads bits, it computes nothing; ``motif_masks`` parses text on the host).
 """
 from __future__ import annotations
 
@@ -47,7 +53,7 @@ import torch
 
 from . import _hip
 from .guidance import residue_tables
-from .io import AA3, BACKBONE_ATOMS, backbone_from_frames
+from .io import AA1, AA3, BACKBONE_ATOMS, backbone_from_frames
 
 MAX_GROUP = 4096  # DIFFAB_METRICS_MAX_GROUP: designs per patch
 MAX_K = 4096  # DIFFAB_METRICS_MAX_K
@@ -69,6 +75,10 @@ CLUSTER_LDS_MAX_N = 1024  # DIFFAB_METRICS_CLUSTER_LDS_MAX_N: up to here cluster
 PARETO_MAX_OBJECTIVES = 16  # DIFFAB_METRICS_PARETO_MAX_OBJECTIVES: objectives of pareto
 INTERFACE_MAX_K = 512  # DIFFAB_INTERFACE_MAX_K: residues per patch of a contact map
 INTERFACE_MAX_WORDS = 8192  # DIFFAB_INTERFACE_MAX_WORDS: 32-bit words per design of pairwise_bits (a contact map at K = 512)
+DEVELOP_MAX_K = 512  # DIFFAB_DEVELOP_MAX_K: residues per patch of patches and liabilities
+DEVELOP_MAX_CLASSES = 32  # DIFFAB_DEVELOP_MAX_CLASSES: entries of the two weight tables of patches, classes of a motif word
+DEVELOP_MAX_MOTIFS = 32  # DIFFAB_DEVELOP_MAX_MOTIFS: motifs of one liabilities call, one bit of motif_start each
+DEVELOP_MOTIF_WORDS = 4  # DIFFAB_DEVELOP_MOTIF_WORDS: a motif is at most four residues long
 SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256# DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
@@ -710,6 +720,232 @@ def pairwise_bits(bits: torch.Tensor, *, group_size: int) -> Dict[str, torch.Ten
     _hip.check(lib.diffab_metrics_pairwise_bits(_hip.ptr(b), G, N, L, _hip.ptr(n_set), _hip.ptr(n_common), _hip.ptr(fcc), _hip.ptr(jaccard),
                                                 _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_pairwise_bits")
     out = {"n_set": n_set, "n_common": n_common, "fcc": fcc, "jaccard": jaccard}
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ developability: surface patches and sequence motifs
+_KD = (1.8, -4.5, -3.5, -3.5, 2.5, -3.5, -3.5, -0.4, -3.2, 4.5, 3.8, -3.9, 1.9, 2.8, -1.6, -0.8, -0.7, -0.9, -1.3, 4.2)  # AA1 order
+# patches(): Kyte-Doolittle hydropathy mapped onto [1, 2], 1 + (kd + 4.5) / 9, in AA1 order; X (UNK) weighs 0
+KYTE_DOOLITTLE = tuple(1.0 + (kd + 4.5) / 9.0 for kd in _KD) + (0.0,)
+# patches(): D, E = -1; K, R = +1; H = +0.1 (partly protonated at neutral pH); everything else 0
+RESIDUE_CHARGE = tuple({"D": -1.0, "E": -1.0, "K": 1.0, "R": 1.0, "H": 0.1}.get(c, 0.0) for c in AA1)
+# liabilities(): name -> pattern of motif_masks
+LIABILITY_MOTIFS = {"n_glycosylation": "N[^P][ST]", "deamidation": "N[GS]", "isomerisation": "D[GS]", "fragmentation": "DP", "cysteine": "C",
+                    "methionine": "M"}
+
+
+def patches_workspace_bytes(G: int, K: int) -> int:
+    """DIFFAB_METRICS_PATCHES_WORKSPACE_BYTES of include/diffab_hip_develop.h."""
+    return G * K * 16 + 1024
+
+
+def motifs_workspace_bytes(G: int, K: int) -> int:
+    """DIFFAB_METRICS_MOTIFS_WORKSPACE_BYTES of include/diffab_hip_develop.h."""
+    return G * K * 4 + 1024
+
+
+def _check_weight_table(who: str, name: str, table) -> torch.Tensor:
+    try:
+        t = torch.as_tensor(table).detach()
+    except (TypeError, ValueError, RuntimeError):
+        t = None
+    if t is None or t.dim() != 1 or t.is_complex() or t.dtype == torch.bool or not 1 <= t.numel() <= DEVELOP_MAX_CLASSES:
+        raise ValueError(f"{who}: {name} must be a sequence or 1-d tensor of 1 to {DEVELOP_MAX_CLASSES} numbers, one per token class")
+    t = t.to(torch.float32)
+    if not bool(torch.isfinite(t.cpu()).all()):
+        raise ValueError(f"{who}: {name} must hold finite numbers")
+    return t
+
+
+def patches(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
+            antigen_mask: Optional[torch.Tensor] = None, residue_mask: Optional[torch.Tensor] = None, group_size: int = 1,
+            exposed: Optional[torch.Tensor] = None, hydrophobicity=KYTE_DOOLITTLE, charge=RESIDUE_CHARGE, neighbour_distance: float = 10.0,
+            max_neighbours: int = 16, vicinity_distance: float = 10.0, patch_distance: float = 7.5,
+            min_distance: float = 3.8) -> Dict[str, torch.Tensor]:
+    """Hydrophobic and charged surface patches of the CDRs of each design and of what they sit on: the aggregation and polyspecificity
+    side of developability.  The project's own restatement of the Therapeutic Antibody Profiler's PSH / PPC / PNC on ONE SITE per
+    residue; no parity with that tool is claimed.  ``designs``, ``generation_mask``, ``context``, ``antigen_mask``, ``residue_mask`` and
+    ``group_size`` are ``contacts``' arguments.  A generated residue's site is the CB of its own frame (``backbone_from_frames``), the CA
+    where the design's token is Gly; a non-generated residue's site is slot 4 of ``context['xyz']`` where ``context['atom_mask']`` has
+    it and the token is not Gly, else slot 1 (CA), and a non-generated residue without a CA is left out; without ``context`` the
+    non-generated residues take the frame sites of the first row of their group.  The antigen is ignored entirely (the unbound
+    antibody is what is made), so are the residues outside ``residue_mask``.
+
+    A residue is IN SCOPE when it is generated or within ``vicinity_distance`` of a generated residue's site, and EXPOSED when it is in
+    scope and has at most ``max_neighbours`` other residues within ``neighbour_distance`` - a CB-neighbour-count proxy of a surface
+    whose default threshold is this project's choice, not a measured value; ``exposed`` (rows,K) bool decides instead where a caller
+    knows better (``surface``'s per-residue free points, say).  Over the pairs of exposed residues closer than ``patch_distance`` the
+    term is ``w_i * w_j / max(d, min_distance)**2``: ``psh`` with w = ``hydrophobicity[token]`` (default ``KYTE_DOOLITTLE``), ``ppc``
+    over the pairs of two positive and ``pnc`` of two negative ``charge[token]`` (default ``RESIDUE_CHARGE``); a token outside a table
+    weighs 0.  Distances are fp32 and compared strictly, the sums fp64 in a fixed order, rounded once.
+
+    Returns, per row (rows,): ``psh``, ``ppc``, ``pnc``, ``charge_generated``, ``charge_scope`` fp32 and ``n_scope``, ``n_exposed``,
+    ``n_pairs`` int32; per residue (rows,K), ready as ``b_factor`` of ``io.write_pdb``: ``residue_psh``, ``residue_ppc``,
+    ``residue_pnc`` fp32, ``n_neighbours`` int32 and ``state`` uint8 (bit 0 present, bit 1 in scope, bit 2 exposed).  One C-ABI call
+    (two launches, ``include/diffab_hip_develop.h``); results on the device of ``designs['seq_idx']``; ValueError naming the argument
+    before any device work."""
+    who = "metrics.patches()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    if K > DEVELOP_MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch, at most {DEVELOP_MAX_K}")
+    if antigen_mask is not None:
+        _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    if exposed is not None and (not isinstance(exposed, torch.Tensor) or exposed.dtype != torch.bool or tuple(exposed.shape) != (rows, K)):
+        raise ValueError(f"{who}: exposed must be a bool tensor {(rows, K)} (one row per design)")
+    hyd, chg = _check_weight_table(who, "hydrophobicity", hydrophobicity), _check_weight_table(who, "charge", charge)
+    if hyd.numel() != chg.numel():
+        raise ValueError(f"{who}: hydrophobicity has {hyd.numel()} classes and charge {chg.numel()}: one table entry per token class in both")
+    near = _check_distance(who, "neighbour_distance", neighbour_distance)
+    vicinity = _check_distance(who, "vicinity_distance", vicinity_distance)
+    patch = _check_distance(who, "patch_distance", patch_distance)
+    floor = _check_positive(who, "min_distance", min_distance)
+    if not _is_int(max_neighbours) or max_neighbours < 0 or max_neighbours >= 2 ** 31:
+        raise ValueError(f"{who}: max_neighbours must be an int >= 0, got {max_neighbours!r}")
+    if context is not None:
+        A = _check_context(who, context, G, K)
+        if A < 2:
+            raise ValueError(f"{who}: context['xyz'] has A = {A} atoms per residue: slot 1 (CA) is needed")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    frame = _hip.dev_f32(backbone_from_frames(x, O, ("CA", "CB")))  # (rows,K,2,3)
+    sites = torch.where((seq == GLY).unsqueeze(-1), frame[:, :, 0], frame[:, :, 1]).contiguous()
+    first = torch.arange(G, device=dev) * group_size
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    if context is None:
+        csites = sites[first].contiguous()
+    else:
+        xyz, am = _hip.dev_f32(context["xyz"]), _hip.dev_mask(context["atom_mask"])
+        use_cb = (am[:, :, 4] & (seq[first] != GLY)) if A > 4 else torch.zeros(G, K, dtype=torch.bool, device=dev)
+        csites = torch.where(use_cb.unsqueeze(-1), xyz[:, :, min(4, A - 1)], xyz[:, :, 1]).contiguous()
+        has_site = am[:, :, 1] | gm  # a non-generated residue without a CA is absent
+        rm = (has_site if rm is None else rm & has_site).contiguous()
+    tokens = seq.to(torch.int32).contiguous()
+    ag = None if antigen_mask is None else _hip.dev_mask(antigen_mask)
+    ex = None if exposed is None else _hip.dev_mask(exposed)
+    hyd, chg = _hip.dev_f32(hyd), _hip.dev_f32(chg)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = {"psh": f32(rows), "ppc": f32(rows), "pnc": f32(rows), "charge_generated": f32(rows), "charge_scope": f32(rows),
+           "n_scope": i32(rows), "n_exposed": i32(rows), "n_pairs": i32(rows), "residue_psh": f32(rows, K), "residue_ppc": f32(rows, K),
+           "residue_pnc": f32(rows, K), "n_neighbours": i32(rows, K), "state": torch.empty(rows, K, dtype=torch.uint8, device=dev)}
+    nbytes = patches_workspace_bytes(G, K)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_patches(_hip.ptr(sites), _hip.ptr(csites), _hip.ptr(tokens), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(ag),
+                                          _hip.ptr(ex), _hip.ptr(hyd), _hip.ptr(chg), rows, group_size, K, int(hyd.numel()), near,
+                                          max_neighbours, vicinity, patch, floor, *[_hip.ptr(t) for t in out.values()], _hip.ptr(ws), nbytes,
+                                          _hip.stream_ptr()), "diffab_metrics_patches")
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+def motif_masks(patterns, V: int = 21) -> torch.Tensor:
+    """Patterns -> the motif words of ``diffab_metrics_motifs``: an int32 tensor (M, 4) on the CPU, word p of motif m with bit v set iff
+    token class v matches at position p, zero words behind the motif's end.  ``patterns`` is a pattern, a sequence of patterns or a dict
+    name -> pattern (its order is kept).  A pattern is one to four positions, each a letter of ``io.AA1`` (``X`` is UNK), ``[ST]`` (any of
+    the letters), ``[^P]`` (any token below ``V`` except the letters) or ``.`` (any token below ``V``); ``V`` is the number of token
+    classes, 1 to 32.  ValueError for anything else, a position that matches no class below ``V`` included."""
+    who = "metrics.motif_masks()"
+    if not _is_int(V) or not 1 <= V <= DEVELOP_MAX_CLASSES:
+        raise ValueError(f"{who}: V must be an int in [1, {DEVELOP_MAX_CLASSES}], got {V!r}")
+    if isinstance(patterns, str):
+        patterns = [patterns]
+    elif isinstance(patterns, dict):
+        patterns = list(patterns.values())
+    if not isinstance(patterns, Sequence) or not 1 <= len(patterns) <= DEVELOP_MAX_MOTIFS:
+        raise ValueError(f"{who}: patterns must be a pattern, or a sequence or dict of 1 to {DEVELOP_MAX_MOTIFS} patterns")
+    every = (1 << V) - 1
+
+    def letter(c: str, pat: str) -> int:
+        v = AA1.find(c)
+        if len(c) != 1 or v < 0:
+            raise ValueError(f"{who}: pattern {pat!r}: {c!r} is no one-letter code of {AA1}")
+        if v >= V:
+            raise ValueError(f"{who}: pattern {pat!r}: {c!r} is token {v}, outside the V = {V} classes")
+        return 1 << v
+
+    table = []
+    for pat in patterns:
+        if not isinstance(pat, str):
+            raise ValueError(f"{who}: a pattern must be a str, got {pat!r}")
+        words, at = [], 0
+        while at < len(pat):
+            c = pat[at]
+            if c == "[":
+                end = pat.find("]", at)
+                body = pat[at + 1:end] if end > 0 else ""
+                negate = body.startswith("^")
+                body = body[1:] if negate else body
+                if end < 0 or not body:
+                    raise ValueError(f"{who}: pattern {pat!r}: a class is [letters] or [^letters]")
+                word = 0
+                for b in body:
+                    word |= letter(b, pat)
+                word = every & ~word if negate else word
+                at = end + 1
+            elif c == ".":
+                word, at = every, at + 1
+            else:
+                word, at = letter(c, pat), at + 1
+            if word == 0:
+                raise ValueError(f"{who}: pattern {pat!r}: position {len(words)} matches no token class")
+            words.append(word)
+        if not 1 <= len(words) <= DEVELOP_MOTIF_WORDS:
+            raise ValueError(f"{who}: pattern {pat!r} has {len(words)} positions, a motif has 1 to {DEVELOP_MOTIF_WORDS}")
+        table.append([w - (1 << 32) if w >= 1 << 31 else w for w in words] + [0] * (DEVELOP_MOTIF_WORDS - len(words)))
+    return torch.tensor(table, dtype=torch.int32)
+
+
+def liabilities(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, motifs=LIABILITY_MOTIFS, chain_idx=None, residue_idx=None,
+                residue_mask: Optional[torch.Tensor] = None, group_size: int = 1, V: int = 21) -> Dict[str, torch.Tensor]:
+    """Sequence liabilities of each design: motifs along the chain that do not survive production, counted where they touch the design.
+    ``motifs`` is a dict name -> pattern of ``motif_masks`` (default ``LIABILITY_MOTIFS``: the N-glycosylation sequon ``N[^P][ST]``,
+    deamidation ``N[GS]``, isomerisation ``D[GS]``, fragmentation ``DP``, free ``C`` and oxidisable ``M``), at most 32 of them, and ``V``
+    the number of token classes.  A motif is read along the CHAIN, not along the slots: the next residue of slot i is the lowest slot
+    inside ``residue_mask`` on the same chain whose ``residue_idx`` is one higher (``backbone``'s chain neighbour; ``chain_idx`` /
+    ``residue_idx`` are (K,) or (G,K), default one chain and ``arange(K)``), so a numbering gap ends a motif and a patch gathered out
+    of order does not.  A match is counted iff at least one of its residues is generated: the framework's own motifs are not the
+    design's fault, one that the design completes is.
+
+    Returns one int32 tensor (rows,) per motif name, its counted matches; ``n_motifs`` (rows,) int32, their sum - a ``violation`` of
+    ``pareto``; and ``motif_start`` (rows,K) int32, bit m set iff a counted match of the m-th motif starts at the residue (the sign
+    bit is data).  ``n_motifs`` and ``motif_start`` are therefore no motif names.  One C-ABI call (two launches,
+    ``include/diffab_hip_develop.h``); results on the device of ``designs['seq_idx']``; ValueError naming the argument before any
+    device work."""
+    who = "metrics.liabilities()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "ca")
+    if K > DEVELOP_MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch, at most {DEVELOP_MAX_K}")
+    if not isinstance(motifs, dict) or not 1 <= len(motifs) <= DEVELOP_MAX_MOTIFS or not all(isinstance(n, str) for n in motifs):
+        raise ValueError(f"{who}: motifs must be a dict of 1 to {DEVELOP_MAX_MOTIFS} entries name -> pattern")
+    for reserved in ("n_motifs", "motif_start"):
+        if reserved in motifs:
+            raise ValueError(f"{who}: motifs: {reserved!r} names an output of its own and cannot name a motif")
+    try:
+        words = motif_masks(motifs, V)
+    except ValueError as e:
+        raise ValueError(f"{who}: motifs: {e}") from None
+    chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    M = len(motifs)
+    tokens = _hip.dev_i64(designs["seq_idx"]).to(torch.int32).contiguous()
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    chain, ridx = chain.to(dev), ridx.to(dev)
+    host = (ctypes.c_int32 * (M * DEVELOP_MOTIF_WORDS))(*words.flatten().tolist())
+    count = torch.empty(rows, M, dtype=torch.int32, device=dev)
+    total = torch.empty(rows, dtype=torch.int32, device=dev)
+    start = torch.empty(rows, K, dtype=torch.int32, device=dev)
+    nbytes = motifs_workspace_bytes(G, K)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_motifs(_hip.ptr(tokens), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(chain), _hip.ptr(ridx),
+                                         ctypes.cast(host, ctypes.c_void_p), rows, group_size, K, M, _hip.ptr(count), _hip.ptr(total),
+                                         _hip.ptr(start), _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_motifs")
+    out = {name: count[:, m].contiguous() for m, name in enumerate(motifs)}
+    out.update(n_motifs=total, motif_start=start)
     return {k: v.to(out_dev) for k, v in out.items()}
 
 
