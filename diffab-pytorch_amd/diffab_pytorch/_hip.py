@@ -338,6 +338,15 @@ DEVELOP_SYMBOLS = {
     "diffab_metrics_motifs": (C.c_int, [_fp] * 6 + [_i32] * 4 + [_fp] * 3 + [_fp, _sz, _fp]),
 }
 
+# every symbol include/diffab_hip_energy.h declares (the six export lists above are pinned by their tests): same library, a seventh
+# table, for the entry that scores a designed residue against the residue it touches by what the two residues are
+ENERGY_SYMBOLS = {
+    # (sites, context_sites, tokens, generation_mask, residue_mask (nullable), antigen_mask (nullable), chain, residue_idx (both or
+    #  neither), table, bin_edges (HOST float[NB + 1]), rows, group_size, K, V, NB, min_separation, e_antigen, e_framework, e_internal,
+    #  n_pairs, residue_energy, residue_antigen_energy, n_partners, substitution (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_pair_energy": (C.c_int, [_fp] * 10 + [_i32] * 6 + [_fp] * 8 + [_fp, _sz, _fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -351,7 +360,8 @@ def load_library() -> C.CDLL:
                 "(or __graft_entry__.build()); there is no CPU fallback for this path")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items())
-                                   + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items()) + list(DEVELOP_SYMBOLS.items())):
+                                   + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items()) + list(DEVELOP_SYMBOLS.items())
+                                   + list(ENERGY_SYMBOLS.items())):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

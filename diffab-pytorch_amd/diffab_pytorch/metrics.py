@@ -20,6 +20,11 @@
 ``liabilities``     per design: sequence motifs along the chain that do not survive production (N-glycosylation sequons, deamidation,
                     isomerisation and fragmentation sites, free Cys, Met), counted where they touch the design; ``motif_masks`` parses
                     the patterns (DESIGN section 4.24, ``csrc/develop_kernels.hip``);
+``interface_energy`` per design: a residue-level, distance-binned pair potential between the designed residues and the antigen, the
+                    framework and each other, per residue and per single substitution at a designed position, and against the
+                    native the share of improved designs - the DiffAb paper's IMP under that potential; ``PairPotential`` holds a
+                    table and its bin edges, ``contact_potential`` builds the placeholder default (DESIGN section 4.25,
+                    ``csrc/energy_kernels.hip``);
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
 ``hbonds``          per design: Kabsch-Sander backbone hydrogen bonds with the peptide-plane O and the amide H they need, the bonds to
@@ -36,15 +41,17 @@ the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse
 ``_similarity`` in ``include/diffab_hip.h``, of ``diffab_metrics_surface`` in ``include/diffab_hip_analysis.h`` and of ``diffab_metrics_hbonds`` in
 ``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` and ``diffab_metrics_pareto`` in ``include/diffab_hip_cluster.h``
 and of ``diffab_metrics_contact_bits`` and ``diffab_metrics_pairwise_bits`` in ``include/diffab_hip_interface.h``
-and of ``diffab_metrics_patches`` and ``diffab_metrics_motifs`` in ``include/diffab_hip_develop.h``;
+and of ``diffab_metrics_patches`` and ``diffab_metrics_motifs`` in ``include/diffab_hip_develop.h``
+and of ``diffab_metrics_pair_energy`` in ``include/diffab_hip_energy.h``;
 every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters, DESIGN
 section 4.15), ``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip``,
-``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip`` and ``csrc/develop_kernels.hip``, and there is
+``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip``, ``csrc/develop_kernels.hip`` and ``csrc/energy_kernels.hip``, and there is
 no torch fallback (``unpack_contact_map`` is plain torch: it reads bits, it computes nothing; ``motif_masks`` parses text on the host).
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import functools
 import math
 from typing import Dict, Optional, Sequence
@@ -79,6 +86,9 @@ DEVELOP_MAX_K = 512  # DIFFAB_DEVELOP_MAX_K: residues per patch of patches and l
 DEVELOP_MAX_CLASSES = 32  # DIFFAB_DEVELOP_MAX_CLASSES: entries of the two weight tables of patches, classes of a motif word
 DEVELOP_MAX_MOTIFS = 32  # DIFFAB_DEVELOP_MAX_MOTIFS: motifs of one liabilities call, one bit of motif_start each
 DEVELOP_MOTIF_WORDS = 4  # DIFFAB_DEVELOP_MOTIF_WORDS: a motif is at most four residues long
+ENERGY_MAX_K = 512  # DIFFAB_ENERGY_MAX_K: residues per patch of interface_energy
+ENERGY_MAX_CLASSES = 32  # DIFFAB_ENERGY_MAX_CLASSES: token classes of a pair potential
+ENERGY_MAX_BINS = 8  # DIFFAB_ENERGY_MAX_BINS: distance bins of a pair potential
 SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256# DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
@@ -757,6 +767,32 @@ def _check_weight_table(who: str, name: str, table) -> torch.Tensor:
     return t
 
 
+def _residue_sites(designs, generation_mask, residue_mask, context, group_size: int):
+    """One site per residue, on the device, of checked arguments -> (sites (rows,K,3) fp32, context_sites (G,K,3) fp32, tokens (rows,K)
+    int32, generation_mask (G,K), residue_mask (G,K) or None).  A row's site is the CB of its own frame, the CA where its token is Gly.
+    A patch's site is slot 4 of ``context['xyz']`` where ``context['atom_mask']`` has it and the token of the group's first row is not
+    Gly, else slot 1 (CA), and a non-generated residue without a CA is ANDed out of ``residue_mask``; without ``context`` it is the
+    site of the first row of the group.  What ``patches`` and ``interface_energy`` put their numbers on."""
+    dev = _hip.device()
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    G, K = int(generation_mask.shape[0]), int(generation_mask.shape[1])
+    frame = _hip.dev_f32(backbone_from_frames(x, O, ("CA", "CB")))  # (rows,K,2,3)
+    sites = torch.where((seq == GLY).unsqueeze(-1), frame[:, :, 0], frame[:, :, 1]).contiguous()
+    first = torch.arange(G, device=dev) * group_size
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    if context is None:
+        csites = sites[first].contiguous()
+    else:
+        xyz, am = _hip.dev_f32(context["xyz"]), _hip.dev_mask(context["atom_mask"])
+        A = int(xyz.shape[2])
+        use_cb = (am[:, :, 4] & (seq[first] != GLY)) if A > 4 else torch.zeros(G, K, dtype=torch.bool, device=dev)
+        csites = torch.where(use_cb.unsqueeze(-1), xyz[:, :, min(4, A - 1)], xyz[:, :, 1]).contiguous()
+        has_site = am[:, :, 1] | gm  # a non-generated residue without a CA is absent
+        rm = (has_site if rm is None else rm & has_site).contiguous()
+    return sites, csites, seq.to(torch.int32).contiguous(), gm, rm
+
+
 def patches(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
             antigen_mask: Optional[torch.Tensor] = None, residue_mask: Optional[torch.Tensor] = None, group_size: int = 1,
             exposed: Optional[torch.Tensor] = None, hydrophobicity=KYTE_DOOLITTLE, charge=RESIDUE_CHARGE, neighbour_distance: float = 10.0,
@@ -808,21 +844,7 @@ def patches(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, 
 
     lib = _hip.lib()
     dev, out_dev = _hip.device(), designs["seq_idx"].device
-    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
-    frame = _hip.dev_f32(backbone_from_frames(x, O, ("CA", "CB")))  # (rows,K,2,3)
-    sites = torch.where((seq == GLY).unsqueeze(-1), frame[:, :, 0], frame[:, :, 1]).contiguous()
-    first = torch.arange(G, device=dev) * group_size
-    gm = _hip.dev_mask(generation_mask)
-    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
-    if context is None:
-        csites = sites[first].contiguous()
-    else:
-        xyz, am = _hip.dev_f32(context["xyz"]), _hip.dev_mask(context["atom_mask"])
-        use_cb = (am[:, :, 4] & (seq[first] != GLY)) if A > 4 else torch.zeros(G, K, dtype=torch.bool, device=dev)
-        csites = torch.where(use_cb.unsqueeze(-1), xyz[:, :, min(4, A - 1)], xyz[:, :, 1]).contiguous()
-        has_site = am[:, :, 1] | gm  # a non-generated residue without a CA is absent
-        rm = (has_site if rm is None else rm & has_site).contiguous()
-    tokens = seq.to(torch.int32).contiguous()
+    sites, csites, tokens, gm, rm = _residue_sites(designs, generation_mask, residue_mask, context, group_size)
     ag = None if antigen_mask is None else _hip.dev_mask(antigen_mask)
     ex = None if exposed is None else _hip.dev_mask(exposed)
     hyd, chg = _hip.dev_f32(hyd), _hip.dev_f32(chg)
@@ -946,6 +968,192 @@ def liabilities(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor,
                                          _hip.ptr(start), _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_motifs")
     out = {name: count[:, m].contiguous() for m, name in enumerate(motifs)}
     out.update(n_motifs=total, motif_start=start)
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ binding score: a distance-binned pair potential
+def pair_energy_workspace_bytes(G: int, K: int) -> int:
+    """DIFFAB_METRICS_PAIR_ENERGY_WORKSPACE_BYTES of include/diffab_hip_energy.h."""
+    return G * K * 24 + 1024
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class PairPotential:
+    """A residue-level, distance-binned pair potential: ``table`` (NB,V,V), or (V,V) for one bin - anything ``torch.as_tensor`` takes,
+    kept as a float32 CPU tensor (NB,V,V) - and ``bin_edges``, NB + 1 distances in Angstrom, kept as a tuple of floats.  A pair of
+    residues whose sites are d apart, ``bin_edges[b] <= d < bin_edges[b + 1]``, scores ``table[b][first][second]``, the designed
+    residue's token first (for two designed residues, the lower slot's): a symmetric table does not care, an asymmetric one can hold
+    paratope-versus-epitope propensities.  1 <= V <= 32 token classes, 1 <= NB <= 8 bins; the edges finite, >= 0 and strictly
+    ascending, and so are their float32 squares (the comparison is made on squared distances).  ValueError otherwise."""
+    table: torch.Tensor
+    bin_edges: tuple
+
+    def __post_init__(self):
+        who = "metrics.PairPotential()"
+        try:
+            t = torch.as_tensor(self.table).detach().cpu()
+        except (TypeError, ValueError, RuntimeError):
+            t = None
+        if t is None or t.is_complex() or t.dtype == torch.bool or t.dim() not in (2, 3):
+            raise ValueError(f"{who}: table must be numbers of shape (NB, V, V) or (V, V)")
+        t = t.unsqueeze(0) if t.dim() == 2 else t
+        NB, V = int(t.shape[0]), int(t.shape[1])
+        if t.shape[2] != V or not 1 <= V <= ENERGY_MAX_CLASSES or not 1 <= NB <= ENERGY_MAX_BINS:
+            raise ValueError(f"{who}: table is {tuple(t.shape)}, expected (NB, V, V) with 1 <= NB <= {ENERGY_MAX_BINS} bins and "
+                             f"1 <= V <= {ENERGY_MAX_CLASSES} token classes")
+        t = t.to(torch.float32).contiguous()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{who}: table must hold numbers that are finite in float32")
+        edges = self.bin_edges
+        if isinstance(edges, torch.Tensor):
+            edges = edges.detach().cpu().tolist() if edges.dim() == 1 else None
+        if isinstance(edges, (str, bytes)) or not isinstance(edges, Sequence) or len(edges) != NB + 1 \
+                or any(isinstance(e, bool) or not isinstance(e, (int, float)) for e in edges):
+            raise ValueError(f"{who}: bin_edges must be NB + 1 = {NB + 1} numbers, the edges of the table's {NB} distance bins")
+        edges = tuple(float(e) for e in edges)
+        e32 = torch.tensor(edges, dtype=torch.float64).to(torch.float32)
+        sq = e32 * e32
+        if not all(math.isfinite(e) and e >= 0 for e in edges) or not bool((e32[1:] > e32[:-1]).all()):
+            raise ValueError(f"{who}: bin_edges must be finite, >= 0 and strictly ascending (in float32), got {edges}")
+        if not bool(torch.isfinite(sq).all()) or not bool((sq[1:] > sq[:-1]).all()):
+            raise ValueError(f"{who}: the float32 squares of bin_edges must be finite and strictly ascending, got {edges}")
+        object.__setattr__(self, "table", t)
+        object.__setattr__(self, "bin_edges", edges)
+
+
+def contact_potential(hydrophobicity=KYTE_DOOLITTLE, charge=RESIDUE_CHARGE, bin_edges=(0.0, 6.5, 9.0), bin_scale=(1.0, 0.5),
+                      hydrophobic: float = 1.0, electrostatic: float = 1.0) -> PairPotential:
+    """The default table of ``interface_energy``: ``E[b][a][c] = bin_scale[b] * (-hydrophobic * (h_a - 1) * (h_c - 1) + electrostatic *
+    q_a * q_c)`` with h = ``hydrophobicity`` (``KYTE_DOOLITTLE``: hydropathy on [1, 2]) and q = ``charge`` (``RESIDUE_CHARGE``), so two
+    hydrophobic residues in contact and two opposite charges score below zero and two like charges above; a class whose hydrophobicity
+    is 0 (X) gets zero rows and columns.  Evaluated in float64, rounded to float32 once.
+
+    THIS IS THE PROJECT'S OWN CHOICE, a placeholder so that the call works out of the box.  It is not a fitted potential and no
+    predictive value is claimed for it.  Where you have a Miyazawa-Jernigan contact-energy matrix or a paratope-epitope propensity
+    table, pass it as ``PairPotential(table, bin_edges)`` instead."""
+    who = "metrics.contact_potential()"
+    hyd, chg = _check_weight_table(who, "hydrophobicity", hydrophobicity), _check_weight_table(who, "charge", charge)
+    if hyd.numel() != chg.numel():
+        raise ValueError(f"{who}: hydrophobicity has {hyd.numel()} classes and charge {chg.numel()}: one table entry per token class in both")
+    try:
+        scale = torch.as_tensor(bin_scale, dtype=torch.float64).detach().cpu()
+    except (TypeError, ValueError, RuntimeError):
+        scale = None
+    if scale is None or scale.dim() != 1 or not 1 <= scale.numel() <= ENERGY_MAX_BINS or not bool(torch.isfinite(scale).all()):
+        raise ValueError(f"{who}: bin_scale must be 1 to {ENERGY_MAX_BINS} finite numbers, one per distance bin")
+    for name, v in (("hydrophobic", hydrophobic), ("electrostatic", electrostatic)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{who}: {name} must be a finite number, got {v!r}")
+    h, q = hyd.double(), chg.double()
+    pair = -float(hydrophobic) * (h - 1)[:, None] * (h - 1)[None, :] + float(electrostatic) * q[:, None] * q[None, :]
+    known = (hyd != 0).double()
+    pair = pair * known[:, None] * known[None, :]
+    try:
+        return PairPotential((scale[:, None, None] * pair[None]).to(torch.float32), bin_edges)
+    except ValueError as e:
+        raise ValueError(f"{who}: {e}") from None
+
+
+def _pair_energy(lib, sites, csites, tokens, gm, rm, ag, chain, ridx, table, edges, rows, group_size, K, min_separation, substitutions):
+    """One diffab_metrics_pair_energy call on device operands -> the dict of its outputs, on the library's device."""
+    dev = _hip.device()
+    NB, V = int(table.shape[0]), int(table.shape[1])
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = {"e_antigen": f32(rows), "e_framework": f32(rows), "e_internal": f32(rows), "n_pairs": i32(rows, 3, NB), "residue_energy": f32(rows, K),
+           "residue_antigen_energy": f32(rows, K), "n_partners": i32(rows, K), "substitution": f32(rows, K, V) if substitutions else None}
+    host = (ctypes.c_float * (NB + 1))(*edges)
+    G = rows // group_size
+    nbytes = pair_energy_workspace_bytes(G, K)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_pair_energy(_hip.ptr(sites), _hip.ptr(csites), _hip.ptr(tokens), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(ag),
+                                              _hip.ptr(chain), _hip.ptr(ridx), _hip.ptr(table), ctypes.cast(host, ctypes.c_void_p), rows,
+                                              group_size, K, V, NB, min_separation, *[_hip.ptr(t) for t in out.values()], _hip.ptr(ws), nbytes,
+                                              _hip.stream_ptr()), "diffab_metrics_pair_energy")
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def interface_energy(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
+                     antigen_mask: Optional[torch.Tensor] = None, residue_mask: Optional[torch.Tensor] = None, chain_idx=None, residue_idx=None,
+                     group_size: int = 1, potential: Optional[PairPotential] = None, min_separation: int = 3, substitutions: bool = False,
+                     native: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """A binding score of each design under a residue-level, distance-binned pair potential: every designed residue against every
+    residue it touches, scored by what the two residues are - the stand-in of docking and design triage for a binding energy on
+    backbone frames, and with ``native`` the DiffAb paper's IMP under this potential.  No parity with Rosetta's ddG is claimed, which
+    needs side chains.  ``designs``, ``generation_mask``, ``context``, ``antigen_mask``, ``residue_mask`` and ``group_size`` are
+    ``patches``' arguments and the sites are ``patches``' sites: a generated residue's is the CB of its own frame, the CA where the
+    design's token is Gly; a non-generated residue's is slot 4 of ``context['xyz']`` where ``context['atom_mask']`` has it and the
+    token is not Gly, else slot 1 (CA), and a non-generated residue without a CA is left out; without ``context`` the non-generated
+    residues take the frame sites of the first row of their group.  Unlike ``patches`` the antigen is what this call is about.
+
+    ``potential`` is a ``PairPotential`` (default ``contact_potential()``, a placeholder of this project's own choice - read its
+    docstring).  A pair of present residues, at least one of them generated, both tokens inside the table, is counted when the squared
+    distance of the two sites falls into a bin, ``edge[b]**2 <= d2 < edge[b + 1]**2`` in float32, and its term is
+    ``table[b][first][second]``, the generated residue's token first (of two generated residues the lower slot's).  Pairs on one chain
+    whose ``residue_idx`` differ by less than ``min_separation`` are skipped - chain neighbours are always in contact and say nothing;
+    ``chain_idx`` / ``residue_idx`` are (K,) or (G,K), given together or not at all (default one chain and ``arange(K)``).  The class of a
+    pair: INTERNAL when both residues are generated, ANTIGEN when the other one is inside ``antigen_mask``, FRAMEWORK otherwise.
+
+    Returns, per row (rows,): ``e_antigen``, ``e_framework``, ``e_internal`` fp32 (every pair once; fp64 sums in a fixed order, rounded
+    once) and ``e_binding``, another name of ``e_antigen``; ``n_pairs`` (rows,3,NB) int32, the counted pairs per class (0 antigen, 1
+    framework, 2 internal) and bin.  Per residue (rows,K), ready as ``b_factor`` of ``io.write_pdb``: ``residue_energy`` (the terms of
+    every counted pair the residue is part of; for an antigen residue its pairs with the design - the epitope's hot spots),
+    ``residue_antigen_energy`` (the ANTIGEN class only) and ``n_partners`` int32.  With ``substitutions=True`` also ``substitution``
+    (rows,K,V): what replacing the token of a generated residue by class v would do to ``e_antigen`` with the structure held (0 at
+    the residue's own token and for every residue that is not generated).
+
+    With ``native`` - the dict ``evaluate`` takes, (G,K) - the same entry runs on the native's frames with ``group_size`` 1 and adds
+    ``native_e_antigen`` (G,), ``delta`` = ``e_antigen - native_e_antigen`` of the row's patch (rows,), ``improved`` (rows,) bool =
+    ``e_antigen < native_e_antigen``, one fp32 comparison, and ``imp`` (G,), the share of improved designs of each patch.  The native
+    is put on the SAME site model as the designs - the CB its frame implies, not its real CB - so that the two numbers compare like
+    with like.
+
+    One C-ABI call (two launches, ``include/diffab_hip_energy.h``), two with ``native``; results on the device of
+    ``designs['seq_idx']``; ValueError naming the argument before any device work."""
+    who = "metrics.interface_energy()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    if K > ENERGY_MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch, at most {ENERGY_MAX_K}")
+    if antigen_mask is not None:
+        _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
+    if potential is None:
+        potential = contact_potential()
+    if not isinstance(potential, PairPotential):
+        raise ValueError(f"{who}: potential must be a metrics.PairPotential (or None for metrics.contact_potential()), got {type(potential).__name__}")
+    if not _is_int(min_separation) or min_separation < 0 or min_separation >= 2 ** 31:
+        raise ValueError(f"{who}: min_separation must be an int >= 0, got {min_separation!r}")
+    if not isinstance(substitutions, bool):
+        raise ValueError(f"{who}: substitutions must be a bool, got {substitutions!r}")
+    if (chain_idx is None) != (residue_idx is None):
+        raise ValueError(f"{who}: chain_idx and residue_idx go together, {'chain_idx' if chain_idx is None else 'residue_idx'} is missing")
+    if context is not None:
+        A = _check_context(who, context, G, K)
+        if A < 2:
+            raise ValueError(f"{who}: context['xyz'] has A = {A} atoms per residue: slot 1 (CA) is needed")
+    if native is not None:
+        nG, nK = _check_frames(who, "native", native, "backbone")
+        if (nG, nK) != (G, K):
+            raise ValueError(f"{who}: native['seq_idx'] is {(nG, nK)}, expected {(G, K)} (one row per patch)")
+    chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    sites, csites, tokens, gm, rm = _residue_sites(designs, generation_mask, residue_mask, context, group_size)
+    ag = None if antigen_mask is None else _hip.dev_mask(antigen_mask)
+    chain, ridx = chain.to(dev), ridx.to(dev)
+    table = _hip.dev_f32(potential.table)
+    out = _pair_energy(lib, sites, csites, tokens, gm, rm, ag, chain, ridx, table, potential.bin_edges, rows, group_size, K, min_separation,
+                       substitutions)
+    out["e_binding"] = out["e_antigen"]
+    if native is not None:
+        nsites, ncsites, ntokens, _, nrm = _residue_sites(native, generation_mask, residue_mask, context, 1)
+        ref = _pair_energy(lib, nsites, ncsites, ntokens, gm, nrm, ag, chain, ridx, table, potential.bin_edges, G, 1, K, min_separation, False)
+        base = ref["e_antigen"]
+        per_row = base.repeat_interleave(group_size)
+        out["native_e_antigen"] = base
+        out["delta"] = out["e_antigen"] - per_row
+        out["improved"] = out["e_antigen"] < per_row
+        out["imp"] = out["improved"].view(G, group_size).float().mean(1)
     return {k: v.to(out_dev) for k, v in out.items()}
 
 
