@@ -9,7 +9,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_cluster.h"
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
@@ -268,17 +268,14 @@ int diffab_metrics_cluster(const float* dist, const float* cutoff, const float* 
                            int32_t* n_unassigned, void* workspace, size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
   const char* who = "metrics_cluster";
-  DIFFAB_REQUIRE(G >= 0 && N >= 1, DIFFAB_ERR_ARG, "%s: negative or empty extent (G = %d, N = %d)", who, G, N);
-  DIFFAB_REQUIRE(N <= kMaxGroup, DIFFAB_ERR_ARG, "%s: N = %d, at most %d designs per group", who, N, kMaxGroup);
+  if (!group_shape_ok(who, G, N)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(M >= 0 && M <= N, DIFFAB_ERR_ARG, "%s: M = %d clusters outside [0, N = %d]", who, M, N);
   if (G == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(dist != nullptr && cutoff != nullptr, DIFFAB_ERR_ARG, "%s: null input", who);
   DIFFAB_REQUIRE(label != nullptr && count != nullptr && (M == 0 || (center != nullptr && size != nullptr)), DIFFAB_ERR_ARG,
                  "%s: null output", who);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const ClusterWorkspace ws = carve_cluster(workspace, G, N);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   const int Np = pad64(N), S = (N + kSegCols - 1) / kSegCols;
   const int64_t items = static_cast<int64_t>(G) * (Np / 64) * S;
   DIFFAB_REQUIRE(items <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "%s: G = %d groups of N = %d are more tiles than one launch holds", who, G, N);

@@ -3,7 +3,7 @@
 // comments of the two entries in include/diffab_hip_develop.h.
 //
 // Built with -ffp-contract=off like the other defined numbers (csrc/Makefile): the squared distance is the fp32 value
-// (dx*dx + dy*dy) + dz*dz of csrc/geometry_kernels.hip and every decision is one strict comparison on it.  A pair term is
+// (dx*dx + dy*dy) + dz*dz (dist2 of analysis_common.h, written out here) and every decision is one strict comparison on it.  A pair term is
 // w_i * w_j / max(d2, min^2) in fp64 - the product of two fp32 values is exact in fp64 and the build has no fast-math flag, so the
 // quotient is correctly rounded - and the sums are fp64 in a fixed order, rounded to fp32 once.  The motifs are integer work on bits.
 // VALU + LDS only; no atomics; every value reaches memory through plain C++ stores.
@@ -11,12 +11,11 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_develop.h"
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
 
-constexpr int kMaxGroup = DIFFAB_METRICS_MAX_GROUP;
 constexpr int kMaxK = DIFFAB_DEVELOP_MAX_K;
 constexpr int kMaxClasses = DIFFAB_DEVELOP_MAX_CLASSES;
 constexpr int kMaxMotifs = DIFFAB_DEVELOP_MAX_MOTIFS;
@@ -24,31 +23,11 @@ constexpr int kMotifWords = DIFFAB_DEVELOP_MOTIF_WORDS;
 static_assert(kMaxK % 64 == 0 && kMaxK <= 65535, "lane l owns residues l, l + 64, ...; the list of exposed residues holds 16-bit slots");
 static_assert(kMaxMotifs <= 32 && kMaxClasses <= 32, "one bit per motif in motif_start, one bit per class in a motif word");
 
-constexpr uint32_t kPresent = 1u, kGenerated = 2u;               // SiteRecord::flags
 constexpr uint8_t kStatePresent = 1, kStateScope = 2, kStateExposed = 4;  // the bits of the state output
 
-// The sum of v over the 64 lanes in a fixed tree (lane ^ 32, ^ 16, ..., ^ 1): every lane ends with the same value.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // ------------------------------------------------------------------ 1. surface patches
-// What depends on the patch alone, one record per slot: the patch's site of a present non-generated residue, zeros for a present
-// generated one (the row kernel puts the row's site there) and NaN for a residue that is not present, which then fails every comparison.
-struct alignas(16) SiteRecord {
-  float x, y, z;
-  uint32_t flags;  // kPresent | kGenerated (kGenerated is set for present residues only)
-};
-
 struct PatchesWorkspace {
-  SiteRecord* site;  // (G, K)
+  SiteRecord* site;  // (G, K): the antigen is not present here, so flags are kSitePresent | kSiteGenerated
   size_t bytes;
 };
 
@@ -71,7 +50,7 @@ patches_pack_kernel(const float* __restrict__ context_sites, const uint8_t* __re
     const bool gen = present && generation_mask[base + k] != 0;
     SiteRecord r;
     r.x = r.y = r.z = present ? 0.f : NAN;
-    r.flags = (present ? kPresent : 0u) | (gen ? kGenerated : 0u);
+    r.flags = (present ? kSitePresent : 0u) | (gen ? kSiteGenerated : 0u);
     if (present && !gen) {
       const float* p = context_sites + (base + k) * 3;
       r.x = p[0], r.y = p[1], r.z = p[2];
@@ -116,7 +95,7 @@ patches_row_kernel(PatchesArgs a, PatchesWorkspace ws) {
 
   for (int k = lane; k < K; k += 64) {
     SiteRecord r = ws.site[gbase + k];
-    if ((r.flags & kGenerated) != 0u) {
+    if ((r.flags & kSiteGenerated) != 0u) {
       const float* p = a.sites + (rbase + k) * 3;
       r.x = p[0], r.y = p[1], r.z = p[2];
     }
@@ -146,9 +125,9 @@ patches_row_kernel(PatchesArgs a, PatchesWorkspace ws) {
       const float dx = me.x - o.x, dy = me.y - o.y, dz = me.z - o.z;
       const float d2 = (dx * dx + dy * dy) + dz * dz;
       count += (d2 < a.neighbour2 && j != i) ? 1 : 0;
-      near |= d2 < a.vicinity2 && (o.flags & kGenerated) != 0u;
+      near |= d2 < a.vicinity2 && (o.flags & kSiteGenerated) != 0u;
     }
-    const bool present = (me.flags & kPresent) != 0u, gen = (me.flags & kGenerated) != 0u;
+    const bool present = (me.flags & kSitePresent) != 0u, gen = (me.flags & kSiteGenerated) != 0u;
     const bool scope = present && (gen || near);
     bool exposed = scope && count <= a.max_neighbours;
     if (a.exposed_in != nullptr) exposed = scope && mine && a.exposed_in[rbase + (mine ? i : 0)] != 0;
@@ -316,8 +295,6 @@ motifs_row_kernel(const int32_t* __restrict__ tokens, const uint8_t* __restrict_
   if (lane == 0 && n_motifs != nullptr) n_motifs[row] = total;
 }
 
-bool finite_nonnegative(float v) { return v >= 0.f && v < INFINITY; }
-
 }  // namespace
 }  // namespace diffab
 
@@ -334,11 +311,7 @@ int diffab_metrics_patches(const float* sites, const float* context_sites, const
                            void* workspace, size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
   const char* who = "metrics_patches";
-  DIFFAB_REQUIRE(rows >= 0 && group_size >= 1 && K >= 1, DIFFAB_ERR_ARG, "%s: negative or empty extent (%d rows, group size %d, K = %d)", who,
-                 rows, group_size, K);
-  DIFFAB_REQUIRE(group_size <= kMaxGroup, DIFFAB_ERR_ARG, "%s: group size %d, at most %d designs per group", who, group_size, kMaxGroup);
-  DIFFAB_REQUIRE(K <= kMaxK, DIFFAB_ERR_ARG, "%s: K = %d residues per patch, at most %d", who, K, kMaxK);
-  DIFFAB_REQUIRE(rows % group_size == 0, DIFFAB_ERR_ARG, "%s: %d rows are not a multiple of group_size = %d", who, rows, group_size);
+  if (!rows_shape_ok(who, rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(V >= 1 && V <= kMaxClasses, DIFFAB_ERR_ARG, "%s: V = %d classes outside [1, %d]", who, V, kMaxClasses);
   DIFFAB_REQUIRE(finite_nonnegative(neighbour_distance), DIFFAB_ERR_ARG, "%s: neighbour_distance must be finite and >= 0, got %g", who,
                  static_cast<double>(neighbour_distance));
@@ -354,11 +327,9 @@ int diffab_metrics_patches(const float* sites, const float* context_sites, const
                  static_cast<double>(min_distance));
   if (rows == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(sites && context_sites && tokens && generation_mask && hydrophobicity && charge, DIFFAB_ERR_ARG, "%s: null input", who);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const int32_t G = rows / group_size;
   const PatchesWorkspace ws = carve_patches(workspace, G, K);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(patches_pack_kernel, dim3(G), dim3(64), 0, st, context_sites, generation_mask, residue_mask, antigen_mask, K, ws);
   PatchesArgs a;
@@ -380,11 +351,7 @@ int diffab_metrics_motifs(const int32_t* tokens, const uint8_t* generation_mask,
                           void* stream) {
   StreamOrder order_(stream);
   const char* who = "metrics_motifs";
-  DIFFAB_REQUIRE(rows >= 0 && group_size >= 1 && K >= 1, DIFFAB_ERR_ARG, "%s: negative or empty extent (%d rows, group size %d, K = %d)", who,
-                 rows, group_size, K);
-  DIFFAB_REQUIRE(group_size <= kMaxGroup, DIFFAB_ERR_ARG, "%s: group size %d, at most %d designs per group", who, group_size, kMaxGroup);
-  DIFFAB_REQUIRE(K <= kMaxK, DIFFAB_ERR_ARG, "%s: K = %d residues per patch, at most %d", who, K, kMaxK);
-  DIFFAB_REQUIRE(rows % group_size == 0, DIFFAB_ERR_ARG, "%s: %d rows are not a multiple of group_size = %d", who, rows, group_size);
+  if (!rows_shape_ok(who, rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(M >= 1 && M <= kMaxMotifs, DIFFAB_ERR_ARG, "%s: M = %d motifs outside [1, %d]", who, M, kMaxMotifs);
   if (rows == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(tokens && generation_mask && chain && residue_idx, DIFFAB_ERR_ARG, "%s: null input", who);
@@ -399,11 +366,9 @@ int diffab_metrics_motifs(const int32_t* tokens, const uint8_t* generation_mask,
       table.word[m * kMotifWords + p] = motifs[m * kMotifWords + p];
     }
   }
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const int32_t G = rows / group_size;
   const MotifsWorkspace ws = carve_motifs(workspace, G, K);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   if (motif_count == nullptr && n_motifs == nullptr && motif_start == nullptr) return DIFFAB_OK;  // nothing was asked for
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(motifs_succ_kernel, dim3(G), dim3(64), 0, st, residue_mask, chain, residue_idx, K, ws);

@@ -1,19 +1,18 @@
 // energy_kernels.hip - a distance-binned residue pair potential over the pairs a design takes part in:
 // diffab_metrics_pair_energy.  The rule is the header comment of the entry in include/diffab_hip_energy.h.
 //
-// Built with -ffp-contract=off like the other defined numbers (csrc/Makefile): the squared distance is the fp32 value
-// (dx*dx + dy*dy) + dz*dz of csrc/geometry_kernels.hip and a pair's bin is decided by comparisons on it.  A term is one fp32 table
+// Built with -ffp-contract=off like the other defined numbers (csrc/Makefile): the squared distance is dist2 of
+// analysis_common.h and a pair's bin is decided by comparisons on it.  A term is one fp32 table
 // entry, exact in fp64, and the sums are fp64 in a fixed order, rounded to fp32 once.  VALU + LDS only; no atomics; every value reaches
 // memory through plain C++ stores.
 #include <cmath>
 
 #include "../../include/diffab_hip_energy.h"
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
 
-constexpr int kMaxGroup = DIFFAB_METRICS_MAX_GROUP;
 constexpr int kMaxK = DIFFAB_ENERGY_MAX_K;
 constexpr int kMaxClasses = DIFFAB_ENERGY_MAX_CLASSES;
 constexpr int kMaxBins = DIFFAB_ENERGY_MAX_BINS;
@@ -23,30 +22,10 @@ static_assert(kMaxK % 64 == 0 && kMaxK <= 65535, "lane l owns residues l, l + 64
 static_assert(kMaxClasses == 32, "the scan gives every class one lane of a half wave; a token takes five bits of a record's flags");
 static_assert(kMaxK / 64 * kMaxK < 65536, "a lane's pairs of one class and bin are counted in 16 bits");
 
-// SiteRecord::flags.  kGenerated and kAntigen are set for present residues only and exclude each other; kKnown and the token (bits 8..12)
-// are the row kernel's: a token inside [0, V).
-constexpr uint32_t kPresent = 1u, kGenerated = 2u, kAntigen = 4u, kKnown = 8u;
+// SiteRecord::flags beside the shared ones: kKnown and the token (bits 8..12) are the row kernel's, a token inside [0, V).
+constexpr uint32_t kKnown = 8u;
 constexpr int kTokenShift = 8;
 enum { kClassAntigen = 0, kClassFramework = 1, kClassInternal = 2 };
-
-// The sum of v over the 64 lanes in a fixed tree (lane ^ 32, ^ 16, ..., ^ 1): every lane ends with the same value.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// What depends on the patch alone, one record per slot: the patch's site of a present non-generated residue, zeros for a present
-// generated one (the row kernel puts the row's site there) and NaN for a residue that is not present, which then has no bin.
-struct alignas(16) SiteRecord {
-  float x, y, z;
-  uint32_t flags;
-};
 
 struct EnergyWorkspace {
   SiteRecord* site;  // (G, K)
@@ -76,7 +55,7 @@ energy_pack_kernel(const float* __restrict__ context_sites, const uint8_t* __res
     const bool antigen = present && !gen && antigen_mask != nullptr && antigen_mask[base + k] != 0;
     SiteRecord r;
     r.x = r.y = r.z = present ? 0.f : NAN;
-    r.flags = (present ? kPresent : 0u) | (gen ? kGenerated : 0u) | (antigen ? kAntigen : 0u);
+    r.flags = (present ? kSitePresent : 0u) | (gen ? kSiteGenerated : 0u) | (antigen ? kSiteAntigen : 0u);
     if (present && !gen) {
       const float* p = context_sites + (base + k) * 3;
       r.x = p[0], r.y = p[1], r.z = p[2];
@@ -105,8 +84,7 @@ struct EnergyArgs {
 // The bin of the pair, -1 without one: the number of edges at or below d2 is 1 ... NB for a pair with a bin, 0 below e2[0] or for a
 // NaN, and more than NB at or beyond e2[NB] (the edges behind NB are +inf, which only an infinite d2 reaches).
 __device__ __forceinline__ int bin_of(const SiteRecord& me, const SiteRecord& o, const EnergyArgs& a) {
-  const float dx = me.x - o.x, dy = me.y - o.y, dz = me.z - o.z;
-  const float d2 = (dx * dx + dy * dy) + dz * dz;
+  const float d2 = dist2(me.x, me.y, me.z, o.x, o.y, o.z);
   int n = 0;
 #pragma unroll
   for (int b = 0; b <= kMaxBins; ++b) n += d2 >= a.e2[b] ? 1 : 0;
@@ -148,7 +126,7 @@ energy_row_kernel(EnergyArgs a, EnergyWorkspace ws) {
     r.x = r.y = r.z = NAN, r.flags = 0u;
     if (mine) {
       r = ws.site[gbase + i];
-      if ((r.flags & kGenerated) != 0u) {
+      if ((r.flags & kSiteGenerated) != 0u) {
         const float* p = a.sites + (rbase + i) * 3;
         r.x = p[0], r.y = p[1], r.z = p[2];
       }
@@ -158,8 +136,8 @@ energy_row_kernel(EnergyArgs a, EnergyWorkspace ws) {
       s_chain[i] = ws.chain[gbase + i];
       s_ridx[i] = ws.ridx[gbase + i];
     }
-    const bool gen = (r.flags & kGenerated) != 0u;
-    const bool ag = (r.flags & (kAntigen | kKnown)) == (kAntigen | kKnown);
+    const bool gen = (r.flags & kSiteGenerated) != 0u;
+    const bool ag = (r.flags & (kSiteAntigen | kKnown)) == (kSiteAntigen | kKnown);
     const unsigned long long vg = __ballot(gen), va = __ballot(ag);
     if (gen) s_gen[n_gen + __popcll(vg & below)] = static_cast<uint16_t>(i);
     if (ag) s_ag[n_ag + __popcll(va & below)] = static_cast<uint16_t>(i);
@@ -181,9 +159,9 @@ energy_row_kernel(EnergyArgs a, EnergyWorkspace ws) {
     const int64_t ri = mine ? s_ridx[i] : 0;
     const int ti = static_cast<int>(me.flags >> kTokenShift);
     const bool known = (me.flags & kKnown) != 0u;
-    const bool walks_all = known && (me.flags & kGenerated) != 0u;
-    const bool walks_gen = known && (me.flags & (kPresent | kGenerated)) == kPresent;
-    const bool i_antigen = (me.flags & kAntigen) != 0u;
+    const bool walks_all = known && (me.flags & kSiteGenerated) != 0u;
+    const bool walks_gen = known && (me.flags & (kSitePresent | kSiteGenerated)) == kSitePresent;
+    const bool i_antigen = (me.flags & kSiteAntigen) != 0u;
     double r_all = 0.0, r_ag = 0.0, r_fw = 0.0, r_in = 0.0;
     int partners = 0;
     if (__ballot(walks_all) != 0ull) {  // (uniform)
@@ -192,10 +170,10 @@ energy_row_kernel(EnergyArgs a, EnergyWorkspace ws) {
         const int b = bin_of(me, o, a);
         if (walks_all && j != i && b >= 0 && (o.flags & kKnown) != 0u && !too_near(ci, ri, s_chain[j], s_ridx[j], a.min_sep)) {
           const int tj = static_cast<int>(o.flags >> kTokenShift);
-          const bool internal = (o.flags & kGenerated) != 0u;
+          const bool internal = (o.flags & kSiteGenerated) != 0u;
           const bool swap = internal && j < i;  // an internal pair: the lower slot first
           const double term = static_cast<double>(s_table[(b * V + (swap ? tj : ti)) * Vp + (swap ? ti : tj)]);
-          const int cls = internal ? kClassInternal : (o.flags & kAntigen) != 0u ? kClassAntigen : kClassFramework;
+          const int cls = internal ? kClassInternal : (o.flags & kSiteAntigen) != 0u ? kClassAntigen : kClassFramework;
           const unsigned long long inc = 1ull << ((b & 3) * 16);
           const int hi = b >> 2;
           ++partners;
@@ -255,7 +233,7 @@ energy_row_kernel(EnergyArgs a, EnergyWorkspace ws) {
     float* out = a.substitution + rbase * V;
     if (live) {
       for (int t = lane; t < K * V; t += 64)
-        if ((s_site[t / V].flags & kGenerated) == 0u) out[t] = 0.f;
+        if ((s_site[t / V].flags & kSiteGenerated) == 0u) out[t] = 0.f;
     }
     const int half = lane >> 5, v = lane & 31;
     for (int e0 = 0; e0 < n_gen; e0 += 2) {
@@ -295,11 +273,7 @@ int diffab_metrics_pair_energy(const float* sites, const float* context_sites, c
                                void* workspace, size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
   const char* who = "metrics_pair_energy";
-  DIFFAB_REQUIRE(rows >= 0 && group_size >= 1 && K >= 1, DIFFAB_ERR_ARG, "%s: negative or empty extent (%d rows, group size %d, K = %d)", who,
-                 rows, group_size, K);
-  DIFFAB_REQUIRE(group_size <= kMaxGroup, DIFFAB_ERR_ARG, "%s: group size %d, at most %d designs per group", who, group_size, kMaxGroup);
-  DIFFAB_REQUIRE(K <= kMaxK, DIFFAB_ERR_ARG, "%s: K = %d residues per patch, at most %d", who, K, kMaxK);
-  DIFFAB_REQUIRE(rows % group_size == 0, DIFFAB_ERR_ARG, "%s: %d rows are not a multiple of group_size = %d", who, rows, group_size);
+  if (!rows_shape_ok(who, rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(V >= 1 && V <= kMaxClasses, DIFFAB_ERR_ARG, "%s: V = %d classes outside [1, %d]", who, V, kMaxClasses);
   DIFFAB_REQUIRE(NB >= 1 && NB <= kMaxBins, DIFFAB_ERR_ARG, "%s: NB = %d bins outside [1, %d]", who, NB, kMaxBins);
   DIFFAB_REQUIRE(min_separation >= 0, DIFFAB_ERR_ARG, "%s: min_separation must be >= 0, got %d", who, min_separation);
@@ -312,7 +286,7 @@ int diffab_metrics_pair_energy(const float* sites, const float* context_sites, c
   for (int b = 0; b <= kMaxBins; ++b) a.e2[b] = INFINITY;
   for (int b = 0; b <= NB; ++b) {
     const float e = bin_edges[b];
-    DIFFAB_REQUIRE(e >= 0.f && e < INFINITY, DIFFAB_ERR_ARG, "%s: bin_edges[%d] must be finite and >= 0, got %g", who, b, static_cast<double>(e));
+    DIFFAB_REQUIRE(finite_nonnegative(e), DIFFAB_ERR_ARG, "%s: bin_edges[%d] must be finite and >= 0, got %g", who, b, static_cast<double>(e));
     DIFFAB_REQUIRE(b == 0 || e > bin_edges[b - 1], DIFFAB_ERR_ARG, "%s: bin_edges must be strictly ascending, bin_edges[%d] = %g after %g", who, b,
                    static_cast<double>(e), static_cast<double>(bin_edges[b > 0 ? b - 1 : 0]));
     a.e2[b] = e * e;
@@ -320,11 +294,9 @@ int diffab_metrics_pair_energy(const float* sites, const float* context_sites, c
                    "%s: the fp32 squares of bin_edges must be finite and strictly ascending, bin_edges[%d] = %g has the square %g", who, b,
                    static_cast<double>(e), static_cast<double>(a.e2[b]));
   }
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const int32_t G = rows / group_size;
   const EnergyWorkspace ws = carve_energy(workspace, G, K);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(energy_pack_kernel, dim3(G), dim3(64), 0, st, context_sites, generation_mask, residue_mask, antigen_mask, chain, residue_idx,
                      K, ws);

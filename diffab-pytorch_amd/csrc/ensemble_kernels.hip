@@ -9,7 +9,7 @@
 // reaches memory through plain C++ stores.  Four launches: accumulate, finish, deviations, rows.
 #include <climits>
 
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
@@ -60,16 +60,6 @@ __device__ inline double weight_of(const float* __restrict__ weights, int64_t ro
   if (weights == nullptr) return 1.0;
   const float w = weights[row];
   return (w > 0.f && w < INFINITY) ? static_cast<double>(w) : 0.0;
-}
-
-// Sum over the 64 lanes of a wave, the same fixed butterfly on every lane (so every lane holds the same bits).
-template <int V>
-__device__ inline void wave_sum(double (&v)[V]) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] += __shfl_xor(v[i], d, 64);
-  }
 }
 
 // The four waves' columns [wave][line][lane] of `lines` lines, added in wave order and stored to out[line * K + k].
@@ -353,10 +343,7 @@ int diffab_metrics_ensemble(const int64_t* seq_idx, const float* points, const u
   if (G == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(seq_idx && points && generation_mask, DIFFAB_ERR_ARG, "metrics_ensemble: null input");
   const EnsembleWorkspace ws = carve_ensemble(workspace, G, N, K, P, V);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 16 == 0, DIFFAB_ERR_ARG,
-                 "metrics_ensemble: the workspace must be a 16-byte aligned device buffer");
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "metrics_ensemble: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 ws.bytes);
+  if (const int e = workspace_ok("metrics_ensemble", workspace, 16, workspace_bytes, ws.bytes)) return e;
   const int S = (N + kSlice - 1) / kSlice, KC = (K + kChunk - 1) / kChunk;
   const dim3 grid(static_cast<unsigned>(G), static_cast<unsigned>(S), static_cast<unsigned>(KC));
   const size_t lds = static_cast<size_t>(kWaves) * static_cast<size_t>(V > 3 * P ? V : 3 * P) * kChunk * sizeof(double);

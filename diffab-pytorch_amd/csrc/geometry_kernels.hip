@@ -2,18 +2,17 @@
 // (diffab_metrics_backbone) and atom clashes / antigen contacts of the generated residues against the rest of the patch
 // (diffab_metrics_contacts).  The definitions are the header comments of the two entries.
 //
-// Built with -ffp-contract=off (csrc/Makefile): the squared distance is the fp32 value (dx*dx + dy*dy) + dz*dz and every count is a
+// Built with -ffp-contract=off (csrc/Makefile): the squared distance is dist2 of analysis_common.h and every count is a
 // comparison on it, so the integer outputs are defined numbers.  The dihedrals and bond lengths are fp64 from the fp32 points, rounded once.
 // VALU + LDS only; the only atomics are integer adds on LDS; every value reaches memory through plain C++ stores.
 #include <climits>
 
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
 
 constexpr int kMaxK = DIFFAB_METRICS_MAX_K;
-constexpr int kMaxGroup = DIFFAB_METRICS_MAX_GROUP;
 constexpr int kMaxPoints = DIFFAB_METRICS_MAX_POINTS;
 constexpr int kMaxContextAtoms = DIFFAB_METRICS_MAX_CONTEXT_ATOMS;
 constexpr int kChunkAtoms = DIFFAB_METRICS_CONTACTS_CHUNK_ATOMS;
@@ -293,8 +292,7 @@ metrics_contacts_kernel(const float* __restrict__ points, const uint8_t* __restr
   auto against = [&](float qx, float qy, float qz, bool q_valid, bool counted, int& c, bool& near) {
 #pragma unroll
     for (int a = 0; a < P; ++a) {
-      const float dx = px[a] - qx, dy = py[a] - qy, dz = pz[a] - qz;
-      float d2 = (dx * dx + dy * dy) + dz * dz;
+      float d2 = dist2(px[a], py[a], pz[a], qx, qy, qz);
       d2 = (q_valid && ((pv >> a) & 1u) != 0u) ? d2 : INFINITY;
       least = fminf(least, d2);
       near |= d2 < contact2;
@@ -432,34 +430,6 @@ metrics_contacts_kernel(const float* __restrict__ points, const uint8_t* __restr
   }
 }
 
-bool shape_ok(const char* who, int32_t rows, int32_t group_size, int32_t K) {
-  if (rows < 0 || group_size < 1 || K < 1) {
-    set_error("%s: negative or empty extent (%d rows, group size %d, K = %d)", who, rows, group_size, K);
-    return false;
-  }
-  if (group_size > kMaxGroup) {
-    set_error("%s: group size %d, at most %d designs per group", who, group_size, kMaxGroup);
-    return false;
-  }
-  if (K > kMaxK) {
-    set_error("%s: K = %d residues per patch, at most %d", who, K, kMaxK);
-    return false;
-  }
-  if (rows % group_size != 0) {
-    set_error("%s: %d rows are not a multiple of group_size = %d", who, rows, group_size);
-    return false;
-  }
-  return true;
-}
-
-bool workspace_ok(const char* who, const void* workspace) {
-  if (workspace == nullptr || reinterpret_cast<uintptr_t>(workspace) % 16 != 0) {
-    set_error("%s: the workspace must be a 16-byte aligned device buffer", who);
-    return false;
-  }
-  return true;
-}
-
 }  // namespace
 }  // namespace diffab
 
@@ -472,18 +442,16 @@ int diffab_metrics_backbone(const float* points, const uint8_t* generation_mask,
                             float* psi, float* omega, float* peptide_bond, int32_t* n_bonds, float* max_peptide_deviation,
                             int32_t* n_chain_break, int32_t* n_cis, void* workspace, size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
-  if (!shape_ok("metrics_backbone", rows, group_size, K)) return DIFFAB_ERR_ARG;
-  DIFFAB_REQUIRE(bond_tolerance >= 0.f && bond_tolerance < INFINITY, DIFFAB_ERR_ARG,
+  if (!rows_shape_ok("metrics_backbone", rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
+  DIFFAB_REQUIRE(finite_nonnegative(bond_tolerance), DIFFAB_ERR_ARG,
                  "metrics_backbone: bond_tolerance must be finite and >= 0, got %g", static_cast<double>(bond_tolerance));
   if (rows == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(points && generation_mask && chain && residue_idx, DIFFAB_ERR_ARG, "metrics_backbone: null input");
   DIFFAB_REQUIRE(phi && psi && omega && peptide_bond && n_bonds && max_peptide_deviation && n_chain_break && n_cis, DIFFAB_ERR_ARG,
                  "metrics_backbone: null output");
-  if (!workspace_ok("metrics_backbone", workspace)) return DIFFAB_ERR_ARG;
   const int32_t G = rows / group_size;
   const LinkWorkspace ws = carve_links(workspace, G, K);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "metrics_backbone: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 ws.bytes);
+  if (const int e = workspace_ok("metrics_backbone", workspace, 16, workspace_bytes, ws.bytes)) return e;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(geometry_links_kernel, dim3(G), dim3(256), 0, st, chain, residue_idx, residue_mask, K, ws.succ, ws.pred);
   hipLaunchKernelGGL(metrics_backbone_kernel, dim3(rows), dim3(64), 0, st, points, generation_mask, ws.succ, ws.pred, group_size, K,
@@ -500,13 +468,13 @@ int diffab_metrics_contacts(const float* points, const uint8_t* valid, const flo
                             int32_t* n_hotspot_contacted, int32_t* n_hotspot, int32_t* residue_clash, int32_t* residue_contact,
                             void* workspace, size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
-  if (!shape_ok("metrics_contacts", rows, group_size, K)) return DIFFAB_ERR_ARG;
+  if (!rows_shape_ok("metrics_contacts", rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(P >= 1 && P <= kMaxPoints, DIFFAB_ERR_ARG, "metrics_contacts: P = %d points per residue outside [1, %d]", P, kMaxPoints);
   DIFFAB_REQUIRE(A >= 1 && A <= kMaxContextAtoms, DIFFAB_ERR_ARG, "metrics_contacts: A = %d context atoms per residue outside [1, %d]", A,
                  kMaxContextAtoms);
-  DIFFAB_REQUIRE(clash_distance >= 0.f && clash_distance < INFINITY, DIFFAB_ERR_ARG,
+  DIFFAB_REQUIRE(finite_nonnegative(clash_distance), DIFFAB_ERR_ARG,
                  "metrics_contacts: clash_distance must be finite and >= 0, got %g", static_cast<double>(clash_distance));
-  DIFFAB_REQUIRE(contact_distance >= 0.f && contact_distance < INFINITY, DIFFAB_ERR_ARG,
+  DIFFAB_REQUIRE(finite_nonnegative(contact_distance), DIFFAB_ERR_ARG,
                  "metrics_contacts: contact_distance must be finite and >= 0, got %g", static_cast<double>(contact_distance));
   DIFFAB_REQUIRE(hotspot_mask == nullptr || antigen_mask != nullptr, DIFFAB_ERR_ARG, "metrics_contacts: a hotspot_mask needs an antigen_mask");
   if (rows == 0) return DIFFAB_OK;
@@ -517,11 +485,9 @@ int diffab_metrics_contacts(const float* points, const uint8_t* valid, const flo
                  "metrics_contacts: null contact output with an antigen_mask");
   DIFFAB_REQUIRE(hotspot_mask == nullptr || (n_hotspot_contacted && n_hotspot), DIFFAB_ERR_ARG,
                  "metrics_contacts: null hotspot output with a hotspot_mask");
-  if (!workspace_ok("metrics_contacts", workspace)) return DIFFAB_ERR_ARG;
   const int32_t G = rows / group_size;
   const ContactWorkspace ws = carve_contacts(workspace, G, K, A);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "metrics_contacts: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 ws.bytes);
+  if (const int e = workspace_ok("metrics_contacts", workspace, 16, workspace_bytes, ws.bytes)) return e;
   const int64_t grid = static_cast<int64_t>(G) * ((group_size + 63) / 64);
   DIFFAB_REQUIRE(grid <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "metrics_contacts: %d rows are more work-groups than one launch holds", rows);
   hipStream_t st = as_stream(stream);

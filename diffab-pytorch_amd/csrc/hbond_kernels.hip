@@ -3,7 +3,7 @@
 // include/diffab_hip_hbonds.h.
 //
 // Built with -ffp-contract=off (csrc/Makefile): the derived atoms (O, H) are fp64 expressions of the fp32 inputs in a written order,
-// rounded once; the CA cull is the fp32 value (dx*dx + dy*dy) + dz*dz; the bond energy is fp64 from the fp32 atoms and "bonded" is a strict
+// rounded once; the CA cull is dist2 of analysis_common.h; the bond energy is fp64 from the fp32 atoms and "bonded" is a strict
 // comparison on it.  fp64 + - * / sqrt are correctly rounded, so every bit of the K x K bond matrix is a defined number, and everything
 // after it is integer work on that matrix in LDS.  VALU + LDS only; the only atomics are integer ones on LDS; every value reaches memory
 // through plain C++ stores.
@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_hbonds.h"
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
@@ -257,9 +257,7 @@ __device__ void stage_atoms(const Lds& l, const HbondIn& in, const float* pp, co
 __device__ inline bool pair_energy(const Lds& l, int K, int a, int d, double& E) {
   const float* ca = atom(l, K, aCA, a);
   const float* cd = atom(l, K, aCA, d);
-  const float dx = ca[0] - cd[0], dy = ca[1] - cd[1], dz = ca[2] - cd[2];
-  const float d2 = (dx * dx + dy * dy) + dz * dz;
-  if (!(d2 < kCull2)) return false;
+  if (!(dist2(ca[0], ca[1], ca[2], cd[0], cd[1], cd[2]) < kCull2)) return false;
   const float *o = atom(l, K, aO, a), *c = atom(l, K, aC, a), *n = atom(l, K, aN, d), *h = atom(l, K, aH, d);
   const double r_on = distance(o, n), r_ch = distance(c, h), r_oh = distance(o, h), r_cn = distance(c, n);
   E = kCoupling * (((1.0 / r_on + 1.0 / r_ch) - 1.0 / r_oh) - 1.0 / r_cn);
@@ -605,11 +603,9 @@ int diffab_metrics_hbonds(const float* points, const uint8_t* donor_off, const f
   if (rows == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(points && donor_off && context_points && context_valid && context_donor_off && generation_mask && chain && residue_idx,
                  DIFFAB_ERR_ARG, "%s: null input", who);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const int32_t G = rows / group_size;
   const HbondWorkspace ws = carve_hbonds(workspace, G, K);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   hipStream_t st = as_stream(stream);
   const int W = (K + 31) / 32;
   const size_t patch_lds = lds_words(K, W, false) * 4, rows_lds = lds_words(K, W, true) * 4;

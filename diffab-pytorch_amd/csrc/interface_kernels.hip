@@ -3,16 +3,15 @@
 // all the designs of a patch (the fraction of common contacts, Jaccard).  The rules are the header comments of the two entries in
 // include/diffab_hip_interface.h.
 //
-// Built with -ffp-contract=off like the other defined numbers (csrc/Makefile): the squared distance is the fp32 value
-// (dx*dx + dy*dy) + dz*dz of csrc/geometry_kernels.hip, whose contacts kernel this file restates beside it and does not touch, and a
-// contact is one strict comparison on it.  The two quotients are plain fp32 divisions of exact integers - the build has no fast-math
+// Built with -ffp-contract=off like the other defined numbers (csrc/Makefile): the squared distance is dist2 of analysis_common.h, as
+// in diffab_metrics_contacts (csrc/geometry_kernels.hip), and a contact is one strict comparison on it.  The two quotients are plain fp32 divisions of exact integers - the build has no fast-math
 // flag, so they are correctly rounded.  Everything else is integer work on bits: ballots, ORs, ANDs, popcounts, adds.  VALU + LDS only;
 // no atomics; every value reaches memory through plain C++ stores.
 #include <climits>
 #include <cmath>
 
 #include "../../include/diffab_hip_interface.h"
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
@@ -203,8 +202,7 @@ contact_bits_kernel(const float* __restrict__ points, const uint8_t* __restrict_
             const float4 q = s_atom[b];
 #pragma unroll
             for (int a = 0; a < P; ++a) {
-              const float dx = px[a] - q.x, dy = py[a] - q.y, dz = pz[a] - q.z;
-              float d2 = (dx * dx + dy * dy) + dz * dz;
+              float d2 = dist2(px[a], py[a], pz[a], q.x, q.y, q.z);
               d2 = ((pv >> a) & 1u) != 0u ? d2 : INFINITY;
               near |= d2 < contact2;
             }
@@ -421,25 +419,19 @@ int diffab_metrics_contact_bits(const float* points, const uint8_t* valid, const
                                 size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
   const char* who = "metrics_contact_bits";
-  DIFFAB_REQUIRE(rows >= 0 && group_size >= 1 && K >= 1, DIFFAB_ERR_ARG, "%s: negative or empty extent (%d rows, group size %d, K = %d)", who,
-                 rows, group_size, K);
-  DIFFAB_REQUIRE(group_size <= kMaxGroup, DIFFAB_ERR_ARG, "%s: group size %d, at most %d designs per group", who, group_size, kMaxGroup);
-  DIFFAB_REQUIRE(K <= kMaxK, DIFFAB_ERR_ARG, "%s: K = %d residues per patch, at most %d", who, K, kMaxK);
-  DIFFAB_REQUIRE(rows % group_size == 0, DIFFAB_ERR_ARG, "%s: %d rows are not a multiple of group_size = %d", who, rows, group_size);
+  if (!rows_shape_ok(who, rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(P >= 1 && P <= kMaxPoints, DIFFAB_ERR_ARG, "%s: P = %d points per residue outside [1, %d]", who, P, kMaxPoints);
   DIFFAB_REQUIRE(A >= 1 && A <= kMaxContextAtoms, DIFFAB_ERR_ARG, "%s: A = %d context atoms per residue outside [1, %d]", who, A,
                  kMaxContextAtoms);
-  DIFFAB_REQUIRE(contact_distance >= 0.f && contact_distance < INFINITY, DIFFAB_ERR_ARG,
+  DIFFAB_REQUIRE(finite_nonnegative(contact_distance), DIFFAB_ERR_ARG,
                  "%s: contact_distance must be finite and >= 0, got %g", who, static_cast<double>(contact_distance));
   if (rows == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(points && valid && context_points && context_valid && generation_mask && antigen_mask && chain && residue_idx,
                  DIFFAB_ERR_ARG, "%s: null input", who);
   DIFFAB_REQUIRE(bits != nullptr && n_contacts != nullptr, DIFFAB_ERR_ARG, "%s: null output", who);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const int32_t G = rows / group_size;
   const ContactBitsWorkspace ws = carve_contact_bits(workspace, G, K, A);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   const int64_t grid = static_cast<int64_t>(G) * ((group_size + 63) / 64);
   DIFFAB_REQUIRE(grid <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "%s: %d rows are more work-groups than one launch holds", who, rows);
   hipStream_t st = as_stream(stream);
@@ -471,10 +463,8 @@ int diffab_metrics_pairwise_bits(const int32_t* bits, int32_t G, int32_t N, int3
   DIFFAB_REQUIRE(L <= kMaxWords, DIFFAB_ERR_ARG, "%s: L = %d words per design, at most %d", who, L, kMaxWords);
   if (G == 0) return DIFFAB_OK;
   DIFFAB_REQUIRE(bits != nullptr, DIFFAB_ERR_ARG, "%s: null input", who);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const PairBitsWorkspace ws = carve_pair_bits(workspace, G, N, L);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   const int Np = pad64(N), S = Np / 64;
   const int64_t tiles = static_cast<int64_t>(G) * (S * (S + 1) / 2);
   DIFFAB_REQUIRE(tiles <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "%s: G = %d groups of N = %d are more tiles than one launch holds", who, G, N);

@@ -8,7 +8,7 @@
 // products enter through explicit fma) and solve in fp64.  VALU + LDS only, no atomics; every value reaches memory through plain C++ stores.
 #include <climits>
 
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
@@ -55,16 +55,6 @@ __device__ inline double kabsch_msd(const double (&h)[9], double spread, double 
   double trace = s0 + s1 + s2;
   if (det < 0.0) trace -= 2.0 * fmin(s0, fmin(s1, s2));
   return fmax(0.0, spread - 2.0 * trace) / m;
-}
-
-// Sum over the 64 lanes of a wave, the same fixed butterfly on every lane (so every lane holds the same bits).
-template <int V>
-__device__ inline void wave_sum(double (&v)[V]) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] += __shfl_xor(v[i], d, 64);
-  }
 }
 
 // ------------------------------------------------------------------ 1. designs against the native
@@ -186,9 +176,9 @@ metrics_pack_kernel(const int64_t* __restrict__ seq, const float* __restrict__ p
     for (int k0 = 0; k0 < K; k0 += 64) {
       const int k = k0 + lane;
       const bool in = k < K && gm[k] != 0 && (rm == nullptr || rm[k] != 0);
-      const unsigned long long vote = __ballot(in);
-      if (in) s_list[n + __popcll(vote & ((1ull << lane) - 1ull))] = static_cast<uint16_t>(k);
-      n += __popcll(vote);
+      const BallotRank r = ballot_rank(in, lane);
+      if (in) s_list[n + r.rank] = static_cast<uint16_t>(k);
+      n += r.count;
     }
     if (lane == 0) s_n = n;
   }
@@ -576,10 +566,7 @@ int diffab_metrics_pairwise(const int64_t* seq_idx, const float* points, const u
   DIFFAB_REQUIRE(seq_idx && points && generation_mask, DIFFAB_ERR_ARG, "metrics_pairwise: null input");
   DIFFAB_REQUIRE(rmsd && seq_identity, DIFFAB_ERR_ARG, "metrics_pairwise: null output");
   const PairWorkspace ws = carve_pairs(workspace, G, N, K, P);
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 16 == 0, DIFFAB_ERR_ARG,
-                 "metrics_pairwise: the workspace must be a 16-byte aligned device buffer");
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "metrics_pairwise: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 ws.bytes);
+  if (const int e = workspace_ok("metrics_pairwise", workspace, 16, workspace_bytes, ws.bytes)) return e;
   const int T = aligned ? 32 : 64;
   const int64_t tiles = (N + T - 1) / T;
   const int64_t grid = static_cast<int64_t>(G) * (tiles * (tiles + 1) / 2), pack_grid = static_cast<int64_t>(G) * ((N + 63) / 64);

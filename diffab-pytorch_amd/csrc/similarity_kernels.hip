@@ -6,7 +6,7 @@
 // comparison is made in fp32 on those values, and every accumulator is an integer - so a row's numbers depend on neither the reduction order
 // nor the rows around it, and they equal an fp32 numpy restatement exactly.  VALU + LDS only, no atomics; every value reaches memory through
 // plain C++ stores.  One launch.
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
@@ -45,16 +45,6 @@ __host__ __device__ inline int plane_stride(int K) { return K | 1; }
 
 size_t similarity_lds_bytes(int K, int P) {
   return static_cast<size_t>(1 + kWaves) * 3 * P * plane_stride(K) * sizeof(float) + static_cast<size_t>(K) * (sizeof(uint16_t) + 1);
-}
-
-// Sum over the 64 lanes of a wave: integers, so every lane ends with the same exact value.
-template <int V>
-__device__ inline void wave_sum(int (&v)[V]) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] += __shfl_xor(v[i], d, 64);
-  }
 }
 
 __device__ inline float ratio(int num, int den) { return den > 0 ? static_cast<float>(num) / static_cast<float>(den) : NAN; }
@@ -98,9 +88,9 @@ similarity_kernel(const float* __restrict__ points, const float* __restrict__ na
     for (int k0 = 0; k0 < K; k0 += 64) {
       const int k = k0 + lane;
       const bool in = k < K && gm[k] != 0 && (rm == nullptr || rm[k] != 0);
-      const unsigned long long vote = __ballot(in);
-      if (in) s_list[n + __popcll(vote & ((1ull << lane) - 1ull))] = static_cast<uint16_t>(k);
-      n += __popcll(vote);
+      const BallotRank r = ballot_rank(in, lane);
+      if (in) s_list[n + r.rank] = static_cast<uint16_t>(k);
+      n += r.count;
     }
     if (lane == 0) s_n = n;
   }

@@ -3,20 +3,19 @@
 // the entry in include/diffab_hip_analysis.h.
 //
 // Built with -ffp-contract=off (csrc/Makefile): a sphere point is fl(c + fl(R * u)) per component, the squared distance is the fp32 value
-// (dx*dx + dy*dy) + dz*dz and "covered" is a strict comparison on it, so every point count is a defined number.  The areas are fp64 from
+// (dx*dx + dy*dy) + dz*dz (dist2 of analysis_common.h, written out here) and "covered" is a strict comparison on it, so every point count is a defined number.  The areas are fp64 from
 // the integer counts and the fp32 radii, summed in a fixed order of the row and rounded once.  VALU + LDS only, no atomics at all; every
 // value reaches memory through plain C++ stores.
 #include <climits>
 #include <cmath>
 
 #include "../../include/diffab_hip_analysis.h"
-#include "common.h"
+#include "analysis_common.h"
 
 namespace diffab {
 namespace {
 
 constexpr int kMaxK = DIFFAB_METRICS_MAX_K;
-constexpr int kMaxGroup = DIFFAB_METRICS_MAX_GROUP;
 constexpr int kMaxPoints = DIFFAB_METRICS_MAX_POINTS;
 constexpr int kMaxContextAtoms = DIFFAB_METRICS_MAX_CONTEXT_ATOMS;
 constexpr int kMinSphere = DIFFAB_METRICS_SURFACE_MIN_POINTS;
@@ -496,8 +495,6 @@ surface_rows_kernel(const float* __restrict__ points, const uint8_t* __restrict_
   if (out.hotspot_buried_area) out.hotspot_buried_area[row] = static_cast<float>(sum_hot);
 }
 
-bool radius_ok(float r) { return r >= 0.f && r < INFINITY; }
-
 }  // namespace
 }  // namespace diffab
 
@@ -516,18 +513,14 @@ int diffab_metrics_surface(const float* points, const uint8_t* valid, const floa
                            size_t workspace_bytes, void* stream) {
   StreamOrder order_(stream);
   const char* who = "metrics_surface";
-  DIFFAB_REQUIRE(rows >= 0 && group_size >= 1 && K >= 1, DIFFAB_ERR_ARG, "%s: negative or empty extent (%d rows, group size %d, K = %d)", who,
-                 rows, group_size, K);
-  DIFFAB_REQUIRE(group_size <= kMaxGroup, DIFFAB_ERR_ARG, "%s: group size %d, at most %d designs per group", who, group_size, kMaxGroup);
-  DIFFAB_REQUIRE(K <= kMaxK, DIFFAB_ERR_ARG, "%s: K = %d residues per patch, at most %d", who, K, kMaxK);
-  DIFFAB_REQUIRE(rows % group_size == 0, DIFFAB_ERR_ARG, "%s: %d rows are not a multiple of group_size = %d", who, rows, group_size);
+  if (!rows_shape_ok(who, rows, group_size, K, kMaxK)) return DIFFAB_ERR_ARG;
   DIFFAB_REQUIRE(P >= 1 && P <= kMaxPoints, DIFFAB_ERR_ARG, "%s: P = %d points per residue outside [1, %d]", who, P, kMaxPoints);
   DIFFAB_REQUIRE(A >= 1 && A <= kMaxContextAtoms, DIFFAB_ERR_ARG, "%s: A = %d context atoms per residue outside [1, %d]", who, A,
                  kMaxContextAtoms);
   DIFFAB_REQUIRE(S >= kMinSphere && S <= kMaxSphere, DIFFAB_ERR_ARG, "%s: S = %d sphere points outside [%d, %d]", who, S, kMinSphere,
                  kMaxSphere);
-  DIFFAB_REQUIRE(radius_ok(probe), DIFFAB_ERR_ARG, "%s: probe must be finite and >= 0, got %g", who, static_cast<double>(probe));
-  DIFFAB_REQUIRE(radius_ok(context_radius_default), DIFFAB_ERR_ARG, "%s: context_radius_default must be finite and >= 0, got %g", who,
+  DIFFAB_REQUIRE(finite_nonnegative(probe), DIFFAB_ERR_ARG, "%s: probe must be finite and >= 0, got %g", who, static_cast<double>(probe));
+  DIFFAB_REQUIRE(finite_nonnegative(context_radius_default), DIFFAB_ERR_ARG, "%s: context_radius_default must be finite and >= 0, got %g", who,
                  static_cast<double>(context_radius_default));
   DIFFAB_REQUIRE(hotspot_mask == nullptr || antigen_mask != nullptr, DIFFAB_ERR_ARG, "%s: a hotspot_mask needs an antigen_mask", who);
   if (rows == 0) return DIFFAB_OK;
@@ -535,15 +528,13 @@ int diffab_metrics_surface(const float* points, const uint8_t* valid, const floa
                  "%s: null input", who);
   Radii radii = {};
   for (int a = 0; a < P; ++a) {
-    DIFFAB_REQUIRE(radius_ok(point_radius[a]), DIFFAB_ERR_ARG, "%s: point_radius[%d] must be finite and >= 0, got %g", who, a,
+    DIFFAB_REQUIRE(finite_nonnegative(point_radius[a]), DIFFAB_ERR_ARG, "%s: point_radius[%d] must be finite and >= 0, got %g", who, a,
                    static_cast<double>(point_radius[a]));
     radii.r[a] = point_radius[a];
   }
-  DIFFAB_REQUIRE(workspace != nullptr && reinterpret_cast<uintptr_t>(workspace) % 256 == 0, DIFFAB_ERR_ARG,
-                 "%s: the workspace must be a 256-byte aligned device buffer", who);
   const int32_t G = rows / group_size;
   const SurfaceWorkspace ws = carve_surface(workspace, G, K, A, S);
-  DIFFAB_REQUIRE(workspace_bytes >= ws.bytes, DIFFAB_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws.bytes);
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   const int blocks_per_patch = (K * A + 3) / 4;
   const int64_t antigen_grid = static_cast<int64_t>(G) * blocks_per_patch;
   DIFFAB_REQUIRE(antigen_grid <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "%s: %d patches of %d atom slots are more work-groups than one launch holds",

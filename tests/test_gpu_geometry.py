@@ -171,10 +171,10 @@ def check_backbone(c, out, ref, angles, what):
         assert worst <= 5e-7
 
 
-@pytest.mark.parametrize("K", [40, 130])
-@pytest.mark.parametrize("N", [1, 5, 70])
+@pytest.mark.parametrize("N, K", [(N, K) for K in (40, 130) for N in (1, 5, 70)] + [(3, 70), (3, 300)])
 def test_backbone_equals_the_oracle(N, K):
-    """The native, the pushed and the pulled loop: dihedrals, bond lengths and counts."""
+    """The native, the pushed and the pulled loop: dihedrals, bond lengths and counts.  K = 70 and K = 300: the chain neighbours of a patch
+    past 64 slots that is no multiple of 64, and of one past the 256 threads of the links kernel."""
     c = case(N, K, kinds=("native", "pushed", "pulled"))
     out = numpy_of(metrics.backbone(c["designs"], c["gen_d"], **c["kw"]))
     pts = design_points(c["designs"], ("N", "CA", "C"))[0]

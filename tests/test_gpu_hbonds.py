@@ -263,6 +263,8 @@ def fair(c, what):
 
 CASES = {  # kind, K, G, N, A, then keywords
     "K24 one chain": ("helix", 24, 1, 1, 4),
+    "K70 ragged": ("helix", 70, 2, 3, 4, dict(ragged=True)),  # past 64 slots and no multiple of it; K300: past the 256 threads
+    "K300": ("helix", 300, 2, 3, 4),
     "K40 three chains, ragged": ("strands", 40, 2, 5, 15, dict(ragged=True)),
     "K96 three patches": ("helix", 96, 3, 1, 32),
     "K96 cloud": ("cloud", 96, 1, 5, 4),
