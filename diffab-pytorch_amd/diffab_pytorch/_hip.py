@@ -347,6 +347,16 @@ ENERGY_SYMBOLS = {
     "diffab_metrics_pair_energy": (C.c_int, [_fp] * 10 + [_i32] * 6 + [_fp] * 8 + [_fp, _sz, _fp]),
 }
 
+# every symbol include/diffab_hip_novelty.h declares (the seven export lists above are pinned by their tests): same library, an eighth
+# table, for the entries that compare a design with sequences outside its patch
+NOVELTY_SYMBOLS = {
+    # (q_tokens, q_len, R, LQ, lib_tokens, lib_len, M, LM, skip (nullable), radius, distance, index, n_within, identity, matrix (each
+    #  output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_edit_nearest": (C.c_int, [_fp, _fp, _i32, _i32, _fp, _fp, _i32, _i32, _fp, _i32] + [_fp] * 5 + [_fp, _sz, _fp]),
+    # (tokens, mask, residue_mask (nullable), segment_idx (nullable), segment, rows, group_size, K, L, out_tokens, out_len, stream)
+    "diffab_metrics_pack_sequences": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp] * 2 + [_fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -361,7 +371,7 @@ def load_library() -> C.CDLL:
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items())
                                    + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items()) + list(DEVELOP_SYMBOLS.items())
-                                   + list(ENERGY_SYMBOLS.items())):
+                                   + list(ENERGY_SYMBOLS.items()) + list(NOVELTY_SYMBOLS.items())):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

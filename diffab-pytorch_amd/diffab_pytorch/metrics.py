@@ -25,6 +25,9 @@
                     native the share of improved designs - the DiffAb paper's IMP under that potential; ``PairPotential`` holds a
                     table and its bin edges, ``contact_potential`` builds the placeholder default (DESIGN section 4.25,
                     ``csrc/energy_kernels.hip``);
+``novelty``         per design: the nearest sequence of a library of known loops by edit distance - is this loop new, is it unique
+                    among its siblings - with ``SequenceSet``, ``sequence_set`` / ``sequence_strings`` for the library and
+                    ``design_sequences`` for the designs (DESIGN section 4.26, ``csrc/novelty_kernels.hip``);
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
 ``hbonds``          per design: Kabsch-Sander backbone hydrogen bonds with the peptide-plane O and the amide H they need, the bonds to
@@ -42,11 +45,13 @@ the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse
 ``include/diffab_hip_hbonds.h`` and of ``diffab_metrics_cluster`` and ``diffab_metrics_pareto`` in ``include/diffab_hip_cluster.h``
 and of ``diffab_metrics_contact_bits`` and ``diffab_metrics_pairwise_bits`` in ``include/diffab_hip_interface.h``
 and of ``diffab_metrics_patches`` and ``diffab_metrics_motifs`` in ``include/diffab_hip_develop.h``
-and of ``diffab_metrics_pair_energy`` in ``include/diffab_hip_energy.h``;
+and of ``diffab_metrics_pair_energy`` in ``include/diffab_hip_energy.h``
+and of ``diffab_metrics_edit_nearest`` and ``diffab_metrics_pack_sequences`` in ``include/diffab_hip_novelty.h``;
 every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters, DESIGN
 section 4.15), ``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip``,
-``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip``, ``csrc/develop_kernels.hip`` and ``csrc/energy_kernels.hip``, and there is
-no torch fallback (``unpack_contact_map`` is plain torch: it reads bits, it computes nothing; ``motif_masks`` parses text on the host).
+``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip``, ``csrc/develop_kernels.hip``, ``csrc/energy_kernels.hip`` and ``csrc/novelty_kernels.hip``, and there is
+no torch fallback (``unpack_contact_map`` is plain torch: it reads bits, it computes nothing; ``motif_masks`` and ``sequence_set`` parse
+text on the host).
 """
 from __future__ import annotations
 
@@ -89,6 +94,10 @@ DEVELOP_MOTIF_WORDS = 4  # DIFFAB_DEVELOP_MOTIF_WORDS: a motif is at most four r
 ENERGY_MAX_K = 512  # DIFFAB_ENERGY_MAX_K: residues per patch of interface_energy
 ENERGY_MAX_CLASSES = 32  # DIFFAB_ENERGY_MAX_CLASSES: token classes of a pair potential
 ENERGY_MAX_BINS = 8  # DIFFAB_ENERGY_MAX_BINS: distance bins of a pair potential
+NOVELTY_MAX_QUERY = 64  # DIFFAB_NOVELTY_MAX_QUERY: tokens of a query of novelty, one bit of a 64-bit word each
+NOVELTY_MAX_LIBRARY = 256  # DIFFAB_NOVELTY_MAX_LIBRARY: tokens of a library sequence of novelty, and of any SequenceSet
+NOVELTY_CHUNK = 2048  # DIFFAB_NOVELTY_CHUNK: library entries per partial result in novelty's workspace
+NOVELTY_PAD = 255  # what stands behind a sequence's last token
 SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256# DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
@@ -1154,6 +1163,196 @@ def interface_energy(designs: Dict[str, torch.Tensor], generation_mask: torch.Te
         out["delta"] = out["e_antigen"] - per_row
         out["improved"] = out["e_antigen"] < per_row
         out["imp"] = out["improved"].view(G, group_size).float().mean(1)
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ novelty: the nearest known sequence by edit distance
+def edit_nearest_workspace_bytes(R: int, M: int, LM: int) -> int:
+    """DIFFAB_METRICS_EDIT_NEAREST_WORKSPACE_BYTES of include/diffab_hip_novelty.h."""
+    return M * ((LM + 3) // 4 * 4 + 8) + (M + NOVELTY_CHUNK - 1) // NOVELTY_CHUNK * R * 12 + 1024
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class SequenceSet:
+    """M sequences of their own lengths: ``tokens`` (M,L) uint8, row m holding ``lengths[m]`` tokens in ``io.AA1`` order (20 = X) and
+    255 behind them, and ``lengths`` (M,) int32; L <= 256, on any device.  Tokens of 32 or more match nothing, themselves included.
+    What ``sequence_set`` builds from strings and ``design_sequences`` from designs, and what ``novelty`` compares.  ValueError otherwise."""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+
+    def __post_init__(self):
+        who = "metrics.SequenceSet()"
+        t, n = self.tokens, self.lengths
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2:
+            raise ValueError(f"{who}: tokens must be a uint8 tensor (M, L)")
+        if not isinstance(n, torch.Tensor) or n.dtype != torch.int32 or tuple(n.shape) != (int(t.shape[0]),):
+            raise ValueError(f"{who}: lengths must be an int32 tensor ({int(t.shape[0])},), one length per row of tokens")
+        if not 1 <= int(t.shape[1]) <= NOVELTY_MAX_LIBRARY:
+            raise ValueError(f"{who}: tokens is {tuple(t.shape)}: L outside [1, {NOVELTY_MAX_LIBRARY}] tokens per sequence")
+        if t.device != n.device:
+            raise ValueError(f"{who}: tokens is on {t.device} and lengths on {n.device}")
+
+    def __len__(self) -> int:
+        return int(self.tokens.shape[0])
+
+
+def sequence_set(strings) -> SequenceSet:
+    """A ``SequenceSet`` on the CPU from one-letter strings in ``io.AA1`` order (X is token 20); as wide as the longest, at least 1.
+    A letter outside ``io.AA1`` raises ValueError naming the string and the letter, a string longer than 256 too; no string gives M = 0."""
+    who = "metrics.sequence_set()"
+    if isinstance(strings, (str, bytes)) or not isinstance(strings, Sequence) or not all(isinstance(s, str) for s in strings):
+        raise ValueError(f"{who}: strings must be a list of str")
+    L = max([len(s) for s in strings] + [1])
+    rows = []
+    for i, s in enumerate(strings):
+        if len(s) > NOVELTY_MAX_LIBRARY:
+            raise ValueError(f"{who}: string {i} has {len(s)} letters, at most {NOVELTY_MAX_LIBRARY}")
+        for c in s:
+            if c not in AA1:
+                raise ValueError(f"{who}: string {i} ({s!r}) has the letter {c!r}, which is not one of {AA1!r}")
+        rows.append([AA1.index(c) for c in s] + [NOVELTY_PAD] * (L - len(s)))
+    tokens = torch.tensor(rows, dtype=torch.uint8).view(len(strings), L)
+    return SequenceSet(tokens, torch.tensor([len(s) for s in strings], dtype=torch.int32))
+
+
+def sequence_strings(sequence_set: SequenceSet) -> list:
+    """The inverse of ``sequence_set``: one string per sequence, a token of 21 or more as ``?``.  Lengths are read as clamped to the width."""
+    if not isinstance(sequence_set, SequenceSet):
+        raise ValueError("metrics.sequence_strings(): sequence_set must be a metrics.SequenceSet")
+    L = int(sequence_set.tokens.shape[1])
+    tokens, lengths = sequence_set.tokens.cpu().tolist(), sequence_set.lengths.cpu().tolist()
+    return ["".join(AA1[t] if t < len(AA1) else "?" for t in row[:min(max(n, 0), L)]) for row, n in zip(tokens, lengths)]
+
+
+def design_sequences(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, group_size: int = 1,
+                     residue_mask: Optional[torch.Tensor] = None, segment_idx: Optional[torch.Tensor] = None, segment: Optional[int] = None,
+                     max_length: int = NOVELTY_MAX_QUERY) -> SequenceSet:
+    """The designed residues of every design row as a sequence: a ``SequenceSet`` of ``rows`` sequences, ``max_length`` wide, on the
+    device of ``designs['seq_idx']``.  A residue is counted when it is inside ``generation_mask`` and ``residue_mask`` (both (G,K) bool,
+    one row per patch) and, with ``segment_idx`` (G,K) integer and ``segment``, when ``segment_idx == segment`` - one CDR of several;
+    the two are given together or not at all.  The tokens of the counted residues follow in slot order.  The largest count per patch
+    is taken from the masks on the host before any device work (one small copy): a patch with more counted residues than
+    ``max_length`` (1 .. 256; the default 64 is the widest query of ``novelty``) raises ValueError naming the patch.  One C-ABI call
+    (``diffab_metrics_pack_sequences``, one launch)."""
+    who = "metrics.design_sequences()"
+    if not isinstance(designs, dict) or not isinstance(designs.get("seq_idx"), torch.Tensor):
+        raise ValueError(f"{who}: designs must be a dict with seq_idx")
+    seq = designs["seq_idx"]
+    if seq.dim() != 2 or seq.is_floating_point() or seq.dtype == torch.bool:
+        raise ValueError(f"{who}: designs['seq_idx'] must be an integer tensor (rows, K), got {tuple(seq.shape)} {seq.dtype}")
+    rows, K = int(seq.shape[0]), int(seq.shape[1])
+    if not _is_int(group_size) or group_size < 1:
+        raise ValueError(f"{who}: group_size must be an int >= 1, got {group_size!r}")
+    if group_size > MAX_GROUP:
+        raise ValueError(f"{who}: group_size = {group_size}, at most {MAX_GROUP} designs per patch")
+    if rows % group_size != 0:
+        raise ValueError(f"{who}: {rows} design rows are not a multiple of group_size = {group_size}")
+    if K < 1 or K > MAX_K:
+        raise ValueError(f"{who}: K = {K} residues per patch outside [1, {MAX_K}]")
+    G = rows // group_size
+    _check_patch_mask(who, "generation_mask", generation_mask, G, K)
+    if residue_mask is not None:
+        _check_patch_mask(who, "residue_mask", residue_mask, G, K)
+    if (segment_idx is None) != (segment is None):
+        raise ValueError(f"{who}: segment_idx and segment go together, {'segment_idx' if segment_idx is None else 'segment'} is missing")
+    if segment_idx is not None:
+        if not isinstance(segment_idx, torch.Tensor) or segment_idx.is_floating_point() or segment_idx.dtype == torch.bool \
+                or tuple(segment_idx.shape) != (G, K):
+            raise ValueError(f"{who}: segment_idx must be an integer tensor {(G, K)} (one row per patch)")
+        if not _is_int(segment) or not -2 ** 31 <= segment < 2 ** 31:
+            raise ValueError(f"{who}: segment must be an int, got {segment!r}")
+    if not _is_int(max_length) or not 1 <= max_length <= NOVELTY_MAX_LIBRARY:
+        raise ValueError(f"{who}: max_length must be an int in [1, {NOVELTY_MAX_LIBRARY}], got {max_length!r}")
+    counted = generation_mask.detach().cpu()
+    if residue_mask is not None:
+        counted = counted & residue_mask.detach().cpu()
+    if segment_idx is not None:
+        counted = counted & (segment_idx.detach().cpu() == segment)
+    n = counted.sum(1)
+    if G and int(n.max()) > max_length:
+        g = int((n > max_length).nonzero()[0])
+        raise ValueError(f"{who}: patch {g} has {int(n[g])} counted residues, more than max_length = {max_length}")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), seq.device
+    tokens = _hip.dev_i64(seq).to(torch.int32).contiguous()
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    seg = None if segment_idx is None else _hip.dev_i64(segment_idx).to(torch.int32).contiguous()
+    out = torch.empty(rows, max_length, dtype=torch.uint8, device=dev)
+    length = torch.empty(rows, dtype=torch.int32, device=dev)
+    _hip.check(lib.diffab_metrics_pack_sequences(_hip.ptr(tokens), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(seg), 0 if segment is None else segment,
+                                                 rows, group_size, K, max_length, _hip.ptr(out), _hip.ptr(length), _hip.stream_ptr()),
+               "diffab_metrics_pack_sequences")
+    return SequenceSet(out.to(out_dev), length.to(out_dev))
+
+
+def novelty(queries: SequenceSet, library: SequenceSet, *, radius: Optional[int] = None, exclude=None,
+            matrix: bool = False) -> Dict[str, torch.Tensor]:
+    """Which designs are new: for every sequence of ``queries`` (R of them, at most 64 wide) the nearest sequence of ``library`` (M of
+    them, at most 256 wide) by Levenshtein distance - the least number of single-residue insertions, deletions and substitutions,
+    each at cost 1, so a known loop one residue longer or a motif in another register is found, which position-by-position identity
+    (``evaluate``, ``pairwise``'s ``seq_identity``) cannot.  Two residues match iff their tokens are equal and below 32; lengths
+    outside their row are read as clamped.  ``exclude`` is an integer tensor (R,), the library entry each query is not compared with
+    (an index outside [0, M) excludes nothing), or ``"self"`` for ``arange(R)``, which needs R == M: the set against itself.
+
+    Returns, on the device of ``queries.tokens``, per query (R,): ``distance`` int32, the least distance; ``index`` int64, the lowest
+    library entry that attains it; ``identity`` fp32 = ``1 - distance / max(length, nearest_length)`` (1 for two empty sequences);
+    ``length`` and ``nearest_length`` int32, the two lengths behind it; with ``radius`` (an int) ``n_within`` int32, the library
+    entries, the excluded one aside, with a distance of at most ``radius``; with ``matrix=True`` ``matrix`` (R,M) int32, every distance
+    (the excluded entry's too; R * M < 2^31).  With nothing to compare (M = 0, or the only entry excluded) ``distance``, ``index`` and
+    ``nearest_length`` are -1, ``identity`` is NaN and ``n_within`` is 0.
+
+    The usual numbers.  NOVELTY of a design: ``distance > 0`` against the known set (the training set, a repertoire, disclosed
+    binders); what distance makes a design "novel" is the caller's call.  UNIQUENESS among R designs:
+    ``novelty(q, q, exclude="self", radius=0)["n_within"] == 0``.  FAMILIES across register shifts: the ``matrix`` of a patch's N
+    designs against themselves, as ``.float().view(1, N, N)``, is a distance matrix for ``cluster``, which groups what ``seq_identity``
+    keeps apart.
+
+    One C-ABI call (``diffab_metrics_edit_nearest``, three launches, ``include/diffab_hip_novelty.h``): Myers' bit-vector algorithm,
+    all integers, every output the same bits on every run.  ValueError naming the argument before any device work."""
+    who = "metrics.novelty()"
+    for name, s in (("queries", queries), ("library", library)):
+        if not isinstance(s, SequenceSet):
+            raise ValueError(f"{who}: {name} must be a metrics.SequenceSet, got {type(s).__name__}")
+    R, LQ, M, LM = len(queries), int(queries.tokens.shape[1]), len(library), int(library.tokens.shape[1])
+    if LQ > NOVELTY_MAX_QUERY:
+        raise ValueError(f"{who}: queries is {LQ} tokens wide, at most {NOVELTY_MAX_QUERY} (the library may be {NOVELTY_MAX_LIBRARY} wide)")
+    if radius is not None and (not _is_int(radius) or not -2 ** 31 <= radius < 2 ** 31):
+        raise ValueError(f"{who}: radius must be an int or None, got {radius!r}")
+    if not isinstance(matrix, bool):
+        raise ValueError(f"{who}: matrix must be a bool, got {matrix!r}")
+    if matrix and R * M >= 2 ** 31:
+        raise ValueError(f"{who}: matrix of R * M = {R} * {M} elements, fewer than 2^31 are needed")
+    if isinstance(exclude, str):
+        if exclude != "self":
+            raise ValueError(f"{who}: exclude must be an integer tensor ({R},), 'self' or None, got {exclude!r}")
+        if R != M:
+            raise ValueError(f"{who}: exclude='self' needs as many queries as library entries, got R = {R} and M = {M}")
+        exclude = torch.arange(R, dtype=torch.int32)
+    elif exclude is not None:
+        if not isinstance(exclude, torch.Tensor) or exclude.is_floating_point() or exclude.dtype == torch.bool or tuple(exclude.shape) != (R,):
+            raise ValueError(f"{who}: exclude must be an integer tensor ({R},), 'self' or None")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), queries.tokens.device
+    on = lambda t: t.detach().to(dev).contiguous()
+    qt, ql, lt, ll = on(queries.tokens), on(queries.lengths), on(library.tokens), on(library.lengths)
+    skip = None if exclude is None else on(exclude).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    out = {"distance": i32(R), "index": i32(R), "n_within": i32(R) if radius is not None else None,
+           "identity": torch.empty(R, dtype=torch.float32, device=dev), "matrix": i32(R, M) if matrix else None}
+    nbytes = edit_nearest_workspace_bytes(R, M, LM)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_edit_nearest(_hip.ptr(qt), _hip.ptr(ql), R, LQ, _hip.ptr(lt), _hip.ptr(ll), M, LM, _hip.ptr(skip),
+                                               -1 if radius is None else radius, *[_hip.ptr(t) for t in out.values()], _hip.ptr(ws), nbytes,
+                                               _hip.stream_ptr()), "diffab_metrics_edit_nearest")
+    out = {k: v for k, v in out.items() if v is not None}
+    out["index"] = out["index"].long()
+    found = out["index"] >= 0
+    out["length"] = ql.clamp(0, LQ)
+    nearest = ll.clamp(0, LM)[out["index"].clamp(min=0)] if M else torch.zeros(R, dtype=torch.int32, device=dev)
+    out["nearest_length"] = torch.where(found, nearest, torch.full_like(nearest, -1))
     return {k: v.to(out_dev) for k, v in out.items()}
 
 
