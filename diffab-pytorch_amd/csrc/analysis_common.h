@@ -1,5 +1,5 @@
 // analysis_common.h - what the analysis translation units (the metrics, geometry, ensemble, similarity, hbond, cluster, pareto,
-// interface, develop, energy and novelty kernels: DESIGN sections 4.13 - 4.26) share: wave reductions and ranks, the defined squared distance,
+// interface, develop, energy, novelty and conformation kernels: DESIGN sections 4.13 - 4.27) share: wave reductions and ranks, the defined squared distance,
 // the site record of a residue, and the host checks every such entry makes on its extents and its workspace.
 // Only what at least two of those files use lives here, and only what leaves the device code the compiler makes of them as it was.
 //

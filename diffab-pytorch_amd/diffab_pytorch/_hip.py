@@ -357,6 +357,17 @@ NOVELTY_SYMBOLS = {
     "diffab_metrics_pack_sequences": (C.c_int, [_fp] * 4 + [_i32] * 5 + [_fp] * 2 + [_fp]),
 }
 
+# every symbol include/diffab_hip_conformation.h declares (the eight export lists above are pinned by their tests): same library, a ninth
+# table, for the entries that compare the shape of a design with loops outside its patch
+CONFORMATION_SYMBOLS = {
+    # (q_feat, q_len, R, LQ, lib_feat, lib_len, M, LM, A, skip (nullable), radius, min_terms, distance, index, n_terms, n_within, matrix
+    #  (each output nullable), workspace, workspace_bytes, stream)
+    "diffab_metrics_dihedral_nearest": (C.c_int, [_fp, _fp, _i32, _i32, _fp, _fp, _i32, _i32, _i32, _fp, C.c_float, _i32] + [_fp] * 5
+                                        + [_fp, _sz, _fp]),
+    # (phi, psi, omega, mask, residue_mask (nullable), segment_idx (nullable), segment, rows, group_size, K, L, out_angles, out_len, stream)
+    "diffab_metrics_pack_dihedrals": (C.c_int, [_fp] * 6 + [_i32] * 5 + [_fp] * 2 + [_fp]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -371,7 +382,7 @@ def load_library() -> C.CDLL:
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(ANALYSIS_SYMBOLS.items()) + list(HBOND_SYMBOLS.items())
                                    + list(CLUSTER_SYMBOLS.items()) + list(INTERFACE_SYMBOLS.items()) + list(DEVELOP_SYMBOLS.items())
-                                   + list(ENERGY_SYMBOLS.items()) + list(NOVELTY_SYMBOLS.items())):
+                                   + list(ENERGY_SYMBOLS.items()) + list(NOVELTY_SYMBOLS.items()) + list(CONFORMATION_SYMBOLS.items())):
             fn = getattr(lib, name)  # AttributeError if a header and the library drift apart
             fn.restype, fn.argtypes = res, args
         _lib = lib

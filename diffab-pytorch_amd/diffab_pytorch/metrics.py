@@ -28,6 +28,10 @@
 ``novelty``         per design: the nearest sequence of a library of known loops by edit distance - is this loop new, is it unique
                     among its siblings - with ``SequenceSet``, ``sequence_set`` / ``sequence_strings`` for the library and
                     ``design_sequences`` for the designs (DESIGN section 4.26, ``csrc/novelty_kernels.hip``);
+``conformation``    per design: the nearest loop of a library of known loops of its length by backbone-dihedral distance - is this
+                    shape one a loop is known to take, which canonical class is it in - with ``DihedralSet``, ``dihedral_set`` for
+                    the library, ``design_dihedrals`` for the designs and ``dihedral_angle`` to read the number (DESIGN section 4.27,
+                    ``csrc/conformation_kernels.hip``);
 ``surface``         per design: solvent-accessible surface of the generated residues and of the antigen, and the area the two bury on
                     each other - the buried surface area of the interface (DESIGN section 4.19, ``csrc/surface_kernels.hip``);
 ``hbonds``          per design: Kabsch-Sander backbone hydrogen bonds with the peptide-plane O and the amide H they need, the bonds to
@@ -46,12 +50,14 @@ the comments of ``diffab_metrics_vs_native`` / ``_pairwise`` / ``_select_diverse
 and of ``diffab_metrics_contact_bits`` and ``diffab_metrics_pairwise_bits`` in ``include/diffab_hip_interface.h``
 and of ``diffab_metrics_patches`` and ``diffab_metrics_motifs`` in ``include/diffab_hip_develop.h``
 and of ``diffab_metrics_pair_energy`` in ``include/diffab_hip_energy.h``
-and of ``diffab_metrics_edit_nearest`` and ``diffab_metrics_pack_sequences`` in ``include/diffab_hip_novelty.h``;
+and of ``diffab_metrics_edit_nearest`` and ``diffab_metrics_pack_sequences`` in ``include/diffab_hip_novelty.h``
+and of ``diffab_metrics_dihedral_nearest`` and ``diffab_metrics_pack_dihedrals`` in ``include/diffab_hip_conformation.h``;
 every number is computed by the HIP kernels of ``csrc/metrics_kernels.hip``, ``csrc/geometry_kernels.hip`` (the filters, DESIGN
 section 4.15), ``csrc/ensemble_kernels.hip``, ``csrc/similarity_kernels.hip``, ``csrc/surface_kernels.hip``, ``csrc/hbond_kernels.hip``,
-``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip``, ``csrc/develop_kernels.hip``, ``csrc/energy_kernels.hip`` and ``csrc/novelty_kernels.hip``, and there is
-no torch fallback (``unpack_contact_map`` is plain torch: it reads bits, it computes nothing; ``motif_masks`` and ``sequence_set`` parse
-text on the host).
+``csrc/cluster_kernels.hip``, ``csrc/pareto_kernels.hip``, ``csrc/interface_kernels.hip``, ``csrc/develop_kernels.hip``, ``csrc/energy_kernels.hip``, ``csrc/novelty_kernels.hip`` and ``csrc/conformation_kernels.hip``, and there is
+no torch fallback (``unpack_contact_map`` is plain torch: it reads bits, it computes nothing; ``motif_masks``, ``sequence_set`` and
+``dihedral_set`` parse their input on the host; ``conformation`` takes the cosines and sines of the angles in torch, on the device, in
+float64 rounded once, and ``dihedral_angle`` is one torch expression for reading a distance).
 """
 from __future__ import annotations
 
@@ -98,6 +104,9 @@ NOVELTY_MAX_QUERY = 64  # DIFFAB_NOVELTY_MAX_QUERY: tokens of a query of novelty
 NOVELTY_MAX_LIBRARY = 256  # DIFFAB_NOVELTY_MAX_LIBRARY: tokens of a library sequence of novelty, and of any SequenceSet
 NOVELTY_CHUNK = 2048  # DIFFAB_NOVELTY_CHUNK: library entries per partial result in novelty's workspace
 NOVELTY_PAD = 255  # what stands behind a sequence's last token
+CONFORMATION_MAX_LENGTH = 64  # DIFFAB_CONFORMATION_MAX_LENGTH: residues of a loop of conformation, one bit of a 64-bit word each
+CONFORMATION_CHUNK = 2048  # DIFFAB_CONFORMATION_CHUNK: sorted library places per partial result in conformation's workspace
+DIHEDRALS = ("phi", "psi", "omega")  # the angle kinds of a DihedralSet, in the order of its last axis
 SURFACE_MIN_POINTS, SURFACE_MAX_POINTS = 8, 256# DIFFAB_METRICS_SURFACE_MIN_POINTS / _MAX_POINTS: sphere points per atom
 # surface(): united-atom radii of the frame atoms in Angstrom (hydrogens folded into the heavy atom) - this project's own choice
 ATOM_RADIUS = {"N": 1.65, "CA": 1.87, "C": 1.76, "O": 1.40, "CB": 1.87}
@@ -1354,6 +1363,222 @@ def novelty(queries: SequenceSet, library: SequenceSet, *, radius: Optional[int]
     nearest = ll.clamp(0, LM)[out["index"].clamp(min=0)] if M else torch.zeros(R, dtype=torch.int32, device=dev)
     out["nearest_length"] = torch.where(found, nearest, torch.full_like(nearest, -1))
     return {k: v.to(out_dev) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------ conformation: the nearest known loop by dihedral distance
+def dihedral_nearest_workspace_bytes(R: int, M: int, LQ: int, LM: int, A: int) -> int:
+    """DIFFAB_METRICS_DIHEDRAL_NEAREST_WORKSPACE_BYTES of include/diffab_hip_conformation.h."""
+    chunks = lambda n: (n + CONFORMATION_CHUNK - 1) // CONFORMATION_CHUNK
+    side = lambda n, L: (n + 15) // 16 * ((2 * A * L + 3) // 4) * 256 + n * (8 * A + 12) + chunks(n) * 260
+    return side(R, LQ) + side(M, LM) + chunks(M) * R * 12 + 8192
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class DihedralSet:
+    """M loops of their own lengths: ``angles`` (M,L,3) fp32 in radians, phi / psi / omega of residue i of loop m at ``[m, i]``, NaN for an
+    angle that does not exist (the phi of a chain's first residue) and behind the loop's length, and ``lengths`` (M,) int32; 1 <= L <= 64,
+    both on one device.  What ``dihedral_set`` builds from tables and ``design_dihedrals`` from frames, and what ``conformation``
+    compares.  ValueError otherwise."""
+    angles: torch.Tensor
+    lengths: torch.Tensor
+
+    def __post_init__(self):
+        who = "metrics.DihedralSet()"
+        t, n = self.angles, self.lengths
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or int(t.shape[2]) != len(DIHEDRALS):
+            raise ValueError(f"{who}: angles must be a float32 tensor (M, L, 3)")
+        if not isinstance(n, torch.Tensor) or n.dtype != torch.int32 or tuple(n.shape) != (int(t.shape[0]),):
+            raise ValueError(f"{who}: lengths must be an int32 tensor ({int(t.shape[0])},), one length per row of angles")
+        if not 1 <= int(t.shape[1]) <= CONFORMATION_MAX_LENGTH:
+            raise ValueError(f"{who}: angles is {tuple(t.shape)}: L outside [1, {CONFORMATION_MAX_LENGTH}] residues per loop")
+        if t.device != n.device:
+            raise ValueError(f"{who}: angles is on {t.device} and lengths on {n.device}")
+
+    def __len__(self) -> int:
+        return int(self.angles.shape[0])
+
+
+def dihedral_set(loops, degrees: bool = False) -> DihedralSet:
+    """A ``DihedralSet`` on the CPU from a list of loops, each an (n_i, 3) array or nested list of phi, psi, omega per residue, in radians
+    or with ``degrees=True`` in degrees; ``None`` or NaN stands for an angle that does not exist.  This is how a table of canonical-class
+    medians or a file of known loops comes in.  As wide as the longest loop, at least 1; a loop longer than 64 residues or not (n, 3)
+    raises ValueError naming it; no loop gives M = 0."""
+    who = "metrics.dihedral_set()"
+    if not isinstance(degrees, bool):
+        raise ValueError(f"{who}: degrees must be a bool, got {degrees!r}")
+    if isinstance(loops, (str, bytes, torch.Tensor)) or not isinstance(loops, Sequence):
+        raise ValueError(f"{who}: loops must be a list of (n, 3) arrays or nested lists")
+    tables = []
+    for i, loop in enumerate(loops):
+        try:
+            if isinstance(loop, torch.Tensor):
+                t = loop.detach().cpu().to(torch.float64)
+            else:
+                rows = loop.tolist() if hasattr(loop, "tolist") else loop
+                t = torch.tensor([[math.nan if v is None else float(v) for v in row] for row in rows], dtype=torch.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: loop {i} is not an (n, 3) table of numbers") from None
+        if t.numel() == 0:
+            t = t.reshape(0, len(DIHEDRALS))
+        if t.dim() != 2 or int(t.shape[1]) != len(DIHEDRALS):
+            raise ValueError(f"{who}: loop {i} is {tuple(t.shape)}, expected (n, 3): phi, psi, omega per residue")
+        if int(t.shape[0]) > CONFORMATION_MAX_LENGTH:
+            raise ValueError(f"{who}: loop {i} has {int(t.shape[0])} residues, at most {CONFORMATION_MAX_LENGTH}")
+        tables.append(torch.deg2rad(t) if degrees else t)
+    L = max([int(t.shape[0]) for t in tables] + [1])
+    angles = torch.full((len(tables), L, len(DIHEDRALS)), math.nan, dtype=torch.float32)
+    for m, t in enumerate(tables):
+        angles[m, :int(t.shape[0])] = t.float()
+    return DihedralSet(angles, torch.tensor([int(t.shape[0]) for t in tables], dtype=torch.int32))
+
+
+def design_dihedrals(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, group_size: int = 1, chain_idx=None,
+                     residue_idx=None, residue_mask: Optional[torch.Tensor] = None, segment_idx: Optional[torch.Tensor] = None,
+                     segment: Optional[int] = None, max_length: int = CONFORMATION_MAX_LENGTH) -> DihedralSet:
+    """The backbone dihedrals of the designed residues of every design row as a loop: a ``DihedralSet`` of ``rows`` loops, ``max_length``
+    wide, on the device of ``designs['seq_idx']``.  The angles are those of ``backbone`` (same ``chain_idx``, ``residue_idx``,
+    ``residue_mask``: NaN where the neighbour an angle needs does not exist).  A residue is counted by the rule of ``design_sequences``:
+    inside ``generation_mask`` and ``residue_mask`` (both (G,K) bool, one row per patch) and, with ``segment_idx`` (G,K) integer and
+    ``segment``, where ``segment_idx == segment`` - one CDR of several; the two are given together or not at all.  The angles of the
+    counted residues follow in slot order.  The largest count per patch is taken from the masks on the host before any device work: a
+    patch with more counted residues than ``max_length`` (1 .. 64) raises ValueError naming the patch.  It serves natives as well as
+    designs: a library of known loops is ``design_dihedrals`` of their own frames, so one builder makes both sides of ``conformation``.
+    Two C-ABI calls (``diffab_metrics_backbone``, then ``diffab_metrics_pack_dihedrals``, one launch)."""
+    who = "metrics.design_dihedrals()"
+    rows, G, K = _check_common(who, designs, generation_mask, residue_mask, group_size, "backbone")
+    residue_tables(who, chain_idx, residue_idx, None, G, K)
+    if (segment_idx is None) != (segment is None):
+        raise ValueError(f"{who}: segment_idx and segment go together, {'segment_idx' if segment_idx is None else 'segment'} is missing")
+    if segment_idx is not None:
+        if not isinstance(segment_idx, torch.Tensor) or segment_idx.is_floating_point() or segment_idx.dtype == torch.bool \
+                or tuple(segment_idx.shape) != (G, K):
+            raise ValueError(f"{who}: segment_idx must be an integer tensor {(G, K)} (one row per patch)")
+        if not _is_int(segment) or not -2 ** 31 <= segment < 2 ** 31:
+            raise ValueError(f"{who}: segment must be an int, got {segment!r}")
+    if not _is_int(max_length) or not 1 <= max_length <= CONFORMATION_MAX_LENGTH:
+        raise ValueError(f"{who}: max_length must be an int in [1, {CONFORMATION_MAX_LENGTH}], got {max_length!r}")
+    counted = generation_mask.detach().cpu()
+    if residue_mask is not None:
+        counted = counted & residue_mask.detach().cpu()
+    if segment_idx is not None:
+        counted = counted & (segment_idx.detach().cpu() == segment)
+    n = counted.sum(1)
+    if G and int(n.max()) > max_length:
+        g = int((n > max_length).nonzero()[0])
+        raise ValueError(f"{who}: patch {g} has {int(n[g])} counted residues, more than max_length = {max_length}")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), designs["seq_idx"].device
+    bb = backbone(designs, generation_mask, chain_idx=chain_idx, residue_idx=residue_idx, residue_mask=residue_mask, group_size=group_size)
+    phi, psi, omega = (_hip.dev_f32(bb[k]) for k in DIHEDRALS)
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    seg = None if segment_idx is None else _hip.dev_i64(segment_idx).to(torch.int32).contiguous()
+    out = torch.empty(rows, max_length, len(DIHEDRALS), dtype=torch.float32, device=dev)
+    length = torch.empty(rows, dtype=torch.int32, device=dev)
+    _hip.check(lib.diffab_metrics_pack_dihedrals(_hip.ptr(phi), _hip.ptr(psi), _hip.ptr(omega), _hip.ptr(gm), _hip.ptr(rm), _hip.ptr(seg),
+                                                 0 if segment is None else segment, rows, group_size, K, max_length, _hip.ptr(out),
+                                                 _hip.ptr(length), _hip.stream_ptr()), "diffab_metrics_pack_dihedrals")
+    return DihedralSet(out.to(out_dev), length.to(out_dev))
+
+
+def dihedral_features(angles: torch.Tensor, which: Sequence[int]) -> torch.Tensor:
+    """(M,L,A,2) fp32: (cos, sin) of the angle kinds ``which`` of ``angles`` (M,L,3), taken in float64 and rounded once; NaN, NaN for an
+    angle that is not finite.  The operand of ``diffab_metrics_dihedral_nearest``, which takes no cosine itself."""
+    a = angles[..., list(which)].double()
+    return torch.stack([torch.cos(a).float(), torch.sin(a).float()], dim=-1).contiguous()
+
+
+def conformation(queries: DihedralSet, library: DihedralSet, *, angles: Sequence[str] = ("phi", "psi"), radius: Optional[float] = None,
+                 exclude=None, matrix: bool = False, labels: Optional[torch.Tensor] = None, min_terms: int = 1) -> Dict[str, torch.Tensor]:
+    """Which designs have a known shape: for every loop of ``queries`` (R of them) the nearest loop of ``library`` (M of them) AMONG THOSE
+    OF ITS OWN LENGTH by backbone-dihedral distance, d = the mean of ``2 (1 - cos(difference))`` over the compared angles - no
+    superposition, no frame, blind to where the loop sits.  ``angles`` is a non-empty subset of ``DIHEDRALS`` without repeats, taken in
+    ``DIHEDRALS`` order.  An angle that is NaN on either side is left out of that pair; a pair is comparable when the (clamped) lengths are
+    equal and at least ``min_terms`` (>= 1) angles are compared; d is in [0, 4], and North, Lehmann and Dunbrack's D over phi and psi
+    is ``2 * d``, so published cut-offs apply after halving.  ``exclude`` is an integer tensor (R,), the library entry each query is not
+    compared with (an index outside [0, M) excludes nothing), or ``"self"`` for ``arange(R)``, which needs R == M.  ``labels`` is an
+    integer tensor (M,), the canonical class of each library entry.
+
+    Returns, on the device of ``queries.angles``, per query (R,): ``distance`` fp32, the least d (+inf with nothing comparable);
+    ``index`` int64, the lowest library entry that attains it (-1); ``n_terms`` int32, the angles compared in that pair (0);
+    ``length`` and ``nearest_length`` int32 (-1 where none); with ``radius`` (a float) ``n_within`` int32, the library entries, the
+    excluded one aside, with ``d <= radius`` (0 for a negative or NaN radius); with ``matrix=True`` ``matrix`` (R,M) fp32, every d (the
+    excluded entry's too; +inf for a pair that is not comparable; R * M < 2^31); with ``labels`` ``label`` int64 = ``labels[index]``, -1
+    where nothing was comparable.
+
+    The usual numbers.  The CANONICAL CLASS of every design: ``label`` where ``distance <= cutoff``.  STRUCTURAL NOVELTY:
+    ``distance > cutoff`` against every known loop of that length.  FAMILIES BY SHAPE: the ``matrix`` of a patch's N designs against
+    themselves, as ``.view(1, N, N)``, is a distance matrix for ``cluster`` (+inf keeps loops of other lengths apart).
+    ``dihedral_angle(distance)`` reads a distance as degrees.
+
+    One C-ABI call (``diffab_metrics_dihedral_nearest``, five launches, ``include/diffab_hip_conformation.h``); the product of the features
+    runs on the fp32 matrix cores.  ValueError naming the argument before any device work."""
+    who = "metrics.conformation()"
+    for name, s in (("queries", queries), ("library", library)):
+        if not isinstance(s, DihedralSet):
+            raise ValueError(f"{who}: {name} must be a metrics.DihedralSet, got {type(s).__name__}")
+    R, LQ, M, LM = len(queries), int(queries.angles.shape[1]), len(library), int(library.angles.shape[1])
+    if isinstance(angles, str) or not isinstance(angles, Sequence) or len(angles) == 0 or any(a not in DIHEDRALS for a in angles) \
+            or len(set(angles)) != len(angles):
+        raise ValueError(f"{who}: angles must be a non-empty subset of {DIHEDRALS} without repeats, got {angles!r}")
+    which = [i for i, a in enumerate(DIHEDRALS) if a in angles]
+    A = len(which)
+    if radius is not None and (isinstance(radius, bool) or not isinstance(radius, (int, float))):
+        raise ValueError(f"{who}: radius must be a float or None, got {radius!r}")
+    if not isinstance(matrix, bool):
+        raise ValueError(f"{who}: matrix must be a bool, got {matrix!r}")
+    if matrix and R * M >= 2 ** 31:
+        raise ValueError(f"{who}: matrix of R * M = {R} * {M} elements, fewer than 2^31 are needed")
+    if not _is_int(min_terms) or not 1 <= min_terms < 2 ** 31:
+        raise ValueError(f"{who}: min_terms must be an int >= 1, got {min_terms!r}")
+    if isinstance(exclude, str):
+        if exclude != "self":
+            raise ValueError(f"{who}: exclude must be an integer tensor ({R},), 'self' or None, got {exclude!r}")
+        if R != M:
+            raise ValueError(f"{who}: exclude='self' needs as many queries as library entries, got R = {R} and M = {M}")
+        exclude = torch.arange(R, dtype=torch.int32)
+    elif exclude is not None:
+        if not isinstance(exclude, torch.Tensor) or exclude.is_floating_point() or exclude.dtype == torch.bool or tuple(exclude.shape) != (R,):
+            raise ValueError(f"{who}: exclude must be an integer tensor ({R},), 'self' or None")
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.is_floating_point() or labels.dtype == torch.bool or tuple(labels.shape) != (M,):
+            raise ValueError(f"{who}: labels must be an integer tensor ({M},), one class per library entry, or None")
+
+    lib = _hip.lib()
+    dev, out_dev = _hip.device(), queries.angles.device
+    on = lambda t: t.detach().to(dev).contiguous()
+    qf, lf = dihedral_features(on(queries.angles), which), dihedral_features(on(library.angles), which)
+    ql, ll = on(queries.lengths), on(library.lengths)
+    skip = None if exclude is None else on(exclude).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = {"distance": f32(R), "index": i32(R), "n_terms": i32(R), "n_within": i32(R) if radius is not None else None,
+           "matrix": f32(R, M) if matrix else None}
+    nbytes = dihedral_nearest_workspace_bytes(R, M, LQ, LM, A)
+    ws = _hip.workspace(nbytes)
+    _hip.check(lib.diffab_metrics_dihedral_nearest(_hip.ptr(qf), _hip.ptr(ql), R, LQ, _hip.ptr(lf), _hip.ptr(ll), M, LM, A, _hip.ptr(skip),
+                                                   -1.0 if radius is None else float(radius), min_terms, *[_hip.ptr(t) for t in out.values()],
+                                                   _hip.ptr(ws), nbytes, _hip.stream_ptr()), "diffab_metrics_dihedral_nearest")
+    out = {k: v for k, v in out.items() if v is not None}
+    out["index"] = out["index"].long()
+    found = out["index"] >= 0
+    at = out["index"].clamp(min=0)
+    out["length"] = ql.clamp(0, LQ)
+    nearest = ll.clamp(0, LM)[at] if M else torch.zeros(R, dtype=torch.int32, device=dev)
+    out["nearest_length"] = torch.where(found, nearest, torch.full_like(nearest, -1))
+    if labels is not None:
+        label = on(labels).long()[at] if M else torch.zeros(R, dtype=torch.int64, device=dev)
+        out["label"] = torch.where(found, label, torch.full_like(label, -1))
+    return {k: v.to(out_dev) for k, v in out.items()}
+
+
+def dihedral_angle(distance: torch.Tensor) -> torch.Tensor:
+    """``degrees(acos(1 - d / 2))`` elementwise: the angle difference that, on every compared angle, would give the distance d of
+    ``conformation`` - 0 for 0, 90 for 2, 180 for 4, NaN beyond.  For reading the number; plain torch."""
+    if not isinstance(distance, torch.Tensor) or not distance.is_floating_point():
+        raise ValueError("metrics.dihedral_angle(): distance must be a float tensor")
+    return torch.rad2deg(torch.acos(1.0 - distance / 2.0))
 
 
 # ------------------------------------------------------------------ accessible and buried surface (DESIGN section 4.19)
