@@ -447,6 +447,8 @@ int launch_fold_beta_table(const diffab_dims* d, const diffab_denoiser_weights* 
   return DIFFAB_OK;
 }
 
+// Tested against the float64 oracle at K = 64, 128, 192, 256 (tests/test_gpu_parity.py, test_gpu_patch_lengths.py) and at K = 320, 384, 512,
+// 640 and 1024 (tests/test_gpu_long_patches.py: up to 8 key chunks, chosen per-chunk maxima); the other multiples of 64 take the same forms.
 bool fast_path_supported(const diffab_dims* d) {
   return d->D == 128 && d->C == AC && d->H == AH && d->DS == ADS && d->PQ == AP && d->PV == AP && d->K % 64 == 0 && d->K >= 64 &&
          d->K <= 1024;  // any multiple of 64: keys are processed in chunks of 128 (or 64) with an online softmax

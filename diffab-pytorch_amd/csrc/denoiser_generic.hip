@@ -179,20 +179,26 @@ __global__ __launch_bounds__(256) void ipa_attn_generic_kernel(const float* __re
   __syncthreads();
   float* frow = feat + row_i * F;
   const int n_os = H * DS, n_oe = H * C, n_og = H * PV * 3;
+  // The sums over the keys run in fp64.  One fp32 accumulator rounds the running sum at every key whose weight is not negligible:
+  // over K = 1024 keys that is several times the error of a blocked fp32 sum, and for the value points it is an error relative to
+  // the GLOBAL coordinates that (p - t) below turns into one relative to the local ones.  Two layers on top of each other at K = 1024
+  // then miss the element-wise bar (tests/test_gpu_long_patches.py: res_emb 3.4e-4 element-wise, 5.4e-5 with these sums in fp64).
   for (int o = threadIdx.x; o < n_os + n_oe + n_og; o += blockDim.x) {
-    float acc = 0.f;
+    double acc = 0.0;
     if (o < n_os) {
       const int h = o / DS;
-      for (int j = 0; j < K; ++j) acc += attn[h * K + j] * proj[(static_cast<int64_t>(b) * K + j) * NP + off_vs + o];
-      frow[o] = acc;
+      for (int j = 0; j < K; ++j)
+        acc += static_cast<double>(attn[h * K + j]) * static_cast<double>(proj[(static_cast<int64_t>(b) * K + j) * NP + off_vs + o]);
+      frow[o] = static_cast<float>(acc);
     } else if (o < n_os + n_oe) {
       const int oo = o - n_os, h = oo / C, c = oo % C;
-      for (int j = 0; j < K; ++j) acc += attn[h * K + j] * erow[static_cast<int64_t>(j) * C + c];
-      frow[o] = acc;
+      for (int j = 0; j < K; ++j) acc += static_cast<double>(attn[h * K + j]) * static_cast<double>(erow[static_cast<int64_t>(j) * C + c]);
+      frow[o] = static_cast<float>(acc);
     } else {
       const int oo = o - n_os - n_oe, h = oo / (PV * 3);
-      for (int j = 0; j < K; ++j) acc += attn[h * K + j] * proj[(static_cast<int64_t>(b) * K + j) * NP + off_gv + oo];
-      og[oo] = acc;
+      for (int j = 0; j < K; ++j)
+        acc += static_cast<double>(attn[h * K + j]) * static_cast<double>(proj[(static_cast<int64_t>(b) * K + j) * NP + off_gv + oo]);
+      og[oo] = static_cast<float>(acc);
     }
   }
   __syncthreads();

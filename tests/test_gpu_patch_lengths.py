@@ -11,6 +11,8 @@ residue_mask.  The HIP code picks different kernels as K changes; at the benchma
   K = 196  generic forward; attention backward ipa_attn_bwd_rows_mr_kernel -> ipa_attn_bwd_keys_mr_kernel<4> (K % 4 == 0)
   K = 256  MFMA forward, two 128-key chunks; attention backward ipa_attn_bwd_rows_mr_kernel -> ipa_attn_bwd_keys_mr_kernel<4> (its LDS
            is exactly 64 KiB; keys_mfma would need 68 KiB)
+  K > 256  tests/test_gpu_long_patches.py continues this table (K = 320, 384, 512, 640, 1024: more and rescaled key chunks in the
+           forward, the one-key and one-row attention backward kernels, the sampler past the patch-resident module launch)
 
 Every case is B = 2 with patch 0 padded after ~4/5 of its residues (`padded`) and patch 1 whole.  The reference denoiser ignores the
 masks (diffab_pytorch.py:566-567), so padded residues are keys like any other: their values and gradients are compared too.  Oracle:
