@@ -39,6 +39,13 @@
  *     not be captured into a hipGraph from a stream other than the last one used.  NOTE for callers: the hardware behaviour applies to
  *     YOUR kernels too - a caller's own VALU kernel holding that packed form can miscompute beside this library's f16 / bf16 MFMA
  *     kernels on another stream (tools/isa_hazard_lint.py checks any gfx950 object file or shared library).
+ *     What is tested (tests/test_gpu_stream_contract.py, every export of every header in the table of
+ *     tests/test_stream_contract_host.py): behind other work on a side stream, every launch, memset and copy of an entry is on `stream`
+ *     or on an internal stream ordered after and before it by events; the call returns without waiting for the stream; and an array
+ *     in host memory (ctx_of_row, slot_of_step, steps, beta_jump, alpha_jump, ctx_of_design, t_list, bin_edges, motifs, point_radius,
+ *     complex_of_row) may be overwritten or freed the moment the call has returned.  Outside that: the queries, setters and host-only
+ *     diagnostics enqueue nothing; diffab_kernel_timer_read waits for its events by design; a call with DIFFAB_FLAG_GRAPH_SAMPLER
+ *     drains its private stream, so it is held to its values only; diffab_debug_start_classes (diffab_hip_debug.h) is not driven.
  *   - Workspaces and tapes: what a workspace or a tape holds ON ENTRY is ignored - it may be zeros, NaN bit patterns or the leftover of a
  *     call at another shape, mask or flag selection, and the result is the same to the bit (for the gradients below: to their stated
  *     accuracy).  What a workspace holds ON EXIT is unspecified.  Nothing outside [p, p + bytes) of the stated *_workspace_bytes /

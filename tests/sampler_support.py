@@ -8,6 +8,7 @@ A new sampler feature's test file starts from here and keeps per file only the f
 """
 import os
 import re
+import time
 import types
 
 import numpy as np
@@ -763,6 +764,7 @@ class GuardedABI:
             raise ValueError(f"fill must be one of {GUARD_FILLS}, not {fill!r}")
         self.C, self.entries, self.fill, self.positions, self.when = ctypes, set(entries), fill, positions or {}, when or {}
         self.real, self.argtypes = lib, argtypes
+        self.headers, self.host_operands = HEADERS, ()  # (the gated-stream harness widens both)
         self.counts, self.tensors, self.known, self.scratch, self.saved, self.patterns, self.last = {}, {}, {}, {}, None, {}, {}
         for t in tensors_of(*known):
             self._see(t, self.known)  # (a tensor _hip.ptr sees inside the context goes first: the operand itself, not a buffer it is cut from)
@@ -780,7 +782,7 @@ class GuardedABI:
             self.real = _hip.lib()
         if self.argtypes is None:
             self.argtypes = {n: a for n, (_, a) in list(_hip.SYMBOLS.items()) + list(_hip.ANALYSIS_SYMBOLS.items())}
-        self.params = {n: [p[0] for p in ps] for n, ps in header_prototypes()[1].items()}
+        self.params = {n: [p[0] for p in ps] for n, ps in header_prototypes(self.headers)[1].items()}
         self.saved = (_hip.lib, _hip.ptr, _hip.workspace)
         real_ptr, real_ws = _hip.ptr, _hip.workspace
 
@@ -820,7 +822,21 @@ class GuardedABI:
             self._guard(self.patterns[key], dtype)
         return self.patterns[key]
 
-    def _shadow(self, entry, operand, address, made):
+    def _new_shadow(self, t, address, owner, operand):
+        """A fresh buffer whose interior holds t's bytes at `address` modulo 256, between two guards.  `owner` is the struct the pointer
+        was a field of (None for a direct argument)."""
+        n = t.numel() * t.element_size()
+        buf = torch.empty(n + 2 * GUARD_BYTES + 256, dtype=torch.uint8, device=t.device)
+        lo = GUARD_BYTES + (address - buf.data_ptr() - GUARD_BYTES) % 256
+        self._guard(buf[lo - GUARD_BYTES:lo], t.dtype)
+        self._guard(buf[lo + n:lo + n + GUARD_BYTES], t.dtype)
+        buf[lo:lo + n].copy_(bytes_of(t))
+        return dict(buf=buf, lo=lo, n=n, t=t, names=[], writable=False)
+
+    def _writable(self, entry, operand):
+        return writable(entry, operand)
+
+    def _shadow(self, entry, operand, address, made, owner=None):
         """The shadow pointer of `address`, or None for a pointer that passes as it is."""
         if address in self.scratch:
             return None
@@ -831,16 +847,10 @@ class GuardedABI:
             raise UnresolvedPointer(f"{entry}: operand {operand} = {address:#x} is not the data pointer of a contiguous tensor the harness "
                                     "has seen (register it with known=, or name it in UNGUARDED with the reason)")
         if address not in made:
-            n = t.numel() * t.element_size()
-            buf = torch.empty(n + 2 * GUARD_BYTES + 256, dtype=torch.uint8, device=t.device)
-            lo = GUARD_BYTES + (address - buf.data_ptr() - GUARD_BYTES) % 256
-            self._guard(buf[lo - GUARD_BYTES:lo], t.dtype)
-            self._guard(buf[lo + n:lo + n + GUARD_BYTES], t.dtype)
-            buf[lo:lo + n].copy_(bytes_of(t))
-            made[address] = dict(buf=buf, lo=lo, n=n, t=t, names=[], writable=False)
+            made[address] = self._new_shadow(t, address, owner, operand)
         s = made[address]
         s["names"].append(operand)
-        s["writable"] |= writable(entry, operand)
+        s["writable"] |= self._writable(entry, operand)
         return s["buf"].data_ptr() + s["lo"]
 
     def _struct_pointers(self, struct, path, NL, visit):
@@ -859,6 +869,9 @@ class GuardedABI:
                 else:
                     self._struct_pointers(v.contents, p, NL, visit)
             # (everything else is a number or a HOST array: slot_of_step, steps, ctx_of_row)
+
+    def _run(self, entry, fn, args, made):
+        return fn(*args)
 
     def _check(self, entry, made):
         devices = {s["buf"].device for s in made.values()}
@@ -916,14 +929,14 @@ class GuardedABI:
             NL = next((int(v.NL) for v in dims if isinstance(v, _hip.Dims)), 1)
 
             def visit(struct, field, v, path):
-                new = self._shadow(name, path, v, made)
+                new = self._shadow(name, path, v, made, struct)
                 if new is not None:
                     restore.append((struct, field, v))
                     setattr(struct, field, new)
 
             try:
                 for i, (a, at, pname) in enumerate(zip(args, types_, names)):
-                    if (only is not None and i not in only) or pname == "stream":
+                    if (only is not None and i not in only) or pname == "stream" or (name, pname) in self.host_operands:
                         out.append(a)
                     elif at is C.c_void_p:
                         v = a.value if isinstance(a, C.c_void_p) else a
@@ -939,7 +952,7 @@ class GuardedABI:
                     else:
                         out.append(a)
                 self.last = made  # (for the host tests' stand-ins: the shadows of the call in flight)
-                rc = fn(*out)
+                rc = self._run(name, fn, out, made)
             finally:
                 for struct, field, v in restore:
                     setattr(struct, field, v)
@@ -949,6 +962,194 @@ class GuardedABI:
 
         return call
 
+
+# ====================================================================== the stream contract (include/diffab_hip.h, "Streams")
+LATER_HEADERS = ("diffab_hip_hbonds.h", "diffab_hip_cluster.h", "diffab_hip_interface.h", "diffab_hip_develop.h", "diffab_hip_energy.h",
+                 "diffab_hip_novelty.h", "diffab_hip_conformation.h")
+ALL_HEADERS = HEADERS + LATER_HEADERS  # the nine headers of the product ABI
+DIAGNOSTIC_HEADERS = ("diffab_hip_debug.h",)  # declared for the launch-form tests alone: no ctypes table in _hip
+# (entry, operand by the prototype's name or struct path): HOST arrays, read during the call only.  They pass the harness as they are.
+HOST_ARRAYS = (("diffab_sample_loop_ex", "opt.ctx_of_row"), ("diffab_sample_loop_ex", "opt.record.slot_of_step"),
+               ("diffab_sample_loop_ex", "opt.steps.steps"), ("diffab_sample_loop_ex", "opt.steps.beta_jump"),
+               ("diffab_sample_loop_ex", "opt.steps.alpha_jump"), ("diffab_score_designs", "ctx_of_design"),
+               ("diffab_score_designs", "t_list"), ("diffab_metrics_pair_energy", "bin_edges"), ("diffab_metrics_motifs", "motifs"),
+               ("diffab_metrics_surface", "point_radius"), ("diffab_patch_gather", "complex_of_row"))
+# HOST memory the headers name that is no array operand of a device call: (entry or struct, name) -> why it has no overwrite case
+HOST_NOT_ARRAYS = {("diffab_denoiser_weights", "layers"): "a host table of pointer structs: its device pointers are copied into launch "
+                                                          "arguments, and every rerun row that takes `w` passes it rebuilt per call",
+                   ("diffab_debug_dense_forms", "out5"): "host output of a host-only query: nothing is enqueued",
+                   ("diffab_debug_start_classes", "plan"): "on_device = 0 runs on the host alone; diagnostic header"}
+# Float operands that keep their true values in the decoy: tables a kernel searches or indexes by
+TRUE_VALUE_OPERANDS = ("cdf", "sigmas", "pdf")
+# Calls that may hold the host: entry -> (predicate of {parameter: argument}, why).  They are held to the value check only.
+GRAPH_SAMPLER_DRAINS = "DIFFAB_FLAG_GRAPH_SAMPLER drains the private replay stream before the call returns (include/diffab_hip.h)"
+MAY_WAIT = {"diffab_sample_loop": (lambda a: bool(int(a["flags"]) & _hip.FLAG_GRAPH_SAMPLER), GRAPH_SAMPLER_DRAINS),
+            "diffab_sample_loop_ex": (lambda a: bool(int(a["flags"]) & _hip.FLAG_GRAPH_SAMPLER), GRAPH_SAMPLER_DRAINS)}
+# Gate length (profiles/stream_contract.md): the longest host time of one entry call at the shapes of tests/test_gpu_stream_contract.py
+# was measured ungated; the floor is well above it, and an entry whose own calls have taken longer gets ten times its longest so far.
+GATE_FLOOR_MS = 40.0
+GATE_MULTIPLE = 10.0
+GATE_RETRY = 4.0
+
+
+class EntryWaited(AssertionError):
+    pass
+
+
+def all_argtypes():
+    return {n: a for name in dir(_hip) if name.endswith("SYMBOLS") for n, (_, a) in getattr(_hip, name).items()}
+
+
+def all_writes():
+    """WRITES, and for the later headers what their C types leave writable (they have no gradient tables)."""
+    out = dict(WRITES)
+    out.update({n: " ".join(ops) for n, ops in typed_writes(LATER_HEADERS).items()})
+    return out
+
+
+_GATED = {}
+
+
+def hip_runtime():
+    """The HIP runtime torch has loaded, through ctypes (dlopen of a loaded library hands back the same library)."""
+    import ctypes
+
+    with open("/proc/self/maps") as f:
+        paths = sorted({line.split()[-1] for line in f if "libamdhip64" in line})
+    assert paths, "torch has not loaded libamdhip64"
+    return ctypes.CDLL(paths[0])
+
+
+def gated_stream():
+    """(side stream, sleep cycles per millisecond): one stream for every harness of the process, checked once to be non-blocking (a
+    blocking stream synchronises with the legacy default stream: every stray launch on it would look ordered), and the gate kernel's
+    length calibrated once with events."""
+    import ctypes
+
+    if not _GATED:
+        s = torch.cuda.Stream()
+        flags = ctypes.c_uint(0)
+        rc = hip_runtime().hipStreamGetFlags(ctypes.c_void_p(s.cuda_stream), ctypes.byref(flags))
+        assert rc == 0 and flags.value & 1, ("the side stream must be hipStreamNonBlocking", rc, flags.value)
+        cycles, best = 20_000_000, None
+        with torch.cuda.stream(s):
+            for _ in range(3):  # (the first run pays the kernel's load)
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(s)
+                torch.cuda._sleep(cycles)
+                b.record(s)
+                b.synchronize()
+                best = a.elapsed_time(b) if best is None else min(best, a.elapsed_time(b))
+        assert best > 0.5, ("the gate kernel did not run for a measurable time", best)
+        _GATED.update(stream=s, cycles_per_ms=cycles / best, calibration=(cycles, best))
+    return _GATED["stream"], _GATED["cycles_per_ms"]
+
+
+class GatedStreamABI(GuardedABI):
+    """Everything between __enter__ and __exit__ reaches the C ABI on a side stream that is busy: the harness of the stream contract
+    (include/diffab_hip.h, "Streams") - every launch and copy of an entry on `stream` or ordered by events after and before it, no host
+    wait, HOST arrays dead on return.
+
+    Stands in for the library like GuardedABI and shares its pointer resolution (`known`, `positions`, `when`, `counts`, `lib`,
+    `argtypes`; all nine headers).  A call of a listed entry: every operand gets a shadow at the original's address modulo 256
+    (workspaces, tapes and scratch pass as they are).  Before anything else a float32 shadow holds a DECOY, the caller's values times
+    0.5; integer, mask, schedule and IGSO3 shadows hold the true values (a decoy index or CDF could send a stray kernel out of bounds).
+    After one synchronisation the side stream waits for the caller's current stream and gets, in order: the gate (bounded device work,
+    torch.cuda._sleep), the event gate_done, a copy of every caller tensor into its shadow (outputs too), the entry with its `stream`
+    argument replaced, a copy of the writable shadows back, the event done - for which the caller's current stream then waits, with no
+    host synchronisation.
+
+    A kernel or copy that the entry puts on any other stream without an event path from `stream` runs during the gate: it reads
+    decoys, or what it writes is overwritten by the copy-in, and the caller's own comparison fails.  A host wait inside the entry
+    outlasts the gate: returned_early = not gate_done.query(), taken directly after the entry returns, is False.  Such a call is
+    repeated once (its copy-back had not been enqueued) under a gate GATE_RETRY times as long; if it still has not returned early
+    EntryWaited names the entry - unless MAY_WAIT lists the call.  calls holds (entry, returned_early, gate ms, host ms, attempts,
+    may wait) of every gated call.  on_return ({entry: f({parameter: argument})}) runs directly after returned_early is taken: the
+    HOST-array cases overwrite the array there.  gate=False runs everything but the gate (the host times of profiles/stream_contract.md).
+    Does not mix with an outer stream capture."""
+
+    def __init__(self, entries, known=(), positions=None, when=None, lib=None, argtypes=None, floor_ms=GATE_FLOOR_MS, multiple=GATE_MULTIPLE,
+                 may_wait=MAY_WAIT, on_return=None, gate=True):
+        super().__init__(entries, "nan0", known=known, positions=positions, when=when, lib=lib, argtypes=argtypes)
+        self.headers, self.host_operands = ALL_HEADERS, set(HOST_ARRAYS)
+        self.floor_ms, self.multiple, self.may_wait, self.on_return, self.gate = floor_ms, multiple, may_wait, on_return or {}, gate
+        self.calls, self.host_ms, self.held, self.writes = [], {}, [], all_writes()
+
+    def __enter__(self):
+        if self.argtypes is None:
+            self.argtypes = all_argtypes()
+        self.stream, self.cycles_per_ms = gated_stream()
+        return super().__enter__()
+
+    def __exit__(self, *exc):
+        self.stream.synchronize()  # the shadows stay referenced until everything that uses them has run
+        torch.cuda.current_stream().synchronize()
+        self.held.clear()
+        return super().__exit__(*exc)
+
+    def _writable(self, entry, operand):
+        ops = self.writes[entry].split()
+        return operand in ops or any(o.endswith(".*") and operand.startswith(o[:-1]) for o in ops)
+
+    def _new_shadow(self, t, address, owner, operand):
+        n = t.numel() * t.element_size()
+        buf = torch.empty(n + 512, dtype=torch.uint8, device=t.device)
+        lo = (address - buf.data_ptr()) % 256
+        inner = buf[lo:lo + n]
+        inner.copy_(bytes_of(t))
+        true_values = isinstance(owner, (_hip.Sched, _hip.Igso3)) or operand.split(".")[-1] in TRUE_VALUE_OPERANDS
+        if t.dtype == torch.float32 and not true_values:
+            inner.view(torch.float32).mul_(0.5)  # the decoy: finite and valid wherever the true value is
+        self.held.append(buf)
+        return dict(buf=buf, lo=lo, n=n, t=t, names=[], writable=False)
+
+    def _run(self, entry, fn, args, made):
+        names = self.params[entry]
+        at = names.index("stream")
+        named = dict(zip(names, args))
+        args = list(args)
+        args[at] = self.C.c_void_p(self.stream.cuda_stream)
+        may_wait = entry in self.may_wait and bool(self.may_wait[entry][0](named))
+        cur, s = torch.cuda.current_stream(), self.stream
+        attempts = 0
+        for scale in (1.0, GATE_RETRY):
+            attempts += 1
+            cur.synchronize()  # allocation and decoy fill are complete: the one synchronisation, of the two streams involved alone
+            s.synchronize()  # (a repeated call: the first attempt has drained)
+            gate_ms = scale * max(self.floor_ms, self.multiple * self.host_ms.get(entry, 0.0)) if self.gate else 0.0
+            s.wait_stream(cur)  # the inputs were produced on the caller's stream
+            gate_done = torch.cuda.Event()
+            with torch.cuda.stream(s):
+                if self.gate:
+                    torch.cuda._sleep(int(gate_ms * self.cycles_per_ms))
+                gate_done.record(s)
+                for sh in made.values():
+                    sh["buf"][sh["lo"]:sh["lo"] + sh["n"]].copy_(bytes_of(sh["t"]))
+            t0 = time.perf_counter()
+            rc = fn(*args)
+            returned_early = not gate_done.query()
+            host_ms = 1e3 * (time.perf_counter() - t0)
+            if entry in self.on_return:
+                self.on_return[entry](named)
+            if returned_early or not self.gate:
+                self.host_ms[entry] = max(self.host_ms.get(entry, 0.0), host_ms)
+            if returned_early or may_wait or not self.gate or rc != 0:
+                break
+        self.calls.append((entry, returned_early, gate_ms, host_ms, attempts, may_wait))
+        with torch.cuda.stream(s):
+            for sh in made.values():
+                if sh["writable"]:
+                    bytes_of(sh["t"]).copy_(sh["buf"][sh["lo"]:sh["lo"] + sh["n"]])
+        done = torch.cuda.Event()
+        done.record(s)
+        cur.wait_event(done)
+        if self.gate and not returned_early and not may_wait and rc == 0:
+            raise EntryWaited(f"{entry} held the host until its stream had drained: it returned after a gate of {gate_ms:.0f} ms "
+                              f"had ended, twice (host time of the call {host_ms:.1f} ms)")
+        return rc
+
+    def _check(self, entry, made):
+        pass  # (values are the caller's own comparison; extents are GuardedABI's)
 
 
 # ====================================================================== host side: argument checks before the library
