@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_develop.h"
-#include "analysis_common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -48,14 +48,7 @@ patches_pack_kernel(const float* __restrict__ context_sites, const uint8_t* __re
     const bool antigen = antigen_mask != nullptr && antigen_mask[base + k] != 0;
     const bool present = in && !antigen;
     const bool gen = present && generation_mask[base + k] != 0;
-    SiteRecord r;
-    r.x = r.y = r.z = present ? 0.f : NAN;
-    r.flags = (present ? kSitePresent : 0u) | (gen ? kSiteGenerated : 0u);
-    if (present && !gen) {
-      const float* p = context_sites + (base + k) * 3;
-      r.x = p[0], r.y = p[1], r.z = p[2];
-    }
-    ws.site[base + k] = r;
+    ws.site[base + k] = pack_site(context_sites + (base + k) * 3, present, gen, false);
   }
 }
 
@@ -94,11 +87,7 @@ patches_row_kernel(PatchesArgs a, PatchesWorkspace ws) {
   const unsigned long long below = (1ull << lane) - 1ull;
 
   for (int k = lane; k < K; k += 64) {
-    SiteRecord r = ws.site[gbase + k];
-    if ((r.flags & kSiteGenerated) != 0u) {
-      const float* p = a.sites + (rbase + k) * 3;
-      r.x = p[0], r.y = p[1], r.z = p[2];
-    }
+    const SiteRecord r = overlay_site(ws.site[gbase + k], a.sites + (rbase + k) * 3);
     const int tok = a.tokens[rbase + k];
     const bool known = tok >= 0 && tok < a.V;
     const float h = a.hydrophobicity[known ? tok : 0], q = a.charge[known ? tok : 0];
@@ -199,7 +188,7 @@ patches_row_kernel(PatchesArgs a, PatchesWorkspace ws) {
 
 // ------------------------------------------------------------------ 2. sequence motifs
 struct MotifsWorkspace {
-  int32_t* succ;  // (G, K): the chain successor of every slot, -1 without one
+  int32_t* succ;  // (G, K): the chain successor of every slot, -1 without one (chain_links_kernel of analysis_prep.h, no pred)
   size_t bytes;
 };
 
@@ -214,32 +203,6 @@ MotifsWorkspace carve_motifs(void* base, int64_t G, int64_t K) {
 struct MotifTable {
   int32_t word[kMaxMotifs * kMotifWords];
 };
-
-// One wave per patch: the lowest slot inside residue_mask on the same chain with the next residue_idx.
-__global__ void __launch_bounds__(64)
-motifs_succ_kernel(const uint8_t* __restrict__ residue_mask, const int32_t* __restrict__ chain, const int32_t* __restrict__ residue_idx, int K,
-                   MotifsWorkspace ws) {
-  __shared__ int32_t s_chain[kMaxK];
-  __shared__ int32_t s_ridx[kMaxK];
-  __shared__ uint8_t s_in[kMaxK];
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * K;
-  for (int k = threadIdx.x; k < K; k += 64) {
-    s_chain[k] = chain[base + k];
-    s_ridx[k] = residue_idx[base + k];
-    s_in[k] = residue_mask == nullptr || residue_mask[base + k] != 0;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < K; i += 64) {
-    int found = -1;
-    if (s_in[i]) {
-      const int ci = s_chain[i];
-      const int64_t next = static_cast<int64_t>(s_ridx[i]) + 1;
-      for (int j = 0; j < K; ++j)
-        if (found < 0 && s_in[j] && s_chain[j] == ci && static_cast<int64_t>(s_ridx[j]) == next) found = j;
-    }
-    ws.succ[base + i] = found;
-  }
-}
 
 // One wave per design row; lane l owns slots l, l + 64, ...  A slot outside residue_mask has no class bit, so it matches nothing.
 __global__ void __launch_bounds__(64)
@@ -371,7 +334,8 @@ int diffab_metrics_motifs(const int32_t* tokens, const uint8_t* generation_mask,
   if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
   if (motif_count == nullptr && n_motifs == nullptr && motif_start == nullptr) return DIFFAB_OK;  // nothing was asked for
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(motifs_succ_kernel, dim3(G), dim3(64), 0, st, residue_mask, chain, residue_idx, K, ws);
+  hipLaunchKernelGGL((chain_links_kernel<64, kMaxK>), dim3(G), dim3(64), 0, st, chain, residue_idx, residue_mask, K, ws.succ,
+                     static_cast<int32_t*>(nullptr));
   hipLaunchKernelGGL(motifs_row_kernel, dim3(rows), dim3(64), 0, st, tokens, generation_mask, residue_mask, group_size, K, M, table, ws,
                      motif_count, n_motifs, motif_start);
   DIFFAB_LAUNCH_CHECK();

@@ -8,7 +8,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_energy.h"
-#include "analysis_common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -53,14 +53,7 @@ energy_pack_kernel(const float* __restrict__ context_sites, const uint8_t* __res
     const bool present = residue_mask == nullptr || residue_mask[base + k] != 0;
     const bool gen = present && generation_mask[base + k] != 0;
     const bool antigen = present && !gen && antigen_mask != nullptr && antigen_mask[base + k] != 0;
-    SiteRecord r;
-    r.x = r.y = r.z = present ? 0.f : NAN;
-    r.flags = (present ? kSitePresent : 0u) | (gen ? kSiteGenerated : 0u) | (antigen ? kSiteAntigen : 0u);
-    if (present && !gen) {
-      const float* p = context_sites + (base + k) * 3;
-      r.x = p[0], r.y = p[1], r.z = p[2];
-    }
-    ws.site[base + k] = r;
+    ws.site[base + k] = pack_site(context_sites + (base + k) * 3, present, gen, antigen);
     ws.chain[base + k] = chain != nullptr ? chain[base + k] : 0;
     ws.ridx[base + k] = residue_idx != nullptr ? residue_idx[base + k] : 0;
   }
@@ -125,11 +118,7 @@ energy_row_kernel(EnergyArgs a, EnergyWorkspace ws) {
     SiteRecord r;
     r.x = r.y = r.z = NAN, r.flags = 0u;
     if (mine) {
-      r = ws.site[gbase + i];
-      if ((r.flags & kSiteGenerated) != 0u) {
-        const float* p = a.sites + (rbase + i) * 3;
-        r.x = p[0], r.y = p[1], r.z = p[2];
-      }
+      r = overlay_site(ws.site[gbase + i], a.sites + (rbase + i) * 3);
       const int tok = a.tokens[rbase + i];
       if (tok >= 0 && tok < V) r.flags |= kKnown | (static_cast<uint32_t>(tok) << kTokenShift);
       s_site[i] = r;

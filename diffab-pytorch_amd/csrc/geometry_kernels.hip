@@ -7,7 +7,7 @@
 // VALU + LDS only; the only atomics are integer adds on LDS; every value reaches memory through plain C++ stores.
 #include <climits>
 
-#include "analysis_common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -21,52 +21,6 @@ constexpr double kPeptideBond = 1.329;
 constexpr double kPi = 3.14159265358979323846;
 static_assert(kChunkResidues == 64, "a wave finds the extent of a chunk: one lane per residue");
 static_assert(kChunkAtoms >= kMaxContextAtoms, "a chunk holds at least one whole residue");
-
-// ------------------------------------------------------------------ chain neighbours of a patch
-// succ[k] / pred[k]: the lowest slot j of the patch with the same chain, residue_idx[j] = residue_idx[k] + 1 / - 1 and both inside
-// residue_mask; -1 without one.  One work-group per patch, the keys in LDS.
-__global__ void __launch_bounds__(256)
-geometry_links_kernel(const int32_t* __restrict__ chain, const int32_t* __restrict__ residue_idx, const uint8_t* __restrict__ residue_mask,
-                      int K, int32_t* __restrict__ succ, int32_t* __restrict__ pred) {
-  __shared__ int2 s_key[kMaxK];
-  __shared__ uint8_t s_in[kMaxK];
-  const int tid = threadIdx.x;
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * K;
-  for (int k = tid; k < K; k += 256) {
-    s_key[k] = make_int2(chain[base + k], residue_idx[base + k]);
-    s_in[k] = residue_mask == nullptr || residue_mask[base + k] != 0;
-  }
-  __syncthreads();
-  for (int k = tid; k < K; k += 256) {
-    int s = -1, p = -1;
-    if (s_in[k]) {
-      const int2 me = s_key[k];
-      for (int j = 0; j < K; ++j) {
-        if (!s_in[j] || s_key[j].x != me.x) continue;
-        const int64_t gap = static_cast<int64_t>(s_key[j].y) - me.y;
-        if (gap == 1 && s < 0) s = j;
-        if (gap == -1 && p < 0) p = j;
-      }
-    }
-    succ[base + k] = s;
-    pred[base + k] = p;
-  }
-}
-
-struct LinkWorkspace {
-  int32_t* succ;  // (G, K)
-  int32_t* pred;  // (G, K)
-  size_t bytes;
-};
-
-LinkWorkspace carve_links(void* base, int64_t G, int64_t K) {
-  Carver c(base);
-  LinkWorkspace w;
-  w.succ = c.take<int32_t>(static_cast<size_t>(G * K));
-  w.pred = c.take<int32_t>(static_cast<size_t>(G * K));
-  w.bytes = c.bytes();
-  return w;
-}
 
 // ------------------------------------------------------------------ 1. backbone dihedrals and peptide bonds
 __device__ inline void load3(const float* p, double (&v)[3]) {
@@ -151,88 +105,9 @@ metrics_backbone_kernel(const float* __restrict__ points, const uint8_t* __restr
 }
 
 // ------------------------------------------------------------------ 2. clashes and contacts
-// Workspace of diffab_metrics_contacts (DIFFAB_METRICS_CONTACTS_WORKSPACE_BYTES covers the carves and their alignment): per patch, the
-// context side compacted once for all its designs.
-struct ContactWorkspace {
-  float4* atoms;  // (G, K*A): the valid atoms of the listed context residues, in residue order
-  int4* res;      // (G, K): listed context residues (non-generated, inside residue_mask, >= 1 valid atom): slot, first atom, atoms, flags
-  int2* key;      // (G, K): chain and residue_idx of the same
-  int32_t* gen;   // (G, K): slots of the generated residues inside residue_mask, ascending
-  int4* hdr;      // (G): generated residues, listed context residues, context atoms, hotspot residues
-  size_t bytes;
-};
-constexpr int kFlagAntigen = 1, kFlagHotspot = 2;
-
-ContactWorkspace carve_contacts(void* base, int64_t G, int64_t K, int64_t A) {
-  Carver c(base);
-  ContactWorkspace w;
-  w.atoms = c.take<float4>(static_cast<size_t>(G * K * A));
-  w.res = c.take<int4>(static_cast<size_t>(G * K));
-  w.key = c.take<int2>(static_cast<size_t>(G * K));
-  w.gen = c.take<int32_t>(static_cast<size_t>(G * K));
-  w.hdr = c.take<int4>(static_cast<size_t>(G));
-  w.bytes = c.bytes();
-  return w;
-}
-
-// One work-group per patch.  Wave 0 lists the residues in ascending order (ballots and a wave prefix sum over the atom counts), then
-// all threads copy the valid atoms behind each other.
-__global__ void __launch_bounds__(256)
-contacts_pack_kernel(const float* __restrict__ ctx_points, const uint32_t* __restrict__ ctx_valid, const uint8_t* __restrict__ generation_mask,
-                     const uint8_t* __restrict__ residue_mask, const uint8_t* __restrict__ antigen_mask, const uint8_t* __restrict__ hotspot_mask,
-                     const int32_t* __restrict__ chain, const int32_t* __restrict__ residue_idx, int K, int A, ContactWorkspace ws) {
-  __shared__ int s_begin[kMaxK];  // first atom of a listed context residue, -1 for every other slot
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t g = blockIdx.x, base = g * K;
-  const uint32_t amask = A >= 32 ? 0xFFFFFFFFu : ((1u << A) - 1u);
-  if (wave == 0) {
-    int ng = 0, nr = 0, na = 0, nh = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int k0 = 0; k0 < K; k0 += 64) {
-      const int k = k0 + lane;
-      const bool in = k < K && (residue_mask == nullptr || residue_mask[base + k] != 0);
-      const bool gen = in && generation_mask[base + k] != 0;
-      const uint32_t bits = (in && !gen) ? (ctx_valid[base + k] & amask) : 0u;
-      const int cnt = __popc(bits);
-      const bool antigen = in && !gen && antigen_mask != nullptr && antigen_mask[base + k] != 0;
-      const bool hot = antigen && hotspot_mask != nullptr && hotspot_mask[base + k] != 0;
-      const unsigned long long vg = __ballot(gen);
-      if (gen) ws.gen[base + ng + __popcll(vg & below)] = k;
-      ng += __popcll(vg);
-      const bool listed = cnt > 0;
-      const unsigned long long vr = __ballot(listed);
-      int incl = cnt;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-      }
-      const int begin = na + incl - cnt;
-      if (listed) {
-        const int r = nr + __popcll(vr & below);
-        ws.res[base + r] = make_int4(k, begin, cnt, (antigen ? kFlagAntigen : 0) | (hot ? kFlagHotspot : 0));
-        ws.key[base + r] = make_int2(chain[base + k], residue_idx[base + k]);
-      }
-      if (k < K) s_begin[k] = listed ? begin : -1;
-      nr += __popcll(vr);
-      na += __shfl(incl, 63, 64);
-      nh += __popcll(__ballot(hot));
-    }
-    if (lane == 0) ws.hdr[g] = make_int4(ng, nr, na, nh);
-  }
-  __syncthreads();
-  float4* out = ws.atoms + base * A;
-  for (int t = tid; t < K * A; t += 256) {
-    const int k = t / A, a = t - k * A;
-    const int b = s_begin[k];
-    if (b < 0) continue;
-    const uint32_t bits = ctx_valid[base + k] & amask;
-    if (((bits >> a) & 1u) == 0u) continue;
-    const float* p = ctx_points + ((base + k) * A + a) * 3;
-    out[b + __popc(bits & ((1u << a) - 1u))] = make_float4(p[0], p[1], p[2], 0.f);
-  }
-}
-
+// The workspace of diffab_metrics_contacts is the ContextWorkspace of analysis_prep.h (DIFFAB_METRICS_CONTACTS_WORKSPACE_BYTES covers
+// its carves and their alignment), filled by context_pack_kernel<false, kMaxK>: every context residue is listed.
+//
 // One work-group per (patch, 64 designs): lane = design, the four waves share the staged context and split the generated residues.
 // The context residues of the patch go through LDS in chunks of whole residues (at most kChunkResidues residues and kChunkAtoms atoms);
 // every lane reads the same context atom (an LDS broadcast) against the atoms of its own design, held in registers.  A generated
@@ -242,7 +117,7 @@ template <int P>
 __global__ void __launch_bounds__(256)
 metrics_contacts_kernel(const float* __restrict__ points, const uint8_t* __restrict__ valid, const int32_t* __restrict__ chain,
                         const int32_t* __restrict__ residue_idx, int N, int K, int A, float clash, float clash2, float contact2, int with_antigen,
-                        ContactWorkspace ws, int32_t* __restrict__ n_clash, float* __restrict__ clash_score, float* __restrict__ min_distance,
+                        ContextWorkspace ws, int32_t* __restrict__ n_clash, float* __restrict__ clash_score, float* __restrict__ min_distance,
                         int32_t* __restrict__ n_contact_pairs, int32_t* __restrict__ n_paratope, int32_t* __restrict__ n_epitope,
                         int32_t* __restrict__ n_hotspot_contacted, int32_t* __restrict__ n_hotspot, int32_t* __restrict__ residue_clash,
                         int32_t* __restrict__ residue_contact) {
@@ -292,8 +167,7 @@ metrics_contacts_kernel(const float* __restrict__ points, const uint8_t* __restr
   auto against = [&](float qx, float qy, float qz, bool q_valid, bool counted, int& c, bool& near) {
 #pragma unroll
     for (int a = 0; a < P; ++a) {
-      float d2 = dist2(px[a], py[a], pz[a], qx, qy, qz);
-      d2 = (q_valid && ((pv >> a) & 1u) != 0u) ? d2 : INFINITY;
+      const float d2 = masked_dist2(px[a], py[a], pz[a], qx, qy, qz, q_valid && ((pv >> a) & 1u) != 0u);
       least = fminf(least, d2);
       near |= d2 < contact2;
       if (d2 < clash2) {
@@ -304,10 +178,6 @@ metrics_contacts_kernel(const float* __restrict__ points, const uint8_t* __restr
         }
       }
     }
-  };
-  auto bonded = [](int ca, int ra, int cb, int rb) {
-    const int64_t gap = static_cast<int64_t>(rb) - ra;
-    return ca == cb && (gap == 1 || gap == -1);
   };
 
   // ---- generated residues against the context, chunk by chunk
@@ -453,7 +323,7 @@ int diffab_metrics_backbone(const float* points, const uint8_t* generation_mask,
   const LinkWorkspace ws = carve_links(workspace, G, K);
   if (const int e = workspace_ok("metrics_backbone", workspace, 16, workspace_bytes, ws.bytes)) return e;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(geometry_links_kernel, dim3(G), dim3(256), 0, st, chain, residue_idx, residue_mask, K, ws.succ, ws.pred);
+  hipLaunchKernelGGL((chain_links_kernel<256, kMaxK>), dim3(G), dim3(256), 0, st, chain, residue_idx, residue_mask, K, ws.succ, ws.pred);
   hipLaunchKernelGGL(metrics_backbone_kernel, dim3(rows), dim3(64), 0, st, points, generation_mask, ws.succ, ws.pred, group_size, K,
                      bond_tolerance, phi, psi, omega, peptide_bond, n_bonds, max_peptide_deviation, n_chain_break, n_cis);
   DIFFAB_LAUNCH_CHECK();
@@ -486,8 +356,9 @@ int diffab_metrics_contacts(const float* points, const uint8_t* valid, const flo
   DIFFAB_REQUIRE(hotspot_mask == nullptr || (n_hotspot_contacted && n_hotspot), DIFFAB_ERR_ARG,
                  "metrics_contacts: null hotspot output with a hotspot_mask");
   const int32_t G = rows / group_size;
-  const ContactWorkspace ws = carve_contacts(workspace, G, K, A);
-  if (const int e = workspace_ok("metrics_contacts", workspace, 16, workspace_bytes, ws.bytes)) return e;
+  Carver carver(workspace);
+  const ContextWorkspace ws = carve_context(carver, G, K, A);
+  if (const int e = workspace_ok("metrics_contacts", workspace, 16, workspace_bytes, carver.bytes())) return e;
   const int64_t grid = static_cast<int64_t>(G) * ((group_size + 63) / 64);
   DIFFAB_REQUIRE(grid <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "metrics_contacts: %d rows are more work-groups than one launch holds", rows);
   hipStream_t st = as_stream(stream);
@@ -495,8 +366,8 @@ int diffab_metrics_contacts(const float* points, const uint8_t* valid, const flo
   DIFFAB_HIP_CHECK(hipMemsetAsync(residue_clash, 0, per_residue, st));
   const int with_antigen = antigen_mask != nullptr;
   if (with_antigen) DIFFAB_HIP_CHECK(hipMemsetAsync(residue_contact, 0, per_residue, st));
-  hipLaunchKernelGGL(contacts_pack_kernel, dim3(G), dim3(256), 0, st, context_points, context_valid, generation_mask, residue_mask,
-                     antigen_mask, hotspot_mask, chain, residue_idx, K, A, ws);
+  hipLaunchKernelGGL((context_pack_kernel<false, kMaxK>), dim3(G), dim3(256), 0, st, context_points, context_valid, generation_mask,
+                     residue_mask, antigen_mask, hotspot_mask, chain, residue_idx, K, A, ws, static_cast<int32_t*>(nullptr));
   const float clash2 = clash_distance * clash_distance, contact2 = contact_distance * contact_distance;
   int32_t* hot_out = hotspot_mask != nullptr ? n_hotspot : nullptr;
 #define DIFFAB_CONTACTS_LAUNCH(PP)                                                                                                       \

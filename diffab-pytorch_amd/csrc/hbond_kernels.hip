@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_hbonds.h"
-#include "analysis_common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -312,29 +312,14 @@ hbonds_patch_kernel(HbondIn in, int K, int A, HbondWorkspace ws) {
   const int64_t g = blockIdx.x, base = g * K;
   const int W = (K + 31) / 32;
   // the keys of the chain rule, borrowed from the atoms' space
-  int* key_chain = reinterpret_cast<int*>(l.xyz);
-  int* key_idx = key_chain + K;
-  int* key_in = key_idx + K;
-  for (int k = tid; k < K; k += kThreads) {
-    key_chain[k] = in.chain[base + k];
-    key_idx[k] = in.residue_idx[base + k];
-    key_in[k] = in.residue_mask == nullptr || in.residue_mask[base + k] != 0;
-  }
+  int2* key = reinterpret_cast<int2*>(l.xyz);
+  uint8_t* key_in = reinterpret_cast<uint8_t*>(key + K);
+  stage_chain_keys<kThreads>(in.chain, in.residue_idx, in.residue_mask, base, K, key, key_in);
   __syncthreads();
   for (int k = tid; k < K; k += kThreads) {
-    int s = -1, p = -1;
-    if (key_in[k]) {
-      const int mc = key_chain[k];
-      const int64_t mi = key_idx[k];
-      for (int j = 0; j < K; ++j) {
-        if (!key_in[j] || key_chain[j] != mc) continue;
-        const int64_t gap = static_cast<int64_t>(key_idx[j]) - mi;
-        if (gap == 1 && s < 0) s = j;
-        if (gap == -1 && p < 0) p = j;
-      }
-    }
-    l.succ[k] = s, l.pred[k] = p;
-    ws.succ[base + k] = s, ws.pred[base + k] = p;
+    const ChainLinks links = chain_links(key, key_in, K, k);
+    l.succ[k] = links.succ, l.pred[k] = links.pred;
+    ws.succ[base + k] = links.succ, ws.pred[base + k] = links.pred;
   }
   __syncthreads();
   stage_atoms(l, in, nullptr, nullptr, g, K, A, tid);

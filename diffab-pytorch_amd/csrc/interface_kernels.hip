@@ -11,7 +11,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_interface.h"
-#include "analysis_common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -29,97 +29,10 @@ static_assert(static_cast<long long>(kMaxWords) * 32 < (1 << 24), "every count i
 constexpr int pad64(int n) { return (n + 63) / 64 * 64; }
 
 // ------------------------------------------------------------------ 1. contact bits
-// Workspace of diffab_metrics_contact_bits (DIFFAB_METRICS_CONTACT_BITS_WORKSPACE_BYTES covers the carves and their alignment): per
-// patch, the antigen side compacted once for all its designs.
-struct ContactBitsWorkspace {
-  float4* atoms;    // (G, K*A): the valid atoms of the listed antigen residues, in residue order
-  int4* res;        // (G, K): listed residues (non-generated, inside residue_mask and antigen_mask, >= 1 valid atom): slot, first atom, atoms
-  int2* key;        // (G, K): chain and residue_idx of the same
-  int32_t* gen;     // (G, K): slots of the generated residues inside residue_mask, ascending
-  int4* hdr;        // (G): generated residues, listed residues, atoms
-  int32_t* wstart;  // (G, W + 1): the first listed residue whose slot is >= 32 w; [W] = the number of listed residues
-  size_t bytes;
-};
-
-ContactBitsWorkspace carve_contact_bits(void* base, int64_t G, int64_t K, int64_t A) {
-  const int64_t W = (K + 31) / 32;
-  Carver c(base);
-  ContactBitsWorkspace w;
-  w.atoms = c.take<float4>(static_cast<size_t>(G * K * A));
-  w.res = c.take<int4>(static_cast<size_t>(G * K));
-  w.key = c.take<int2>(static_cast<size_t>(G * K));
-  w.gen = c.take<int32_t>(static_cast<size_t>(G * K));
-  w.hdr = c.take<int4>(static_cast<size_t>(G));
-  w.wstart = c.take<int32_t>(static_cast<size_t>(G * (W + 1)));
-  w.bytes = c.bytes();
-  return w;
-}
-
-// One work-group per patch.  Wave 0 lists the residues in ascending order (ballots and a wave prefix sum over the atom counts), then
-// all threads copy the valid atoms behind each other: the pack of diffab_metrics_contacts, with the antigen mask as part of the listing
-// and the start of every word column noted on the way.
-__global__ void __launch_bounds__(256)
-contact_bits_pack_kernel(const float* __restrict__ ctx_points, const uint32_t* __restrict__ ctx_valid, const uint8_t* __restrict__ generation_mask,
-                         const uint8_t* __restrict__ residue_mask, const uint8_t* __restrict__ antigen_mask, const int32_t* __restrict__ chain,
-                         const int32_t* __restrict__ residue_idx, int K, int A, ContactBitsWorkspace ws) {
-  __shared__ int s_begin[kMaxK];  // first atom of a listed residue, -1 for every other slot
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int W = (K + 31) / 32;
-  const int64_t g = blockIdx.x, base = g * K;
-  const uint32_t amask = A >= 32 ? 0xFFFFFFFFu : ((1u << A) - 1u);
-  if (wave == 0) {
-    int ng = 0, nr = 0, na = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (int k0 = 0; k0 < K; k0 += 64) {
-      const int k = k0 + lane;
-      const bool in = k < K && (residue_mask == nullptr || residue_mask[base + k] != 0);
-      const bool gen = in && generation_mask[base + k] != 0;
-      const bool antigen = in && !gen && antigen_mask[base + k] != 0;
-      const uint32_t bits = antigen ? (ctx_valid[base + k] & amask) : 0u;
-      const int cnt = __popc(bits);
-      const unsigned long long vg = __ballot(gen);
-      if (gen) ws.gen[base + ng + __popcll(vg & below)] = k;
-      ng += __popcll(vg);
-      const bool listed = cnt > 0;
-      const unsigned long long vr = __ballot(listed);
-      int incl = cnt;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-      }
-      const int begin = na + incl - cnt;
-      if (listed) {
-        const int r = nr + __popcll(vr & below);
-        ws.res[base + r] = make_int4(k, begin, cnt, 0);
-        ws.key[base + r] = make_int2(chain[base + k], residue_idx[base + k]);
-      }
-      if (k < K) s_begin[k] = listed ? begin : -1;
-      if (lane == 0) {
-        ws.wstart[g * (W + 1) + k0 / 32] = nr;
-        if (k0 / 32 + 1 < W) ws.wstart[g * (W + 1) + k0 / 32 + 1] = nr + __popcll(vr & 0xFFFFFFFFull);
-      }
-      nr += __popcll(vr);
-      na += __shfl(incl, 63, 64);
-    }
-    if (lane == 0) {
-      ws.wstart[g * (W + 1) + W] = nr;
-      ws.hdr[g] = make_int4(ng, nr, na, 0);
-    }
-  }
-  __syncthreads();
-  float4* out = ws.atoms + base * A;
-  for (int t = tid; t < K * A; t += 256) {
-    const int k = t / A, a = t - k * A;
-    const int b = s_begin[k];
-    if (b < 0) continue;
-    const uint32_t bits = ctx_valid[base + k] & amask;
-    if (((bits >> a) & 1u) == 0u) continue;
-    const float* p = ctx_points + ((base + k) * A + a) * 3;
-    out[b + __popc(bits & ((1u << a) - 1u))] = make_float4(p[0], p[1], p[2], 0.f);
-  }
-}
-
+// The workspace of diffab_metrics_contact_bits (DIFFAB_METRICS_CONTACT_BITS_WORKSPACE_BYTES covers the carves and their alignment) is the
+// ContextWorkspace of analysis_prep.h, then wstart (G, W + 1).  context_pack_kernel<true, kMaxK> fills both: the pack of
+// diffab_metrics_contacts, with the antigen mask as part of the listing and the start of every word column noted on the way.
+//
 // One work-group per (patch, 64 designs): lane = design, the four waves share the staged antigen atoms and split the generated residues.
 // The listed residues go through LDS one word column (32 slots) at a time; every lane reads the same antigen atom (an LDS broadcast)
 // against the atoms of its own design, held in registers.  The word of (design, generated residue i, column w) is built by one thread in
@@ -129,8 +42,8 @@ contact_bits_pack_kernel(const float* __restrict__ ctx_points, const uint32_t* _
 template <int P>
 __global__ void __launch_bounds__(256)
 contact_bits_kernel(const float* __restrict__ points, const uint8_t* __restrict__ valid, const int32_t* __restrict__ chain,
-                    const int32_t* __restrict__ residue_idx, int N, int K, int A, float contact2, ContactBitsWorkspace ws,
-                    uint32_t* __restrict__ bits, int32_t* __restrict__ n_contacts) {
+                    const int32_t* __restrict__ residue_idx, int N, int K, int A, float contact2, ContextWorkspace ws,
+                    const int32_t* __restrict__ wstarts, uint32_t* __restrict__ bits, int32_t* __restrict__ n_contacts) {
   __shared__ float4 s_atom[kColumnAtoms];
   __shared__ int4 s_res[32];  // slot, first atom in s_atom, atoms
   __shared__ int2 s_key[32];
@@ -149,7 +62,7 @@ contact_bits_kernel(const float* __restrict__ points, const uint8_t* __restrict_
   const int4* res = ws.res + g * K;
   const int2* key = ws.key + g * K;
   const float4* atoms = ws.atoms + g * K * A;
-  const int32_t* wstart = ws.wstart + g * (W + 1);
+  const int32_t* wstart = wstarts + g * (W + 1);
   const float* pp = points + row * K * P * 3;
   const uint8_t* vv = valid + row * K;
   const int32_t* ch = chain + g * K;
@@ -195,16 +108,13 @@ contact_bits_kernel(const float* __restrict__ points, const uint8_t* __restrict_
         for (int rl = 0; rl < nres; ++rl) {
           const int4 r = s_res[rl];
           const int2 kk = s_key[rl];
-          const int64_t gap = static_cast<int64_t>(kk.y) - rri;
-          if (ci == kk.x && (gap == 1 || gap == -1)) continue;  // chain neighbours
+          if (bonded(ci, rri, kk.x, kk.y)) continue;
           bool near = false;
           for (int b = r.y; b < r.y + r.z; ++b) {
             const float4 q = s_atom[b];
 #pragma unroll
             for (int a = 0; a < P; ++a) {
-              float d2 = dist2(px[a], py[a], pz[a], q.x, q.y, q.z);
-              d2 = ((pv >> a) & 1u) != 0u ? d2 : INFINITY;
-              near |= d2 < contact2;
+              near |= masked_dist2(px[a], py[a], pz[a], q.x, q.y, q.z, ((pv >> a) & 1u) != 0u) < contact2;
             }
           }
           if (near) word |= 1u << (r.x & 31);
@@ -430,18 +340,20 @@ int diffab_metrics_contact_bits(const float* points, const uint8_t* valid, const
                  DIFFAB_ERR_ARG, "%s: null input", who);
   DIFFAB_REQUIRE(bits != nullptr && n_contacts != nullptr, DIFFAB_ERR_ARG, "%s: null output", who);
   const int32_t G = rows / group_size;
-  const ContactBitsWorkspace ws = carve_contact_bits(workspace, G, K, A);
-  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, ws.bytes)) return e;
+  Carver carver(workspace);
+  const ContextWorkspace ws = carve_context(carver, G, K, A);
+  int32_t* wstart = carver.take<int32_t>(static_cast<size_t>(G) * ((K + 31) / 32 + 1));
+  if (const int e = workspace_ok(who, workspace, 256, workspace_bytes, carver.bytes())) return e;
   const int64_t grid = static_cast<int64_t>(G) * ((group_size + 63) / 64);
   DIFFAB_REQUIRE(grid <= INT_MAX, DIFFAB_ERR_UNSUPPORTED, "%s: %d rows are more work-groups than one launch holds", who, rows);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(contact_bits_pack_kernel, dim3(G), dim3(256), 0, st, context_points, context_valid, generation_mask, residue_mask,
-                     antigen_mask, chain, residue_idx, K, A, ws);
+  hipLaunchKernelGGL((context_pack_kernel<true, kMaxK>), dim3(G), dim3(256), 0, st, context_points, context_valid, generation_mask,
+                     residue_mask, antigen_mask, static_cast<const uint8_t*>(nullptr), chain, residue_idx, K, A, ws, wstart);
   const float contact2 = contact_distance * contact_distance;
   uint32_t* out = reinterpret_cast<uint32_t*>(bits);
 #define DIFFAB_CONTACT_BITS_LAUNCH(PP)                                                                                                    \
   hipLaunchKernelGGL((contact_bits_kernel<PP>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, st, points, valid, chain, residue_idx, \
-                     group_size, K, A, contact2, ws, out, n_contacts)
+                     group_size, K, A, contact2, ws, wstart, out, n_contacts)
   switch (P) {
     case 1: DIFFAB_CONTACT_BITS_LAUNCH(1); break;
     case 2: DIFFAB_CONTACT_BITS_LAUNCH(2); break;

@@ -9,7 +9,7 @@
 // plain C++ stores.
 #include <climits>
 
-#include "common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -27,52 +27,6 @@ constexpr float kBond = DIFFAB_REFINE_BOND, kAngleCaN = DIFFAB_REFINE_CA_N, kAng
 constexpr float kInertia = DIFFAB_REFINE_INERTIA;
 constexpr float kTiny = 1e-6f;  // a pair closer than this exerts no force (guidance's guard); below it Exp uses its limit values
 constexpr unsigned kIn = 1u, kMoving = 2u;
-
-// ------------------------------------------------------------------ chain neighbours of a patch
-// succ[k] / pred[k]: the lowest slot j of the patch with the same chain, residue_idx[j] = residue_idx[k] + 1 / - 1 and both inside
-// residue_mask; -1 without one (the rule of diffab_metrics_backbone).  One work-group per patch, the keys in LDS.
-__global__ void __launch_bounds__(kThreads)
-refine_links_kernel(const int32_t* __restrict__ chain, const int32_t* __restrict__ residue_idx, const uint8_t* __restrict__ residue_mask,
-                    int K, int32_t* __restrict__ succ, int32_t* __restrict__ pred) {
-  __shared__ int2 s_key[kMaxK];
-  __shared__ uint8_t s_in[kMaxK];
-  const int tid = threadIdx.x;
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * K;
-  for (int k = tid; k < K; k += kThreads) {
-    s_key[k] = make_int2(chain[base + k], residue_idx[base + k]);
-    s_in[k] = residue_mask == nullptr || residue_mask[base + k] != 0;
-  }
-  __syncthreads();
-  for (int k = tid; k < K; k += kThreads) {
-    int s = -1, p = -1;
-    if (s_in[k]) {
-      const int2 me = s_key[k];
-      for (int j = 0; j < K; ++j) {
-        if (!s_in[j] || s_key[j].x != me.x) continue;
-        const int64_t gap = static_cast<int64_t>(s_key[j].y) - me.y;
-        if (gap == 1 && s < 0) s = j;
-        if (gap == -1 && p < 0) p = j;
-      }
-    }
-    succ[base + k] = s;
-    pred[base + k] = p;
-  }
-}
-
-struct LinkWorkspace {
-  int32_t* succ;  // (G, K)
-  int32_t* pred;  // (G, K)
-  size_t bytes;
-};
-
-LinkWorkspace carve_links(void* base, int64_t G, int64_t K) {
-  Carver c(base);
-  LinkWorkspace w;
-  w.succ = c.take<int32_t>(static_cast<size_t>(G * K));
-  w.pred = c.take<int32_t>(static_cast<size_t>(G * K));
-  w.bytes = c.bytes();
-  return w;
-}
 
 // ------------------------------------------------------------------ the refinement
 struct RefineParams {
@@ -104,12 +58,6 @@ __device__ inline Vec3 pair_force(Vec3 a, Vec3 b, float d0, float w) {
 __device__ inline float pair_energy(Vec3 a, Vec3 b, float d0, float w) {
   const float e = sqrtf(norm2(a - b)) - d0;
   return w * (e * e);
-}
-
-// chain neighbours in either direction, by the keys (both slots are inside residue_mask where this is asked)
-__device__ inline bool bonded(int2 a, int2 b) {
-  const int64_t gap = static_cast<int64_t>(b.y) - a.y;
-  return a.x == b.x && (gap == 1 || gap == -1);
 }
 
 // The LDS of one work-group, carved from the dynamic allocation: 148 K bytes (DIFFAB_REFINE_LDS_BYTES).
@@ -167,7 +115,7 @@ __device__ inline void row_energy(const RowLds& s, int b, int K, const RefinePar
     const int2 me = s.key[k];
     for (int j = k + 1; j < K; ++j) {
       const unsigned fj = s.flag[j];
-      if ((fj & kIn) == 0u || !(mine || (fj & kMoving) != 0u) || bonded(me, s.key[j])) continue;
+      if ((fj & kIn) == 0u || !(mine || (fj & kMoving) != 0u) || bonded(me.x, me.y, s.key[j].x, s.key[j].y)) continue;
       const float d = sqrtf(norm2(ca - v3(s.ca[b * K + j])));
       if (d < p.clash) {
         const float t = p.clash - d;
@@ -266,7 +214,7 @@ refine_backbone_kernel(const float* __restrict__ translations, const float* __re
         if (p.w_clash != 0.f) {
           const int2 me = s.key[k];
           for (int j = sub; j < K; j += kLanes) {
-            if (j == k || (s.flag[j] & kIn) == 0u || bonded(me, s.key[j])) continue;
+            if (j == k || (s.flag[j] & kIn) == 0u || bonded(me.x, me.y, s.key[j].x, s.key[j].y)) continue;
             const Vec3 r = ca - v3(s.ca[b * K + j]);
             const float d = sqrtf(norm2(r));
             if (d < p.clash && !(d < kTiny)) push = push + (((2.f * p.w_clash) * (p.clash - d)) / d) * r;
@@ -444,7 +392,7 @@ int diffab_refine_backbone(const float* translations, const float* orientations,
   p.w_bond = o.w_bond, p.w_angle = o.w_angle, p.w_trans = o.w_trans, p.w_clash = o.w_clash, p.w_tether = o.w_tether;
   p.clash = o.clash_distance;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(refine_links_kernel, dim3(G), dim3(kThreads), 0, st, chain, residue_idx, residue_mask, K, ws.succ, ws.pred);
+  hipLaunchKernelGGL((chain_links_kernel<kThreads, kMaxK>), dim3(G), dim3(kThreads), 0, st, chain, residue_idx, residue_mask, K, ws.succ, ws.pred);
   hipLaunchKernelGGL(refine_backbone_kernel, dim3(rows), dim3(kThreads), DIFFAB_REFINE_LDS_BYTES(K), st, translations, orientations,
                      generation_mask, residue_mask, chain, residue_idx, ws.succ, ws.pred, group_size, K, p, out_translations,
                      out_orientations, energy_before, energy_after, terms_after, max_shift);

@@ -10,7 +10,7 @@
 #include <cmath>
 
 #include "../../include/diffab_hip_analysis.h"
-#include "analysis_common.h"
+#include "analysis_prep.h"
 
 namespace diffab {
 namespace {
@@ -80,18 +80,15 @@ surface_pack_kernel(const float* __restrict__ ctx_points, const uint32_t* __rest
   __shared__ int s_n_antigen;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t g = blockIdx.x, base = g * K;
-  const uint32_t amask = A >= 32 ? 0xFFFFFFFFu : ((1u << A) - 1u);
+  const uint32_t amask = atom_mask_of(A);
   if (wave == 0) {
     int ng = 0, nt = 0, na = 0, nf = 0, nh = 0;
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int k0 = 0; k0 < K; k0 += 64) {
       const int k = k0 + lane;
-      const bool in = k < K && (residue_mask == nullptr || residue_mask[base + k] != 0);
-      const bool gen = in && generation_mask[base + k] != 0;
-      const uint32_t bits = (in && !gen) ? (ctx_valid[base + k] & amask) : 0u;
-      const int cnt = __popc(bits);
-      const bool antigen = in && !gen && antigen_mask != nullptr && antigen_mask[base + k] != 0;
-      const bool hot = antigen && hotspot_mask != nullptr && hotspot_mask[base + k] != 0;
+      const SlotClass c = classify_slot(k, K, base, residue_mask, generation_mask, antigen_mask, hotspot_mask, ctx_valid, amask);
+      const bool gen = c.gen, antigen = c.antigen, hot = c.hot;
+      const int cnt = __popc(c.bits);
       const unsigned long long vg = __ballot(gen);
       const int gi = ng + __popcll(vg & below);
       if (gen) ws.gen[base + gi] = k;

@@ -116,6 +116,25 @@ def _is_int(v) -> bool:
     return isinstance(v, int) and not isinstance(v, bool)
 
 
+def _check_dist(who: str, dist) -> tuple:
+    """dist (G,N,N) float32 -> (G, N)."""
+    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 3 or dist.shape[1] != dist.shape[2]:
+        raise ValueError(f"{who}: dist must be a float32 tensor (G, N, N)")
+    G, N = int(dist.shape[0]), int(dist.shape[1])
+    if N < 1 or N > MAX_GROUP:
+        raise ValueError(f"{who}: dist has N = {N} designs per patch, outside [1, {MAX_GROUP}]")
+    return G, N
+
+
+def _check_per_design(who: str, G: int, N: int, **tensors) -> None:
+    """Optional (G,N) operands, checked in the order given: ``candidates`` is a bool tensor, every other one a float tensor."""
+    for name, t in tensors.items():
+        kind = "bool" if name == "candidates" else "float"
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (G, N)
+                              or not (t.dtype == torch.bool if kind == "bool" else t.is_floating_point())):
+            raise ValueError(f"{who}: {name} must be a {kind} tensor {(G, N)}")
+
+
 def _check_frames(who: str, name: str, d, atoms: str):
     """seq_idx (R,K) integer, translations (R,K,3) float, orientations (R,K,3,3) float (needed for the backbone only) -> (R, K)."""
     if not isinstance(d, dict) or not isinstance(d.get("seq_idx"), torch.Tensor) or not isinstance(d.get("translations"), torch.Tensor):
@@ -256,18 +275,10 @@ def select_diverse(dist: torch.Tensor, m: int, *, score: Optional[torch.Tensor] 
     (G,m) int64, ``min_dist`` (G,m) fp32 - that smallest distance when the design was picked, +inf for the first - and ``count`` (G,)
     int32; with fewer than ``m`` candidates the tail is -1 / NaN.  Comparisons only: the result is a function of the fp32 matrix."""
     who = "metrics.select_diverse()"
-    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 3 or dist.shape[1] != dist.shape[2]:
-        raise ValueError(f"{who}: dist must be a float32 tensor (G, N, N)")
-    G, N = int(dist.shape[0]), int(dist.shape[1])
-    if N < 1 or N > MAX_GROUP:
-        raise ValueError(f"{who}: dist has N = {N} designs per patch, outside [1, {MAX_GROUP}]")
+    G, N = _check_dist(who, dist)
     if not _is_int(m) or m < 0:
         raise ValueError(f"{who}: m must be an int >= 0, got {m!r}")
-    if score is not None and (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (G, N)):
-        raise ValueError(f"{who}: score must be a float tensor {(G, N)}")
-    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.bool
-                                   or tuple(candidates.shape) != (G, N)):
-        raise ValueError(f"{who}: candidates must be a bool tensor {(G, N)}")
+    _check_per_design(who, G, N, score=score, candidates=candidates)
     lib = _hip.lib()
     dev, out_dev = _hip.device(), dist.device
     d = _hip.dev_f32(dist)
@@ -305,21 +316,13 @@ def cluster(dist: torch.Tensor, cutoff, *, candidates: Optional[torch.Tensor] = 
     popcounts and integer adds only: the result is a function of the fp32 matrix.  One C-ABI call (two launches); results on
     ``dist``'s device; ValueError naming the argument before any device work."""
     who = "metrics.cluster()"
-    if not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or dist.dim() != 3 or dist.shape[1] != dist.shape[2]:
-        raise ValueError(f"{who}: dist must be a float32 tensor (G, N, N)")
-    G, N = int(dist.shape[0]), int(dist.shape[1])
-    if N < 1 or N > MAX_GROUP:
-        raise ValueError(f"{who}: dist has N = {N} designs per patch, outside [1, {MAX_GROUP}]")
+    G, N = _check_dist(who, dist)
     if isinstance(cutoff, torch.Tensor):
         if not cutoff.is_floating_point() or tuple(cutoff.shape) != (G,):
             raise ValueError(f"{who}: cutoff must be a number or a float tensor {(G,)}")
     elif isinstance(cutoff, bool) or not isinstance(cutoff, (int, float)):
         raise ValueError(f"{who}: cutoff must be a number or a float tensor {(G,)}, got {cutoff!r}")
-    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.bool
-                                   or tuple(candidates.shape) != (G, N)):
-        raise ValueError(f"{who}: candidates must be a bool tensor {(G, N)}")
-    if score is not None and (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (G, N)):
-        raise ValueError(f"{who}: score must be a float tensor {(G, N)}")
+    _check_per_design(who, G, N, candidates=candidates, score=score)
     M = N if max_clusters is None else max_clusters
     if not _is_int(M) or M < 0 or M > N:
         raise ValueError(f"{who}: max_clusters must be an int in [0, N = {N}] or None, got {max_clusters!r}")
@@ -440,14 +443,7 @@ def pareto(objectives, *, group_size: Optional[int] = None, maximize=None, viola
         flags = list(maximize)
     else:
         raise ValueError(f"{who}: maximize must be a bool or a sequence of M = {M} bools, got {maximize!r}")
-    if violation is not None and (not isinstance(violation, torch.Tensor) or not violation.is_floating_point()
-                                  or tuple(violation.shape) != (G, N)):
-        raise ValueError(f"{who}: violation must be a float tensor {(G, N)}")
-    if score is not None and (not isinstance(score, torch.Tensor) or not score.is_floating_point() or tuple(score.shape) != (G, N)):
-        raise ValueError(f"{who}: score must be a float tensor {(G, N)}")
-    if candidates is not None and (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.bool
-                                   or tuple(candidates.shape) != (G, N)):
-        raise ValueError(f"{who}: candidates must be a bool tensor {(G, N)}")
+    _check_per_design(who, G, N, violation=violation, score=score, candidates=candidates)
     F = N if max_fronts is None else max_fronts
     if not _is_int(F) or F < 0 or F > N:
         raise ValueError(f"{who}: max_fronts must be an int in [0, N = {N}] or None, got {max_fronts!r}")
@@ -566,6 +562,26 @@ def _frame_atoms(seq: torch.Tensor, x: torch.Tensor, O: torch.Tensor, atoms: Seq
     return pts, bits.contiguous()
 
 
+def _atom_operands(designs, generation_mask, residue_mask, context, A, atoms, group_size: int, G: int):
+    """The operands every atom-level filter takes, on the device: the frame atoms ``pts`` (rows,K,P,3) of every design and their
+    validity bits ``valid``; the context side ``cpts`` (G,K,A,3) / ``cvalid`` (G,K) int32 - ``context``'s real atoms (A as checked), or
+    without ``context`` the frame atoms of the first row of each group (A = P); and the two masks.
+    -> pts, valid, cpts, cvalid, A, gm, rm."""
+    dev = _hip.device()
+    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
+    pts, valid = _frame_atoms(seq, x, O, atoms)
+    if context is None:
+        first = torch.arange(G, device=dev) * group_size
+        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
+        A, cvalid = len(atoms), cbits.to(torch.int32).contiguous()
+    else:
+        cpts = _hip.dev_f32(context["xyz"])
+        cvalid = _valid_word(context["atom_mask"], A, dev)
+    gm = _hip.dev_mask(generation_mask)
+    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    return pts, valid, cpts, cvalid, A, gm, rm
+
+
 def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, context: Optional[Dict[str, torch.Tensor]] = None,
              antigen_mask: Optional[torch.Tensor] = None, hotspot_mask: Optional[torch.Tensor] = None, chain_idx=None, residue_idx=None,
              residue_mask: Optional[torch.Tensor] = None, group_size: int = 1, clash_distance: float = 3.0, contact_distance: float = 5.0,
@@ -595,24 +611,14 @@ def contacts(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *,
         if antigen_mask is None:
             raise ValueError(f"{who}: hotspot_mask needs an antigen_mask")
         _check_patch_mask(who, "hotspot_mask", hotspot_mask, G, K)
-    if context is not None:
-        A = _check_context(who, context, G, K)
+    A = None if context is None else _check_context(who, context, G, K)
     chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
 
     lib = _hip.lib()
     dev, out_dev = _hip.device(), designs["seq_idx"].device
     P = len(atoms)
-    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
-    pts, valid = _frame_atoms(seq, x, O, atoms)
-    if context is None:
-        first = torch.arange(G, device=dev) * group_size
-        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
-        A, cvalid = P, cbits.to(torch.int32).contiguous()
-    else:
-        cpts = _hip.dev_f32(context["xyz"])
-        cvalid = _valid_word(context["atom_mask"], A, dev)
-    gm = _hip.dev_mask(generation_mask)
-    rm, ag, hs = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask, hotspot_mask))
+    pts, valid, cpts, cvalid, A, gm, rm = _atom_operands(designs, generation_mask, residue_mask, context, A, atoms, group_size, G)
+    ag, hs = (None if m is None else _hip.dev_mask(m) for m in (antigen_mask, hotspot_mask))
     chain, ridx = chain.to(dev), ridx.to(dev)
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     out = {"n_clash": i32(rows), "clash_score": torch.empty(rows, dtype=torch.float32, device=dev),
@@ -670,24 +676,14 @@ def contact_map(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor,
     if antigen_mask is None:
         raise ValueError(f"{who}: antigen_mask is required: the columns of a contact map are the antigen residues")
     _check_patch_mask(who, "antigen_mask", antigen_mask, G, K)
-    if context is not None:
-        A = _check_context(who, context, G, K)
+    A = None if context is None else _check_context(who, context, G, K)
     chain, ridx, _ = residue_tables(who, chain_idx, residue_idx, None, G, K)
 
     lib = _hip.lib()
     dev, out_dev = _hip.device(), designs["seq_idx"].device
     P = len(atoms)
-    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
-    pts, valid = _frame_atoms(seq, x, O, atoms)
-    if context is None:
-        first = torch.arange(G, device=dev) * group_size
-        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
-        A, cvalid = P, cbits.to(torch.int32).contiguous()
-    else:
-        cpts = _hip.dev_f32(context["xyz"])
-        cvalid = _valid_word(context["atom_mask"], A, dev)
-    gm, ag = _hip.dev_mask(generation_mask), _hip.dev_mask(antigen_mask)
-    rm = None if residue_mask is None else _hip.dev_mask(residue_mask)
+    pts, valid, cpts, cvalid, A, gm, rm = _atom_operands(designs, generation_mask, residue_mask, context, A, atoms, group_size, G)
+    ag = _hip.dev_mask(antigen_mask)
     chain, ridx = chain.to(dev), ridx.to(dev)
     bits = torch.empty(rows, K, (K + 31) // 32, dtype=torch.int32, device=dev)
     n_contacts = torch.empty(rows, dtype=torch.int32, device=dev)
@@ -1657,7 +1653,7 @@ def surface(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, 
         if antigen_mask is None:
             raise ValueError(f"{who}: hotspot_mask needs an antigen_mask")
         _check_patch_mask(who, "hotspot_mask", hotspot_mask, G, K)
-    ctx_radius = None
+    A = ctx_radius = None
     if context is not None:
         A = _check_context(who, context, G, K)
         ctx_radius = context.get("atom_radius")
@@ -1670,19 +1666,12 @@ def surface(designs: Dict[str, torch.Tensor], generation_mask: torch.Tensor, *, 
     lib = _hip.lib()
     dev, out_dev = _hip.device(), designs["seq_idx"].device
     P = len(atoms)
-    seq, x, O = _hip.dev_i64(designs["seq_idx"]), _hip.dev_f32(designs["translations"]), _hip.dev_f32(designs["orientations"])
-    pts, valid = _frame_atoms(seq, x, O, atoms)
+    pts, valid, cpts, cvalid, A, gm, rm = _atom_operands(designs, generation_mask, residue_mask, context, A, atoms, group_size, G)
     if context is None:
-        first = torch.arange(G, device=dev) * group_size
-        cpts, cbits = _frame_atoms(seq[first], x[first].contiguous(), O[first].contiguous(), atoms)
-        A, cvalid = P, cbits.to(torch.int32).contiguous()
         crad = torch.tensor(radii, dtype=torch.float32, device=dev).expand(G, K, P).contiguous()
     else:
-        cpts = _hip.dev_f32(context["xyz"])
-        cvalid = _valid_word(context["atom_mask"], A, dev)
         crad = None if ctx_radius is None else _hip.dev_f32(ctx_radius)
-    gm = _hip.dev_mask(generation_mask)
-    rm, ag, hs = (None if m is None else _hip.dev_mask(m) for m in (residue_mask, antigen_mask, hotspot_mask))
+    ag, hs = (None if m is None else _hip.dev_mask(m) for m in (antigen_mask, hotspot_mask))
     table = _hip.dev_f32(_sphere_table(n_points))
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
     f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)

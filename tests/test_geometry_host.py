@@ -48,6 +48,28 @@ def neighbours(chain, ridx, rm):
     return succ, pred
 
 
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+
+
+def tangle_chain_keys(chain, ridx, rm, at, far):
+    """Rewrites, in place, the keys of one patch so that each way to get the chain rule wrong gives other links.  Slots at .. at + 12
+    must be a run of one chain numbered r, r + 1, ... and inside rm; `far` is a slot of another chain.  Afterwards
+      - slot `at` has residue_idx INT32_MIN and `far`, moved into the run's chain, INT32_MAX: no neighbours, a 32-bit gap says they are;
+      - slot at + 4 repeats the key of at + 2: the lower slot is the neighbour of at + 1 and at + 3;
+      - slot at + 7, outside rm, carries the key of at + 9 ahead of it: it is skipped;
+      - slot at + 10, in `far`'s old chain, carries the number of at + 12 ahead of it: another chain is no neighbour.
+    Returns {slot: (succ, pred)}, the links the rule gives the rewritten slots (derived by hand, not by a reference)."""
+    c, r, other = chain[at], int(ridx[at]), chain[far]
+    assert other != c and rm[at:at + 13].all() and (chain[at:at + 13] == c).all() and (ridx[at:at + 13] == r + np.arange(13)).all()
+    ridx[at], ridx[far], chain[far] = INT32_MIN, INT32_MAX, c
+    ridx[at + 4] = r + 2
+    ridx[at + 7], rm[at + 7] = r + 9, False
+    ridx[at + 10], chain[at + 10] = r + 12, other
+    a = at
+    return {a: (-1, -1), far: (-1, -1), a + 1: (a + 2, -1), a + 2: (a + 3, a + 1), a + 3: (-1, a + 2), a + 4: (a + 3, a + 1),
+            a + 5: (a + 6, -1), a + 6: (-1, a + 5), a + 7: (-1, -1), a + 8: (a + 9, -1), a + 9: (-1, a + 8), a + 11: (a + 12, -1)}
+
+
 def dihedrals_ref(p0, p1, p2, p3):
     """dihedral_ref over leading axes: (…,3) float64 points -> angle (…), the smaller of the two cross-product norms (…)."""
     b1, b2, b3 = p1 - p0, p2 - p1, p3 - p2
@@ -315,6 +337,26 @@ def test_chain_neighbours_and_generated_pairs():
     # an atom whose bit is clear does not exist; no pair at all gives +inf
     out = contacts_ref(pts, np.array([[1, 1, 0]], np.uint8), pts, np.zeros((1, 3), np.int64), gen, rm, chain, ridx)
     assert out["n_clash"][0] == 0 and out["min_distance"][0] == np.inf
+
+
+def test_every_reference_of_the_chain_rule_takes_the_gap_in_64_bits_and_the_lowest_slot():
+    """The four entries that link chain neighbours share one kernel; their tests share tangle_chain_keys.  What the references (this
+    file's, the hydrogen bonds' and the motifs') make of such keys is checked here against links derived by hand."""
+    from developability_ref import succ_ref  # (imports this module)
+    from test_hbonds_host import links
+
+    K = 40
+    chain, rm = np.repeat([1, 2], K // 2).astype(np.int32), np.ones(K, bool)
+    ridx = np.arange(K, dtype=np.int32) + 7
+    expect = tangle_chain_keys(chain, ridx, rm, 3, K - 1)
+    assert ridx.dtype == np.int32 and int(ridx[K - 1]) - int(ridx[3]) == 2 ** 32 - 1  # (the difference is 1 where it wraps)
+    for name, (succ, pred) in (("neighbours", neighbours(chain, ridx, rm)), ("links", links(chain, ridx, rm)),
+                               ("succ_ref", (succ_ref(rm, chain, ridx), None))):
+        for slot, (s, p) in expect.items():
+            assert succ[slot] == s and (pred is None or pred[slot] == p), (name, slot, succ[slot], s, None if pred is None else pred[slot], p)
+    # bonded pairs in either direction, as contacts_ref and refine_ref ask: the two ends of the int32 range are not bonded
+    gap = ridx.astype(np.int64)[:, None] - ridx[None, :]
+    assert abs(int(gap[K - 1, 3])) == 2 ** 32 - 1
 
 
 # ------------------------------------------------------------------ C ABI

@@ -15,6 +15,7 @@ import torch
 
 import sampler_support
 from developability_ref import EXPOSED, PRESENT, SCOPE, motifs_ref, patches_ref, same_bits, ulps_apart
+from test_geometry_host import tangle_chain_keys
 from diffab_pytorch import _hip, io as dio, metrics
 from sampler_support import GuardedABI, header_prototypes, hip, misaligned
 from scratch_poison import poisoned
@@ -297,6 +298,12 @@ def test_a_patch_alone_gives_the_bits_it_gives_in_a_batch(context):
 
 
 # ------------------------------------------------------------------ motifs
+# (K, N) -> per patch, the first of 13 slots of the second chain that take the keys of test_geometry_host.tangle_chain_keys, slot 0 with
+# them: a 32-bit gap, the highest slot, a masked slot or another chain would give other successors.  The slots are generated and hold
+# D P, N A . G, D G and G N A along the right and the wrong successors, so each wrong rule counts another number of motifs.
+TANGLED = {(65, 2): (36, 37)}
+
+
 @functools.lru_cache(maxsize=None)
 def motif_case(K, N, seed=0):
     """G = 2 patches x N designs of random tokens 0..20 (and a token of 32 and a negative one where there is room).  Two chains with a gap
@@ -322,6 +329,12 @@ def motif_case(K, N, seed=0):
         tokens[:, half + 2], tokens[:, half + 3] = 32, -3
         tokens[:, lo:lo + len(planted)] = [dio.AA1.index(ch) for ch in planted]
         tokens[:, K - 4:K - 1] = [dio.AA1.index(ch) for ch in "NKT"]  # outside the generated residues: matched, not counted
+    for g, at in enumerate(TANGLED.get((K, N), ())):
+        chain, ridx = chain.astype(np.int32), ridx.astype(np.int32)
+        tangle_chain_keys(chain[g], ridx[g], rm[g], at, 0)
+        gen[g, at:at + 13] = gen[g, 0] = True
+        for slot, ch in zip([0, at, at + 1, at + 2, at + 4, at + 8, at + 9, at + 7, at + 10, at + 11, at + 12], "DPNAGDGGGNA"):
+            tokens[g * N:(g + 1) * N, slot] = dio.AA1.index(ch)
     designs = {"seq_idx": cuda(tokens), "translations": cuda(np.zeros((G * N, K, 3), f32))}
     return dict(G=G, N=N, K=K, gen=gen, rm=rm, chain=chain, ridx=ridx, tokens=tokens, designs=designs, gen_d=cuda(gen), rm_d=cuda(rm),
                 chain_d=cuda(chain), ridx_d=cuda(ridx))
@@ -353,7 +366,7 @@ def check_motifs(out, want, names, what):
         assert len(bad) == 0, (what, k, "first differing elements:", bad[:5].tolist())
 
 
-@pytest.mark.parametrize("K, N", SHAPES + [(70, 3), (300, 3)])  # (successors past the 64 threads of their kernel, ragged and not)
+@pytest.mark.parametrize("K, N", SHAPES + [(70, 3), (300, 3)] + list(TANGLED))  # (successors past the 64 threads of their kernel, ragged and not)
 def test_liabilities_equal_the_restatement(K, N):
     m, want = motif_case(K, N), motif_reference(K, N)
     if K >= 33:  # what the inputs must contain

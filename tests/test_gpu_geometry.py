@@ -17,7 +17,7 @@ import torch
 
 from diffab_pytorch import DiffAb, io as dio, metrics, patch, synthetic as syn
 from sampler_support import hip
-from test_geometry_host import backbone_ref, contacts_ref, frames_of, nerf_chain, wrapped
+from test_geometry_host import backbone_ref, contacts_ref, frames_of, nerf_chain, tangle_chain_keys, wrapped
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("hip")]  # every test here needs the device, whether it names the fixture or not
 
@@ -129,6 +129,34 @@ def case(N, K, A=15, dense=False, kinds=KINDS, seed=0):
     return c
 
 
+TANGLED = (2, 257)  # (N, K) of tangled_case: the chain rule where one links kernel serves four entries, past its 256 threads
+
+
+@functools.lru_cache(maxsize=None)
+def tangled_case(N, K):
+    """G = 2 patches x N designs with the keys of test_geometry_host.tangle_chain_keys in chain 1, at slots 38 .. 50 and 20 .. 32, and
+    in the last slot of the patch; those slots are generated, so their bonds are counted.  The fields of case()."""
+    rng = np.random.default_rng(1000 * K + 10 * N + 7)
+    G = 2
+    patches = [build_patch(rng, K, 15, "loop", False) for _ in range(G)]
+    rm = np.ones((G, K), bool)
+    for g, at in enumerate((38, 20)):
+        p = patches[g]
+        p["chain_idx"], p["residue_idx"] = p["chain_idx"].astype(np.int32), p["residue_idx"].astype(np.int32)
+        tangle_chain_keys(p["chain_idx"], p["residue_idx"], rm[g], at, K - 1)
+        p["generation_mask"][at:at + 13] = p["generation_mask"][K - 1] = True
+    stack = lambda k: np.stack([p[k] for p in patches])
+    gen, chain, ridx = stack("generation_mask"), stack("chain_idx"), stack("residue_idx")
+    kinds = [("native", "pushed")[(g + r) % 2] for g in range(G) for r in range(N)]
+    rows = [design_of(rng, patches[g], chain[g] == 3, kinds[g * N + r]) for g in range(G) for r in range(N)]
+    des = {"seq_idx": np.stack([r[0] for r in rows]), "translations": np.stack([r[1] for r in rows]), "orientations": np.stack([r[2] for r in rows])}
+    cuda = lambda v: torch.from_numpy(np.ascontiguousarray(v)).cuda()
+    c = dict(G=G, N=N, K=K, gen=gen, chain=chain, ridx=ridx, rm=rm, kinds=kinds, designs={k: cuda(v) for k, v in des.items()})
+    c["kw"] = dict(chain_idx=cuda(chain), residue_idx=cuda(ridx), residue_mask=cuda(rm), group_size=N)
+    c["gen_d"] = cuda(gen)
+    return c
+
+
 def design_points(designs, atoms):
     """The fp32 atoms the contacts kernel reads, and their validity bits, as numpy."""
     pts = dio.backbone_from_frames(designs["translations"], designs["orientations"], atoms).float().cpu().numpy()
@@ -171,16 +199,20 @@ def check_backbone(c, out, ref, angles, what):
         assert worst <= 5e-7
 
 
-@pytest.mark.parametrize("N, K", [(N, K) for K in (40, 130) for N in (1, 5, 70)] + [(3, 70), (3, 300)])
+@pytest.mark.parametrize("N, K", [(N, K) for K in (40, 130) for N in (1, 5, 70)] + [(3, 70), (3, 300), TANGLED])
 def test_backbone_equals_the_oracle(N, K):
     """The native, the pushed and the pulled loop: dihedrals, bond lengths and counts.  K = 70 and K = 300: the chain neighbours of a patch
-    past 64 slots that is no multiple of 64, and of one past the 256 threads of the links kernel."""
-    c = case(N, K, kinds=("native", "pushed", "pulled"))
+    past 64 slots that is no multiple of 64, and of one past the 256 threads of the links kernel.  TANGLED: keys on which a 32-bit gap,
+    the highest slot, a masked slot or another chain would give other neighbours."""
+    c = tangled_case(N, K) if (N, K) == TANGLED else case(N, K, kinds=("native", "pushed", "pulled"))
     out = numpy_of(metrics.backbone(c["designs"], c["gen_d"], **c["kw"]))
     pts = design_points(c["designs"], ("N", "CA", "C"))[0]
     ref = backbone_ref(pts, c["gen"], c["chain"], c["ridx"], c["rm"], N)
     assert ref["tolerance_gap"] > 1e-4 and ref["cis_gap"] > 1e-4  # the threshold counts are well defined
     check_backbone(c, out, ref, True, f"backbone N={N} K={K}")
+    if (N, K) == TANGLED:
+        assert (ref["n_bonds"] >= 6).all(), ref["n_bonds"]  # the tangled slots are generated: their links are counted bonds
+        return  # (what follows is about the three patches of case())
     rows = np.arange(3 * N)
     assert (out["n_bonds"][rows // N == 1] == 0).all() and (out["max_peptide_deviation"][rows // N == 1] == 0).all()  # no generated residue
     assert (out["n_bonds"][rows // N == 0] == 2).all()  # one generated residue inside a chain

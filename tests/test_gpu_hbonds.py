@@ -19,6 +19,7 @@ import torch
 
 from diffab_pytorch import _hip, io as dio, metrics
 from sampler_support import hip  # noqa: F401
+from test_geometry_host import tangle_chain_keys
 from test_hbonds_host import OUTPUTS, RESIDUE_OUTPUTS, backbone, f32, f64, hbonds_ref, helix, links, place, rotation, strands
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("hip")]
@@ -162,7 +163,7 @@ def ideal_oxygen(pts, nxt):
 
 
 @functools.lru_cache(maxsize=None)
-def case(kind, K, G, N, A, seed=0, context=True, antigen=True, hotspot=True, ragged=False):
+def case(kind, K, G, N, A, seed=0, context=True, antigen=True, hotspot=True, ragged=False, tangled=False):
     """G patches of K residues x N designs, as numpy inputs of the C ABI, with the oracle's outputs under 'ref'.
 
     kind 'helix': the 12-residue ideal helix first, 'strands': the 14 residues of the two-strand ladder first (two chains), then
@@ -170,12 +171,14 @@ def case(kind, K, G, N, A, seed=0, context=True, antigen=True, hotspot=True, rag
     middle of the first chain (so both of its ends meet context residues) and, for 'strands', one whole strand end.  Design 0 of every
     patch is the native; the others add N(0, 0.25 A) to the atoms of the generated residues.  Context residues have their real O in two
     slots out of three, and about one residue in twelve outside the two hand cases is Pro.  ragged: a numbering gap, a residue outside residue_mask, a context residue without its CA, another with only
-    its O missing, duplicate numbers in a chain."""
+    its O missing, duplicate numbers in a chain.  tangled: the keys of test_geometry_host.tangle_chain_keys in the first chain of 14 or more
+    residues behind the first and in the last slot - a 32-bit gap, the highest slot, a masked slot or another chain would link others."""
     rng = np.random.default_rng(1000 * K + 100 * G + 10 * N + seed)
     rows = G * N
     pts = np.zeros((G, K, 3, 3))
     chain, ridx = np.zeros((G, K), np.int32), np.zeros((G, K), np.int32)
     gen = np.zeros((G, K), bool)
+    inside = np.ones((G, K), bool)
     for g in range(G):
         pieces = []
         if kind == "helix":
@@ -198,6 +201,9 @@ def case(kind, K, G, N, A, seed=0, context=True, antigen=True, hotspot=True, rag
             n = len(piece)
             pts[g, at:at + n], chain[g, at:at + n], ridx[g, at:at + n] = piece, c, np.arange(n) + 5 * c
             at += n
+        if tangled:
+            c = next(c for c in range(1, len(pieces) - 1) if len(pieces[c]) >= 14)
+            tangle_chain_keys(chain[g], ridx[g], inside[g], sum(len(p) for p in pieces[:c]) + g, K - 1)
         n0 = len(pieces[0])
         lo, hi = (2, 2 + max(1, n0 // 3)) if kind == "strands" else (n0 // 3, n0 // 3 + max(2, n0 // 3) - (kind == "helix"))
         gen[g, lo:hi] = True  # (the helix: 4, 5, 6, so that C=O of 3 - its O built from the design's N of 4 - meets N-H of the context's 7)
@@ -208,9 +214,9 @@ def case(kind, K, G, N, A, seed=0, context=True, antigen=True, hotspot=True, rag
             gen[g, start + 3:start + 3 + min(6, len(pieces[2]) - 4)] = True
         if g == 2:
             gen[g] = False  # a patch with nothing generated
-    rm = None
+    rm = inside if tangled else None
     if ragged:
-        rm = np.ones((G, K), bool)
+        rm = inside
         for g in range(G):
             last = K - 1
             ridx[g, last - 6:] += 3  # a numbering gap inside the last chain
@@ -273,6 +279,7 @@ CASES = {  # kind, K, G, N, A, then keywords
     "K512": ("strands", 512, 1, 1, 4),
     "K40 no hotspots": ("strands", 40, 2, 5, 32, dict(hotspot=False)),
     "K64": ("helix", 64, 3, 5, 15, dict(ragged=True)),
+    "K257 tangled keys": ("helix", 257, 2, 2, 4, dict(tangled=True)),
 }
 
 

@@ -14,7 +14,7 @@ import torch
 
 from diffab_pytorch import metrics, refine, synthetic as syn
 from sampler_support import hip, make_model, sample
-from test_geometry_host import backbone_ref
+from test_geometry_host import backbone_ref, tangle_chain_keys
 from test_gpu_geometry import build_patch, same_bits
 from test_refine_host import noisy, place, refine_ref
 
@@ -22,9 +22,13 @@ pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("hip")]
 
 EPS = float(np.finfo(np.float32).eps)
 KINDS = ("native", "noisy03", "noisy1", "pushed")
-SHAPES = [(3, 5, 70), (2, 3, 33), (1, 1, 1), (1, 2, 256)]  # (G, N, K)
-ROLES = {(3, 5, 70): ("one", "none", "loop"), (2, 3, 33): ("loop+ends", "one"), (1, 1, 1): ("single",), (1, 2, 256): ("loop+ends",)}
-FIRST_KIND = {(3, 5, 70): 0, (2, 3, 33): 0, (1, 1, 1): 1, (1, 2, 256): 1}
+SHAPES = [(3, 5, 70), (2, 3, 33), (1, 1, 1), (1, 2, 256), (2, 2, 256)]  # (G, N, K)
+ROLES = {(3, 5, 70): ("one", "none", "loop"), (2, 3, 33): ("loop+ends", "one"), (1, 1, 1): ("single",), (1, 2, 256): ("loop+ends",),
+         (2, 2, 256): ("loop", "loop")}
+FIRST_KIND = {(3, 5, 70): 0, (2, 3, 33): 0, (1, 1, 1): 1, (1, 2, 256): 1, (2, 2, 256): 1}
+# per patch, the first of 13 slots behind the loop that take the keys of test_geometry_host.tangle_chain_keys (and slot K - 1 with them):
+# keys on which a 32-bit gap, the highest slot, a masked slot or another chain would link other residues.  These slots move.
+TANGLED = {(2, 2, 256): (60, 75)}
 OUTPUTS = ("translations", "orientations", "energy_before", "energy_after", "terms", "max_shift")
 
 
@@ -58,9 +62,12 @@ def case(shape):
     G, N, K = shape
     rng = np.random.default_rng(7000 + 10 * K + N)
     patches = [make_patch(rng, K, role) for role in ROLES[shape]]
+    rm = np.ones((G, K), bool)
+    for g, at in enumerate(TANGLED.get(shape, ())):
+        tangle_chain_keys(patches[g]["chain_idx"], patches[g]["residue_idx"], rm[g], at, K - 1)
+        patches[g]["generation_mask"][at:at + 13] = patches[g]["generation_mask"][K - 1] = True
     stack = lambda k: np.stack([p[k] for p in patches])
     gen, chain, ridx = stack("generation_mask"), stack("chain_idx"), stack("residue_idx")
-    rm = np.ones((G, K), bool)
     if K > 1:  # the patch with the loop loses a generated and two context residues
         g = int(gen.sum(1).argmax())
         loop, ctx = np.flatnonzero(gen[g]), np.flatnonzero(~gen[g])
