@@ -254,13 +254,25 @@ __device__ __forceinline__ void rotvec_head_bwd(const float (&G0)[9], const floa
       for (int r = 0; r < 3; ++r) s += Ot[r * 3 + a] * G0[r * 3 + b];
       G[a * 3 + b] = s;
     }
-  // S = hat(v), n = |v|, a = sin n / n, b = (1 - cos n) / n^2
+  // S = hat(v), n = |v|, a = sin n / n, b = (1 - cos n) / n^2;  ca = a'(n) / n = (cos n - a) / n^2, cb = b'(n) / n = (a - 2 b) / n^2.
+  // All four by their series below n^2 = kSo3Series, where the quotients cancel and are 0/0 at v = 0 (ca -> -1/3, cb -> -1/12)
   const float vx = v3[0], vy = v3[1], vz = v3[2];
-  const float n = sqrtf(vx * vx + vy * vy + vz * vz);
-  float sn, cn;
-  sincosf(n, &sn, &cn);
-  const float a = sn / n, b = (1.0f - cn) / (n * n);
-  const float da = (cn - a) / n, db = (a - 2.0f * b) / n;  // derivatives with respect to n
+  const float n2 = vx * vx + vy * vy + vz * vz;
+  float a, b, ca, cb;
+  if (n2 < kSo3Series) {
+    so3_exp_series(n2, a, b);
+    ca = n2 * (1.0f / 30.0f) - 1.0f / 3.0f;
+    cb = n2 * (1.0f / 180.0f) - 1.0f / 12.0f;
+  } else {
+    const float n = sqrtf(n2);
+    float sn, cn;
+    sincosf(n, &sn, &cn);
+    const float sh = sinf(0.5f * n);
+    a = sn / n;
+    b = 2.0f * sh * sh / n2;  // (1 - cos n) / n^2 without the cancellation: cb divides its error by n^2 once more
+    ca = (cn - a) / n2;
+    cb = (a - 2.0f * b) / n2;
+  }
   float S[9], S2[9];
   so3_hat(vx, vy, vz, S);
   mat3_mul(S, S, S2);
@@ -281,7 +293,7 @@ __device__ __forceinline__ void rotvec_head_bwd(const float (&G0)[9], const floa
   // <H, hat(e_x)> = H21 - H12, <H, hat(e_y)> = H02 - H20, <H, hat(e_z)> = H10 - H01
   const float hk[3] = {H[7] - H[5], H[2] - H[6], H[3] - H[1]};
 #pragma unroll
-  for (int k = 0; k < 3; ++k) dv3[k] = hk[k] + (da * gS + db * gS2) * vv[k] / n;
+  for (int k = 0; k < 3; ++k) dv3[k] = hk[k] + (ca * gS + cb * gS2) * vv[k];
 }
 
 __global__ void losses_bwd_kernel(const float* __restrict__ post, const float* __restrict__ tpost, const float* __restrict__ eps,

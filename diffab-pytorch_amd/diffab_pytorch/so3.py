@@ -65,12 +65,12 @@ def _mat_op(fn_name: str, M: torch.Tensor, out_last: tuple) -> torch.Tensor:
 
 
 def log_rotmat(R: torch.Tensor) -> torch.Tensor:
-    """theta/(2 sin theta) (R - R^T); NaN at theta = 0, like the reference (so3.py:146-162)."""
+    """theta/(2 sin theta) (R - R^T) (so3.py:146-162), defined at every angle: 0 at theta = 0, where the reference gives NaN."""
     return _mat_op("diffab_so3_log", R, (3, 3))
 
 
 def exp_skew_symmetric_mat(S: torch.Tensor) -> torch.Tensor:
-    """Rodrigues; NaN at |v| = 0, like the reference (so3.py:219-237)."""
+    """Rodrigues (so3.py:219-237); the identity at |v| = 0, where the reference gives NaN."""
     return _mat_op("diffab_so3_exp", S, (3, 3))
 
 

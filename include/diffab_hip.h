@@ -316,9 +316,10 @@ int diffab_debug_gemm_tn(const float* A, const float* B, float* C, float* db, in
 int diffab_debug_dense_forms(int64_t rows, int32_t nblocks, int32_t has_parts, int32_t* out5);
 int diffab_kernel_timer_read(int64_t* launches, double* total_ms);
 /* ---- SO(3) maps, n matrices/vectors each --------------------------------- */
-/* so3.py:146-162  log R = theta/(2 sin theta) (R - R^T); NaN at theta = 0 like the reference */
+/* so3.py:146-162  log R = theta/(2 sin theta) (R - R^T), theta in [0, pi], defined at every angle (unlike the reference: DESIGN.md,
+ * "SO(3) maps at theta near 0 and pi"): log I = 0; at theta = pi exactly the axis whose largest component is positive */
 int diffab_so3_log(const float* R, float* S, int64_t n, void* stream);
-/* so3.py:219-237  exp of a skew-symmetric matrix (Rodrigues); NaN at |v| = 0 like the reference */
+/* so3.py:219-237  exp of a skew-symmetric matrix (Rodrigues); exp(0) = I (NaN in the reference) */
 int diffab_so3_exp(const float* S, float* R, int64_t n, void* stream);
 /* so3.py:173-182 */
 int diffab_so3_matrix_to_rotvec(const float* R, float* v, int64_t n, void* stream);

@@ -341,3 +341,38 @@ def test_backward_lds_limit_is_refused_before_launch(hip):
     assert rc.grad is None and pc.grad is None
     assert all(p.grad is None for p in model.parameters())
     run_losses("odd")
+
+
+# ------------------------------------------------------------------ 7. the rotation head's gradient at small |v|
+@pytest.mark.parametrize("mag", [0.0, 1e-6, 1e-4, 3e-4, 1e-3, 1e-2, 0.1], ids=lambda m: f"v{m:g}")
+def test_rotation_head_gradient_at_small_rotvec(hip, mag):
+    """O0 = O_t exp(hat(v)) differentiated where sin n / n, (1 - cos n) / n^2 and their derivatives are 0/0 or cancel (rotvec_head_bwd,
+    csrc/noslp_kernels.hip).  `odd_k5`, the smallest geometry; the rotation head's last layer has zero weight and the bias v, so every
+    row's rotvec is exactly v, |v| = mag; seeded cotangents on O0 alone.  Then d bias = sum over the rows of so3_ref.exp_head_vjp (float64,
+    the series limits at small |v|) and d O_t = G0 exp(hat(v))^T: both finite at |v| = 0 and within GTOL at every |v|, 0 included."""
+    import so3_ref as ref
+
+    gid = "odd_k5"
+    B, K, d, seed = geom(gid)
+    sd = syn.denoiser_state_dict(d, seed=seed, prefix="")
+    v = (mag * np.array([0.6, -0.48, 0.64])).astype(np.float32)
+    sd["orientation_denoising.4.weight"] = torch.zeros_like(sd["orientation_denoising.4.weight"])
+    sd["orientation_denoising.4.bias"] = torch.from_numpy(v.copy())
+    den = denoiser(d, sd).train()
+    inp = inputs(gid, seed=800 + seed)
+    G0 = torch.randn(B, K, 3, 3, generator=torch.Generator().manual_seed(seed))
+    lv = {k: inp[k].cuda().requires_grad_(True) for k in ARGS[1:]}
+    out = den(inp["seq_idx"].cuda(), lv["translations"], lv["orientations"], lv["res_context_emb"], lv["pair_context_emb"], betas(B).cuda(),
+              None, None)
+    (out["orientations_t0"] * G0.cuda()).sum().backward()
+    O_t = inp["orientations"].double().numpy().reshape(-1, 3, 3)
+    G = G0.double().numpy().reshape(-1, 3, 3)
+    vs = np.broadcast_to(v.astype(np.float64), (B * K, 3))
+    want_v = ref.exp_head_vjp(vs, O_t, G).sum(0)
+    want_O = G @ ref.T(ref.exp(vs))
+    got_v, got_O = den.orientation_denoising[4].bias.grad.cpu(), lv["orientations"].grad.cpu().reshape(-1, 3, 3)
+    r_O0 = maxrel(out["orientations_t0"].detach().reshape(-1, 3, 3), O_t @ ref.exp(vs))
+    r_v, r_O = maxrel(got_v, want_v), maxrel(got_O, want_O)
+    print(f"rotation head at |v| = {mag:g}: O0 {r_O0:.1e}, d bias {r_v:.1e}, d O_t {r_O:.1e}")
+    assert torch.isfinite(got_v).all() and torch.isfinite(got_O).all() and torch.isfinite(out["orientations_t0"]).all(), mag
+    assert r_O0 < TOL and r_v < GTOL and r_O < GTOL, (mag, r_O0, r_v, r_O)
